@@ -4,6 +4,7 @@ Benchmark of the hot path: element*quadrature-point updates per seco
 strain -> Drucker-Prager return map -> tangent-stiffness (CSR values) -> internal force.
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--elem P1|P2|Q1|Q2] [--cells C] [--state S]
+                    [--dump-outputs DIR] [--full]
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...` as a
@@ -25,9 +26,16 @@ on the points) is BASELINE configs[4]; its documented 8-GPU command is
     python bench.py --gpus 8 --elem P2 --cells 1414 --state random --scaling strong
 (one square split over the ranks by contiguous element ranges; the element types other than P1 run the element route).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HIP-event timed on the launch
-stream, algorithmic bytes 537 B/update for P1: SURVEY 8d) and `cpu_baseline` (the NumPy oracle timed on this
-host, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the headline (`value`, `ms_per_step` = wall time of the K steps / K, `config`).  `--full` goes on to measure and
+check the rest in the same process and adds it to the line: `roofline` (HIP-event timed on the launch stream, algorithmic
+bytes 537 B/update for P1: SURVEY 8d; per-kernel split from a second pass), `kf_only` and `return_map_only` (passes of
+their own), `cpu_baseline` (the NumPy oracle timed on this host, N=1 only) with `parity_vs_oracle`, and at N > 1
+`per_rank`, `exchange` (both exchange forms timed) and the `strong` companion.
+
+`--dump-outputs DIR` writes what the last timed step computed (s, ds, ind_p, K values, F, counts of rank 0's shard;
+float64, fixed samples of the large arrays, at most 46 MB) as DIR/<name>.npy: the inputs are a function of the
+arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -127,6 +135,36 @@ def parity_vs_oracle(oracle_out, shard, torch):
     return errs
 
 
+DUMP_POINTS = 1 << 18               # integration points sampled for s / ds / ind_p
+DUMP_ENTRIES = 1 << 20              # entries sampled of K's CSR values and of F (with the points: 46 MB in all)
+
+
+def sample_positions(n, m, seed):
+    """Sorted positions of a sample of m of n entries (all of them when n <= m); a function of (n, m, seed) alone."""
+    if n <= m:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+
+
+def dump_outputs(out_dir, shard, f_buf, torch):
+    """What the caller of the timed step receives, from its last step, as out_dir/<name>.npy in float64: s (4 x m), ds
+    (9 x m), ind_p (m, 0 / 1) at the same m sampled integration points, K (CSR values in the order of ctx.pattern()) and F
+    (force per DOF) at sampled entries, counts ([smooth, apex] of the step).  The samples depend on the sizes alone, so two
+    runs with the same arguments write the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    dev = shard.S.device
+
+    def take(t, n, m, seed):
+        idx = torch.from_numpy(sample_positions(n, m, seed)).to(dev)
+        return t.index_select(t.dim() - 1, idx).to(torch.float64).cpu().numpy()
+    pts = dict(n=shard.n_int, m=DUMP_POINTS, seed=1)
+    out = {'s': take(shard.S, **pts), 'ds': take(shard.DS, **pts), 'ind_p': take(shard.indp, **pts),
+           'K': take(shard.Kd, shard.ctx.nnz, DUMP_ENTRIES, 2), 'F': take(shard.Fb[f_buf], shard.ctx.n_dof, DUMP_ENTRIES, 3),
+           'counts': shard.counts.to(torch.float64).cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -144,7 +182,14 @@ def parse_args():
     ap.add_argument('--preheat-ms', type=float, default=250.0,
                     help='untimed passes of the same step for this long before the W warm-up steps of every timed run (the '
                          'clocks ramp with load: a 2 ms timed region straight after set-up measures 4-5 %% slower); 0 = off')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure and check everything else: per-kernel times and the roofline, the '
+                         'K/F-only and return-map-only passes, the CPU baseline with the parity check against the oracle, '
+                         'and at N > 1 both exchange forms and the strong-scaling companion (off: the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, a fixed sample of the large "
+                         "arrays, rank 0's shard): s, ds, ind_p, K, F, counts")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline and no parity check')
     ap.add_argument('--cpu-cells', type=int, default=None,
                     help='cells per side of the CPU-baseline square (default: --cells for P1, min(--cells, 354) otherwise: a bounded sample)')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)')
@@ -152,7 +197,10 @@ def parse_args():
                     help='form of the interface exchange the HEADLINE uses at N > 1 (both are timed in the same run: `exchange`)')
     ap.add_argument('--min-elements-per-rank', type=int, default=100000,
                     help='the north_star gate: only as many ranks take elements as leaves each at least this many (0 = off)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def launch_ranks(n):
@@ -351,10 +399,55 @@ def run(args):
     n_el_total = int(mesh['elements'].shape[1])
     n_total = n_el_total * NQ[et]                      # integration points = element*quadpt updates per step, all ranks
     dt, step, stream_ms = timed(shard, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0 and not shard.idle:
+        # the force buffer of the last timed step (double-buffered at N > 1: warm-up and timed steps alternate them)
+        dump_outputs(args.dump_outputs, shard, (args.warmup + args.steps - 1) & 1 if world > 1 else 0, torch)
     cnt = shard.counts.clone()
     if world > 1:
         dist.all_reduce(cnt)
     n_smooth, n_apex = [int(v) for v in cnt.cpu()]
+    n_int = shard.n_int
+    ctx = shard.ctx
+    # what the library runs (FEP_ROUTE: unset = the product's default route; coo / patch = the element route's cross-check forms)
+    env_route = os.environ.get('FEP_ROUTE', '')
+    route = ('node' if not env_route else 'coo' if env_route == 'coo' else 'element') if et == 'P1' else 'element'
+
+    def headline():
+        """The result line without the figures of --full."""
+        label = ' (BASELINE configs[3])' if (et, N) == ('P1', N_CELLS) else ' (BASELINE configs[4])' if (et, N) == ('P2', 1414) else ''
+        pts = '' if et == 'P1' else f' x {NQ[et]} points'
+        if strong:
+            wl = (f'Plasticity2D_DP strip-footing square, {N}x{N} cells = {n_el_total} {et} elements{pts}{label} split over '
+                  f'{world} GPU(s)')
+        else:
+            wl = (f'Plasticity2D_DP strip-footing square, {N}x{N} cells = {n_int // NQ[et]} {et} elements{pts} per GPU{label}')
+        line = {
+            'metric': 'element*quadpt updates/sec (return-map + K_tan assemble)',
+            'value': n_total * args.steps / dt, 'unit': 'updates/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'preheat_ms': args.preheat_ms,
+            'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling,
+            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': wl + ', Drucker-Prager, strain->return map->K_tan CSR values->F per step',
+                       'element_type': et, 'points_per_gpu': n_int, 'points_total': n_total, 'elements_total': n_el_total,
+                       'nnz_per_gpu': ctx.nnz,
+                       'smooth_points': n_smooth, 'apex_points': n_apex, 'field_scale': args.field_scale, 'state': args.state,
+                       'route': route,
+                       'elements_per_gpu': n_int // NQ[et],
+                       'parallelism': (f'element-shard x{world} ({shard.sh.active_world} active), interface-force exchange: '
+                                       f'{args.exchange}') if world > 1 else 'single GPU'},
+        }
+        if world > 1:
+            line['active_ranks'] = shard.sh.active_world               # < n_gpus: the min-elements-per-rank gate left ranks idle
+        return line
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     if shard.idle:
         kms, n_prof = {'element': 0.0, 'csr': 0.0, 'force': 0.0}, 0
         barrier()
@@ -362,8 +455,6 @@ def run(args):
         kms, n_prof = per_kernel(shard, step, args.steps)
     ranks_ms = gather_ranks([kms['element'], kms['csr'], kms['force']])
     x_rep = exchange_report(shard, dt)
-    n_int = shard.n_int
-    ctx = shard.ctx
 
     # K/F-only pass (what a Newton iterate asks for: no s / ds / ind_p leave the kernels), N = 1
     kf = None
@@ -442,9 +533,6 @@ def run(args):
         dist.barrier()
         dist.destroy_process_group()
         return
-    # what the library runs (FEP_ROUTE: unset = the product's default route; coo / patch = the element route's cross-check forms)
-    env_route = os.environ.get('FEP_ROUTE', '')
-    route = ('node' if not env_route else 'coo' if env_route == 'coo' else 'element') if et == 'P1' else 'element'
     patch_form = env_route != 'coo'
     k_names = ctx.kernel_names(0)                   # as rocprofv3 prints them (fep_ctx_kernel_names)
     if et != 'P1' or route != 'node':
@@ -506,7 +594,7 @@ def run(args):
                         and args.field_scale == 1.0 and args.state == tj.get('state', 'bands')):
                     traffic = tj.get('hbm_bytes_per_launch')
                     traffic_source = ('profiles/traffic_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of '
-                                      '`python bench.py`, 2*FETCH + WRITE per the gfx950 correction; not measured in this run)')
+                                      '`python bench.py --full`, 2*FETCH + WRITE per the gfx950 correction; not measured in this run)')
                     kf_names = ctx.kernel_names(1).split(' + ')
                     if kf and sorted(tj.get('kf_only_kernel', {})) == sorted(kf_names):
                         kf['traffic'] = sum(tj['kf_only_kernel'].values())
@@ -515,38 +603,16 @@ def run(args):
                           file=sys.stderr)
             except Exception:
                 traffic = None
-        label = ' (BASELINE configs[3])' if (et, N) == ('P1', N_CELLS) else ' (BASELINE configs[4])' if (et, N) == ('P2', 1414) else ''
-        pts = '' if et == 'P1' else f' x {NQ[et]} points'
-        if strong:
-            wl = (f'Plasticity2D_DP strip-footing square, {N}x{N} cells = {n_el_total} {et} elements{pts}{label} split over '
-                  f'{world} GPU(s)')
-        else:
-            wl = (f'Plasticity2D_DP strip-footing square, {N}x{N} cells = {n_int // NQ[et]} {et} elements{pts} per GPU{label}')
-        line = {
-            'metric': 'element*quadpt updates/sec (return-map + K_tan assemble)',
-            'value': n_total * args.steps / dt, 'unit': 'updates/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'preheat_ms': args.preheat_ms,
-            'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling,
-            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': wl + ', Drucker-Prager, strain->return map->K_tan CSR values->F per step',
-                       'element_type': et, 'points_per_gpu': n_int, 'points_total': n_total, 'elements_total': n_el_total,
-                       'nnz_per_gpu': ctx.nnz,
-                       'smooth_points': n_smooth, 'apex_points': n_apex, 'field_scale': args.field_scale, 'state': args.state,
-                       'route': route,
-                       'elements_per_gpu': n_int // NQ[et],
-                       'parallelism': (f'element-shard x{world} ({shard.sh.active_world} active), interface-force exchange: '
-                                       f'{args.exchange}') if world > 1 else 'single GPU'},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_source,
-                         'kernel': k_name, 'kernel_ms': k_ms,
-                         'algorithmic_bytes_per_launch': alg, 'timing': timing, 'kernel_ms_event_pairs': k_ms_split,
-                         'kernels_ms': others, 'per_kernel': per_k},
-        }
+        line = headline()
+        line['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                            'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_source,
+                            'kernel': k_name, 'kernel_ms': k_ms,
+                            'algorithmic_bytes_per_launch': alg, 'timing': timing, 'kernel_ms_event_pairs': k_ms_split,
+                            'kernels_ms': others, 'per_kernel': per_k}
         if world > 1:
             line['per_rank'] = [{'point_ms': r[0], 'assembly_ms': r[1]} for r in ranks_ms]      # first / second kernel of the step
             line['exchange'] = x_rep
             line['exchange_ms'] = x_rep['alone_ms']                   # {'allreduce': ms, 'p2p': ms}; the headline used x_rep['headline']
-            line['active_ranks'] = shard.sh.active_world               # < n_gpus: the min-elements-per-rank gate left ranks idle
             if strong_line:
                 line['strong'] = strong_line
         if kf:
@@ -566,16 +632,16 @@ def run(args):
                 if errs['ind_p_mismatches'] or line['parity_max_rel'] > 1e-11:      # reported, never fatal: the line is the product
                     print(f'[bench] parity against the oracle outside the stated tolerance: {errs}', file=sys.stderr)
         print(json.dumps(line), flush=True)
-        try:        # the box's clocks next to the line (stderr): runs of the same binary differ by ~10 % between boxes of the pool
-            # (a profiler's preloaded library must not ride into the child: with --pmc it starts the GPU runtime in every process it
-            # is loaded into, and rocm-smi — an `env python3` script — would then replace a GPU-initialised process, which the box refuses)
-            env_smi = {k: v for k, v in os.environ.items() if k != 'LD_PRELOAD' and not k.startswith(('ROCP', 'ROCPROF'))}
-            smi = subprocess.run(['rocm-smi', '--showclocks', '--showpower'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                                 text=True, timeout=20, env=env_smi).stdout
-            keep = [l.strip() for l in smi.splitlines() if 'GPU[0]' in l and any(k in l for k in ('sclk', 'mclk', 'fclk', 'Power'))]
-            print('[bench] ' + ' | '.join(keep), file=sys.stderr)
-        except Exception as exc:                                        # rocm-smi missing or refused: the line stands
-            print(f'[bench] rocm-smi not available: {exc}', file=sys.stderr)
+        # the GPU's clocks next to the line (stderr): runs of the same binary differ by ~10 % between machines.  Not under a
+        # profiler (ROCPROF* settings present): its tool library would ride into the child and start the GPU runtime there
+        if not any(k.startswith('ROCPROF') for k in os.environ):
+            try:
+                smi = subprocess.run(['rocm-smi', '--showclocks', '--showpower'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                                     text=True, timeout=20).stdout
+                keep = [l.strip() for l in smi.splitlines() if 'GPU[0]' in l and any(k in l for k in ('sclk', 'mclk', 'fclk', 'Power'))]
+                print('[bench] ' + ' | '.join(keep), file=sys.stderr)
+            except Exception as exc:                                    # rocm-smi missing or refused: the line stands
+                print(f'[bench] rocm-smi not available: {exc}', file=sys.stderr)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -96,7 +96,7 @@ def main():
         json.dump({'round': tag, 'kernels': {k: hb[k] for k in dom}, 'hbm_bytes_per_launch': sum(hb[k] for k in dom),
                    'kf_only_kernel': {k: hb[k] for k in hb if k.startswith('p1_fused_kernel')},
                    'note': 'full-output step = p1_point_kernel + p1_node_lds_kernel; 2*FETCH_SIZE + WRITE_SIZE (KiB) * 1024, '
-                           'separate rocprofv3 --pmc passes of `python3 bench.py --steps 10 --no-cpu-baseline` (tools/prof.sh)',
+                           'separate rocprofv3 --pmc passes of `python3 bench.py --full --steps 10 --no-cpu-baseline` (tools/prof.sh)',
                    'elements_per_gpu': 1002528, 'element_type': 'P1', 'state': 'bands'},
                   open(os.path.join(out, 'traffic_latest.json'), 'w'), indent=1)
 
