@@ -27,17 +27,16 @@ using namespace fep;
 thread_local int fep_g_last_hip = 0;
 #define g_last_hip fep_g_last_hip
 
-// The switches of the PRODUCT library (read once): everything else goes through fep_tune() and exists in -DFEP_ABLATION
-// builds only (fep_common.h).
+// The switches of the PRODUCT library, read at every context creation (a process may create contexts on different routes
+// one after the other; the parity tests do): everything else goes through fep_tune() and exists in -DFEP_ABLATION builds
+// only (fep_common.h).
 //   FEP_ROUTE=coo | patch   the element route in its COO form (every K_e block through HBM, csr_reduce_kernel) / its patch
 //                           form for EVERY element type, P1 included: the independent cross-checks of the parity tests
 //                           (unset: P1 takes its node route, the other types the patch form)
 //   FEP_VALIDATE_PLAN=1     replay the gather plan against the symbolic phase at context creation (tests)
-//   FEP_VERBOSE=1           plan statistics on stderr
-static const char* env_once(const char* name) { const char* v = std::getenv(name); return (v && *v) ? v : nullptr; }
-static bool route_is(const char* v) { static const char* r = env_once("FEP_ROUTE"); return r && std::strcmp(r, v) == 0; }
-static bool validate_plans() { static const bool on = env_once("FEP_VALIDATE_PLAN") != nullptr; return on; }
-static bool verbose_on() { static const bool on = env_once("FEP_VERBOSE") != nullptr; return on; }
+//   FEP_VERBOSE=1           plan statistics on stderr (kept with the context for its steps)
+static const char* env_now(const char* name) { const char* v = std::getenv(name); return (v && *v) ? v : nullptr; }
+static bool env_is(const char* name, const char* v) { const char* r = env_now(name); return r && std::strcmp(r, v) == 0; }
 
 struct fep_ctx {
     int device = 0;
@@ -115,6 +114,7 @@ struct fep_ctx {
     // in-situ profiling: 4 events per step (before element, after element, after csr, after force)
     bool profiling = false;
     std::vector<hipEvent_t> events;
+    bool verbose = false;                               // FEP_VERBOSE at creation
 };
 
 __attribute__((visibility("hidden"))) int fep_set_device(int dev) {
@@ -480,6 +480,9 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     c = new (std::nothrow) fep_ctx();
     if (!c) return FEP_ENOMEM;
     c->device = device_id; c->elem_type = elem_type; c->n_p = n_p; c->n_q = n_q;
+    const bool route_coo = env_is("FEP_ROUTE", "coo"), route_patch = env_is("FEP_ROUTE", "patch");
+    const bool validate_plans = env_now("FEP_VALIDATE_PLAN") != nullptr;
+    c->verbose = env_now("FEP_VERBOSE") != nullptr;
     c->n_e = n_e; c->n_n = n_n; c->n_int = n_e * n_q; c->n_dof = 2 * n_n;
     c->n_blk = (int64_t)S.ncol.size(); c->nnz = 4 * c->n_blk; c->n_contrib = (int64_t)S.perm.size();
     for (int64_t n = 0; n < n_n && !c->has_orphans; ++n) c->has_orphans = S.iptr[n + 1] == S.iptr[n];
@@ -514,7 +517,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     std::vector<int32_t> tstart_all;
     CK(fep_host::row_tiles(S, n_n, kBlock, tstart_all));
     // P1 runs the node-centric fast path unless FEP_ROUTE asks for the element route (coo | patch)
-    c->p1_node = elem_type == FEP_P1 && !route_is("coo") && !route_is("patch");
+    c->p1_node = elem_type == FEP_P1 && !route_coo && !route_patch;
     if (c->p1_node) {
         // gather plan of the node route (host, fep_host.h): tiles, staged element / node lists, codes, descriptors
         fep_host::P1Options opt;
@@ -537,7 +540,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
 #endif
         fep_host::P1Plan P;
         CK(fep_host::build_p1_plan(S, n_e, n_n, elements_h, opt, P));
-        if (r == FEP_OK && validate_plans()) {
+        if (r == FEP_OK && validate_plans) {
             const int bad = fep_host::validate_p1_plan(P, S, n_e, n_n, elements_h);
             if (bad) { std::fprintf(stderr, "[fep] P1 plan fails check %d\n", bad); r = FEP_EINVAL; }
         }
@@ -546,7 +549,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
         // takes the element route like every other element type: the product keeps ONE node route.
         if (r == FEP_OK && !(P.lds && P.pk)) {
             c->p1_node = false;
-            if (verbose_on()) std::fprintf(stderr, "[fep] P1 plan without the LDS-staged packed form (lds %d pk %d): element route\n", (int)P.lds, (int)P.pk);
+            if (c->verbose) std::fprintf(stderr, "[fep] P1 plan without the LDS-staged packed form (lds %d pk %d): element route\n", (int)P.lds, (int)P.pk);
         }
 #endif
         if (r == FEP_OK && c->p1_node) {
@@ -575,7 +578,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
                 CK(dmalloc(&c->slot_counts, 256 * 16));
                 if (r == FEP_OK && hipMemset(c->slot_counts, 0, 256 * 16 * sizeof(unsigned long long)) != hipSuccess) r = FEP_EHIP;
             }
-            if (verbose_on())
+            if (c->verbose)
                 std::fprintf(stderr, "[fep] P1 plan: %lld tiles of <= %d blocks in <= %d segment(s), staged elements %lld "
                              "(%.2f per element, <= %d per tile), staged nodes <= %d, codes <= %d; lds %d rng %d pk %d fused %d/%d\n",
                              (long long)P.n_wg, P.tile, P.n_segs, (long long)P.staged_total, (double)P.staged_total / (double)n_e,
@@ -611,7 +614,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     // element route: the patch form (no K_e round trip through HBM; default) or the COO form (FEP_ROUTE=coo).
     // Same session, 0.25-4 M elements (profiles/r03_ablation.md, r03_elem_bench.log): P2 -17 % (K,F-only -19 %, BASELINE
     // configs[4] -14 %), Q2 -14 %, Q1 -13 %, P4 -21 % against the COO form
-    const bool coo_form = route_is("coo");
+    const bool coo_form = route_coo;
     const bool want_patch = !c->p1_node && !c->gn && !coo_form;
     {   // interleaved (x, y) per node: the kernels recompute dphi / weight from the coordinates
         std::vector<double> xy(2 * (size_t)n_n);
@@ -700,7 +703,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
                 if (!fep_tune("FEP_PATCH_RUNS")) popt.runs = 2;
                 CK(fep_host::build_patch_plan(S, n_p, n_e, n_n, elements_h, coords_h, elem_eb, popt, P));
             }
-            if (r == FEP_OK && P.ok && validate_plans()) {
+            if (r == FEP_OK && P.ok && validate_plans) {
                 const int bad = fep_host::validate_patch_plan(P, S, n_p, n_e, n_n, elements_h);
                 if (bad) { std::fprintf(stderr, "[fep] patch plan fails check %d\n", bad); r = FEP_EINVAL; }
             }
@@ -727,7 +730,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
 #endif
                 CK(dmalloc(&c->Pc, 4 * P.n_part));
                 CK(dmalloc(&c->Pf, 2 * P.n_fpart));
-                if (verbose_on())
+                if (c->verbose)
                     std::fprintf(stderr, "[fep] patch plan: %lld patches of <= %d elements, %zu items (<= %d per patch), %lld open blocks of %lld, "
                                  "%lld partials (%.2f per element), %lld open nodes\n", (long long)P.n_patch, P.eb, P.items.size(), P.max_items,
                                  (long long)P.n_open, (long long)c->n_blk, (long long)P.n_part, (double)P.n_part / (double)n_e,
@@ -1063,7 +1066,7 @@ static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const do
                                         (size_t)c->tile * 3 * sizeof(double2));
             const int n_wg = c->n_wg_p1;
             const int chunk = (n_wg + 7) / 8;
-            if (verbose_on()) {
+            if (c->verbose) {
                 static bool once = false;
                 if (!once) {
                     once = true;

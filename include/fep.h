@@ -42,7 +42,8 @@ extern "C" {
 #define FEP_ENODEV       -2   /* no usable HIP device / hipSetDevice failed */
 #define FEP_ENOMEM       -3   /* host or device allocation failed */
 #define FEP_EHIP         -4   /* a HIP runtime call or kernel launch failed (see fep_last_hip_error) */
-#define FEP_ERANGE       -5   /* an index is out of range (element -> node id, 32-bit offset overflow) */
+#define FEP_ERANGE       -5   /* an index is out of range (element -> node id, 32-bit offset overflow, a node row of
+                                 * more than 256 blocks: fep_ctx_create) */
 #define FEP_ESTATE       -6   /* call order violated (e.g. materials not set) */
 
 /* LagrangeElementType values of the reference (DP:55-60, TSX:57-63) */
@@ -119,6 +120,11 @@ int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
  *              and shifts in place, EL:389 — shift before calling)
  *   coords     (2, n_n) C-order
  *   dhatp1/2   (n_p, n_q) C-order reference-element derivative tables, wf (n_q) weight factors
+ *
+ * At most 256 node-pair blocks per node row of K, i.e. at most 255 neighbours of any node (the nodes it shares an
+ * element with): a larger row fits no tile of the assembly and FEP_ERANGE is returned, whatever the route.  P1: a node
+ * in 256 triangles; P2: 86 triangles around a vertex; P4: 26.  The library's switches FEP_ROUTE, FEP_VALIDATE_PLAN and
+ * FEP_VERBOSE (fep_build_is_ablation) are read by every call and hold for the context it creates.
  */
 int fep_ctx_create(fep_ctx** ctx_out, int device_id, int elem_type,
                    int64_t n_e, int64_t n_n,

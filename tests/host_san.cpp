@@ -3,7 +3,9 @@
 //   host_san MESHFILE [max_segs]
 // MESHFILE: int32 n_p, n_e, n_n, then elements (n_p x n_e, C order), optionally 2 x n_n doubles of coordinates.  Runs the symbolic phase (threaded), the COO
 // tiles, the P1 plans with every table option (validated against the mesh), the opt-in node plan of P2/Q1/Q2 and
-// the multigrid aggregation on the node graph; prints one summary line per plan; exit code 0 = all consistent.
+// the multigrid aggregation on the node graph; prints one summary line per plan; exit code 0 = all consistent, 1 = an
+// inconsistency, 2 = unreadable mesh file, 3 = a node row of more than 256 blocks (row_tiles: FEP_ERANGE, which
+// fep_ctx_create returns for such a mesh on every route).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +47,7 @@ int main(int argc, char** argv) {
     }
     std::vector<int32_t> tstart;
     r = row_tiles(S, n_n, 256, tstart);
+    if (r == FEP_ERANGE) { std::printf("row_tiles: FEP_ERANGE\n"); return 3; }    // a node row of more than 256 blocks: no context
     if (r != FEP_OK || tstart.front() != 0 || tstart.back() != n_blk) return 1;
     for (size_t i = 1; i < tstart.size(); ++i)
         if (tstart[i] - tstart[i - 1] > 256 || tstart[i] < tstart[i - 1]) return 1;

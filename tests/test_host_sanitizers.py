@@ -3,7 +3,8 @@ Sanitizer builds of the host-only native code (SURVEY section 5, row "race detec
 symbolic phase, the tile / gather plans of the P1 kernels, the patch plans of the element route (every element type), the
 opt-in node plan of P2 / Q2 and the multigrid aggregation (fem-elastoplasticity_amd/csrc/fep_host.h) are compiled into tests/host_san.cpp with
   g++ -fsanitize=address,undefined   and   g++ -fsanitize=thread
-and driven on structured, Delaunay (row order and random numbering), tsx-tunnel and orphan-node meshes.  Every plan
+and driven on structured, Delaunay (row order and random numbering), tsx-tunnel, orphan-node and fan meshes (one node of
+high degree, up to the 256-block row limit).  Every plan
 is checked against the mesh by fep_host::validate_p1_plan (all indices the kernels will form stay inside their
 tables / LDS regions, tiles partition the blocks, every element has one owner).  CPU only.
 """
@@ -16,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from fan_mesh import centre_of, fan_mesh, row_blocks
 
 SRC = os.path.join(ROOT, 'tests', 'host_san.cpp')
 
@@ -37,11 +39,18 @@ def binaries(tmp_path_factory):
     return {k: _build(tmp, k) for k in ('asan', 'tsan')}
 
 
-def _dump(path, elem, n_n):
+def _dump(path, elem, n_n, coord=None):
     elem = np.ascontiguousarray(elem, dtype=np.int32)
     with open(path, 'wb') as f:
         np.array([elem.shape[0], elem.shape[1], n_n], dtype=np.int32).tofile(f)
         elem.tofile(f)
+        if coord is not None:                                               # x[n_n], y[n_n]: the patch plans group by them
+            np.ascontiguousarray(coord, dtype=np.float64).tofile(f)
+
+
+# fans of k triangles around one node (tests/fan_mesh.py): the node route's last / first degree (P1 15 / 16), a row of
+# exactly 256 blocks (P1 255, P2 85), P4's last size below the limit
+FANS = (('P1', 15), ('P1', 16), ('P1', 64), ('P1', 255), ('P2', 85), ('P4', 25))
 
 
 def _meshes(fep):
@@ -68,15 +77,18 @@ def _meshes(fep):
     m = fep.square_mesh(12, 'P1', 10)                                       # nodes 50 and the last belong to no element
     out['orphans_P1'] = (np.where(m['elements'] >= 50, m['elements'] + 1, m['elements']), m['coordinates'].shape[1] + 2)
     out['one_element'] = (np.array([[0], [1], [2]]), 3)
+    for t, k in FANS:
+        elem, coord = fan_mesh(k, t, shuffle=k % 2 == 1)
+        out[f'fan{k}_{t}'] = (elem, coord.shape[1], coord)
     return out
 
 
 @pytest.mark.parametrize('kind', ['asan', 'tsan'])
 def test_host_native_code_under_sanitizers(fep, binaries, tmp_path, kind):
     env = dict(os.environ, FEP_HOST_THREADS='6', ASAN_OPTIONS='detect_leaks=1', TSAN_OPTIONS='halt_on_error=1')
-    for name, (elem, n_n) in _meshes(fep).items():
+    for name, (elem, n_n, *coord) in _meshes(fep).items():
         path = str(tmp_path / f'{name}.bin')
-        _dump(path, elem, n_n)
+        _dump(path, elem, n_n, *coord)
         for segs in ('2',) if kind == 'tsan' else ('2', '3'):
             res = subprocess.run([binaries[kind], path, segs], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                                  timeout=600)
@@ -127,6 +139,56 @@ def test_random_meshes_through_the_plan_validator(fep, binaries, tmp_path):
         for segs in ('1', '2', '4'):
             res = subprocess.run([binaries['asan'], path, segs], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
             assert res.returncode == 0 and 'result ok' in res.stdout, (trial, segs, res.stdout[-2000:])
+
+
+def _run(binary, path, segs='2'):
+    return subprocess.run([binary, path, segs], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+
+
+def test_p1_node_route_ends_at_a_node_of_16_elements(fep, binaries, tmp_path):
+    """The node route's packed descriptor counts a block's contributions in 4 bits: the centre's diagonal block of a fan
+    of k triangles has k, so the default P1 plan is packed (node route, one-kernel K,F-only step) at k = 15 and not at
+    k = 16, where fep_ctx_create puts the mesh on the element route (fep_api.hip).  Both plans validate."""
+    for k, pk, fused in ((15, 1, '1/1'), (16, 0, '0/0')):
+        elem, coord = fan_mesh(k, 'P1')
+        path = str(tmp_path / f'fan{k}.bin')
+        _dump(path, elem, coord.shape[1], coord)
+        res = _run(binaries['asan'], path)
+        assert res.returncode == 0 and 'result ok' in res.stdout, (k, res.stdout[-3000:])
+        line = [l for l in res.stdout.splitlines() if l.startswith('p1 plan [default]')][0]
+        assert ': rc 0 check 0 ' in line and ' lds 1 ' in line, line
+        assert f' pk {pk} ' in line and line.endswith(f' fused {fused}'), line
+
+
+def test_p2_fan_at_the_row_limit_has_both_patch_shapes(fep, binaries, tmp_path):
+    """fep_ctx_create retries a P2 patch plan of 56 elements (512 threads) with 28 (256 threads) when the big one cannot be
+    built.  No mesh that passes row_tiles reaches that branch: a plan fails only on a field that does not fit, and here
+    a block gathers <= 56 < 64 contributions inside one patch (one per element), a node in more than 255 patches needs
+    more than 255 elements around it and so more than 256 blocks in its row, and a row's degree is <= 256.  The P2 fan
+    whose centre row has exactly 256 blocks (k = 85, 255 elements around one node) builds and validates both shapes."""
+    elem, coord = fan_mesh(85, 'P2', shuffle=True)
+    assert row_blocks(elem, centre_of(elem)) == 256
+    path = str(tmp_path / 'fan85.bin')
+    _dump(path, elem, coord.shape[1], coord)
+    res = _run(binaries['asan'], path)
+    assert res.returncode == 0 and 'result ok' in res.stdout, res.stdout[-3000:]
+    for eb in (56, 28):
+        lines = [l for l in res.stdout.splitlines() if l.startswith(f'patch plan eb {eb} ')]
+        assert len(lines) == 4 and all(': rc 0 ok 1 check 0 ' in l for l in lines), lines
+
+
+@pytest.mark.parametrize('t,k,blocks', [('P1', 256, 257), ('P2', 86, 259), ('P4', 26, 261)])
+def test_node_row_over_256_blocks_is_erange(fep, binaries, tmp_path, t, k, blocks):
+    """One node with more than 256 blocks in its CSR row (more than 255 neighbours) does not fit a tile of the COO
+    route's reduce kernel: row_tiles returns FEP_ERANGE (fep_ctx_create then fails on every route), which the driver
+    reports as its own exit status 3, not as an inconsistency (1)."""
+    elem, coord = fan_mesh(k, t, shuffle=True)
+    assert row_blocks(elem, centre_of(elem)) == blocks
+    path = str(tmp_path / f'fan{k}.bin')
+    _dump(path, elem, coord.shape[1], coord)
+    res = _run(binaries['asan'], path)
+    assert res.returncode == 3 and 'row_tiles: FEP_ERANGE' in res.stdout, res.stdout[-3000:]
+    assert 'runtime error' not in res.stdout and 'Sanitizer' not in res.stdout, res.stdout[-3000:]
 
 
 @pytest.mark.parametrize('kind', ['asan', 'tsan'])

@@ -103,8 +103,11 @@ def test_tsx_p1_mesh_one_step_on_every_table_variant(fep, monkeypatch, route):
     both forms — with the plan replayed against the mesh first (FEP_VALIDATE_PLAN), checked against the oracle.  Once per
     route, no repetition.  (The table variants behind FEP_P1_PATH exist in the -DFEP_ABLATION build only.)"""
     from oracle import fep_oracle as orc
+    from routes import assert_route
     if route != 'node':
         monkeypatch.setenv('FEP_ROUTE', route)
+    else:
+        monkeypatch.delenv('FEP_ROUTE', raising=False)
     monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
     g = load_golden('tsx')
     elem, coord = g['elem'], g['coord']
@@ -116,6 +119,7 @@ def test_tsx_p1_mesh_one_step_on_every_table_variant(fep, monkeypatch, route):
     U = 1e-5 * np.array([y * (x / 10) + 0.5 * x * (y > 0), -0.6 * y * (x < 0) + 0.8 * y * (x >= 0)])
     U += rng.normal(0, 5e-7, size=U.shape)                         # 148 smooth / 128 apex / 611 elastic points
     ctx = fep.MeshContext(elem, coord)
+    assert_route(ctx, route)
     ctx.set_materials(sh, bu, eta, c)
     r = ctx.step(U, np.zeros((4, n)), want=('s', 'ds', 'ind_p', 'K', 'F'))
     r_kf = ctx.step(U, np.zeros((4, n)), want=('K', 'F'))

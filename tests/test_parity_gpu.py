@@ -14,7 +14,9 @@ import pytest
 import scipy.sparse as ssp
 
 from conftest import dp_materials, load_golden, relerr, relerr_points, relerr_rows
+from fan_mesh import fan_mesh
 from oracle import fep_oracle as orc
+from routes import assert_route
 
 pytestmark = pytest.mark.gpu
 
@@ -149,14 +151,27 @@ def test_elastic_setup_vs_reference_golden(fep, t):
 
 
 # ---- a1..a5 ---------------------------------------------------------------------------
+def _set_route(fep, monkeypatch, route, types):
+    """FEP_ROUTE for `route` (unset for the default one: a value the session was started with must not leak in), then a
+    context on a tiny mesh of every type in `types` must run that route: a switch the library ignores fails here."""
+    if route in ('node', 'default'):
+        monkeypatch.delenv('FEP_ROUTE', raising=False)
+    else:
+        monkeypatch.setenv('FEP_ROUTE', route)
+    monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
+    for t in types:
+        m = fep.square_mesh(2, t, 10)
+        ctx = fep.MeshContext(m['elements'], m['coordinates'])
+        assert_route(ctx, 'patch' if route == 'default' else route)
+        ctx.close()
+
+
 @pytest.fixture(params=['node', 'patch', 'coo'])
-def p1_route(request, monkeypatch):
+def p1_route(request, monkeypatch, fep):
     """P1 routes: the node-centric fast path (default: one fused kernel per K,F-only step, two kernels otherwise) and, as
     independent cross-checks, the element route every other type runs — FEP_ROUTE=patch: K_e summed in LDS, FEP_ROUTE=coo:
     K_e through HBM.  (The measured-slower variants of the node route live in the -DFEP_ABLATION build only.)"""
-    if request.param != 'node':
-        monkeypatch.setenv('FEP_ROUTE', request.param)
-    monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
+    _set_route(fep, monkeypatch, request.param, ('P1',))
     return request.param
 
 
@@ -254,13 +269,27 @@ def test_p1_mesh_with_a_node_of_no_element(fep, p1_route):
 
 
 @pytest.fixture(params=['patch', 'coo'])
-def gen_route(request, monkeypatch):
+def gen_route(request, monkeypatch, fep):
     """P2 / Q1 / Q2 (and P4): the element route in its patch form (default: K_e stays in LDS) and, as the independent
     cross-check, with the K_e round trip through HBM (FEP_ROUTE=coo)."""
-    if request.param == 'coo':
-        monkeypatch.setenv('FEP_ROUTE', 'coo')
-    monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
+    _set_route(fep, monkeypatch, 'default' if request.param == 'patch' else 'coo', ('P2', 'Q1', 'Q2'))
     return request.param
+
+
+def test_route_switches_are_read_at_every_context_creation(fep, monkeypatch):
+    """FEP_ROUTE is read by each fep_ctx_create, not once per process: in one process a context made with the switch
+    set runs the switched route and the next one, made without it, the default route again (both ways, P2 and P1)."""
+    monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
+    for t, route, default in (('P2', 'coo', 'patch'), ('P1', 'patch', 'node'), ('P2', 'coo', 'patch')):
+        m = fep.square_mesh(3, t, 10)
+        for r in (route, default):
+            if r == default:
+                monkeypatch.delenv('FEP_ROUTE', raising=False)
+            else:
+                monkeypatch.setenv('FEP_ROUTE', r)
+            ctx = fep.MeshContext(m['elements'], m['coordinates'])
+            assert_route(ctx, r)
+            ctx.close()
 
 
 def _patch_cases(fep):
@@ -283,11 +312,14 @@ def _patch_cases(fep):
                          np.concatenate([co[:, :50], [[3.3], [4.4]], co[:, 50:], [[20.0], [20.0]]], axis=1))
     m = fep.square_mesh(1, 'P2', 10)                                        # a single patch: nothing open
     out['one_cell_P2'] = (m['elements'], m['coordinates'])
+    for t, k in (('P1', 16), ('P1', 255), ('P2', 85)):                      # one node of k elements (tests/fan_mesh.py):
+        elem, coord = fan_mesh(k, t, shuffle=k % 2 == 1)                    # P1's element route, a row of 256 blocks
+        out[f'fan{k}_{t}'] = (elem, 5 + 2.5 * coord)                        # (the displacement below expects [0, 10]^2)
     return out
 
 
 @pytest.mark.parametrize('name', ['square_P2', 'square_Q1', 'square_Q2', 'square_P1', 'tsx_P1', 'tsx_P2', 'tsx_P4', 'shuffled_P2',
-                                  'orphans_Q2', 'one_cell_P2'])
+                                  'orphans_Q2', 'one_cell_P2', 'fan16_P1', 'fan255_P1', 'fan85_P2'])
 def test_patch_route_against_the_coo_route(fep, monkeypatch, name):
     """Element route, patch form (K_e blocks summed inside the workgroup's LDS, partials only for node pairs on a patch
     boundary) against the COO form (every K_e block through HBM, one flat sum per CSR block): the point outputs are the same
@@ -309,6 +341,7 @@ def test_patch_route_against_the_coo_route(fep, monkeypatch, name):
     for route in routes:
         monkeypatch.setenv('FEP_ROUTE', route)                                # (P1 too: its node route is not what is compared here)
         ctx = fep.MeshContext(elem, coord)
+        assert_route(ctx, route)
         ctx.set_materials(*dp_materials(n))
         F_poison = ctx.step(1e3 * U, None, want=('K', 'F'))                   # other values in the scratch buffers
         r = ctx.step(U, Ep.copy(), want=('E', 's', 'ds', 'ind_p', 'K', 'F'))
