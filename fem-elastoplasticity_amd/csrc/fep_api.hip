@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <new>
 #include <thread>
 #include <vector>
@@ -38,20 +40,33 @@ thread_local int fep_g_last_hip = 0;
 static const char* env_now(const char* name) { const char* v = std::getenv(name); return (v && *v) ? v : nullptr; }
 static bool env_is(const char* name, const char* v) { const char* r = env_now(name); return r && std::strcmp(r, v) == 0; }
 
+// What a context runs, chosen once at creation (choose_route):
+//   P1Node   P1's node route: p1_point_kernel + p1_node_lds_kernel, or p1_fused_kernel alone (K,F-only steps)
+//   Patch    element_kernel in its patch form (K_e summed in LDS) + fixup_kernel: every other type, P1 with FEP_ROUTE=patch
+//   Coo      element_kernel with every K_e block through HBM + csr_reduce*: FEP_ROUTE=coo, or a mesh without a patch plan
+//   GenNode  (-DFEP_ABLATION, FEP_GEN_PATH=node) P2 / Q1 / Q2: point_kernel + node_lds_kernel
+enum class Route {
+    P1Node, Patch, Coo,
+#ifdef FEP_ABLATION
+    GenNode,
+#endif
+};
+
 struct fep_ctx {
     int device = 0;
     int elem_type = 0;
     int n_p = 0, n_q = 0;
-    int64_t n_e = 0, n_n = 0, n_int = 0, n_dof = 0, nnz = 0, n_blk = 0, n_contrib = 0;
+    int64_t n_e = 0, n_n = 0, n_int = 0, n_dof = 0, nnz = 0, n_blk = 0;
+    Route route = Route::Coo;
     bool have_materials = false;
+    std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
     int csr_gathers = 4;                                // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
                                                         // measured P2 / Q2 / P4 reduce kernel: 2: 0.406 / 0.376 / 0.654 ms, 4: 0.392 / 0.347 / 0.651,
                                                         // 6: 0.382 / 0.371 / 0.650, 8 (5 waves per SIMD): 0.432 / 0.425 / 0.733)
     bool kc_aos = false;                                // K_e half-blocks: all blocks of an element adjacent (AoS) or block-major (SoA)
-    // patch route of the element kernel (default; FEP_ROUTE=coo keeps the K_e round trip): fep_host.h, PatchPlan
-    bool patch = false;
-    int patch_eb = 0, patch_dbg = 0, patch_tpb = 256, patch_js = 1;   // workgroup shape of the patch form (ElemCfg)
+    // patch route of the element kernel: fep_host.h, PatchPlan
+    int patch_eb = 0, patch_tpb = 256, patch_js = 1;    // workgroup shape of the patch form (ElemCfg)
     int lds_pad = 0;                                    // FEP_ELEM_LDS_PAD: extra LDS bytes per workgroup of element_kernel (occupancy experiments)
     int64_t n_open = 0, n_fopen = 0;
     int32_t *pt_desc = nullptr, *pt_plist = nullptr, *pt_pel = nullptr, *pt_pnodes = nullptr;
@@ -74,15 +89,14 @@ struct fep_ctx {
     int32_t *segptr = nullptr, *perm = nullptr, *iptr = nullptr, *ilist = nullptr;
     uint32_t* meta = nullptr;
     // P1 fast path (node-centric gather assembly): 64-byte geometry records, re-encoded gather list
-    bool p1_node = false, p1_lds = false;
+    bool p1_lds = false;
     double *geo = nullptr, *xy = nullptr;               // xy: interleaved (x,y) per node
     P1Tab p1tab{};
     int32_t *perm2 = nullptr, *ncol = nullptr;
-    int32_t *wg_eptr = nullptr, *wg_elist = nullptr, *wg_rng = nullptr;   // wg_rng: <= 8 (start, cum) runs per tile
+    int32_t *wg_elist = nullptr, *wg_rng = nullptr;     // wg_rng: <= 8 (start, cum) runs per tile
     bool p1_rng = false, p1_pk = false;
     uint2* pk = nullptr;                                // packed block descriptors, lanes sorted by segment length
     int4* tdesc = nullptr;                              // P1 tiles: (1 + kSegMax) int4 per tile (fep_host.h, P1Plan)
-    int p1_segs = 1;                                    // segments per tile of the plan in use
     int32_t* tstart = nullptr;                          // COO route: first block of every tile of csr_reduce_kernel
     int n_wg_p1 = 0;   // LDS-staged variant: per-workgroup element lists
     // one-kernel step (p1_fused_kernel): per-tile node lists / runs, per staged element its tile-local node indices + owner bit
@@ -97,8 +111,7 @@ struct fep_ctx {
     bool has_orphans = false;                           // nodes that belong to no element (their F entries are zeroed per step)
     uint16_t* perm_l = nullptr;
     int tile = 256;                                     // node-pair blocks per workgroup of the assembly kernel
-    bool gn = false;                                    // node route for P2 / Q1 / Q2 (point_kernel + node_lds_kernel)
-    int gn_tile = 256;
+    int gn_tile = 256;                                  // GenNode route
     size_t gn_lds = 0;
     int lds_L = 0, lds_C = 0;                           // staged elements / gather codes per workgroup (max)
     // device, scratch rewritten by every step
@@ -111,7 +124,7 @@ struct fep_ctx {
     size_t hbuf_bytes[12] = {};
     // host copies of the pattern
     std::vector<int32_t> indptr, indices;
-    // in-situ profiling: 4 events per step (before element, after element, after csr, after force)
+    // in-situ profiling: 4 events per call (fep_step_dev, fep_assemble_dev)
     bool profiling = false;
     std::vector<hipEvent_t> events;
     bool verbose = false;                               // FEP_VERBOSE at creation
@@ -127,19 +140,58 @@ __attribute__((visibility("hidden"))) int fep_set_device(int dev) {
     return FEP_OK;
 }
 
-template <class T> static int dmalloc(T** p, int64_t count) {
+// device memory of a context: recorded in c->owned, freed by fep_ctx_destroy
+template <class T> static int dmalloc(fep_ctx* c, T** p, int64_t count) {
     *p = nullptr;
     if (count <= 0) count = 1;
+    try { c->owned.reserve(c->owned.size() + 1); } catch (...) { return FEP_ENOMEM; }   // (recording cannot fail once the memory is held)
     HIP_TRY(hipMalloc((void**)p, (size_t)count * sizeof(T)));
+    c->owned.push_back(*p);
     return FEP_OK;
 }
-template <class T> static int upload(T** p, const T* src, int64_t count) {
-    FEP_TRY(dmalloc(p, count));
+template <class T> static int upload(fep_ctx* c, T** p, const T* src, int64_t count) {
+    FEP_TRY(dmalloc(c, p, count));
     if (count > 0) HIP_TRY(hipMemcpy(*p, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
     return FEP_OK;
 }
 
 static inline unsigned grid_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// Compile-time dispatch: every generic lambda below receives its template arguments as std::integral_constant /
+// std::bool_constant values (C++17 has no template lambdas)
+template <int T, int NP_, int NQ_> struct ElemT { static constexpr int type = T, NP = NP_, NQ = NQ_; };
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// f(ElemT<type, NP, NQ>) for the element type `elem_type`; FEP_EINVAL for an unknown type
+template <class F> static int with_type(int elem_type, F&& f) {
+    switch (elem_type) {
+        case FEP_P1: return f(ElemT<FEP_P1, 3, 1>{});
+        case FEP_P2: return f(ElemT<FEP_P2, 6, 7>{});
+        case FEP_Q1: return f(ElemT<FEP_Q1, 4, 4>{});
+        case FEP_Q2: return f(ElemT<FEP_Q2, 8, 9>{});
+        case FEP_P4: return f(ElemT<FEP_P4, 15, 12>{});
+        default: return FEP_EINVAL;
+    }
+}
+template <class F> static int with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+// A switch that only the ablation build varies: the product instantiates the value `Product` alone and refuses the other
+// one (FEP_ESTATE: a context the product never creates)
+template <bool Product, class F> static int with_ablation_bool(bool v, F&& f) {
+#ifdef FEP_ABLATION
+    return with_bool(v, f);
+#else
+    return v == Product ? f(std::bool_constant<Product>{}) : FEP_ESTATE;
+#endif
+}
+
+// Launches `kernel` with `lds` bytes of dynamic LDS, raising its limit first when `lds` is above `limit`
+template <class... P, class... A>
+static int launch_lds(void (*kernel)(P...), unsigned grid, unsigned tpb, size_t lds, size_t limit, hipStream_t st, A... args) {
+    if (lds > limit) HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(tpb), lds, st, args...);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 extern "C" int fep_version(void) { return 1; }
@@ -175,18 +227,11 @@ extern "C" int fep_device_count(int* n_out) {
 }
 
 extern "C" int fep_element_shape(int elem_type, int* n_p, int* n_q) {
-    int p, q;
-    switch (elem_type) {
-        case FEP_P1: p = 3; q = 1; break;
-        case FEP_P2: p = 6; q = 7; break;
-        case FEP_Q1: p = 4; q = 4; break;
-        case FEP_Q2: p = 8; q = 9; break;
-        case FEP_P4: p = 15; q = 12; break;
-        default: return FEP_EINVAL;
-    }
-    if (n_p) *n_p = p;
-    if (n_q) *n_q = q;
-    return FEP_OK;
+    return with_type(elem_type, [&](auto et) {
+        if (n_p) *n_p = decltype(et)::NP;
+        if (n_q) *n_q = decltype(et)::NQ;
+        return FEP_OK;
+    });
 }
 
 extern "C" int fep_malloc(int device_id, void** ptr_d, int64_t bytes) {
@@ -228,13 +273,18 @@ static E0 make_e0(const double* e0_h) {
     return z;
 }
 
+// Allocating is illegal while the stream is being captured into a graph: such a call is refused (FEP_ESTATE) instead of
+// breaking the capture — run the same call once outside the capture first (fep.h, fep_step_dev).
+static int scratch_alloc_allowed(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_OK; }
+    return cs == hipStreamCaptureStatusNone ? FEP_OK : FEP_ESTATE;
+}
+
 // Per-workgroup branch counters of the mesh-free return map (summed by counts_reduce_kernel): one grow-only buffer per
 // (device, stream), so that calls on different streams never share it.  The kernel used to add its two counters to the
 // caller's counts with global atomics — one contended pair per workgroup, the pattern that cost the P1 kernels 70 us per
 // launch in round 1.  Growing the buffer is an allocation: refused (FEP_ESTATE) while the stream is being captured.
-#include <map>
-#include <mutex>
-static int scratch_alloc_allowed(hipStream_t st);
 static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) {
     static std::mutex m;
     static auto& bufs = *new std::map<std::pair<int, void*>, std::pair<uint2*, size_t>>();
@@ -371,24 +421,60 @@ using fep_host::build_symbolic;
 
 static_assert(fep_host::kSegMax == fep::kSegMax, "tile descriptor layout shared by host and kernels");
 
-template <int NP, int NQ>
 static int launch_geometry(fep_ctx* c) {
-    hipLaunchKernelGGL((geometry_kernel<NP, NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, nullptr,
-                       c->n_e, c->n_n, c->elem, c->coords, c->dh1, c->dh2, c->wf, c->dphi1, c->dphi2, c->weight, c->det,
-                       c->geo);
-    HIP_TRY(hipGetLastError());
-    return FEP_OK;
+    return with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        hipLaunchKernelGGL((geometry_kernel<ET::NP, ET::NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, nullptr,
+                           c->n_e, c->n_n, c->elem, c->coords, c->dh1, c->dh2, c->wf, c->dphi1, c->dphi2, c->weight, c->det,
+                           c->geo);
+        HIP_TRY(hipGetLastError());
+        return FEP_OK;
+    });
 }
 
-#define DISPATCH_ELEM(type, CALL)                    \
-    switch (type) {                                  \
-        case FEP_P1: { CALL(3, 1); } break;          \
-        case FEP_P2: { CALL(6, 7); } break;          \
-        case FEP_Q1: { CALL(4, 4); } break;          \
-        case FEP_Q2: { CALL(8, 9); } break;          \
-        case FEP_P4: { CALL(15, 12); } break;        \
-        default: return FEP_EINVAL;                  \
-    }
+// The element kernel's per-type choices (measured; the notes are at their use in elem_form / setup_patch)
+static constexpr bool elem_geo_default(int elem_type, bool patch_form) {
+    return elem_type == FEP_Q1 || elem_type == FEP_Q2 || ((elem_type == FEP_P2 || elem_type == FEP_P4) && patch_form);
+}
+
+// Every instantiated shape of element_kernel: f(ElemT, PATCH, GEO, TPB, JS) with compile-time arguments, or FEP_ESTATE for
+// a shape without an instantiation.  The COO form runs kBlock threads, the patch form kBlock and, for P2, 512.  The
+// product instantiates one geometry form per element type and form (elem_geo_default); the ablation build both, and
+// three more patch shapes (Q2 384 / 2 and 512 / 1, P4 512 / 2).
+template <class F> static int elem_shape(int elem_type, bool patch_form, bool geo, int tpb, int js, F&& f) {
+    return with_type(elem_type, [&](auto et) {
+        using ET = decltype(et);
+        return with_bool(patch_form, [&](auto pf) {
+            constexpr bool PATCH = decltype(pf)::value;
+            auto shape = [&](auto tpb_c, auto js_c) {
+#ifdef FEP_ABLATION
+                return with_bool(geo, [&](auto g) { return f(et, pf, g, tpb_c, js_c); });
+#else
+                constexpr bool G = elem_geo_default(ET::type, PATCH);
+                return geo == G ? f(et, pf, std::bool_constant<G>{}, tpb_c, js_c) : FEP_ESTATE;
+#endif
+            };
+            if (tpb == kBlock && js == 1) return shape(int_c<kBlock>{}, int_c<1>{});
+            if constexpr (PATCH && ET::type == FEP_P2) { if (tpb == 512 && js == 1) return shape(int_c<512>{}, int_c<1>{}); }
+#ifdef FEP_ABLATION
+            if constexpr (PATCH && ET::type == FEP_Q2) {
+                if (tpb == 384 && js == 2) return shape(int_c<384>{}, int_c<2>{});
+                if (tpb == 512 && js == 1) return shape(int_c<512>{}, int_c<1>{});
+            }
+            if constexpr (PATCH && ET::type == FEP_P4) { if (tpb == 512 && js == 2) return shape(int_c<512>{}, int_c<2>{}); }
+#endif
+            return FEP_ESTATE;
+        });
+    });
+}
+
+static int elements_per_workgroup(const fep_ctx* c, bool patch_form, int tpb, int js, int* eb) {
+    return elem_shape(c->elem_type, patch_form, c->elem_geo, tpb, js, [&](auto et, auto, auto geo, auto tpb_c, auto js_c) {
+        using ET = decltype(et);
+        *eb = ElemCfg<ET::NP, ET::NQ, decltype(geo)::value, decltype(tpb_c)::value, decltype(js_c)::value>::EB;
+        return FEP_OK;
+    });
+}
 
 extern "C" int fep_ctx_destroy(fep_ctx* c) {
     if (!c) return FEP_OK;
@@ -415,16 +501,9 @@ extern "C" int fep_ctx_destroy(fep_ctx* c) {
                              acc[5] / c->n_patch, (acc[0] + acc[1] + acc[2] + acc[3] + acc[4] + acc[5]) / c->n_patch, hi - lo,
                              real > 0 ? cyc / real * 100.0 : 0.0);
             }
-            (void)hipFree(c->phase_clk);
         }
 #endif
-        void* ptrs[] = {c->elem, c->coords, c->dh1, c->dh2, c->wf, c->dphi1, c->dphi2, c->weight, c->det, c->shear, c->bulk,
-                        c->eta, c->c, c->segptr, c->perm, c->iptr, c->ilist, c->meta, c->Kc, c->fe, c->geo, c->perm2,
-                        c->ncol, c->s_int, c->ds_int, c->blk_counts, c->wg_eptr, c->wg_elist, c->wg_rng, c->perm_l, c->xy, c->pk, c->tdesc, c->tstart,
-                        c->wg_nlist, c->wg_nrng, c->el_nodes, c->slot_counts, c->pkc, c->pt_desc, c->pt_plist, c->pt_items,
-                        c->pt_fitems, c->pt_codes, c->pt_fcodes, c->pt_fix, c->pt_ffix, c->Pc, c->Pf, c->pt_pel, c->pt_pnodes, c->pt_fixT};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
+        for (void* p : c->owned) (void)hipFree(p);
         for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
         for (void* p : c->hbuf)
             if (p) (void)hipFree(p);
@@ -457,14 +536,290 @@ extern "C" int fep_ctx_create(fep_ctx** ctx_out, int device_id, int elem_type, i
     return r;
 }
 
-// The element kernel's per-type choices (measured; the notes are at their use in ctx_create_impl)
-static constexpr bool elem_geo_default(int elem_type, bool patch_form) {
-    return elem_type == FEP_Q1 || elem_type == FEP_Q2 || ((elem_type == FEP_P2 || elem_type == FEP_P4) && patch_form);
+// What the route set-ups read of fep_ctx_create's inputs
+struct MeshIn {
+    const Symbolic& S;
+    const int32_t* elem;
+    const double *coords, *dh1, *dh2, *wf;
+    bool validate;                                      // FEP_VALIDATE_PLAN: replay every plan against the symbolic phase
+};
+
+// P1 node route: the gather plan (fep_host.h, P1Plan) and its tables.  *taken = false: the product takes the element
+// route instead.
+static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
+    *taken = false;
+    fep_host::P1Options opt;
+#ifdef FEP_ABLATION
+    // FEP_P1_TILE=128: tiles of 128 blocks on 128 threads (16 instead of 8 resident per CU; VERDICT r3 item 5's structural
+    // attempt: the K,F-only step measured 0.0706-0.0715 against 0.0629-0.0631 ms, profiles/r04_ablation.md)
+    if (const char* tl = fep_tune("FEP_P1_TILE")) c->tile = std::atoi(tl) == 128 ? 128 : 256;
+    {   // FEP_P1_PATH=node_direct | node_list | node_unpacked | node2k: plans without one of the default's ingredients
+        const char* pth = fep_tune("FEP_P1_PATH");
+        auto is = [&](const char* v) { return pth && std::strcmp(pth, v) == 0; };
+        opt.allow_lds = !is("node_direct");
+        opt.allow_rng = !is("node_list");
+        opt.allow_pk = !is("node_unpacked");
+        opt.allow_fused = !is("node2k");
+        if (const char* sg = fep_tune("FEP_P1_SEGS")) opt.max_segs = std::max(1, std::min(std::atoi(sg), fep_host::kSegMax));
+    }
+#endif
+    opt.tile = c->tile;
+    fep_host::P1Plan P;
+    FEP_TRY(fep_host::build_p1_plan(in.S, c->n_e, c->n_n, in.elem, opt, P));
+    if (in.validate) {
+        const int bad = fep_host::validate_p1_plan(P, in.S, c->n_e, c->n_n, in.elem);
+        if (bad) { std::fprintf(stderr, "[fep] P1 plan fails check %d\n", bad); return FEP_EINVAL; }
+    }
+#ifndef FEP_ABLATION
+    // A mesh whose tiles do not fit the LDS-staged form or whose descriptor fields do not pack (node degree >= 2^12, ...)
+    // takes the element route like every other element type: the product keeps ONE node route.
+    if (!(P.lds && P.pk)) {
+        if (c->verbose) std::fprintf(stderr, "[fep] P1 plan without the LDS-staged packed form (lds %d pk %d): element route\n", (int)P.lds, (int)P.pk);
+        return FEP_OK;
+    }
+#endif
+    *taken = true;
+    c->n_wg_p1 = (int)P.n_wg;
+    c->p1_lds = P.lds; c->lds_L = P.L; c->lds_C = P.C; c->p1_rng = P.rng; c->p1_pk = P.pk;
+    c->p1_fused = P.fused; c->p1_fused_rng = P.fused_rng; c->lds_NL = P.NL;
+#ifdef FEP_ABLATION
+    if (const char* am = fep_tune("FEP_P1_ASM")) c->asm_from_nodes = std::strcmp(am, "nodes") == 0;
+    if (const char* dm = fep_tune("FEP_P1_DMA")) c->p1_dma = std::strcmp(dm, "0") != 0;
+    if (const char* fm = fep_tune("FEP_P1_FUSED"))
+        c->fused_mode = std::strcmp(fm, "off") == 0 ? 0 : std::strcmp(fm, "kf") == 0 ? 1 : 2;
+#endif
+    FEP_TRY(upload(c, &c->perm2, P.perm2.data(), (int64_t)P.perm2.size()));
+    FEP_TRY(upload(c, &c->ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
+    FEP_TRY(upload(c, &c->tdesc, (const int4*)P.tdesc.data(), (int64_t)P.tdesc.size() / 4));
+    if (P.lds) {
+        FEP_TRY(upload(c, &c->wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
+        FEP_TRY(upload(c, &c->perm_l, P.codes_pad.data(), (int64_t)P.codes_pad.size()));
+        if (P.rng) FEP_TRY(upload(c, &c->wg_rng, P.rng_tab.data(), (int64_t)P.rng_tab.size()));
+        if (P.pk) FEP_TRY(upload(c, &c->pk, (const uint2*)P.pkv.data(), (int64_t)P.pkv.size()));
+    }
+    if (P.fused) {
+        FEP_TRY(upload(c, &c->el_nodes, P.elnodes.data(), (int64_t)P.elnodes.size()));
+        if (P.fused_rng) FEP_TRY(upload(c, &c->wg_nrng, P.nrng_tab.data(), (int64_t)P.nrng_tab.size()));
+        else FEP_TRY(upload(c, &c->wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size()));
+        FEP_TRY(dmalloc(c, &c->slot_counts, 256 * 16));
+        HIP_TRY(hipMemset(c->slot_counts, 0, 256 * 16 * sizeof(unsigned long long)));
+    }
+    if (c->verbose)
+        std::fprintf(stderr, "[fep] P1 plan: %lld tiles of <= %d blocks in <= %d segment(s), staged elements %lld "
+                     "(%.2f per element, <= %d per tile), staged nodes <= %d, codes <= %d; lds %d rng %d pk %d fused %d/%d\n",
+                     (long long)P.n_wg, P.tile, P.n_segs, (long long)P.staged_total, (double)P.staged_total / (double)c->n_e,
+                     P.L, P.NL, P.C, (int)P.lds, (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
+    FEP_TRY(dmalloc(c, &c->geo, 6 * c->n_e));
+    for (int a = 0; a < 3; ++a) { c->p1tab.h1[a] = in.dh1[a]; c->p1tab.h2[a] = in.dh2[a]; }
+    c->p1tab.wf = in.wf[0];
+    c->n_count_blocks = (int)grid_for(c->n_e, kBlock);
+    return FEP_OK;
 }
-static void patch_shape_default(int elem_type, bool patch_form, int& tpb, int& js) {
-    tpb = 256; js = 1;
-    if (patch_form && elem_type == FEP_P2) tpb = 512;
-    if (patch_form && elem_type == FEP_P4) { tpb = FEP_P4_TPB; js = FEP_P4_JS; }
+
+#ifdef FEP_ABLATION
+// FEP_GEN_PATH=node: node route for P2 / Q1 / Q2 (point_kernel + node_lds_kernel; measured on MI355X, 1 M elements:
+// Q1 0.276 vs 0.286 ms, P2 1.80 vs 1.30 ms, Q2 0.41 vs 0.34 ms per step — its LDS gather costs n_q times the P1 one).
+// *taken = false: no plan fits, the element route.
+static int setup_gen_node(fep_ctx* c, const MeshIn& in, bool* taken) {
+    fep_host::GnPlan G;
+    fep_host::build_gn_plan(in.S, c->n_p, c->n_q, c->n_e, G);
+    *taken = G.ok;
+    if (!G.ok) return FEP_OK;
+    c->gn_tile = G.tile; c->lds_L = G.L; c->lds_C = G.C; c->gn_lds = G.lds;
+    FEP_TRY(upload(c, &c->wg_elist, G.elist_pad.data(), (int64_t)G.elist_pad.size()));
+    FEP_TRY(upload(c, &c->perm_l, G.codes_pad.data(), (int64_t)G.codes_pad.size()));
+    FEP_TRY(upload(c, &c->ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
+    c->n_count_blocks = (int)grid_for(c->n_int, kBlock);
+    return FEP_OK;
+}
+#endif
+
+// Geometry of the element kernel from the coordinates (GEO) or from the streamed dphi arrays, fixed per type and form
+// (elem_geo_default): measured on MI355X (1 M elements, element kernel alone): recomputed geometry wins for Q1 (0.204 vs
+// 0.218 ms) and Q2 (0.344 vs 0.391 ms with 24 instead of 28 elements per workgroup, so that three workgroups still fit a
+// CU) and loses for P2 in the COO form (0.50 vs 0.47 ms at 28 / 32 elements per workgroup); round 3, patch form:
+// recomputed geometry wins for P2 as well (same session, 1 M elements: 0.754 vs 0.783 ms on a fast box, 0.888 vs 0.936
+// on a slow one); round 4, final patch kernel, one session, two passes each: P4 0.769-0.771 against 0.842-0.869 ms (its 30
+// gradient loads per point were a third of its workgroup's life), Q2 0.604 / 0.709, P2 0.632-0.638 / 0.700-0.710, Q1
+// 0.163-0.164 / 0.167-0.174: recomputed for every type in the patch form
+static void elem_form(fep_ctx* c, bool patch_form) {
+    c->elem_geo = elem_geo_default(c->elem_type, patch_form);
+#ifdef FEP_ABLATION
+    if (const char* ge = fep_tune("FEP_ELEM_GEO")) c->elem_geo = std::strcmp(ge, "0") != 0;
+    if (const char* lp = fep_tune("FEP_ELEM_LDS_PAD")) c->lds_pad = std::max(0, std::atoi(lp));
+#endif
+}
+
+// Patch form of the element route (no K_e round trip through HBM; same session, 0.25-4 M elements, profiles/r03_ablation.md,
+// r03_elem_bench.log: P2 -17 % (K,F-only -19 %, BASELINE configs[4] -14 %), Q2 -14 %, Q1 -13 %, P4 -21 % against the COO
+// form).  *taken = false: no patch plan fits (a descriptor field too wide), the COO form.
+static int setup_patch(fep_ctx* c, const MeshIn& in, bool* taken) {
+    *taken = false;
+    elem_form(c, true);
+    // Workgroup shape (threads; lanes per (element, node) pair in phase 2: ElemCfg's JS), fixed per type:
+    //   P2  512 / 1: 56 elements on 512 threads (two workgroups of eight waves per CU instead of four of four: the same waves,
+    //       2.0 instead of 3.2 partials per element with four runs, fix-up kernel -35 %, element kernel +3-12 %): three boxes,
+    //       same session each: 1 M elements 0.653 / 0.681 / 0.724 against 0.700 / 0.713 / 0.716 ms, BASELINE configs[4] 2.61 /
+    //       2.89 / 2.89 against 2.86 / 3.09 / 3.00, K,F-only 0.613 against 0.653
+    //   Q2  256 / 1 (40 elements on 512 threads, 3.5 instead of 5.8 partials per element: 0.76-0.80 against 0.62 ms; 24 elements
+    //       on 384 threads with JS = 2: 0.82-0.83 against 0.62, profiles/r04_ablation.md)
+    //   P4  FEP_P4_TPB / FEP_P4_JS
+    int tpb = c->elem_type == FEP_P2 ? 512 : c->elem_type == FEP_P4 ? FEP_P4_TPB : 256;
+    int js = c->elem_type == FEP_P4 ? FEP_P4_JS : 1;
+    bool shape_forced = false;
+#ifdef FEP_ABLATION
+    if (const char* tpb_env = fep_tune("FEP_PATCH_TPB")) {
+        tpb = std::atoi(tpb_env);
+        const char* js_env = fep_tune("FEP_PATCH_JS");
+        js = js_env ? std::atoi(js_env) : 1;
+        shape_forced = true;
+    }
+#endif
+    int eb = 0;
+    if (elements_per_workgroup(c, true, tpb, js, &eb) != FEP_OK) return FEP_EINVAL;      // no such instantiation
+    fep_host::PatchPlan P;
+    fep_host::PatchOptions popt;
+#ifdef FEP_ABLATION
+    if (const char* po = fep_tune("FEP_PATCH_ORDER"))
+        popt.order = std::strcmp(po, "consecutive") == 0 ? 0 : std::strcmp(po, "hilbert") == 0 ? 1 : 2;
+#endif
+    // Q1 (64 elements per patch): 4 runs of 16 measured 6 % faster than 2 of 32; P2 with 56 elements: 4 runs of 14
+    // (1.96 partials per element) 1-3 % faster than 2 of 28 (2.86); with 28 elements 2 runs of 14 (4 of 7: +7 %)
+    popt.runs = (c->elem_type == FEP_Q1 || tpb == 512) ? 4 : 2;
+    // (runs starting on 128-byte boundaries of the point arrays — 16 / gcd(16, n_q) elements — measured no faster and
+    // cost a third more partials: the aligned starts leave short leftovers)
+#ifdef FEP_ABLATION
+    if (const char* pr = fep_tune("FEP_PATCH_RUNS")) popt.runs = std::max(1, std::atoi(pr));
+    if (const char* pa = fep_tune("FEP_PATCH_ALIGN")) popt.align = std::max(1, std::atoi(pa));
+#endif
+    FEP_TRY(fep_host::build_patch_plan(in.S, c->n_p, c->n_e, c->n_n, in.elem, in.coords, eb, popt, P));
+    if (!P.ok && tpb == 512 && js == 1 && !shape_forced) {         // the big patches cannot be built: the small ones
+        tpb = 256;                                                  // (a forced shape is never changed silently)
+        FEP_TRY(elements_per_workgroup(c, true, tpb, js, &eb));
+        if (!fep_tune("FEP_PATCH_RUNS")) popt.runs = 2;
+        FEP_TRY(fep_host::build_patch_plan(in.S, c->n_p, c->n_e, c->n_n, in.elem, in.coords, eb, popt, P));
+    }
+    if (!P.ok) return shape_forced && tpb != 256 ? FEP_ESTATE : FEP_OK;      // (a forced plan that could not be built)
+    if (in.validate) {
+        const int bad = fep_host::validate_patch_plan(P, in.S, c->n_p, c->n_e, c->n_n, in.elem);
+        if (bad) { std::fprintf(stderr, "[fep] patch plan fails check %d\n", bad); return FEP_EINVAL; }
+    }
+    *taken = true;
+    c->patch_tpb = tpb; c->patch_js = js;
+    c->patch_eb = P.eb; c->n_open = P.n_open; c->n_fopen = P.n_fopen; c->n_patch = P.n_patch;
+    // one zero pad entry after each item / code table: element_kernel reads them at clamped indices, also for a patch
+    // without items
+    P.items.push_back(fep_host::U2{0u, 0u});
+    P.fitems.push_back(fep_host::U2{0u, 0u});
+    P.codes.insert(P.codes.end(), 2, 0);
+    P.fcodes.insert(P.fcodes.end(), 2, 0);
+    FEP_TRY(upload(c, &c->pt_desc, P.pdesc.data(), (int64_t)P.pdesc.size()));
+    FEP_TRY(upload(c, &c->pt_pel, P.pel.data(), (int64_t)P.pel.size()));
+    FEP_TRY(upload(c, &c->pt_pnodes, P.pnodes.data(), (int64_t)P.pnodes.size()));
+    FEP_TRY(upload(c, &c->pt_items, (const uint2*)P.items.data(), (int64_t)P.items.size()));
+    FEP_TRY(upload(c, &c->pt_codes, P.codes.data(), (int64_t)P.codes.size()));
+    FEP_TRY(upload(c, &c->pt_fitems, (const uint2*)P.fitems.data(), (int64_t)P.fitems.size()));
+    FEP_TRY(upload(c, &c->pt_fcodes, P.fcodes.data(), (int64_t)P.fcodes.size()));
+    FEP_TRY(upload(c, &c->pt_fix, (const uint4*)P.fix.data(), (int64_t)P.fix.size()));
+    FEP_TRY(upload(c, &c->pt_fixT, (const uint2*)P.fixT.data(), (int64_t)P.fixT.size()));
+    FEP_TRY(upload(c, &c->pt_ffix, (const uint4*)P.ffix.data(), (int64_t)P.ffix.size()));
+    FEP_TRY(upload(c, &c->pt_plist, P.plist.data(), (int64_t)P.plist.size()));
+#ifdef FEP_ABLATION
+    if (fep_tune("FEP_PHASE_CLK")) {
+        FEP_TRY(dmalloc(c, &c->phase_clk, 12 * P.n_patch));
+        (void)hipMemset(c->phase_clk, 0, (size_t)(12 * P.n_patch) * sizeof(unsigned long long));
+    }
+#endif
+    FEP_TRY(dmalloc(c, &c->Pc, 4 * P.n_part));
+    FEP_TRY(dmalloc(c, &c->Pf, 2 * P.n_fpart));
+    if (c->verbose)
+        std::fprintf(stderr, "[fep] patch plan: %lld patches of <= %d elements, %zu items (<= %d per patch), %lld open blocks of %lld, "
+                     "%lld partials (%.2f per element), %lld open nodes\n", (long long)P.n_patch, P.eb, P.items.size(), P.max_items,
+                     (long long)P.n_open, (long long)c->n_blk, (long long)P.n_part, (double)P.n_part / (double)c->n_e,
+                     (long long)P.n_fopen);
+    c->n_count_blocks = (int)c->n_patch;
+    return FEP_OK;
+}
+
+// COO form of the element route: K_e / f_e through HBM, csr_reduce* and the force gather sum them per block / node
+static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& tstart) {
+    elem_form(c, false);
+    int eb = 0;
+    if (elements_per_workgroup(c, false, kBlock, 1, &eb) != FEP_OK) return FEP_EINVAL;
+    c->n_count_blocks = (int)grid_for(c->n_e, eb);
+    // measured at ~1 M points per type (tools/elem_bench.py): the element-major layout pays for the 15-node element only
+    // (P4: step 1.47 -> 1.35 ms; P2 0.96 -> 1.06, Q2 0.82 -> 0.94, Q1 0.22 -> 0.26: their stores lose coalescing)
+    c->kc_aos = c->elem_type == FEP_P4;
+#ifdef FEP_ABLATION
+    if (const char* kl = fep_tune("FEP_KC_LAYOUT")) c->kc_aos = std::strcmp(kl, "aos") == 0;
+    if (const char* cg = fep_tune("FEP_CSR_GATHERS")) c->csr_gathers = std::atoi(cg);
+#endif
+    const int n_p = c->n_p;
+    const int64_t n_e = c->n_e;
+    if ((int64_t)sym_block_count(n_p) * n_e >= (int64_t)1 << 30) return FEP_ERANGE;     // 2 * position fits int32
+    const Symbolic& S = in.S;
+    {   // element_kernel stores half of the symmetric K_e: re-address the contributions (block, transposed)
+        std::vector<int32_t> perm_sym(S.perm.size());
+        for (size_t i = 0; i < S.perm.size(); ++i) {
+            const int64_t v = S.perm[i];
+            const int ab = (int)(v / n_e);
+            const int64_t e = v - (int64_t)ab * n_e;
+            int idx; bool tr;
+            sym_block_index(n_p, ab / n_p, ab % n_p, idx, tr, c->kc_aos);
+            const int64_t pos = c->kc_aos ? e * sym_block_count(n_p) + idx : (int64_t)idx * n_e + e;
+            perm_sym[i] = (int32_t)(2 * pos + (tr ? 1 : 0));
+        }
+        perm_sym.resize(perm_sym.size() + 4, 0);                    // csr_reduce_pk_kernel reads the addresses four at a time
+        FEP_TRY(upload(c, &c->perm, perm_sym.data(), (int64_t)perm_sym.size()));
+    }
+    // one 8-byte descriptor per block, if its fields fit (count < 256, degree and slot < 4096)
+    std::vector<uint2> pkc((size_t)c->n_blk);
+    bool fits = fep_tune("FEP_CSR_UNPACKED") == nullptr;
+    for (int64_t b = 0; b < c->n_blk && fits; ++b) {
+        const uint32_t len = (uint32_t)(S.segptr[b + 1] - S.segptr[b]), deg = S.meta[b] >> 16, slot = S.meta[b] & 0x7fffu;
+        fits = len < 256 && deg < 4096 && slot < 4096;
+        pkc[b] = make_uint2((uint32_t)S.segptr[b], len | (deg << 8) | (slot << 20));
+    }
+    if (fits) FEP_TRY(upload(c, &c->pkc, pkc.data(), (int64_t)pkc.size()));
+    FEP_TRY(upload(c, &c->tstart, tstart.data(), (int64_t)tstart.size()));
+    c->n_wg_p1 = (int)tstart.size() - 1;
+    FEP_TRY(dmalloc(c, &c->Kc, 4 * (int64_t)sym_block_count(n_p) * n_e));
+    FEP_TRY(dmalloc(c, &c->fe, 2 * (int64_t)n_p * n_e));
+    return FEP_OK;
+}
+
+// The route of a new context, from its element type, FEP_ROUTE and whether the route's plan can be built:
+//   P1         the node route unless FEP_ROUTE names a form of the element route (the product takes the patch form for a
+//              plan without the LDS-staged packed form: setup_p1_node)
+//   P2 Q1 Q2   (ablation build, FEP_GEN_PATH=node) the GenNode route if its plan fits
+//   otherwise  the patch form unless FEP_ROUTE=coo; the COO form if no patch plan fits
+static int choose_route(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& tstart) {
+    const bool route_coo = env_is("FEP_ROUTE", "coo"), route_patch = env_is("FEP_ROUTE", "patch");
+    bool taken = false;
+    if (c->elem_type == FEP_P1 && !route_coo && !route_patch) {
+        FEP_TRY(setup_p1_node(c, in, &taken));
+        if (taken) c->route = Route::P1Node;
+    }
+#ifdef FEP_ABLATION
+    else if (c->elem_type == FEP_P2 || c->elem_type == FEP_Q1 || c->elem_type == FEP_Q2) {
+        const char* gp = fep_tune("FEP_GEN_PATH");
+        if (gp && std::strcmp(gp, "node") == 0) FEP_TRY(setup_gen_node(c, in, &taken));
+        if (taken) c->route = Route::GenNode;
+    }
+#endif
+    if (!taken && !route_coo) {
+        FEP_TRY(setup_patch(c, in, &taken));
+        if (taken) c->route = Route::Patch;
+    }
+    if (!taken) {
+        c->route = Route::Coo;
+        FEP_TRY(setup_coo(c, in, tstart));
+    }
+    if (c->route != Route::Patch) {                     // every block's contribution list (the node routes and the COO form)
+        FEP_TRY(upload(c, &c->segptr, in.S.segptr.data(), (int64_t)in.S.segptr.size()));
+        FEP_TRY(upload(c, &c->meta, in.S.meta.data(), (int64_t)in.S.meta.size()));
+    }
+    return FEP_OK;
 }
 
 static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int elem_type, int64_t n_e, int64_t n_n,
@@ -480,11 +835,9 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     c = new (std::nothrow) fep_ctx();
     if (!c) return FEP_ENOMEM;
     c->device = device_id; c->elem_type = elem_type; c->n_p = n_p; c->n_q = n_q;
-    const bool route_coo = env_is("FEP_ROUTE", "coo"), route_patch = env_is("FEP_ROUTE", "patch");
-    const bool validate_plans = env_now("FEP_VALIDATE_PLAN") != nullptr;
     c->verbose = env_now("FEP_VERBOSE") != nullptr;
     c->n_e = n_e; c->n_n = n_n; c->n_int = n_e * n_q; c->n_dof = 2 * n_n;
-    c->n_blk = (int64_t)S.ncol.size(); c->nnz = 4 * c->n_blk; c->n_contrib = (int64_t)S.perm.size();
+    c->n_blk = (int64_t)S.ncol.size(); c->nnz = 4 * c->n_blk;
     for (int64_t n = 0; n < n_n && !c->has_orphans; ++n) c->has_orphans = S.iptr[n + 1] == S.iptr[n];
     // host CSR pattern on DOFs
     c->indptr.resize(c->n_dof + 1);
@@ -501,302 +854,34 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
         }
     }
     c->indptr[c->n_dof] = (int32_t)c->nnz;
-    int r = FEP_OK;
-#define CK(x) do { if (r == FEP_OK) r = (x); } while (0)
-    CK(upload(&c->elem, elements_h, (int64_t)n_p * n_e));
-    CK(upload(&c->coords, coords_h, 2 * n_n));
-    CK(upload(&c->dh1, dhatp1_h, (int64_t)n_p * n_q));
-    CK(upload(&c->dh2, dhatp2_h, (int64_t)n_p * n_q));
-    CK(upload(&c->wf, wf_h, (int64_t)n_q));
-    CK(dmalloc(&c->dphi1, (int64_t)n_p * c->n_int));
-    CK(dmalloc(&c->dphi2, (int64_t)n_p * c->n_int));
-    CK(dmalloc(&c->weight, c->n_int));
-    CK(dmalloc(&c->det, c->n_int));
-    CK(dmalloc(&c->shear, c->n_int)); CK(dmalloc(&c->bulk, c->n_int)); CK(dmalloc(&c->eta, c->n_int)); CK(dmalloc(&c->c, c->n_int));
-    // COO route: tiles of whole nodes with at most kBlock node-pair blocks (csr_reduce_kernel's work units)
-    std::vector<int32_t> tstart_all;
-    CK(fep_host::row_tiles(S, n_n, kBlock, tstart_all));
-    // P1 runs the node-centric fast path unless FEP_ROUTE asks for the element route (coo | patch)
-    c->p1_node = elem_type == FEP_P1 && !route_coo && !route_patch;
-    if (c->p1_node) {
-        // gather plan of the node route (host, fep_host.h): tiles, staged element / node lists, codes, descriptors
-        fep_host::P1Options opt;
-#ifdef FEP_ABLATION
-        // FEP_P1_TILE=128: tiles of 128 blocks on 128 threads (16 instead of 8 resident per CU; VERDICT r3 item 5's structural
-        // attempt: the K,F-only step measured 0.0706-0.0715 against 0.0629-0.0631 ms, profiles/r04_ablation.md)
-        if (const char* tl = fep_tune("FEP_P1_TILE")) c->tile = std::atoi(tl) == 128 ? 128 : 256;
-#endif
-        opt.tile = c->tile;
-#ifdef FEP_ABLATION
-        {   // FEP_P1_PATH=node_direct | node_list | node_unpacked | node2k: plans without one of the default's ingredients
-            const char* pth = fep_tune("FEP_P1_PATH");
-            auto is = [&](const char* v) { return pth && std::strcmp(pth, v) == 0; };
-            opt.allow_lds = !is("node_direct");
-            opt.allow_rng = !is("node_list");
-            opt.allow_pk = !is("node_unpacked");
-            opt.allow_fused = !is("node2k");
-            if (const char* sg = fep_tune("FEP_P1_SEGS")) opt.max_segs = std::max(1, std::min(std::atoi(sg), fep_host::kSegMax));
-        }
-#endif
-        fep_host::P1Plan P;
-        CK(fep_host::build_p1_plan(S, n_e, n_n, elements_h, opt, P));
-        if (r == FEP_OK && validate_plans) {
-            const int bad = fep_host::validate_p1_plan(P, S, n_e, n_n, elements_h);
-            if (bad) { std::fprintf(stderr, "[fep] P1 plan fails check %d\n", bad); r = FEP_EINVAL; }
-        }
-#ifndef FEP_ABLATION
-        // A mesh whose tiles do not fit the LDS-staged form or whose descriptor fields do not pack (node degree >= 2^12, ...)
-        // takes the element route like every other element type: the product keeps ONE node route.
-        if (r == FEP_OK && !(P.lds && P.pk)) {
-            c->p1_node = false;
-            if (c->verbose) std::fprintf(stderr, "[fep] P1 plan without the LDS-staged packed form (lds %d pk %d): element route\n", (int)P.lds, (int)P.pk);
-        }
-#endif
-        if (r == FEP_OK && c->p1_node) {
-            c->n_wg_p1 = (int)P.n_wg; c->p1_segs = P.n_segs;
-            c->p1_lds = P.lds; c->lds_L = P.L; c->lds_C = P.C; c->p1_rng = P.rng; c->p1_pk = P.pk;
-            c->p1_fused = P.fused; c->p1_fused_rng = P.fused_rng; c->lds_NL = P.NL;
-#ifdef FEP_ABLATION
-            if (const char* am = fep_tune("FEP_P1_ASM")) c->asm_from_nodes = std::strcmp(am, "nodes") == 0;
-            if (const char* dm = fep_tune("FEP_P1_DMA")) c->p1_dma = std::strcmp(dm, "0") != 0;
-            if (const char* fm = fep_tune("FEP_P1_FUSED"))
-                c->fused_mode = std::strcmp(fm, "off") == 0 ? 0 : std::strcmp(fm, "kf") == 0 ? 1 : 2;
-#endif
-            CK(upload(&c->perm2, P.perm2.data(), (int64_t)P.perm2.size()));
-            CK(upload(&c->ncol, S.ncol.data(), (int64_t)S.ncol.size()));
-            CK(upload(&c->tdesc, (const int4*)P.tdesc.data(), (int64_t)P.tdesc.size() / 4));
-            if (P.lds) {
-                CK(upload(&c->wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
-                CK(upload(&c->perm_l, P.codes_pad.data(), (int64_t)P.codes_pad.size()));
-                if (P.rng) CK(upload(&c->wg_rng, P.rng_tab.data(), (int64_t)P.rng_tab.size()));
-                if (P.pk) CK(upload(&c->pk, (const uint2*)P.pkv.data(), (int64_t)P.pkv.size()));
-            }
-            if (P.fused) {
-                CK(upload(&c->el_nodes, P.elnodes.data(), (int64_t)P.elnodes.size()));
-                if (P.fused_rng) { CK(upload(&c->wg_nrng, P.nrng_tab.data(), (int64_t)P.nrng_tab.size())); }
-                else { CK(upload(&c->wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size())); }
-                CK(dmalloc(&c->slot_counts, 256 * 16));
-                if (r == FEP_OK && hipMemset(c->slot_counts, 0, 256 * 16 * sizeof(unsigned long long)) != hipSuccess) r = FEP_EHIP;
-            }
-            if (c->verbose)
-                std::fprintf(stderr, "[fep] P1 plan: %lld tiles of <= %d blocks in <= %d segment(s), staged elements %lld "
-                             "(%.2f per element, <= %d per tile), staged nodes <= %d, codes <= %d; lds %d rng %d pk %d fused %d/%d\n",
-                             (long long)P.n_wg, P.tile, P.n_segs, (long long)P.staged_total, (double)P.staged_total / (double)n_e,
-                             P.L, P.NL, P.C, (int)P.lds, (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
-        }
-        if (c->p1_node) {
-            CK(dmalloc(&c->geo, 6 * n_e));
-            for (int a = 0; a < 3; ++a) { c->p1tab.h1[a] = dhatp1_h[a]; c->p1tab.h2[a] = dhatp2_h[a]; }
-            c->p1tab.wf = wf_h[0];
-            c->n_count_blocks = (int)grid_for(n_e, kBlock);
-        }
-    }
-#ifdef FEP_ABLATION
-    else {
-        // FEP_GEN_PATH=node: node route for P2 / Q1 / Q2 (point_kernel + node_lds_kernel; measured on MI355X, 1 M elements:
-        // Q1 0.276 vs 0.286 ms, P2 1.80 vs 1.30 ms, Q2 0.41 vs 0.34 ms per step — its LDS gather costs n_q times the P1 one)
-        const char* gp = fep_tune("FEP_GEN_PATH");
-        const bool want_gn = (elem_type == FEP_P2 || elem_type == FEP_Q1 || elem_type == FEP_Q2) &&
-                             gp && std::strcmp(gp, "node") == 0 && r == FEP_OK;
-        if (want_gn) {
-            fep_host::GnPlan G;
-            fep_host::build_gn_plan(S, n_p, n_q, n_e, G);
-            if (G.ok) {
-                c->gn = true; c->gn_tile = G.tile; c->lds_L = G.L; c->lds_C = G.C; c->gn_lds = G.lds;
-                CK(upload(&c->wg_elist, G.elist_pad.data(), (int64_t)G.elist_pad.size()));
-                CK(upload(&c->perm_l, G.codes_pad.data(), (int64_t)G.codes_pad.size()));
-                CK(upload(&c->ncol, S.ncol.data(), (int64_t)S.ncol.size()));
-                c->n_count_blocks = (int)grid_for(c->n_int, kBlock);
-            }
-        }
-    }
-#endif
-    // element route: the patch form (no K_e round trip through HBM; default) or the COO form (FEP_ROUTE=coo).
-    // Same session, 0.25-4 M elements (profiles/r03_ablation.md, r03_elem_bench.log): P2 -17 % (K,F-only -19 %, BASELINE
-    // configs[4] -14 %), Q2 -14 %, Q1 -13 %, P4 -21 % against the COO form
-    const bool coo_form = route_coo;
-    const bool want_patch = !c->p1_node && !c->gn && !coo_form;
+    FEP_TRY(upload(c, &c->elem, elements_h, (int64_t)n_p * n_e));
+    FEP_TRY(upload(c, &c->coords, coords_h, 2 * n_n));
+    FEP_TRY(upload(c, &c->dh1, dhatp1_h, (int64_t)n_p * n_q));
+    FEP_TRY(upload(c, &c->dh2, dhatp2_h, (int64_t)n_p * n_q));
+    FEP_TRY(upload(c, &c->wf, wf_h, (int64_t)n_q));
+    FEP_TRY(dmalloc(c, &c->dphi1, (int64_t)n_p * c->n_int));
+    FEP_TRY(dmalloc(c, &c->dphi2, (int64_t)n_p * c->n_int));
+    FEP_TRY(dmalloc(c, &c->weight, c->n_int));
+    FEP_TRY(dmalloc(c, &c->det, c->n_int));
+    FEP_TRY(dmalloc(c, &c->shear, c->n_int)); FEP_TRY(dmalloc(c, &c->bulk, c->n_int));
+    FEP_TRY(dmalloc(c, &c->eta, c->n_int)); FEP_TRY(dmalloc(c, &c->c, c->n_int));
     {   // interleaved (x, y) per node: the kernels recompute dphi / weight from the coordinates
         std::vector<double> xy(2 * (size_t)n_n);
         for (int64_t n = 0; n < n_n; ++n) { xy[2 * n] = coords_h[n]; xy[2 * n + 1] = coords_h[n_n + n]; }
-        CK(upload(&c->xy, xy.data(), (int64_t)xy.size()));
-        // geometry of the element kernel from the coordinates (GEO) or from the streamed dphi arrays, fixed per type and form
-        // (elem_geo_default): measured on MI355X (1 M elements, element kernel alone): recomputed geometry wins for Q1 (0.204 vs
-        // 0.218 ms) and Q2 (0.344 vs 0.391 ms with 24 instead of 28 elements per workgroup, so that three workgroups still fit a
-        // CU) and loses for P2 in the COO form (0.50 vs 0.47 ms at 28 / 32 elements per workgroup); round 3, patch form:
-        // recomputed geometry wins for P2 as well (same session, 1 M elements: 0.754 vs 0.783 ms on a fast box, 0.888 vs 0.936
-        // on a slow one); round 4, final patch kernel, one session, two passes each: P4 0.769-0.771 against 0.842-0.869 ms (its 30
-        // gradient loads per point were a third of its workgroup's life), Q2 0.604 / 0.709, P2 0.632-0.638 / 0.700-0.710, Q1
-        // 0.163-0.164 / 0.167-0.174: recomputed for every type in the patch form
-        c->elem_geo = elem_geo_default(elem_type, want_patch);
-#ifdef FEP_ABLATION
-        if (const char* ge = fep_tune("FEP_ELEM_GEO")) c->elem_geo = std::strcmp(ge, "0") != 0;
-        if (const char* lp = fep_tune("FEP_ELEM_LDS_PAD")) c->lds_pad = std::max(0, std::atoi(lp));
-#endif
+        FEP_TRY(upload(c, &c->xy, xy.data(), (int64_t)xy.size()));
     }
     // node -> incident (element, local node) lists: force gather of the COO route and fep_transform_*
-    CK(upload(&c->iptr, S.iptr.data(), (int64_t)S.iptr.size()));
-    CK(upload(&c->ilist, S.ilist.data(), (int64_t)S.ilist.size()));
-    int elem_eb = 1;
-    // Workgroup shape of the patch form (threads; lanes per (element, node) pair in phase 2: ElemCfg's JS), fixed per type:
-    //   P2  512 / 1: 56 elements on 512 threads (two workgroups of eight waves per CU instead of four of four: the same waves,
-    //       2.0 instead of 3.2 partials per element with four runs, fix-up kernel -35 %, element kernel +3-12 %): three boxes,
-    //       same session each: 1 M elements 0.653 / 0.681 / 0.724 against 0.700 / 0.713 / 0.716 ms, BASELINE configs[4] 2.61 /
-    //       2.89 / 2.89 against 2.86 / 3.09 / 3.00, K,F-only 0.613 against 0.653
-    //   Q2  256 / 1 (40 elements on 512 threads, 3.5 instead of 5.8 partials per element: 0.76-0.80 against 0.62 ms; 24 elements
-    //       on 384 threads with JS = 2: 0.82-0.83 against 0.62, profiles/r04_ablation.md)
-    patch_shape_default(elem_type, want_patch, c->patch_tpb, c->patch_js);
-    bool shape_forced = false;
-#ifdef FEP_ABLATION
-    if (const char* tpb_env = want_patch ? fep_tune("FEP_PATCH_TPB") : nullptr) {
-        c->patch_tpb = std::atoi(tpb_env);
-        const char* js_env = fep_tune("FEP_PATCH_JS");
-        c->patch_js = js_env ? std::atoi(js_env) : 1;
-        shape_forced = true;
-    }
-#endif
-    const auto elements_per_workgroup = [&]() -> int {
-        const bool g = c->elem_geo;
-        const int tpb = c->patch_tpb, js = c->patch_js;
-#define EBOF(NP, NQ, TPB, JS) if (tpb == TPB && js == JS) return g ? ElemCfg<NP, NQ, true, TPB, JS>::EB : ElemCfg<NP, NQ, false, TPB, JS>::EB
-        switch (elem_type) {
-            case FEP_P1: EBOF(3, 1, 256, 1); break;
-            case FEP_P2: EBOF(6, 7, 256, 1); EBOF(6, 7, 512, 1); break;
-            case FEP_Q1: EBOF(4, 4, 256, 1); break;
-            case FEP_Q2: EBOF(8, 9, 256, 1);
-#ifdef FEP_ABLATION
-                EBOF(8, 9, 384, 2); EBOF(8, 9, 512, 1);
-#endif
-                break;
-            case FEP_P4: EBOF(15, 12, 256, 1);
-#ifdef FEP_ABLATION
-                EBOF(15, 12, 512, 2);
-#endif
-                break;
-        }
-#undef EBOF
-        return 0;                                        // no such instantiation
-    };
-    elem_eb = elements_per_workgroup();
-    if (elem_eb == 0) return FEP_EINVAL;
-    if (!c->p1_node && !c->gn && r == FEP_OK) {
-        if (want_patch) {
-            fep_host::PatchPlan P;
-            fep_host::PatchOptions popt;
-#ifdef FEP_ABLATION
-            if (const char* po = fep_tune("FEP_PATCH_ORDER"))
-                popt.order = std::strcmp(po, "consecutive") == 0 ? 0 : std::strcmp(po, "hilbert") == 0 ? 1 : 2;
-#endif
-            // Q1 (64 elements per patch): 4 runs of 16 measured 6 % faster than 2 of 32; P2 with 56 elements: 4 runs of 14
-            // (1.96 partials per element) 1-3 % faster than 2 of 28 (2.86); with 28 elements 2 runs of 14 (4 of 7: +7 %)
-            popt.runs = (elem_type == FEP_Q1 || c->patch_tpb == 512) ? 4 : 2;
-            // (runs starting on 128-byte boundaries of the point arrays — 16 / gcd(16, n_q) elements — measured no faster and
-            // cost a third more partials: the aligned starts leave short leftovers)
-#ifdef FEP_ABLATION
-            if (const char* pr = fep_tune("FEP_PATCH_RUNS")) popt.runs = std::max(1, std::atoi(pr));
-            if (const char* pa = fep_tune("FEP_PATCH_ALIGN")) popt.align = std::max(1, std::atoi(pa));
-#endif
-            CK(fep_host::build_patch_plan(S, n_p, n_e, n_n, elements_h, coords_h, elem_eb, popt, P));
-            if (r == FEP_OK && !P.ok && c->patch_tpb == 512 && c->patch_js == 1 && !shape_forced) {     // the big patches cannot be built: the small ones
-                c->patch_tpb = 256;                                            // (a forced size is never changed silently)
-                elem_eb = elements_per_workgroup();
-                if (!fep_tune("FEP_PATCH_RUNS")) popt.runs = 2;
-                CK(fep_host::build_patch_plan(S, n_p, n_e, n_n, elements_h, coords_h, elem_eb, popt, P));
-            }
-            if (r == FEP_OK && P.ok && validate_plans) {
-                const int bad = fep_host::validate_patch_plan(P, S, n_p, n_e, n_n, elements_h);
-                if (bad) { std::fprintf(stderr, "[fep] patch plan fails check %d\n", bad); r = FEP_EINVAL; }
-            }
-            if (r == FEP_OK && P.ok) {
-                c->patch = true; c->patch_eb = P.eb; c->n_open = P.n_open; c->n_fopen = P.n_fopen; c->n_patch = P.n_patch;
-                CK(upload(&c->pt_desc, P.pdesc.data(), (int64_t)P.pdesc.size()));
-                CK(upload(&c->pt_pel, P.pel.data(), (int64_t)P.pel.size()));
-                CK(upload(&c->pt_pnodes, P.pnodes.data(), (int64_t)P.pnodes.size()));
-                P.items.push_back(fep_host::U2{0u, 0u});                         // (one pad entry each: element_kernel reads its tables
-                P.fitems.push_back(fep_host::U2{0u, 0u});                        //  at clamped indices, also for a patch without items)
-                CK(upload(&c->pt_items, (const uint2*)P.items.data(), (int64_t)P.items.size()));
-                CK(upload(&c->pt_codes, P.codes.data(), (int64_t)P.codes.size()));
-                CK(upload(&c->pt_fitems, (const uint2*)P.fitems.data(), (int64_t)P.fitems.size()));
-                CK(upload(&c->pt_fcodes, P.fcodes.data(), (int64_t)P.fcodes.size()));
-                CK(upload(&c->pt_fix, (const uint4*)P.fix.data(), (int64_t)P.fix.size()));
-                CK(upload(&c->pt_fixT, (const uint2*)P.fixT.data(), (int64_t)P.fixT.size()));
-                CK(upload(&c->pt_ffix, (const uint4*)P.ffix.data(), (int64_t)P.ffix.size()));
-                CK(upload(&c->pt_plist, P.plist.data(), (int64_t)P.plist.size()));
-#ifdef FEP_ABLATION
-                if (fep_tune("FEP_PHASE_CLK")) {
-                    CK(dmalloc(&c->phase_clk, 12 * P.n_patch));
-                    if (r == FEP_OK) (void)hipMemset(c->phase_clk, 0, (size_t)(12 * P.n_patch) * sizeof(unsigned long long));
-                }
-#endif
-                CK(dmalloc(&c->Pc, 4 * P.n_part));
-                CK(dmalloc(&c->Pf, 2 * P.n_fpart));
-                if (c->verbose)
-                    std::fprintf(stderr, "[fep] patch plan: %lld patches of <= %d elements, %zu items (<= %d per patch), %lld open blocks of %lld, "
-                                 "%lld partials (%.2f per element), %lld open nodes\n", (long long)P.n_patch, P.eb, P.items.size(), P.max_items,
-                                 (long long)P.n_open, (long long)c->n_blk, (long long)P.n_part, (double)P.n_part / (double)n_e,
-                                 (long long)P.n_fopen);
-            }
-        }
-        c->n_count_blocks = c->patch ? (int)c->n_patch : (int)grid_for(n_e, elem_eb);
-    }
-    if (!c->patch && shape_forced && c->patch_tpb != 256) r = r == FEP_OK ? FEP_ESTATE : r;        // (a forced plan that could not be built)
-    if (!c->patch) { c->patch_tpb = 256; c->patch_js = 1; }
-    if (!c->patch) {
-        CK(upload(&c->segptr, S.segptr.data(), (int64_t)S.segptr.size()));
-        CK(upload(&c->meta, S.meta.data(), (int64_t)S.meta.size()));
-    }
-    if (!c->p1_node && !c->gn && !c->patch) {
-        // measured at ~1 M points per type (tools/elem_bench.py): the element-major layout pays for the 15-node element only
-        // (P4: step 1.47 -> 1.35 ms; P2 0.96 -> 1.06, Q2 0.82 -> 0.94, Q1 0.22 -> 0.26: their stores lose coalescing)
-        c->kc_aos = elem_type == FEP_P4;
-#ifdef FEP_ABLATION
-        if (const char* kl = fep_tune("FEP_KC_LAYOUT")) c->kc_aos = std::strcmp(kl, "aos") == 0;
-        if (const char* cg = fep_tune("FEP_CSR_GATHERS")) c->csr_gathers = std::atoi(cg);
-#endif
-        if ((int64_t)sym_block_count(n_p) * n_e >= (int64_t)1 << 30) r = FEP_ERANGE;     // 2 * position fits int32
-        {   // element_kernel stores half of the symmetric K_e: re-address the contributions (block, transposed)
-            std::vector<int32_t> perm_sym(S.perm.size());
-            for (size_t i = 0; i < S.perm.size(); ++i) {
-                const int64_t v = S.perm[i];
-                const int ab = (int)(v / n_e);
-                const int64_t e = v - (int64_t)ab * n_e;
-                int idx; bool tr;
-                sym_block_index(n_p, ab / n_p, ab % n_p, idx, tr, c->kc_aos);
-                const int64_t pos = c->kc_aos ? e * sym_block_count(n_p) + idx : (int64_t)idx * n_e + e;
-                perm_sym[i] = (int32_t)(2 * pos + (tr ? 1 : 0));
-            }
-            perm_sym.resize(perm_sym.size() + 4, 0);                    // csr_reduce_pk_kernel reads the addresses four at a time
-            CK(upload(&c->perm, perm_sym.data(), (int64_t)perm_sym.size()));
-            // one 8-byte descriptor per block, if its fields fit (count < 256, degree and slot < 4096)
-            std::vector<uint2> pkc((size_t)c->n_blk);
-            bool fits = fep_tune("FEP_CSR_UNPACKED") == nullptr;
-            for (int64_t b = 0; b < c->n_blk && fits; ++b) {
-                const uint32_t len = (uint32_t)(S.segptr[b + 1] - S.segptr[b]), deg = S.meta[b] >> 16, slot = S.meta[b] & 0x7fffu;
-                fits = len < 256 && deg < 4096 && slot < 4096;
-                pkc[b] = make_uint2((uint32_t)S.segptr[b], len | (deg << 8) | (slot << 20));
-            }
-            if (fits) CK(upload(&c->pkc, pkc.data(), (int64_t)pkc.size()));
-        }
-        CK(upload(&c->tstart, tstart_all.data(), (int64_t)tstart_all.size()));
-        c->n_wg_p1 = (int)tstart_all.size() - 1;
-        CK(dmalloc(&c->Kc, 4 * (int64_t)sym_block_count(n_p) * n_e));
-        CK(dmalloc(&c->fe, 2 * (int64_t)n_p * n_e));
-    }
-    CK(dmalloc(&c->blk_counts, c->n_count_blocks));
-#undef CK
-    if (r == FEP_OK) {
-#define CALL(NP, NQ) r = launch_geometry<NP, NQ>(c)
-        switch (elem_type) {
-            case FEP_P1: CALL(3, 1); break;
-            case FEP_P2: CALL(6, 7); break;
-            case FEP_Q1: CALL(4, 4); break;
-            case FEP_Q2: CALL(8, 9); break;
-            case FEP_P4: CALL(15, 12); break;
-        }
-#undef CALL
-    }
-    if (r == FEP_OK && hipDeviceSynchronize() != hipSuccess) { g_last_hip = (int)hipGetLastError(); r = FEP_EHIP; }
-    if (r != FEP_OK) return r;                          // the caller destroys the partial context
+    FEP_TRY(upload(c, &c->iptr, S.iptr.data(), (int64_t)S.iptr.size()));
+    FEP_TRY(upload(c, &c->ilist, S.ilist.data(), (int64_t)S.ilist.size()));
+    // COO route: tiles of whole nodes with at most kBlock node-pair blocks (csr_reduce_kernel's work units; a node of more
+    // blocks is refused on every route)
+    std::vector<int32_t> tstart;
+    FEP_TRY(fep_host::row_tiles(S, n_n, kBlock, tstart));
+    FEP_TRY(choose_route(c, MeshIn{S, elements_h, coords_h, dhatp1_h, dhatp2_h, wf_h, env_now("FEP_VALIDATE_PLAN") != nullptr},
+                         tstart));
+    FEP_TRY(dmalloc(c, &c->blk_counts, c->n_count_blocks));
+    FEP_TRY(launch_geometry(c));
+    if (hipDeviceSynchronize() != hipSuccess) { g_last_hip = (int)hipGetLastError(); return FEP_EHIP; }
     *ctx_out = c;
     return FEP_OK;
 }
@@ -814,16 +899,18 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
     auto b = [](bool v) { return v ? "true" : "false"; };
     char tmp[256];
-    if (c->p1_node && c->p1_lds) {
+    if (c->route == Route::P1Node && c->p1_lds) {
         if (which == 1 && c->p1_fused && c->fused_mode >= 1)
             std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", c->tile, b(c->p1_fused_rng), b(c->p1_dma));
         else
             std::snprintf(tmp, sizeof tmp, "p1_point_kernel + p1_node_lds_kernel<%d, %s, 1, %s>", c->tile, b(c->p1_rng), b(c->p1_pk));
-    } else if (c->p1_node) {
+    } else if (c->route == Route::P1Node) {
         std::snprintf(tmp, sizeof tmp, "p1_point_kernel + p1_node_kernel");
-    } else if (c->gn) {
+#ifdef FEP_ABLATION
+    } else if (c->route == Route::GenNode) {
         std::snprintf(tmp, sizeof tmp, "point_kernel<%d, %d> + node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, c->n_p, c->n_q, c->gn_tile);
-    } else if (c->patch) {
+#endif
+    } else if (c->route == Route::Patch) {
         std::snprintf(tmp, sizeof tmp, "element_kernel<%d, %d, true, %s, true, %d, %d> + fixup_kernel", c->n_p, c->n_q, b(c->elem_geo),
                       c->patch_tpb, c->patch_js);
     } else {
@@ -834,6 +921,18 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     return FEP_OK;
 }
 
+// The two-kernel node routes pass ds / s from the point kernel to the assembly kernel through HBM: the internal ds (want_ds)
+// / s (want_s) scratch for callers that want K / F without them, allocated once (refused while `st` is being captured)
+static int point_scratch(fep_ctx* c, hipStream_t st, bool want_ds, bool want_s) {
+    want_ds = want_ds && !c->ds_int;
+    want_s = want_s && !c->s_int;
+    if (want_ds || want_s) FEP_TRY(scratch_alloc_allowed(st));
+    if (want_ds) FEP_TRY(dmalloc(c, &c->ds_int, 9 * c->n_int));
+    if (want_s) FEP_TRY(dmalloc(c, &c->s_int, 4 * c->n_int));
+    return FEP_OK;
+}
+
+static bool element_route(const fep_ctx* c) { return c->route == Route::Patch || c->route == Route::Coo; }
 extern "C" int fep_ctx_geometry_host(fep_ctx* c, double* dphi1_h, double* dphi2_h, double* weight_h, double* det_h) {
     if (!c) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
@@ -862,14 +961,10 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     HIP_TRY(hipMemcpy(c->eta, eta_h, nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->c, c_h, nb, hipMemcpyHostToDevice));
     c->have_materials = true;
-    // the two-kernel node routes pass ds / s from the point kernel to the assembly kernel through HBM: when the caller
-    // wants K / F without them the scratch must exist before the first fep_step_dev (which may run inside a stream
-    // capture, where allocating is illegal).  P1 contexts with the one-kernel step only need it for accepting calls that
-    // also ask for K / F without ds / s (allocated on first use, outside any capture, by those rare callers).
-    if ((c->p1_node && !c->p1_fused) || c->gn) {
-        if (!c->ds_int) FEP_TRY(dmalloc(&c->ds_int, 9 * c->n_int));
-        if (!c->s_int) FEP_TRY(dmalloc(&c->s_int, 4 * c->n_int));
-    }
+    // the ds / s scratch of the two-kernel node routes must exist before the first fep_step_dev (which may run inside a
+    // stream capture).  P1 contexts with the one-kernel step only need it for accepting calls that also ask for K / F
+    // without ds / s (allocated on first use, outside any capture, by those rare callers).
+    if (!element_route(c) && !(c->route == Route::P1Node && c->p1_fused)) FEP_TRY(point_scratch(c, nullptr, true, true));
     // every parameter constant over the mesh (the reference's demos): the kernels skip the four arrays
     bool uni = fep_tune("FEP_NO_UNIFORM") == nullptr;
     for (int64_t k = 1; uni && k < c->n_int; ++k)
@@ -905,314 +1000,232 @@ static int prof_mark(fep_ctx* c, hipStream_t st) {
     return FEP_OK;
 }
 
-template <int NP, int NQ, bool FROM_U>
+static constexpr size_t kLdsDefault = 64 * 1024;        // dynamic LDS a launch gets without raising the kernel's limit
+static constexpr size_t kLdsNodeLds = 48 * 1024;        // (node_lds_kernel raises it from 48 KiB on)
+
+// Nodes of no element get no block: no kernel writes their force except the COO form's force gather.  Their F is zeroed
+// per call, before mark 0 on the node routes, inside stage A on the patch route (in_stage_a).
+static int zero_orphan_forces(fep_ctx* c, hipStream_t st, double* f_out, bool in_stage_a) {
+    if (!c->has_orphans || !f_out || c->route == Route::Coo || in_stage_a != (c->route == Route::Patch)) return FEP_OK;
+    HIP_TRY(hipMemsetAsync(f_out, 0, (size_t)c->n_dof * sizeof(double), st));
+    return FEP_OK;
+}
+
+// element routes, stage A: element_kernel.  Patch form: phase 3 writes the caller's CSR values / force, fixup_kernel the
+// open rest; COO form: K_e / f_e to HBM (c->Kc, c->fe) when K / F are wanted
+template <bool FROM_U>
 static int launch_element(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept,
-                          double* eout, double* s, double* ds, uint8_t* indp, uint2* blk_counts,
-                          double* Kc, double* fe) {
-    // patch route: Kc / fe carry the caller's CSR values / force (phase 3 writes them, fixup_kernel the open rest)
+                          double* eout, double* s, double* ds, uint8_t* indp, uint2* blk_counts, double* k_data, double* f_out) {
+    const bool patch = c->route == Route::Patch;
+    double* Kc = !patch && k_data ? c->Kc : nullptr;
+    double* fe = !patch && f_out ? c->fe : nullptr;
     const PatchArgs pa{c->pt_desc, c->pt_pel, c->pt_pnodes, c->pt_items, c->pt_codes, c->pt_fitems, c->pt_fcodes, c->Pc, c->Pf,
-                       c->patch ? Kc : nullptr, c->patch ? fe : nullptr
+                       patch ? k_data : nullptr, patch ? f_out : nullptr
 #ifdef FEP_ABLATION
                        , c->phase_clk
 #endif
     };
-    (void)pa;
-#define ELEM_LAUNCH_T(GEO, PATCH, TPB, JS)                                                                               \
-    do {                                                                                                                 \
-        if (c->patch_eb != 0 && c->patch_eb != ElemCfg<NP, NQ, GEO, TPB, JS>::EB) return FEP_ESTATE;                    \
-        hipLaunchKernelGGL((element_kernel<NP, NQ, FROM_U, GEO, PATCH, TPB, JS>),                                       \
-                           dim3(PATCH ? (unsigned)c->n_patch : grid_for(c->n_e, ElemCfg<NP, NQ, GEO, TPB, JS>::EB)),       \
-                           dim3(TPB), (size_t)c->lds_pad, st, c->n_e,                                                   \
-                           c->elem, c->dphi1, c->dphi2, c->weight, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear,   \
-                           c->bulk, c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk_counts,                       \
-                           PATCH ? nullptr : Kc, PATCH ? nullptr : fe, c->kc_aos ? 1 : 0, pa);                          \
-    } while (0)
-#ifdef FEP_ABLATION
-#define ELEM_GEO_BOTH(PATCH, TPB, JS) do { if (c->elem_geo) ELEM_LAUNCH_T(true, PATCH, TPB, JS); else ELEM_LAUNCH_T(false, PATCH, TPB, JS); } while (0)
-#else       // the product instantiates ONE geometry form per element type and form of the route
-#define ELEM_GEO_BOTH(PATCH, TPB, JS)                                                                                    \
-    do {                                                                                                                 \
-        constexpr bool G = elem_geo_default(NP == 3 ? FEP_P1 : NP == 6 ? FEP_P2 : NP == 4 ? FEP_Q1 : NP == 8 ? FEP_Q2 : FEP_P4, PATCH); \
-        if (c->elem_geo != G) return FEP_ESTATE;                                                                         \
-        ELEM_LAUNCH_T(G, PATCH, TPB, JS);                                                                                \
-    } while (0)
-#endif
-#define ELEM_PATCH(TPB, JS) ELEM_GEO_BOTH(true, TPB, JS)
-    const int shape = c->patch_tpb * 8 + c->patch_js;
-    if (!c->patch) ELEM_GEO_BOTH(false, kBlock, 1);
-    else if (shape == 256 * 8 + 1) ELEM_PATCH(256, 1);
-    else if (NP == 6 && shape == 512 * 8 + 1) { if constexpr (NP == 6) ELEM_PATCH(512, 1); }
-#ifdef FEP_ABLATION
-    else if (NP == 15 && shape == 512 * 8 + 2) { if constexpr (NP == 15) ELEM_PATCH(512, 2); }
-    else if (NP == 8 && shape == 512 * 8 + 1) { if constexpr (NP == 8) ELEM_PATCH(512, 1); }
-    else if (NP == 8 && shape == 384 * 8 + 2) { if constexpr (NP == 8) ELEM_PATCH(384, 2); }
-#endif
-    else return FEP_ESTATE;
-#undef ELEM_PATCH
-#undef ELEM_GEO_BOTH
-#undef ELEM_LAUNCH_T
+    FEP_TRY(elem_shape(c->elem_type, patch, c->elem_geo, c->patch_tpb, c->patch_js, [&](auto et, auto pf, auto geo, auto tpb_c, auto js_c) {
+        using ET = decltype(et);
+        constexpr bool PATCH = decltype(pf)::value, GEO = decltype(geo)::value;
+        constexpr int TPB = decltype(tpb_c)::value, JS = decltype(js_c)::value;
+        using Cfg = ElemCfg<ET::NP, ET::NQ, GEO, TPB, JS>;
+        if (c->patch_eb != 0 && c->patch_eb != Cfg::EB) return FEP_ESTATE;
+        hipLaunchKernelGGL((element_kernel<ET::NP, ET::NQ, FROM_U, GEO, PATCH, TPB, JS>),
+                           dim3(PATCH ? (unsigned)c->n_patch : grid_for(c->n_e, Cfg::EB)), dim3(TPB), (size_t)c->lds_pad, st, c->n_e,
+                           c->elem, c->dphi1, c->dphi2, c->weight, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear,
+                           c->bulk, c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk_counts, Kc, fe, c->kc_aos ? 1 : 0, pa);
+        return FEP_OK;
+    }));
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
 
-static int launch_counts(fep_ctx* c, hipStream_t st, unsigned long long* counts_d) {
-    if (!counts_d) return FEP_OK;
-    hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, c->n_count_blocks, c->blk_counts, counts_d);
+// COO form, stage B: K_e blocks -> CSR values (the force gather rides in the reduce kernel's launch: the workgroups past
+// the last tile take 256 nodes each; so does the counter sum).  *f_due: F is still to be gathered (stage C)
+static int launch_reduce(fep_ctx* c, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d,
+                         bool* counted, bool* f_due) {
+    *f_due = f_out && !k_data;
+    if (!k_data) return FEP_OK;
+    ForceArgs fa{c->n_n, c->iptr, c->ilist, c->fe, f_out};
+    const unsigned grid = (unsigned)c->n_wg_p1 + (counts_d ? 1u : 0u) + (f_out ? grid_for(c->n_n, kBlock) : 0u);
+    auto reduce = [&](auto gathers) {
+        hipLaunchKernelGGL(csr_reduce_kernel<decltype(gathers)::value>, dim3(grid), dim3(kBlock), 0, st,
+                           c->n_wg_p1, c->tstart, c->segptr, c->perm, c->meta, c->Kc, k_data, c->n_count_blocks,
+                           c->blk_counts, counts_d, fa);
+    };
+    if (c->pkc)
+        hipLaunchKernelGGL(csr_reduce_pk_kernel, dim3(grid), dim3(kBlock), 0, st, c->n_wg_p1,
+                           c->tstart, c->pkc, c->perm, c->Kc, k_data, c->n_count_blocks, c->blk_counts, counts_d, fa);
+#ifdef FEP_ABLATION
+    else if (c->csr_gathers == 2) reduce(int_c<2>{});
+    else if (c->csr_gathers == 6) reduce(int_c<6>{});
+    else if (c->csr_gathers == 8) reduce(int_c<8>{});
+#endif
+    else reduce(int_c<4>{});                             // (descriptor fields too wide for the packed form: four gathers in flight)
+    HIP_TRY(hipGetLastError());
+    *counted = counts_d != nullptr;
+    return FEP_OK;
+}
+
+// COO form, stage C: the force gather when the reduce kernel did not take it
+static int launch_force(fep_ctx* c, hipStream_t st, double* f_out) {
+    hipLaunchKernelGGL(force_reduce_kernel, dim3(grid_for(c->n_n, kBlock)), dim3(kBlock), 0, st,
+                       c->n_n, c->iptr, c->ilist, c->fe, f_out);
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
 
-// COO route, numeric phase: K_e blocks -> CSR values, f_e pairs -> nodal force (the force gather rides in the reduce
-// kernel's launch: the workgroups past the last tile take 256 nodes each)
-static int launch_reduce(fep_ctx* c, hipStream_t st, double* k_data, double* f_out,
-                         unsigned long long* counts_d = nullptr, bool* counts_done = nullptr) {
-    if (counts_done) *counts_done = false;
-    FEP_TRY(prof_mark(c, st));
-    bool force_done = false;
-    if (k_data) {
-        ForceArgs fa{c->n_n, c->iptr, c->ilist, c->fe, f_out};
-        const unsigned grid = (unsigned)c->n_wg_p1 + (counts_d ? 1u : 0u) + (f_out ? grid_for(c->n_n, kBlock) : 0u);
-#define CSR_REDUCE(G)                                                                                                    \
-    hipLaunchKernelGGL(csr_reduce_kernel<G>, dim3(grid), dim3(kBlock), 0, st,                                            \
-                       c->n_wg_p1, c->tstart, c->segptr, c->perm, c->meta, c->Kc, k_data, c->n_count_blocks,             \
-                       c->blk_counts, counts_d, fa)
-        if (c->pkc)
-            hipLaunchKernelGGL(csr_reduce_pk_kernel, dim3(grid), dim3(kBlock), 0, st, c->n_wg_p1,
-                               c->tstart, c->pkc, c->perm, c->Kc, k_data, c->n_count_blocks, c->blk_counts, counts_d, fa);
-        else
-#ifdef FEP_ABLATION
-        switch (c->csr_gathers) {
-            case 2: CSR_REDUCE(2); break;
-            case 6: CSR_REDUCE(6); break;
-            case 8: CSR_REDUCE(8); break;
-            default: CSR_REDUCE(4); break;
-        }
-#else
-        CSR_REDUCE(4);                                   // (descriptor fields too wide for the packed form: four gathers in flight)
-#endif
-#undef CSR_REDUCE
-        HIP_TRY(hipGetLastError());
-        if (counts_done) *counts_done = counts_d != nullptr;
-        force_done = f_out != nullptr;
-    }
-    FEP_TRY(prof_mark(c, st));
-    if (f_out && !force_done) {
-        hipLaunchKernelGGL(force_reduce_kernel, dim3(grid_for(c->n_n, kBlock)), dim3(kBlock), 0, st,
-                           c->n_n, c->iptr, c->ilist, c->fe, f_out);
-        HIP_TRY(hipGetLastError());
-    }
-    FEP_TRY(prof_mark(c, st));
-    return FEP_OK;
-}
-
-// patch route, second kernel: open blocks / open nodes from the patches' partials (+ the branch counters on the side)
-static int launch_fixup(fep_ctx* c, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d, bool* counts_done) {
-    if (counts_done) *counts_done = false;
-    FEP_TRY(prof_mark(c, st));
+// patch form, stage B: open blocks / open nodes from the patches' partials (+ the branch counters on the side)
+static int launch_fixup(fep_ctx* c, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d, bool* counted) {
     const unsigned nb_k = k_data ? grid_for(c->n_open, kBlock) : 0u;
     const unsigned nb_f = f_out ? grid_for(c->n_fopen, kBlock) : 0u;
     const unsigned grid = nb_k + nb_f + (counts_d ? 1u : 0u);
-    if (grid > 0) {
-        hipLaunchKernelGGL(fixup_kernel, dim3(grid), dim3(kBlock), 0, st, (int)nb_k, c->n_open, c->pt_fix, c->pt_fixT, c->n_fopen, c->pt_ffix,
-                           c->pt_plist, c->Pc, c->Pf, k_data, f_out, c->n_count_blocks, c->blk_counts, counts_d);
-        HIP_TRY(hipGetLastError());
-        if (counts_done) *counts_done = counts_d != nullptr;
-    }
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(prof_mark(c, st));
+    if (grid == 0) return FEP_OK;
+    hipLaunchKernelGGL(fixup_kernel, dim3(grid), dim3(kBlock), 0, st, (int)nb_k, c->n_open, c->pt_fix, c->pt_fixT, c->n_fopen, c->pt_ffix,
+                       c->pt_plist, c->Pc, c->Pf, k_data, f_out, c->n_count_blocks, c->blk_counts, counts_d);
+    HIP_TRY(hipGetLastError());
+    *counted = counts_d != nullptr;
     return FEP_OK;
 }
 
-// P1 node route, assembly kernel (reads ds / s, writes CSR values and nodal force)
-// `counts_d` != NULL: the assembly kernel also sums the point kernel's per-workgroup branch counters
-// (*counts_done tells the caller whether that happened)
+// P1 node route, stage B: the assembly kernel (reads ds / s, writes CSR values and nodal force; with `counts_d` it also
+// sums the point kernel's per-workgroup branch counters: *counted)
 static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                          unsigned long long* counts_d, bool* counts_done) {
-    FEP_TRY(prof_mark(c, st));
-    if (counts_done) *counts_done = false;
-    if ((k_data && ds) || (f_out && s)) {
+                          unsigned long long* counts_d, bool* counted) {
+    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
+    if (!k_data) ds = nullptr;
+    if (!f_out) s = nullptr;
+    const int n_wg = c->n_wg_p1;
+    const unsigned grid = 8 * ((n_wg + 7) / 8);
 #ifdef FEP_ABLATION
-        if (c->p1_fused && c->asm_from_nodes) {
-            // opt-in (FEP_P1_ASM=nodes): assembly-only form of the one-kernel step, geometry from the tile's LDS-staged nodes
-            // instead of the 48-byte record per staged element (same values bit for bit; 25 % fewer bytes but one barrier
-            // and the geometry arithmetic more: 72.0 against 66.4 us at 1 M elements, profiles/r02_ablation.md)
-            const size_t lds_stage = (((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * 2 + 15) & ~(size_t)15) +
-                                     (size_t)c->lds_NL * 2 * sizeof(double2);
-            const size_t lds = std::max(lds_stage, (size_t)c->tile * 3 * sizeof(double2));
-            const int n_wg = c->n_wg_p1;
-            const int chunk = (n_wg + 7) / 8;
-#define ASM4(RNG, EPT, NPT)                                                                                              \
-    do {                                                                                                                 \
-        if (lds > 64 * 1024)                                                                                             \
-            HIP_TRY(hipFuncSetAttribute((const void*)p1_fused_kernel<false, 256, RNG, EPT, NPT, true>,                   \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-        hipLaunchKernelGGL((p1_fused_kernel<false, 256, RNG, EPT, NPT, true>), dim3(8 * chunk), dim3(256), lds, st,      \
-                           c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist, (const int4*)c->wg_rng,        \
-                           c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes, c->pk, c->tdesc, c->xy, c->p1tab,          \
-                           (const double*)nullptr, make_e0(nullptr), (const double*)nullptr, c->shear, c->bulk, c->eta,  \
-                           c->c, c->matu, (double*)nullptr, (double*)nullptr, (double*)nullptr, (uint8_t*)nullptr,       \
-                           k_data, f_out, n_wg, (unsigned long long*)nullptr, k_data ? ds : (const double*)nullptr,      \
-                           f_out ? s : (const double*)nullptr, c->n_count_blocks, c->blk_counts, counts_d);              \
-    } while (0)
-            if (c->lds_L > 256 || c->lds_NL > 256) return FEP_ESTATE;
-            if (c->p1_fused_rng) ASM4(true, 1, 1); else ASM4(false, 1, 1);
-#undef ASM4
-            if (counts_done) *counts_done = counts_d != nullptr;
-        } else
-#endif
-        if (c->p1_lds) {
-            // operands + codes while gathering, then the same LDS holds the tile's output (4*TPB values + forces)
-            const size_t lds = std::max((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * sizeof(uint16_t),
-                                        (size_t)c->tile * 3 * sizeof(double2));
-            const int n_wg = c->n_wg_p1;
-            const int chunk = (n_wg + 7) / 8;
-            if (c->verbose) {
-                static bool once = false;
-                if (!once) {
-                    once = true;
-                    std::fprintf(stderr, "[fep] p1 assembly kernel: %d tiles of <= %d blocks, staged elements <= %d, codes <= %d, "
-                                 "LDS %zu bytes per workgroup\n", n_wg, c->tile, c->lds_L, c->lds_C, lds);
-                }
-            }
-#define NODE_LDS3(TPB, RNG, EPT, PK)                                                                                     \
-    do {                                                                                                                 \
-        if (lds > 64 * 1024)                                                                                             \
-            HIP_TRY(hipFuncSetAttribute((const void*)p1_node_lds_kernel<TPB, RNG, EPT, PK>,                              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-        hipLaunchKernelGGL((p1_node_lds_kernel<TPB, RNG, EPT, PK>), dim3(8 * chunk), dim3(TPB), lds, st,                 \
-                           c->n_e, c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol, c->wg_elist,              \
-                           (const int4*)c->wg_rng, c->pk, c->tdesc, c->geo, k_data ? ds : nullptr,                       \
-                           f_out ? s : nullptr, k_data, f_out, n_wg, c->n_count_blocks, c->blk_counts, counts_d);        \
-    } while (0)
-#ifdef FEP_ABLATION
-#define NODE_LDS2(TPB, RNG, EPT) do { if (c->p1_pk) NODE_LDS3(TPB, RNG, EPT, true); else NODE_LDS3(TPB, RNG, EPT, false); } while (0)
-#else       // (a plan without packed descriptors never reaches the node route in the product: fep_ctx_create takes the element route)
-#define NODE_LDS2(TPB, RNG, EPT) do { if (!c->p1_pk) return FEP_ESTATE; NODE_LDS3(TPB, RNG, EPT, true); } while (0)
-#endif
-#define NODE_LDS(TPB)                                                                                                    \
-    do {                                                                                                                 \
-        if (c->lds_L > TPB) return FEP_ESTATE;          /* one staged element per lane (fep_host.h) */                  \
-        if (c->p1_rng) NODE_LDS2(TPB, true, 1); else NODE_LDS2(TPB, false, 1);                                           \
-    } while (0)
-#ifdef FEP_ABLATION
-            if (c->tile == 128) NODE_LDS(128); else
-#endif
-            NODE_LDS(256);                 // tiles of 128 / 512 blocks were measured slower (profiles/r01_ablation.md)
-#undef NODE_LDS
-#undef NODE_LDS2
-#undef NODE_LDS3
-            if (counts_done) *counts_done = counts_d != nullptr;
-        } else {
-#ifdef FEP_ABLATION
-            hipLaunchKernelGGL(p1_node_kernel, dim3(grid_for(c->n_blk, kBlock)), dim3(kBlock), 0, st,
-                               c->n_blk, c->n_e, c->segptr, c->perm2, c->meta, c->ncol, c->geo,
-                               k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out);
+    if (c->p1_fused && c->asm_from_nodes) {
+        // opt-in (FEP_P1_ASM=nodes): assembly-only form of the one-kernel step, geometry from the tile's LDS-staged nodes
+        // instead of the 48-byte record per staged element (same values bit for bit; 25 % fewer bytes but one barrier
+        // and the geometry arithmetic more: 72.0 against 66.4 us at 1 M elements, profiles/r02_ablation.md)
+        const size_t lds_stage = (((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * 2 + 15) & ~(size_t)15) +
+                                 (size_t)c->lds_NL * 2 * sizeof(double2);
+        const size_t lds = std::max(lds_stage, (size_t)c->tile * 3 * sizeof(double2));
+        if (c->lds_L > 256 || c->lds_NL > 256) return FEP_ESTATE;
+        FEP_TRY(with_bool(c->p1_fused_rng, [&](auto rng) {
+            return launch_lds(p1_fused_kernel<false, 256, decltype(rng)::value, 1, 1, true>, grid, 256, lds, kLdsDefault, st,
+                              c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist, (const int4*)c->wg_rng,
+                              c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes, c->pk, c->tdesc, c->xy, c->p1tab,
+                              (const double*)nullptr, make_e0(nullptr), (const double*)nullptr, c->shear, c->bulk, c->eta,
+                              c->c, c->matu, (double*)nullptr, (double*)nullptr, (double*)nullptr, (uint8_t*)nullptr,
+                              k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, c->n_count_blocks, c->blk_counts, counts_d);
+        }));
+        *counted = counts_d != nullptr;
+        return FEP_OK;
+    }
+    if (!c->p1_lds) {
+        hipLaunchKernelGGL(p1_node_kernel, dim3(grid_for(c->n_blk, kBlock)), dim3(kBlock), 0, st,
+                           c->n_blk, c->n_e, c->segptr, c->perm2, c->meta, c->ncol, c->geo, ds, s, k_data, f_out);
+        HIP_TRY(hipGetLastError());
+        return FEP_OK;
+    }
 #else
-            return FEP_ESTATE;
+    if (!c->p1_lds) return FEP_ESTATE;
 #endif
+    // operands + codes while gathering, then the same LDS holds the tile's output (4*TPB values + forces)
+    const size_t lds = std::max((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * sizeof(uint16_t),
+                                (size_t)c->tile * 3 * sizeof(double2));
+    if (c->verbose) {
+        static bool once = false;
+        if (!once) {
+            once = true;
+            std::fprintf(stderr, "[fep] p1 assembly kernel: %d tiles of <= %d blocks, staged elements <= %d, codes <= %d, "
+                         "LDS %zu bytes per workgroup\n", n_wg, c->tile, c->lds_L, c->lds_C, lds);
         }
-        HIP_TRY(hipGetLastError());
     }
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(prof_mark(c, st));
+    // tiles of 128 blocks (ablation build, FEP_P1_TILE) or 256 (128 / 512 were measured slower, profiles/r01_ablation.md)
+    FEP_TRY(with_ablation_bool<false>(c->tile == 128, [&](auto t128) {
+        constexpr int TPB = decltype(t128)::value ? 128 : 256;
+        if (c->lds_L > TPB) return FEP_ESTATE;          // one staged element per lane (fep_host.h)
+        return with_bool(c->p1_rng, [&](auto rng) {
+            // (the product's node route always has packed descriptors: setup_p1_node)
+            return with_ablation_bool<true>(c->p1_pk, [&](auto pk) {
+                return launch_lds(p1_node_lds_kernel<TPB, decltype(rng)::value, 1, decltype(pk)::value>, grid, TPB, lds,
+                                  kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol,
+                                  c->wg_elist, (const int4*)c->wg_rng, c->pk, c->tdesc, c->geo, ds, s, k_data, f_out, n_wg,
+                                  c->n_count_blocks, c->blk_counts, counts_d);
+            });
+        });
+    }));
+    *counted = counts_d != nullptr;
     return FEP_OK;
 }
 
 #ifdef FEP_ABLATION
-// node route for P2 / Q1 / Q2: assembly kernel
-static int launch_gn_node(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                          unsigned long long* counts_d, bool* counts_done) {
-    FEP_TRY(prof_mark(c, st));
-    if (counts_done) *counts_done = false;
-    if ((k_data && ds) || (f_out && s)) {
-        const int n_wg = (int)grid_for(c->n_blk, c->gn_tile);
-        const int chunk = (n_wg + 7) / 8;
-        const size_t lds = c->gn_lds;
-#define GN(NP, NQ, TPB)                                                                                                  \
-    do {                                                                                                                 \
-        if (lds > 48 * 1024)                                                                                             \
-            HIP_TRY(hipFuncSetAttribute((const void*)node_lds_kernel<NP, NQ, TPB>,                                       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-        hipLaunchKernelGGL((node_lds_kernel<NP, NQ, TPB>), dim3(8 * chunk), dim3(TPB), lds, st, c->n_blk, c->n_e,        \
-                           c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol, c->wg_elist, c->elem, c->xy,      \
-                           c->dh1, c->dh2, c->wf, k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out, n_wg,       \
-                           c->n_count_blocks, c->blk_counts, counts_d);                                                  \
-    } while (0)
-        const bool t256 = c->gn_tile == 256;
-        switch (c->elem_type) {
-            case FEP_P2: if (t256) GN(6, 7, 256); else GN(6, 7, 128); break;
-            case FEP_Q1: if (t256) GN(4, 4, 256); else GN(4, 4, 128); break;
-            case FEP_Q2: if (t256) GN(8, 9, 256); else GN(8, 9, 128); break;
-            default: return FEP_EINVAL;
-        }
-#undef GN
-        HIP_TRY(hipGetLastError());
-        if (counts_done) *counts_done = counts_d != nullptr;
-    }
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(prof_mark(c, st));
-    return FEP_OK;
-}
-
-template <int NP, int NQ>
+// GenNode route, stage A: point_kernel
 static int launch_point(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept, double* eout,
                         double* s, double* ds, uint8_t* indp, uint2* blk) {
-    hipLaunchKernelGGL((point_kernel<NP, NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, st, c->n_e, c->elem,
-                       c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk);
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
+        else {
+            hipLaunchKernelGGL((point_kernel<ET::NP, ET::NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, st, c->n_e,
+                               c->elem, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
+                               accept, eout, s, ds, indp, blk);
+            return FEP_OK;
+        }
+    }));
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
 
+// GenNode route, stage B: node_lds_kernel
+static int launch_gn_node(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
+                          unsigned long long* counts_d, bool* counted) {
+    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
+    const int n_wg = (int)grid_for(c->n_blk, c->gn_tile);
+    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
+        else return with_bool(c->gn_tile == 256, [&](auto t256) {
+            constexpr int TPB = decltype(t256)::value ? 256 : 128;
+            return launch_lds(node_lds_kernel<ET::NP, ET::NQ, TPB>, grid, TPB, c->gn_lds, kLdsNodeLds, st, c->n_blk, c->n_e,
+                              c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol, c->wg_elist, c->elem, c->xy,
+                              c->dh1, c->dh2, c->wf, k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out, n_wg,
+                              c->n_count_blocks, c->blk_counts, counts_d);
+        });
+    }));
+    *counted = counts_d != nullptr;
+    return FEP_OK;
+}
 #endif  // FEP_ABLATION
 
-// P1, one kernel per step (non-accepting calls with K and/or F wanted): p1_fused_kernel
+// P1, one kernel per step (non-accepting calls with K and/or F wanted): p1_fused_kernel, then the counter sum
 static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, const double* ep, double* eout, double* s,
                            double* ds, uint8_t* indp, double* k_data, double* f_out, unsigned long long* counts_d) {
     const bool dma = c->p1_dma;
-    (void)dma;
     const size_t Cp = dma ? ((size_t)c->lds_C + 127) & ~(size_t)127 : (size_t)c->lds_C;
     const size_t NLp = dma ? ((size_t)c->lds_NL + 63) & ~(size_t)63 : (size_t)c->lds_NL;
     const size_t lds_stage = (((size_t)c->lds_L * 15 * sizeof(double) + Cp * 2 + 15) & ~(size_t)15) + NLp * 2 * sizeof(double2);
     const size_t lds = std::max(lds_stage, (size_t)c->tile * 3 * sizeof(double2));
     const int n_wg = c->n_wg_p1;
-    const int chunk = (n_wg + 7) / 8;
-    const bool full = eout || s || ds || indp;
-#ifdef FEP_ABLATION
-#define FUSED4(FULL, RNG, EPT, NPT)  do { if (dma) FUSED5(FULL, RNG, EPT, NPT, true); else FUSED5(FULL, RNG, EPT, NPT, false); } while (0)
-#else
-#define FUSED4(FULL, RNG, EPT, NPT)  FUSED5(FULL, RNG, EPT, NPT, false)
-#endif
-#define FUSED6(FULL, RNG, EPT, NPT, DMA, TPB)                                                                                 \
-    do {                                                                                                                 \
-        if (lds > 64 * 1024)                                                                                             \
-            HIP_TRY(hipFuncSetAttribute((const void*)p1_fused_kernel<FULL, TPB, RNG, EPT, NPT, false, DMA>,              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-        hipLaunchKernelGGL((p1_fused_kernel<FULL, TPB, RNG, EPT, NPT, false, DMA>), dim3(8 * chunk), dim3(TPB), lds, st, \
-                           c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist, (const int4*)c->wg_rng,        \
-                           c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes, c->pk, c->tdesc, c->xy,                   \
-                           c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu, eout, s, ds, indp, k_data,      \
-                           f_out, n_wg, counts_d ? c->slot_counts : (unsigned long long*)nullptr,                        \
-                           (const double*)nullptr, (const double*)nullptr, 0, (const uint2*)nullptr,                     \
-                           (unsigned long long*)nullptr);                                                                \
-    } while (0)
-#ifdef FEP_ABLATION
-#define FUSED5(FULL, RNG, EPT, NPT, DMA) do { if (c->tile == 128) FUSED6(FULL, RNG, EPT, NPT, DMA, 128); else FUSED6(FULL, RNG, EPT, NPT, DMA, 256); } while (0)
-#else
-#define FUSED5(FULL, RNG, EPT, NPT, DMA) FUSED6(FULL, RNG, EPT, NPT, DMA, 256)
-#endif
-#define FUSED3(FULL, RNG) FUSED4(FULL, RNG, 1, 1)      /* L, NL <= threads: one staged element / node per lane (fep_host.h) */
+    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    // L, NL <= threads: one staged element / node per lane (fep_host.h)
     if (c->lds_L > c->tile || c->lds_NL > c->tile) return FEP_ESTATE;
-#ifdef FEP_ABLATION
-    if (full) { if (c->p1_fused_rng) FUSED3(true, true); else FUSED3(true, false); } else
-#else
-    if (full) return FEP_ESTATE;                         // (the product runs the one-kernel step for K,F-only calls: fused_mode 1)
-#endif
-    { if (c->p1_fused_rng) FUSED3(false, true); else FUSED3(false, false); }
-#undef FUSED3
-#undef FUSED4
-#undef FUSED5
-#undef FUSED6
-    HIP_TRY(hipGetLastError());
+    // (the product runs the one-kernel step for K,F-only calls: fused_mode 1)
+    const bool full = eout || s || ds || indp;
+    FEP_TRY(with_ablation_bool<false>(full, [&](auto full_c) {
+        return with_bool(c->p1_fused_rng, [&](auto rng) {
+            return with_ablation_bool<false>(dma, [&](auto dma_c) {
+                return with_ablation_bool<false>(c->tile == 128, [&](auto t128) {
+                    constexpr int TPB = decltype(t128)::value ? 128 : 256;
+                    return launch_lds(p1_fused_kernel<decltype(full_c)::value, TPB, decltype(rng)::value, 1, 1, false, decltype(dma_c)::value>,
+                                      grid, TPB, lds, kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l,
+                                      c->wg_elist, (const int4*)c->wg_rng, c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes,
+                                      c->pk, c->tdesc, c->xy, c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
+                                      eout, s, ds, indp, k_data, f_out, n_wg,
+                                      counts_d ? c->slot_counts : (unsigned long long*)nullptr, (const double*)nullptr,
+                                      (const double*)nullptr, 0, (const uint2*)nullptr, (unsigned long long*)nullptr);
+                });
+            });
+        });
+    }));
     if (counts_d) {
         hipLaunchKernelGGL(counts_finalize_kernel, dim3(1), dim3(256), 0, st, c->slot_counts, counts_d);
         HIP_TRY(hipGetLastError());
@@ -1220,15 +1233,23 @@ static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, c
     return FEP_OK;
 }
 
-// The internal ds / s scratch of the two-kernel routes is allocated on first use.  Allocating is illegal while the
-// stream is being captured into a graph: such a call is refused (FEP_ESTATE) instead of breaking the capture — run the
-// same call once outside the capture first (fep.h, fep_step_dev).
-static int scratch_alloc_allowed(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_OK; }
-    return cs == hipStreamCaptureStatusNone ? FEP_OK : FEP_ESTATE;
+// Stage B of every route but the one-kernel step: the route's assembly kernel (the node routes read ds / s, the element
+// routes stage A's partials / K_e blocks).  *counted: it also summed the branch counters; *f_due: F is still to be
+// gathered (stage C, COO form only)
+static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
+                           unsigned long long* counts_d, bool* counted, bool* f_due) {
+    *counted = *f_due = false;
+    if (c->route == Route::P1Node) return launch_p1_node(c, st, ds, s, k_data, f_out, counts_d, counted);
+#ifdef FEP_ABLATION
+    if (c->route == Route::GenNode) return launch_gn_node(c, st, ds, s, k_data, f_out, counts_d, counted);
+#endif
+    if (c->route == Route::Patch) return launch_fixup(c, st, k_data, f_out, counts_d, counted);
+    return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
 }
 
+// fep_step_dev and fep_assemble_dev record four events per call (fep_ctx_profile_end: three intervals):
+//   mark 0, stage A (point / element kernel), mark 1, stage B (assembly), mark 2, stage C (COO: force gather), mark 3
+// then the branch-counter sum if no kernel took it.
 extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const double* e0_h,
                             double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d,
                             uint8_t* ind_p_d, double* k_data_d, double* f_out_d, int64_t* counts_d) {
@@ -1240,88 +1261,68 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     unsigned long long* cnt = (unsigned long long*)counts_d;
     uint2* blk = cnt ? c->blk_counts : nullptr;
     const E0 e0 = make_e0(e0_h);
-    if ((c->p1_node || c->gn) && c->has_orphans && f_out_d)        // nodes of no element: no block, no lane writes their force
-        HIP_TRY(hipMemsetAsync(f_out_d, 0, (size_t)c->n_dof * sizeof(double), st));
     const bool point_outputs = e_out_d || s_d || ds_d || ind_p_d;
-    if (c->p1_node && c->p1_fused && !accept && (k_data_d || f_out_d) && c->fused_mode > (point_outputs ? 1 : 0)) {
-        FEP_TRY(prof_mark(c, st));
-        FEP_TRY(prof_mark(c, st));                      // profile slots: [0] = 0, [1] = the fused kernel (+ counter sum), [2] = 0
-        FEP_TRY(launch_p1_fused(c, st, u_d, e0, ep_prev_d, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt));
-        FEP_TRY(prof_mark(c, st));
-        FEP_TRY(prof_mark(c, st));
-        return FEP_OK;
+    const bool fused = c->route == Route::P1Node && c->p1_fused && !accept && (k_data_d || f_out_d) &&
+                       c->fused_mode > (point_outputs ? 1 : 0);
+    if (!element_route(c) && !fused) {                  // the assembly kernel reads ds / s from HBM
+        FEP_TRY(point_scratch(c, st, k_data_d && !ds_d, f_out_d && !s_d));
+        if (k_data_d && !ds_d) ds_d = c->ds_int;
+        if (f_out_d && !s_d) s_d = c->s_int;
     }
-    if (c->p1_node) {
-        // the assembly kernel consumes ds / s from HBM: use internal buffers when the caller wants neither
-        if (k_data_d && !ds_d) {
-            if (!c->ds_int) { FEP_TRY(scratch_alloc_allowed(st)); FEP_TRY(dmalloc(&c->ds_int, 9 * c->n_int)); }
-            ds_d = c->ds_int;
-        }
-        if (f_out_d && !s_d) {
-            if (!c->s_int) { FEP_TRY(scratch_alloc_allowed(st)); FEP_TRY(dmalloc(&c->s_int, 4 * c->n_int)); }
-            s_d = c->s_int;
-        }
-        FEP_TRY(prof_mark(c, st));
-        hipLaunchKernelGGL(p1_point_kernel, dim3(grid_for(c->n_e, kBlock)), dim3(kBlock), 0, st,
-                           c->n_e, c->elem, c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
-                           e_out_d, s_d, ds_d, ind_p_d, blk);
-        HIP_TRY(hipGetLastError());
-        bool counted = false;
-        FEP_TRY(launch_p1_node(c, st, ds_d, s_d, k_data_d, f_out_d, cnt, &counted));
-        return counted ? FEP_OK : launch_counts(c, st, cnt);
-    }
-#ifdef FEP_ABLATION
-    if (c->gn) {
-        if (k_data_d && !ds_d) {
-            if (!c->ds_int) { FEP_TRY(scratch_alloc_allowed(st)); FEP_TRY(dmalloc(&c->ds_int, 9 * c->n_int)); }
-            ds_d = c->ds_int;
-        }
-        if (f_out_d && !s_d) {
-            if (!c->s_int) { FEP_TRY(scratch_alloc_allowed(st)); FEP_TRY(dmalloc(&c->s_int, 4 * c->n_int)); }
-            s_d = c->s_int;
-        }
-        FEP_TRY(prof_mark(c, st));
-        switch (c->elem_type) {
-            case FEP_P2: FEP_TRY((launch_point<6, 7>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk))); break;
-            case FEP_Q1: FEP_TRY((launch_point<4, 4>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk))); break;
-            case FEP_Q2: FEP_TRY((launch_point<8, 9>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk))); break;
-            default: return FEP_EINVAL;
-        }
-        bool counted = false;
-        FEP_TRY(launch_gn_node(c, st, ds_d, s_d, k_data_d, f_out_d, cnt, &counted));
-        return counted ? FEP_OK : launch_counts(c, st, cnt);
-    }
-#endif
-    FEP_TRY(prof_mark(c, st));
-    if (c->has_orphans && c->patch && f_out_d)                    // nodes of no element: no item writes their force
-        HIP_TRY(hipMemsetAsync(f_out_d, 0, (size_t)c->n_dof * sizeof(double), st));
-#define CALL(NP, NQ)                                                                                     \
-    FEP_TRY((launch_element<NP, NQ, true>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, \
-                                          c->patch ? k_data_d : (k_data_d ? c->Kc : nullptr),            \
-                                          c->patch ? f_out_d : (f_out_d ? c->fe : nullptr))))
-    bool counted = false;
+    hipStream_t ms = st;                                // stream of marks 1-3 and of stages B and C
 #ifdef FEP_ABLATION
     // FEP_FIX_SIDE=1 — an UPPER BOUND, not a route: fixup_kernel on a side stream, NOT ordered behind this call's element kernel (it
     // adds whatever partials the call before left; K's open blocks are stale), joined at the end: what a perfectly overlapped
     // fix-up could save
-    if (c->patch && fep_tune("FEP_FIX_SIDE")) {
-        static hipStream_t side = nullptr;
-        static hipEvent_t ev_a = nullptr, ev_b = nullptr;
-        if (!side) { HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming)); }
+    const bool fix_side = c->route == Route::Patch && fep_tune("FEP_FIX_SIDE");
+    static hipStream_t side = nullptr;
+    static hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    if (fix_side && !side) { HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming)); }
+#endif
+    bool counted = false, f_due = false;
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
+    FEP_TRY(prof_mark(c, st));
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    if (c->route == Route::P1Node) {
+        if (!fused) {                                   // (the one-kernel step is all stage B)
+            hipLaunchKernelGGL(p1_point_kernel, dim3(grid_for(c->n_e, kBlock)), dim3(kBlock), 0, st,
+                               c->n_e, c->elem, c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu,
+                               accept, e_out_d, s_d, ds_d, ind_p_d, blk);
+            HIP_TRY(hipGetLastError());
+        }
+#ifdef FEP_ABLATION
+    } else if (c->route == Route::GenNode) {
+        FEP_TRY(launch_point(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk));
+    } else if (fix_side) {
         HIP_TRY(hipEventRecord(ev_a, st));
         HIP_TRY(hipStreamWaitEvent(side, ev_a, 0));
-        FEP_TRY(launch_fixup(c, side, k_data_d, f_out_d, cnt, &counted));
+        ms = side;
+#endif
+    } else {
+        FEP_TRY(launch_element<true>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
+    }
+    FEP_TRY(prof_mark(c, ms));
+    if (fused) {
+        FEP_TRY(launch_p1_fused(c, st, u_d, e0, ep_prev_d, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt));
+        counted = true;
+    } else {
+        FEP_TRY(launch_assembly(c, ms, ds_d, s_d, k_data_d, f_out_d, cnt, &counted, &f_due));
+    }
+    FEP_TRY(prof_mark(c, ms));
+    if (f_due) FEP_TRY(launch_force(c, ms, f_out_d));
+    FEP_TRY(prof_mark(c, ms));
+#ifdef FEP_ABLATION
+    if (fix_side) {
         HIP_TRY(hipEventRecord(ev_b, side));
-        DISPATCH_ELEM(c->elem_type, CALL)
+        FEP_TRY(launch_element<true>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
         HIP_TRY(hipStreamWaitEvent(st, ev_b, 0));
-        return counted ? FEP_OK : launch_counts(c, st, cnt);
     }
 #endif
-    DISPATCH_ELEM(c->elem_type, CALL)
-#undef CALL
-    if (c->patch) FEP_TRY(launch_fixup(c, st, k_data_d, f_out_d, cnt, &counted));
-    else FEP_TRY(launch_reduce(c, st, k_data_d, f_out_d, cnt, &counted));
-    return counted ? FEP_OK : launch_counts(c, st, cnt);
+    if (cnt && !counted) {
+        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, c->n_count_blocks, c->blk_counts, cnt);
+        HIP_TRY(hipGetLastError());
+    }
+    return FEP_OK;
 }
 
 extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, const double* s_d,
@@ -1331,31 +1332,19 @@ extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, co
     if (!fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
     hipStream_t st = (hipStream_t)stream;
-    if ((c->p1_node || c->gn) && c->has_orphans && f_out_d)
-        HIP_TRY(hipMemsetAsync(f_out_d, 0, (size_t)c->n_dof * sizeof(double), st));
-    if (c->p1_node) {
-        FEP_TRY(prof_mark(c, st));
-        return launch_p1_node(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, nullptr);
-    }
-#ifdef FEP_ABLATION
-    if (c->gn) {
-        FEP_TRY(prof_mark(c, st));
-        return launch_gn_node(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, nullptr);
-    }
-#endif
-    const E0 e0 = make_e0(nullptr);
+    bool counted = false, f_due = false;
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
     FEP_TRY(prof_mark(c, st));
-    if (c->has_orphans && c->patch && f_out_d)
-        HIP_TRY(hipMemsetAsync(f_out_d, 0, (size_t)c->n_dof * sizeof(double), st));
-#define CALL(NP, NQ)                                                                                         \
-    FEP_TRY((launch_element<NP, NQ, false>(c, st, nullptr, e0, nullptr, 0, nullptr, const_cast<double*>(s_d), \
-                                           const_cast<double*>(ds_d), nullptr, nullptr,                      \
-                                           c->patch ? k_data_d : (k_data_d ? c->Kc : nullptr),               \
-                                           c->patch ? f_out_d : (f_out_d ? c->fe : nullptr))))
-    DISPATCH_ELEM(c->elem_type, CALL)
-#undef CALL
-    if (c->patch) return launch_fixup(c, st, k_data_d, f_out_d, nullptr, nullptr);
-    return launch_reduce(c, st, k_data_d, f_out_d);
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    if (element_route(c))
+        FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s_d),
+                                      const_cast<double*>(ds_d), nullptr, nullptr, k_data_d, f_out_d));
+    FEP_TRY(prof_mark(c, st));
+    FEP_TRY(launch_assembly(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, &counted, &f_due));
+    FEP_TRY(prof_mark(c, st));
+    if (f_due) FEP_TRY(launch_force(c, st, f_out_d));
+    FEP_TRY(prof_mark(c, st));
+    return FEP_OK;
 }
 
 static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const double* e0_h, double* ep_prev_h, int accept,
