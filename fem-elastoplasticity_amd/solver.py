@@ -224,6 +224,7 @@ class KrylovSolver:
         self.free_dof = fd.view(np.bool_)
         self._pattern = (ip, ix)
         self.amg_levels = None
+        self.amg_hierarchy = None
         self.last = None
 
     def close(self):
@@ -307,6 +308,7 @@ class KrylovSolver:
                 _lib.check(l.fep_solver_amg_push_level(self._h, lv['P'].shape[0], lv['P'].shape[1], *[_lib.ptr(m) for m in mats],
                                                        float(lv['omega']), int(lv['last'])), 'fep_solver_amg_push_level')
         push_levels()
+        self.amg_hierarchy = levels                      # the pushed level dicts (tests restate the V-cycle from them)
         self.amg_levels = [(K.shape[0], K.nnz)] + [lv['size'] for lv in levels]
         self.amg_refresh = False
         t2 = time.perf_counter()

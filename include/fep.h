@@ -226,7 +226,9 @@ int fep_transform_host(fep_ctx* ctx, const double* q_int_h, double* q_node_h);
 
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on
- * the device; K is the `data` array fep_step_dev wrote, on the context's CSR pattern.
+ * the device; K is the `data` array fep_step_dev wrote, on the context's CSR pattern.  The Jacobi blocks are the 2x2
+ * diagonal blocks of K with constrained DOFs replaced by identity rows and columns and the off-diagonal symmetrised to
+ * (K[2n,2n+1] + K[2n+1,2n]) / 2; a block that is not positive definite is replaced by the identity.
  *
  *   fep_solver_create   pattern = fep_ctx_pattern_host (checked: rows 2n, 2n+1 share their columns, which come in
  *                       pairs 2m, 2m+1 -> FEP_EINVAL otherwise); free_dof_h (2 n_n) is Q in DOF order, non-zero = free
@@ -252,9 +254,10 @@ int fep_solver_pcg_dev(fep_solver* solver, void* stream, const double* k_data_d,
 /* Multigrid preconditioner for the same solve (smoothed aggregation).  The hierarchy is built on the host (solver.py:
  * aggregates from fep_aggregate_host, rigid-body-mode prolongators, Galerkin products with SciPy) from a reference
  * matrix on the context's pattern — normally K_elast — and pushed level by level; the solver applies it as a V(2,2)
- * cycle in which level 0 is always the CURRENT tangent (k_data_d of the call) and the coarse operators stay those of the
- * reference matrix.  Smoother: degree-2 Chebyshev in D^-1 A on [lmax/20, lmax], lmax = 1.2 x the value the hierarchy's
- * omega encodes (omega = 4 / (3 * 1.05 * rho)).
+ * cycle in which level 0 is always the CURRENT tangent (k_data_d of the call) and the coarse operators are those of the
+ * reference matrix unless the refresh re-projects them (fep_solver_amg_enable_refresh).  Smoother: degree-2 Chebyshev in
+ * D^-1 A on [lmax/20, lmax], lmax = 1.2 x the value the smoothed level's omega encodes (omega = 4 / (3 * 1.05 * rho)),
+ * D = the Jacobi blocks above on level 0 and the 3x3 block inverses below it.
  * The preconditioner reads single precision — K in the smoother's level-0 passes, the refreshed coarse operators
  * and the transfers, applied in node blocks —;
  * CG's own product, its vectors and the Galerkin products are double precision.
