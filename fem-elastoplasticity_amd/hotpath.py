@@ -320,7 +320,8 @@ class MeshContext:
 
     def assemble(self, ds=None, s=None):
         """K = B^T blockdiag(w*ds) B and F = B^T (w*s[0:3]) from given point data (DP:1047-1058).
-        Returns (K csr or None, F or None)."""
+        Returns (K csr or None, F or None).  `ds` must be symmetric per point: only its upper triangle (rows 0, 1, 2, 4,
+        5, 8) is read (include/fep.h, fep_assemble_host)."""
         n = self.n_int
         dsv = None if ds is None else _f64(ds, (9, n))
         sv = None if s is None else _f64(np.asarray(s)[0:3], (3, n))
@@ -443,6 +444,7 @@ def get_elastic_stiffness_matrix_el(elements, coordinates, shear, bulk, dhatp1, 
 def assemble_tangent(handle, ds, s=None):
     """Replaces the inline DP:1047-1050 (+1058): K_tangent (csr) and F from `ds` (9,n_int) and
     `s` (4,n_int).  `handle` is a MeshContext or any object carrying `.fep_ctx` (the K/B returned
-    by get_elastic_stiffness_matrix).  Returns (K_tangent, F); F is None when `s` is None."""
+    by get_elastic_stiffness_matrix).  Returns (K_tangent, F); F is None when `s` is None.  `ds` must be symmetric per
+    point (the reference's tangents are): only its upper triangle, rows 0, 1, 2, 4, 5, 8, is read."""
     ctx = handle if isinstance(handle, MeshContext) else handle.fep_ctx
     return ctx.assemble(ds, s)

@@ -197,7 +197,11 @@ int fep_step_host_planar(fep_ctx* ctx, const double* u2_h, const double* e0_h,
 /* ---- a3..a5 only: assembly from given ds / s ------------------------------------------
  * Replaces DP:1047-1050 + DP:1058 when the caller already holds `ds` (9,n_int) and `s` (>=3 rows
  * used, (4,n_int) layout).  Either output may be NULL.  With ds = the elastic tensor this is the
- * K_elast = B^T D B of DP:595. */
+ * K_elast = B^T D B of DP:595.
+ * `ds` must be symmetric per point (every tangent the return map produces is): only its upper triangle,
+ * rows m = 0, 1, 2, 4, 5, 8, is read, and rows 3, 6, 7 are taken to equal rows 1, 2, 5.  A non-symmetric
+ * ds is assembled as its upper triangle mirrored, without an error (a check would cost as much as the
+ * assembly). */
 int fep_assemble_dev(fep_ctx* ctx, void* stream, const double* ds_d, const double* s_d,
                      double* k_data_d, double* f_out_d);
 int fep_assemble_host(fep_ctx* ctx, const double* ds_h, const double* s_h,

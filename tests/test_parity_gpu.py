@@ -15,6 +15,7 @@ import scipy.sparse as ssp
 
 from conftest import dp_materials, load_golden, relerr, relerr_points, relerr_rows
 from fan_mesh import fan_mesh
+from meshes import rect as rect_mesh_of, square as square_mesh_of
 from oracle import fep_oracle as orc
 from routes import assert_route
 
@@ -502,13 +503,12 @@ def test_el_p1_K_pins(fep, level, nnz, trace, frob):
 
 
 # ---- mid size vs oracle, every element type ------------------------------------------------
-@pytest.mark.parametrize('t,N', [('P1', 60), ('P2', 24), ('Q1', 40), ('Q2', 20)])
+@pytest.mark.parametrize('t,N', [('P1', 60), ('P2', 24), ('Q1', 40), ('Q2', 20), ('P4', 10)])
 def test_hot_path_mid_size_vs_oracle(fep, t, N, heterogeneous=False):
     rng = np.random.default_rng(5)
-    mesh = fep.square_mesh(N, t, 10)
-    elem, coord = mesh['elements'], mesh['coordinates'].copy()
+    elem, coord = square_mesh_of(t, N)                   # (P4: the P1 square raised by create_midpoints_P4)
     inner = np.logical_and.reduce([coord[0] > 0, coord[0] < 10, coord[1] > 0, coord[1] < 10])
-    coord[:, inner] += rng.uniform(-0.1, 0.1, size=(2, inner.sum())) * (10 / N) / (2 if t in ('P2', 'Q2') else 1)
+    coord[:, inner] += rng.uniform(-0.1, 0.1, size=(2, inner.sum())) * (10 / N) / {'P2': 2, 'Q2': 2, 'P4': 4}.get(t, 1)
     d1, d2, wf = fep.element_tables(t)
     n_int = elem.shape[1] * NQ[t]
     sh, bu, eta, c = dp_materials(n_int)
@@ -538,7 +538,7 @@ def test_hot_path_mid_size_vs_oracle(fep, t, N, heterogeneous=False):
     assert relerr(r['F'], F) <= TOL_K
 
 
-@pytest.mark.parametrize('t,N', [('P1', 60), ('P2', 20), ('Q1', 30), ('Q2', 12)])
+@pytest.mark.parametrize('t,N', [('P1', 60), ('P2', 20), ('Q1', 30), ('Q2', 12), ('P4', 8)])
 def test_heterogeneous_materials_vs_oracle(fep, t, N):
     test_hot_path_mid_size_vs_oracle(fep, t, N, heterogeneous=True)
 
@@ -718,14 +718,14 @@ def test_p4_hot_path_vs_oracle_on_tsx_mesh(fep):
     assert relerr(r['F'], F) <= 1e-11
 
 
-@pytest.mark.parametrize('t,nx,ny', [('P1', 1, 1), ('P1', 3, 2), ('Q1', 1, 1), ('Q1', 5, 3), ('P2', 1, 1), ('P2', 3, 3), ('Q2', 2, 2)])
+@pytest.mark.parametrize('t,nx,ny', [('P1', 1, 1), ('P1', 3, 2), ('Q1', 1, 1), ('Q1', 5, 3), ('P2', 1, 1), ('P2', 3, 3), ('Q2', 2, 2),
+                                     ('P4', 1, 1), ('P4', 3, 2)])
 def test_tiny_and_ragged_meshes(fep, t, nx, ny):
     """Meshes far smaller than a workgroup tile, element counts that are not multiples of any block size."""
-    if t in ('P1', 'Q1'):
-        mesh = fep.rect_mesh(nx, ny, t, 2.0, 3.0)
+    if t in ('P1', 'Q1', 'P4'):
+        elem, coord = rect_mesh_of(t, nx, ny, 2.0, 3.0)
     else:
-        mesh = fep.square_mesh(nx, t, 2.0)
-    elem, coord = mesh['elements'], mesh['coordinates']
+        elem, coord = square_mesh_of(t, nx, 2.0)
     d1, d2, wf = fep.element_tables(t)
     n_int = elem.shape[1] * NQ[t]
     sh, bu, eta, c = dp_materials(n_int)
@@ -907,14 +907,13 @@ def test_config5_full_size_p2_properties(fep):
     sub.close()
 
 
-@pytest.mark.parametrize('t,N', [('P1', 24), ('P2', 8), ('Q1', 12), ('Q2', 6)])
+@pytest.mark.parametrize('t,N', [('P1', 24), ('P2', 8), ('Q1', 12), ('Q2', 6), ('P4', 4)])
 def test_tangent_is_the_derivative_of_the_internal_force(fep, t, N):
     """End to end without any checker: K_tangent(U) v equals the central difference of F(U + h v) (the Newton
     linearisation DP:1050 / DP:1058 is consistent), on a state with all three branches."""
     rng = np.random.default_rng(8)
-    mesh = fep.square_mesh(N, t, 10)
-    coord = mesh['coordinates']
-    ctx = fep.MeshContext(mesh['elements'], coord)
+    elem, coord = square_mesh_of(t, N)
+    ctx = fep.MeshContext(elem, coord)
     ctx.set_materials(*[v[0] for v in dp_materials(1)])
     x, y = coord
     U = np.array([2.0e-4 * y * (x / 10) + 1.0e-4 * x * (y > 5), -1.2e-4 * y * (x < 5) + 1.6e-4 * y * (x >= 5)])

@@ -8,14 +8,15 @@ import numpy as np
 import pytest
 
 from conftest import dp_materials, relerr
+from meshes import rect as rect_mesh_of
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize('t,nx,ny,world', [('P1', 40, 60, 2), ('P1', 30, 45, 3), ('Q1', 24, 36, 2), ('P2', 20, 30, 2), ('P2', 14, 21, 3)])
+@pytest.mark.parametrize('t,nx,ny,world', [('P1', 40, 60, 2), ('P1', 30, 45, 3), ('Q1', 24, 36, 2), ('P2', 20, 30, 2), ('P2', 14, 21, 3),
+                                           ('Q2', 12, 18, 2), ('Q2', 10, 15, 3), ('P4', 8, 12, 2)])
 def test_shards_reproduce_global_step(fep, t, nx, ny, world):
-    mesh = fep.rect_mesh(nx, ny, t, 10, 15)
-    elem, coord = mesh['elements'], mesh['coordinates']
+    elem, coord = rect_mesh_of(t, nx, ny, 10, 15)          # (P4: the P1 rectangle raised by create_midpoints_P4)
     n_q = fep.ELEMENT_SHAPE[fep.LagrangeElementType[t]][1]
     n_int = elem.shape[1] * n_q
     sh, bu, eta, c = dp_materials(n_int)
