@@ -10,14 +10,15 @@ The directory name contains a hyphen; import it with
 Flavours of the reference's three `pythonFEM.py` copies:
     fep.plasticity2d_dp   Plasticity2D_DP/pythonFEM.py   (P1, P2, Q1, Q2)
     fep.tsx_tunnel        tsx-tunnel/pythonFEM.py        (adds e0 and P4)
-    fep.elasticity2d      Elasticity2D/pythonFEM.py      (elastic K only)
+    fep.elasticity2d      Elasticity2D/pythonFEM.py      (P1, Q1, Q2; external loads)
 """
-from .tables import (ELEMENT_SHAPE, LagrangeElementType, element_tables, get_local_basis_volume,
-                     get_quadrature_volume)
-from .mesh import assemble_mesh, rect_mesh, renumber_for_locality, square_mesh
+from .tables import (ELEMENT_SHAPE, LagrangeElementType, element_tables, get_local_basis_surface,
+                     get_local_basis_volume, get_quadrature_surface, get_quadrature_volume, surface_tables)
+from .mesh import assemble_mesh, assemble_mesh_el, rect_mesh, renumber_for_locality, square_mesh
 from .hotpath import (MeshContext, assemble_tangent, construct_constitutive_problem,
                       construct_constitutive_problem_tsx, default_device, get_elastic_stiffness_matrix,
-                      get_elastic_stiffness_matrix_el)
+                      get_elastic_stiffness_matrix_el, get_vector_traction, get_vector_volume, load_traction)
+from .elastic import solve_elasticity2d
 from ._lib import FepError, lib, lib_path
 from .build import build
 from .sharding import Partition, ShardedContext, element_ranges
@@ -34,4 +35,6 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'assemble_tangent', 'default_device', 'FepError', 'lib', 'lib_path', 'build',
            'solve_strip_footing', 'solve_tsx_tunnel', 'transform', 'KrylovSolver', 'DistributedPCG', 'solve_strip_footing_sharded', 'build_amg_hierarchy', 'create_midpoints', 'create_midpoints_P2',
            'create_midpoints_P4', 'load_tsx_mesh', 'dump_free_dof_csv',
+           'get_quadrature_surface', 'get_local_basis_surface', 'surface_tables', 'assemble_mesh_el', 'get_vector_volume',
+           'get_vector_traction', 'load_traction', 'solve_elasticity2d',
            'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d']

@@ -59,6 +59,10 @@ PROTOTYPES = {
     'fep_iface_sum_f64': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_transform_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_transform_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_load_volume_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'fep_load_volume_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'fep_load_traction_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    'fep_load_traction_host': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 7),
     'fep_solver_create': (C.c_int, [c_void_pp, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_solver_destroy': (C.c_int, [C.c_void_p]),
     'fep_solver_sizes': (C.c_int, [C.c_void_p, c_i64_p]),

@@ -1477,6 +1477,138 @@ extern "C" int fep_transform_host(fep_ctx* c, const double* q_int_h, double* q_n
     FEP_GUARD(transform_host_impl(c, q_int_h, q_node_h))
 }
 
+// ---- external loads (EL:246-364) ----
+extern "C" int fep_load_volume_dev(fep_ctx* c, void* stream, const double* hatp_h, const double* f_v_d, double fx, double fy,
+                                   const double* weight_d, double* f_out_d) {
+    if (!c || !hatp_h || !f_out_d) return FEP_EINVAL;
+    if (!fep_aligned16(f_out_d)) return FEP_EINVAL;
+    if (c->n_p * c->n_q > kLoadTabMax) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    if (c->n_n == 0) return FEP_OK;
+    LoadTab tab{};                                      // travels as a kernel argument: nothing to copy, capturable
+    for (int i = 0; i < c->n_p * c->n_q; ++i) tab.h[i] = hatp_h[i];
+    const double* w = weight_d ? weight_d : c->weight;
+    const dim3 grid(grid_for(c->n_n, kBlock)), block(kBlock);
+    if (f_v_d)
+        hipLaunchKernelGGL(load_volume_kernel<true>, grid, block, 0, (hipStream_t)stream, c->n_n, c->n_e, c->n_p, c->n_q,
+                           c->iptr, c->ilist, w, f_v_d, 0.0, 0.0, tab, f_out_d);
+    else
+        hipLaunchKernelGGL(load_volume_kernel<false>, grid, block, 0, (hipStream_t)stream, c->n_n, c->n_e, c->n_p, c->n_q,
+                           c->iptr, c->ilist, w, (const double*)nullptr, fx, fy, tab, f_out_d);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+static int load_volume_host_impl(fep_ctx* c, const double* hatp_h, const double* f_v_h, double fx, double fy,
+                                 const double* weight_h, double* f_out_h) {
+    if (!c || !hatp_h || !f_out_h) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    fep_stage::Engine* E = nullptr;
+    FEP_TRY(fep_stage::engine(c->device, &E));
+    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
+    const size_t nb = (size_t)c->n_int * sizeof(double);
+    void *f = nullptr, *w = nullptr, *o = nullptr;
+    if (f_v_h) { FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &f)); FEP_TRY(E->h2d(f, f_v_h, 2 * nb)); }
+    if (weight_h) { FEP_TRY(ctx_buf(c, 9, (int64_t)nb, &w)); FEP_TRY(E->h2d(w, weight_h, nb)); }
+    FEP_TRY(ctx_buf(c, 7, c->n_dof * (int64_t)sizeof(double), &o));
+    FEP_TRY(fep_load_volume_dev(c, E->stream, hatp_h, (const double*)f, fx, fy, (const double*)w, (double*)o));
+    FEP_TRY(E->d2h(f_out_h, o, (size_t)c->n_dof * sizeof(double)));
+    return call.finish();
+}
+
+extern "C" int fep_load_volume_host(fep_ctx* c, const double* hatp_h, const double* f_v_h, double fx, double fy,
+                                    const double* weight_h, double* f_out_h) {
+    FEP_GUARD(load_volume_host_impl(c, hatp_h, f_v_h, fx, fy, weight_h, f_out_h))
+}
+
+// Incidence of the loaded nodes, built per call (n_e_s is of the order of sqrt(n_e)), packed with the edge table into one
+// int32 upload: [edges | bnode | bptr | blist].
+static int load_traction_impl(int device_id, void* stream, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s,
+                              const int32_t* edges_h, const double* xy, bool xy_on_host, const double* hatp_s_h,
+                              const double* dhatp1_s_h, const double* wf_s_h, const double* t_int, bool t_on_host,
+                              double* f_out, bool out_on_host) {
+    if (n_n < 0 || n_e_s < 0 || n_p_s < 2 || n_p_s > kEdgeNodesMax || n_q_s < 1 || n_q_s > kEdgePointsMax) return FEP_EINVAL;
+    if (!f_out && n_n > 0) return FEP_EINVAL;
+    if (n_e_s > 0 && (!edges_h || !xy || !hatp_s_h || !dhatp1_s_h || !wf_s_h || !t_int)) return FEP_EINVAL;
+    if (!out_on_host && !fep_aligned16(f_out)) return FEP_EINVAL;
+    const int64_t n_inc = (int64_t)n_p_s * n_e_s;
+    if (n_inc * (int64_t)kEdgePointsMax >= (int64_t)INT32_MAX / 4) return FEP_ERANGE;
+    for (int64_t i = 0; i < n_inc; ++i)
+        if (edges_h[i] < 0 || edges_h[i] >= n_n) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(device_id));
+    if (n_n == 0) return FEP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // loaded nodes in ascending id, each with its (edge, local node) codes ordered by (e, a)
+    std::vector<int32_t> bnode(edges_h, edges_h + n_inc);
+    std::sort(bnode.begin(), bnode.end());
+    bnode.erase(std::unique(bnode.begin(), bnode.end()), bnode.end());
+    const int64_t n_b = (int64_t)bnode.size();
+    std::vector<int32_t> pack((size_t)(2 * n_inc + 2 * n_b + 1), 0);
+    int32_t* P_edges = pack.data();
+    int32_t* P_bnode = P_edges + n_inc;
+    int32_t* P_bptr = P_bnode + n_b;
+    int32_t* P_blist = P_bptr + n_b + 1;
+    auto slot = [&](int32_t nd) { return (int64_t)(std::lower_bound(bnode.begin(), bnode.end(), nd) - bnode.begin()); };
+    for (int64_t i = 0; i < n_inc; ++i) { P_edges[i] = edges_h[i]; P_bptr[slot(edges_h[i]) + 1]++; }
+    for (int64_t b = 0; b < n_b; ++b) { P_bnode[b] = bnode[b]; P_bptr[b + 1] += P_bptr[b]; }
+    {
+        std::vector<int32_t> fill(P_bptr, P_bptr + n_b);
+        for (int64_t e = 0; e < n_e_s; ++e)
+            for (int a = 0; a < n_p_s; ++a) P_blist[fill[slot(edges_h[(int64_t)a * n_e_s + e])]++] = (int32_t)((int64_t)a * n_e_s + e);
+    }
+    EdgeTab tab{};
+    for (int i = 0; i < n_p_s * n_q_s; ++i) { tab.h[i] = hatp_s_h[i]; tab.dh[i] = dhatp1_s_h[i]; }
+    for (int q = 0; q < n_q_s; ++q) tab.wf[q] = wf_s_h[q];
+    // device scratch of this call: released on every exit
+    struct Scratch {
+        std::vector<void*> p;
+        ~Scratch() { for (void* q : p) (void)hipFree(q); }
+        int get(void** out, size_t bytes) {
+            HIP_TRY(hipMalloc(out, bytes ? bytes : 1));
+            p.push_back(*out);
+            return FEP_OK;
+        }
+    } scratch;
+    const size_t n_pts = (size_t)(n_e_s * n_q_s);
+    void *d_pack = nullptr, *d_xy = (void*)xy, *d_t = (void*)t_int, *d_out = (void*)f_out;
+    FEP_TRY(scratch.get(&d_pack, pack.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(d_pack, pack.data(), pack.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (xy_on_host && n_e_s > 0) {
+        FEP_TRY(scratch.get(&d_xy, 2 * (size_t)n_n * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(d_xy, xy, 2 * (size_t)n_n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (t_on_host && n_e_s > 0) {
+        FEP_TRY(scratch.get(&d_t, 2 * n_pts * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(d_t, t_int, 2 * n_pts * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (out_on_host) FEP_TRY(scratch.get(&d_out, 2 * (size_t)n_n * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(d_out, 0, 2 * (size_t)n_n * sizeof(double), st));
+    if (n_b > 0) {
+        const int32_t* dp = (const int32_t*)d_pack;
+        hipLaunchKernelGGL(load_traction_kernel, dim3(grid_for(n_b, kBlock)), dim3(kBlock), 0, st, (int)n_b, n_n, n_e_s, n_p_s,
+                           n_q_s, dp, dp + n_inc, dp + n_inc + n_b, dp + n_inc + 2 * n_b + 1, (const double*)d_xy,
+                           (const double*)d_t, tab, (double*)d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    if (out_on_host) HIP_TRY(hipMemcpyAsync(f_out, d_out, 2 * (size_t)n_n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                  // the scratch above is freed on return
+    return FEP_OK;
+}
+
+extern "C" int fep_load_traction_dev(int device_id, void* stream, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s,
+                                     const int32_t* edges_h, const double* xy_d, const double* hatp_s_h,
+                                     const double* dhatp1_s_h, const double* wf_s_h, const double* t_int_d, double* f_out_d) {
+    FEP_GUARD(load_traction_impl(device_id, stream, n_n, n_e_s, n_p_s, n_q_s, edges_h, xy_d, false, hatp_s_h, dhatp1_s_h, wf_s_h,
+                                 t_int_d, false, f_out_d, false))
+}
+
+extern "C" int fep_load_traction_host(int device_id, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s,
+                                      const int32_t* edges_h, const double* xy_h, const double* hatp_s_h,
+                                      const double* dhatp1_s_h, const double* wf_s_h, const double* t_int_h, double* f_out_h) {
+    FEP_GUARD(load_traction_impl(device_id, nullptr, n_n, n_e_s, n_p_s, n_q_s, edges_h, xy_h, true, hatp_s_h, dhatp1_s_h, wf_s_h,
+                                 t_int_h, true, f_out_h, true))
+}
+
 extern "C" int fep_ctx_profile_begin(fep_ctx* c) {
     if (!c) return FEP_EINVAL;
     for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);

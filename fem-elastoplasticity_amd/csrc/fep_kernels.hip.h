@@ -1000,6 +1000,85 @@ nodal_average_kernel(int64_t n_n, int64_t n_e, int n_q, const int32_t* __restric
     q_node[n] = f1 / f2;
 }
 
+// External loads (EL:246-364, TSX:546-988).  No floating-point atomics; every node's terms are added in the fixed order
+// of its incidence list, (element, local node) ascending and the points of an element in turn, so a call is bitwise
+// reproducible.  Products are formed as the reference forms them, hatp * (weight * f), without FMA contraction, so the
+// uniform form (f = two scalars) and the field form holding the same two numbers give the same bits.
+constexpr int kLoadTabMax = 15 * 12;                        // P4: the largest (n_p, n_q) table
+struct LoadTab { double h[kLoadTabMax]; };                  // basis-function VALUES hatp (n_p, n_q), row-major
+
+// Volume load: f_V[c, n] = sum over the (e, a) with elements[a, e] == n, over q, of hatp[a, q] * weight[e, q] * f[c, e, q].
+// One lane per node over the incidence lists, as nodal_average_kernel; a node of no element gets 0.
+template <bool kField>
+__global__ void __launch_bounds__(kBlock)
+load_volume_kernel(int64_t n_n, int64_t n_e, int n_p, int n_q, const int32_t* __restrict__ iptr,
+                   const int32_t* __restrict__ ilist, const double* __restrict__ weight,
+                   const double* __restrict__ f_v, double fx, double fy, LoadTab tab, double* __restrict__ f_out) {
+#pragma clang fp contract(off)
+    __shared__ double hat[kLoadTabMax];
+    for (int i = threadIdx.x; i < n_p * n_q; i += kBlock) hat[i] = tab.h[i];
+    __syncthreads();
+    const int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (n >= n_n) return;
+    const int64_t n_int = n_e * n_q;
+    double a1 = 0.0, a2 = 0.0;
+    for (int32_t t = iptr[n]; t < iptr[n + 1]; ++t) {
+        const int64_t code = ilist[t];
+        const int a = (int)(code / n_e);
+        const int64_t k0 = (code - (int64_t)a * n_e) * n_q;
+        const double* h = hat + a * n_q;
+        for (int q = 0; q < n_q; ++q) {
+            const double w = weight[k0 + q];
+            const double g1 = kField ? f_v[k0 + q] : fx;
+            const double g2 = kField ? f_v[n_int + k0 + q] : fy;
+            a1 += h[q] * (w * g1);
+            a2 += h[q] * (w * g2);
+        }
+    }
+    *reinterpret_cast<double2*>(f_out + 2 * n) = make_double2(a1, a2);
+}
+
+// Traction load over boundary edges (EL:295-364 with the full arc-length Jacobian and a value per surface point).
+// One lane per loaded node b: node id bnode[b], its (edge, local node) codes a * n_e_s + e in blist[bptr[b] .. bptr[b + 1])
+// ordered by (e, a).  f_out is zeroed by the caller beforehand.
+constexpr int kEdgeNodesMax = 5, kEdgePointsMax = 8;
+struct EdgeTab { double h[kEdgeNodesMax * kEdgePointsMax], dh[kEdgeNodesMax * kEdgePointsMax], wf[kEdgePointsMax]; };
+
+__global__ void __launch_bounds__(kBlock)
+load_traction_kernel(int n_b, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s, const int32_t* __restrict__ edges,
+                     const int32_t* __restrict__ bnode, const int32_t* __restrict__ bptr, const int32_t* __restrict__ blist,
+                     const double* __restrict__ xy, const double* __restrict__ t_int, EdgeTab tab,
+                     double* __restrict__ f_out) {
+#pragma clang fp contract(off)
+    __shared__ EdgeTab T;
+    if (threadIdx.x == 0) T = tab;
+    __syncthreads();
+    const int b = blockIdx.x * kBlock + threadIdx.x;
+    if (b >= n_b) return;
+    const int64_t n_int_s = n_e_s * n_q_s;
+    double a1 = 0.0, a2 = 0.0;
+    for (int32_t t = bptr[b]; t < bptr[b + 1]; ++t) {
+        const int64_t code = blist[t];
+        const int a = (int)(code / n_e_s);
+        const int64_t e = code - (int64_t)a * n_e_s;
+        for (int q = 0; q < n_q_s; ++q) {
+            double j1 = 0.0, j2 = 0.0;
+            for (int m = 0; m < n_p_s; ++m) {
+                const int64_t nd = edges[(int64_t)m * n_e_s + e];
+                j1 += xy[nd] * T.dh[m * n_q_s + q];
+                j2 += xy[n_n + nd] * T.dh[m * n_q_s + q];
+            }
+            const double w = sqrt(j1 * j1 + j2 * j2) * T.wf[q];
+            const double h = T.h[a * n_q_s + q];
+            a1 += h * (w * t_int[e * n_q_s + q]);
+            a2 += h * (w * t_int[n_int_s + e * n_q_s + q]);
+        }
+    }
+    const int64_t nd = bnode[b];
+    f_out[2 * nd] = a1;
+    f_out[2 * nd + 1] = a2;
+}
+
 // P1 geometry recomputed from the node coordinates (48 bytes gathered through L2 instead of a 64-byte
 // record streamed from HBM).  Same operations, same order, no FMA contraction as geometry_kernel, hence
 // bit-identical dphi / weight (DP:530-546, 585).  `tab` = the P1 reference-element tables.

@@ -11,12 +11,14 @@ Reference interface mirrored here (DP = Plasticity2D_DP/pythonFEM.py, TSX = tsx-
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 import scipy.sparse as ssp
 
 from . import _lib
-from .tables import ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables
+from .tables import (ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables, get_local_basis_volume,
+                     get_quadrature_volume)
 
 _NP_TO_TYPE = {3: LagrangeElementType.P1, 6: LagrangeElementType.P2, 4: LagrangeElementType.Q1,
                8: LagrangeElementType.Q2, 15: LagrangeElementType.P4}
@@ -215,6 +217,7 @@ class MeshContext:
         self.elements = el32
         self._pattern = None
         self._geom = None
+        self._hatp_own = None
 
     # -- lifetime
     def close(self):
@@ -354,6 +357,42 @@ class MeshContext:
     def transform_dev(self, stream, q_int, q_node):
         _lib.check(_lib.lib().fep_transform_dev(self._h, stream, q_int, q_node), 'fep_transform_dev')
 
+    # -- external loads (EL:246-292)
+    def _hatp(self, hatp):
+        if hatp is None:
+            if self._hatp_own is None:                                       # the library's table, evaluated once
+                own = get_local_basis_volume(self.element_type, get_quadrature_volume(self.element_type)[0])[0]
+                self._hatp_own = np.ascontiguousarray(np.broadcast_to(np.asarray(own, dtype=np.float64), (self.n_p, self.n_q)))
+            return self._hatp_own
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(hatp, dtype=np.float64), (self.n_p, self.n_q)))
+
+    def load_volume(self, f_v_int=None, uniform=None, hatp=None, weight=None):
+        """Body-force vector (EL:246-292) -> (2, n_n) ndarray.  Either `f_v_int` (2, n_int), a value per integration
+        point, or `uniform` = (fx, fy), the same force everywhere (self-weight) without a field in memory.  `hatp`: the
+        (n_p, n_q) basis-function values, default the library's table of the context's element type; `weight`: (n_int),
+        default the context's own."""
+        if (f_v_int is None) == (uniform is None):
+            raise ValueError('give exactly one of f_v_int and uniform')
+        h = self._hatp(hatp)
+        f = None if f_v_int is None else _f64(f_v_int, (2, self.n_int))
+        fx, fy = (0.0, 0.0) if uniform is None else (float(uniform[0]), float(uniform[1]))
+        w = None if weight is None else _f64(weight).ravel()
+        if w is not None and w.size != self.n_int:
+            raise ValueError(f'weight must hold {self.n_int} values')
+        out = np.empty(self.n_dof)
+        _lib.check(_lib.lib().fep_load_volume_host(self._h, _lib.ptr(h), _lib.ptr(f), fx, fy, _lib.ptr(w), _lib.ptr(out)),
+                   'fep_load_volume_host')
+        return np.ascontiguousarray(out.reshape(self.n_n, 2).T)
+
+    def load_volume_dev(self, stream, f_out, f_v_int=0, uniform=None, hatp=None, weight=0):
+        """The same on device pointers (ints): `f_out` (n_dof) interleaved like F of step_dev, `f_v_int` (2, n_int) planar or
+        0 with `uniform` = (fx, fy).  Only enqueues one kernel: capturable in a graph."""
+        if bool(f_v_int) == (uniform is not None):
+            raise ValueError('give exactly one of f_v_int and uniform')
+        fx, fy = (0.0, 0.0) if uniform is None else (float(uniform[0]), float(uniform[1]))
+        _lib.check(_lib.lib().fep_load_volume_dev(self._h, stream, _lib.ptr(self._hatp(hatp)), f_v_int or None, fx, fy,
+                                                  weight or None, f_out), 'fep_load_volume_dev')
+
     def profile_begin(self):
         """Start bracketing every kernel of the following step_dev/assemble_dev calls with HIP events."""
         _lib.check(_lib.lib().fep_ctx_profile_begin(self._h), 'fep_ctx_profile_begin')
@@ -430,6 +469,7 @@ def get_elastic_stiffness_matrix(elements, coordinates, shear, bulk, dhatp1, dha
     jD = np.repeat(aux, 3, axis=0)                                             # DP:590
     K.fep_ctx = ctx
     B.fep_ctx = ctx
+    _remember_context(weight, ctx)
     return K, B, weight, iD, jD, D
 
 
@@ -439,6 +479,98 @@ def get_elastic_stiffness_matrix_el(elements, coordinates, shear, bulk, dhatp1, 
     elements -= 1
     K, _, weight, *_ = get_elastic_stiffness_matrix(elements, coordinates, shear, bulk, dhatp1, dhatp2, wf, device)
     return K, weight
+
+
+# ---------------------------------------------------------------------------------------
+# external loads: get_vector_volume (EL:246-292), get_vector_traction (EL:295-364)
+# ---------------------------------------------------------------------------------------
+# The reference's get_vector_volume receives `weight` but no handle of ours: the context that produced a weight array is
+# found by the array's identity.  Both sides are held weakly (the context owns the array through its geometry cache, K and B
+# own the context), so an entry lives exactly as long as the arrays the caller still holds.
+_CTX_OF_WEIGHT = {}
+
+
+def _remember_context(weight, ctx):
+    key = id(weight)
+
+    def forget(_, key=key):
+        _CTX_OF_WEIGHT.pop(key, None)
+    _CTX_OF_WEIGHT[key] = (weakref.ref(weight, forget), weakref.ref(ctx))
+
+
+def _context_for(elements, n_n, weight):
+    hit = _CTX_OF_WEIGHT.get(id(weight))
+    if hit is None or hit[0]() is not weight:
+        return None
+    ctx = hit[1]()
+    if ctx is None or not ctx._h or ctx.n_n != n_n or ctx.elements.shape != elements.shape \
+            or not np.array_equal(ctx.elements, elements):
+        return None
+    return ctx
+
+
+def _sparse_rows(dense, touched):
+    """(2, n_n) csc_matrix with both rows stored for every touched node, zeros included: what the reference's sum of
+    triplets yields (EL:289-290)."""
+    cols = np.flatnonzero(touched)
+    indptr = np.zeros(dense.shape[1] + 1, dtype=np.int32)
+    indptr[1:] = 2 * np.cumsum(touched)
+    return ssp.csc_matrix((dense[:, cols].T.ravel(), np.tile(np.array([0, 1], dtype=np.int32), cols.size), indptr),
+                          shape=dense.shape)
+
+
+def get_vector_volume(elements, coordinates, f_V_int, hatp, weight, device=None):
+    """Drop-in for EL:246-292 / TSX:311-357: the body-force vector as a (2, n_n) csc_matrix.  `elements` 0-based (the
+    reference's driver calls it after get_elastic_stiffness_matrix shifted them).  The sum runs on the GPU
+    (fep_load_volume_host) with the caller's `hatp` and `weight`; the mesh context is the one whose
+    get_elastic_stiffness_matrix* call returned this very `weight` array, else a new one built from `elements` /
+    `coordinates` with the library's tables for the element type that `hatp.shape[0]` names."""
+    elements = np.asarray(elements)
+    coordinates = np.asarray(coordinates)
+    n_n = coordinates.shape[1]
+    ctx = _context_for(elements, n_n, weight)
+    if ctx is None:
+        ctx = MeshContext(elements, coordinates, device=device)
+    f = ctx.load_volume(f_v_int=np.asarray(f_V_int, dtype=np.float64)[0:2], hatp=hatp, weight=weight)
+    touched = np.zeros(n_n, dtype=bool)
+    touched[elements.ravel()] = True
+    return _sparse_rows(f, touched)
+
+
+def load_traction(edges, coordinates, t_int, hatp_s, dhatp1_s, wf_s, device=None):
+    """Surface-load vector over boundary edges -> (2, n_n) ndarray (fep_load_traction_host): `edges` (n_p_s, n_e_s) 0-based
+    node ids (end, end[, middle]), `t_int` (2, n_e_s * n_q_s) a traction PER surface point, Jacobian = arc length, so
+    edges of any direction are right."""
+    coordinates = _f64(coordinates)
+    n_n = coordinates.shape[1]
+    ed = np.ascontiguousarray(edges, dtype=np.int32)
+    n_p_s, n_e_s = ed.shape
+    wf = _f64(wf_s).ravel()
+    n_q_s = wf.size
+    h = np.ascontiguousarray(np.broadcast_to(np.asarray(hatp_s, dtype=np.float64), (n_p_s, n_q_s)))
+    dh = np.ascontiguousarray(np.broadcast_to(np.asarray(dhatp1_s, dtype=np.float64), (n_p_s, n_q_s)))
+    t = _f64(t_int, (2, n_e_s * n_q_s))
+    out = np.empty(2 * n_n)
+    dev = default_device() if device is None else device
+    _lib.check(_lib.lib().fep_load_traction_host(dev, n_n, n_e_s, n_p_s, n_q_s, _lib.ptr(ed), _lib.ptr(coordinates),
+                                                 _lib.ptr(h), _lib.ptr(dh), _lib.ptr(wf), _lib.ptr(t), _lib.ptr(out)),
+               'fep_load_traction_host')
+    return np.ascontiguousarray(out.reshape(n_n, 2).T)
+
+
+def get_vector_traction(elements_s, coordinates, f_t_int, hatp_s, dhatp1_s, wf_s, device=None):
+    """Drop-in for EL:295-364: (2, n_n) csc_matrix.  `elements_s` as the reference's `neumann_nodes` (0-based, float).
+    The reference applies the LAST point's traction `f_t_int[:, -1]` at every point (EL:352-353): that quirk is kept here,
+    by broadcasting, while the library honours a value per point (`load_traction`).  On the reference's horizontal edges
+    its Jacobian |dx/dxi| and the library's arc length agree."""
+    ed = np.asarray(elements_s).astype(np.int64)
+    f_t_int = np.asarray(f_t_int, dtype=np.float64)
+    n_pts = ed.shape[1] * np.asarray(wf_s).size
+    t = np.repeat(f_t_int[0:2, -1:], n_pts, axis=1)
+    f = load_traction(ed, coordinates, t, hatp_s, dhatp1_s, wf_s, device=device)
+    touched = np.zeros(np.asarray(coordinates).shape[1], dtype=bool)
+    touched[ed.ravel()] = True
+    return _sparse_rows(f, touched)
 
 
 def assemble_tangent(handle, ds, s=None):

@@ -101,6 +101,73 @@ def assemble_mesh(level, element_type, size_xy):
     return square_mesh(size_xy * 2 ** level, element_type, size_xy)
 
 
+def assemble_mesh_el(level, element_type, size_xy=10, size_hole=5):
+    """The Elasticity2D flavour's mesh (EL:481-942): the square [0, size_xy]^2 without the corner [0, size_hole]^2, with
+    N = size_xy * 2**level cells per side, for P1, Q1 and Q2.  Returns the reference's dictionary: 'coordinates' (2, n_n),
+    'elements' (n_p, n_e) int64 **1-based** (the K routine shifts them in place, EL:389), 'surface' (float, 1-based),
+    'neumann_nodes' (n_p_s, N) float **0-based** = the edges of the top side y == size_xy (end, end[, middle]),
+    'dirichlet_nodes' (2, n_n) (1 in x on y == 0: the prescribed displacement is half of it) and 'Q' (2, n_n) bool.
+
+    Numbering: the lattice points outside the cut-out (for Q2 without the cell centres) are counted row by row, x
+    fastest; the cells likewise, P1 cells split as (V1, V2, V4), (V2, V3, V4).  'surface' repeats the reference's six
+    faces as it composes them, slips included: faces 5 and 6 are read from the lattice columns size_hole * 2**level and
+    one further (for Q2 those lie inside the cut-out and hold 0), and Q2's face 1 names each middle node twice.  Only
+    'neumann_nodes' (face 3) is used by the driver.
+
+    P2 raises ValueError: the reference's own generator fails for it at every level (EL:698 assigns a transposed block)."""
+    t = _coerce(element_type)
+    if t is LagrangeElementType.P2:
+        raise ValueError('Elasticity2D has no P2 cut-out mesh: the reference generator fails at EL:698 '
+                         '("could not broadcast input array from shape (20,21) into shape (21,20)" at level 1)')
+    if t not in (LagrangeElementType.P1, LagrangeElementType.Q1, LagrangeElementType.Q2):
+        raise ValueError(f'no cut-out mesh for {t}')
+    N = int(size_xy) * 2 ** int(level)
+    N1 = int(size_hole) * 2 ** int(level)
+    s = 2 if t is LagrangeElementType.Q2 else 1                             # lattice steps per cell
+    M, H = s * N + 1, s * N1                                                # lattice points per side, first row above the hole
+    li, lj = np.meshgrid(np.arange(M), np.arange(M), indexing='ij')         # lattice [i (x), j (y)]
+    valid = np.logical_not(np.logical_and(li < H, lj < H))
+    if s == 2:
+        valid &= np.logical_not(np.logical_and(li % 2 == 1, lj % 2 == 1))
+    vt = valid.T                                                            # rows of constant y: the counting order
+    C = np.zeros((M, M))
+    C.T[vt] = np.arange(1, int(valid.sum()) + 1)
+    xs = np.linspace(0, size_xy, M)
+    coord = np.array([xs[li.T[vt]], xs[lj.T[vt]]])
+    cj, ci = np.meshgrid(np.arange(N), np.arange(N), indexing='ij')         # cells, j outer
+    keep = np.logical_not(np.logical_and(ci < N1, cj < N1))
+    ci, cj = s * ci[keep], s * cj[keep]
+    if s == 1:
+        V1, V2, V3, V4 = C[ci, cj], C[ci + 1, cj], C[ci + 1, cj + 1], C[ci, cj + 1]
+        if t is LagrangeElementType.P1:
+            elem = np.array((V1, V2, V4, V2, V3, V4)).reshape((3, 2 * ci.size), order='F')
+        else:
+            elem = np.array((V1, V2, V3, V4))
+    else:
+        elem = np.array((C[ci, cj], C[ci + 2, cj], C[ci + 2, cj + 2], C[ci, cj + 2],
+                         C[ci + 1, cj], C[ci + 2, cj + 1], C[ci + 1, cj + 2], C[ci, cj + 1]))
+    lo, up, all_ = s * np.arange(N1), s * np.arange(N1, N), s * np.arange(N)
+    top = M - 1
+
+    def along_x(i, j, first=False):
+        if s == 1:
+            return np.array((C[i, j], C[i + 1, j]))
+        return np.array((C[i, j], C[i + 1, j] if first else C[i + 2, j], C[i + 1, j]))
+
+    def along_y(i, j):
+        if s == 1:
+            return np.array((C[i, j], C[i, j + 1]))
+        return np.array((C[i, j], C[i, j + 2], C[i, j + 1]))
+    faces = (along_x(up, 0, first=True), along_y(top, all_), along_x(all_, top), along_y(0, up),
+             along_y(N1, lo), along_y(N1 + 1, lo))
+    dirichlet = np.zeros(coord.shape)
+    dirichlet[0, coord[1, :] == 0] = 1
+    Q = coord > 0
+    Q[0, coord[1, :] == 0] = 0
+    return {'coordinates': coord, 'elements': elem.astype(np.int64), 'surface': np.concatenate(faces, axis=1),
+            'neumann_nodes': faces[2] - 1, 'dirichlet_nodes': dirichlet, 'Q': Q}
+
+
 def renumber_for_locality(elements, coordinates):
     """Node and element numbering along a Morton (Z-order) curve — no counterpart in the reference, whose meshes come
     numbered row by row.  The GPU path gathers node and element data of neighbouring nodes together; a mesh numbered

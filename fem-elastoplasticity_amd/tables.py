@@ -163,6 +163,45 @@ def get_local_basis_volume(el_type, xi):
     raise ValueError(el_type)
 
 
+def get_quadrature_surface(el_type):
+    """Quadrature on the reference edge [-1, 1] for the surface loads: points `xi_s` (n_q_s,) and weight factors `wf_s`
+    (n_q_s,).  EL:112-133 (TSX has the same rules).  Linear edges (P1, Q1): the midpoint rule; quadratic edges (P2,
+    Q2): two Gauss points.  The linear rule comes back as integer arrays, as the reference's literals make it."""
+    t = _coerce(el_type)
+    if t in (LagrangeElementType.P1, LagrangeElementType.Q1):
+        return np.array([0]), np.array([2])
+    if t in (LagrangeElementType.P2, LagrangeElementType.Q2):
+        g = 1 / np.sqrt(3)
+        return np.array([-g, g]), np.array([1, 1])
+    raise ValueError(f'no surface quadrature for {t}')
+
+
+def get_local_basis_surface(el_type, xi_s):
+    """Edge basis functions at the points `xi_s` (n_q_s,): (hatp_s (n_p_s, n_q_s), dhatp1_s).  EL:212-243.
+    Linear edges: two end nodes, the derivative table is the constant (2, 1) column.  Quadratic edges: end, end, middle
+    (the order of the rows of `neumann_nodes`), derivatives (3, n_q_s)."""
+    t = _coerce(el_type)
+    x = xi_s
+    if t in (LagrangeElementType.P1, LagrangeElementType.Q1):
+        return 0.5 * np.array([1 - x, 1 + x]), np.array([[-0.5], [0.5]])
+    if t in (LagrangeElementType.P2, LagrangeElementType.Q2):
+        hat = np.array([np.multiply(x, (x - 1) / 2), np.multiply(x, (x + 1) / 2), np.multiply(x + 1, 1 - x)])
+        return hat, np.array([x - 0.5, x + 0.5, -2 * x])
+    raise ValueError(f'no surface basis for {t}')
+
+
+def surface_tables(el_type):
+    """(hatp_s, dhatp1_s, wf_s) as C-contiguous (n_p_s, n_q_s), (n_p_s, n_q_s), (n_q_s,) float64 arrays: the form
+    fep_load_traction_* takes (include/fep.h)."""
+    t = _coerce(el_type)
+    xi_s, wf_s = get_quadrature_surface(t)
+    hat, dh = get_local_basis_surface(t, xi_s)
+    shape = (hat.shape[0], wf_s.size)
+    return (np.ascontiguousarray(np.broadcast_to(np.asarray(hat, dtype=float), shape)),
+            np.ascontiguousarray(np.broadcast_to(np.asarray(dh, dtype=float), shape)),
+            np.ascontiguousarray(np.asarray(wf_s, dtype=float).ravel()))
+
+
 def element_tables(el_type):
     """(dhatp1, dhatp2, wf) as C-contiguous (n_p,n_q), (n_p,n_q), (n_q,) float64 arrays —
     the form the C ABI takes (include/fep.h: fep_ctx_create)."""

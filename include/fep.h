@@ -228,6 +228,53 @@ int fep_iface_sum_f64(int device_id, void* stream, int64_t n, const int32_t* loc
 int fep_transform_dev(fep_ctx* ctx, void* stream, const double* q_int_d, double* q_node_d);
 int fep_transform_host(fep_ctx* ctx, const double* q_int_h, double* q_node_h);
 
+/* ---- external loads (EL:246-364; the same two functions at TSX:546-988) ---------------------------------
+ * Volume (body-force) vector, get_vector_volume EL:246-292:
+ *     f_V[c, n] = sum over the (element e, local node a) with elements[a, e] == n, over the points q of e, of
+ *                 hatp[a, q] * weight[e * n_q + q] * f_v[c, e * n_q + q]
+ *
+ *   hatp_h     (n_p, n_q) C-order basis-function VALUES at the quadrature points (get_local_basis_volume's first
+ *              result, EL:136-209); host memory, read during the call and passed on as a kernel argument
+ *   f_v        (2, n_int) planar, or NULL: the uniform body force (fx, fy) at every point (self-weight), without a field
+ *              in memory; fx, fy are ignored when f_v is given
+ *   weight     (n_int) or NULL = the context's own |det J| * wf (EL:441); a caller's modified weights are honoured as the
+ *              reference honours its `weight` argument
+ *   f_out      (n_dof) interleaved (x, y) per node, DOF order like F of fep_step_dev; every node is written, a node that
+ *              belongs to no element gets 0 (the reference's sparse sum has no entry there)
+ *
+ * One lane per node over the node -> (element, local node) lists; no floating-point atomics, terms added in the fixed
+ * order (e, a) ascending then q, products formed as hatp * (weight * f) without contraction: two calls give the same
+ * bits, and so do the uniform form and a field holding the same two numbers.  fep_load_volume_dev neither allocates nor
+ * copies nor synchronises: it can be captured into a hipGraph (the table is baked into the captured launch). */
+int fep_load_volume_dev(fep_ctx* ctx, void* stream, const double* hatp_h, const double* f_v_d, double fx, double fy,
+                        const double* weight_d, double* f_out_d);
+int fep_load_volume_host(fep_ctx* ctx, const double* hatp_h, const double* f_v_h, double fx, double fy,
+                         const double* weight_h, double* f_out_h);
+
+/* Traction (surface-load) vector over boundary edges, get_vector_traction EL:295-364, context-free (edges are not
+ * elements of a context):
+ *     f_t[c, n] = sum over the (edge e, local node a) with edges[a, e] == n, over the surface points q, of
+ *                 hatp_s[a, q] * |J(e, q)| * wf_s[q] * t_int[c, e * n_q_s + q]
+ *     |J| = sqrt(j1^2 + j2^2),  j_c = sum_a coords[c, edges[a, e]] * dhatp1_s[a, q]
+ * Two departures from EL:344-353, both supersets of it: the Jacobian is the full arc length (the reference takes |j1|,
+ * right on horizontal edges only), and t_int holds a value PER surface point (the reference applies the last point's
+ * value everywhere; the Python wrapper get_vector_traction broadcasts it to keep that quirk).
+ *
+ *   edges_h    (n_p_s, n_e_s) C-order, 0-based node ids, HOST memory in both forms (FEP_ERANGE for an id outside [0, n_n));
+ *              n_p_s = 2 (P1, Q1), 3 (P2, Q2: end, end, middle), up to 5; n_q_s up to 8
+ *   xy         (2, n_n) planar node coordinates       hatp_s_h, dhatp1_s_h (n_p_s, n_q_s), wf_s_h (n_q_s): host
+ *   t_int      (2, n_e_s * n_q_s) planar              f_out (2 n_n) interleaved, zero off the loaded edges
+ *
+ * The node -> (edge, local node) lists of the loaded nodes are built on the host and uploaded by every call, so BOTH forms
+ * allocate scratch and synchronise `stream` before they return (not capturable; n_e_s is of the order of sqrt(n_e)).  No
+ * floating-point atomics, fixed order (e, a) ascending then q. */
+int fep_load_traction_dev(int device_id, void* stream, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s,
+                          const int32_t* edges_h, const double* xy_d, const double* hatp_s_h, const double* dhatp1_s_h,
+                          const double* wf_s_h, const double* t_int_d, double* f_out_d);
+int fep_load_traction_host(int device_id, int64_t n_n, int64_t n_e_s, int n_p_s, int n_q_s,
+                           const int32_t* edges_h, const double* xy_h, const double* hatp_s_h, const double* dhatp1_s_h,
+                           const double* wf_s_h, const double* t_int_h, double* f_out_h);
+
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on
  * the device; K is the `data` array fep_step_dev wrote, on the context's CSR pattern.  The Jacobi blocks are the 2x2
