@@ -15,16 +15,19 @@ ranks once per solve).  Per iteration: one local block SpMV (fep_solver_spmv_dev
 it), one interface exchange, two small all-reduces (p.Kp; r.z and r.r together).  The loop is driven from the host with
 torch tensors as device vectors; convergence is looked at every `check_every` iterations.
 
-solve_strip_footing_sharded: Plasticity2D_DP's load-step loop (newton.solve_strip_footing, DP:986-1131) on the ranks of
-the default process group; same step control, same stopping norms (energy norms through the weighted inner product).
+solve_strip_footing_sharded: Plasticity2D_DP's load-step loop (DP:986-1131) on the ranks of the default process group.
+It is newton.py's loop itself, entered with a ShardedContext and _ShardOps: newton's device ops with the local slice
+in `vec`, the interface exchange of F, all-reduced branch counters, DistributedPCG as the solver, energy norms through
+the weighted inner product and global gathers in `host` / `nodal`.
 
 The reference has no parallelism of any kind; this module is new.
 """
+from contextlib import closing
+
 import numpy as np
 
-from .mesh import square_mesh
+from .newton import _DeviceOps, _footing_setup, _strip_footing, point_sums
 from .sharding import ShardedContext
-from .tables import _coerce, element_tables
 
 
 def _allreduce_(t, group=None, device=None):
@@ -160,69 +163,27 @@ class DistributedPCG:
         return x
 
 
-class _ShardOps:
-    """newton._DeviceOps on a ShardedContext: local vectors (consistent on the interface), sub-assembled K."""
+class _ShardOps(_DeviceOps):
+    """newton._DeviceOps on a ShardedContext: local vectors (consistent on the interface), sub-assembled K, DistributedPCG
+    as the solver.  Only what the sharding changes is stated here."""
 
     def __init__(self, sc, qf_global, rtol=1e-11, max_iter=200000, inexact_rtol=None, group=None):
-        import torch
-        self.torch, self.sc, self.ctx, self.group = torch, sc, sc.ctx, group
-        self.dev = torch.device('cuda', self.ctx.device)
-        self.cg = DistributedPCG(sc, qf_global, group)
-        self.rtol, self.max_iter, self.inexact_rtol = rtol, max_iter, inexact_rtol
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        ctx = self.ctx
-        self.kd = torch.empty(ctx.nnz, **f64)
-        self.F = torch.empty(ctx.n_dof, **f64)
-        self.s = torch.empty((4, ctx.n_int), **f64)
-        self.ind = torch.empty(ctx.n_int, dtype=torch.uint8, device=self.dev)
-        self.counts = torch.zeros(2, dtype=torch.int64, device=self.dev)
-        self.pcg_iters = []
+        super().__init__(sc.ctx, DistributedPCG(sc, qf_global, group), rtol=rtol, max_iter=max_iter, inexact_rtol=inexact_rtol)
+        self.sc, self.group = sc, group
         self.n_dof_global = int(np.asarray(qf_global).size)
 
     def vec(self, a_global):
-        a = np.asarray(a_global, dtype=np.float64).ravel()[self.cg.dofs_global]
+        a = np.asarray(a_global, dtype=np.float64).ravel()[self.solver.dofs_global]
         return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
 
-    def zeros(self):
-        return self.torch.zeros(self.ctx.n_dof, dtype=self.torch.float64, device=self.dev)
+    def _finish_force(self):
+        self.sc.exchange_force_(self.F, group=self.group)                # the one exchange of the hot path: interface forces
 
-    def new_ep(self):
-        return self.torch.zeros((4, self.ctx.n_int), dtype=self.torch.float64, device=self.dev)
-
-    def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False):
-        t = self.torch
-        st = t.cuda.current_stream(self.dev).cuda_stream
-        kd = None
-        if 'K' in want:
-            kd = t.empty(self.ctx.nnz, dtype=t.float64, device=self.dev) if keep_K else self.kd
-        logs = 's' in want or 'ind_p' in want
-        self.ctx.step_dev(st, U.data_ptr(), ep=0 if Ep is None else Ep.data_ptr(), accept=accept and Ep is not None, e0=e0,
-                          s=self.s.data_ptr() if 's' in want else 0, ind_p=self.ind.data_ptr() if 'ind_p' in want else 0,
-                          k_data=0 if kd is None else kd.data_ptr(), f_out=self.F.data_ptr() if 'F' in want else 0,
-                          counts=self.counts.data_ptr() if logs else 0)
-        if 'F' in want:
-            self.sc.exchange_force_(self.F, group=self.group)            # the one exchange of the hot path: interface forces
-        out = {k: v for k, v in {'K': kd, 'F': self.F, 's': self.s, 'ind_p': self.ind}.items() if k in want}
-        if logs:
-            c = _allreduce_(self.counts.clone(), self.group).cpu()
-            out['n_smooth'], out['n_apex'] = int(c[0]), int(c[1])
-        return out
-
-    def solve(self, K, rhs, criterion=None):
-        rtol = self.rtol
-        if self.inexact_rtol and criterion is not None:
-            rtol = max(self.rtol, self.inexact_rtol)
-        x = self.cg.pcg(K, rhs, rtol=rtol, max_iter=self.max_iter)
-        self.pcg_iters.append(self.cg.last['iters'])
-        if self.cg.last['state'] != 1:
-            x.fill_(float('nan'))
-        return x
-
-    def matvec(self, K, v):
-        return self.cg.spmv(K, v)
+    def _global_counts(self):
+        return _allreduce_(self.counts.clone(), self.group)
 
     def energy(self, K, v):
-        return float(self.torch.sqrt(self.cg.dot(v, self.cg.spmv(K, v))))
+        return float(self.torch.sqrt(self.solver.dot(v, self.solver.spmv(K, v))))
 
     def host(self, v):
         """The GLOBAL vector on every rank (every DOF from the ranks that hold it, weighted: they agree)."""
@@ -230,26 +191,15 @@ class _ShardOps:
         if v.dim() == 2:                                                 # point data (rows, n_int): this rank's slice only
             return v.cpu().numpy()
         g = t.zeros(self.n_dof_global, dtype=t.float64)
-        g[t.from_numpy(self.cg.dofs_global)] = (v * self.cg.w).cpu()
+        g[t.from_numpy(self.solver.dofs_global)] = (v * self.solver.w).cpu()
         return _allreduce_(g, self.group, self.dev).numpy()
 
     def nodal(self, q_int, elem_global, weight_local):
         """transform (DP:760-816) of a point field: numerators and denominators summed over the ranks, global nodal array."""
-        t = self.torch
-        le = self.sc.local_elements
-        n_p, n_e = le.shape
-        w = np.asarray(weight_local, dtype=float).ravel()
-        n_q = w.size // n_e
-        nodes = self.sc.nodes[np.repeat(le, n_q, axis=1)]
-        n_n = self.n_dof_global // 2
-        wq = w * q_int.cpu().numpy().ravel()
-        f = t.from_numpy(np.stack([np.bincount(nodes.ravel(), weights=np.tile(wq, n_p), minlength=n_n),
-                                   np.bincount(nodes.ravel(), weights=np.tile(w, n_p), minlength=n_n)]))
+        f = self.torch.from_numpy(np.stack(point_sums(q_int.cpu().numpy(), self.sc.nodes[self.sc.local_elements], weight_local,
+                                                      self.n_dof_global // 2)))
         _allreduce_(f, self.group, self.dev)
         return (f[0] / f[1]).numpy()
-
-    def close(self):
-        self.cg.close()
 
 
 def solve_strip_footing_sharded(element_type='P1', level=1, n_cells=None, size_xy=10, max_steps=None, zeta_max=1.0,
@@ -257,21 +207,13 @@ def solve_strip_footing_sharded(element_type='P1', level=1, n_cells=None, size_x
     """newton.solve_strip_footing on the ranks of the process group (torch.distributed initialised by the caller; a
     single process works too): the mesh is split by contiguous element ranges, every rank runs the hot path on its
     shard and the distributed conjugate gradients above solve the Newton corrections.  Returns the same history on every
-    rank ('U' holds GLOBAL displacement fields)."""
+    rank ('U' holds GLOBAL displacement fields; 'Ep' is the rank's own slice)."""
     import torch.distributed as dist
-    from . import newton
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
-    t = _coerce(element_type)
-    mesh = square_mesh(size_xy * 2 ** level if n_cells is None else n_cells, t, size_xy)
-    d1, d2, wf = element_tables(t)
-    holder = {}
-
-    def factory(elem, coord, dh1, dh2, w):
-        holder['sc'] = ShardedContext(elem, coord, rank, world, dh1, dh2, w, device=device)
-        return holder['sc'].ctx
-
-    def make_ops(ctx, qf, *a, **k):
-        return _ShardOps(holder['sc'], qf, rtol=pcg_rtol, inexact_rtol=pcg_inexact_rtol, group=group)
-    return newton.solve_strip_footing(element_type, level, n_cells, size_xy, max_steps, zeta_max, device, log, factory,
-                                      'pcg', pcg_rtol, keep_U, None, 1e-4, pcg_inexact_rtol, _ops_factory=make_ops)
+    mesh, sc, c0, t_setup = _footing_setup(element_type, level, n_cells, size_xy,
+                                           lambda elem, coord, *tab: ShardedContext(elem, coord, rank, world, *tab, device=device))
+    with closing(sc), closing(_ShardOps(sc, mesh['Q'].flatten(order='F'), rtol=pcg_rtol, inexact_rtol=pcg_inexact_rtol,
+                                        group=group)) as ops:
+        return _strip_footing(mesh=mesh, ctx=sc.ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
+                              zeta_max=zeta_max, keep_U=keep_U, log=log)

@@ -3,11 +3,13 @@ The Elasticity2D flavour end to end (EL:1052-1179): the square with a corner cut
 on its top side, one linear solve.  Mesh, elastic K (the hot path at U = 0), both load vectors (fep_load_volume_*,
 fep_load_traction_*), lifting of the prescribed displacement, solve on the free DOFs, stored energy.
 """
+from contextlib import closing
+
 import numpy as np
 
 from .hotpath import MeshContext, load_traction
 from .mesh import assemble_mesh_el
-from .newton import _make_ops
+from .newton import make_ops
 from .tables import LagrangeElementType, _coerce, element_tables, surface_tables
 
 
@@ -28,35 +30,25 @@ def solve_elasticity2d(element_type='P1', level=1, linear_solver='amg', volume_f
     d1, d2, wf = element_tables(t)
     ctx = MeshContext(elem, coord, d1, d2, wf, device=device)
     ctx.set_materials(young / (2 * (1 + poisson)), young / (3 * (1 - 2 * poisson)), 1.0, 1.0)
-    qf = Q.flatten(order='F')
-    ops = _make_ops(ctx, qf, linear_solver, pcg_rtol)
-    K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                              # EL:1118 (elastic at U = 0)
-    if linear_solver == 'amg':
-        ops.setup_amg(K, coord)
-    # load vectors (EL:1126-1138)
-    edges = mesh['neumann_nodes'].astype(np.int64)
-    hatp_s, dhatp1_s, wf_s = surface_tables(t)
-    t_int = np.repeat(np.asarray(traction_force, dtype=float).reshape(2, 1), edges.shape[1] * wf_s.size, axis=1)
-    f_t2 = load_traction(edges, coord, t_int, hatp_s, dhatp1_s, wf_s, device=ctx.device)
-    f_t = ops.vec(f_t2.flatten(order='F'))
-    if linear_solver == 'direct':
-        f_V = ops.vec(ctx.load_volume(uniform=volume_force).flatten(order='F'))
-    else:
-        f_V = ops.zeros()
-        ctx.load_volume_dev(ops.torch.cuda.current_stream(ops.dev).cuda_stream, f_V.data_ptr(), uniform=volume_force)
-    f_ext = f_t + f_V
-    ud = ops.vec((0.5 * mesh['dirichlet_nodes']).flatten(order='F'))                      # EL:1140
-    u = ud + ops.solve(K, f_ext - ops.matvec(K, ud))                                      # EL:1146-1160
-    energy = 0.5 * float(u @ ops.matvec(K, u)) - float(f_ext @ u)                         # EL:1172
-    iters = getattr(ops, 'pcg_iters', None)
-    out = {'U': ops.host(u).reshape((2, -1), order='F').copy(), 'energy': energy,
-           'f_V': ops.host(f_V).reshape((2, -1), order='F').copy(), 'f_t': f_t2,
-           'K': K if linear_solver == 'direct' else ctx.csr(ops.host(K)),
-           'iterations': None if not iters else int(iters[-1]), 'mesh': mesh}
+    with closing(ctx), closing(make_ops(ctx, Q.flatten(order='F'), linear_solver, pcg_rtol)) as ops:
+        K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                          # EL:1118 (elastic at U = 0)
+        ops.setup_amg(K, coord)                                                           # linear_solver='amg' only
+        # load vectors (EL:1126-1138)
+        edges = mesh['neumann_nodes'].astype(np.int64)
+        hatp_s, dhatp1_s, wf_s = surface_tables(t)
+        t_int = np.repeat(np.asarray(traction_force, dtype=float).reshape(2, 1), edges.shape[1] * wf_s.size, axis=1)
+        f_t2 = load_traction(edges, coord, t_int, hatp_s, dhatp1_s, wf_s, device=ctx.device)
+        f_t = ops.vec(f_t2.flatten(order='F'))
+        f_V = ops.load_volume(volume_force)
+        f_ext = f_t + f_V
+        ud = ops.vec((0.5 * mesh['dirichlet_nodes']).flatten(order='F'))                  # EL:1140
+        u = ud + ops.solve(K, f_ext - ops.matvec(K, ud))                                  # EL:1146-1160
+        energy = 0.5 * float(u @ ops.matvec(K, u)) - float(f_ext @ u)                     # EL:1172
+        out = {'U': ops.host(u).reshape((2, -1), order='F').copy(), 'energy': energy,
+               'f_V': ops.host(f_V).reshape((2, -1), order='F').copy(), 'f_t': f_t2, 'K': ops.csr(K),
+               'iterations': None if not ops.pcg_iters else int(ops.pcg_iters[-1]), 'mesh': mesh}
     if log:
         log(f'Stored energy: {energy!r}')
-    ops.close()
-    ctx.close()
     return out
 
 

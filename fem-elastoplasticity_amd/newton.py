@@ -6,8 +6,12 @@ re-stated around the GPU step.
   solve_tsx_tunnel      tsx-tunnel/pythonFEM.py:1729-1832      (17 uniform steps of the initial-stress factor;
                         the accepting call leaves `apply_plastic_strain` False)
 
+Both run ONE loop, `_load_step_loop`: load steps, the Newton iteration with its stopping norms, accept / halve and the
+extrapolation of the next iterate, following the reference line by line.  A driver hands it what its flavour does
+differently: first step and smallest step, the initial strain of a step, the accepting call and what is recorded from
+it, whether the step grows, when to stop.  The loop works on an ops object (`make_ops`): host arrays and a sparse direct
+solve, or device tensors and conjugate gradients; dist_newton.py derives the element-sharded ops from the device ones.
 Per Newton iterate ONE call of the fused step replaces DP:1043-1058 (strain, return map, tangent, residual).
-Step control, stopping norms and the extrapolation of the next iterate follow the reference line by line.
 The linear solve (the reference's dense `np.linalg.solve` on a (2 n_n)^2 boolean-masked matrix) is
   linear_solver='direct'  SciPy SuperLU on the host CSR matrix (K travels to the host every iterate), or
   linear_solver='pcg'     conjugate gradients on the GPU (solver.py, block-Jacobi preconditioner); the iterate, K, F,
@@ -23,6 +27,7 @@ states are the same to the Newton tolerance either way.
 with `np.bincount` on the host and as `fep_transform_dev` on the device.
 """
 import time
+from contextlib import closing
 
 import numpy as np
 import scipy.sparse.linalg as sspl
@@ -32,21 +37,28 @@ from .mesh import square_mesh
 from .tables import ELEMENT_SHAPE, _coerce, element_tables
 
 
-def transform(q_int, elements, weight):
-    """Integration-point values -> nodal values, weighted average over the adjacent points (DP:760-816)."""
+def point_sums(q_int, elements, weight, n_n=None):
+    """Per node, over the adjacent integration points: sum of w*q and sum of w (the two accumulations of DP:760-816).
+    `n_n` defaults to the highest node of `elements` + 1."""
     n_p, n_e = elements.shape
     w = np.asarray(weight, dtype=float).ravel()
-    n_q = w.size // n_e
-    nodes = np.repeat(np.asarray(elements), n_q, axis=1)                 # (n_p, n_int)
-    n_n = int(nodes.max()) + 1
+    nodes = np.repeat(np.asarray(elements), w.size // n_e, axis=1)       # (n_p, n_int)
+    if n_n is None:
+        n_n = int(nodes.max()) + 1
     wq = w * np.asarray(q_int, dtype=float).ravel()
-    f1 = np.bincount(nodes.ravel(), weights=np.tile(wq, n_p), minlength=n_n)
-    f2 = np.bincount(nodes.ravel(), weights=np.tile(w, n_p), minlength=n_n)
+    return (np.bincount(nodes.ravel(), weights=np.tile(wq, n_p), minlength=n_n),
+            np.bincount(nodes.ravel(), weights=np.tile(w, n_p), minlength=n_n))
+
+
+def transform(q_int, elements, weight):
+    """Integration-point values -> nodal values, weighted average over the adjacent points (DP:760-816)."""
+    f1, f2 = point_sums(q_int, elements, weight)
     return f1 / f2
 
 
 class _HostOps:
     """Vectors as ndarrays, K as csr_matrix, sparse direct solve."""
+    pcg_iters = None
 
     def __init__(self, ctx, qf):
         self.ctx, self.qf = ctx, qf
@@ -55,7 +67,7 @@ class _HostOps:
         return np.array(a, dtype=np.float64).ravel()
 
     def zeros(self):
-        return np.zeros(self.ctx.n_dof if hasattr(self.ctx, 'n_dof') else self.qf.size)
+        return np.zeros(self.qf.size)
 
     def new_ep(self):
         return np.zeros((4, self.ctx.n_int))
@@ -63,6 +75,9 @@ class _HostOps:
     def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False):
         kw = {} if e0 is None else {'e0': e0}
         return self.ctx.step(U, Ep, apply_plastic_strain=accept, want=want, **kw)
+
+    def setup_amg(self, K, coordinates):
+        pass
 
     def solve(self, K, rhs, criterion=None):
         rhs = np.asarray(rhs).ravel()
@@ -79,8 +94,14 @@ class _HostOps:
     def host(self, v):
         return np.asarray(v)
 
+    def csr(self, K):
+        return K
+
     def nodal(self, q_int, elem, weight):
         return transform(self.host(q_int), elem, weight)
+
+    def load_volume(self, uniform):
+        return self.vec(self.ctx.load_volume(uniform=uniform).flatten(order='F'))
 
     def close(self):
         pass
@@ -88,15 +109,14 @@ class _HostOps:
 
 class _DeviceOps:
     """Vectors, K data, plastic strain and stresses as device tensors; `MeshContext.step_dev` writes them and
-    `KrylovSolver.pcg` solves on them.  A linear solve that breaks down or runs out of iterations yields NaNs,
-    which the drivers treat like the reference treats a NaN criterion (DP:1076): the load step is halved."""
+    `solver.pcg` (KrylovSolver; dist_newton.DistributedPCG in the subclass there) solves on them.  A linear solve that
+    breaks down or runs out of iterations yields NaNs, which the load-step loop treats like the reference treats a NaN
+    criterion (DP:1076): the load step is halved."""
 
-    def __init__(self, ctx, qf, rtol=1e-11, max_iter=200000, forcing=None, forcing_cap=1e-4, inexact_rtol=None):
+    def __init__(self, ctx, solver, rtol=1e-11, max_iter=200000, forcing=None, forcing_cap=1e-4, inexact_rtol=None, amg=False):
         import torch
-        from .solver import KrylovSolver
-        self.torch, self.ctx, self.qf = torch, ctx, qf
+        self.torch, self.ctx, self.solver, self.amg = torch, ctx, solver, amg
         self.dev = torch.device('cuda', ctx.device)
-        self.solver = KrylovSolver(ctx, qf)
         self.rtol, self.max_iter, self.forcing, self.forcing_cap = rtol, max_iter, forcing, forcing_cap
         self.inexact_rtol = inexact_rtol
         f64 = dict(dtype=torch.float64, device=self.dev)
@@ -108,6 +128,9 @@ class _DeviceOps:
         self.tmp = torch.empty(ctx.n_dof, **f64)
         self.pcg_iters = []
 
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
     def vec(self, a):
         return self.torch.from_numpy(np.array(a, dtype=np.float64).ravel()).to(self.dev)
 
@@ -117,28 +140,37 @@ class _DeviceOps:
     def new_ep(self):
         return self.torch.zeros((4, self.ctx.n_int), dtype=self.torch.float64, device=self.dev)
 
+    def _finish_force(self):
+        """F as the step kernels left it is the whole internal force (the sharded subclass sums the interface)."""
+
+    def _global_counts(self):
+        return self.counts
+
     def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False):
         t = self.torch
-        st = t.cuda.current_stream(self.dev).cuda_stream
         kd = None
         if 'K' in want:
             kd = t.empty(self.ctx.nnz, dtype=t.float64, device=self.dev) if keep_K else self.kd
-        self.ctx.step_dev(st, U.data_ptr(), ep=0 if Ep is None else Ep.data_ptr(), accept=accept and Ep is not None,
-                          e0=e0, s=self.s.data_ptr() if 's' in want else 0,
+        logs = 's' in want or 'ind_p' in want                  # accepting calls: the counters are logged
+        self.ctx.step_dev(self._stream(), U.data_ptr(), ep=0 if Ep is None else Ep.data_ptr(),
+                          accept=accept and Ep is not None, e0=e0, s=self.s.data_ptr() if 's' in want else 0,
                           ind_p=self.ind.data_ptr() if 'ind_p' in want else 0,
                           k_data=0 if kd is None else kd.data_ptr(), f_out=self.F.data_ptr() if 'F' in want else 0,
-                          counts=self.counts.data_ptr() if ('s' in want or 'ind_p' in want) else 0)   # logged on accepting calls only
+                          counts=self.counts.data_ptr() if logs else 0)
+        if 'F' in want:
+            self._finish_force()
         out = {'K': kd, 'F': self.F, 's': self.s, 'ind_p': self.ind}
         out = {k: v for k, v in out.items() if k in want}
-        if 's' in want or 'ind_p' in want:                     # accepting calls: the counters are logged
-            c = self.counts.cpu()
+        if logs:
+            c = self._global_counts().cpu()
             out['n_smooth'], out['n_apex'] = int(c[0]), int(c[1])
         return out
 
     def setup_amg(self, K, coordinates):
         # built once from K_elast; rebuilding it from the current tangent when the plastic zone grows was measured
         # (1 M elements, 10 load steps: 6 rebuilds) and did not lower the iteration counts
-        self.solver.setup_amg(self.host(K), coordinates, k_dev=K)
+        if self.amg:
+            self.solver.setup_amg(self.host(K), coordinates, k_dev=K)
 
     def solve(self, K, rhs, criterion=None):
         # inexact Newton: while the iterate is far from converged the correction need not be solved to 11 digits.
@@ -165,36 +197,91 @@ class _DeviceOps:
     def host(self, v):
         return v.cpu().numpy()
 
+    def csr(self, K):
+        return self.ctx.csr(self.host(K))
+
     def nodal(self, q_int, elem, weight):
         t = self.torch
         q = q_int.contiguous()
         out = t.empty(self.ctx.n_n, dtype=t.float64, device=self.dev)
-        self.ctx.transform_dev(t.cuda.current_stream(self.dev).cuda_stream, q.data_ptr(), out.data_ptr())
+        self.ctx.transform_dev(self._stream(), q.data_ptr(), out.data_ptr())
         return out.cpu().numpy()
+
+    def load_volume(self, uniform):
+        f = self.zeros()
+        self.ctx.load_volume_dev(self._stream(), f.data_ptr(), uniform=uniform)
+        return f
 
     def close(self):
         self.solver.close()
 
 
-def _make_ops(ctx, qf, linear_solver, pcg_rtol, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None):
+def make_ops(ctx, qf, linear_solver, pcg_rtol, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None):
+    """The vector / step / solve operations of a driver for `linear_solver` and its options (module docstring)."""
     if linear_solver == 'direct':
         return _HostOps(ctx, qf)
     if linear_solver in ('pcg', 'amg'):
         if not isinstance(ctx, MeshContext):
             raise ValueError(f"linear_solver='{linear_solver}' needs the GPU MeshContext")
-        return _DeviceOps(ctx, qf, rtol=pcg_rtol, forcing=pcg_forcing, forcing_cap=pcg_forcing_cap, inexact_rtol=pcg_inexact_rtol)
+        from .solver import KrylovSolver
+        return _DeviceOps(ctx, KrylovSolver(ctx, qf), rtol=pcg_rtol, forcing=pcg_forcing, forcing_cap=pcg_forcing_cap,
+                          inexact_rtol=pcg_inexact_rtol, amg=linear_solver == 'amg')
     raise ValueError("linear_solver must be 'direct', 'pcg' or 'amg'")
 
 
-def solve_strip_footing(element_type='P1', level=1, n_cells=None, size_xy=10, max_steps=None, zeta_max=1.0,
-                        device=None, log=None, context_factory=None, linear_solver='direct', pcg_rtol=1e-11,
-                        keep_U=True, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None, _ops_factory=None):
-    """Strip-footing benchmark of Plasticity2D_DP (DP:901-1131).  `level` as in the reference
-    (N = size_xy * 2**level cells per side) or `n_cells` directly.  Returns a dict with the load history
-    ('zeta', 'pressure'), the accepted displacements 'U' (list of (2,n_n)), final 'Ep', counters.
-    `context_factory(elements, coordinates, dhatp1, dhatp2, wf)` may supply another object with MeshContext's
-    `set_materials / step / geometry / close` (the tests drive the same loop with their CPU checker that way);
-    `_ops_factory` supplies the vector / solve operations (dist_newton.py runs this loop on an element-sharded mesh)."""
+def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, accept_kw, accepted, finished):
+    """The load-step loop with its semismooth-Newton iteration, for both flavours (DP:1031-1127, TSX:1765-1826).
+    `U_it`: the starting iterate.  Per flavour: `e0_of(zeta)` the initial strain of a step (or None), `accept_kw` the
+    arguments of the accepting call of the step, `accepted(r, zeta, U, Ep_old, its, criterion)` records the step from
+    that call's result `r` and returns (the plastic strain to go on with, whether the step may grow),
+    `finished(zeta_old)` the flavour's stop besides `d_zeta_min`.  Returns the last accepted U and plastic strain."""
+    d_zeta_old = d_zeta
+    zeta_old = 0.0
+    U = ops.zeros()
+    U_old = -U_it
+    Ep_old = ops.new_ep()
+    criterion = None
+    while True:
+        zeta = zeta_old + d_zeta                                                          # DP:1031
+        e0 = e0_of(zeta)                                                                  # TSX:1765
+        its = 0
+        for _ in range(25):                                                               # DP:1040
+            r = ops.step(U_it, Ep_old, e0=e0, want=('K', 'F'))                            # DP:1043-1058, TSX:1771-1778
+            hist['n_calls'] += 1
+            its += 1
+            dU = ops.solve(r['K'], -r['F'], criterion if its > 1 else 1.0)                # DP:1062-1066, TSX:1781
+            U_new = U_it + dU
+            q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)   # DP:1072-1074
+            criterion = q1 / (q2 + q3)                                                    # TSX:1788-1792
+            if np.isnan(criterion):                                                       # DP:1076
+                break
+            U_it = U_new
+            if criterion < 1e-12:                                                         # DP:1086
+                break
+        if criterion < 1e-10:                                                             # DP:1091, TSX:1804
+            U_old = U
+            U = U_it
+            r = ops.step(U, Ep_old, e0=e0, **accept_kw)                                   # DP:1095-1098, TSX:1809
+            hist['n_calls'] += 1
+            zeta_old = zeta
+            d_zeta_old = d_zeta
+            hist['zeta'].append(zeta)
+            Ep_old, grow = accepted(r, zeta, U, Ep_old, its, criterion)
+            if grow:
+                d_zeta *= 2                                                               # DP:1109
+        else:
+            d_zeta /= 2                                                                   # DP:1117, TSX:1818
+        U_it = d_zeta * (U - U_old) / d_zeta_old + U                                      # DP:1120, TSX:1821
+        if finished(zeta_old) or d_zeta < d_zeta_min:                                     # DP:1123-1127, TSX:1824
+            return U, Ep_old
+
+
+def _context_maker(context_factory, device):
+    return context_factory or (lambda *a: MeshContext(*a, device=device))
+
+
+def _footing_setup(element_type, level, n_cells, size_xy, make_context):
+    """Mesh and context (materials set) of the strip-footing benchmark (DP:910-945), `c0`, and the times for the log."""
     t = _coerce(element_type)
     young, poisson, c0, phi = 1e7, 0.48, 450, np.pi / 9                                   # DP:910-933
     shear0 = young / (2 * (1 + poisson))
@@ -204,19 +291,34 @@ def solve_strip_footing(element_type='P1', level=1, n_cells=None, size_xy=10, ma
     t_setup = [time.perf_counter()]
     mesh = square_mesh(size_xy * 2 ** level if n_cells is None else n_cells, t, size_xy)  # DP:945
     t_setup.append(time.perf_counter())
-    elem, coord, Q = mesh['elements'], mesh['coordinates'], mesh['Q']
-    q_nd = mesh['dirichlet_nodes'][1, :] > 0
-    n_n = coord.shape[1]
-    d1, d2, wf = element_tables(t)
-    ctx = (context_factory or (lambda *a: MeshContext(*a, device=device)))(elem, coord, d1, d2, wf)
+    ctx = make_context(mesh['elements'], mesh['coordinates'], *element_tables(t))
     ctx.set_materials(shear0, bulk0, eta0, c_0)
-    qf = Q.flatten(order='F')
     t_setup.append(time.perf_counter())
-    ops = (_ops_factory or _make_ops)(ctx, qf, linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap, pcg_inexact_rtol)
+    return mesh, ctx, c0, t_setup
+
+
+def solve_strip_footing(element_type='P1', level=1, n_cells=None, size_xy=10, max_steps=None, zeta_max=1.0,
+                        device=None, log=None, context_factory=None, linear_solver='direct', pcg_rtol=1e-11,
+                        keep_U=True, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None):
+    """Strip-footing benchmark of Plasticity2D_DP (DP:901-1131).  `level` as in the reference
+    (N = size_xy * 2**level cells per side) or `n_cells` directly.  Returns a dict with the load history
+    ('zeta', 'pressure'), the accepted displacements 'U' (list of (2,n_n)), final 'Ep', counters.
+    `context_factory(elements, coordinates, dhatp1, dhatp2, wf)` may supply another object with MeshContext's
+    `set_materials / step / geometry / close` (the tests drive the same loop with their CPU checker that way)."""
+    mesh, ctx, c0, t_setup = _footing_setup(element_type, level, n_cells, size_xy, _context_maker(context_factory, device))
+    with closing(ctx), closing(make_ops(ctx, mesh['Q'].flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing,
+                                        pcg_forcing_cap, pcg_inexact_rtol)) as ops:
+        return _strip_footing(mesh=mesh, ctx=ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
+                              zeta_max=zeta_max, keep_U=keep_U, log=log)
+
+
+def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, log):
+    """solve_strip_footing once mesh, context and ops exist (dist_newton.py enters here with its sharded ones)."""
+    elem, coord = mesh['elements'], mesh['coordinates']
+    q_nd = mesh['dirichlet_nodes'][1, :] > 0
     K_elast = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                        # DP:977
     t_setup.append(time.perf_counter())
-    if linear_solver == 'amg':
-        ops.setup_amg(K_elast, coord)
+    ops.setup_amg(K_elast, coord)                                                         # linear_solver='amg' only
     _, _, weight, _ = ctx.geometry()
     t_setup.append(time.perf_counter())
     if log:
@@ -224,77 +326,42 @@ def solve_strip_footing(element_type='P1', level=1, n_cells=None, size_xy=10, ma
             % tuple(b - a for a, b in zip(t_setup[:-1], t_setup[1:])))
 
     d_zeta = 1 / 1000                                                                     # DP:989-994
-    d_zeta_min = d_zeta / 1300
-    d_zeta_old = d_zeta
-    zeta_old = 0.0
     Ud = ops.vec((-d_zeta * mesh['dirichlet_nodes']).flatten(order='F'))                  # DP:997-1004
     U_it = Ud + ops.solve(K_elast, -ops.matvec(K_elast, Ud))
-    U = ops.zeros()
-    U_old = -U_it
-    Ep_old = ops.new_ep()
-    pressure_old = 0.0
     hist = {'zeta': [], 'pressure': [], 'U': [], 'counts': [], 'n_calls': 0, 'newton_its': []}
-    criterion = None
-    while True:
-        zeta = zeta_old + d_zeta                                                          # DP:1031
-        its = 0
-        for _ in range(25):                                                               # DP:1040
-            r = ops.step(U_it, Ep_old, accept=False, want=('K', 'F'))                     # DP:1043-1058
-            hist['n_calls'] += 1
-            its += 1
-            dU = ops.solve(r['K'], -r['F'], criterion if its > 1 else 1.0)                # DP:1062-1066
-            U_new = U_it + dU
-            q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)   # DP:1072-1074
-            criterion = q1 / (q2 + q3)
-            if np.isnan(criterion):                                                       # DP:1076
-                break
-            U_it = U_new
-            if criterion < 1e-12:                                                         # DP:1086
-                break
-        if criterion < 1e-10:                                                             # DP:1091
-            U_old = U
-            U = U_it
-            r = ops.step(U, Ep_old, accept=True, want=('s',))                             # DP:1095-1098
-            hist['n_calls'] += 1
-            zeta_old = zeta
-            d_zeta_old = d_zeta
-            pressure_arr = ops.nodal(r['s'][1, :], elem, weight)                          # DP:1105
-            pressure = -np.mean(pressure_arr[q_nd]) / c0
-            hist['zeta'].append(zeta)
-            hist['pressure'].append(pressure)
-            if keep_U:
-                hist['U'].append(ops.host(U).reshape((2, -1), order='F').copy())
-            hist['counts'].append((r['n_smooth'], r['n_apex']))
-            hist['newton_its'].append(its)
-            if log:
-                log(f'zeta={zeta:.6g} pressure={pressure:.10g} its={its} smooth/apex={r["n_smooth"]}/{r["n_apex"]}')
-            if pressure - pressure_old < 0.1 and criterion < 1e-12:                       # DP:1109
-                d_zeta *= 2
-            pressure_old = pressure
-        else:
-            d_zeta /= 2                                                                   # DP:1117
-        U_it = d_zeta * (U - U_old) / d_zeta_old + U                                      # DP:1120
-        if zeta_old >= zeta_max:                                                          # DP:1123
-            break
-        if d_zeta < d_zeta_min:                                                           # DP:1127
-            break
-        if max_steps is not None and len(hist['zeta']) >= max_steps:
-            break
+
+    def accepted(r, zeta, U, Ep_old, its, criterion):                                     # Ep_old was updated in place
+        pressure_old = hist['pressure'][-1] if hist['pressure'] else 0.0
+        pressure_arr = ops.nodal(r['s'][1, :], elem, weight)                              # DP:1105
+        pressure = -np.mean(pressure_arr[q_nd]) / c0
+        hist['pressure'].append(pressure)
+        if keep_U:
+            hist['U'].append(ops.host(U).reshape((2, -1), order='F').copy())
+        hist['counts'].append((r['n_smooth'], r['n_apex']))
+        hist['newton_its'].append(its)
+        if log:
+            log(f'zeta={zeta:.6g} pressure={pressure:.10g} its={its} smooth/apex={r["n_smooth"]}/{r["n_apex"]}')
+        return Ep_old, pressure - pressure_old < 0.1 and criterion < 1e-12                # DP:1109
+
+    def finished(zeta_old):                                                               # DP:1123
+        return zeta_old >= zeta_max or (max_steps is not None and len(hist['zeta']) >= max_steps)
+
+    U, Ep_old = _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta / 1300, hist, e0_of=lambda zeta: None,
+                                accept_kw=dict(accept=True, want=('s',)), accepted=accepted, finished=finished)
     hist['Ep'] = ops.host(Ep_old)
     hist['U_last'] = ops.host(U).reshape((2, -1), order='F').copy()
     hist['mesh'] = mesh
-    hist['pcg_iters'] = getattr(ops, 'pcg_iters', None)
-    ops.close()
-    ctx.close()
+    hist['pcg_iters'] = ops.pcg_iters
     return hist
 
 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
-                     linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None):
+                     linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
+                     pcg_forcing_cap=1e-4, context_factory=None):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
-    displacements."""
+    displacements.  `context_factory` as in solve_strip_footing (the object also needs `assemble` and `n_int`)."""
     t = _coerce(element_type)
     if mesh_dir is not None:
         from .meshio import load_tsx_mesh
@@ -316,68 +383,33 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     Q[0, coords[0, :] > 49.99] = 0
     Q[1, coords[1, :] < -49.99] = 0
     Q[1, coords[1, :] > 49.99] = 0
-    qf = Q.flatten(order='F')
-    d1, d2, wf = element_tables(t)
-    ctx = MeshContext(elem, coords, d1, d2, wf, device=device)
+    ctx = _context_maker(context_factory, device)(elem, coords, *element_tables(t))
     n_int = ctx.n_int
     assert n_int == elem.shape[1] * ELEMENT_SHAPE[t][1]
     ctx.set_materials(shear0, bulk0, eta0, c_0)
-    ops = _make_ops(ctx, qf, linear_solver, pcg_rtol, pcg_forcing, pcg_inexact_rtol=pcg_inexact_rtol)
-    K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                              # TSX:1722
-    if linear_solver == 'amg':
-        ops.setup_amg(K, coords)
-    _, F0 = ctx.assemble(None, s0 * np.ones((1, n_int)))                                   # TSX:1737
+    with closing(ctx), closing(make_ops(ctx, Q.flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
+                                        pcg_inexact_rtol)) as ops:
+        K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                          # TSX:1722
+        ops.setup_amg(K, coords)                                                          # linear_solver='amg' only
+        _, F0 = ctx.assemble(None, s0 * np.ones((1, n_int)))                               # TSX:1737
 
-    d_zeta = 1 / n_load_steps                                                             # TSX:1730-1735
-    d_zeta_min = d_zeta / 10
-    d_zeta_old = d_zeta
-    zeta_old = 0.0
-    U_elast = ops.solve(K, ops.vec(-F0))                                                  # TSX:1748
-    U_it = d_zeta * U_elast
-    U = ops.zeros()
-    U_old = -U_it
-    Ep_old = ops.new_ep()
-    hist = {'zeta': [], 'displ': [], 'n_plast': [], 'U': [], 'n_calls': 0}
-    criterion = None
-    while True:
-        zeta = zeta_old + d_zeta
-        e0 = zeta * init_strain                                                           # TSX:1765
-        for it in range(25):
-            r = ops.step(U_it, Ep_old, e0=e0, want=('K', 'F'))                            # TSX:1771-1778
-            hist['n_calls'] += 1
-            dU = ops.solve(r['K'], -r['F'], criterion if it > 0 else 1.0)                 # TSX:1781
-            U_new = U_it + dU
-            criterion = ops.energy(K, dU) / (ops.energy(K, U_it) + ops.energy(K, U_new))  # TSX:1788-1792
-            if np.isnan(criterion):
-                break
-            U_it = U_new
-            if criterion < 1e-12:
-                break
-        if criterion < 1e-10:                                                             # TSX:1804
-            U_old = U
-            U = U_it
-            r = ops.step(U, Ep_old, e0=e0, want=('ind_p',))          # accept WITHOUT apply_plastic_strain (C7)
-            hist['n_calls'] += 1
-            Ep_old = ops.new_ep()                                    # 'ep' of a non-accepting call, TSX:1809
-            zeta_old = zeta
-            d_zeta_old = d_zeta
+        d_zeta = 1 / n_load_steps                                                         # TSX:1730-1735
+        U_elast = ops.solve(K, ops.vec(-F0))                                              # TSX:1748
+        hist = {'zeta': [], 'displ': [], 'n_plast': [], 'U': [], 'n_calls': 0}
+
+        def accepted(r, zeta, U, Ep_old, its, criterion):
             Um = ops.host(U).reshape((2, -1), order='F')
-            hist['zeta'].append(zeta)
             hist['displ'].append(Um[monitor])
             hist['n_plast'].append(int(ops.host(r['ind_p']).astype(bool).sum()))
             hist['U'].append(Um.copy())
             if log:
                 log(f'zeta={zeta:.6g} U{monitor}={Um[monitor]:.16g} n_plast={hist["n_plast"][-1]}')
-        else:
-            d_zeta = d_zeta / 2                                                           # TSX:1818
-        U_it = d_zeta * (U - U_old) / d_zeta_old + U                                      # TSX:1821
-        if zeta_old >= 1:                                                                 # TSX:1824
-            break
-        if d_zeta < d_zeta_min:
-            break
-    hist['F0'] = F0.reshape((2, -1), order='F')
-    hist['Q'] = Q
-    hist['pcg_iters'] = getattr(ops, 'pcg_iters', None)
-    ops.close()
-    ctx.close()
-    return hist
+            return ops.new_ep(), False                               # 'ep' of a non-accepting call, TSX:1809
+
+        # the accepting call leaves apply_plastic_strain False (C7)
+        _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
+                        accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
+        hist['F0'] = F0.reshape((2, -1), order='F')
+        hist['Q'] = Q
+        hist['pcg_iters'] = ops.pcg_iters
+        return hist
