@@ -63,6 +63,13 @@ PROTOTYPES = {
     'fep_load_volume_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     'fep_load_traction_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 7),
     'fep_load_traction_host': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    'fep_mesh_create': (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    'fep_mesh_destroy': (C.c_int, [C.c_void_p]),
+    'fep_mesh_info': (C.c_int, [C.c_void_p, c_i64_p]),
+    'fep_mesh_enrich_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    'fep_mesh_enrich_host': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    'fep_mesh_refine_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_refine_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_solver_create': (C.c_int, [c_void_pp, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_solver_destroy': (C.c_int, [C.c_void_p]),
     'fep_solver_sizes': (C.c_int, [C.c_void_p, c_i64_p]),

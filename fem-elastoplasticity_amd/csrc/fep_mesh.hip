@@ -1,0 +1,554 @@
+// Triangle-mesh operations that run before any context exists (include/fep.h, "mesh"): edge matching, the P1 -> P2 / P4
+// enrichment with the reference's node numbering (TSX:1354-1626) and uniform refinement.
+//
+// The sequential numbering of the reference (first element to see an edge creates its nodes) has an order-free form on
+// edge-manifold, consistently oriented meshes: a half-edge owns its edge iff it has no neighbour or its element id is the
+// lower one, and the k-th owned slot of element i (in the reference's visit order) gets index base_i + k, base = the
+// exclusive prefix sum of the owned counts.  Everything below computes that form; nothing depends on the order in which
+// lanes run (integer atomics only where the outcome is order-free: counts, cursors into lists whose order is not observed).
+//
+// Edge k of an element runs from vertex k to vertex (k + 1) % 3.  P2 visits the edges in the order 1, 2, 0 (slots V2V3, V3V1,
+// V1V2: TSX:1530, 1561, 1591), P4 in the order 0, 1, 2 (TSX:1386, 1424, 1463).
+#include "fep_common.h"
+
+#include <new>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kScanItems = 4;
+constexpr int kScanTile = kBlock * kScanItems;
+
+inline unsigned grid_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// counters of fep_mesh_create
+enum { C_RANGE = 0, C_DEGENERATE, C_NONMANIFOLD, C_INCONSISTENT, C_COUNT };
+
+__device__ __forceinline__ bool load_tri(const int32_t* __restrict__ elem, int64_t n_e, int64_t n_n, int64_t i, int32_t v[3]) {
+    v[0] = elem[i];
+    v[1] = elem[n_e + i];
+    v[2] = elem[2 * n_e + i];
+    const bool in_range = v[0] >= 0 && v[0] < n_n && v[1] >= 0 && v[1] < n_n && v[2] >= 0 && v[2] < n_n;
+    return in_range && v[0] != v[1] && v[1] != v[2] && v[2] != v[0];
+}
+
+// elements per node; elements with an id outside [0, n_n) or a repeated vertex are counted and take no further part
+__global__ void __launch_bounds__(kBlock) mesh_degree_kernel(int64_t n_e, int64_t n_n, const int32_t* __restrict__ elem,
+                                                             int32_t* __restrict__ deg, int32_t* __restrict__ counters) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_e) return;
+    int32_t v[3];
+    if (!load_tri(elem, n_e, n_n, i, v)) {
+        const bool in_range = v[0] >= 0 && v[0] < n_n && v[1] >= 0 && v[1] < n_n && v[2] >= 0 && v[2] < n_n;
+        atomicAdd(&counters[in_range ? C_DEGENERATE : C_RANGE], 1);
+        return;
+    }
+    for (int k = 0; k < 3; ++k) atomicAdd(&deg[v[k]], 1);
+}
+
+// list of node v = [ptr[v], ptr[v + 1]) holds 3 * element + position of v in it, in no particular order
+__global__ void __launch_bounds__(kBlock) mesh_fill_kernel(int64_t n_e, int64_t n_n, const int32_t* __restrict__ elem,
+                                                           const int32_t* __restrict__ ptr, int32_t* __restrict__ cursor,
+                                                           int32_t* __restrict__ list) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_e) return;
+    int32_t v[3];
+    if (!load_tri(elem, n_e, n_n, i, v)) return;
+    for (int k = 0; k < 3; ++k) {
+        const int32_t at = atomicAdd(&cursor[v[k]], 1);
+        const int32_t lo = ptr[v[k]], hi = ptr[v[k] + 1];
+        if (at < hi - lo) list[lo + at] = (int32_t)(3 * i + k);
+    }
+}
+
+// One lane per element, its three edges in turn: the other elements that hold both ends, found in the list of the start
+// vertex (a loop of the node's degree).  mask: bit k = edge k is owned, bit 3 + k = edge k is a boundary edge.
+// nbr[k * n_e + i] = 3 * j + (edge of j that is the same edge), -1 on the boundary.
+__global__ void __launch_bounds__(kBlock) mesh_match_kernel(int64_t n_e, int64_t n_n, const int32_t* __restrict__ elem,
+                                                            const int32_t* __restrict__ ptr, const int32_t* __restrict__ list,
+                                                            int32_t* __restrict__ nbr, uint8_t* __restrict__ mask,
+                                                            int32_t* __restrict__ n_own, int32_t* __restrict__ n_bnd,
+                                                            int32_t* __restrict__ counters) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_e) return;
+    int32_t v[3];
+    const bool ok = load_tri(elem, n_e, n_n, i, v);
+    int m = 0, c_own = 0, c_bnd = 0;
+    for (int k = 0; k < 3; ++k) {
+        int32_t found = -1;
+        if (ok) {
+            const int32_t A = v[k], B = v[(k + 1) % 3];
+            int n_match = 0, n_same_way = 0;
+            int64_t j_min = n_e;
+            const int32_t lo = ptr[A], hi = ptr[A + 1];
+            for (int32_t q = lo; q < hi; ++q) {
+                const int32_t code = list[q];
+                const int64_t j = code / 3;
+                const int p = code % 3;
+                if (j == i) continue;
+                const int32_t before = elem[(int64_t)((p + 2) % 3) * n_e + j];      // j walks before -> A -> after
+                const int32_t after = elem[(int64_t)((p + 1) % 3) * n_e + j];
+                if (before == B) {
+                    found = (int32_t)(3 * j + (p + 2) % 3);
+                } else if (after == B) {
+                    found = (int32_t)(3 * j + p);
+                    ++n_same_way;
+                } else {
+                    continue;
+                }
+                ++n_match;
+                j_min = j < j_min ? j : j_min;
+            }
+            if (n_match == 0) {
+                m |= (1 << k) | (8 << k);
+                ++c_own;
+                ++c_bnd;
+            } else if (n_match == 1) {
+                if (i < j_min) {
+                    m |= 1 << k;
+                    ++c_own;
+                    if (n_same_way) atomicAdd(&counters[C_INCONSISTENT], 1);
+                }
+            } else if (i < j_min) {
+                atomicAdd(&counters[C_NONMANIFOLD], 1);                               // once per edge: by its lowest element
+            }
+        }
+        nbr[(int64_t)k * n_e + i] = found;
+    }
+    mask[i] = (uint8_t)m;
+    n_own[i] = c_own;
+    n_bnd[i] = c_bnd;
+}
+
+// ---- exclusive prefix sum of int32, any length: block scan, scan of the block sums (recursively), add ---------------------
+__global__ void __launch_bounds__(kBlock) scan_tile_kernel(int64_t n, int32_t* __restrict__ data, int32_t* __restrict__ sums) {
+    __shared__ int32_t lds[kBlock];
+    const int64_t first = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+    int32_t x[kScanItems];
+    int32_t acc = 0;
+    for (int r = 0; r < kScanItems; ++r) {
+        x[r] = first + r < n ? data[first + r] : 0;
+        acc += x[r];
+    }
+    lds[threadIdx.x] = acc;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d *= 2) {
+        const int32_t other = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
+        __syncthreads();
+        lds[threadIdx.x] += other;
+        __syncthreads();
+    }
+    int32_t run = lds[threadIdx.x] - acc;
+    for (int r = 0; r < kScanItems; ++r) {
+        if (first + r < n) data[first + r] = run;
+        run += x[r];
+    }
+    if (threadIdx.x == kBlock - 1) sums[blockIdx.x] = lds[kBlock - 1];
+}
+
+__global__ void __launch_bounds__(kBlock) scan_add_kernel(int64_t n, int32_t* __restrict__ data, const int32_t* __restrict__ sums) {
+    const int64_t first = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+    const int32_t add = sums[blockIdx.x];
+    for (int r = 0; r < kScanItems; ++r)
+        if (first + r < n) data[first + r] += add;
+}
+
+// in place; `scratch` holds the block sums of every level (scan_scratch_len(n) entries)
+int64_t scan_scratch_len(int64_t n) {
+    int64_t total = 0;
+    while (true) {
+        n = (n + kScanTile - 1) / kScanTile;
+        total += n;
+        if (n <= 1) return total;
+    }
+}
+
+int scan_exclusive(hipStream_t st, int64_t n, int32_t* data, int32_t* scratch) {
+    const int64_t n_tiles = (n + kScanTile - 1) / kScanTile;
+    hipLaunchKernelGGL(scan_tile_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, n, data, scratch);
+    HIP_TRY(hipGetLastError());
+    if (n_tiles > 1) {
+        FEP_TRY(scan_exclusive(st, n_tiles, scratch, scratch + n_tiles));
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, n, data, scratch);
+        HIP_TRY(hipGetLastError());
+    }
+    return FEP_OK;
+}
+
+// ---- numbering ------------------------------------------------------------------------------------------------------------
+// index of edge k of element e among the new nodes, the edge being OWNED by e (bit k of m set)
+__device__ __forceinline__ int32_t p2_index(int32_t base_e, int m, int k) {
+    const int rank = k == 1 ? 0 : (k == 2 ? ((m >> 1) & 1) : (((m >> 1) & 1) + ((m >> 2) & 1)));   // visit order 1, 2, 0
+    return base_e + rank;
+}
+__device__ __forceinline__ int32_t p4_index(int64_t e, int32_t base_e, int m, int k) {
+    return (int32_t)(3 * e + 3 * (int64_t)base_e + 3 + 3 * __popc(m & ((1 << k) - 1)));         // visit order 0, 1, 2
+}
+__device__ __forceinline__ int bnd_rank_p2(int m, int k) {
+    return k == 1 ? 0 : (k == 2 ? ((m >> 4) & 1) : (((m >> 4) & 1) + ((m >> 5) & 1)));
+}
+
+struct MeshView {
+    int64_t n_e, n_n, n_edges, n_bnd;
+    const int32_t* elem;
+    const double* coord;
+    const int32_t* nbr;
+    const uint8_t* mask;
+    const int32_t* base;     // exclusive prefix sum of the owned counts
+    const int32_t* bbase;    // ... of the boundary counts
+};
+
+// P2 index of edge k of element i, whoever owns it
+__device__ __forceinline__ int32_t p2_edge(const MeshView& M, int64_t i, int k, int m, bool* owned, int64_t* j_out) {
+    *owned = (m >> k) & 1;
+    if (*owned) {
+        const int32_t nb = M.nbr[(int64_t)k * M.n_e + i];
+        *j_out = nb < 0 ? -1 : nb / 3;
+        return p2_index(M.base[i], m, k);
+    }
+    const int32_t nb = M.nbr[(int64_t)k * M.n_e + i];
+    const int64_t j = nb / 3;
+    *j_out = j;
+    return p2_index(M.base[j], M.mask[j], nb % 3);
+}
+
+// grid.y = slot s (edge k = (s + 1) % 3), one lane per element: coalesced rows of elem_ext / elem_ed
+__global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
+                                                           int32_t* __restrict__ surf, int32_t* __restrict__ elem_ed,
+                                                           int32_t* __restrict__ edge_el) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int s = blockIdx.y, k = (s + 1) % 3;
+    const int m = M.mask[i];
+    const int32_t A = M.elem[(int64_t)k * M.n_e + i], B = M.elem[(int64_t)((k + 1) % 3) * M.n_e + i];
+    bool owned;
+    int64_t j;
+    const int32_t ind = p2_edge(M, i, k, m, &owned, &j);
+    const int64_t n_tot = M.n_n + M.n_edges;
+    elem_ext[(int64_t)s * M.n_e + i] = M.elem[(int64_t)s * M.n_e + i];
+    elem_ext[(int64_t)(3 + s) * M.n_e + i] = (int32_t)(M.n_n + ind);
+    if (elem_ed) elem_ed[(int64_t)s * M.n_e + i] = ind;
+    if (!owned) return;
+    coord_ext[M.n_n + ind] = (M.coord[A] + M.coord[B]) / 2;
+    coord_ext[n_tot + M.n_n + ind] = (M.coord[M.n_n + A] + M.coord[M.n_n + B]) / 2;
+    if (edge_el) {
+        edge_el[ind] = (int32_t)i;
+        edge_el[M.n_edges + ind] = j < 0 ? 0 : (int32_t)j;       // the reference leaves its zero on a boundary edge
+    }
+    if (j < 0) {
+        const int64_t at = M.bbase[i] + bnd_rank_p2(m, k);
+        surf[at] = B;
+        surf[M.n_bnd + at] = A;
+        surf[2 * M.n_bnd + at] = (int32_t)(M.n_n + ind);
+    }
+}
+
+// grid.y = edge k = slot; lane k of an element also writes its interior node k (nearest vertex k, TSX:1374-1381)
+__global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
+                                                           int32_t* __restrict__ surf) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int k = blockIdx.y;
+    const int m = M.mask[i];
+    const int64_t n_e = M.n_e, n_n = M.n_n;
+    const int64_t n_tot = n_n + 3 * n_e + 3 * M.n_edges;
+    const int32_t A = M.elem[(int64_t)k * n_e + i], B = M.elem[(int64_t)((k + 1) % 3) * n_e + i];
+    const int32_t C = M.elem[(int64_t)((k + 2) % 3) * n_e + i];
+    const int32_t base_i = M.base[i];
+    const bool owned = (m >> k) & 1;
+    const int32_t nb = M.nbr[(int64_t)k * n_e + i];
+    int32_t mid;
+    if (owned) {
+        mid = p4_index(i, base_i, m, k);
+    } else {
+        const int64_t j = nb / 3;
+        mid = p4_index(j, M.base[j], M.mask[j], nb % 3);
+    }
+    elem_ext[(int64_t)k * n_e + i] = A;
+    elem_ext[(int64_t)(3 + k) * n_e + i] = (int32_t)(n_n + mid);
+    elem_ext[(int64_t)(6 + 2 * k) * n_e + i] = (int32_t)(n_n + mid + (owned ? 1 : 2));     // the neighbour walks the edge backwards
+    elem_ext[(int64_t)(7 + 2 * k) * n_e + i] = (int32_t)(n_n + mid + (owned ? 2 : 1));
+    const int64_t inner = 3 * i + 3 * (int64_t)base_i + k;
+    elem_ext[(int64_t)(12 + k) * n_e + i] = (int32_t)(n_n + inner);
+    const double ax = M.coord[A], ay = M.coord[n_n + A], bx = M.coord[B], by = M.coord[n_n + B];
+    const double cx = M.coord[C], cy = M.coord[n_n + C];
+    // c1 / 2 + c2 / 4 + c3 / 4 and its permutations, summed in the order V1, V2, V3
+    double ix, iy;
+    if (k == 0) { ix = ax / 2 + bx / 4 + cx / 4; iy = ay / 2 + by / 4 + cy / 4; }            // A = V1, B = V2, C = V3
+    else if (k == 1) { ix = cx / 4 + ax / 2 + bx / 4; iy = cy / 4 + ay / 2 + by / 4; }       // C = V1, A = V2, B = V3
+    else { ix = bx / 4 + cx / 4 + ax / 2; iy = by / 4 + cy / 4 + ay / 2; }                   // B = V1, C = V2, A = V3
+    coord_ext[n_n + inner] = ix;
+    coord_ext[n_tot + n_n + inner] = iy;
+    if (!owned) return;
+    coord_ext[n_n + mid] = (ax + bx) / 2;
+    coord_ext[n_tot + n_n + mid] = (ay + by) / 2;
+    coord_ext[n_n + mid + 1] = 3 * ax / 4 + bx / 4;
+    coord_ext[n_tot + n_n + mid + 1] = 3 * ay / 4 + by / 4;
+    coord_ext[n_n + mid + 2] = ax / 4 + 3 * bx / 4;
+    coord_ext[n_tot + n_n + mid + 2] = ay / 4 + 3 * by / 4;
+    if (nb < 0) {
+        const int64_t at = M.bbase[i] + __popc((m >> 3) & ((1 << k) - 1));
+        const int64_t n_b = M.n_bnd;
+        surf[at] = B;
+        surf[n_b + at] = A;
+        surf[2 * n_b + at] = (int32_t)(n_n + mid);
+        surf[3 * n_b + at] = (int32_t)(n_n + mid + 1);
+        surf[4 * n_b + at] = (int32_t)(n_n + mid + 2);
+    }
+}
+
+// one lane per element: its three P2 midside ids, the coordinates of those it owns, its four children
+__global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, int32_t* __restrict__ child, double* __restrict__ coord_ext) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int m = M.mask[i];
+    const int64_t n_tot = M.n_n + M.n_edges;
+    int32_t v[3], mid[3];
+    for (int k = 0; k < 3; ++k) v[k] = M.elem[(int64_t)k * M.n_e + i];
+    for (int k = 0; k < 3; ++k) {
+        bool owned;
+        int64_t j;
+        const int32_t ind = p2_edge(M, i, k, m, &owned, &j);
+        mid[k] = (int32_t)(M.n_n + ind);
+        if (owned) {
+            const int32_t A = v[k], B = v[(k + 1) % 3];
+            coord_ext[M.n_n + ind] = (M.coord[A] + M.coord[B]) / 2;
+            coord_ext[n_tot + M.n_n + ind] = (M.coord[M.n_n + A] + M.coord[M.n_n + B]) / 2;
+        }
+    }
+    const int32_t m12 = mid[0], m23 = mid[1], m31 = mid[2];
+    const int64_t n_c = 4 * M.n_e;
+    int32_t* r0 = child + 4 * i;
+    int32_t* r1 = child + n_c + 4 * i;
+    int32_t* r2 = child + 2 * n_c + 4 * i;
+    r0[0] = v[0]; r0[1] = m12;  r0[2] = m31;  r0[3] = m12;          // children (V1, m12, m31), (m12, V2, m23),
+    r1[0] = m12;  r1[1] = v[1]; r1[2] = m23;  r1[3] = m23;          //          (m31, m23, V3), (m12, m23, m31)
+    r2[0] = m31;  r2[1] = m23;  r2[2] = v[2]; r2[3] = m31;
+}
+
+struct DeviceBlocks {
+    std::vector<void*> p;
+    ~DeviceBlocks() { for (void* q : p) (void)hipFree(q); }
+    template <class T>
+    int get(T** out, int64_t count) {
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)));
+        p.push_back(q);
+        *out = (T*)q;
+        return FEP_OK;
+    }
+};
+
+}  // namespace
+
+struct fep_mesh {
+    int device = 0;
+    int64_t n_e = 0, n_n = 0, n_edges = 0, n_bnd = 0, n_nonmanifold = 0, n_inconsistent = 0, n_degenerate = 0;
+    int32_t* elem = nullptr;
+    double* coord = nullptr;
+    int32_t* nbr = nullptr;
+    uint8_t* mask = nullptr;
+    int32_t* base = nullptr;
+    int32_t* bbase = nullptr;
+    DeviceBlocks blocks;
+
+    bool refused() const { return n_nonmanifold > 0 || n_inconsistent > 0 || n_degenerate > 0; }
+    MeshView view() const { return MeshView{n_e, n_n, n_edges, n_bnd, elem, coord, nbr, mask, base, bbase}; }
+};
+
+static int mesh_create_impl(fep_mesh** out, int device_id, hipStream_t st, int64_t n_e, int64_t n_n, const int32_t* elem,
+                            const double* coord, int on_device) {
+    if (!out) return FEP_EINVAL;
+    *out = nullptr;
+    if (n_e < 1 || n_n < 0 || !elem || (!coord && n_n > 0)) return FEP_EINVAL;
+    if (n_n >= (int64_t)INT32_MAX || 4 * n_e >= (int64_t)INT32_MAX) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(device_id));
+    fep_mesh* M = new fep_mesh();
+    struct Guard {
+        fep_mesh* m;
+        ~Guard() { delete m; }
+    } guard{M};
+    M->device = device_id;
+    M->n_e = n_e;
+    M->n_n = n_n;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    FEP_TRY(M->blocks.get(&M->elem, 3 * n_e));
+    FEP_TRY(M->blocks.get(&M->coord, 2 * n_n));
+    FEP_TRY(M->blocks.get(&M->nbr, 3 * n_e));
+    FEP_TRY(M->blocks.get(&M->mask, n_e));
+    FEP_TRY(M->blocks.get(&M->base, n_e + 1));
+    FEP_TRY(M->blocks.get(&M->bbase, n_e + 1));
+    HIP_TRY(hipMemcpyAsync(M->elem, elem, (size_t)(3 * n_e) * sizeof(int32_t), kind, st));
+    if (n_n > 0) HIP_TRY(hipMemcpyAsync(M->coord, coord, (size_t)(2 * n_n) * sizeof(double), kind, st));
+    // scratch of the analysis: released when this function returns (it synchronises first)
+    DeviceBlocks tmp;
+    int32_t *ptr = nullptr, *cursor = nullptr, *list = nullptr, *counters = nullptr, *scan = nullptr;
+    const int64_t n_longest = (n_n > n_e ? n_n : n_e) + 1;
+    FEP_TRY(tmp.get(&ptr, n_n + 1));
+    FEP_TRY(tmp.get(&cursor, n_n));
+    FEP_TRY(tmp.get(&list, 3 * n_e));
+    FEP_TRY(tmp.get(&counters, C_COUNT));
+    FEP_TRY(tmp.get(&scan, scan_scratch_len(n_longest)));
+    HIP_TRY(hipMemsetAsync(ptr, 0, (size_t)(n_n + 1) * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)(n_n > 0 ? n_n : 1) * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(counters, 0, C_COUNT * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(M->base + n_e, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(M->bbase + n_e, 0, sizeof(int32_t), st));
+    const dim3 grid(grid_for(n_e, kBlock)), block(kBlock);
+    hipLaunchKernelGGL(mesh_degree_kernel, grid, block, 0, st, n_e, n_n, M->elem, ptr, counters);
+    HIP_TRY(hipGetLastError());
+    FEP_TRY(scan_exclusive(st, n_n + 1, ptr, scan));
+    hipLaunchKernelGGL(mesh_fill_kernel, grid, block, 0, st, n_e, n_n, M->elem, ptr, cursor, list);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mesh_match_kernel, grid, block, 0, st, n_e, n_n, M->elem, ptr, list, M->nbr, M->mask, M->base, M->bbase,
+                       counters);
+    HIP_TRY(hipGetLastError());
+    FEP_TRY(scan_exclusive(st, n_e + 1, M->base, scan));
+    FEP_TRY(scan_exclusive(st, n_e + 1, M->bbase, scan));
+    int32_t h_counters[C_COUNT] = {0, 0, 0, 0}, h_edges = 0, h_bnd = 0;
+    HIP_TRY(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_edges, M->base + n_e, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_bnd, M->bbase + n_e, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_counters[C_RANGE] > 0) return FEP_ERANGE;
+    M->n_edges = h_edges;
+    M->n_bnd = h_bnd;
+    M->n_degenerate = h_counters[C_DEGENERATE];
+    M->n_nonmanifold = h_counters[C_NONMANIFOLD];
+    M->n_inconsistent = h_counters[C_INCONSISTENT];
+    guard.m = nullptr;
+    *out = M;
+    return FEP_OK;
+}
+
+static int64_t mesh_new_nodes(const fep_mesh* M, int elem_type) {
+    return elem_type == FEP_P2 ? M->n_edges : 3 * M->n_e + 3 * M->n_edges;
+}
+
+static int mesh_enrich_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* elem_ext, double* coord_ext, int32_t* surf,
+                            int32_t* elem_ed, int32_t* edge_el) {
+    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || !elem_ext || !coord_ext || (!surf && M->n_bnd > 0)) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    const int64_t n_tot = M->n_n + mesh_new_nodes(M, elem_type);
+    if (n_tot >= (int64_t)INT32_MAX) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(M->device));
+    for (int r = 0; r < 2 && M->n_n > 0; ++r)
+        HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    const dim3 grid(grid_for(M->n_e, kBlock), 3), block(kBlock);
+    if (elem_type == FEP_P2)
+        hipLaunchKernelGGL(enrich_p2_kernel, grid, block, 0, st, M->view(), elem_ext, coord_ext, surf, elem_ed, edge_el);
+    else
+        hipLaunchKernelGGL(enrich_p4_kernel, grid, block, 0, st, M->view(), elem_ext, coord_ext, surf);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+static int mesh_refine_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext) {
+    if (!M || !elem_child || !coord_ext) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    const int64_t n_tot = M->n_n + M->n_edges;
+    if (n_tot >= (int64_t)INT32_MAX) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(M->device));
+    for (int r = 0; r < 2 && M->n_n > 0; ++r)
+        HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(refine_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), elem_child, coord_ext);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+// host forms: device outputs of this call, copied back, released on every exit
+template <class T>
+static int fetch(T* dst_h, const T* src_d, int64_t count) {
+    if (dst_h && count > 0) HIP_TRY(hipMemcpyAsync(dst_h, src_d, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, nullptr));
+    return FEP_OK;
+}
+
+static int mesh_enrich_host_impl(const fep_mesh* M, int elem_type, int32_t* elem_ext_h, double* coord_ext_h, int32_t* surf_h,
+                                 int32_t* elem_ed_h, int32_t* edge_el_h) {
+    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || !elem_ext_h || !coord_ext_h || (!surf_h && M->n_bnd > 0)) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    const bool p2 = elem_type == FEP_P2;
+    const int64_t n_tot = M->n_n + mesh_new_nodes(M, elem_type), n_p = p2 ? 6 : 15, n_s = p2 ? 3 : 5;
+    DeviceBlocks tmp;
+    int32_t *elem_ext = nullptr, *surf = nullptr, *elem_ed = nullptr, *edge_el = nullptr;
+    double* coord_ext = nullptr;
+    FEP_TRY(tmp.get(&elem_ext, n_p * M->n_e));
+    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
+    FEP_TRY(tmp.get(&surf, n_s * M->n_bnd));
+    if (p2 && elem_ed_h) FEP_TRY(tmp.get(&elem_ed, 3 * M->n_e));
+    if (p2 && edge_el_h) FEP_TRY(tmp.get(&edge_el, 2 * M->n_edges));
+    FEP_TRY(mesh_enrich_impl(M, nullptr, elem_type, elem_ext, coord_ext, surf, elem_ed, edge_el));
+    FEP_TRY(fetch(elem_ext_h, elem_ext, n_p * M->n_e));
+    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
+    FEP_TRY(fetch(surf_h, surf, n_s * M->n_bnd));
+    if (elem_ed) FEP_TRY(fetch(elem_ed_h, elem_ed, 3 * M->n_e));
+    if (edge_el) FEP_TRY(fetch(edge_el_h, edge_el, 2 * M->n_edges));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
+static int mesh_refine_host_impl(const fep_mesh* M, int32_t* elem_child_h, double* coord_ext_h) {
+    if (!M || !elem_child_h || !coord_ext_h) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    const int64_t n_tot = M->n_n + M->n_edges;
+    DeviceBlocks tmp;
+    int32_t* child = nullptr;
+    double* coord_ext = nullptr;
+    FEP_TRY(tmp.get(&child, 12 * M->n_e));
+    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
+    FEP_TRY(mesh_refine_impl(M, nullptr, child, coord_ext));
+    FEP_TRY(fetch(elem_child_h, child, 12 * M->n_e));
+    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
+#define FEP_GUARD(call) \
+    try { return call; } catch (const std::bad_alloc&) { return FEP_ENOMEM; } catch (...) { return FEP_EINVAL; }
+
+extern "C" int fep_mesh_create(fep_mesh** mesh_out, int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem,
+                               const double* coord, int on_device) {
+    FEP_GUARD(mesh_create_impl(mesh_out, device_id, (hipStream_t)stream, n_e, n_n, elem, coord, on_device))
+}
+
+extern "C" int fep_mesh_destroy(fep_mesh* mesh) {
+    if (!mesh) return FEP_OK;
+    (void)fep_set_device(mesh->device);
+    delete mesh;
+    return FEP_OK;
+}
+
+extern "C" int fep_mesh_info(const fep_mesh* mesh, int64_t info[7]) {
+    if (!mesh || !info) return FEP_EINVAL;
+    info[0] = mesh->n_e;
+    info[1] = mesh->n_n;
+    info[2] = mesh->n_edges;
+    info[3] = mesh->n_bnd;
+    info[4] = mesh->n_nonmanifold;
+    info[5] = mesh->n_inconsistent;
+    info[6] = mesh->n_degenerate;
+    return FEP_OK;
+}
+
+extern "C" int fep_mesh_enrich_dev(const fep_mesh* mesh, void* stream, int elem_type, int32_t* elem_ext_d, double* coord_ext_d,
+                                   int32_t* surf_d, int32_t* elem_ed_d, int32_t* edge_el_d) {
+    FEP_GUARD(mesh_enrich_impl(mesh, (hipStream_t)stream, elem_type, elem_ext_d, coord_ext_d, surf_d, elem_ed_d, edge_el_d))
+}
+
+extern "C" int fep_mesh_enrich_host(const fep_mesh* mesh, int elem_type, int32_t* elem_ext_h, double* coord_ext_h, int32_t* surf_h,
+                                    int32_t* elem_ed_h, int32_t* edge_el_h) {
+    FEP_GUARD(mesh_enrich_host_impl(mesh, elem_type, elem_ext_h, coord_ext_h, surf_h, elem_ed_h, edge_el_h))
+}
+
+extern "C" int fep_mesh_refine_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d) {
+    FEP_GUARD(mesh_refine_impl(mesh, (hipStream_t)stream, elem_child_d, coord_ext_d))
+}
+
+extern "C" int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h) {
+    FEP_GUARD(mesh_refine_host_impl(mesh, elem_child_h, coord_ext_h))
+}

@@ -11,6 +11,8 @@ Local orders: P2 rows 3..5 = midpoints of (V2V3, V3V1, V1V2); P4
 (V1V2, V2V3, V3V1), rows 6..11 = quarter points (two per edge, nearer the edge's first vertex first),
 rows 12..14 = interior nodes nearest V1, V2, V3.
 """
+import ctypes as C
+
 import numpy as np
 
 from .tables import LagrangeElementType, _coerce
@@ -35,8 +37,12 @@ def _neighbour(m, a, b, i):
     return None
 
 
-def create_midpoints_P2(coord, elem):
-    """TSX:1508-1626.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext', 'elem_ed', 'edge_el'."""
+def create_midpoints_P2(coord, elem, device=None):
+    """TSX:1508-1626.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext', 'elem_ed', 'edge_el'.
+    `device` (a GPU index): the same dict from the library's kernels (fep_mesh_*), see DeviceMesh."""
+    if device is not None:
+        with DeviceMesh(coord, elem, device) as m:
+            return m.enrich(LagrangeElementType.P2)
     coord = np.asarray(coord, dtype=float)
     elem = np.asarray(elem)
     n_e, n_n = elem.shape[1], coord.shape[1]
@@ -77,8 +83,11 @@ def create_midpoints_P2(coord, elem):
             'elem_ed': elem_ed, 'edge_el': edge_el[:, 0:ind]}
 
 
-def create_midpoints_P4(coord, elem):
-    """TSX:1354-1505.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext'."""
+def create_midpoints_P4(coord, elem, device=None):
+    """TSX:1354-1505.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext'.  `device` as in create_midpoints_P2."""
+    if device is not None:
+        with DeviceMesh(coord, elem, device) as m:
+            return m.enrich(LagrangeElementType.P4)
     coord = np.asarray(coord, dtype=float)
     elem = np.asarray(elem)
     n_e, n_n = elem.shape[1], coord.shape[1]
@@ -122,11 +131,173 @@ def create_midpoints_P4(coord, elem):
             'elem_ext': np.array(np.concatenate([elem, elem_mid], axis=0), dtype=int)}
 
 
-def create_midpoints(elem_type, coord, elem):
+def create_midpoints(elem_type, coord, elem, device=None):
     """TSX:1629-1633 (returns None for element types without midpoints, like the reference)."""
     t = _coerce(elem_type)
     if t is LagrangeElementType.P2:
-        return create_midpoints_P2(coord, elem)
+        return create_midpoints_P2(coord, elem, device=device)
     if t is LagrangeElementType.P4:
-        return create_midpoints_P4(coord, elem)
+        return create_midpoints_P4(coord, elem, device=device)
     return None
+
+
+# ---------------------------------------------------------------------------------------
+# the same numbering on the GPU (include/fep.h, "mesh") and uniform refinement
+# ---------------------------------------------------------------------------------------
+_FEP_TYPE = {LagrangeElementType.P2: 2, LagrangeElementType.P4: 5}
+_INFO = ('n_e', 'n_n', 'n_edges', 'n_boundary_edges', 'n_nonmanifold', 'n_inconsistent', 'n_degenerate')
+
+
+class DeviceMesh:
+    """A P1 triangle mesh analysed on GPU `device` (fep_mesh_create): half-edges matched, owners and prefix sums ready.
+    `coord` (2, n_n) and `elem` (3, n_e) are host arrays, or — `on_device=True` — torch tensors of that GPU (float64 /
+    int32, contiguous).  `info` holds the counts of fep_mesh_info.  The device path numbers edge-manifold, consistently
+    oriented meshes only: on any other, `enrich` / `refine` raise ValueError and write nothing (the host functions,
+    device=None, keep the reference's visit-order-dependent result for those)."""
+
+    def __init__(self, coord, elem, device, on_device=False):
+        from . import _lib
+        self._lib, self._h, self.device = _lib, None, int(device)
+        if on_device:
+            if elem.dtype.itemsize != 4 or coord.dtype.itemsize != 8 or not (elem.is_contiguous() and coord.is_contiguous()):
+                raise ValueError('device meshes are contiguous int32 / float64 tensors')
+            n_e, n_n = int(elem.shape[1]), int(coord.shape[1])
+            pe, pc, stream = elem.data_ptr(), coord.data_ptr(), self._stream()
+            self._keep = (elem, coord)
+        else:
+            coord = np.ascontiguousarray(coord, dtype=np.float64)
+            e64 = np.asarray(elem)
+            if e64.ndim != 2 or e64.shape[0] != 3 or coord.ndim != 2 or coord.shape[0] != 2:
+                raise ValueError(f'expected (2, n_n) coordinates and (3, n_e) vertex ids, got {coord.shape} and {e64.shape}')
+            if e64.size and (e64.min() < -2 ** 31 or e64.max() >= 2 ** 31):
+                raise _lib.FepError(-5, 'fep_mesh_create')
+            e32 = np.ascontiguousarray(e64, dtype=np.int32)
+            n_e, n_n = e32.shape[1], coord.shape[1]
+            pe, pc, stream = _lib.ptr(e32), _lib.ptr(coord), None
+        h = C.c_void_p()
+        _lib.check(_lib.lib().fep_mesh_create(C.byref(h), self.device, stream, n_e, n_n, pe, pc, int(bool(on_device))),
+                   'fep_mesh_create')
+        self._h = h
+        info = np.zeros(7, dtype=np.int64)
+        _lib.check(_lib.lib().fep_mesh_info(h, info.ctypes.data_as(_lib.c_i64_p)), 'fep_mesh_info')
+        self.info = dict(zip(_INFO, (int(v) for v in info)))
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if self._h is not None:
+            self._lib.lib().fep_mesh_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _accepted(self):
+        i = self.info
+        if i['n_nonmanifold'] or i['n_inconsistent'] or i['n_degenerate']:
+            raise ValueError(f"the device path numbers edge-manifold, consistently oriented meshes only: "
+                             f"n_nonmanifold={i['n_nonmanifold']}, n_inconsistent={i['n_inconsistent']}, "
+                             f"n_degenerate={i['n_degenerate']}; use the host functions (device=None) for this mesh")
+
+    def new_nodes(self, elem_type):
+        t = _coerce(elem_type)
+        return self.info['n_edges'] if t is LagrangeElementType.P2 else 3 * self.info['n_e'] + 3 * self.info['n_edges']
+
+    def enrich(self, elem_type):
+        """The dict of create_midpoints_P2 / _P4 (same keys, shapes, dtypes and bits), host arrays."""
+        t = _coerce(elem_type)
+        self._accepted()
+        i, p2 = self.info, t is LagrangeElementType.P2
+        n_tot = i['n_n'] + self.new_nodes(t)
+        elem_ext = np.empty((6 if p2 else 15, i['n_e']), dtype=np.int32)
+        coord_ext = np.empty((2, n_tot))
+        surf = np.empty((3 if p2 else 5, i['n_boundary_edges']), dtype=np.int32)
+        elem_ed = np.empty((3, i['n_e']), dtype=np.int32) if p2 else None
+        edge_el = np.empty((2, i['n_edges']), dtype=np.int32) if p2 else None
+        ptr = self._lib.ptr
+        self._lib.check(self._lib.lib().fep_mesh_enrich_host(self._h, _FEP_TYPE[t], ptr(elem_ext), ptr(coord_ext), ptr(surf),
+                                                             ptr(elem_ed), ptr(edge_el)), 'fep_mesh_enrich_host')
+        out = {'coord_mid': coord_ext[:, i['n_n']:], 'surf': surf.astype(np.float64), 'coord_ext': coord_ext,
+               'elem_ext': elem_ext.astype(int)}
+        if p2:
+            out['elem_ed'], out['edge_el'] = elem_ed.astype(np.float64), edge_el.astype(np.float64)
+        return out
+
+    def enrich_dev(self, elem_type):
+        """Device-resident form: torch tensors (elem_ext int32, coord_ext, surf int32[, elem_ed, edge_el int32]) written on
+        the current stream; nothing is synchronised."""
+        import torch
+        t = _coerce(elem_type)
+        self._accepted()
+        i, p2 = self.info, t is LagrangeElementType.P2
+        dev = torch.device('cuda', self.device)
+        n_tot = i['n_n'] + self.new_nodes(t)
+        out = [torch.empty((6 if p2 else 15, i['n_e']), dtype=torch.int32, device=dev),
+               torch.empty((2, n_tot), dtype=torch.float64, device=dev),
+               torch.empty((3 if p2 else 5, i['n_boundary_edges']), dtype=torch.int32, device=dev)]
+        if p2:
+            out += [torch.empty((3, i['n_e']), dtype=torch.int32, device=dev),
+                    torch.empty((2, i['n_edges']), dtype=torch.int32, device=dev)]
+        ptrs = [C.c_void_p(a.data_ptr()) for a in out] + [None] * (5 - len(out))
+        self._lib.check(self._lib.lib().fep_mesh_enrich_dev(self._h, self._stream(), _FEP_TYPE[t], *ptrs), 'fep_mesh_enrich_dev')
+        return tuple(out)
+
+    def refine(self):
+        """One level of uniform refinement -> (coordinates (2, n_n + n_edges), elements (3, 4 n_e) int64), host arrays."""
+        self._accepted()
+        i = self.info
+        child = np.empty((3, 4 * i['n_e']), dtype=np.int32)
+        coord_ext = np.empty((2, i['n_n'] + i['n_edges']))
+        self._lib.check(self._lib.lib().fep_mesh_refine_host(self._h, self._lib.ptr(child), self._lib.ptr(coord_ext)),
+                        'fep_mesh_refine_host')
+        return coord_ext, child.astype(np.int64)
+
+    def refine_dev(self):
+        """Device-resident form -> torch tensors (coordinates float64, elements int32) on the current stream."""
+        import torch
+        self._accepted()
+        i = self.info
+        dev = torch.device('cuda', self.device)
+        child = torch.empty((3, 4 * i['n_e']), dtype=torch.int32, device=dev)
+        coord_ext = torch.empty((2, i['n_n'] + i['n_edges']), dtype=torch.float64, device=dev)
+        self._lib.check(self._lib.lib().fep_mesh_refine_dev(self._h, self._stream(), C.c_void_p(child.data_ptr()),
+                                                            C.c_void_p(coord_ext.data_ptr())), 'fep_mesh_refine_dev')
+        return coord_ext, child
+
+
+def refine_uniform(coord, elem, levels=1, device=None):
+    """Uniform (red) refinement of a P1 triangle mesh, `levels` times -> (coordinates, elements (3, 4**levels n_e) int64).
+    No counterpart in the reference.  One level = the P2 enrichment: the new vertices are the P2 midside nodes, with
+    create_midpoints_P2's ids and coordinates (old nodes keep their ids and coordinates), and with its rows
+    (V1, V2, V3, m23, m31, m12) the children 4i .. 4i + 3 of element i are (V1, m12, m31), (m12, V2, m23), (m31, m23, V3),
+    (m12, m23, m31).  Orientation is preserved.  Boundaries are refined as polygons: a curved boundary (the tunnel's hole) is
+    not re-projected onto its curve.  `device` (a GPU index): the levels are chained on the GPU without a host round
+    trip (DeviceMesh; edge-manifold, consistently oriented meshes only), bit-equal to the host form."""
+    if levels < 0:
+        raise ValueError('levels must be >= 0')
+    if device is not None and levels > 0:
+        m = DeviceMesh(coord, elem, device)
+        try:
+            for lv in range(levels):
+                c_d, e_d = m.refine_dev()
+                m.close()
+                if lv + 1 < levels:
+                    m = DeviceMesh(c_d, e_d, device, on_device=True)
+        finally:
+            m.close()
+        return c_d.cpu().numpy(), e_d.cpu().numpy().astype(np.int64)
+    coord, elem = np.asarray(coord, dtype=float), np.asarray(elem).astype(np.int64)
+    for _ in range(levels):
+        h = create_midpoints_P2(coord, elem)
+        V1, V2, V3, m23, m31, m12 = h['elem_ext']
+        elem = np.stack([np.stack([V1, m12, m31]), np.stack([m12, V2, m23]), np.stack([m31, m23, V3]),
+                         np.stack([m12, m23, m31])], axis=2).reshape(3, -1).astype(np.int64)
+        coord = h['coord_ext']
+    return coord, elem

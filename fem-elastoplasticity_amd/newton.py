@@ -357,13 +357,35 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
-                     pcg_forcing_cap=1e-4, context_factory=None):
+                     pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
-    displacements.  `context_factory` as in solve_strip_footing (the object also needs `assemble` and `n_int`)."""
+    displacements.  `context_factory` as in solve_strip_footing (the object also needs `assemble` and `n_int`).
+    `refine` > 0 or `renumber` (no counterpart in the reference): the P1 mesh — `mesh_dir`'s, or `coords` / `elem` with
+    3 vertex rows — is refined uniformly `refine` times (refine_uniform; the hole's boundary stays a polygon), then, with
+    `renumber`, numbered along a Morton curve (refinement appends every level's nodes at the end), then raised to
+    `element_type`; on the GPU when the context is the GPU one, on the host with a `context_factory`.  `monitor` keeps
+    naming a node of the INPUT mesh; 'U' is in the numbering of the mesh solved on, returned as 'coords' / 'elem', and
+    'node_of_input' maps input node ids to it (None unless renumbered)."""
     t = _coerce(element_type)
-    if mesh_dir is not None:
+    node_of_input, t_mesh = None, {}
+    if refine or renumber:
+        from .hotpath import default_device
+        from .meshio import load_tsx_mesh, prepare_tsx_mesh
+        if mesh_dir is not None:
+            coords, elem = load_tsx_mesh(mesh_dir, 'P1')
+        if coords is None or elem is None:
+            raise ValueError('pass the mesh (coords, elem) or mesh_dir')
+        mesh_device = None if context_factory is not None else (default_device() if device is None else device)
+        coords, elem, node_of_input, t_mesh = prepare_tsx_mesh(coords, elem, t, refine=refine, renumber=renumber,
+                                                               device=mesh_device)
+        if node_of_input is not None:
+            monitor = (monitor[0], int(node_of_input[monitor[1]]))
+        if log:
+            log('mesh: refine %.3f s, renumber %.3f s, enrich %.3f s; %d elements, %d nodes'
+                % (t_mesh['refine'], t_mesh['renumber'], t_mesh['enrich'], elem.shape[1], coords.shape[1]))
+    elif mesh_dir is not None:
         from .meshio import load_tsx_mesh
         coords, elem = load_tsx_mesh(mesh_dir, t)
     if coords is None or elem is None:
@@ -383,14 +405,23 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     Q[0, coords[0, :] > 49.99] = 0
     Q[1, coords[1, :] < -49.99] = 0
     Q[1, coords[1, :] > 49.99] = 0
+    clock = [time.perf_counter()]
     ctx = _context_maker(context_factory, device)(elem, coords, *element_tables(t))
     n_int = ctx.n_int
     assert n_int == elem.shape[1] * ELEMENT_SHAPE[t][1]
     ctx.set_materials(shear0, bulk0, eta0, c_0)
+    clock.append(time.perf_counter())
     with closing(ctx), closing(make_ops(ctx, Q.flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
                                         pcg_inexact_rtol)) as ops:
         K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                          # TSX:1722
+        clock.append(time.perf_counter())
         ops.setup_amg(K, coords)                                                          # linear_solver='amg' only
+        clock.append(time.perf_counter())
+        t_setup = dict(t_mesh, **dict(zip(('context', 'solver + K_elast', 'hierarchy'),
+                                          (b - a for a, b in zip(clock[:-1], clock[1:])))))
+        if log:
+            log('setup: context %.2f s, solver + K_elast %.2f s, multigrid hierarchy %.2f s'
+                % (t_setup['context'], t_setup['solver + K_elast'], t_setup['hierarchy']))
         _, F0 = ctx.assemble(None, s0 * np.ones((1, n_int)))                               # TSX:1737
 
         d_zeta = 1 / n_load_steps                                                         # TSX:1730-1735
@@ -412,4 +443,7 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
         hist['F0'] = F0.reshape((2, -1), order='F')
         hist['Q'] = Q
         hist['pcg_iters'] = ops.pcg_iters
+        hist['t_setup'] = t_setup
+        if refine or renumber:
+            hist['coords'], hist['elem'], hist['node_of_input'] = coords, elem, node_of_input
         return hist

@@ -4,3 +4,6 @@ from .tables import LagrangeElementType, get_local_basis_volume, get_quadrature_
 from .hotpath import assemble_tangent, get_elastic_stiffness_matrix                      # noqa: F401  TSX:432-542
 from .hotpath import construct_constitutive_problem_tsx as construct_constitutive_problem  # noqa: F401  TSX:990-1157
 from .midpoints import create_midpoints, create_midpoints_P2, create_midpoints_P4                 # noqa: F401  TSX:1354-1633
+from .midpoints import DeviceMesh, refine_uniform                                        # noqa: F401  uniform refinement: no counterpart
+from .meshio import load_tsx_mesh, prepare_tsx_mesh                                      # noqa: F401  TSX:1687-1690
+from .newton import solve_tsx_tunnel                                                     # noqa: F401  TSX:1637-1832

@@ -275,6 +275,59 @@ int fep_load_traction_host(int device_id, int64_t n_n, int64_t n_e_s, int n_p_s,
                            const int32_t* edges_h, const double* xy_h, const double* hatp_s_h, const double* dhatp1_s_h,
                            const double* wf_s_h, const double* t_int_h, double* f_out_h);
 
+/* ---- mesh: P1 -> P2 / P4 enrichment and uniform refinement of triangle meshes ------------
+ * Replaces create_midpoints_P2 (TSX:1508-1626) and create_midpoints_P4 (TSX:1354-1505) — a sequential loop over
+ * elements in which the first element to see an edge creates its nodes — by the order-free form of the same numbering,
+ * and adds uniform (red) refinement, which the reference does not have.  Context-free: the mesh exists before any context.
+ *
+ * Edge k of a triangle runs from vertex k to vertex (k + 1) % 3.  A half-edge (element i, edge k) OWNS its edge iff no
+ * other element holds both ends or the one that does has the higher id.  With c_i = number of owned edges of i and
+ * base = the exclusive prefix sum of c:
+ *   P2  slots in visit order (V2V3, V3V1, V1V2: TSX:1530, 1561, 1591); the r-th owned slot of i has index base_i + r;
+ *       its node is n_n + index at (cA + cB) / 2.  elem_ext rows (V1, V2, V3, m23, m31, m12).
+ *   P4  slots (V1V2, V2V3, V3V1: TSX:1386, 1424, 1463); interior nodes 3 i + 3 base_i + {0, 1, 2} (nearest V1, V2, V3,
+ *       TSX:1374-1381); the r-th owned slot has its midpoint at m = 3 i + 3 base_i + 3 + 3 r, the quarter point nearer
+ *       its start A at m + 1 (3 cA / 4 + cB / 4), nearer its end B at m + 2; the neighbour, which walks the edge
+ *       backwards, takes them swapped (TSX:1405-1416).  elem_ext rows: 3 vertices, 3 midpoints, 6 quarter points (two per
+ *       slot), 3 interior nodes.
+ *   surf  the owned boundary half-edges in (element, visit slot) order: rows (B, A, node) for P2 and
+ *       (B, A, mid, mid + 1, mid + 2) for P4.   elem_ed (3, n_e): index of the edge in each P2 slot;
+ *       edge_el (2, n_edges): owner element, neighbour element (0 on a boundary edge: the reference leaves its zero there).
+ *   refinement  new vertices = the P2 midside nodes (old nodes keep their ids); children 4 i .. 4 i + 3 of element i =
+ *       (V1, m12, m31), (m12, V2, m23), (m31, m23, V3), (m12, m23, m31); orientation is preserved and boundary edges are
+ *       halved as straight segments (a curved boundary is not re-projected).
+ * Coordinates are computed without contraction into fused multiply-adds, so every array equals the host functions' bit for
+ * bit.  No floating-point atomics; two calls give the same bytes.
+ *
+ *   fep_mesh_create     elem (3, n_e) int32 C-order, coord (2, n_n), both host pointers (on_device == 0) or both device
+ *                       pointers of device_id; copies them, builds node -> element lists, matches the half-edges (one
+ *                       lane per element, a loop of the start vertex's degree per edge), owners and both prefix sums on
+ *                       `stream`, then synchronises it.  Nodes of no element are legal.  FEP_EINVAL: n_e < 1, NULL
+ *                       pointers; FEP_ERANGE: a vertex id outside [0, n_n), n_n or 4 n_e beyond int32 (no mesh is made).
+ *   fep_mesh_info       info = {n_e, n_n, n_edges, n_boundary_edges, n_nonmanifold (edges of more than two elements),
+ *                       n_inconsistent (interior edges whose two elements walk them the same way), n_degenerate
+ *                       (triangles naming a vertex twice)}.  Output sizes follow from it: P2 adds n_edges nodes,
+ *                       P4 3 n_e + 3 n_edges.
+ *   fep_mesh_enrich_*   elem_type FEP_P2 / FEP_P4 (FEP_EINVAL otherwise).  elem_ext (6 | 15, n_e), coord_ext (2, n_n + new),
+ *                       surf (3 | 5, n_boundary_edges) (may be NULL when there is no boundary edge); P2 only, each may be
+ *                       NULL: elem_ed (3, n_e), edge_el (2, n_edges); ignored for P4.  ids are int32.
+ *   fep_mesh_refine_*   elem_child (3, 4 n_e), coord_ext (2, n_n + n_edges)
+ *                       Both: FEP_ESTATE, and nothing written, when n_nonmanifold, n_inconsistent or n_degenerate > 0 (on
+ *                       such meshes the reference's result depends on its visit order and has no parallel form);
+ *                       FEP_ERANGE when n_n + new nodes exceeds int32.  _dev forms enqueue on `stream` and leave
+ *                       everything on the device, so levels chain without a host round trip; _host forms are synchronous. */
+typedef struct fep_mesh fep_mesh;
+int fep_mesh_create(fep_mesh** mesh_out, int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem,
+                    const double* coord, int on_device);
+int fep_mesh_destroy(fep_mesh* mesh);
+int fep_mesh_info(const fep_mesh* mesh, int64_t info[7]);
+int fep_mesh_enrich_dev(const fep_mesh* mesh, void* stream, int elem_type, int32_t* elem_ext_d, double* coord_ext_d,
+                        int32_t* surf_d, int32_t* elem_ed_d, int32_t* edge_el_d);
+int fep_mesh_enrich_host(const fep_mesh* mesh, int elem_type, int32_t* elem_ext_h, double* coord_ext_h, int32_t* surf_h,
+                         int32_t* elem_ed_h, int32_t* edge_el_h);
+int fep_mesh_refine_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d);
+int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h);
+
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on
  * the device; K is the `data` array fep_step_dev wrote, on the context's CSR pattern.  The Jacobi blocks are the 2x2
