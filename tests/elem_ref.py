@@ -17,6 +17,16 @@ this reference must agree to a small multiple of u * S entry by entry, however s
 
 The geometry is computed with the operations, order and rounding of geometry_kernel / geometry_at_q (no fused
 multiply-adds), so dphi and w are bit-identical to the kernels' and B carries no error of its own.
+
+The P1 node route does not assemble from those three gradients.  Its kernels read a 48-byte record per element: the
+gradients of local nodes 0 and 1 and the weight, and form  d[2] = -(d[0] + d[1])  (fep_kernels.hip.h: p1_node_kernel,
+p1_node_lds_kernel, p1_fused_kernel).  That is one rounding of a sum whose terms may cancel, so a term with local node 2
+is accurate to u (|d[0]| + |d[1]|), not to u |d[2]|.  Two things state this here, for P1 only:
+  ElemRef(..., record=True)      the record form: assemble() takes d[2] = -(d[0] + d[1]), that operation in float64, and
+                                 its scales are the plain ones of the record's own |B|; strain() keeps the table
+                                 gradients, as p1_point_kernel does
+  assemble(..., widened=True)    the widened scales: S_K, S_F with |d[2]| replaced by |d[0]| + |d[1]|, the terms the
+                                 record form really sums — the scale on which the record form and the exact form agree
 """
 import numpy as np
 
@@ -54,12 +64,15 @@ class ElemRef:
     dhatp2, wf) as element_tables(t) returns them; `pattern` = (indptr, indices) of the CSR values K is accumulated into
     (MeshContext.pattern(); default: node_block_pattern)."""
 
-    def __init__(self, elem, coord, tables, pattern=None, chunk=4096):
+    def __init__(self, elem, coord, tables, pattern=None, chunk=4096, record=False):
         self.elem = np.ascontiguousarray(elem, dtype=np.int64)
         self.coord = np.ascontiguousarray(coord, dtype=np.float64)
         self.n_p, self.n_e = self.elem.shape
         self.n_n = self.coord.shape[1]
         self.t = TYPE_OF_NP[self.n_p]
+        if record and self.t != 'P1':
+            raise ValueError('the record form is the P1 node route\'s: no other element type has it')
+        self.record = bool(record)
         d1, d2, wf = tables
         self.wf = np.asarray(wf, dtype=np.float64).ravel()
         self.n_q = self.wf.size
@@ -95,6 +108,20 @@ class ElemRef:
         """det of every point, (n_int,) in point order (k = e * n_q + q)."""
         return np.concatenate([self.geometry(e0, min(e0 + self.chunk, self.n_e))[3].ravel()
                                for e0 in range(0, self.n_e, self.chunk)]) if self.n_e else np.zeros(0)
+
+    def assembly_gradients(self, d1, d2, widened=False):
+        """(d1, d2, |d1|, |d2|) as assemble() uses them: the table gradients or, in the record form, d[2] = -(d[0] + d[1]);
+        the magnitudes are those of the gradients used or, widened, |d[2]| replaced by |d[0]| + |d[1]|."""
+        if self.record:
+            d1 = np.concatenate([d1[..., :2], -(d1[..., 0:1] + d1[..., 1:2])], axis=-1)
+            d2 = np.concatenate([d2[..., :2], -(d2[..., 0:1] + d2[..., 1:2])], axis=-1)
+        a1, a2 = np.abs(d1), np.abs(d2)
+        if widened:
+            if self.t != 'P1':
+                raise ValueError('the widened scale is the P1 node route\'s: no other element type has it')
+            a1 = np.concatenate([a1[..., :2], a1[..., 0:1] + a1[..., 1:2]], axis=-1)
+            a2 = np.concatenate([a2[..., :2], a2[..., 0:1] + a2[..., 1:2]], axis=-1)
+        return d1, d2, a1, a2
 
     def _B(self, d1, d2):
         """B per point, (m, n_q, 3, 2 n_p): rows [11, 22, 12 (engineering)], columns 2a + [x, y]."""
@@ -170,10 +197,11 @@ class ElemRef:
         dst[lo:hi] += np.bincount(idx.ravel() - lo, weights=val.ravel(), minlength=hi - lo)
 
     # -- a3 + a4, a5: assembly from given point data
-    def assemble(self, ds=None, s=None):
+    def assemble(self, ds=None, s=None, widened=False):
         """(K, S_K, F, S_F): K, S_K the CSR values (nnz,) of sum_e sum_q B^T (w ds) B and of its scale, F, S_F (n_dof,)
         of sum_e sum_q B^T (w s[0:3]); the pairs of an absent input are None.  `ds` (9, n_int) row-major 3x3 (all nine
-        entries are used: a non-symmetric ds gives the non-symmetric K), `s` (>= 3, n_int)."""
+        entries are used: a non-symmetric ds gives the non-symmetric K), `s` (>= 3, n_int).  `widened` (P1): the scales with
+        |d[2]| replaced by |d[0]| + |d[1]| (module docstring); the values do not depend on it."""
         nq, npp = self.n_q, self.n_p
         K = S_K = F = S_F = None
         if ds is not None:
@@ -185,15 +213,17 @@ class ElemRef:
             e1 = min(e0 + self.chunk, self.n_e)
             m = e1 - e0
             d1, d2, w, _ = self.geometry(e0, e1)
+            d1, d2, a1, a2 = self.assembly_gradients(d1, d2, widened)
             B = self._B(d1, d2)                                              # (m, nq, 3, 2np)
             Bf = B.reshape(m, nq * 3, 2 * npp)
-            aB = np.abs(Bf)
+            absB = self._B(a1, a2)                                           # |B|, or its widened form
+            aB = absB.reshape(m, nq * 3, 2 * npp)
             el = self.elem[:, e0:e1].T
             sl = slice(e0 * nq, e1 * nq)
             if ds is not None:
                 D = (w[..., None, None] * np.asarray(ds)[:, sl].T.reshape(m, nq, 3, 3))
                 DB = np.matmul(D, B).reshape(m, nq * 3, 2 * npp)             # (w ds) B per point
-                aDB = np.matmul(np.abs(D), np.abs(B)).reshape(m, nq * 3, 2 * npp)
+                aDB = np.matmul(np.abs(D), absB).reshape(m, nq * 3, 2 * npp)
                 Ke = np.matmul(Bf.transpose(0, 2, 1), DB)                    # (m, 2np, 2np)
                 Se = np.matmul(aB.transpose(0, 2, 1), aDB)
                 p = self._positions(el)

@@ -1,11 +1,13 @@
 // Host-only driver of fem-elastoplasticity_amd/csrc/fep_host.h for the sanitizer builds
 // (tests/test_host_sanitizers.py: g++ -fsanitize=address,undefined and -fsanitize=thread; CPU only, no HIP).
-//   host_san MESHFILE [max_segs]
+//   host_san MESHFILE [max_segs] [plan]
 // MESHFILE: int32 n_p, n_e, n_n, then elements (n_p x n_e, C order), optionally 2 x n_n doubles of coordinates.  Runs the symbolic phase (threaded), the COO
 // tiles, the P1 plans with every table option (validated against the mesh), the opt-in node plan of P2/Q1/Q2 and
 // the multigrid aggregation on the node graph; prints one summary line per plan; exit code 0 = all consistent, 1 = an
 // inconsistency, 2 = unreadable mesh file, 3 = a node row of more than 256 blocks (row_tiles: FEP_ERANGE, which
 // fep_ctx_create returns for such a mesh on every route).
+// With a third argument `plan` (tests/test_p1_node_cases.py) a P1 mesh gets its default plan only, validated, with the
+// shape of its last tile on a line of its own, and nothing else: a million elements in a few seconds.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +54,24 @@ int main(int argc, char** argv) {
     for (size_t i = 1; i < tstart.size(); ++i)
         if (tstart[i] - tstart[i - 1] > 256 || tstart[i] < tstart[i - 1]) return 1;
     int rc = 0;
+    if (n_p == 3 && argc > 3) {
+        P1Options opt;
+        opt.max_segs = max_segs;
+        P1Plan P;
+        r = build_p1_plan(S, n_e, n_n, elem.data(), opt, P);
+        const int bad = r == FEP_OK ? validate_p1_plan(P, S, n_e, n_n, elem.data()) : -1;
+        std::printf("p1 plan [default]: rc %d check %d tiles %lld segs %d staged %lld (%.3f per element) nodes %lld L %d C %d NL %d "
+                    "lds %d rng %d pk %d fused %d/%d\n", r, bad, (long long)P.n_wg, P.n_segs, (long long)P.staged_total,
+                    (double)P.staged_total / (double)n_e, (long long)P.staged_nodes_total, P.L, P.C, P.NL, (int)P.lds,
+                    (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
+        if (r == FEP_OK && P.n_wg > 0) {
+            const int32_t* d = P.tdesc.data() + (size_t)(P.n_wg - 1) * kDescInts;
+            std::printf("last tile: blocks %d nodes %d own %d staged %d\n", d[1], d[2] & 255, d[2] >> 8, (d[3] >> 4) & 4095);
+        }
+        rc = (r != FEP_OK || bad) ? 1 : 0;
+        std::printf("result %s\n", rc ? "FAILED" : "ok");
+        return rc;
+    }
     if (n_p == 3) {
         for (int segs = 1; segs <= kSegMax; ++segs) {       // the raw tilings, before build_p1_plan chooses
             P1Plan P;

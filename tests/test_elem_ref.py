@@ -149,3 +149,181 @@ def test_node_block_pattern_is_the_oracles_symbolic_pattern():
     ip, ix = ref.pattern()
     v = on_pattern(K, ip, ix)                      # every stored entry of the oracle's K is in the pattern
     assert (v != 0).mean() > 0.9 and ip[-1] == ix.size
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The P1 node route's 48-byte record: d[2] = -(d[0] + d[1]) (elem_ref's module docstring).
+#
+# Record form against exact form, worst |delta| / (u S) over RECORD_MESHES with a random symmetric ds (measured, CPU):
+#   widened scale   K 2.85   F 1.88      bound C_RECORD = 4      (with the return map's ds, s of the GPU cases: K 3.29, F 2.67)
+#   plain scale     K 21.9   F 26.6      (near-right mesh; the others: K <= 8.7, F <= 12.4)
+#   widened / plain scale, worst entry: K 23.9 / 26.9 / 31.8 / 86.7, F 36.2 / 25.0 / 16.0 / 89.4  (jittered / mixed / Delaunay / near-right)
+# Why 4: a term B_a^T (w ds) B_b carries the third gradient in at most two factors; each differs from the table gradient
+# by the one rounding of the sum, u (|d0| + |d1|) (widened: u * its own magnitude), and by the table gradient's own
+# roundings (two products and a sum: <= ~1 u of |d0| + |d1| in practice); 2 factors x (1 + 1) = 4 u of the widened term.
+# ---------------------------------------------------------------------------------------------------------------------------
+C_RECORD = 4
+RECORD_MESHES = ('jittered24', 'mixed24', 'delaunay24r', 'nearright24', 'aniso')
+STRUCTURED = ('square24', 'aniso', 'rect54x10', 'strip301x1', 'square7')
+
+
+def _p1_refs(name):
+    import p1_node_cases as cases
+    elem, coord, _ = cases.mesh(name)
+    tb = fep.element_tables('P1')
+    return ElemRef(elem, coord, tb), ElemRef(elem, coord, tb, record=True)
+
+
+def _symmetric_state(n_int, rng, decades=3):
+    A = rng.normal(size=(3, 3, n_int))
+    return (A + A.transpose(1, 0, 2)).reshape(9, n_int), rng.normal(size=(4, n_int)) * 10.0 ** rng.uniform(-decades, decades, n_int)
+
+
+@pytest.mark.parametrize('name', RECORD_MESHES)
+def test_record_form_against_exact_form_on_the_widened_scale(name):
+    exact, rec = _p1_refs(name)
+    ds, s = _symmetric_state(exact.n_int, np.random.default_rng(zlib.crc32(name.encode())))
+    K, S_K, F, S_F = exact.assemble(ds, s)
+    _, W_K, _, W_F = exact.assemble(ds, s, widened=True)
+    Kr, R_K, Fr, R_F = rec.assemble(ds, s)
+    rk, rf = ratio(Kr, K, W_K), ratio(Fr, F, W_F)
+    print(f'[record] {name}: widened K {rk:.2f} F {rf:.2f}; plain K {ratio(Kr, K, S_K):.2f} F {ratio(Fr, F, S_F):.2f}; '
+          f'widened / plain scale <= K {(W_K / S_K).max():.1f} F {(W_F / S_F).max():.1f}')
+    assert rk <= C_RECORD and rf <= C_RECORD, (rk, rf)
+    assert (W_K >= S_K * (1 - 1e-14)).all() and (W_F >= S_F * (1 - 1e-14)).all()
+    # the record's own plain scale lies within a rounding of the widened one from below (|d0 + d1| <= |d0| + |d1|)
+    assert (R_K <= W_K * (1 + 1e-14)).all() and (R_F <= W_F * (1 + 1e-14)).all()
+    # the strain keeps the table gradients (p1_point_kernel does)
+    U = np.random.default_rng(1).normal(size=(2, exact.n_n))
+    assert all(np.array_equal(a, b) for a, b in zip(exact.strain(U), rec.strain(U)))
+    # the values do not depend on the scale asked for
+    assert np.array_equal(rec.assemble(ds, s, widened=True)[0], Kr)
+
+
+@pytest.mark.parametrize('name', STRUCTURED)
+def test_record_form_is_bit_identical_on_structured_meshes(name):
+    """Un-jittered right triangles: d[0] + d[1] is exact (one of the two terms is 0 or they are equal and opposite in
+    each direction), so the record loses nothing, at 1 : 1000 cells either."""
+    exact, rec = _p1_refs(name)
+    ds, s = _symmetric_state(exact.n_int, np.random.default_rng(2))
+    a, b = exact.assemble(ds, s), rec.assemble(ds, s)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_near_right_mesh_exceeds_the_plain_bound():
+    """Why the widened scale exists: on right triangles moved by 1e-9 the third gradient has components of ~1e-9 of the
+    others, and -(d[0] + d[1]) gives them with the absolute error of the large ones.  Against the exact form the record
+    form then misses the element route's bound C_K['P1'] on the PLAIN scale (measured 21.9 against 10) while it is
+    within C_RECORD on the widened one.  If this test fails, the record no longer behaves as the node-route test assumes."""
+    from test_element_route_gpu import C_K
+    exact, rec = _p1_refs('nearright24')
+    ds, s = _symmetric_state(exact.n_int, np.random.default_rng(zlib.crc32(b'nearright24')))
+    K, S_K, _, _ = exact.assemble(ds, s)
+    W_K = exact.assemble(ds, s, widened=True)[1]
+    Kr = rec.assemble(ds, s)[0]
+    assert ratio(Kr, K, S_K) > C_K['P1']
+    assert ratio(Kr, K, W_K) <= C_RECORD
+    assert (W_K / S_K).max() > 20
+
+
+@pytest.mark.parametrize('name', RECORD_MESHES)
+def test_record_form_matches_the_oracle_on_the_widened_scale(name):
+    exact, rec = _p1_refs(name)
+    rng = np.random.default_rng(zlib.crc32(name.encode()) + 1)
+    ds, s, U = _random_state(rec.n_int, rec.n_n, rng)
+    Kt, F, _ = _oracle(rec.elem, rec.coord, fep.element_tables('P1'), ds, s, U)
+    K, W_K, Fr, W_F = rec.assemble(ds, s, widened=True)
+    ip, ix = rec.pattern()
+    assert ratio(K, on_pattern(Kt, ip, ix), W_K) <= C_REF
+    assert ratio(Fr, F, W_F) <= C_REF
+
+
+def test_record_form_is_p1_only():
+    elem, coord = meshes.square('P2', 3)
+    with pytest.raises(ValueError):
+        ElemRef(elem, coord, fep.element_tables('P2'), record=True)
+    with pytest.raises(ValueError):
+        ElemRef(elem, coord, fep.element_tables('P2')).assemble(np.zeros((9, elem.shape[1] * 7)), widened=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Sensitivity of the node-route criterion (reference side only, NumPy arrays): the faults a wrong gather plan produces,
+# one at a time, must each push |delta| / (u S) above the GPU test's bounds in at least one entry.
+# ---------------------------------------------------------------------------------------------------------------------------
+FAULTS = ('dropped', 'twice', 'wrong_node', 'neighbours_w', 'rows_swapped', 'off_by_1e-12')
+
+
+def _element_terms(rec, e, ds, s):
+    """K_e (6, 6), f_e (6,), w of element e in the record form."""
+    d1, d2, w, _ = rec.geometry(e, e + 1)
+    d1, d2, _, _ = rec.assembly_gradients(d1, d2)
+    B = rec._B(d1, d2)[0, 0]                                                  # (3, 6)
+    D = w[0, 0] * ds[:, e].reshape(3, 3)
+    return B.T @ D @ B, B.T @ (w[0, 0] * s[0:3, e]), w[0, 0]
+
+
+def _placements(rec):
+    """{'diag' | 'edge' | 'boundary': (element e, local a, local b, another element e2 at the block)}: the diagonal block
+    of an interior node, the block of an interior edge (two contributions) and the block of a boundary edge (one)."""
+    elem = rec.elem
+    x, y = rec.coord
+    on_edge = (x == x.min()) | (x == x.max()) | (y == y.min()) | (y == y.max())
+    out = {}
+    for e in range(rec.n_e):
+        for a in range(3):
+            b = (a + 1) % 3
+            n, m = elem[a, e], elem[b, e]
+            shared = np.flatnonzero((elem == n).any(axis=0) & (elem == m).any(axis=0))
+            other = [int(v) for v in shared if v != e]
+            if 'boundary' not in out and on_edge[n] and on_edge[m] and not other:
+                out['boundary'] = (e, a, b, int(np.flatnonzero((elem == n).any(axis=0) & (np.arange(rec.n_e) != e))[0]))
+            if 'edge' not in out and not on_edge[n] and not on_edge[m] and len(other) == 1:
+                out['edge'] = (e, a, b, other[0])
+            if 'diag' not in out and not on_edge[n] and other:
+                out['diag'] = (e, a, a, other[0])
+        if len(out) == 3:
+            break
+    return out
+
+
+@pytest.mark.parametrize('name', ['renumbered24', 'delaunay24r'])
+def test_node_route_criterion_detects_every_gather_fault(name):
+    from test_element_route_gpu import C_F, C_K
+    exact, rec = _p1_refs(name)
+    # point data of one magnitude: a contribution that is 1e-6 of its entry's scale can be off by 1e-12 of itself unseen by
+    # any criterion of this kind (first tried with s over six decades: the 1e-12 fault in F reached 6.7 against 12)
+    ds, s = _symmetric_state(rec.n_int, np.random.default_rng(zlib.crc32(name.encode()) + 2), decades=0)
+    K, S_K, F, S_F = rec.assemble(ds, s)
+    Kx, _, Fx, _ = exact.assemble(ds, s)
+    _, W_K, _, W_F = exact.assemble(ds, s, widened=True)
+    assert ratio(K, Kx, W_K) <= C_RECORD and ratio(F, Fx, W_F) <= C_RECORD
+    places = _placements(rec)
+    assert set(places) == {'diag', 'edge', 'boundary'}
+    for place, (e, a, b, e2) in places.items():
+        Ke, fe, w = _element_terms(rec, e, ds, s)
+        _, _, w2 = _element_terms(rec, e2, ds, s)
+        assert w2 != w
+        pos = rec._positions(rec.elem[:, e:e + 1].T)[0][2 * a:2 * a + 2, 2 * b:2 * b + 2]      # the block's four CSR positions
+        dof = 2 * rec.elem[a, e] + np.arange(2)
+        blk, f = Ke[2 * a:2 * a + 2, 2 * b:2 * b + 2], fe[2 * a:2 * a + 2]
+        c = (a + 1) % 3 if a == b else None                        # diagonal block: the second gradient of a wrong node
+        wrong = Ke[2 * a:2 * a + 2, 2 * c:2 * c + 2] if a == b else Ke[2 * b:2 * b + 2, 2 * a:2 * a + 2]
+        for fault in FAULTS:
+            Kf, Ff = K.copy(), F.copy()
+            if fault == 'dropped':
+                Kf[pos] -= blk; Ff[dof] -= f
+            elif fault == 'twice':
+                Kf[pos] += blk; Ff[dof] += f
+            elif fault == 'wrong_node':
+                Kf[pos] += wrong - blk; Ff[dof] += fe[2 * ((a + 1) % 3):2 * ((a + 1) % 3) + 2] - f
+            elif fault == 'neighbours_w':
+                Kf[pos] += (w2 / w - 1) * blk; Ff[dof] += (w2 / w - 1) * f
+            elif fault == 'rows_swapped':
+                Kf[pos] = Kf[pos][::-1]; Ff[dof] = Ff[dof][::-1]
+            else:
+                Kf[pos] += 1e-12 * blk; Ff[dof] += 1e-12 * f
+            rk, rkx = ratio(Kf, K, S_K), ratio(Kf, Kx, W_K)
+            rf, rfx = ratio(Ff, F, S_F), ratio(Ff, Fx, W_F)
+            print(f'[fault] {name} {place} {fault}: K {rk:.3g} (exact form, widened {rkx:.3g}) F {rf:.3g} ({rfx:.3g})')
+            assert rk > C_K['P1'] and rkx > C_K['P1'] + 4, (place, fault, rk, rkx)
+            assert rf > C_F['P1'] and rfx > C_F['P1'] + 4, (place, fault, rf, rfx)

@@ -32,6 +32,9 @@ pytestmark = pytest.mark.gpu
 C_E = {'P1': 6, 'P2': 8, 'Q1': 8, 'Q2': 8, 'P4': 8}           # measured 2.75, 3.83, 3.79, 3.73, 3.37
 C_K = {'P1': 10, 'P2': 16, 'Q1': 12, 'Q2': 16, 'P4': 24}      # measured 4.55, 7.63, 5.87, 7.29, 11.23
 C_F = {'P1': 8, 'P2': 12, 'Q1': 10, 'Q2': 10, 'P4': 12}       # measured 3.52, 5.70, 4.77, 4.71, 5.79
+# the P1 node route under the same P1 bounds (test_p1_node_route_gpu.py, against the record form): measured E 3.13, K 4.73, F 5.13;
+# against the exact form on the widened scale, bounds C_K + C_RECORD, C_F + C_RECORD: measured K 4.65, F 4.66
+C_RECORD = 4                   # the P1 record form against the exact form on the widened scale (test_elem_ref.py)
 TOL_PT_EACH = 1e-12            # stage 2, per point against its own largest entry (test_parity_gpu.py)
 TOL_PT_WIDE = 5e-12            # ... with materials spanning decades (test_return_map_random_materials_wide_ranges)
 
@@ -112,9 +115,12 @@ def _state(kind, coord, h, n_int, rng):
     return U, Ep, mats, e0, kind == 'accept'
 
 
-def _run_case(fep, monkeypatch, capfd, t, route, elem, coord, kind, h, rng, structured_ppe=None):
+def _run_case(fep, monkeypatch, capfd, t, route, elem, coord, kind, h, rng, structured_ppe=None, keep=None):
+    """One case on `route`: patch | coo (FEP_ROUTE), default (FEP_ROUTE unset, must come out as the patch form) or node (P1,
+    FEP_ROUTE unset, must come out as the node route: test_p1_node_route_gpu.py).  Returns the plan line's figures (node:
+    p1_node_cases.parse_lib's), None on the COO form; `keep` (a dict) receives the full-output step."""
     n_e = elem.shape[1]
-    if route == 'default':
+    if route in ('default', 'node'):
         monkeypatch.delenv('FEP_ROUTE', raising=False)
     else:
         monkeypatch.setenv('FEP_ROUTE', route)
@@ -125,9 +131,10 @@ def _run_case(fep, monkeypatch, capfd, t, route, elem, coord, kind, h, rng, stru
         monkeypatch.delenv('FEP_VALIDATE_PLAN', raising=False)
     capfd.readouterr()
     ctx = fep.MeshContext(elem, coord)
-    plan = PLAN.findall(capfd.readouterr().err)
+    err = capfd.readouterr().err
+    plan = PLAN.findall(err)
     assert_route(ctx, 'patch' if route == 'default' else route)
-    assert len(plan) == (0 if route == 'coo' else 1), plan
+    assert len(plan) == (0 if route in ('coo', 'node') else 1), plan
     n_int = ctx.n_int
     U, Ep, mats, e0, accept = _state(kind, coord, h, n_int, rng)
     ctx.set_materials(*mats)
@@ -163,6 +170,23 @@ def _run_case(fep, monkeypatch, capfd, t, route, elem, coord, kind, h, rng, stru
     if n_int >= 200:                                                # all three branches
         assert o['n_smooth'] > 0 and o['n_apex'] > 0 and o['n_smooth'] + o['n_apex'] < n_int, (o['n_smooth'], o['n_apex'])
     # 3. assembly of the kernel's ds and s
+    if keep is not None:
+        keep['full'] = full
+    if route == 'node':
+        # the node route sums the terms of the 48-byte record (elem_ref's module docstring): against the record form on
+        # its plain scale with the element route's bounds, against the exact form on the widened scale with C + C_RECORD
+        import p1_node_cases
+        rec = ElemRef(elem, coord, fep.element_tables(t), pattern=pattern, record=True)
+        K, S_K, F, S_F = rec.assemble(full['ds'], full['s'])
+        r_K, r_F = ratio(full['K'].data, K, S_K), ratio(full['F'], F, S_F)
+        Kx, W_K, Fx, W_F = ref.assemble(full['ds'], full['s'], widened=True)
+        x_K, x_F = ratio(full['K'].data, Kx, W_K), ratio(full['F'], Fx, W_F)
+        print(f'[ratios] {t} node n_e={n_e} E {r_E:.2f} K {r_K:.2f} F {r_F:.2f}; exact form, widened scale: K {x_K:.2f} F {x_F:.2f}')
+        assert r_K <= C_K[t], ('K', r_K)
+        assert r_F <= C_F[t], ('F', r_F)
+        assert x_K <= C_K[t] + C_RECORD, ('K, exact form', x_K)
+        assert x_F <= C_F[t] + C_RECORD, ('F, exact form', x_F)
+        return p1_node_cases.parse_lib(err)
     K, S_K, F, S_F = ref.assemble(full['ds'], full['s'])
     r_K = ratio(full['K'].data, K, S_K)
     r_F = ratio(full['F'], F, S_F)
