@@ -1449,6 +1449,19 @@ extern "C" int fep_iface_sum_f64(int device_id, void* stream, int64_t n, const i
     return FEP_OK;
 }
 
+extern "C" int fep_csr_merge_f64(int device_id, void* stream, int64_t n_blocks, const int32_t* first_d, const int32_t* multi_ptr_d,
+                                 const int32_t* multi_src_d, const double* recv_d, double* k_global_d) {
+    if (n_blocks < 0 || (n_blocks > 0 && (!first_d || !multi_ptr_d || !recv_d || !k_global_d))) return FEP_EINVAL;
+    if ((((uintptr_t)recv_d) | ((uintptr_t)k_global_d)) & 15) return FEP_EINVAL;      // pairs move as 16-byte words
+    if (n_blocks >= (int64_t)INT32_MAX / 4) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(device_id));
+    if (n_blocks == 0) return FEP_OK;
+    hipLaunchKernelGGL(csr_merge_kernel, dim3(grid_for(2 * n_blocks, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, 2 * n_blocks,
+                       first_d, multi_ptr_d, multi_src_d, (const double2*)recv_d, (double2*)k_global_d);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
 extern "C" int fep_transform_dev(fep_ctx* c, void* stream, const double* q_int_d, double* q_node_d) {
     if (!c || !q_int_d || !q_node_d) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));

@@ -1920,4 +1920,27 @@ iface_sum_kernel(int64_t n, const int32_t* __restrict__ loc, const int32_t* __re
     f[d] = acc;
 }
 
+// Gathered solve (sharding.GatherPlan): K = sum_r P_r^T K_r P_r on the global pattern from the receive buffer of the solve
+// rank.  One lane per PAIR of doubles (one row of a 2x2 node-pair block, two lanes per block): 16-byte loads and stores,
+// consecutive lanes write consecutive memory, every 64-byte chunk of `out` is written whole and exactly once — no zero
+// fill, no atomics.  first[q] >= 0: the pair's only contribution, a copy; else the pairs
+// msrc[mptr[k] .. mptr[k + 1]), k = -1 - first[q], summed from 0.0 in the listed (ascending rank) order.  The load of the
+// common case is issued unconditionally (for a listed pair it reads pair 0, which exists), so that no lane waits for a
+// load under a condition; the list is walked only by the few pairs between two interface nodes.
+__global__ void __launch_bounds__(kBlock)
+csr_merge_kernel(int64_t n_pairs, const int32_t* __restrict__ first, const int32_t* __restrict__ mptr,
+                 const int32_t* __restrict__ msrc, const double2* __restrict__ recv, double2* __restrict__ out) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n_pairs) return;
+    const int32_t f = first[q];
+    double2 v = recv[f >= 0 ? f : 0];
+    if (f < 0) {
+        const int32_t k = -1 - f;
+        double2 acc = make_double2(0.0, 0.0);
+        for (int32_t j = mptr[k]; j < mptr[k + 1]; ++j) { const double2 c = recv[msrc[j]]; acc.x += c.x; acc.y += c.y; }
+        v = acc;
+    }
+    out[q] = v;
+}
+
 }  // namespace fep

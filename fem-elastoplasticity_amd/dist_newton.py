@@ -15,19 +15,27 @@ ranks once per solve).  Per iteration: one local block SpMV (fep_solver_spmv_dev
 it), one interface exchange, two small all-reduces (p.Kp; r.z and r.r together).  The loop is driven from the host with
 torch tensors as device vectors; convergence is looked at every `check_every` iterations.
 
+GatheredSolver: the single-GPU multigrid conjugate gradients (solver.KrylovSolver) on K gathered to one rank every
+Newton iterate — K_r and right-hand sides sent to the solve rank, merged by fep_csr_merge_f64 through the tables of
+sharding.GatherPlan, solved there, x broadcast.  Block-Jacobi needs hundreds of times the iterations of the multigrid;
+the solve is not on the sharded hot path, so the cheapest sound form keeps the solver whole.
+
 solve_strip_footing_sharded: Plasticity2D_DP's load-step loop (DP:986-1131) on the ranks of the default process group.
 It is newton.py's loop itself, entered with a ShardedContext and _ShardOps: newton's device ops with the local slice
-in `vec`, the interface exchange of F, all-reduced branch counters, DistributedPCG as the solver, energy norms through
-the weighted inner product and global gathers in `host` / `nodal`.
+in `vec`, the interface exchange of F, all-reduced branch counters, DistributedPCG or GatheredSolver as the solver,
+energy norms through the weighted inner product and global gathers in `host` / `nodal`.
+solve_tsx_tunnel_sharded: the same for the TSX tunnel (TSX:1729-1832).
 
 The reference has no parallelism of any kind; this module is new.
 """
+import time
 from contextlib import closing
 
 import numpy as np
 
-from .newton import _DeviceOps, _footing_setup, _strip_footing, point_sums
+from .newton import _DeviceOps, _footing_setup, _strip_footing, _tsx_setup, _tsx_tunnel, point_sums
 from .sharding import ShardedContext
+from .tables import element_tables
 
 
 def _allreduce_(t, group=None, device=None):
@@ -52,8 +60,9 @@ def _allreduce_(t, group=None, device=None):
     return t
 
 
-class DistributedPCG:
-    """Block-Jacobi conjugate gradients on the sub-assembled K of a ShardedContext."""
+class _DistAlgebra:
+    """What every distributed solver here offers besides `pcg`: the local DOF numbering, the multiplicity weights, products
+    with the sub-assembled K (local block SpMV + interface exchange) and global inner products of consistent vectors."""
 
     def __init__(self, sc, free_dof_global, group=None):
         import torch
@@ -65,9 +74,32 @@ class DistributedPCG:
         self.dofs_global = dofs
         free = np.asarray(free_dof_global).ravel()[dofs] != 0
         self.solver = KrylovSolver(ctx, free)
-        f64 = dict(dtype=torch.float64, device=self.dev)
         self.free = torch.from_numpy(free.astype(np.float64)).to(self.dev)
         self.w = torch.from_numpy(np.repeat(1.0 / sc.mult, 2)).to(self.dev)          # 1 / multiplicity per local DOF
+        self.n_dof = ctx.n_dof
+        self.last = None
+
+    def close(self):
+        self.solver.close()
+
+    def exchange_(self, v):
+        return self.sc.exchange_force_(v, group=self.group)
+
+    def dot(self, a, b):
+        return _allreduce_((self.w * a * b).sum().reshape(1), self.group)[0]
+
+    def spmv(self, k_data, x, masked=False):
+        y = self.solver.spmv(k_data, x, masked=masked)
+        return self.exchange_(y)
+
+
+class DistributedPCG(_DistAlgebra):
+    """Block-Jacobi conjugate gradients on the sub-assembled K of a ShardedContext."""
+
+    def __init__(self, sc, free_dof_global, group=None):
+        super().__init__(sc, free_dof_global, group)
+        torch, ctx = self.torch, sc.ctx
+        f64 = dict(dtype=torch.float64, device=self.dev)
         self.wfree = self.w * self.free
         # positions of every node's diagonal 2x2 block in the CSR data of the local pattern
         ip, ix = ctx.pattern()
@@ -82,23 +114,7 @@ class DistributedPCG:
         p[row_of[hit] // 2] = hit - rows0[row_of[hit] // 2]
         self._d_idx = [torch.from_numpy(a).to(self.dev) for a in (rows0 + p, rows0 + p + 1, rows1 + p, rows1 + p + 1)]
         self._has = torch.from_numpy(has.astype(np.float64)).to(self.dev)
-        self.n_dof = ctx.n_dof
         self.tmp = [torch.empty(self.n_dof, **f64) for _ in range(2)]
-        self.last = None
-
-    def close(self):
-        self.solver.close()
-
-    # ---- building blocks ---------------------------------------------------------------------------------------
-    def exchange_(self, v):
-        return self.sc.exchange_force_(v, group=self.group)
-
-    def dot(self, a, b):
-        return _allreduce_((self.w * a * b).sum().reshape(1), self.group)[0]
-
-    def spmv(self, k_data, x, masked=False):
-        y = self.solver.spmv(k_data, x, masked=masked)
-        return self.exchange_(y)
 
     def _block_jacobi(self, k_data):
         """Inverse of the assembled 2x2 diagonal blocks restricted to the free DOFs, as four per-node vectors."""
@@ -163,14 +179,201 @@ class DistributedPCG:
         return x
 
 
+class GatheredSolver(_DistAlgebra):
+    """The single-GPU multigrid conjugate gradients (solver.KrylovSolver, precond='amg') on K gathered to one rank.
+
+    Every solve, each rank sends its K_r values and its right-hand side to the solve rank (one message per rank, persistent
+    buffers, one `batch_isend_irecv`); there fep_csr_merge_f64 sums them onto the global pattern (sharding.GatherPlan),
+    fep_gather_f64 picks the global right-hand side, the unchanged KrylovSolver solves, and x travels back in one
+    broadcast together with `iters`, `relres` and `state` — so `last` is the same on every rank and the load-step loop
+    branches the same way everywhere.  Products and inner products (energy norms) stay distributed (_DistAlgebra).
+    With one rank everything is a device copy and no process group is needed.  Under nccl only device tensors move and the
+    host is not synchronised before the solver itself reports its iteration count; under gloo (the rehearsal backend) the
+    messages are staged through pinned host buffers.  Ranks without elements (`min_elements_per_rank`) are not supported.
+
+    `seconds` accumulates, when `timed` is set (it synchronises the device around every phase), the wall time of
+    'send', 'merge', 'solve', 'broadcast' over `n_solves` solves (tools/newton_bench.py)."""
+
+    def __init__(self, sc, free_dof_global, elements_global, group=None, solve_rank=0):
+        import torch.distributed as dist
+        from .sharding import GatherPlan
+        if sc.gated:
+            raise ValueError('the gathered solve does not support ranks without elements (min_elements_per_rank)')
+        super().__init__(sc, free_dof_global, group)
+        torch = self.torch
+        self.world = sc.world
+        if self.world > 1 and not dist.is_initialized():
+            raise ValueError('more than one rank needs an initialised process group')
+        self.gloo = self.world > 1 and dist.get_backend(group) == 'gloo'         # resolved once
+        self._root = solve_rank if (group is None or self.world == 1) else dist.get_global_rank(group, solve_rank)
+        free_g = np.asarray(free_dof_global).ravel() != 0
+        n_n = free_g.size // 2
+        plan = self.plan = GatherPlan(sc, elements_global, n_n, solve_rank)
+        self.is_solve_rank = plan.is_solve_rank
+        if plan.block_map.size != sc.ctx.nnz // 4:
+            raise AssertionError('the local pattern is not the node graph of the local elements')
+        if self.world == 1:
+            maps = [plan.own_map()]
+        else:
+            maps = [None] * self.world if self.is_solve_rank else None
+            dist.gather_object(plan.own_map(), maps, dst=self._root, group=group)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev)
+        self.n_dof_g = 2 * n_n
+        self.nnz_l = sc.ctx.nnz
+        self._xbuf = torch.empty(self.n_dof_g + 3, **f64)                        # x, iters, relres, state: one broadcast
+        self._xbuf_h = torch.empty(self.n_dof_g + 3, dtype=torch.float64).pin_memory() if self.gloo else None
+        self._slice = i32(self.dofs_global)
+        self.global_solver = None
+        if self.is_solve_rank:
+            from .solver import KrylovSolver
+            plan.build_merge(maps)
+            self._tab = [i32(a) for a in (plan.first, plan.multi_ptr, plan.multi_src, plan.rhs_index)]
+            self._recv = torch.empty(plan.n_recv, **f64)
+            self._recv_h = torch.empty(plan.n_recv, dtype=torch.float64).pin_memory() if self.gloo else None
+            self._kg = torch.empty(plan.nnz, **f64)
+            self._bg = torch.empty(self.n_dof_g, **f64)
+            self._tail_h = torch.empty(3, dtype=torch.float64).pin_memory()
+            self.global_solver = KrylovSolver(plan.pattern, free_g, device=sc.ctx.device)
+        else:
+            self._send = torch.empty(plan.n_send, **f64)
+            self._send_h = torch.empty(plan.n_send, dtype=torch.float64).pin_memory() if self.gloo else None
+            plan.nptr = plan.ncol = plan._pattern = None                         # the global pattern was only needed for the map
+        self.timed = False
+        self.seconds = {'send': 0.0, 'merge': 0.0, 'solve': 0.0, 'broadcast': 0.0}
+        self.n_solves = 0
+
+    def close(self):
+        super().close()
+        if self.global_solver is not None:
+            self.global_solver.close()
+
+    def _tick(self, key, t0):
+        if not self.timed:
+            return t0
+        import time
+        self.torch.cuda.synchronize(self.dev)
+        t1 = time.perf_counter()
+        if key is not None:
+            self.seconds[key] += t1 - t0
+        return t1
+
+    def _gather(self, k_data, b):
+        """K_r and b_r of every rank into the receive buffer of the solve rank."""
+        import torch.distributed as dist
+        n = self.nnz_l
+        if self.is_solve_rank:
+            a = self.plan.offsets
+            own = self._recv[a[self.sc.rank]:a[self.sc.rank + 1]]
+            own[:n].copy_(k_data)
+            own[n:].copy_(b)
+            if self.world > 1:
+                buf = self._recv_h if self.gloo else self._recv
+                ops = [dist.P2POp(dist.irecv, buf[a[r]:a[r + 1]], self._peer(r), self.group)
+                       for r in range(self.world) if r != self.sc.rank]
+                for w in dist.batch_isend_irecv(ops):
+                    w.wait()                                                     # nccl: orders the stream, no host wait
+                if self.gloo:
+                    for r in range(self.world):
+                        if r != self.sc.rank:
+                            self._recv[a[r]:a[r + 1]].copy_(buf[a[r]:a[r + 1]], non_blocking=True)
+        else:
+            buf = self._send_h if self.gloo else self._send                      # (gloo: the copies synchronise; rehearsal only)
+            buf[:n].copy_(k_data)
+            buf[n:].copy_(b)
+            for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, buf, self._root, self.group)]):
+                w.wait()
+
+    def _peer(self, r):
+        import torch.distributed as dist
+        return dist.get_global_rank(self.group, r) if self.group is not None else r
+
+    def _merge(self):
+        """K on the global pattern and the global right-hand side from the receive buffer (solve rank)."""
+        from . import _lib
+        first, mptr, msrc, rhs = self._tab
+        st = self.torch.cuda.current_stream(self.dev).cuda_stream
+        l = _lib.lib()
+        _lib.check(l.fep_csr_merge_f64(self.dev.index, st, self.plan.n_blocks, first.data_ptr(), mptr.data_ptr(), msrc.data_ptr(),
+                                       self._recv.data_ptr(), self._kg.data_ptr()), 'fep_csr_merge_f64')
+        _lib.check(l.fep_gather_f64(self.dev.index, st, self.n_dof_g, self._recv.data_ptr(), rhs.data_ptr(), self._bg.data_ptr()),
+                   'fep_gather_f64')
+
+    def setup(self, K_elast, coordinates):
+        """The multigrid hierarchy of the solve rank from the gathered K_elast (local values in, global coordinates)."""
+        self._gather(K_elast, self.torch.zeros(self.n_dof, dtype=self.torch.float64, device=self.dev))
+        if self.is_solve_rank:
+            self._merge()
+            self.global_solver.setup_amg(self._kg.cpu().numpy(), coordinates, k_dev=self._kg)
+
+    def pcg(self, k_data, b, rtol=1e-11, max_iter=100000):
+        """x (consistent, 0 on constrained DOFs) with |r| <= rtol |b[Q]|, by the multigrid solver of the solve rank."""
+        from . import _lib
+        import torch.distributed as dist
+        torch = self.torch
+        if self.is_solve_rank and not self.global_solver.amg_levels:
+            raise RuntimeError('GatheredSolver.setup has not run')
+        t = self._tick(None, 0.0)
+        self._gather(k_data, b)
+        t = self._tick('send', t)
+        if self.is_solve_rank:
+            self._merge()
+            t = self._tick('merge', t)
+            gs = self.global_solver
+            gs.pcg(self._kg, self._bg, out=self._xbuf[:self.n_dof_g], rtol=rtol, max_iter=max_iter, precond='amg')
+            self._tail_h[0], self._tail_h[1], self._tail_h[2] = gs.last['iters'], gs.last['relres'], gs.last['state']
+            self._xbuf[self.n_dof_g:].copy_(self._tail_h, non_blocking=True)
+            t = self._tick('solve', t)
+        if self.world > 1:
+            if self.gloo:
+                if self.is_solve_rank:
+                    self._xbuf_h.copy_(self._xbuf)
+                dist.broadcast(self._xbuf_h, self._root, group=self.group)
+                if not self.is_solve_rank:
+                    self._xbuf.copy_(self._xbuf_h, non_blocking=True)
+                tail = self._xbuf_h[self.n_dof_g:]
+            else:
+                dist.broadcast(self._xbuf, self._root, group=self.group)
+                tail = self._xbuf[self.n_dof_g:].cpu()
+        else:
+            tail = self._tail_h
+            torch.cuda.current_stream(self.dev).synchronize()
+        x = torch.empty(self.n_dof, dtype=torch.float64, device=self.dev)
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        _lib.check(_lib.lib().fep_gather_f64(self.dev.index, st, self.n_dof, self._xbuf.data_ptr(), self._slice.data_ptr(),
+                                             x.data_ptr()), 'fep_gather_f64')
+        self.last = {'iters': int(tail[0]), 'relres': float(tail[1]), 'state': int(tail[2]), 'precond': 'amg'}
+        self._tick('broadcast', t)
+        self.n_solves += 1
+        return x
+
+
 class _ShardOps(_DeviceOps):
     """newton._DeviceOps on a ShardedContext: local vectors (consistent on the interface), sub-assembled K, DistributedPCG
-    as the solver.  Only what the sharding changes is stated here."""
+    (`linear_solver='pcg'`) or GatheredSolver ('amg', which needs the global element table) as the solver.  Only what the
+    sharding changes is stated here."""
 
-    def __init__(self, sc, qf_global, rtol=1e-11, max_iter=200000, inexact_rtol=None, group=None):
-        super().__init__(sc.ctx, DistributedPCG(sc, qf_global, group), rtol=rtol, max_iter=max_iter, inexact_rtol=inexact_rtol)
+    def __init__(self, sc, qf_global, rtol=1e-11, max_iter=200000, inexact_rtol=None, group=None, linear_solver='pcg',
+                 solve_rank=0, elements_global=None):
+        if linear_solver not in ('pcg', 'amg'):
+            raise ValueError("linear_solver must be 'pcg' or 'amg'")
+        solver = (DistributedPCG(sc, qf_global, group) if linear_solver == 'pcg' else
+                  GatheredSolver(sc, qf_global, elements_global, group, solve_rank))
+        super().__init__(sc.ctx, solver, rtol=rtol, max_iter=max_iter, inexact_rtol=inexact_rtol, amg=linear_solver == 'amg')
         self.sc, self.group = sc, group
         self.n_dof_global = int(np.asarray(qf_global).size)
+
+    def setup_amg(self, K, coordinates):
+        if self.amg:
+            self.solver.setup(K, coordinates)
+
+    def assembled(self, f_local):
+        """A force vector assembled by the rank's context (partial on the interface), made consistent."""
+        return self.solver.exchange_(self.torch.from_numpy(np.array(f_local, dtype=np.float64).ravel()).to(self.dev))
+
+    def count(self, flags):
+        n = self.torch.count_nonzero(flags).reshape(1).to(self.torch.int64)
+        return int(_allreduce_(n, self.group))
 
     def vec(self, a_global):
         a = np.asarray(a_global, dtype=np.float64).ravel()[self.solver.dofs_global]
@@ -202,18 +405,54 @@ class _ShardOps(_DeviceOps):
         return (f[0] / f[1]).numpy()
 
 
+def _ranks(group):
+    import torch.distributed as dist
+    if not dist.is_initialized():
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
+
+
 def solve_strip_footing_sharded(element_type='P1', level=1, n_cells=None, size_xy=10, max_steps=None, zeta_max=1.0,
-                                device=None, log=None, pcg_rtol=1e-11, pcg_inexact_rtol=None, keep_U=True, group=None):
+                                device=None, log=None, pcg_rtol=1e-11, pcg_inexact_rtol=None, keep_U=True, group=None,
+                                linear_solver='pcg', solve_rank=0, timed=False):
     """newton.solve_strip_footing on the ranks of the process group (torch.distributed initialised by the caller; a
     single process works too): the mesh is split by contiguous element ranges, every rank runs the hot path on its
-    shard and the distributed conjugate gradients above solve the Newton corrections.  Returns the same history on every
-    rank ('U' holds GLOBAL displacement fields; 'Ep' is the rank's own slice)."""
-    import torch.distributed as dist
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    shard, and the Newton corrections are solved by the distributed block-Jacobi conjugate gradients above
+    (`linear_solver='pcg'`) or by the multigrid solver on K gathered to rank `solve_rank` ('amg', GatheredSolver).  Every
+    rank takes elements: idle ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on every
+    rank ('U' holds GLOBAL displacement fields; 'Ep' is the rank's own slice).  `timed` ('amg' only): the gathered solve
+    synchronises around its phases and the history gets 'gathered_solve' = seconds per phase and the number of solves."""
+    rank, world = _ranks(group)
     mesh, sc, c0, t_setup = _footing_setup(element_type, level, n_cells, size_xy,
                                            lambda elem, coord, *tab: ShardedContext(elem, coord, rank, world, *tab, device=device))
     with closing(sc), closing(_ShardOps(sc, mesh['Q'].flatten(order='F'), rtol=pcg_rtol, inexact_rtol=pcg_inexact_rtol,
-                                        group=group)) as ops:
-        return _strip_footing(mesh=mesh, ctx=sc.ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
+                                        group=group, linear_solver=linear_solver, solve_rank=solve_rank,
+                                        elements_global=mesh['elements'])) as ops:
+        if linear_solver == 'amg':
+            ops.solver.timed = bool(timed)
+        hist = _strip_footing(mesh=mesh, ctx=sc.ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
                               zeta_max=zeta_max, keep_U=keep_U, log=log)
+        if linear_solver == 'amg' and timed:
+            hist['gathered_solve'] = dict(ops.solver.seconds, n_solves=ops.solver.n_solves)
+        return hist
+
+
+def solve_tsx_tunnel_sharded(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
+                             linear_solver='amg', pcg_rtol=1e-11, mesh_dir=None, pcg_inexact_rtol=None, refine=0,
+                             renumber=False, group=None, solve_rank=0):
+    """newton.solve_tsx_tunnel on the ranks of the process group (a single process works too), arguments as there
+    (`linear_solver` 'pcg' or 'amg' as in solve_strip_footing_sharded; no `context_factory`, no forcing).  Every rank
+    prepares the same mesh (`refine` / `renumber` run on each rank's device; the device refinement is bit-equal to the host
+    one, so all ranks see one mesh), takes a contiguous range of its elements and enters newton's loop with its
+    ShardedContext: the initial-stress force is made consistent by the interface exchange, the plastic-point counts are
+    summed over the ranks.  Idle ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on
+    every rank."""
+    rank, world = _ranks(group)
+    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, None, log)
+    clock = [time.perf_counter()]
+    sc = ShardedContext(p['elem'], p['coords'], rank, world, *element_tables(p['type']), device=device)
+    sc.set_materials(*p['materials'])
+    clock.append(time.perf_counter())
+    with closing(sc), closing(_ShardOps(sc, p['Q'].flatten(order='F'), rtol=pcg_rtol, inexact_rtol=pcg_inexact_rtol, group=group,
+                                        linear_solver=linear_solver, solve_rank=solve_rank, elements_global=p['elem'])) as ops:
+        return _tsx_tunnel(p, sc.ctx, ops, clock, n_load_steps, log)

@@ -103,6 +103,13 @@ class _HostOps:
     def load_volume(self, uniform):
         return self.vec(self.ctx.load_volume(uniform=uniform).flatten(order='F'))
 
+    def assembled(self, f):
+        """A force vector the context assembled on the host, as a vector of these ops."""
+        return self.vec(f)
+
+    def count(self, flags):
+        return int(self.host(flags).astype(bool).sum())
+
     def close(self):
         pass
 
@@ -206,6 +213,14 @@ class _DeviceOps:
         out = t.empty(self.ctx.n_n, dtype=t.float64, device=self.dev)
         self.ctx.transform_dev(self._stream(), q.data_ptr(), out.data_ptr())
         return out.cpu().numpy()
+
+    def assembled(self, f):
+        """A force vector the context assembled on the host, as a vector of these ops (the sharded subclass sums the interface)."""
+        return self.vec(f)
+
+    def count(self, flags):
+        """Number of set flags of a point array (the sharded subclass sums over the ranks)."""
+        return int(self.host(flags).astype(bool).sum())
 
     def load_volume(self, uniform):
         f = self.zeros()
@@ -368,6 +383,19 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     `element_type`; on the GPU when the context is the GPU one, on the host with a `context_factory`.  `monitor` keeps
     naming a node of the INPUT mesh; 'U' is in the numbering of the mesh solved on, returned as 'coords' / 'elem', and
     'node_of_input' maps input node ids to it (None unless renumbered)."""
+    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log)
+    clock = [time.perf_counter()]
+    ctx = _context_maker(context_factory, device)(p['elem'], p['coords'], *element_tables(p['type']))
+    assert ctx.n_int == p['elem'].shape[1] * ELEMENT_SHAPE[p['type']][1]
+    ctx.set_materials(*p['materials'])
+    clock.append(time.perf_counter())
+    with closing(ctx), closing(make_ops(ctx, p['Q'].flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
+                                        pcg_inexact_rtol)) as ops:
+        return _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log)
+
+
+def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log):
+    """Mesh, materials, initial stress and constraints of the TSX problem (TSX:1637-1699), before any context exists."""
     t = _coerce(element_type)
     node_of_input, t_mesh = None, {}
     if refine or renumber:
@@ -405,45 +433,46 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     Q[0, coords[0, :] > 49.99] = 0
     Q[1, coords[1, :] < -49.99] = 0
     Q[1, coords[1, :] > 49.99] = 0
-    clock = [time.perf_counter()]
-    ctx = _context_maker(context_factory, device)(elem, coords, *element_tables(t))
-    n_int = ctx.n_int
-    assert n_int == elem.shape[1] * ELEMENT_SHAPE[t][1]
-    ctx.set_materials(shear0, bulk0, eta0, c_0)
+    return {'type': t, 'coords': coords, 'elem': elem, 'monitor': monitor, 'node_of_input': node_of_input, 't_mesh': t_mesh,
+            'materials': (shear0, bulk0, eta0, c_0), 's0': s0, 'init_strain': init_strain, 'Q': Q,
+            'prepared': bool(refine or renumber)}
+
+
+def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log):
+    """solve_tsx_tunnel once the problem `p` (_tsx_setup), context (materials set) and ops exist (dist_newton.py enters here
+    with its sharded ones).  `clock`: the times before and after the context was made."""
+    coords, monitor, s0, init_strain = p['coords'], p['monitor'], p['s0'], p['init_strain']
+    K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                              # TSX:1722
     clock.append(time.perf_counter())
-    with closing(ctx), closing(make_ops(ctx, Q.flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
-                                        pcg_inexact_rtol)) as ops:
-        K = ops.step(ops.zeros(), want=('K',), keep_K=True)['K']                          # TSX:1722
-        clock.append(time.perf_counter())
-        ops.setup_amg(K, coords)                                                          # linear_solver='amg' only
-        clock.append(time.perf_counter())
-        t_setup = dict(t_mesh, **dict(zip(('context', 'solver + K_elast', 'hierarchy'),
-                                          (b - a for a, b in zip(clock[:-1], clock[1:])))))
+    ops.setup_amg(K, coords)                                                              # linear_solver='amg' only
+    clock.append(time.perf_counter())
+    t_setup = dict(p['t_mesh'], **dict(zip(('context', 'solver + K_elast', 'hierarchy'),
+                                           (b - a for a, b in zip(clock[:-1], clock[1:])))))
+    if log:
+        log('setup: context %.2f s, solver + K_elast %.2f s, multigrid hierarchy %.2f s'
+            % (t_setup['context'], t_setup['solver + K_elast'], t_setup['hierarchy']))
+    F0 = ops.assembled(ctx.assemble(None, s0 * np.ones((1, ctx.n_int)))[1])               # TSX:1737
+
+    d_zeta = 1 / n_load_steps                                                             # TSX:1730-1735
+    U_elast = ops.solve(K, -F0)                                                           # TSX:1748
+    hist = {'zeta': [], 'displ': [], 'n_plast': [], 'U': [], 'n_calls': 0}
+
+    def accepted(r, zeta, U, Ep_old, its, criterion):
+        Um = ops.host(U).reshape((2, -1), order='F')
+        hist['displ'].append(Um[monitor])
+        hist['n_plast'].append(ops.count(r['ind_p']))
+        hist['U'].append(Um.copy())
         if log:
-            log('setup: context %.2f s, solver + K_elast %.2f s, multigrid hierarchy %.2f s'
-                % (t_setup['context'], t_setup['solver + K_elast'], t_setup['hierarchy']))
-        _, F0 = ctx.assemble(None, s0 * np.ones((1, n_int)))                               # TSX:1737
+            log(f'zeta={zeta:.6g} U{monitor}={Um[monitor]:.16g} n_plast={hist["n_plast"][-1]}')
+        return ops.new_ep(), False                                   # 'ep' of a non-accepting call, TSX:1809
 
-        d_zeta = 1 / n_load_steps                                                         # TSX:1730-1735
-        U_elast = ops.solve(K, ops.vec(-F0))                                              # TSX:1748
-        hist = {'zeta': [], 'displ': [], 'n_plast': [], 'U': [], 'n_calls': 0}
-
-        def accepted(r, zeta, U, Ep_old, its, criterion):
-            Um = ops.host(U).reshape((2, -1), order='F')
-            hist['displ'].append(Um[monitor])
-            hist['n_plast'].append(int(ops.host(r['ind_p']).astype(bool).sum()))
-            hist['U'].append(Um.copy())
-            if log:
-                log(f'zeta={zeta:.6g} U{monitor}={Um[monitor]:.16g} n_plast={hist["n_plast"][-1]}')
-            return ops.new_ep(), False                               # 'ep' of a non-accepting call, TSX:1809
-
-        # the accepting call leaves apply_plastic_strain False (C7)
-        _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
-                        accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
-        hist['F0'] = F0.reshape((2, -1), order='F')
-        hist['Q'] = Q
-        hist['pcg_iters'] = ops.pcg_iters
-        hist['t_setup'] = t_setup
-        if refine or renumber:
-            hist['coords'], hist['elem'], hist['node_of_input'] = coords, elem, node_of_input
-        return hist
+    # the accepting call leaves apply_plastic_strain False (C7)
+    _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
+                    accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
+    hist['F0'] = np.asarray(ops.host(F0)).reshape((2, -1), order='F')
+    hist['Q'] = p['Q']
+    hist['pcg_iters'] = ops.pcg_iters
+    hist['t_setup'] = t_setup
+    if p['prepared']:
+        hist['coords'], hist['elem'], hist['node_of_input'] = coords, p['elem'], p['node_of_input']
+    return hist

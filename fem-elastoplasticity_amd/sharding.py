@@ -284,3 +284,204 @@ class ShardedContext(Partition):
     def local_point_slice(self):
         n_q = self.ctx.n_q if self.ctx is not None else 0
         return slice(self.lo * n_q, self.hi * n_q)
+
+
+# ---- gathering the sub-assembled K on one rank (dist_newton.GatheredSolver) ------------------------------------------
+#
+# K = sum_r P_r^T K_r P_r is formed on ONE rank, the "solve rank", so that the single-GPU multigrid solver can run on it
+# unchanged.  Everything below is index work on the host, done once per mesh.
+#
+#   pair      two adjacent doubles of a CSR data array: one row of a 2x2 node-pair block.  Block b = nptr[n] + s of node n
+#             (s-th neighbour, deg = deg(n)) owns the pairs 2 b - s (row 2n) and 2 b - s + deg (row 2n + 1): the values
+#             data[4 b - 2 s], +1 and +2 deg, +1.  All tables of the merge count in pairs, so that the kernel
+#             moves 16 bytes per lane and consecutive lanes write consecutive memory.
+#   receive   buffer of the solve rank: per rank, in ascending rank order, its K_r values followed by its right-hand side.
+
+_I32_MAX = 2 ** 31 - 1
+
+
+def node_graph(elements, n_n):
+    """Node graph of an element table (n_p, n_e): `nptr` (n_n + 1, int64) and `ncol` (int32), per node the ascending ids of
+    the nodes it shares an element with, itself included — the graph `build_symbolic` of csrc/fep_host.h forms."""
+    elements = np.asarray(elements, dtype=np.int64)
+    n_p, n_e = elements.shape
+    n_n = int(n_n)
+    if n_e and (int(elements.min()) < 0 or int(elements.max()) >= n_n):
+        raise ValueError('node id out of range')
+    key = (elements[:, None, :] * n_n + elements[None, :, :]).ravel()          # (node, neighbour) of every element-local block
+    key = np.unique(key)
+    if 4 * key.size > _I32_MAX:
+        raise ValueError('the pattern has more than 2^31 - 1 entries (FEP_ERANGE)')
+    row = key // n_n
+    nptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=n_n))]).astype(np.int64)
+    return nptr, (key - row * n_n).astype(np.int32)
+
+
+def pattern_of_graph(nptr, ncol):
+    """The CSR pattern on DOFs that `MeshContext.pattern()` reports for the node graph: (indptr, indices), int32."""
+    nptr = np.asarray(nptr, dtype=np.int64)
+    deg = np.diff(nptr)
+    indptr = np.empty(2 * deg.size + 1, dtype=np.int64)
+    indptr[0:-1:2] = 4 * nptr[:-1]
+    indptr[1::2] = 4 * nptr[:-1] + 2 * deg
+    indptr[-1] = 4 * nptr[-1]
+    cols = (2 * np.asarray(ncol, dtype=np.int64)[:, None] + np.arange(2)[None, :]).ravel()      # one block row of every node
+    row2 = np.repeat(np.arange(deg.size), 2 * deg)                                              # ... laid down twice per node
+    pos = np.arange(cols.size) - 2 * nptr[row2]
+    indices = np.empty(2 * cols.size, dtype=np.int32)
+    indices[4 * nptr[row2] + pos] = cols
+    indices[4 * nptr[row2] + 2 * deg[row2] + pos] = cols
+    return indptr.astype(np.int32), indices
+
+
+def global_pattern(elements, n_n):
+    """CSR pattern of the whole mesh, entry for entry what `MeshContext(whole mesh).pattern()` reports (no GPU needed)."""
+    return pattern_of_graph(*node_graph(elements, n_n))
+
+
+def merge_host(first, multi_ptr, multi_src, recv, out=None):
+    """What fep_csr_merge_f64 does, in NumPy: pair q of the result is pair first[q] of `recv` where first[q] >= 0 (one
+    contribution: a copy), else the sum from 0.0, in the listed (ascending rank) order, of the pairs
+    multi_src[multi_ptr[k] : multi_ptr[k + 1]], k = -1 - first[q]."""
+    first = np.asarray(first)
+    r2 = np.asarray(recv, dtype=np.float64).reshape(-1, 2)
+    res = np.empty((first.size, 2)) if out is None else out.reshape(-1, 2)
+    one = first >= 0
+    res[one] = r2[first[one]]
+    sel = np.flatnonzero(~one)
+    k = -1 - first[sel].astype(np.int64)
+    lo, cnt = np.asarray(multi_ptr)[k], np.diff(np.asarray(multi_ptr))[k]
+    acc = np.zeros((sel.size, 2))
+    for j in range(int(cnt.max()) if cnt.size else 0):                          # j-th contribution of every pair that has one
+        m = cnt > j
+        acc[m] += r2[np.asarray(multi_src)[lo[m] + j]]
+    res[sel] = acc
+    return res.reshape(-1)
+
+
+class GatherPlan:
+    """Index tables of the gathered solve for one rank of a Partition.
+
+    Every rank:    `pattern`     (indptr, indices) of the whole mesh (needed for the map; may be dropped afterwards),
+                   `block_map`   int32 per LOCAL node-pair block: the global block of (nodes[i], nodes[j]); increasing,
+                                 because local nodes are sorted by global id.  One word per four values of K_r.
+                   `n_send`      doubles this rank sends per solve: its K_r values, then its right-hand side.
+    Solve rank, after `build_merge(maps)` with every rank's (nodes, block_map) in rank order:
+                   `offsets`     start of every rank's segment of the receive buffer (doubles), `n_recv` its length,
+                   `first`, `multi_ptr`, `multi_src`   the merge tables (merge_host), one word per PAIR of the global data,
+                   `rhs_index`   per global DOF its position in the receive buffer, taken from the lowest rank that holds it
+                                 (-1, i.e. 0.0 through fep_gather_f64, for a DOF of no element)."""
+
+    def __init__(self, part, elements, n_n, solve_rank=0):
+        if not 0 <= int(solve_rank) < part.active_world:
+            raise ValueError('solve_rank must be a rank that holds elements')
+        self.part, self.solve_rank, self.n_n = part, int(solve_rank), int(n_n)
+        self.is_solve_rank = part.rank == self.solve_rank
+        self.nptr, self.ncol = node_graph(elements, n_n)
+        self.n_blocks = int(self.nptr[-1])
+        self.nnz = 4 * self.n_blocks
+        lptr, lcol = node_graph(part.local_elements, part.nodes.size)
+        g = part.nodes.astype(np.int64)
+        lrow = np.repeat(np.arange(g.size), np.diff(lptr))
+        key_l = g[lrow] * self.n_n + g[lcol]
+        key_g = np.repeat(np.arange(self.n_n, dtype=np.int64), np.diff(self.nptr)) * self.n_n + self.ncol
+        bm = np.searchsorted(key_g, key_l)
+        if not (bm.size == 0 or (bm[-1] < key_g.size and np.array_equal(key_g[bm], key_l))):
+            raise AssertionError('a local block is missing from the global pattern')
+        self.block_map = bm.astype(np.int32)
+        self.n_send = 4 * bm.size + 2 * g.size
+        self._pattern = None
+        self.first = self.multi_ptr = self.multi_src = self.rhs_index = self.offsets = None
+        self.n_recv = 0
+
+    @property
+    def pattern(self):
+        if self._pattern is None:
+            self._pattern = pattern_of_graph(self.nptr, self.ncol)
+        return self._pattern
+
+    def own_map(self):
+        """What this rank sends to the solve rank once: its global node ids and its block map."""
+        return self.part.nodes.astype(np.int64), self.block_map
+
+    def build_merge(self, maps):
+        """Merge tables from every active rank's `own_map()`, in ascending rank order."""
+        deg_g = np.diff(self.nptr)
+        row_g = np.repeat(np.arange(self.n_n, dtype=np.int64), deg_g)           # node of every global block
+        n_pairs = 2 * self.n_blocks
+        tgt, src, offsets, off = [], [], [], 0
+        holder = np.full(self.n_n, -1, dtype=np.int64)                          # per node: position of its DOF pair in recv
+        for nodes, bm in maps:
+            nodes, bm = np.asarray(nodes, dtype=np.int64), np.asarray(bm, dtype=np.int64)
+            offsets.append(off)
+            rows = row_g[bm]
+            start = np.flatnonzero(np.concatenate([[True], rows[1:] != rows[:-1]])) if bm.size else np.zeros(0, np.int64)
+            if not np.array_equal(rows[start], nodes):                          # one run of blocks per local node, in node order
+                raise AssertionError('block map and node list of a rank do not match')
+            deg_l = np.diff(np.concatenate([start, [bm.size]]))
+            ls = np.arange(bm.size) - np.repeat(start, deg_l)
+            top_l = off // 2 + 2 * np.arange(bm.size) - ls
+            top_g = 2 * bm - (bm - self.nptr[rows])
+            tgt += [top_g, top_g + deg_g[rows]]
+            src += [top_l, top_l + np.repeat(deg_l, deg_l)]
+            new = nodes[holder[nodes] < 0]
+            holder[new] = off + 4 * bm.size + 2 * np.searchsorted(nodes, new)
+            off += 4 * bm.size + 2 * nodes.size
+        if off > _I32_MAX:
+            raise ValueError('the receive buffer has more than 2^31 - 1 values (FEP_ERANGE)')
+        self.offsets, self.n_recv = np.asarray(offsets + [off], dtype=np.int64), off
+        tgt, src = np.concatenate(tgt), np.concatenate(src)
+        order = np.argsort(tgt, kind='stable')                                  # stable: contributions stay in ascending rank order
+        tgt, src = tgt[order], src[order]
+        cnt = np.bincount(tgt, minlength=n_pairs)
+        if cnt.size != n_pairs or (n_pairs and int(cnt.min()) < 1):
+            raise AssertionError('a global block has no contribution')
+        ptr = np.concatenate([[0], np.cumsum(cnt)])
+        multi = np.flatnonzero(cnt > 1)
+        first = src[ptr[:-1]].astype(np.int32)
+        first[multi] = -1 - np.arange(multi.size, dtype=np.int32)
+        self.first = first
+        self.multi_ptr = np.concatenate([[0], np.cumsum(cnt[multi])]).astype(np.int32)
+        sel = np.repeat(cnt > 1, cnt)
+        self.multi_src = src[sel].astype(np.int32)
+        self.rhs_index = np.where(holder >= 0, holder, -1)[:, None] + np.where(holder >= 0, 1, 0)[:, None] * np.arange(2)[None, :]
+        self.rhs_index = self.rhs_index.ravel().astype(np.int32)
+        return self
+
+    def pack_host(self, k_local, b_local):
+        """This rank's segment of the receive buffer."""
+        return np.concatenate([np.asarray(k_local, dtype=np.float64).ravel(), np.asarray(b_local, dtype=np.float64).ravel()])
+
+    def merge_host(self, recv):
+        """(K values on the global pattern, global right-hand side) from the receive buffer: the host statement of
+        fep_csr_merge_f64 followed by fep_gather_f64."""
+        recv = np.asarray(recv, dtype=np.float64)
+        k = merge_host(self.first, self.multi_ptr, self.multi_src, recv[:2 * (recv.size // 2)])
+        b = np.where(self.rhs_index >= 0, recv[np.maximum(self.rhs_index, 0)], 0.0)
+        return k, b
+
+    def solve_host(self, k_local, b_local, solve, group=None):
+        """Host form of one gathered solve (the gloo tests): every rank sends its segment to the solve rank, which merges,
+        calls `solve(k_global, b_global) -> x_global`, and broadcasts x; returns this rank's slice of x."""
+        import torch
+        import torch.distributed as dist
+        p = self.part
+        seg = torch.from_numpy(self.pack_host(k_local, b_local))
+        x = torch.empty(2 * self.n_n, dtype=torch.float64)
+        if p.world == 1:
+            x = torch.from_numpy(np.asarray(solve(*self.merge_host(seg.numpy())), dtype=np.float64))
+        else:
+            glob = (lambda r: dist.get_global_rank(group, r)) if group is not None else (lambda r: r)
+            if self.is_solve_rank:
+                recv = torch.empty(self.n_recv, dtype=torch.float64)
+                a = self.offsets
+                recv[a[p.rank]:a[p.rank + 1]] = seg
+                ops = [dist.P2POp(dist.irecv, recv[a[r]:a[r + 1]], glob(r), group) for r in range(p.active_world) if r != p.rank]
+                for w in dist.batch_isend_irecv(ops):
+                    w.wait()
+                x = torch.from_numpy(np.ascontiguousarray(solve(*self.merge_host(recv.numpy())), dtype=np.float64))
+            else:
+                for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, seg, glob(self.solve_rank), group)]):
+                    w.wait()
+            dist.broadcast(x, glob(self.solve_rank), group=group)
+        return x.numpy()[_dofs(p.nodes)]

@@ -221,6 +221,16 @@ int fep_scatter_f64(int device_id, void* stream, int64_t n, const double* src_d,
 int fep_iface_sum_f64(int device_id, void* stream, int64_t n, const int32_t* loc_d, const int32_t* ptr_d,
                       const int32_t* src_d, const double* recv_d, double* f_d);
 
+/* Gathered solve (sharding.GatherPlan, dist_newton.GatheredSolver): the sub-assembled K_r of all ranks, lying in the receive
+ * buffer `recv` of the solve rank, summed onto the global CSR pattern, K = sum_r P_r^T K_r P_r.  Tables count in PAIRS of
+ * doubles (one row of a 2x2 node-pair block; recv and k_global 16-byte aligned): for q < 2 n_blocks, pair q of k_global is
+ * pair first[q] of recv where first[q] >= 0, else 0.0 + the pairs multi_src[multi_ptr[k] .. multi_ptr[k+1]) of recv in the
+ * listed (ascending rank) order, k = -1 - first[q].  One pass, every value written exactly once: no zero fill, no atomics,
+ * the same bits for any launch geometry.  Entries of the tables are not checked against the length of recv.  n_blocks
+ * beyond the 32-bit pattern: FEP_ERANGE.  Replaces nothing in the reference. */
+int fep_csr_merge_f64(int device_id, void* stream, int64_t n_blocks, const int32_t* first_d, const int32_t* multi_ptr_d,
+                      const int32_t* multi_src_d, const double* recv_d, double* k_global_d);
+
 /* ---- callers of the hot path ----------------------------------------------------------------
  * transform (DP:760-816): integration-point values (n_int) -> nodal values (n_n), mean over the points of the
  * adjacent elements weighted with quadrature weight * |det J| (the footing pressure that steers the load step,
