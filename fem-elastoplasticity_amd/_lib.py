@@ -71,6 +71,11 @@ PROTOTYPES = {
     'fep_mesh_enrich_host': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     'fep_mesh_refine_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_mesh_refine_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_set_curves': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'fep_mesh_surf_curve_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'fep_mesh_surf_curve_host': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'fep_mesh_area_stats_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_area_stats_host': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_solver_create': (C.c_int, [c_void_pp, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_solver_destroy': (C.c_int, [C.c_void_p]),
     'fep_solver_sizes': (C.c_int, [C.c_void_p, c_i64_p]),

@@ -11,7 +11,11 @@
 // V1V2: TSX:1530, 1561, 1591), P4 in the order 0, 1, 2 (TSX:1386, 1424, 1463).
 #include "fep_common.h"
 
+#include <cmath>
+#include <map>
+#include <mutex>
 #include <new>
+#include <utility>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -201,6 +205,43 @@ struct MeshView {
     const int32_t* bbase;    // ... of the boundary counts
 };
 
+// ---- curved boundaries (fep.h, fep_mesh_set_curves) -----------------------------------------------------------------------
+// Axis-aligned ellipses (cx, cy, a, b, tol), passed to the kernels by value.  g(p) = sqrt(u u + v v), u = (x - cx) / a,
+// v = (y - cy) / b; p is ON the curve iff |g - 1| <= tol.  The host functions (midpoints.py) do the same operations in the
+// same order; contraction is off for this file, division and square root of doubles are correctly rounded.
+struct CurveSet {
+    int n;
+    double v[FEP_MAX_CURVES][5];
+};
+
+__device__ __forceinline__ double curve_g(const double* __restrict__ c, double x, double y, double* dx, double* dy) {
+    *dx = x - c[0];
+    *dy = y - c[1];
+    const double u = *dx / c[2], v = *dy / c[3];
+    return sqrt(u * u + v * v);
+}
+
+__device__ __forceinline__ bool on_curve(const double* __restrict__ c, double x, double y) {
+    double dx, dy;
+    return fabs(curve_g(c, x, y, &dx, &dy) - 1) <= c[4];
+}
+
+// the curve a boundary edge with the ends a, b follows: the lowest one that holds both, -1 if none does
+__device__ __forceinline__ int edge_curve(const CurveSet& S, double ax, double ay, double bx, double by) {
+    for (int q = 0; q < S.n; ++q)
+        if (on_curve(S.v[q], ax, ay) && on_curve(S.v[q], bx, by)) return q;
+    return -1;
+}
+
+// the straight point moved along its ray from the centre onto the curve; a point AT the centre (g == 0) stays
+__device__ __forceinline__ void project(const double* __restrict__ c, double* x, double* y) {
+    double dx, dy;
+    const double g = curve_g(c, *x, *y, &dx, &dy);
+    if (g == 0) return;
+    *x = c[0] + dx / g;
+    *y = c[1] + dy / g;
+}
+
 // P2 index of edge k of element i, whoever owns it
 __device__ __forceinline__ int32_t p2_edge(const MeshView& M, int64_t i, int k, int m, bool* owned, int64_t* j_out) {
     *owned = (m >> k) & 1;
@@ -216,7 +257,7 @@ __device__ __forceinline__ int32_t p2_edge(const MeshView& M, int64_t i, int k, 
 }
 
 // grid.y = slot s (edge k = (s + 1) % 3), one lane per element: coalesced rows of elem_ext / elem_ed
-__global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
+__global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, CurveSet S, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
                                                            int32_t* __restrict__ surf, int32_t* __restrict__ elem_ed,
                                                            int32_t* __restrict__ edge_el) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -232,8 +273,14 @@ __global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, int32_t* 
     elem_ext[(int64_t)(3 + s) * M.n_e + i] = (int32_t)(M.n_n + ind);
     if (elem_ed) elem_ed[(int64_t)s * M.n_e + i] = ind;
     if (!owned) return;
-    coord_ext[M.n_n + ind] = (M.coord[A] + M.coord[B]) / 2;
-    coord_ext[n_tot + M.n_n + ind] = (M.coord[M.n_n + A] + M.coord[M.n_n + B]) / 2;
+    const double ax = M.coord[A], ay = M.coord[M.n_n + A], bx = M.coord[B], by = M.coord[M.n_n + B];
+    double mx = (ax + bx) / 2, my = (ay + by) / 2;
+    if (j < 0 && S.n > 0) {
+        const int q = edge_curve(S, ax, ay, bx, by);
+        if (q >= 0) project(S.v[q], &mx, &my);
+    }
+    coord_ext[M.n_n + ind] = mx;
+    coord_ext[n_tot + M.n_n + ind] = my;
     if (edge_el) {
         edge_el[ind] = (int32_t)i;
         edge_el[M.n_edges + ind] = j < 0 ? 0 : (int32_t)j;       // the reference leaves its zero on a boundary edge
@@ -247,7 +294,7 @@ __global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, int32_t* 
 }
 
 // grid.y = edge k = slot; lane k of an element also writes its interior node k (nearest vertex k, TSX:1374-1381)
-__global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
+__global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, CurveSet S, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
                                                            int32_t* __restrict__ surf) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= M.n_e) return;
@@ -283,12 +330,17 @@ __global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, int32_t* 
     coord_ext[n_n + inner] = ix;
     coord_ext[n_tot + n_n + inner] = iy;
     if (!owned) return;
-    coord_ext[n_n + mid] = (ax + bx) / 2;
-    coord_ext[n_tot + n_n + mid] = (ay + by) / 2;
-    coord_ext[n_n + mid + 1] = 3 * ax / 4 + bx / 4;
-    coord_ext[n_tot + n_n + mid + 1] = 3 * ay / 4 + by / 4;
-    coord_ext[n_n + mid + 2] = ax / 4 + 3 * bx / 4;
-    coord_ext[n_tot + n_n + mid + 2] = ay / 4 + 3 * by / 4;
+    double px[3] = {(ax + bx) / 2, 3 * ax / 4 + bx / 4, ax / 4 + 3 * bx / 4};
+    double py[3] = {(ay + by) / 2, 3 * ay / 4 + by / 4, ay / 4 + 3 * by / 4};
+    if (nb < 0 && S.n > 0) {
+        const int q = edge_curve(S, ax, ay, bx, by);
+        if (q >= 0)
+            for (int r = 0; r < 3; ++r) project(S.v[q], &px[r], &py[r]);
+    }
+    for (int r = 0; r < 3; ++r) {
+        coord_ext[n_n + mid + r] = px[r];
+        coord_ext[n_tot + n_n + mid + r] = py[r];
+    }
     if (nb < 0) {
         const int64_t at = M.bbase[i] + __popc((m >> 3) & ((1 << k) - 1));
         const int64_t n_b = M.n_bnd;
@@ -301,7 +353,7 @@ __global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, int32_t* 
 }
 
 // one lane per element: its three P2 midside ids, the coordinates of those it owns, its four children
-__global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, int32_t* __restrict__ child, double* __restrict__ coord_ext) {
+__global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, CurveSet S, int32_t* __restrict__ child, double* __restrict__ coord_ext) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= M.n_e) return;
     const int m = M.mask[i];
@@ -315,8 +367,14 @@ __global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, int32_t* __r
         mid[k] = (int32_t)(M.n_n + ind);
         if (owned) {
             const int32_t A = v[k], B = v[(k + 1) % 3];
-            coord_ext[M.n_n + ind] = (M.coord[A] + M.coord[B]) / 2;
-            coord_ext[n_tot + M.n_n + ind] = (M.coord[M.n_n + A] + M.coord[M.n_n + B]) / 2;
+            const double ax = M.coord[A], ay = M.coord[M.n_n + A], bx = M.coord[B], by = M.coord[M.n_n + B];
+            double mx = (ax + bx) / 2, my = (ay + by) / 2;
+            if (j < 0 && S.n > 0) {
+                const int q = edge_curve(S, ax, ay, bx, by);
+                if (q >= 0) project(S.v[q], &mx, &my);
+            }
+            coord_ext[M.n_n + ind] = mx;
+            coord_ext[n_tot + M.n_n + ind] = my;
         }
     }
     const int32_t m12 = mid[0], m23 = mid[1], m31 = mid[2];
@@ -327,6 +385,87 @@ __global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, int32_t* __r
     r0[0] = v[0]; r0[1] = m12;  r0[2] = m31;  r0[3] = m12;          // children (V1, m12, m31), (m12, V2, m23),
     r1[0] = m12;  r1[1] = v[1]; r1[2] = m23;  r1[3] = m23;          //          (m31, m23, V3), (m12, m23, m31)
     r2[0] = m31;  r2[1] = m23;  r2[2] = v[2]; r2[3] = m31;
+}
+
+// curve index (-1: none) of every boundary edge, in the surf order of the element type (P2: visit order 1, 2, 0; P4: 0, 1, 2)
+__global__ void __launch_bounds__(kBlock) surf_curve_kernel(MeshView M, CurveSet S, int p2, int32_t* __restrict__ curve_of_surf) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int m = M.mask[i];
+    if (!(m >> 3)) return;
+    for (int k = 0; k < 3; ++k) {
+        if (!((m >> (3 + k)) & 1)) continue;
+        const int32_t A = M.elem[(int64_t)k * M.n_e + i], B = M.elem[(int64_t)((k + 1) % 3) * M.n_e + i];
+        const int64_t at = M.bbase[i] + (p2 ? bnd_rank_p2(m, k) : __popc((m >> 3) & ((1 << k) - 1)));
+        curve_of_surf[at] = edge_curve(S, M.coord[A], M.coord[M.n_n + A], M.coord[B], M.coord[M.n_n + B]);
+    }
+}
+
+// ---- area statistics: min doubled area, sum of areas, count of doubled areas <= 0 ------------------------------------------
+// Doubled signed area d = (x2 - x1)(y3 - y1) - (x3 - x1)(y2 - y1).  A fixed grid (a function of n_e alone), a grid-stride
+// loop per lane, a tree over the workgroup in LDS, one partial per workgroup, a second tree over the partials in one
+// workgroup: the order of every sum is fixed, no atomics.  A triangle naming a node outside [0, n_n) reads nothing and
+// counts as d = 0.
+constexpr int kAreaMaxBlocks = 1024;
+
+__device__ __forceinline__ void area_tree(double* __restrict__ l_min, double* __restrict__ l_sum, double* __restrict__ l_cnt) {
+    for (int d = kBlock / 2; d > 0; d /= 2) {
+        __syncthreads();
+        if (threadIdx.x < (unsigned)d) {
+            const double o = l_min[threadIdx.x + d];
+            l_min[threadIdx.x] = o < l_min[threadIdx.x] ? o : l_min[threadIdx.x];
+            l_sum[threadIdx.x] += l_sum[threadIdx.x + d];
+            l_cnt[threadIdx.x] += l_cnt[threadIdx.x + d];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(kBlock) area_partial_kernel(int64_t n_e, int64_t n_n, const int32_t* __restrict__ elem,
+                                                              const double* __restrict__ coord, double* __restrict__ part) {
+    __shared__ double l_min[kBlock], l_sum[kBlock], l_cnt[kBlock];
+    double mn = INFINITY, sum = 0, cnt = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * kBlock) {
+        const int32_t a = elem[i], b = elem[n_e + i], c = elem[2 * n_e + i];
+        double d = 0;
+        if (a >= 0 && a < n_n && b >= 0 && b < n_n && c >= 0 && c < n_n) {
+            const double x1 = coord[a], y1 = coord[n_n + a];
+            d = (coord[b] - x1) * (coord[n_n + c] - y1) - (coord[c] - x1) * (coord[n_n + b] - y1);
+        }
+        mn = d < mn ? d : mn;
+        sum += d / 2;
+        cnt += d <= 0 ? 1 : 0;
+    }
+    l_min[threadIdx.x] = mn;
+    l_sum[threadIdx.x] = sum;
+    l_cnt[threadIdx.x] = cnt;
+    area_tree(l_min, l_sum, l_cnt);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = l_min[0];
+        part[gridDim.x + blockIdx.x] = l_sum[0];
+        part[2 * gridDim.x + blockIdx.x] = l_cnt[0];
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) area_final_kernel(int n_part, const double* __restrict__ part, int64_t n_e,
+                                                            double* __restrict__ out) {
+    __shared__ double l_min[kBlock], l_sum[kBlock], l_cnt[kBlock];
+    double mn = INFINITY, sum = 0, cnt = 0;
+    for (int b = threadIdx.x; b < n_part; b += kBlock) {
+        mn = part[b] < mn ? part[b] : mn;
+        sum += part[n_part + b];
+        cnt += part[2 * n_part + b];
+    }
+    l_min[threadIdx.x] = mn;
+    l_sum[threadIdx.x] = sum;
+    l_cnt[threadIdx.x] = cnt;
+    area_tree(l_min, l_sum, l_cnt);
+    if (threadIdx.x == 0) {
+        out[0] = l_min[0];
+        out[1] = l_sum[0];
+        out[2] = l_cnt[0];
+        out[3] = (double)n_e;
+    }
 }
 
 struct DeviceBlocks {
@@ -353,6 +492,7 @@ struct fep_mesh {
     uint8_t* mask = nullptr;
     int32_t* base = nullptr;
     int32_t* bbase = nullptr;
+    CurveSet curves{};
     DeviceBlocks blocks;
 
     bool refused() const { return n_nonmanifold > 0 || n_inconsistent > 0 || n_degenerate > 0; }
@@ -439,9 +579,9 @@ static int mesh_enrich_impl(const fep_mesh* M, hipStream_t st, int elem_type, in
         HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
     const dim3 grid(grid_for(M->n_e, kBlock), 3), block(kBlock);
     if (elem_type == FEP_P2)
-        hipLaunchKernelGGL(enrich_p2_kernel, grid, block, 0, st, M->view(), elem_ext, coord_ext, surf, elem_ed, edge_el);
+        hipLaunchKernelGGL(enrich_p2_kernel, grid, block, 0, st, M->view(), M->curves, elem_ext, coord_ext, surf, elem_ed, edge_el);
     else
-        hipLaunchKernelGGL(enrich_p4_kernel, grid, block, 0, st, M->view(), elem_ext, coord_ext, surf);
+        hipLaunchKernelGGL(enrich_p4_kernel, grid, block, 0, st, M->view(), M->curves, elem_ext, coord_ext, surf);
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
@@ -454,7 +594,65 @@ static int mesh_refine_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_chi
     FEP_TRY(fep_set_device(M->device));
     for (int r = 0; r < 2 && M->n_n > 0; ++r)
         HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(refine_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), elem_child, coord_ext);
+    hipLaunchKernelGGL(refine_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->curves, elem_child, coord_ext);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+static int mesh_set_curves_impl(fep_mesh* M, int n_curves, const double* curves_h) {
+    if (!M || n_curves < 0 || n_curves > FEP_MAX_CURVES || (n_curves > 0 && !curves_h)) return FEP_EINVAL;
+    CurveSet S{};
+    for (int q = 0; q < n_curves; ++q) {
+        const double* c = curves_h + 5 * q;
+        for (int r = 0; r < 5; ++r)
+            if (!std::isfinite(c[r])) return FEP_EINVAL;
+        if (!(c[2] > 0) || !(c[3] > 0) || !(c[4] >= 0)) return FEP_EINVAL;
+        for (int r = 0; r < 5; ++r) S.v[q][r] = c[r];
+    }
+    S.n = n_curves;
+    M->curves = S;
+    return FEP_OK;
+}
+
+static int mesh_surf_curve_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* curve_of_surf) {
+    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || (!curve_of_surf && M->n_bnd > 0)) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    if (M->n_bnd == 0) return FEP_OK;
+    hipLaunchKernelGGL(surf_curve_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->curves,
+                       elem_type == FEP_P2 ? 1 : 0, curve_of_surf);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+// partials of fep_mesh_area_stats_dev: one fixed-size block per (device, stream), made by the first call on it (an
+// allocation: refused, FEP_ESTATE, while that stream is being captured) and kept
+static int area_scratch(int device, hipStream_t st, double** out) {
+    static std::mutex m;
+    static auto& bufs = *new std::map<std::pair<int, void*>, double*>();
+    std::lock_guard<std::mutex> g(m);
+    double*& b = bufs[{device, (void*)st}];
+    if (!b) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
+        HIP_TRY(hipMalloc((void**)&b, 3 * kAreaMaxBlocks * sizeof(double)));
+    }
+    *out = b;
+    return FEP_OK;
+}
+
+static int area_stats_impl(int device_id, hipStream_t st, int64_t n_e, int64_t n_n, const int32_t* elem, const double* coord,
+                           double* out) {
+    if (n_e < 0 || n_n < 0 || !out || (n_e > 0 && (!elem || (!coord && n_n > 0)))) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(device_id));
+    double* part = nullptr;
+    FEP_TRY(area_scratch(device_id, st, &part));
+    int64_t n_part = (n_e + kBlock - 1) / kBlock;
+    n_part = n_part < 1 ? 1 : (n_part > kAreaMaxBlocks ? kAreaMaxBlocks : n_part);
+    hipLaunchKernelGGL(area_partial_kernel, dim3((unsigned)n_part), dim3(kBlock), 0, st, n_e, n_n, elem, coord, part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(area_final_kernel, dim3(1), dim3(kBlock), 0, st, (int)n_part, part, n_e, out);
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
@@ -508,6 +706,37 @@ static int mesh_refine_host_impl(const fep_mesh* M, int32_t* elem_child_h, doubl
     return FEP_OK;
 }
 
+static int mesh_surf_curve_host_impl(const fep_mesh* M, int elem_type, int32_t* curve_of_surf_h) {
+    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || (!curve_of_surf_h && M->n_bnd > 0)) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    DeviceBlocks tmp;
+    int32_t* out = nullptr;
+    FEP_TRY(tmp.get(&out, M->n_bnd));
+    FEP_TRY(mesh_surf_curve_impl(M, nullptr, elem_type, out));
+    FEP_TRY(fetch(curve_of_surf_h, out, M->n_bnd));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
+static int area_stats_host_impl(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
+                                double* out_h) {
+    if (n_e < 0 || n_n < 0 || !out_h || (n_e > 0 && (!elem_h || (!coord_h && n_n > 0)))) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(device_id));
+    DeviceBlocks tmp;
+    int32_t* elem = nullptr;
+    double *coord = nullptr, *out = nullptr;
+    FEP_TRY(tmp.get(&elem, 3 * n_e));
+    FEP_TRY(tmp.get(&coord, 2 * n_n));
+    FEP_TRY(tmp.get(&out, 4));
+    if (n_e > 0) HIP_TRY(hipMemcpyAsync(elem, elem_h, (size_t)(3 * n_e) * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
+    if (n_n > 0 && coord_h) HIP_TRY(hipMemcpyAsync(coord, coord_h, (size_t)(2 * n_n) * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    FEP_TRY(area_stats_impl(device_id, nullptr, n_e, n_n, elem, coord, out));
+    FEP_TRY(fetch(out_h, out, 4));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
 #define FEP_GUARD(call) \
     try { return call; } catch (const std::bad_alloc&) { return FEP_ENOMEM; } catch (...) { return FEP_EINVAL; }
 
@@ -551,4 +780,26 @@ extern "C" int fep_mesh_refine_dev(const fep_mesh* mesh, void* stream, int32_t* 
 
 extern "C" int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h) {
     FEP_GUARD(mesh_refine_host_impl(mesh, elem_child_h, coord_ext_h))
+}
+
+extern "C" int fep_mesh_set_curves(fep_mesh* mesh, int n_curves, const double* curves_h) {
+    FEP_GUARD(mesh_set_curves_impl(mesh, n_curves, curves_h))
+}
+
+extern "C" int fep_mesh_surf_curve_dev(const fep_mesh* mesh, void* stream, int elem_type, int32_t* curve_of_surf_d) {
+    FEP_GUARD(mesh_surf_curve_impl(mesh, (hipStream_t)stream, elem_type, curve_of_surf_d))
+}
+
+extern "C" int fep_mesh_surf_curve_host(const fep_mesh* mesh, int elem_type, int32_t* curve_of_surf_h) {
+    FEP_GUARD(mesh_surf_curve_host_impl(mesh, elem_type, curve_of_surf_h))
+}
+
+extern "C" int fep_mesh_area_stats_dev(int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem_d,
+                                       const double* coord_d, double* out_d) {
+    FEP_GUARD(area_stats_impl(device_id, (hipStream_t)stream, n_e, n_n, elem_d, coord_d, out_d))
+}
+
+extern "C" int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
+                                        double* out_h) {
+    FEP_GUARD(area_stats_host_impl(device_id, n_e, n_n, elem_h, coord_h, out_h))
 }

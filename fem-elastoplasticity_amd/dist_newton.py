@@ -33,7 +33,7 @@ from contextlib import closing
 
 import numpy as np
 
-from .newton import _DeviceOps, _footing_setup, _strip_footing, _tsx_setup, _tsx_tunnel, point_sums
+from .newton import _DeviceOps, _footing_setup, _refuse_folded, _strip_footing, _tsx_setup, _tsx_tunnel, point_sums
 from .sharding import ShardedContext
 from .tables import element_tables
 
@@ -439,20 +439,21 @@ def solve_strip_footing_sharded(element_type='P1', level=1, n_cells=None, size_x
 
 def solve_tsx_tunnel_sharded(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                              linear_solver='amg', pcg_rtol=1e-11, mesh_dir=None, pcg_inexact_rtol=None, refine=0,
-                             renumber=False, group=None, solve_rank=0):
+                             renumber=False, group=None, solve_rank=0, curves=None):
     """newton.solve_tsx_tunnel on the ranks of the process group (a single process works too), arguments as there
     (`linear_solver` 'pcg' or 'amg' as in solve_strip_footing_sharded; no `context_factory`, no forcing).  Every rank
     prepares the same mesh (`refine` / `renumber` run on each rank's device; the device refinement is bit-equal to the host
     one, so all ranks see one mesh), takes a contiguous range of its elements and enters newton's loop with its
     ShardedContext: the initial-stress force is made consistent by the interface exchange, the plastic-point counts are
-    summed over the ranks.  Idle ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on
-    every rank."""
+    summed over the ranks.  `curves` as in solve_tsx_tunnel (each rank checks the determinants of its own elements).  Idle
+    ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on every rank."""
     rank, world = _ranks(group)
-    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, None, log)
+    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, None, log, curves)
     clock = [time.perf_counter()]
     sc = ShardedContext(p['elem'], p['coords'], rank, world, *element_tables(p['type']), device=device)
     sc.set_materials(*p['materials'])
     clock.append(time.perf_counter())
     with closing(sc), closing(_ShardOps(sc, p['Q'].flatten(order='F'), rtol=pcg_rtol, inexact_rtol=pcg_inexact_rtol, group=group,
                                         linear_solver=linear_solver, solve_rank=solve_rank, elements_global=p['elem'])) as ops:
+        _refuse_folded(p, sc.ctx)                                                         # each rank: its own elements
         return _tsx_tunnel(p, sc.ctx, ops, clock, n_load_steps, log)

@@ -22,11 +22,13 @@ from .midpoints import create_midpoints, refine_uniform
 from .tables import LagrangeElementType, _coerce
 
 
-def prepare_tsx_mesh(coords, elem, element_type='P1', refine=0, renumber=False, device=None):
+def prepare_tsx_mesh(coords, elem, element_type='P1', refine=0, renumber=False, device=None, curves=None):
     """P1 triangles (`coords` (2, n_n), `elem` (3, n_e) 0-based) -> the mesh a driver runs on: refined `refine` times
     (refine_uniform), then — `renumber` — numbered along a Morton curve (renumber_for_locality, on the host: refinement
     appends each level's nodes at the end, which scatters a node's neighbours over memory), then raised to
     `element_type` (create_midpoints).  `device` (a GPU index) runs refinement and enrichment on the GPU, None on the host.
+    `curves` (a sequence of Ellipse, e.g. tsx_tunnel.TSX_HOLE): the new nodes of boundary edges with both ends on a curve are
+    moved onto it, at every refinement level and in the enrichment (refine_uniform, create_midpoints).
     Returns (coordinates float64, elements int64, node_of_input, seconds): node_of_input[n] = the id of input node n in
     the result (vertices keep their ids under refinement and enrichment; None when not renumbered), seconds =
     {'refine', 'renumber', 'enrich'}."""
@@ -39,7 +41,7 @@ def prepare_tsx_mesh(coords, elem, element_type='P1', refine=0, renumber=False, 
     n_in = coords.shape[1]
     clock = [time.perf_counter()]
     if refine:
-        coords, elem = refine_uniform(coords, elem, levels=refine, device=device)
+        coords, elem = refine_uniform(coords, elem, levels=refine, device=device, curves=curves)
     clock.append(time.perf_counter())
     node_of_input = None
     if renumber:
@@ -49,17 +51,18 @@ def prepare_tsx_mesh(coords, elem, element_type='P1', refine=0, renumber=False, 
         node_of_input = inv[:n_in]
     clock.append(time.perf_counter())
     if t is not LagrangeElementType.P1:
-        ext = create_midpoints(t, coords, elem, device=device)
+        ext = create_midpoints(t, coords, elem, device=device, curves=curves)
         coords, elem = ext['coord_ext'], ext['elem_ext']
     clock.append(time.perf_counter())
     seconds = dict(zip(('refine', 'renumber', 'enrich'), (b - a for a, b in zip(clock[:-1], clock[1:]))))
     return np.asarray(coords, dtype=np.float64), np.asarray(elem, dtype=np.int64), node_of_input, seconds
 
 
-def load_tsx_mesh(directory='.', element_type='P1', coord_file='coord.csv', elem_file='elem.csv', refine=0, device=None):
+def load_tsx_mesh(directory='.', element_type='P1', coord_file='coord.csv', elem_file='elem.csv', refine=0, device=None,
+                  curves=None):
     """(coordinates, elements) of the CSV mesh in `directory`, elements 0-based (TSX:1687-1688), midpoints per TSX:1690.
     `refine` > 0: the P1 mesh is refined uniformly that many times before the midpoints are added; `device` (a GPU
-    index) runs refinement and midpoints on the GPU (None: on the host)."""
+    index) runs refinement and midpoints on the GPU (None: on the host); `curves` as in prepare_tsx_mesh."""
     coords = np.genfromtxt(os.path.join(directory, coord_file), delimiter=',', ndmin=2)
     elem = np.genfromtxt(os.path.join(directory, elem_file), delimiter=',', dtype=int, ndmin=2) - 1
     if coords.shape[0] != 2 or elem.shape[0] != 3:
@@ -68,9 +71,9 @@ def load_tsx_mesh(directory='.', element_type='P1', coord_file='coord.csv', elem
         raise IndexError('element file refers to nodes the coordinate file does not hold (ids are 1-based on disk)')
     t = _coerce(element_type)
     if refine or device is not None:
-        return prepare_tsx_mesh(coords, elem, t, refine=refine, device=device)[:2]
+        return prepare_tsx_mesh(coords, elem, t, refine=refine, device=device, curves=curves)[:2]
     if t in (LagrangeElementType.P2, LagrangeElementType.P4):
-        ext = create_midpoints(t, coords, elem)
+        ext = create_midpoints(t, coords, elem, curves=curves)
         return np.asarray(ext['coord_ext'], dtype=np.float64), np.asarray(ext['elem_ext'], dtype=np.int64)
     if t is not LagrangeElementType.P1:
         raise ValueError('the CSV mesh holds triangles: element_type must be P1, P2 or P4')

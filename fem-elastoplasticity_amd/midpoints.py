@@ -11,11 +11,88 @@ Local orders: P2 rows 3..5 = midpoints of (V2V3, V3V1, V1V2); P4
 (V1V2, V2V3, V3V1), rows 6..11 = quarter points (two per edge, nearer the edge's first vertex first),
 rows 12..14 = interior nodes nearest V1, V2, V3.
 """
+import collections
 import ctypes as C
+import math
 
 import numpy as np
 
 from .tables import LagrangeElementType, _coerce
+
+
+class Ellipse(collections.namedtuple('Ellipse', 'cx cy a b tol', defaults=(1e-3,))):
+    """An axis-aligned ellipse a mesh boundary follows: centre (cx, cy), semi-axes a (along x) and b (along y); a circle
+    has a == b.  A vertex p is ON it iff |g(p) - 1| <= tol, g = sqrt(((x - cx) / a)**2 + ((y - cy) / b)**2).  Passed as
+    `curves=[...]` (at most 4) to the enrichment and refinement functions: every node they create on a boundary edge with
+    both ends on the same curve (the lowest index wins) is moved from its straight position along its ray from the centre
+    onto the curve; interior edges, existing vertices and P4 interior nodes are never moved (include/fep.h,
+    fep_mesh_set_curves)."""
+    __slots__ = ()
+
+
+MAX_CURVES = 4
+
+
+def _curve_rows(curves):
+    """`curves` (None, or a sequence of Ellipse / 5-tuples) -> None or a validated (n, 5) float64 array."""
+    if curves is None or len(curves) == 0:
+        return None
+    rows = np.ascontiguousarray([tuple(Ellipse(*c)) for c in curves], dtype=np.float64)
+    if rows.shape[0] > MAX_CURVES:
+        raise ValueError(f'at most {MAX_CURVES} curves, got {rows.shape[0]}')
+    if not np.isfinite(rows).all() or (rows[:, 2] <= 0).any() or (rows[:, 3] <= 0).any() or (rows[:, 4] < 0).any():
+        raise ValueError('a curve is (cx, cy, a, b, tol) with finite values, a > 0, b > 0 and tol >= 0')
+    return rows
+
+
+def _g(c, x, y):
+    """(g, dx, dy) of the point (x, y) for the curve row c — the operations of the kernels, in their order."""
+    dx, dy = x - c[0], y - c[1]
+    u, v = dx / c[2], dy / c[3]
+    return math.sqrt(u * u + v * v), dx, dy
+
+
+def _edge_curve(rows, pa, pb):
+    """Index of the lowest curve that holds both ends of a boundary edge, -1 if none does."""
+    for q, c in enumerate(rows):
+        if abs(_g(c, pa[0], pa[1])[0] - 1) <= c[4] and abs(_g(c, pb[0], pb[1])[0] - 1) <= c[4]:
+            return q
+    return -1
+
+
+def _project(c, p):
+    """The straight point p moved onto the curve row c along its ray from the centre (p itself at the centre)."""
+    g, dx, dy = _g(c, p[0], p[1])
+    if g == 0:
+        return p
+    return np.array([c[0] + dx / g, c[1] + dy / g])
+
+
+def _curve_rows_py(rows):
+    return [tuple(float(v) for v in r) for r in rows]
+
+
+def doubled_areas(coord, elem):
+    """Doubled signed areas (x2 - x1)(y3 - y1) - (x3 - x1)(y2 - y1) of the vertex triangles of `elem`'s first three rows."""
+    x, y = np.asarray(coord, dtype=np.float64)
+    a, b, c = np.asarray(elem)[0:3]
+    return (x[b] - x[a]) * (y[c] - y[a]) - (x[c] - x[a]) * (y[b] - y[a])
+
+
+def area_stats(coord, elem, device=None):
+    """[min doubled area, sum of areas, number of triangles with doubled area <= 0, n_e] of a triangle mesh's vertex rows:
+    NumPy, or — `device`, a GPU index — fep_mesh_area_stats_host."""
+    elem = np.asarray(elem)
+    if device is None:
+        d = doubled_areas(coord, elem)
+        return np.array([d.min() if d.size else np.inf, (d / 2).sum(), np.count_nonzero(d <= 0), d.size], dtype=np.float64)
+    from . import _lib
+    coord = np.ascontiguousarray(coord, dtype=np.float64)
+    e32 = np.ascontiguousarray(elem[0:3], dtype=np.int32)
+    out = np.empty(4)
+    _lib.check(_lib.lib().fep_mesh_area_stats_host(int(device), e32.shape[1], coord.shape[1], _lib.ptr(e32), _lib.ptr(coord),
+                                                   _lib.ptr(out)), 'fep_mesh_area_stats_host')
+    return out
 
 
 def _edge_map(elem):
@@ -37,16 +114,23 @@ def _neighbour(m, a, b, i):
     return None
 
 
-def create_midpoints_P2(coord, elem, device=None):
+def create_midpoints_P2(coord, elem, device=None, curves=None):
     """TSX:1508-1626.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext', 'elem_ed', 'edge_el'.
-    `device` (a GPU index): the same dict from the library's kernels (fep_mesh_*), see DeviceMesh."""
+    `device` (a GPU index): the same dict from the library's kernels (fep_mesh_*), see DeviceMesh.
+    `curves` (a sequence of Ellipse): the midpoints of boundary edges with both ends on a curve are moved onto it, and the
+    dict gains 'surf_curve' (n_boundary_edges,): the curve index of each column of 'surf', -1 for a straight edge."""
+    rows = _curve_rows(curves)
     if device is not None:
         with DeviceMesh(coord, elem, device) as m:
+            if rows is not None:
+                m.set_curves(curves)
             return m.enrich(LagrangeElementType.P2)
     coord = np.asarray(coord, dtype=float)
     elem = np.asarray(elem)
     n_e, n_n = elem.shape[1], coord.shape[1]
     m = _edge_map(elem)
+    cv = _curve_rows_py(rows) if rows is not None else None
+    surf_curve = []
     coord_mid = np.zeros((2, 3 * n_e))
     elem_mid = np.zeros((3, n_e))
     elem_ed = np.zeros((3, n_e))
@@ -76,22 +160,36 @@ def create_midpoints_P2(coord, elem, device=None):
             else:
                 surf[:, ind_s] = (B, A, n_n + ind)
                 ind_s += 1
+                if cv is not None:
+                    q = _edge_curve(cv, coord[:, A], coord[:, B]) if len(m[(A, B) if A < B else (B, A)]) == 1 else -1
+                    surf_curve.append(q)
+                    if q >= 0:
+                        coord_mid[:, ind] = _project(cv[q], coord_mid[:, ind])
             ind += 1
     coord_mid = coord_mid[:, 0:ind]
-    return {'coord_mid': coord_mid, 'surf': surf[:, 0:ind_s], 'coord_ext': np.concatenate([coord, coord_mid], axis=1),
-            'elem_ext': np.array(np.concatenate([elem, elem_mid], axis=0), dtype=int),
-            'elem_ed': elem_ed, 'edge_el': edge_el[:, 0:ind]}
+    out = {'coord_mid': coord_mid, 'surf': surf[:, 0:ind_s], 'coord_ext': np.concatenate([coord, coord_mid], axis=1),
+           'elem_ext': np.array(np.concatenate([elem, elem_mid], axis=0), dtype=int),
+           'elem_ed': elem_ed, 'edge_el': edge_el[:, 0:ind]}
+    if cv is not None:
+        out['surf_curve'] = np.array(surf_curve, dtype=np.int64)
+    return out
 
 
-def create_midpoints_P4(coord, elem, device=None):
-    """TSX:1354-1505.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext'.  `device` as in create_midpoints_P2."""
+def create_midpoints_P4(coord, elem, device=None, curves=None):
+    """TSX:1354-1505.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext'.  `device` and `curves` as in
+    create_midpoints_P2: the midpoint and the two quarter points of a curved edge are moved, the interior nodes are not."""
+    rows = _curve_rows(curves)
     if device is not None:
         with DeviceMesh(coord, elem, device) as m:
+            if rows is not None:
+                m.set_curves(curves)
             return m.enrich(LagrangeElementType.P4)
     coord = np.asarray(coord, dtype=float)
     elem = np.asarray(elem)
     n_e, n_n = elem.shape[1], coord.shape[1]
     m = _edge_map(elem)
+    cv = _curve_rows_py(rows) if rows is not None else None
+    surf_curve = []
     coord_mid = np.zeros((2, 12 * n_e))
     elem_mid = np.zeros((12, n_e))
     surf = np.zeros((5, 3 * n_e))
@@ -125,19 +223,28 @@ def create_midpoints_P4(coord, elem, device=None):
             else:
                 ind_s += 1
                 surf[:, ind_s] = (B, A, n_n + ind + 1, n_n + ind + 2, n_n + ind + 3)
+                if cv is not None:
+                    q = _edge_curve(cv, cA, cB) if len(m[(A, B) if A < B else (B, A)]) == 1 else -1
+                    surf_curve.append(q)
+                    if q >= 0:
+                        for r in (1, 2, 3):
+                            coord_mid[:, ind + r] = _project(cv[q], coord_mid[:, ind + r])
             ind += 3
     coord_mid = coord_mid[:, 0:ind + 1]
-    return {'coord_mid': coord_mid, 'surf': surf[:, 0:ind_s + 1], 'coord_ext': np.concatenate([coord, coord_mid], axis=1),
-            'elem_ext': np.array(np.concatenate([elem, elem_mid], axis=0), dtype=int)}
+    out = {'coord_mid': coord_mid, 'surf': surf[:, 0:ind_s + 1], 'coord_ext': np.concatenate([coord, coord_mid], axis=1),
+           'elem_ext': np.array(np.concatenate([elem, elem_mid], axis=0), dtype=int)}
+    if cv is not None:
+        out['surf_curve'] = np.array(surf_curve, dtype=np.int64)
+    return out
 
 
-def create_midpoints(elem_type, coord, elem, device=None):
+def create_midpoints(elem_type, coord, elem, device=None, curves=None):
     """TSX:1629-1633 (returns None for element types without midpoints, like the reference)."""
     t = _coerce(elem_type)
     if t is LagrangeElementType.P2:
-        return create_midpoints_P2(coord, elem, device=device)
+        return create_midpoints_P2(coord, elem, device=device, curves=curves)
     if t is LagrangeElementType.P4:
-        return create_midpoints_P4(coord, elem, device=device)
+        return create_midpoints_P4(coord, elem, device=device, curves=curves)
     return None
 
 
@@ -157,7 +264,7 @@ class DeviceMesh:
 
     def __init__(self, coord, elem, device, on_device=False):
         from . import _lib
-        self._lib, self._h, self.device = _lib, None, int(device)
+        self._lib, self._h, self.device, self.n_curves = _lib, None, int(device), 0
         if on_device:
             if elem.dtype.itemsize != 4 or coord.dtype.itemsize != 8 or not (elem.is_contiguous() and coord.is_contiguous()):
                 raise ValueError('device meshes are contiguous int32 / float64 tensors')
@@ -206,6 +313,31 @@ class DeviceMesh:
                              f"n_nonmanifold={i['n_nonmanifold']}, n_inconsistent={i['n_inconsistent']}, "
                              f"n_degenerate={i['n_degenerate']}; use the host functions (device=None) for this mesh")
 
+    def set_curves(self, curves):
+        """The curved boundaries of the next enrich / refine calls (fep_mesh_set_curves): a sequence of Ellipse, at most 4;
+        None or an empty one clears them."""
+        rows = _curve_rows(curves)
+        n = 0 if rows is None else rows.shape[0]
+        self._lib.check(self._lib.lib().fep_mesh_set_curves(self._h, n, self._lib.ptr(rows) if n else None), 'fep_mesh_set_curves')
+        self.n_curves = n
+
+    def surf_curve(self, elem_type):
+        """Curve index (-1: straight) of every boundary edge, in the order of `elem_type`'s 'surf' columns; int64."""
+        self._accepted()
+        out = np.empty(self.info['n_boundary_edges'], dtype=np.int32)
+        self._lib.check(self._lib.lib().fep_mesh_surf_curve_host(self._h, _FEP_TYPE[_coerce(elem_type)], self._lib.ptr(out)),
+                        'fep_mesh_surf_curve_host')
+        return out.astype(np.int64)
+
+    def surf_curve_dev(self, elem_type):
+        """Device-resident form: an int32 tensor written on the current stream."""
+        import torch
+        self._accepted()
+        out = torch.empty(self.info['n_boundary_edges'], dtype=torch.int32, device=torch.device('cuda', self.device))
+        self._lib.check(self._lib.lib().fep_mesh_surf_curve_dev(self._h, self._stream(), _FEP_TYPE[_coerce(elem_type)],
+                                                                C.c_void_p(out.data_ptr())), 'fep_mesh_surf_curve_dev')
+        return out
+
     def new_nodes(self, elem_type):
         t = _coerce(elem_type)
         return self.info['n_edges'] if t is LagrangeElementType.P2 else 3 * self.info['n_e'] + 3 * self.info['n_edges']
@@ -228,6 +360,8 @@ class DeviceMesh:
                'elem_ext': elem_ext.astype(int)}
         if p2:
             out['elem_ed'], out['edge_el'] = elem_ed.astype(np.float64), edge_el.astype(np.float64)
+        if self.n_curves:
+            out['surf_curve'] = self.surf_curve(t)
         return out
 
     def enrich_dev(self, elem_type):
@@ -272,32 +406,72 @@ class DeviceMesh:
         return coord_ext, child
 
 
-def refine_uniform(coord, elem, levels=1, device=None):
+def area_stats_dev(coord_d, elem_d, device, out=None):
+    """fep_mesh_area_stats_dev on torch tensors of GPU `device` (coord (2, n_n) float64, elem (3, n_e) int32, contiguous),
+    on the current stream -> a float64 tensor of 4 (`out`, or a new one); nothing is synchronised."""
+    import torch
+    from . import _lib
+    if elem_d.dtype != torch.int32 or coord_d.dtype != torch.float64 or elem_d.shape[0] != 3 or coord_d.shape[0] != 2 \
+            or not (elem_d.is_contiguous() and coord_d.is_contiguous()):
+        raise ValueError('area statistics take contiguous (3, n_e) int32 / (2, n_n) float64 tensors')
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=torch.device('cuda', device))
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(_lib.lib().fep_mesh_area_stats_dev(int(device), stream, int(elem_d.shape[1]), int(coord_d.shape[1]),
+                                                  C.c_void_p(elem_d.data_ptr()), C.c_void_p(coord_d.data_ptr()),
+                                                  C.c_void_p(out.data_ptr())), 'fep_mesh_area_stats_dev')
+    return out
+
+
+def _folded(level, stats):
+    return ValueError(f'refinement level {level}: {int(stats[2])} of {int(stats[3])} triangles have a non-positive area '
+                      f'(smallest doubled area {stats[0]:.3e}) after projection onto the curves')
+
+
+def refine_uniform(coord, elem, levels=1, device=None, curves=None):
     """Uniform (red) refinement of a P1 triangle mesh, `levels` times -> (coordinates, elements (3, 4**levels n_e) int64).
     No counterpart in the reference.  One level = the P2 enrichment: the new vertices are the P2 midside nodes, with
     create_midpoints_P2's ids and coordinates (old nodes keep their ids and coordinates), and with its rows
     (V1, V2, V3, m23, m31, m12) the children 4i .. 4i + 3 of element i are (V1, m12, m31), (m12, V2, m23), (m31, m23, V3),
-    (m12, m23, m31).  Orientation is preserved.  Boundaries are refined as polygons: a curved boundary (the tunnel's hole) is
-    not re-projected onto its curve.  `device` (a GPU index): the levels are chained on the GPU without a host round
-    trip (DeviceMesh; edge-manifold, consistently oriented meshes only), bit-equal to the host form."""
+    (m12, m23, m31).  Orientation is preserved.  Without `curves` boundaries are refined as polygons.  `curves` (a sequence
+    of Ellipse, e.g. the tunnel's hole): at every level the new vertex of a boundary edge with both ends on a curve is moved
+    onto it, so the boundary converges to the curve; every level is then checked with the area statistics
+    (fep_mesh_area_stats_dev on the GPU, NumPy on the host) and a level with a child of non-positive area raises
+    ValueError naming the level and the count.  `device` (a GPU index): the levels are chained on the GPU without a host
+    round trip (DeviceMesh; edge-manifold, consistently oriented meshes only), bit-equal to the host form without curves."""
     if levels < 0:
         raise ValueError('levels must be >= 0')
+    rows = _curve_rows(curves)
     if device is not None and levels > 0:
+        import torch
+        stats = torch.empty((levels, 4), dtype=torch.float64, device=torch.device('cuda', device)) if rows is not None else None
         m = DeviceMesh(coord, elem, device)
         try:
             for lv in range(levels):
+                if rows is not None:
+                    m.set_curves(curves)
                 c_d, e_d = m.refine_dev()
+                if rows is not None:
+                    area_stats_dev(c_d, e_d, device, out=stats[lv])
                 m.close()
                 if lv + 1 < levels:
                     m = DeviceMesh(c_d, e_d, device, on_device=True)
         finally:
             m.close()
+        if rows is not None:
+            for lv, st in enumerate(stats.cpu().numpy()):
+                if st[2] > 0:
+                    raise _folded(lv + 1, st)
         return c_d.cpu().numpy(), e_d.cpu().numpy().astype(np.int64)
     coord, elem = np.asarray(coord, dtype=float), np.asarray(elem).astype(np.int64)
-    for _ in range(levels):
-        h = create_midpoints_P2(coord, elem)
+    for lv in range(levels):
+        h = create_midpoints_P2(coord, elem, curves=curves)
         V1, V2, V3, m23, m31, m12 = h['elem_ext']
         elem = np.stack([np.stack([V1, m12, m31]), np.stack([m12, V2, m23]), np.stack([m31, m23, V3]),
                          np.stack([m12, m23, m31])], axis=2).reshape(3, -1).astype(np.int64)
         coord = h['coord_ext']
+        if rows is not None:
+            st = area_stats(coord, elem)
+            if st[2] > 0:
+                raise _folded(lv + 1, st)
     return coord, elem

@@ -372,18 +372,21 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
-                     pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False):
+                     pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
     displacements.  `context_factory` as in solve_strip_footing (the object also needs `assemble` and `n_int`).
     `refine` > 0 or `renumber` (no counterpart in the reference): the P1 mesh — `mesh_dir`'s, or `coords` / `elem` with
-    3 vertex rows — is refined uniformly `refine` times (refine_uniform; the hole's boundary stays a polygon), then, with
-    `renumber`, numbered along a Morton curve (refinement appends every level's nodes at the end), then raised to
+    3 vertex rows — is refined uniformly `refine` times (refine_uniform; the hole's boundary stays a polygon unless `curves`
+    names it), then, with `renumber`, numbered along a Morton curve (refinement appends every level's nodes at the end), then raised to
     `element_type`; on the GPU when the context is the GPU one, on the host with a `context_factory`.  `monitor` keeps
     naming a node of the INPUT mesh; 'U' is in the numbering of the mesh solved on, returned as 'coords' / 'elem', and
-    'node_of_input' maps input node ids to it (None unless renumbered)."""
-    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log)
+    'node_of_input' maps input node ids to it (None unless renumbered).
+    `curves` (a sequence of Ellipse; tsx_tunnel.TSX_HOLE is the tunnel wall): refinement and enrichment put their new
+    boundary nodes on these curves (prepare_tsx_mesh; with `mesh_dir` alone the midpoints of load_tsx_mesh), and a mesh with
+    a non-positive Jacobian determinant at any integration point (a P2 / P4 element folded by its curved side) is refused."""
+    p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves)
     clock = [time.perf_counter()]
     ctx = _context_maker(context_factory, device)(p['elem'], p['coords'], *element_tables(p['type']))
     assert ctx.n_int == p['elem'].shape[1] * ELEMENT_SHAPE[p['type']][1]
@@ -391,13 +394,25 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     clock.append(time.perf_counter())
     with closing(ctx), closing(make_ops(ctx, p['Q'].flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
                                         pcg_inexact_rtol)) as ops:
+        _refuse_folded(p, ctx)
         return _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log)
 
 
-def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log):
+def _refuse_folded(p, ctx):
+    """With curves, a mesh is refused unless the determinant of every integration point of `ctx` is positive."""
+    if not p['curved']:
+        return
+    det = np.asarray(ctx.geometry()[3])
+    if not (det > 0).all():
+        raise ValueError(f'curved mesh: {int(np.count_nonzero(~(det > 0)))} of {det.size} integration points have a '
+                         f'non-positive Jacobian determinant (smallest {det.min():.3e})')
+
+
+def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves=None):
     """Mesh, materials, initial stress and constraints of the TSX problem (TSX:1637-1699), before any context exists."""
     t = _coerce(element_type)
     node_of_input, t_mesh = None, {}
+    curved = curves is not None and len(curves) > 0
     if refine or renumber:
         from .hotpath import default_device
         from .meshio import load_tsx_mesh, prepare_tsx_mesh
@@ -407,7 +422,7 @@ def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, 
             raise ValueError('pass the mesh (coords, elem) or mesh_dir')
         mesh_device = None if context_factory is not None else (default_device() if device is None else device)
         coords, elem, node_of_input, t_mesh = prepare_tsx_mesh(coords, elem, t, refine=refine, renumber=renumber,
-                                                               device=mesh_device)
+                                                               device=mesh_device, curves=curves)
         if node_of_input is not None:
             monitor = (monitor[0], int(node_of_input[monitor[1]]))
         if log:
@@ -415,7 +430,7 @@ def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, 
                 % (t_mesh['refine'], t_mesh['renumber'], t_mesh['enrich'], elem.shape[1], coords.shape[1]))
     elif mesh_dir is not None:
         from .meshio import load_tsx_mesh
-        coords, elem = load_tsx_mesh(mesh_dir, t)
+        coords, elem = load_tsx_mesh(mesh_dir, t, curves=curves)
     if coords is None or elem is None:
         raise ValueError('pass the mesh (coords, elem) or mesh_dir')
     young, nu = 60000, 0.2                                                                # TSX:1663-1672
@@ -435,7 +450,7 @@ def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, 
     Q[1, coords[1, :] > 49.99] = 0
     return {'type': t, 'coords': coords, 'elem': elem, 'monitor': monitor, 'node_of_input': node_of_input, 't_mesh': t_mesh,
             'materials': (shear0, bulk0, eta0, c_0), 's0': s0, 'init_strain': init_strain, 'Q': Q,
-            'prepared': bool(refine or renumber)}
+            'prepared': bool(refine or renumber), 'curved': curved}
 
 
 def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log):

@@ -305,7 +305,7 @@ int fep_load_traction_host(int device_id, int64_t n_n, int64_t n_e_s, int n_p_s,
  *       edge_el (2, n_edges): owner element, neighbour element (0 on a boundary edge: the reference leaves its zero there).
  *   refinement  new vertices = the P2 midside nodes (old nodes keep their ids); children 4 i .. 4 i + 3 of element i =
  *       (V1, m12, m31), (m12, V2, m23), (m31, m23, V3), (m12, m23, m31); orientation is preserved and boundary edges are
- *       halved as straight segments (a curved boundary is not re-projected).
+ *       halved as straight segments unless curves are set (fep_mesh_set_curves below).
  * Coordinates are computed without contraction into fused multiply-adds, so every array equals the host functions' bit for
  * bit.  No floating-point atomics; two calls give the same bytes.
  *
@@ -337,6 +337,41 @@ int fep_mesh_enrich_host(const fep_mesh* mesh, int elem_type, int32_t* elem_ext_
                          int32_t* elem_ed_h, int32_t* edge_el_h);
 int fep_mesh_refine_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d);
 int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h);
+
+/* Curved boundaries (opt-in; without curves every output above is byte for byte what it was).  A curve is an axis-aligned
+ * ellipse, five doubles (cx, cy, a, b, tol); a circle has a == b.  For a point p: dx = x - cx, dy = y - cy, u = dx / a,
+ * v = dy / b, g = sqrt(u u + v v), evaluated in this order without fused multiply-adds.  A vertex is ON the curve iff
+ * |g - 1| <= tol.  An edge is CURVED iff it is a boundary edge (exactly one element holds it) and both its ends are on
+ * the same curve; the lowest curve index wins; an interior edge is never curved.  Every node the library creates on a
+ * curved edge (the refinement / P2 midpoint, the P4 midpoint and its two quarter points) is computed as a straight point
+ * exactly as above and then moved to (cx + dx / g, cy + dy / g), with dx, dy, g of that straight point; for g == 0 (a
+ * chord through the centre) it stays.  Existing vertices and P4 interior nodes never move; ids, elem_ext, elem_ed, edge_el,
+ * surf and the child table do not depend on the curves.  The host functions apply the same rule with the same operations.
+ *
+ *   fep_mesh_set_curves   curves_h: n_curves x 5 HOST doubles, copied; they travel to the enrichment / refinement kernels as
+ *                         a by-value argument (no allocation: the _dev forms stay capturable).  n_curves = 0 clears them.
+ *                         FEP_EINVAL, and the mesh keeps the curves it had: n_curves < 0 or > FEP_MAX_CURVES, a <= 0,
+ *                         b <= 0, tol < 0, any value not finite.
+ *   fep_mesh_surf_curve_* curve_of_surf (n_boundary_edges): for every boundary edge in the `surf` order of elem_type
+ *                         (FEP_P2 / FEP_P4) the index of its curve, -1 for a straight one: what a caller needs to put a
+ *                         traction on one curved boundary with fep_load_traction_*.  FEP_ESTATE as fep_mesh_enrich_*.
+ *   fep_mesh_area_stats_* Context-free: P1 vertex rows elem (3, n_e) int32, coord (2, n_n); both device pointers of
+ *                         device_id (_dev, enqueued on `stream`, out: 4 device doubles) or all host pointers (_host,
+ *                         synchronous).  With the doubled signed area d = (x2 - x1)(y3 - y1) - (x3 - x1)(y2 - y1):
+ *                         out = {min d, sum of d / 2, number of triangles with d <= 0, n_e}; min d = +inf for n_e = 0.  A
+ *                         triangle with a vertex id outside [0, n_n) counts as d = 0.  Per-workgroup partials and a
+ *                         one-workgroup final pass in a fixed order: two calls give the same bytes; no floating-point
+ *                         atomics.  The partials live in one fixed block per (device, stream) made by the first call on
+ *                         that stream (FEP_ESTATE if that first call comes while the stream is being captured).  The check
+ *                         that a projected level folded no element, without leaving the device. */
+#define FEP_MAX_CURVES 4
+int fep_mesh_set_curves(fep_mesh* mesh, int n_curves, const double* curves_h);
+int fep_mesh_surf_curve_dev(const fep_mesh* mesh, void* stream, int elem_type, int32_t* curve_of_surf_d);
+int fep_mesh_surf_curve_host(const fep_mesh* mesh, int elem_type, int32_t* curve_of_surf_h);
+int fep_mesh_area_stats_dev(int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem_d, const double* coord_d,
+                            double* out_d);
+int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
+                             double* out_h);
 
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on

@@ -12,10 +12,15 @@ triangles):
                   of the enrichment's output bytes, timed the same way in the same run — the yardstick of the fill
   d  refine       refine_uniform host and device (levels chained on the GPU) for the same depth from the 887-triangle mesh
 
+`--curved` runs the device passes a second time with the tunnel wall's ellipse set (tsx_tunnel.TSX_HOLE; key 'curved'), so that
+both sit in one record, and writes profiles/mesh_bench_curved.json unless `--out` says otherwise; with `--solve R` it also
+solves levels 0..R on the wall's polygon and on its ellipse and prints U[0, 40] of both.  Every run also times the refinement
+kernel alone and fep_mesh_area_stats_dev on its children (HIP events).
+
 `--solve R` adds the end-to-end TSX run solve_tsx_tunnel(refine=R, 'P1', linear_solver='amg', pcg_inexact_rtol=1e-2) with
 its set-up split, without and with renumbering.  One JSON line (and `--out FILE`).
 
-    python tools/mesh_bench.py [--refine 4] [--type P2] [--passes 5] [--solve 5] [--out profiles/mesh_bench.json]
+    python tools/mesh_bench.py [--refine 4] [--type P2] [--passes 5] [--solve 5] [--curved] [--out profiles/mesh_bench.json]
 """
 import argparse
 import importlib
@@ -52,49 +57,56 @@ def events(torch, f, passes):
     return {'best_ms': min(ts), 'median_ms': float(np.median(ts))}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--refine', type=int, default=4)
-    ap.add_argument('--type', default='P2,P4')
-    ap.add_argument('--passes', type=int, default=5)
-    ap.add_argument('--solve', type=int, default=None)
-    ap.add_argument('--device', type=int, default=0)
-    ap.add_argument('--out', default=None)
-    a = ap.parse_args()
-    import torch
-    fep = importlib.import_module('fem-elastoplasticity_amd')
-    fep.build()
+def measure(fep, torch, a, coord0, elem0, curves, host=True):
+    """Passes a-d on the tunnel mesh refined a.refine times; `curves` (None or [TSX_HOLE]) go to every call.  host=False
+    leaves out the host loops (a, and d's host side)."""
     dev = a.device
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'tsx.npz'))
-    coord0, elem0 = g['coord'], g['elem']
-    res = {'tool': 'mesh_bench', 'refine': a.refine, 'device_name': torch.cuda.get_device_name(dev)}
-
+    kw = {} if curves is None else {'curves': curves}
+    res = {}
     # d: refinement, host and device, same depth
-    t0 = time.perf_counter()
-    coord, elem = fep.refine_uniform(coord0, elem0, levels=a.refine)
-    res['refine_host_ms'] = 1e3 * (time.perf_counter() - t0)
-    fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev)                    # warm-up
-    res['refine_device'] = wall(lambda: fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev), a.passes)
-    cd, ed = fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev)
-    res['refine_bit_equal'] = bool(np.array_equal(cd, coord) and np.array_equal(ed, elem))
+    if host:
+        t0 = time.perf_counter()
+        coord, elem = fep.refine_uniform(coord0, elem0, levels=a.refine, **kw)
+        res['refine_host_ms'] = 1e3 * (time.perf_counter() - t0)
+    fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev, **kw)              # warm-up
+    res['refine_device'] = wall(lambda: fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev, **kw), a.passes)
+    cd, ed = fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev, **kw)
+    if host:
+        res['refine_bit_equal'] = bool(np.array_equal(cd, coord) and np.array_equal(ed, elem))
+    else:
+        coord, elem = cd, ed
     res['n_e'], res['n_n'] = int(elem.shape[1]), int(coord.shape[1])
 
     tdev = torch.device('cuda', dev)
     coord_d = torch.from_numpy(coord).to(tdev)
     elem_d = torch.from_numpy(elem.astype(np.int32)).to(tdev)
+    # the refinement kernel alone (one level from this mesh) and the area statistics of its children, HIP events
+    with fep.DeviceMesh(coord_d, elem_d, dev, on_device=True) as m:
+        m.set_curves(curves)
+        c1, e1 = m.refine_dev()                                                       # warm-up
+        torch.cuda.synchronize(dev)
+        res['resident_refine'] = events(torch, m.refine_dev, a.passes)
+        out = fep.area_stats_dev(c1, e1, dev)                                         # warm-up: makes the partials' block
+        res['area_stats'] = events(torch, lambda: fep.area_stats_dev(c1, e1, dev, out=out), a.passes)
+        res['area_stats_out'] = [float(v) for v in out.cpu().numpy()]
+        del c1, e1
     for t in a.type.split(','):
         r = {}
-        t0 = time.perf_counter()
-        h = fep.create_midpoints(t, coord, elem)
-        r['host_ms'] = 1e3 * (time.perf_counter() - t0)                                # a
-        d = fep.create_midpoints(t, coord, elem, device=dev)                          # warm-up
-        r['bit_equal'] = bool(all(np.array_equal(h[k], d[k]) and h[k].dtype == d[k].dtype for k in h))
-        r['device_host'] = wall(lambda: fep.create_midpoints(t, coord, elem, device=dev), a.passes)       # b
-        r['speedup_device_host'] = r['host_ms'] / r['device_host']['median_ms']
+        if host:
+            t0 = time.perf_counter()
+            h = fep.create_midpoints(t, coord, elem, **kw)
+            r['host_ms'] = 1e3 * (time.perf_counter() - t0)                            # a
+        d = fep.create_midpoints(t, coord, elem, device=dev, **kw)                    # warm-up
+        if host:
+            r['bit_equal'] = bool(all(np.array_equal(h[k], d[k]) and h[k].dtype == d[k].dtype for k in h))
+        r['device_host'] = wall(lambda: fep.create_midpoints(t, coord, elem, device=dev, **kw), a.passes)   # b
+        if host:
+            r['speedup_device_host'] = r['host_ms'] / r['device_host']['median_ms']
         meshes = []
 
         def analyse():
             meshes.append(fep.DeviceMesh(coord_d, elem_d, dev, on_device=True))
+            meshes[-1].set_curves(curves)
         analyse()
         m = meshes[0]
         out = m.enrich_dev(t)                                                          # warm-up
@@ -113,6 +125,44 @@ def main():
         for mm in meshes:
             mm.close()
         res[t] = r
+    return res
+
+
+def solve(fep, a, mesh_dir, refine, renumber, curves):
+    t0 = time.perf_counter()
+    h = fep.solve_tsx_tunnel(mesh_dir=mesh_dir, element_type='P1', refine=refine, renumber=renumber, linear_solver='amg',
+                             pcg_inexact_rtol=1e-2, device=a.device, curves=curves,
+                             log=lambda s: print(s, file=sys.stderr, flush=True))
+    return {'wall_s': time.perf_counter() - t0, 'n_e': int(h['elem'].shape[1]) if 'elem' in h else None, 'n_n': int(h['U'][-1].shape[1]),
+            'accepted_steps': len(h['zeta']), 'zeta_last': float(h['zeta'][-1]), 'displ_last': float(h['displ'][-1]),
+            'n_plast_last': int(h['n_plast'][-1]), 'n_calls': int(h['n_calls']),
+            'pcg_iters': int(np.sum(h['pcg_iters'])) if h['pcg_iters'] is not None else None,
+            'setup_s': {k: float(v) for k, v in h['t_setup'].items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--refine', type=int, default=4)
+    ap.add_argument('--type', default='P2,P4')
+    ap.add_argument('--passes', type=int, default=5)
+    ap.add_argument('--solve', type=int, default=None)
+    ap.add_argument('--curved', action='store_true')
+    ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    import torch
+    fep = importlib.import_module('fem-elastoplasticity_amd')
+    fep.build()
+    dev = a.device
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'tsx.npz'))
+    coord0, elem0 = g['coord'], g['elem']
+    hole = [fep.tsx_tunnel.TSX_HOLE]
+    res = {'tool': 'mesh_bench', 'refine': a.refine, 'device_name': torch.cuda.get_device_name(dev)}
+    res.update(measure(fep, torch, a, coord0, elem0, None))
+    if a.curved:
+        res['curved'] = measure(fep, torch, a, coord0, elem0, hole, host=False)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'mesh_bench_curved.json')
 
     if a.solve is not None:
         d = tempfile.mkdtemp(prefix='tsx_csv_')
@@ -120,16 +170,15 @@ def main():
         np.savetxt(os.path.join(d, 'elem.csv'), elem0 + 1, delimiter=',', fmt='%d')
         res['solve'] = {'refine': a.solve}
         for renumber in (False, True):
-            t0 = time.perf_counter()
-            h = fep.solve_tsx_tunnel(mesh_dir=d, element_type='P1', refine=a.solve, renumber=renumber, linear_solver='amg',
-                                     pcg_inexact_rtol=1e-2, device=dev, log=lambda s: print(s, file=sys.stderr, flush=True))
-            res['solve']['renumber' if renumber else 'as_refined'] = {
-                'wall_s': time.perf_counter() - t0, 'n_e': int(h['elem'].shape[1]), 'n_n': int(h['coords'].shape[1]),
-                'accepted_steps': len(h['zeta']), 'zeta_last': float(h['zeta'][-1]), 'displ_last': float(h['displ'][-1]),
-                'n_plast_last': int(h['n_plast'][-1]), 'n_calls': int(h['n_calls']),
-                'pcg_iters': int(np.sum(h['pcg_iters'])) if h['pcg_iters'] is not None else None,
-                'setup_s': {k: float(v) for k, v in h['t_setup'].items()}}
-            del h
+            res['solve']['renumber' if renumber else 'as_refined'] = solve(fep, a, d, a.solve, renumber, None)
+        if a.curved:
+            # U[0, 40] (the tunnel's crown) per level, on the wall's polygon and on its ellipse
+            res['solve']['levels'] = []
+            for lv in range(a.solve + 1):
+                row = {'refine': lv, 'polygon': solve(fep, a, d, lv, False, None), 'ellipse': solve(fep, a, d, lv, False, hole)}
+                res['solve']['levels'].append(row)
+                print('refine %d: U[0, 40] polygon %.10e, ellipse %.10e' % (lv, row['polygon']['displ_last'],
+                                                                           row['ellipse']['displ_last']), file=sys.stderr, flush=True)
     line = json.dumps(res)
     print(line)
     if a.out:
