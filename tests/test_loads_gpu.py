@@ -202,9 +202,10 @@ def test_traction_on_sloping_strips_vs_closed_form(fep, direction, n_p_s):
     Two-node edges: t L / 2 per end node; three-node edges with the middle node at the midpoint: t L / 6, t L / 6, 4 t L / 6.
     All coordinates are multiples of 2^-9 (exact in binary, exact midpoints); each edge length is taken from the float end
     points with 60 digits, so the closed form carries one rounding per edge and node.
-    The bound has no term for the cancellation inside j_c = sum_a x_a dhat_a of a three-node edge (the reference's formula,
-    kept so that its horizontal edges are reproduced to the bits of its own Jacobian): its absolute error grows with the
-    distance of the edge from the origin, up to (n_p_s + 1) u sum_a |x_a dhat_a|.  The strips are therefore centred at the
+    The cancellation inside j_c = sum_a x_a dhat_a of a three-node edge (the reference's formula, kept so that its horizontal
+    edges are reproduced to the bits of its own Jacobian) is not in this bound: its absolute error grows with the distance of
+    the edge from the origin, up to (n_p_s + 1) u sum_a |x_a dhat_a|.  tests/loads_exact.py, traction_bound, carries that term
+    and tests/test_loads_shapes_gpu.py applies it to curved and high-order edges anywhere.  The strips here are centred at the
     origin, |x| <= 3 edge lengths; for two-node edges on this lattice j_c is exact anywhere."""
     step = {'vertical': (0.0, 0.5), '30 degrees': (round(np.sqrt(3) / 4 * 256) / 256, 0.25)}[direction]
     n_e = 6
