@@ -16,9 +16,10 @@ from .tables import (ELEMENT_SHAPE, LagrangeElementType, element_tables, get_loc
                      get_local_basis_volume, get_quadrature_surface, get_quadrature_volume, surface_tables)
 from .mesh import assemble_mesh, assemble_mesh_el, rect_mesh, renumber_for_locality, square_mesh
 from .hotpath import (MeshContext, assemble_tangent, construct_constitutive_problem,
-                      construct_constitutive_problem_tsx, default_device, get_elastic_stiffness_matrix,
+                      construct_constitutive_problem_tsx, construct_constitutive_problem_vm, default_device, get_elastic_stiffness_matrix,
                       get_elastic_stiffness_matrix_el, get_vector_traction, get_vector_volume, load_traction)
 from .elastic import solve_elasticity2d
+from .vonmises import solve_cutout_cyclic
 from ._lib import FepError, lib, lib_path
 from .build import build
 from .sharding import GatherPlan, Partition, ShardedContext, element_ranges, global_pattern, merge_host
@@ -28,7 +29,7 @@ from .dist_newton import DistributedPCG, GatheredSolver, solve_strip_footing_sha
 from .midpoints import (DeviceMesh, Ellipse, area_stats, area_stats_dev, create_midpoints, create_midpoints_P2, create_midpoints_P4,
                         refine_uniform)
 from .meshio import dump_free_dof_csv, load_tsx_mesh, prepare_tsx_mesh
-from . import plasticity2d_dp, tsx_tunnel, elasticity2d
+from . import plasticity2d_dp, tsx_tunnel, elasticity2d, vonmises
 
 __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get_local_basis_volume',
            'element_tables', 'assemble_mesh', 'square_mesh', 'rect_mesh', 'renumber_for_locality', 'Partition', 'ShardedContext', 'element_ranges', 'GatherPlan', 'global_pattern', 'merge_host', 'MeshContext', 'construct_constitutive_problem',
@@ -38,4 +39,5 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'create_midpoints_P4', 'refine_uniform', 'DeviceMesh', 'Ellipse', 'area_stats', 'area_stats_dev', 'load_tsx_mesh', 'prepare_tsx_mesh', 'dump_free_dof_csv',
            'get_quadrature_surface', 'get_local_basis_surface', 'surface_tables', 'assemble_mesh_el', 'get_vector_volume',
            'get_vector_traction', 'load_traction', 'solve_elasticity2d',
-           'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d']
+           'construct_constitutive_problem_vm', 'solve_cutout_cyclic',
+           'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d', 'vonmises']

@@ -59,6 +59,8 @@ struct fep_ctx {
     int64_t n_e = 0, n_n = 0, n_int = 0, n_dof = 0, nnz = 0, n_blk = 0;
     Route route = Route::Coo;
     bool have_materials = false;
+    int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
+    uint2* vm_blk = nullptr;                            // FEP_MODEL_VM: per-workgroup plastic counts of the point kernel
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
     int csr_gathers = 4;                                // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
@@ -302,11 +304,12 @@ static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) 
     return FEP_OK;
 }
 
-extern "C" int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
-                                  const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
-                                  const double* e0_h, double* ep_prev_d,
-                                  const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
-                                  int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+// (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager or a, Y of von Mises)
+static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n_int,
+                               const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                               const double* e0_h, double* ep_prev_d,
+                               const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
+                               int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_d || !shear_d || !bulk_d || !eta_d || !c_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(device_id));
@@ -315,7 +318,7 @@ extern "C" int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
     const unsigned n_blocks = grid_for(n_int, kBlock);
     uint2* blk = nullptr;
     if (counts_d) FEP_TRY(rm_scratch(device_id, st, n_blocks, &blk));
-    hipLaunchKernelGGL(return_map_kernel, dim3(n_blocks), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(model == FEP_MODEL_VM ? return_map_vm_kernel : return_map_kernel, dim3(n_blocks), dim3(kBlock), 0, st,
                        n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
                        shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
     HIP_TRY(hipGetLastError());
@@ -324,6 +327,24 @@ extern "C" int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
         HIP_TRY(hipGetLastError());
     }
     return FEP_OK;
+}
+
+extern "C" int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
+                                  const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                  const double* e0_h, double* ep_prev_d,
+                                  const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
+                                  int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    return return_map_dev_impl(FEP_MODEL_DP, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
+}
+
+extern "C" int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
+                                     const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                     const double* e0_h, double* ep_prev_d,
+                                     const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                                     int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    return return_map_dev_impl(FEP_MODEL_VM, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
 }
 
 // persistent device buffer `idx` of a context's host entry points (sizes are fixed by the mesh: allocated once)
@@ -353,7 +374,7 @@ extern "C" int fep_host_trim(void) {
     catch (...) { return FEP_ENOMEM; }
 }
 
-static int return_map_host_impl(int device_id, int64_t n_int,
+static int return_map_host_impl(int model, int device_id, int64_t n_int,
                                 const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
                                 const double* e0_h, double* ep_prev_h,
                                 const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
@@ -389,9 +410,9 @@ static int return_map_host_impl(int device_id, int64_t n_int,
         std::fprintf(stderr, "[fep] return_map_host: inputs on the device after %.3f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
-    FEP_TRY(fep_return_map_dev(device_id, E->stream, n_int, (const double*)e, e_pt_stride, e_comp_stride, e0_h, (double*)ep,
-                               (const double*)sh, (const double*)bu, (const double*)et, (const double*)cc, accept, (double*)s,
-                               (double*)ds, (uint8_t*)ip, (int64_t*)cnt));
+    FEP_TRY(return_map_dev_impl(model, device_id, E->stream, n_int, (const double*)e, e_pt_stride, e_comp_stride, e0_h,
+                                (double*)ep, (const double*)sh, (const double*)bu, (const double*)et, (const double*)cc, accept,
+                                (double*)s, (double*)ds, (uint8_t*)ip, (int64_t*)cnt));
     if (s_h) FEP_TRY(E->d2h(s_h, s, (size_t)(4 * nb)));
     if (ds_h) FEP_TRY(E->d2h(ds_h, ds, (size_t)(9 * nb)));
     if (ind_p_h) FEP_TRY(E->d2h(ind_p_h, ip, (size_t)n_int));
@@ -412,8 +433,17 @@ extern "C" int fep_return_map_host(int device_id, int64_t n_int,
                                    const double* e0_h, double* ep_prev_h,
                                    const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
                                    int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
-    FEP_GUARD(return_map_host_impl(device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h, bulk_h, eta_h,
-                                   c_h, accept, s_h, ds_h, ind_p_h, counts_h))
+    FEP_GUARD(return_map_host_impl(FEP_MODEL_DP, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, eta_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
+}
+
+extern "C" int fep_return_map_vm_host(int device_id, int64_t n_int,
+                                      const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                                      const double* e0_h, double* ep_prev_h,
+                                      const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                                      int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+    FEP_GUARD(return_map_host_impl(FEP_MODEL_VM, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
 }
 
 using fep_host::Symbolic;
@@ -899,7 +929,21 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
     auto b = [](bool v) { return v ? "true" : "false"; };
     char tmp[256];
-    if (c->route == Route::P1Node && c->p1_lds) {
+    if (c->model == FEP_MODEL_VM) {                     // point kernel + the route's assembly from ds / s (step_vm)
+        char pt[64], el[96];
+        if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_vm_kernel");
+        else std::snprintf(pt, sizeof pt, "point_vm_kernel<%d, %d>", c->n_p, c->n_q);
+        const bool patch = c->route == Route::Patch;
+        std::snprintf(el, sizeof el, "element_kernel<%d, %d, false, %s, %s, %d, %d>", c->n_p, c->n_q, b(c->elem_geo), b(patch),
+                      patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
+        if (c->route == Route::P1Node && c->p1_lds)
+            std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, c->tile, b(c->p1_rng), b(c->p1_pk));
+        else if (c->route == Route::P1Node) std::snprintf(tmp, sizeof tmp, "%s + p1_node_kernel", pt);
+        else if (patch) std::snprintf(tmp, sizeof tmp, "%s + %s + fixup_kernel", pt, el);
+        else if (c->route == Route::Coo)
+            std::snprintf(tmp, sizeof tmp, "%s + %s + %s", pt, el, c->pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
+        else return FEP_ESTATE;
+    } else if (c->route == Route::P1Node && c->p1_lds) {
         if (which == 1 && c->p1_fused && c->fused_mode >= 1)
             std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", c->tile, b(c->p1_fused_rng), b(c->p1_dma));
         else
@@ -970,6 +1014,34 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     for (int64_t k = 1; uni && k < c->n_int; ++k)
         uni = shear_h[k] == shear_h[0] && bulk_h[k] == bulk_h[0] && eta_h[k] == eta_h[0] && c_h[k] == c_h[0];
     c->matu = MatU{shear_h[0], bulk_h[0], eta_h[0], c_h[0], uni ? 1 : 0};
+    return FEP_OK;
+}
+
+// The second material model runs as point kernel + the route's assembly: its ds / s scratch and the point kernel's
+// per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
+extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
+    if (!c || (model != FEP_MODEL_DP && model != FEP_MODEL_VM)) return FEP_EINVAL;
+    if (model == FEP_MODEL_VM) {
+#ifdef FEP_ABLATION
+        if (c->route == Route::GenNode) return FEP_ESTATE;
+#endif
+        FEP_TRY(fep_set_device(c->device));
+        if (!c->ds_int || !c->s_int || !c->vm_blk) {
+            // refused while a capture is in progress (the query on the default stream fails during a capture on another)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(nullptr, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_ESTATE; }
+            if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
+        }
+        FEP_TRY(point_scratch(c, nullptr, true, true));
+        if (!c->vm_blk) FEP_TRY(dmalloc(c, &c->vm_blk, (int64_t)grid_for(c->n_int, kBlock)));
+    }
+    c->model = model;
+    return FEP_OK;
+}
+
+extern "C" int fep_ctx_model(const fep_ctx* c, int* model) {
+    if (!c || !model) return FEP_EINVAL;
+    *model = c->model;
     return FEP_OK;
 }
 
@@ -1247,6 +1319,49 @@ static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const d
     return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
 }
 
+// Von Mises contexts (FEP_MODEL_VM): stage A is the model's point kernel (geometry, strain, vm_return_map; s / ds to the
+// caller's arrays or the context's scratch), stage B exactly what fep_assemble_dev launches for the route (the element routes'
+// element_kernel in its assembly-only form, then the route's assembly kernel), stage C the COO form's force gather.
+static int step_vm(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
+                   double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt) {
+    if (!c->ds_int || !c->s_int || !c->vm_blk) return FEP_ESTATE;
+    if (k_data_d && !ds_d) ds_d = c->ds_int;
+    if (f_out_d && !s_d) s_d = c->s_int;
+    uint2* blk = cnt ? c->vm_blk : nullptr;
+    const unsigned n_blocks = grid_for(c->n_int, kBlock);
+    bool counted = false, f_due = false;
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
+    FEP_TRY(prof_mark(c, st));
+    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        if constexpr (ET::type == FEP_P1)
+            hipLaunchKernelGGL(p1_point_vm_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->p1tab, u_d, e0,
+                               ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
+        else
+            hipLaunchKernelGGL((point_vm_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
+                               c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
+                               e_out_d, s_d, ds_d, ind_p_d, blk);
+        return FEP_OK;
+    }));
+    HIP_TRY(hipGetLastError());
+    FEP_TRY(prof_mark(c, st));
+    if (k_data_d || f_out_d) {
+        if (element_route(c))
+            FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, s_d, ds_d, nullptr, nullptr,
+                                          k_data_d, f_out_d));
+        FEP_TRY(launch_assembly(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, &counted, &f_due));
+    }
+    FEP_TRY(prof_mark(c, st));
+    if (f_due) FEP_TRY(launch_force(c, st, f_out_d));
+    FEP_TRY(prof_mark(c, st));
+    if (cnt) {
+        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)n_blocks, c->vm_blk, cnt);
+        HIP_TRY(hipGetLastError());
+    }
+    return FEP_OK;
+}
+
 // fep_step_dev and fep_assemble_dev record four events per call (fep_ctx_profile_end: three intervals):
 //   mark 0, stage A (point / element kernel), mark 1, stage B (assembly), mark 2, stage C (COO: force gather), mark 3
 // then the branch-counter sum if no kernel took it.
@@ -1261,6 +1376,8 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     unsigned long long* cnt = (unsigned long long*)counts_d;
     uint2* blk = cnt ? c->blk_counts : nullptr;
     const E0 e0 = make_e0(e0_h);
+    if (c->model == FEP_MODEL_VM)
+        return step_vm(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt);
     const bool point_outputs = e_out_d || s_d || ds_d || ind_p_d;
     const bool fused = c->route == Route::P1Node && c->p1_fused && !accept && (k_data_d || f_out_d) &&
                        c->fused_mode > (point_outputs ? 1 : 0);

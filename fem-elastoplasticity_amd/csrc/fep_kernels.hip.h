@@ -103,6 +103,64 @@ __device__ __forceinline__ int dp_return_map(const double e[3], const double z[4
     return branch;
 }
 
+// ---------------------------------------------------------------------------------------
+// Per-point von Mises return map with linear kinematic hardening (the second material model, FEP_MODEL_VM; no
+// counterpart in the reference): radial return onto |dev s - a*p| = Y, symmetric consistent tangent.
+//   a  hardening modulus (>= 0: the back stress is a*p, so the plastic strain is the only state),
+//   Y  yield radius sqrt(2/3)*sigma_y (> 0).  Everything else as dp_return_map.  Returns 0 elastic, 1 plastic.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int vm_return_map(const double e[3], const double z[4], double p[4],
+                                             double G, double K, double a, double Y, bool accept,
+                                             double s[4], double d[6]) {
+    const double I3 = 1.0 / 3.0;
+    const double DD = 1.0 - 1.0 / 3.0;
+    const double Et0 = (e[0] + z[0]) - p[0];
+    const double Et1 = (e[1] + z[1]) - p[1];
+    const double Et2 = (e[2] + z[2]) - p[2];
+    const double Et3 = (0.0 + z[3]) - p[3];
+    const double tr = Et0 + Et1 + Et3;
+    const double dv0 = DD * Et0 - I3 * Et1 - I3 * Et3;
+    const double dv1 = -I3 * Et0 + DD * Et1 - I3 * Et3;
+    const double dv2 = 0.5 * Et2;
+    const double dv3 = -I3 * Et0 - I3 * Et1 + DD * Et3;
+    const double G2 = 2.0 * G;
+    const double Ktr = K * tr;
+    double s0 = G2 * dv0 + Ktr, s1 = G2 * dv1 + Ktr, s2 = G2 * dv2, s3 = G2 * dv3 + Ktr;   // trial stress
+    // relative trial stress xi = dev s_tr - a*p (tensor shear: half the engineering p[2])
+    const double x0 = G2 * dv0 - a * p[0], x1 = G2 * dv1 - a * p[1], x2 = G2 * dv2 - a * (0.5 * p[2]), x3 = G2 * dv3 - a * p[3];
+    const double nrm = sqrt(x0 * x0 + x1 * x1 + 2.0 * (x2 * x2) + x3 * x3);
+    const double crit = nrm - Y;
+    // elastic tangent 2*Dev*G + Vol*K
+    double d00 = 2.0 * DD * G + K, d01 = 2.0 * (-I3) * G + K, d02 = 0.0;
+    double d11 = d00, d12 = 0.0, d22 = 2.0 * 0.5 * G;
+    int branch = 0;
+    if (crit > 0.0) {
+        branch = 1;
+        const double H = G2 + a;
+        const double lam = crit / H;
+        const double N0 = x0 / nrm, N1 = x1 / nrm, N2 = x2 / nrm, N3 = x3 / nrm;
+        const double g = G2 * lam;
+        s0 -= g * N0; s1 -= g * N1; s2 -= g * N2; s3 -= g * N3;
+        const double cn = G2 * G2 / H;                    // along N (x) N
+        const double cf = G2 * G2 * lam / nrm;            // along Dev - N (x) N
+        d00 = d00 - cn * (N0 * N0) - cf * (DD - N0 * N0);
+        d01 = d01 - cn * (N0 * N1) - cf * (-I3 - N0 * N1);
+        d02 = d02 - cn * (N0 * N2) - cf * (0.0 - N0 * N2);
+        d11 = d11 - cn * (N1 * N1) - cf * (DD - N1 * N1);
+        d12 = d12 - cn * (N1 * N2) - cf * (0.0 - N1 * N2);
+        d22 = d22 - cn * (N2 * N2) - cf * (0.5 - N2 * N2);
+        if (accept) {
+            p[0] += lam * N0;
+            p[1] += lam * N1;
+            p[2] += 2.0 * lam * N2;
+            p[3] += lam * N3;
+        }
+    }
+    s[0] = s0; s[1] = s1; s[2] = s2; s[3] = s3;
+    d[0] = d00; d[1] = d01; d[2] = d02; d[3] = d11; d[4] = d12; d[5] = d22;
+    return branch;
+}
+
 // Smooth / apex counters (the numbers the reference logs at DP:730).  Wave ballot -> LDS -> per
 // workgroup either a plain store into blk_counts[blockIdx.x] (summed by counts_reduce_kernel; no
 // global atomics at all) or, for the mesh-free entry point, one global atomic per workgroup.
@@ -228,6 +286,27 @@ return_map_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64_t 
         if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
     }
     count_branches(branch, nullptr, blk_counts);      // per-workgroup counters, summed by counts_reduce_kernel (no global atomics)
+}
+
+// The same for the von Mises model: `hard` / `yld` = a / Y per point (vm_return_map)
+__global__ void __launch_bounds__(kBlock)
+return_map_vm_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, E0 e0,
+                     double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
+                     const double* __restrict__ hard, const double* __restrict__ yld, int accept,
+                     double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
+                     uint2* blk_counts) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int branch = 0;
+    if (k < n) {
+        double ev[3] = {e[k * eps], e[k * eps + ecs], e[k * eps + 2 * ecs]};
+        double p[4] = {0.0, 0.0, 0.0, 0.0};
+        if (ep) { p[0] = ep[k]; p[1] = ep[n + k]; p[2] = ep[2 * n + k]; p[3] = ep[3 * n + k]; }
+        double s[4], d[6];
+        branch = vm_return_map(ev, e0.v, p, shear[k], bulk[k], hard[k], yld[k], accept != 0, s, d);
+        store_point(k, n, s, d, branch, S, DS, indp);
+        if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
+    }
+    count_branches(branch, nullptr, blk_counts);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1154,6 +1233,44 @@ p1_point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __r
     count_branches(branch, nullptr, blk_counts);
 }
 
+// Von Mises step of a P1 context (FEP_MODEL_VM), stage A: p1_point_kernel with vm_return_map — one lane per element, same
+// geometry and strain; `hard` / `yld` = a / Y per point (MatU: eta / c hold them).  Stage B is the context's own assembly.
+__global__ void __launch_bounds__(kBlock)
+p1_point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, P1Tab tab,
+                   const double* __restrict__ U, E0 e0, double* __restrict__ ep,
+                   const double* __restrict__ shear, const double* __restrict__ bulk,
+                   const double* __restrict__ hard, const double* __restrict__ yld, MatU mu, int accept,
+                   double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+                   uint8_t* __restrict__ indp, uint2* blk_counts) {
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int branch = 0;
+    if (e < n_e) {
+        const int64_t n0 = elem[e], n1 = elem[n_e + e], n2 = elem[2 * n_e + e];
+        const double2 c0 = *reinterpret_cast<const double2*>(xy + 2 * n0);
+        const double2 c1 = *reinterpret_cast<const double2*>(xy + 2 * n1);
+        const double2 c2 = *reinterpret_cast<const double2*>(xy + 2 * n2);
+        const double2 u0 = *reinterpret_cast<const double2*>(U + 2 * n0);
+        const double2 u1 = *reinterpret_cast<const double2*>(U + 2 * n1);
+        const double2 u2 = *reinterpret_cast<const double2*>(U + 2 * n2);
+        double d1[3], d2[3], w;
+        p1_geometry(tab, c0, c1, c2, d1, d2, w);
+        double ev[3];
+        ev[0] = d1[0] * u0.x + d1[1] * u1.x + d1[2] * u2.x;
+        ev[1] = d2[0] * u0.y + d2[1] * u1.y + d2[2] * u2.y;
+        ev[2] = (d2[0] * u0.x + d1[0] * u0.y) + (d2[1] * u1.x + d1[1] * u1.y) + (d2[2] * u2.x + d1[2] * u2.y);
+        double p[4] = {0.0, 0.0, 0.0, 0.0};
+        if (ep) { p[0] = ep[e]; p[1] = ep[n_e + e]; p[2] = ep[2 * n_e + e]; p[3] = ep[3 * n_e + e]; }
+        double s[4], d[6];
+        const double m_sh = mu.on ? mu.shear : shear[e], m_bu = mu.on ? mu.bulk : bulk[e];
+        const double m_a = mu.on ? mu.eta : hard[e], m_y = mu.on ? mu.c : yld[e];
+        branch = vm_return_map(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
+        store_point(e, n_e, s, d, branch, S, DS, indp);
+        if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
+        if (accept && ep && branch) { ep[e] = p[0]; ep[n_e + e] = p[1]; ep[2 * n_e + e] = p[2]; ep[3 * n_e + e] = p[3]; }
+    }
+    count_branches(branch, nullptr, blk_counts);
+}
+
 __global__ void __launch_bounds__(kBlock)
 p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, const int32_t* __restrict__ perm2,
                const uint32_t* __restrict__ meta, const int32_t* __restrict__ ncol,
@@ -1784,6 +1901,82 @@ point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __rest
         const double m_sh = mu.on ? mu.shear : shear[k], m_bu = mu.on ? mu.bulk : bulk[k];
         const double m_eta = mu.on ? mu.eta : eta[k], m_c = mu.on ? mu.c : cc[k];
         branch = dp_return_map(ev, e0.v, p, m_sh, m_bu, m_eta, m_c, accept != 0, s, d);
+        store_point(k, n_int, s, d, branch, S, DS, indp);
+        if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
+        if (accept && ep && branch) { ep[k] = p[0]; ep[n_int + k] = p[1]; ep[2 * n_int + k] = p[2]; ep[3 * n_int + k] = p[3]; }
+    }
+    count_branches(branch, nullptr, blk_counts);
+}
+
+// Von Mises step (FEP_MODEL_VM), stage A for P2, Q1, Q2 and P4: point_kernel's split with vm_return_map.  One lane per
+// integration point; writes s / ds (the caller's arrays or the context's scratch) for the context's own assembly.
+// Unlike point_kernel it holds no per-node array but the node ids: the Jacobian is summed while the coordinates are
+// gathered, the strain while the displacements are (the 15-node element would otherwise hold 90 doubles per lane).
+// Jacobian, inverse and gradients in geometry_kernel's operations and order without contraction, the strain sums in
+// element_kernel's fused form: dphi and E are bit-identical to theirs.
+__device__ __forceinline__ void inverse_jacobian(double j11, double j12, double j21, double j22, double wfq,
+                                                 double& i11, double& i12, double& i21, double& i22, double& w) {
+#pragma clang fp contract(off)
+    const double det = j11 * j22 - j12 * j21;            // DP:536
+    i11 = j22 / det; i12 = -j12 / det; i21 = -j21 / det; i22 = j11 / det;   // DP:539-542
+    w = fabs(det) * wfq;                                 // DP:585
+}
+
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock)
+point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
+                const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
+                const double* __restrict__ U, E0 e0, double* __restrict__ ep,
+                const double* __restrict__ shear, const double* __restrict__ bulk,
+                const double* __restrict__ hard, const double* __restrict__ yld, MatU mu, int accept,
+                double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+                uint8_t* __restrict__ indp, uint2* blk_counts) {
+    __shared__ double t1[NP * NQ], t2[NP * NQ], tw[NQ];
+    for (int i = threadIdx.x; i < NP * NQ; i += kBlock) { t1[i] = dh1[i]; t2[i] = dh2[i]; }
+    for (int i = threadIdx.x; i < NQ; i += kBlock) tw[i] = wf[i];
+    __syncthreads();
+    const int64_t n_int = n_e * NQ;
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int branch = 0;
+    if (k < n_int) {
+        const int64_t e = k / NQ;
+        const int q = (int)(k - e * NQ);
+        int32_t nd[NP];
+#pragma unroll
+        for (int a = 0; a < NP; ++a) nd[a] = elem[(int64_t)a * n_e + e];
+        double j11 = 0.0, j12 = 0.0, j21 = 0.0, j22 = 0.0;
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int a = 0; a < NP; ++a) {               // DP:530-533
+                const double2 c = *reinterpret_cast<const double2*>(xy + 2 * (int64_t)nd[a]);
+                const double h1 = t1[a * NQ + q], h2 = t2[a * NQ + q];
+                j11 = j11 + c.x * h1; j12 = j12 + c.y * h1; j21 = j21 + c.x * h2; j22 = j22 + c.y * h2;
+            }
+        }
+        double i11, i12, i21, i22, w;
+        inverse_jacobian(j11, j12, j21, j22, tw[q], i11, i12, i21, i22, w);
+        double ev[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int a = 0; a < NP; ++a) {                   // DP:545-546, DP:1043
+            const double2 u = *reinterpret_cast<const double2*>(U + 2 * (int64_t)nd[a]);
+            const double h1 = t1[a * NQ + q], h2 = t2[a * NQ + q];
+            double g1, g2;
+            {
+#pragma clang fp contract(off)
+                g1 = i11 * h1 + i12 * h2;
+                g2 = i21 * h1 + i22 * h2;
+            }
+            ev[0] = __builtin_fma(g1, u.x, ev[0]);
+            ev[1] = __builtin_fma(g2, u.y, ev[1]);
+            ev[2] += __builtin_fma(g1, u.y, g2 * u.x);
+        }
+        double p[4] = {0.0, 0.0, 0.0, 0.0};
+        if (ep) { p[0] = ep[k]; p[1] = ep[n_int + k]; p[2] = ep[2 * n_int + k]; p[3] = ep[3 * n_int + k]; }
+        double s[4], d[6];
+        const double m_sh = mu.on ? mu.shear : shear[k], m_bu = mu.on ? mu.bulk : bulk[k];
+        const double m_a = mu.on ? mu.eta : hard[k], m_y = mu.on ? mu.c : yld[k];
+        branch = vm_return_map(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
         store_point(k, n_int, s, d, branch, S, DS, indp);
         if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
         if (accept && ep && branch) { ep[k] = p[0]; ep[n_int + k] = p[1]; ep[2 * n_int + k] = p[2]; ep[3 * n_int + k] = p[3]; }

@@ -54,7 +54,7 @@ def _strain_view(e, n_int):
 # ---------------------------------------------------------------------------------------
 # a2  construct_constitutive_problem
 # ---------------------------------------------------------------------------------------
-def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, device=None):
+def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, device=None, entry='fep_return_map_host'):
     l = _lib.lib()
     dev = default_device() if device is None else device
     shear = _f64(shear).ravel()
@@ -77,10 +77,9 @@ def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, 
     ind = _lib.pinned_empty(n_int, np.uint8)
     counts = np.zeros(2, dtype=np.int64)
     accept = bool(apply_plastic_strain) and ep_prev is not None
-    _lib.check(l.fep_return_map_host(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
-                                     _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), int(accept),
-                                     _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(counts)),
-               'fep_return_map_host')
+    _lib.check(getattr(l, entry)(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
+                                 _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), int(accept),
+                                 _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(counts)), entry)
     n_smooth, n_apex = int(counts[0]), int(counts[1])
     out = _Result({'s': s, 'ds': ds, 'ind_p': ind.view(np.bool_), 'n_smooth': n_smooth, 'n_apex': n_apex})
     early_out = tsx and n_smooth == 0 and n_apex == 0                  # TSX:1103
@@ -178,6 +177,19 @@ def construct_constitutive_problem_tsx(e, e0, ep_prev, shear, bulk, eta, c, appl
     return _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx=True, device=device)
 
 
+def construct_constitutive_problem_vm(e, ep_prev, shear, bulk, a, Y, apply_plastic_strain=False, e0=None, device=None):
+    """The second material model, no counterpart in the reference: von Mises plasticity with linear kinematic hardening
+    (include/fep.h, fep_return_map_vm_host).  `a` the hardening modulus, `Y` = sqrt(2/3) sigma_y the yield radius, per point;
+    the other arguments as construct_constitutive_problem, `e0` an optional (4,1) initial strain.  Returns
+    {'s', 'ds', 'ind_p', 'ep', 'n_plast'}; with `apply_plastic_strain`, `ep_prev` is updated in place and returned as 'ep'."""
+    r = _return_map(e, e0, ep_prev, shear, bulk, a, Y, apply_plastic_strain, tsx=False, device=device,
+                    entry='fep_return_map_vm_host')
+    return {'s': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'], 'ep': r['ep'], 'n_plast': r['n_smooth']}
+
+
+MODELS = {'dp': 0, 'vm': 1}                                # FEP_MODEL_DP, FEP_MODEL_VM
+
+
 # ---------------------------------------------------------------------------------------
 # mesh context: static operands + fused step
 # ---------------------------------------------------------------------------------------
@@ -218,6 +230,7 @@ class MeshContext:
         self._pattern = None
         self._geom = None
         self._hatp_own = None
+        self.model = 'dp'
 
     # -- lifetime
     def close(self):
@@ -272,6 +285,15 @@ class MeshContext:
     def set_materials(self, shear, bulk, eta, c):
         a = [_f64(np.broadcast_to(np.asarray(v, dtype=np.float64).ravel(), (self.n_int,))) for v in (shear, bulk, eta, c)]
         _lib.check(_lib.lib().fep_ctx_set_materials_host(self._h, *[_lib.ptr(v) for v in a]), 'fep_ctx_set_materials_host')
+
+    def set_model(self, model):
+        """'dp' (Drucker-Prager, the default) or 'vm' (von Mises with linear kinematic hardening: `set_materials` then takes
+        (shear, bulk, a, Y), the results carry the plastic count in 'n_smooth' and 'n_apex' is 0).  Before or after
+        `set_materials`."""
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {sorted(MODELS)}")
+        _lib.check(_lib.lib().fep_ctx_set_model(self._h, MODELS[model]), 'fep_ctx_set_model')
+        self.model = model
 
     def device_ptr(self, which):
         p = C.c_void_p()

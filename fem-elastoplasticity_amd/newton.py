@@ -6,6 +6,7 @@ re-stated around the GPU step.
   solve_tsx_tunnel      tsx-tunnel/pythonFEM.py:1729-1832      (17 uniform steps of the initial-stress factor;
                         the accepting call leaves `apply_plastic_strain` False)
 
+(vonmises.py's cyclic driver runs `_load_history_loop` below, a fixed history of load factors on the same ops objects.)
 Both run ONE loop, `_load_step_loop`: load steps, the Newton iteration with its stopping norms, accept / halve and the
 extrapolation of the next iterate, following the reference line by line.  A driver hands it what its flavour does
 differently: first step and smallest step, the initial strain of a step, the accepting call and what is recorded from
@@ -289,6 +290,47 @@ def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, acce
         U_it = d_zeta * (U - U_old) / d_zeta_old + U                                      # DP:1120, TSX:1821
         if finished(zeta_old) or d_zeta < d_zeta_min:                                     # DP:1123-1127, TSX:1824
             return U, Ep_old
+
+
+def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted):
+    """A prescribed history of load factors on an external load (no counterpart in the reference, whose plastic drivers
+    load through prescribed displacements or an initial stress): for every `zeta` of `zetas` the Newton iteration of
+    _load_step_loop — same iterate update, same stopping quantity in the K_elast norm — on the residual
+    zeta * f_ext - F(U), started from the last accepted U, then the accepting call, which updates the plastic strain in
+    place: the state a load cycle carries.  The stopping quantity is 0 when the correction is exactly 0 (an elastic cycle
+    returns to exactly U = 0 at zeta = 0, where the quotient is 0/0).  There is no sub-stepping: a step that does not
+    converge ends the history and its index goes to hist['failed_at'].  `accepted(r, zeta, U, its)` records a step from
+    the accepting call's result.  Returns the last accepted U and the plastic strain."""
+    U = ops.zeros()
+    Ep = ops.new_ep()
+    criterion = None
+    hist['failed_at'] = None
+    for k, zeta in enumerate(zetas):
+        zeta = float(zeta)
+        U_it = U
+        its = 0
+        for _ in range(25):
+            r = ops.step(U_it, Ep, want=('K', 'F'))
+            hist['n_calls'] += 1
+            its += 1
+            dU = ops.solve(r['K'], zeta * f_ext - r['F'], criterion if its > 1 else 1.0)
+            U_new = U_it + dU
+            q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)
+            criterion = 0.0 if q1 == 0 else q1 / (q2 + q3)
+            if np.isnan(criterion):
+                break
+            U_it = U_new
+            if criterion < 1e-12:
+                break
+        if not criterion < 1e-10:
+            hist['failed_at'] = k
+            break
+        U = U_it
+        r = ops.step(U, Ep, accept=True, want=('ind_p',))
+        hist['n_calls'] += 1
+        hist['zeta'].append(float(zeta))
+        accepted(r, zeta, U, its)
+    return U, Ep
 
 
 def _context_maker(context_factory, device):

@@ -53,6 +53,10 @@ extern "C" {
 #define FEP_Q2 4
 #define FEP_P4 5
 
+/* material models of a mesh context (fep_ctx_set_model) */
+#define FEP_MODEL_DP 0        /* perfectly plastic Drucker-Prager (the reference's law; the default) */
+#define FEP_MODEL_VM 1        /* von Mises with linear kinematic hardening (no reference counterpart) */
+
 typedef struct fep_ctx fep_ctx;
 
 /* ---- library ------------------------------------------------------------------------ */
@@ -111,6 +115,35 @@ int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
                        int accept,
                        double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
 
+/* ---- second material model: von Mises with linear kinematic hardening, mesh-free -------
+ * No reference counterpart.  Plane strain, radial return with the symmetric consistent tangent; layout, strides, e0_h,
+ * ep_prev (NULL = zeros; updated in place when `accept`), outputs and the scratch rule of counts_d exactly as
+ * fep_return_map_*, with the parameters
+ *   a   (n_int) kinematic hardening modulus, >= 0        Y   (n_int) yield radius sqrt(2/3)*sigma_y, > 0
+ * in the places of eta and c.  Per point, with p = ep_prev (engineering shear in p[2]) and z = e0:
+ *     Et = (e, 0) + z - p                    tr = Et0 + Et1 + Et3
+ *     dv = (Et0 - tr/3, Et1 - tr/3, Et2/2, Et3 - tr/3)
+ *     s_tr = 2G*dv + K*tr*(1,1,0,1)
+ *     xi = 2G*dv - a*(p0, p1, p2/2, p3)      nrm = sqrt(xi0^2 + xi1^2 + 2 xi2^2 + xi3^2)      crit = nrm - Y
+ *     crit <= 0:  s = s_tr,  ds = 2G*Dev + K*Vol (the elastic tangent of the Drucker-Prager map)
+ *     crit >  0:  lambda = crit/(2G + a),  N = xi/nrm,  s = s_tr - 2G*lambda*N,
+ *                 ds = 2G*Dev + K*Vol - (2G)^2/(2G+a) N(x)N - (2G)^2*lambda/nrm (Dev - N(x)N)     (rows / columns 11, 22, 12)
+ *                 accept:  p += lambda*(N0, N1, 2 N2, N3)
+ * ind_p = (crit > 0); counts = {number of plastic points, 0}.  The back stress is a*p: the plastic strain is the only
+ * state.  ds is symmetric, so fep_assemble_* takes it as it is. */
+int fep_return_map_vm_host(int device_id, int64_t n_int,
+                           const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                           const double* e0_h, double* ep_prev_h,
+                           const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                           int accept,
+                           double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h);
+int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
+                          const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                          const double* e0_h, double* ep_prev_d,
+                          const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                          int accept,
+                          double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
+
 /* ---- a6/a7: mesh context (static operands of the hot path) ----------------------------
  * Replaces the geometry / index part of get_elastic_stiffness_matrix
  * (DP:491-601, TSX:432-542, EL:368-477): Jacobians, dphi_1/dphi_2, weight = |det|*wf,
@@ -151,6 +184,18 @@ int fep_ctx_pattern_host(const fep_ctx* ctx, int32_t* indptr_h /* n_dof+1 */, in
  * read the arrays; results are bitwise the same either way. */
 int fep_ctx_set_materials_host(fep_ctx* ctx, const double* shear_h, const double* bulk_h,
                                const double* eta_h, const double* c_h);
+/* The material model of the context's steps: FEP_MODEL_DP (the default) or FEP_MODEL_VM; may be called before or after
+ * fep_ctx_set_materials_host.  On a von Mises context the third and fourth arrays of fep_ctx_set_materials_host are a
+ * and Y (fep_return_map_vm_*; the constant-parameter shortcut applies as for Drucker-Prager), and fep_step_* keep their
+ * signature and every output: they run the model's point kernel (geometry from the node coordinates, strain, return map;
+ * s / ds to the caller's arrays or a scratch of the context) and then what fep_assemble_dev launches for the context.
+ * counts = {number of plastic points, 0}.  The call allocates that scratch itself, so fep_step_dev on a von Mises
+ * context never allocates and can be captured into a hipGraph.  Drucker-Prager steps of any context are not affected.
+ * FEP_EINVAL: NULL context or unknown model; FEP_ESTATE: the scratch would have to be allocated while a stream capture
+ * is in progress. */
+int fep_ctx_set_model(fep_ctx* ctx, int model);
+int fep_ctx_model(const fep_ctx* ctx, int* model);
+
 /* Device pointers of the context's static per-point arrays (for the mesh-free entry points):
  * which = 0 shear, 1 bulk, 2 eta, 3 c, 4 weight, 5 dphi1, 6 dphi2. */
 int fep_ctx_device_ptr(const fep_ctx* ctx, int which, void** ptr_d);
