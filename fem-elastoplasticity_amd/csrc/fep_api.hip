@@ -60,7 +60,7 @@ struct fep_ctx {
     Route route = Route::Coo;
     bool have_materials = false;
     int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
-    uint2* vm_blk = nullptr;                            // FEP_MODEL_VM: per-workgroup plastic counts of the point kernel
+    uint2* vm_blk = nullptr;                            // FEP_MODEL_VM / _MC: per-workgroup plastic counts of the point kernel
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
     int csr_gathers = 4;                                // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
@@ -304,7 +304,7 @@ static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) 
     return FEP_OK;
 }
 
-// (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager or a, Y of von Mises)
+// (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises or sin_phi, c of Mohr-Coulomb)
 static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n_int,
                                const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                const double* e0_h, double* ep_prev_d,
@@ -318,7 +318,8 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     const unsigned n_blocks = grid_for(n_int, kBlock);
     uint2* blk = nullptr;
     if (counts_d) FEP_TRY(rm_scratch(device_id, st, n_blocks, &blk));
-    hipLaunchKernelGGL(model == FEP_MODEL_VM ? return_map_vm_kernel : return_map_kernel, dim3(n_blocks), dim3(kBlock), 0, st,
+    const auto kernel = model == FEP_MODEL_MC ? return_map_mc_kernel : model == FEP_MODEL_VM ? return_map_vm_kernel : return_map_kernel;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), 0, st,
                        n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
                        shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
     HIP_TRY(hipGetLastError());
@@ -345,6 +346,15 @@ extern "C" int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
                                      int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     return return_map_dev_impl(FEP_MODEL_VM, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
                                shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
+}
+
+extern "C" int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
+                                     const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                     const double* e0_h, double* ep_prev_d,
+                                     const double* shear_d, const double* bulk_d, const double* sin_phi_d, const double* c_d,
+                                     int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    return return_map_dev_impl(FEP_MODEL_MC, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, sin_phi_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
 }
 
 // persistent device buffer `idx` of a context's host entry points (sizes are fixed by the mesh: allocated once)
@@ -444,6 +454,15 @@ extern "C" int fep_return_map_vm_host(int device_id, int64_t n_int,
                                       int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_VM, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
                                    bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
+}
+
+extern "C" int fep_return_map_mc_host(int device_id, int64_t n_int,
+                                      const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                                      const double* e0_h, double* ep_prev_h,
+                                      const double* shear_h, const double* bulk_h, const double* sin_phi_h, const double* c_h,
+                                      int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+    FEP_GUARD(return_map_host_impl(FEP_MODEL_MC, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, sin_phi_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
 }
 
 using fep_host::Symbolic;
@@ -929,10 +948,11 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
     auto b = [](bool v) { return v ? "true" : "false"; };
     char tmp[256];
-    if (c->model == FEP_MODEL_VM) {                     // point kernel + the route's assembly from ds / s (step_vm)
+    if (c->model != FEP_MODEL_DP) {                     // point kernel + the route's assembly from ds / s (step_model)
         char pt[64], el[96];
-        if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_vm_kernel");
-        else std::snprintf(pt, sizeof pt, "point_vm_kernel<%d, %d>", c->n_p, c->n_q);
+        const char* law = c->model == FEP_MODEL_MC ? "mc" : "vm";
+        if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%s_kernel", law);
+        else std::snprintf(pt, sizeof pt, "point_%s_kernel<%d, %d>", law, c->n_p, c->n_q);
         const bool patch = c->route == Route::Patch;
         std::snprintf(el, sizeof el, "element_kernel<%d, %d, false, %s, %s, %d, %d>", c->n_p, c->n_q, b(c->elem_geo), b(patch),
                       patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
@@ -1017,11 +1037,11 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     return FEP_OK;
 }
 
-// The second material model runs as point kernel + the route's assembly: its ds / s scratch and the point kernel's
+// The models besides Drucker-Prager run as point kernel + the route's assembly: the ds / s scratch and the point kernel's
 // per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
 extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
-    if (!c || (model != FEP_MODEL_DP && model != FEP_MODEL_VM)) return FEP_EINVAL;
-    if (model == FEP_MODEL_VM) {
+    if (!c || (model != FEP_MODEL_DP && model != FEP_MODEL_VM && model != FEP_MODEL_MC)) return FEP_EINVAL;
+    if (model != FEP_MODEL_DP) {
 #ifdef FEP_ABLATION
         if (c->route == Route::GenNode) return FEP_ESTATE;
 #endif
@@ -1319,10 +1339,10 @@ static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const d
     return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
 }
 
-// Von Mises contexts (FEP_MODEL_VM): stage A is the model's point kernel (geometry, strain, vm_return_map; s / ds to the
+// Von Mises and Mohr-Coulomb contexts (FEP_MODEL_VM, _MC): stage A is the model's point kernel (geometry, strain, return map; s / ds to the
 // caller's arrays or the context's scratch), stage B exactly what fep_assemble_dev launches for the route (the element routes'
 // element_kernel in its assembly-only form, then the route's assembly kernel), stage C the COO form's force gather.
-static int step_vm(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
+static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
                    double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt) {
     if (!c->ds_int || !c->s_int || !c->vm_blk) return FEP_ESTATE;
     if (k_data_d && !ds_d) ds_d = c->ds_int;
@@ -1333,15 +1353,17 @@ static int step_vm(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double*
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
     FEP_TRY(prof_mark(c, st));
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    const bool mc = c->model == FEP_MODEL_MC;
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
         if constexpr (ET::type == FEP_P1)
-            hipLaunchKernelGGL(p1_point_vm_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->p1tab, u_d, e0,
-                               ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
+            hipLaunchKernelGGL(mc ? p1_point_mc_kernel : p1_point_vm_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
+                               c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d,
+                               ds_d, ind_p_d, blk);
         else
-            hipLaunchKernelGGL((point_vm_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
-                               c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
-                               e_out_d, s_d, ds_d, ind_p_d, blk);
+            hipLaunchKernelGGL((mc ? point_mc_kernel<ET::NP, ET::NQ> : point_vm_kernel<ET::NP, ET::NQ>), dim3(n_blocks),
+                               dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear,
+                               c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
         return FEP_OK;
     }));
     HIP_TRY(hipGetLastError());
@@ -1376,8 +1398,8 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     unsigned long long* cnt = (unsigned long long*)counts_d;
     uint2* blk = cnt ? c->blk_counts : nullptr;
     const E0 e0 = make_e0(e0_h);
-    if (c->model == FEP_MODEL_VM)
-        return step_vm(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt);
+    if (c->model != FEP_MODEL_DP)
+        return step_model(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt);
     const bool point_outputs = e_out_d || s_d || ds_d || ind_p_d;
     const bool fused = c->route == Route::P1Node && c->p1_fused && !accept && (k_data_d || f_out_d) &&
                        c->fused_mode > (point_outputs ? 1 : 0);

@@ -161,6 +161,126 @@ __device__ __forceinline__ int vm_return_map(const double e[3], const double z[4
     return branch;
 }
 
+// ---------------------------------------------------------------------------------------
+// Per-point Mohr-Coulomb return map (the third material model, FEP_MODEL_MC; no counterpart in the reference):
+// associative, perfectly plastic, the closest-point projection in principal stresses with its spectral tangent
+// (include/fep.h, fep_return_map_mc_*, has the law).  sp = sin(phi) in (0, 1), c > 0; everything else as dp_return_map.
+// Returns 0 elastic, 1 smooth face, 2 left edge (sig1 = sig2), 3 right edge (sig2 = sig3), 4 apex.
+//
+// The five branches diverge within a wave, so no work sits inside a branch: the face and the two edges are ONE formula on
+// the branch's normal n and strains t (an edge averages its merged pair), A n = 2G n + 2 lam sp,  den = n . A n,
+//     L = (2G n . e + 2 lam sp tr - 2 c cos) / den,   sig = lam tr + 2G t - L A n,   dsig/deps = lam + G M - (A n)(A n)^T / den
+// (M = 2I with the merged pair's block replaced by ones), the operands chosen by selects; the elastic branch is L = 0 and
+// 1/den = 0 in it, the apex overwrites its results.  The in-plane eigenvalues are ordered by construction (ea >= eb), so
+// the stable sort is the place pz of the out-of-plane strain, and the way back picks by pz as well: no indexed arrays.
+// An edge is not tested against its lower bound g_lo <= L: den_e (L_e - g_lo) = den_s (L_s - g_lo), so the failed test of the
+// face has decided it, and a second test could only send a point within rounding of the face's boundary to the apex.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ double pick3(int pz, double v0, double v1, double v2) { return pz == 0 ? v0 : (pz == 1 ? v1 : v2); }
+
+__device__ __forceinline__ int mc_return_map(const double e[3], const double z[4], double p[4],
+                                             double G, double K, double sp, double c, bool accept,
+                                             double s[4], double d[6]) {
+    const double Et0 = (e[0] + z[0]) - p[0];
+    const double Et1 = (e[1] + z[1]) - p[1];
+    const double Et2 = (e[2] + z[2]) - p[2];
+    const double Et3 = (0.0 + z[3]) - p[3];
+    const double lam = K - 2.0 * G / 3.0;
+    const double G2 = 2.0 * G;
+    const double tr = Et0 + Et1 + Et3;
+    // in-plane eigen-decomposition
+    const double m = (Et0 + Et1) / 2.0, dd = (Et0 - Et1) / 2.0, h = Et2 / 2.0;
+    const double r = sqrt(dd * dd + h * h);
+    const double ea = m + r, eb = m - r, ez = Et3;
+    const bool rpos = r > 0.0;
+    const double rs = rpos ? r : 1.0;
+    const double ca = rpos ? dd / rs : 1.0, sa = rpos ? h / rs : 0.0;
+    const double Pa0 = (1.0 + ca) / 2.0, Pa1 = (1.0 - ca) / 2.0, Pa2 = sa / 2.0;
+    const double Pb0 = Pa1, Pb1 = Pa0, Pb2 = -Pa2;
+    // stable descending sort: the place of ez
+    const int pz = ez > ea ? 0 : (ez > eb ? 1 : 2);
+    const double e1 = pick3(pz, ez, ea, ea), e2 = pick3(pz, ea, ez, eb), e3 = pick3(pz, eb, eb, ez);
+    // trial values and the branch
+    const double cphi = sqrt(1.0 - sp * sp);
+    const double ltr = lam * tr;
+    const double k0 = 2.0 * lam * sp * tr - 2.0 * c * cphi;
+    const double f = G2 * ((1.0 + sp) * e1 - (1.0 - sp) * e3) + k0;
+    const double g_sl = (e1 - e2) / (1.0 + sp), g_sr = (e2 - e3) / (1.0 - sp);
+    const double ls2 = 4.0 * lam * sp * sp;
+    const double den_s = ls2 + 4.0 * G * (1.0 + sp * sp);
+    const double L_s = f / den_s;
+    const bool left = g_sl < g_sr;
+    const double f_e = (left ? G * ((1.0 + sp) * (e1 + e2) - 2.0 * (1.0 - sp) * e3)
+                             : G * (2.0 * (1.0 + sp) * e1 - (1.0 - sp) * (e2 + e3))) + k0;
+    const double den_e = ls2 + (left ? G * ((1.0 + sp) * (1.0 + sp)) + G2 * ((1.0 - sp) * (1.0 - sp))
+                                     : G2 * ((1.0 + sp) * (1.0 + sp)) + G * ((1.0 - sp) * (1.0 - sp)));
+    const double L_e = f_e / den_e;
+    const double g_lo = left ? g_sl : g_sr;
+    const double g_hi = left ? (e1 + e2 - 2.0 * e3) / (3.0 - sp) : (2.0 * e1 - e2 - e3) / (3.0 + sp);
+    const int branch = f <= 0.0 ? 0 : (L_s <= g_lo ? 1 : (L_e <= g_hi ? (left ? 2 : 3) : 4));
+    const bool ml = branch == 2, mr = branch == 3;
+    // the branch's normal, strains and multiplier
+    const double n1 = ml ? (1.0 + sp) / 2.0 : 1.0 + sp;
+    const double n2 = ml ? (1.0 + sp) / 2.0 : (mr ? -(1.0 - sp) / 2.0 : 0.0);
+    const double n3 = mr ? -(1.0 - sp) / 2.0 : -(1.0 - sp);
+    const double m12 = (e1 + e2) / 2.0, m23 = (e2 + e3) / 2.0;
+    const double t1 = ml ? m12 : e1, t2 = ml ? m12 : (mr ? m23 : e2), t3 = mr ? m23 : e3;
+    const double L = branch == 0 ? 0.0 : (branch == 1 ? L_s : L_e);
+    const double ls = 2.0 * lam * sp;
+    const double a1 = G2 * n1 + ls, a2 = G2 * n2 + ls, a3 = G2 * n3 + ls;
+    double sig1 = (ltr + G2 * t1) - L * a1, sig2 = (ltr + G2 * t2) - L * a2, sig3 = (ltr + G2 * t3) - L * a3;
+    const double iden = branch == 0 ? 0.0 : 1.0 / (branch == 1 ? den_s : den_e);
+    double D11 = lam + G * (ml ? 1.0 : 2.0) - a1 * a1 * iden;
+    double D12 = lam + G * (ml ? 1.0 : 0.0) - a1 * a2 * iden;
+    double D13 = lam - a1 * a3 * iden;
+    double D22 = lam + G * ((ml || mr) ? 1.0 : 2.0) - a2 * a2 * iden;
+    double D23 = lam + G * (mr ? 1.0 : 0.0) - a2 * a3 * iden;
+    double D33 = lam + G * (mr ? 1.0 : 2.0) - a3 * a3 * iden;
+    if (branch == 4) {
+        sig1 = sig2 = sig3 = c * cphi / sp;
+        D11 = D12 = D13 = D22 = D23 = D33 = 0.0;
+    }
+    // back to (a, b, z) and to the Cartesian frame
+    const double sig_a = pick3(pz, sig2, sig1, sig1), sig_b = pick3(pz, sig3, sig3, sig2), sig_z = pick3(pz, sig1, sig2, sig3);
+    const double Daa = pick3(pz, D22, D11, D11), Dbb = pick3(pz, D33, D33, D22), Dab = pick3(pz, D23, D13, D12);
+    s[0] = sig_a * Pa0 + sig_b * Pb0;
+    s[1] = sig_a * Pa1 + sig_b * Pb1;
+    s[2] = sig_a * Pa2 + sig_b * Pb2;
+    s[3] = sig_z;
+    const double theta = rpos ? (sig_a - sig_b) / (2.0 * rs) : Daa - Dab;
+#define FEP_MC_T(i, j, I) \
+    (Daa * (Pa##i * Pa##j) + Dab * (Pa##i * Pb##j + Pb##i * Pa##j) + Dbb * (Pb##i * Pb##j) + theta * ((I) - Pa##i * Pa##j - Pb##i * Pb##j))
+    d[0] = FEP_MC_T(0, 0, 1.0); d[1] = FEP_MC_T(0, 1, 0.0); d[2] = FEP_MC_T(0, 2, 0.0);
+    d[3] = FEP_MC_T(1, 1, 1.0); d[4] = FEP_MC_T(1, 2, 0.0); d[5] = FEP_MC_T(2, 2, 0.5);
+#undef FEP_MC_T
+    if (accept && branch != 0) {
+        // the plastic strain takes what the elastic strain of the new stress leaves of the trial strain
+        const double th = (sig_a + sig_b + sig_z) / (3.0 * K);
+        const double dpa = ea - (sig_a - lam * th) / G2, dpb = eb - (sig_b - lam * th) / G2, dpz = ez - (sig_z - lam * th) / G2;
+        p[0] += dpa * Pa0 + dpb * Pb0;
+        p[1] += dpa * Pa1 + dpb * Pb1;
+        p[2] += 2.0 * (dpa * Pa2 + dpb * Pb2);
+        p[3] += dpz;
+    }
+    return branch;
+}
+
+// The return map of a model other than Drucker-Prager, and the counter its branch goes to (count_branches: 1 -> counts[0],
+// 2 -> counts[1]): von Mises counts its plastic points, Mohr-Coulomb face and edges together and the apex apart.
+template <int MODEL>
+__device__ __forceinline__ int model_return_map(const double e[3], const double z[4], double p[4],
+                                                double G, double K, double m3, double m4, bool accept,
+                                                double s[4], double d[6]) {
+    static_assert(MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC, "model");
+    if constexpr (MODEL == FEP_MODEL_MC) return mc_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+    else return vm_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+}
+template <int MODEL>
+__device__ __forceinline__ int count_class(int branch) {
+    if constexpr (MODEL == FEP_MODEL_MC) return branch == 0 ? 0 : (branch == 4 ? 2 : 1);
+    else return branch;
+}
+
 // Smooth / apex counters (the numbers the reference logs at DP:730).  Wave ballot -> LDS -> per
 // workgroup either a plain store into blk_counts[blockIdx.x] (summed by counts_reduce_kernel; no
 // global atomics at all) or, for the mesh-free entry point, one global atomic per workgroup.
@@ -288,13 +408,14 @@ return_map_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64_t 
     count_branches(branch, nullptr, blk_counts);      // per-workgroup counters, summed by counts_reduce_kernel (no global atomics)
 }
 
-// The same for the von Mises model: `hard` / `yld` = a / Y per point (vm_return_map)
-__global__ void __launch_bounds__(kBlock)
-return_map_vm_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, E0 e0,
-                     double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
-                     const double* __restrict__ hard, const double* __restrict__ yld, int accept,
-                     double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
-                     uint2* blk_counts) {
+// The same for the other models (model_return_map): `m3` / `m4` = a / Y of von Mises or sin_phi / c of Mohr-Coulomb per point
+template <int MODEL>
+__device__ __forceinline__ void
+return_map_model_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, const E0& e0,
+                      double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
+                      const double* __restrict__ hard, const double* __restrict__ yld, int accept,
+                      double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
+                      uint2* blk_counts) {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (k < n) {
@@ -302,12 +423,25 @@ return_map_vm_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64
         double p[4] = {0.0, 0.0, 0.0, 0.0};
         if (ep) { p[0] = ep[k]; p[1] = ep[n + k]; p[2] = ep[2 * n + k]; p[3] = ep[3 * n + k]; }
         double s[4], d[6];
-        branch = vm_return_map(ev, e0.v, p, shear[k], bulk[k], hard[k], yld[k], accept != 0, s, d);
+        branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], hard[k], yld[k], accept != 0, s, d);
         store_point(k, n, s, d, branch, S, DS, indp);
         if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
     }
-    count_branches(branch, nullptr, blk_counts);
+    count_branches(count_class<MODEL>(branch), nullptr, blk_counts);
 }
+
+#define FEP_RETURN_MAP_ARGS                                                                                              \
+    int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, E0 e0, double* __restrict__ ep,                    \
+    const double* __restrict__ shear, const double* __restrict__ bulk, const double* __restrict__ m3,                    \
+    const double* __restrict__ m4, int accept, double* __restrict__ S, double* __restrict__ DS,                          \
+    uint8_t* __restrict__ indp, uint2* blk_counts
+__global__ void __launch_bounds__(kBlock) return_map_vm_kernel(FEP_RETURN_MAP_ARGS) {
+    return_map_model_body<FEP_MODEL_VM>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
+__global__ void __launch_bounds__(kBlock) return_map_mc_kernel(FEP_RETURN_MAP_ARGS) {
+    return_map_model_body<FEP_MODEL_MC>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
+#undef FEP_RETURN_MAP_ARGS
 
 // ---------------------------------------------------------------------------------------
 // Geometry (setup, once): Jacobian, dphi_1, dphi_2, weight.  DP:530-546, 585.
@@ -1233,15 +1367,17 @@ p1_point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __r
     count_branches(branch, nullptr, blk_counts);
 }
 
-// Von Mises step of a P1 context (FEP_MODEL_VM), stage A: p1_point_kernel with vm_return_map — one lane per element, same
-// geometry and strain; `hard` / `yld` = a / Y per point (MatU: eta / c hold them).  Stage B is the context's own assembly.
-__global__ void __launch_bounds__(kBlock)
-p1_point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, P1Tab tab,
-                   const double* __restrict__ U, E0 e0, double* __restrict__ ep,
-                   const double* __restrict__ shear, const double* __restrict__ bulk,
-                   const double* __restrict__ hard, const double* __restrict__ yld, MatU mu, int accept,
-                   double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-                   uint8_t* __restrict__ indp, uint2* blk_counts) {
+// Von Mises or Mohr-Coulomb step of a P1 context (FEP_MODEL_VM / _MC), stage A: p1_point_kernel with the model's return map —
+// one lane per element, same geometry and strain; `hard` / `yld` = a / Y or sin_phi / c per point (MatU: eta / c hold them).
+// Stage B is the context's own assembly.
+template <int MODEL>
+__device__ __forceinline__ void
+p1_point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, const P1Tab& tab,
+                    const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
+                    const double* __restrict__ shear, const double* __restrict__ bulk,
+                    const double* __restrict__ hard, const double* __restrict__ yld, const MatU& mu, int accept,
+                    double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+                    uint8_t* __restrict__ indp, uint2* blk_counts) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (e < n_e) {
@@ -1263,13 +1399,26 @@ p1_point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* 
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[e], m_bu = mu.on ? mu.bulk : bulk[e];
         const double m_a = mu.on ? mu.eta : hard[e], m_y = mu.on ? mu.c : yld[e];
-        branch = vm_return_map(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
+        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
         store_point(e, n_e, s, d, branch, S, DS, indp);
         if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
         if (accept && ep && branch) { ep[e] = p[0]; ep[n_e + e] = p[1]; ep[2 * n_e + e] = p[2]; ep[3 * n_e + e] = p[3]; }
     }
-    count_branches(branch, nullptr, blk_counts);
+    count_branches(count_class<MODEL>(branch), nullptr, blk_counts);
 }
+
+#define FEP_P1_POINT_ARGS                                                                                                \
+    int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, P1Tab tab, const double* __restrict__ U, \
+    E0 e0, double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,                   \
+    const double* __restrict__ m3, const double* __restrict__ m4, MatU mu, int accept, double* __restrict__ Eout,        \
+    double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp, uint2* blk_counts
+__global__ void __launch_bounds__(kBlock) p1_point_vm_kernel(FEP_P1_POINT_ARGS) {
+    p1_point_model_body<FEP_MODEL_VM>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+}
+__global__ void __launch_bounds__(kBlock) p1_point_mc_kernel(FEP_P1_POINT_ARGS) {
+    p1_point_model_body<FEP_MODEL_MC>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+}
+#undef FEP_P1_POINT_ARGS
 
 __global__ void __launch_bounds__(kBlock)
 p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, const int32_t* __restrict__ perm2,
@@ -1922,15 +2071,15 @@ __device__ __forceinline__ void inverse_jacobian(double j11, double j12, double 
     w = fabs(det) * wfq;                                 // DP:585
 }
 
-template <int NP, int NQ>
-__global__ void __launch_bounds__(kBlock)
-point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
-                const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
-                const double* __restrict__ U, E0 e0, double* __restrict__ ep,
-                const double* __restrict__ shear, const double* __restrict__ bulk,
-                const double* __restrict__ hard, const double* __restrict__ yld, MatU mu, int accept,
-                double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-                uint8_t* __restrict__ indp, uint2* blk_counts) {
+template <int MODEL, int NP, int NQ>
+__device__ __forceinline__ void
+point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
+                 const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
+                 const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
+                 const double* __restrict__ shear, const double* __restrict__ bulk,
+                 const double* __restrict__ hard, const double* __restrict__ yld, const MatU& mu, int accept,
+                 double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+                 uint8_t* __restrict__ indp, uint2* blk_counts) {
     __shared__ double t1[NP * NQ], t2[NP * NQ], tw[NQ];
     for (int i = threadIdx.x; i < NP * NQ; i += kBlock) { t1[i] = dh1[i]; t2[i] = dh2[i]; }
     for (int i = threadIdx.x; i < NQ; i += kBlock) tw[i] = wf[i];
@@ -1976,13 +2125,31 @@ point_vm_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __r
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[k], m_bu = mu.on ? mu.bulk : bulk[k];
         const double m_a = mu.on ? mu.eta : hard[k], m_y = mu.on ? mu.c : yld[k];
-        branch = vm_return_map(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
+        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
         store_point(k, n_int, s, d, branch, S, DS, indp);
         if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
         if (accept && ep && branch) { ep[k] = p[0]; ep[n_int + k] = p[1]; ep[2 * n_int + k] = p[2]; ep[3 * n_int + k] = p[3]; }
     }
-    count_branches(branch, nullptr, blk_counts);
+    count_branches(count_class<MODEL>(branch), nullptr, blk_counts);
 }
+
+#define FEP_POINT_ARGS                                                                                                   \
+    int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, const double* __restrict__ dh1,        \
+    const double* __restrict__ dh2, const double* __restrict__ wf, const double* __restrict__ U, E0 e0,                  \
+    double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,                          \
+    const double* __restrict__ m3, const double* __restrict__ m4, MatU mu, int accept, double* __restrict__ Eout,        \
+    double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp, uint2* blk_counts
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock) point_vm_kernel(FEP_POINT_ARGS) {
+    point_model_body<FEP_MODEL_VM, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                           indp, blk_counts);
+}
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock) point_mc_kernel(FEP_POINT_ARGS) {
+    point_model_body<FEP_MODEL_MC, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                           indp, blk_counts);
+}
+#undef FEP_POINT_ARGS
 
 template <int NP, int NQ, int TPB>
 __global__ void __launch_bounds__(TPB)

@@ -187,7 +187,19 @@ def construct_constitutive_problem_vm(e, ep_prev, shear, bulk, a, Y, apply_plast
     return {'s': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'], 'ep': r['ep'], 'n_plast': r['n_smooth']}
 
 
-MODELS = {'dp': 0, 'vm': 1}                                # FEP_MODEL_DP, FEP_MODEL_VM
+def construct_constitutive_problem_mc(e, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain=False, e0=None, device=None):
+    """The third material model, no counterpart in the reference: associative, perfectly plastic Mohr-Coulomb, the return
+    map in principal stresses with its spectral tangent (include/fep.h, fep_return_map_mc_host).  `sin_phi` in (0, 1) the
+    sine of the friction angle, `c` > 0 the cohesion, per point; the other arguments as construct_constitutive_problem,
+    `e0` an optional (4,1) initial strain.  Returns {'s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex'}: 'n_smooth' counts the
+    points on the smooth face and on the two edges, 'n_apex' those at the apex; with `apply_plastic_strain`, `ep_prev` is
+    updated in place and returned as 'ep'."""
+    r = _return_map(e, e0, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain, tsx=False, device=device,
+                    entry='fep_return_map_mc_host')
+    return {k: r[k] for k in ('s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex')}
+
+
+MODELS = {'dp': 0, 'vm': 1, 'mc': 2}                       # FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC
 
 
 # ---------------------------------------------------------------------------------------
@@ -287,9 +299,10 @@ class MeshContext:
         _lib.check(_lib.lib().fep_ctx_set_materials_host(self._h, *[_lib.ptr(v) for v in a]), 'fep_ctx_set_materials_host')
 
     def set_model(self, model):
-        """'dp' (Drucker-Prager, the default) or 'vm' (von Mises with linear kinematic hardening: `set_materials` then takes
-        (shear, bulk, a, Y), the results carry the plastic count in 'n_smooth' and 'n_apex' is 0).  Before or after
-        `set_materials`."""
+        """'dp' (Drucker-Prager, the default), 'vm' (von Mises with linear kinematic hardening: `set_materials` then takes
+        (shear, bulk, a, Y), the results carry the plastic count in 'n_smooth' and 'n_apex' is 0) or 'mc' (Mohr-Coulomb:
+        `set_materials` takes (shear, bulk, sin_phi, c), 'n_smooth' counts face and edges, 'n_apex' the apex).  Before or
+        after `set_materials`."""
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}")
         _lib.check(_lib.lib().fep_ctx_set_model(self._h, MODELS[model]), 'fep_ctx_set_model')

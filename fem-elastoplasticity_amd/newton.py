@@ -337,10 +337,21 @@ def _context_maker(context_factory, device):
     return context_factory or (lambda *a: MeshContext(*a, device=device))
 
 
-def _footing_setup(element_type, level, n_cells, size_xy, make_context):
-    """Mesh and context (materials set) of the strip-footing benchmark (DP:910-945), `c0`, and the times for the log."""
+def prandtl_nc(phi):
+    """Prandtl's bearing-capacity factor of a strip footing on a weightless Mohr-Coulomb half plane: the limit pressure
+    over the cohesion, N_c = (tan^2(45 deg + phi/2) e^(pi tan phi) - 1) / tan phi."""
+    return (np.tan(np.pi / 4 + phi / 2) ** 2 * np.exp(np.pi * np.tan(phi)) - 1) / np.tan(phi)
+
+
+def _footing_setup(element_type, level, n_cells, size_xy, make_context, model='dp', friction_angle=None, cohesion=None):
+    """Mesh and context (materials set) of the strip-footing benchmark (DP:910-945), `c0`, and the times for the log.
+    `model='mc'`: a Mohr-Coulomb context on (shear0, bulk0, sin(phi), c0) instead of the matched Drucker-Prager cone."""
+    if model not in ('dp', 'mc'):
+        raise ValueError("model must be 'dp' or 'mc'")
     t = _coerce(element_type)
     young, poisson, c0, phi = 1e7, 0.48, 450, np.pi / 9                                   # DP:910-933
+    phi = phi if friction_angle is None else float(friction_angle)
+    c0 = c0 if cohesion is None else cohesion
     shear0 = young / (2 * (1 + poisson))
     bulk0 = young / (3 * (1 - 2 * poisson))
     eta0 = 3 * np.tan(phi) / np.sqrt(9 + 12 * (np.tan(phi)) ** 2)
@@ -349,24 +360,45 @@ def _footing_setup(element_type, level, n_cells, size_xy, make_context):
     mesh = square_mesh(size_xy * 2 ** level if n_cells is None else n_cells, t, size_xy)  # DP:945
     t_setup.append(time.perf_counter())
     ctx = make_context(mesh['elements'], mesh['coordinates'], *element_tables(t))
-    ctx.set_materials(shear0, bulk0, eta0, c_0)
+    if model == 'mc':
+        ctx.set_model('mc')
+        ctx.set_materials(shear0, bulk0, np.sin(phi), c0)
+    else:
+        ctx.set_materials(shear0, bulk0, eta0, c_0)
     t_setup.append(time.perf_counter())
     return mesh, ctx, c0, t_setup
 
 
 def solve_strip_footing(element_type='P1', level=1, n_cells=None, size_xy=10, max_steps=None, zeta_max=1.0,
                         device=None, log=None, context_factory=None, linear_solver='direct', pcg_rtol=1e-11,
-                        keep_U=True, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None):
+                        keep_U=True, pcg_forcing=None, pcg_forcing_cap=1e-4, pcg_inexact_rtol=None, model='dp',
+                        friction_angle=None, cohesion=None):
     """Strip-footing benchmark of Plasticity2D_DP (DP:901-1131).  `level` as in the reference
     (N = size_xy * 2**level cells per side) or `n_cells` directly.  Returns a dict with the load history
     ('zeta', 'pressure'), the accepted displacements 'U' (list of (2,n_n)), final 'Ep', counters.
     `context_factory(elements, coordinates, dhatp1, dhatp2, wf)` may supply another object with MeshContext's
-    `set_materials / step / geometry / close` (the tests drive the same loop with their CPU checker that way)."""
-    mesh, ctx, c0, t_setup = _footing_setup(element_type, level, n_cells, size_xy, _context_maker(context_factory, device))
+    `set_materials / step / geometry / close` (the tests drive the same loop with their CPU checker that way).
+
+    `model='dp'` (the default) is the reference's run: the Drucker-Prager cone matched in plane strain to the friction
+    angle (20 degrees) and cohesion (450) of the benchmark.  `model='mc'` runs the same displacement-controlled loop on a
+    Mohr-Coulomb context (MeshContext.set_model, also asked of a `context_factory`'s object) with the materials
+    (shear0, bulk0, sin(phi), c0) from the same Young's modulus, Poisson's ratio, `friction_angle` (radians) and
+    `cohesion`; the two arguments override the benchmark's values for either model.  'pressure' stays normalised by the
+    cohesion, so for Mohr-Coulomb it tends to Prandtl's limit N_c = (tan^2(45 deg + phi/2) e^(pi tan phi) - 1) / tan phi
+    from above as the mesh is refined (14.83 at 20 degrees; coarse meshes overshoot it).  The result's 'prandtl_nc' holds
+    that number, and the log shows it beside the last pressure."""
+    mesh, ctx, c0, t_setup = _footing_setup(element_type, level, n_cells, size_xy, _context_maker(context_factory, device),
+                                            model, friction_angle, cohesion)
+    nc = prandtl_nc(np.pi / 9 if friction_angle is None else float(friction_angle)) if model == 'mc' else None
     with closing(ctx), closing(make_ops(ctx, mesh['Q'].flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing,
                                         pcg_forcing_cap, pcg_inexact_rtol)) as ops:
-        return _strip_footing(mesh=mesh, ctx=ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
+        hist = _strip_footing(mesh=mesh, ctx=ctx, ops=ops, c0=c0, t_setup=t_setup, max_steps=max_steps,
                               zeta_max=zeta_max, keep_U=keep_U, log=log)
+    if nc is not None:
+        hist['prandtl_nc'] = float(nc)
+        if log and hist['pressure']:
+            log(f'last pressure / c0 = {hist["pressure"][-1]:.6g}; Prandtl N_c = {nc:.6g}')
+    return hist
 
 
 def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, log):

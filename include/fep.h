@@ -56,6 +56,7 @@ extern "C" {
 /* material models of a mesh context (fep_ctx_set_model) */
 #define FEP_MODEL_DP 0        /* perfectly plastic Drucker-Prager (the reference's law; the default) */
 #define FEP_MODEL_VM 1        /* von Mises with linear kinematic hardening (no reference counterpart) */
+#define FEP_MODEL_MC 2        /* associative, perfectly plastic Mohr-Coulomb (no reference counterpart) */
 
 typedef struct fep_ctx fep_ctx;
 
@@ -144,6 +145,51 @@ int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
                           int accept,
                           double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
 
+/* ---- third material model: associative, perfectly plastic Mohr-Coulomb, mesh-free ------
+ * No reference counterpart.  Plane strain, the closest-point return map in principal stresses (elastic, smooth face, two
+ * edges, apex) with its spectral tangent; layout, strides, e0_h, ep_prev, outputs and the scratch rule of counts_d
+ * exactly as fep_return_map_*, with the parameters
+ *   sin_phi (n_int) sine of the friction angle, in (0, 1)        c (n_int) cohesion, > 0
+ * in the places of eta and c (the bounds are a precondition, as eta > 0 is for Drucker-Prager).  Yield function,
+ * tension positive, sig1 >= sig2 >= sig3:  (1+s) sig1 - (1-s) sig3 - 2 c cos(phi) <= 0,  s = sin_phi, cos = sqrt(1-s^2).
+ * Per point, with lam = K - 2G/3:
+ *     Et = (e, 0) + z - p                    tr = Et0 + Et1 + Et3
+ *     m = (Et0+Et1)/2, dd = (Et0-Et1)/2, h = Et2/2, r = sqrt(dd^2 + h^2)      ea = m + r, eb = m - r, ez = Et3
+ *     ca = dd/r, sa = h/r (1, 0 at r = 0)    Pa = ((1+ca)/2, (1-ca)/2, sa/2), Pb = ((1-ca)/2, (1+ca)/2, -sa/2)
+ *     (e1, e2, e3) = (ea, eb, ez) sorted descending and stable
+ *     f = 2G[(1+s)e1 - (1-s)e3] + 2 lam s tr - 2c cos;          f <= 0: elastic (branch 0), L = 0
+ *     g_sl = (e1-e2)/(1+s), g_sr = (e2-e3)/(1-s), g_la = (e1+e2-2e3)/(3-s), g_ra = (2e1-e2-e3)/(3+s)
+ *   Every plastic branch but the apex is one formula on its normal n and its strains t:
+ *     A n = 2G n + 2 lam s,  den = n.A n = 2G|n|^2 + 4 lam s^2,  L = (2G n.e + 2 lam s tr - 2c cos)/den,
+ *     sig = lam tr + 2G t - L A n,        dsig/deps = lam + G M - (A n)(A n)^T/den
+ *     1 smooth      L <= min(g_sl, g_sr):             n = (1+s, 0, -(1-s)),          t = e,  M = 2I
+ *     2 left edge   g_sl < g_sr,  L <= g_la:           n = ((1+s)/2, (1+s)/2, -(1-s)), t = ((e1+e2)/2, (e1+e2)/2, e3),
+ *                                                     M = [[1,1,0],[1,1,0],[0,0,2]]                      (sig1 = sig2)
+ *     3 right edge  g_sl >= g_sr, L <= g_ra:           n = (1+s, -(1-s)/2, -(1-s)/2),  t = (e1, (e2+e3)/2, (e2+e3)/2),
+ *                                                     M = [[2,0,0],[0,1,1],[0,1,1]]                      (sig2 = sig3)
+ *     4 apex        otherwise:                        sig_i = c cos/s,  dsig/deps = 0
+ *   Back through the permutation to (sig_a, sig_b, sig_z) and D over (a, b, z):
+ *     (s11, s22, s12) = sig_a Pa + sig_b Pb,  s33 = sig_z
+ *     ds = D_aa Pa Pa^T + D_ab (Pa Pb^T + Pb Pa^T) + D_bb Pb Pb^T + theta (diag(1, 1, 1/2) - Pa Pa^T - Pb Pb^T),
+ *     theta = (sig_a - sig_b)/(2r)  (D_aa - D_ab at r = 0)                                (rows / columns 11, 22, 12)
+ *   accept, plastic points:  th = (sig_a+sig_b+sig_z)/(3K),  dp_i = e_i - (sig_i - lam th)/(2G) over (a, b, z),
+ *     p += (dp_a Pa0 + dp_b Pb0,  dp_a Pa1 + dp_b Pb1,  2 (dp_a Pa2 + dp_b Pb2),  dp_z)
+ * (An edge's L >= g_sl resp. g_sr needs no test: den (L - g) of the edge equals den (L - g) of the failed smooth test.)
+ * ind_p = (branch != 0); counts = {smooth face + both edges, apex}.  ds is symmetric.  theta loses the digits of
+ * max|Et| / r as r -> 0, and a point within rounding of a branch boundary may take either side (s is continuous there). */
+int fep_return_map_mc_host(int device_id, int64_t n_int,
+                           const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                           const double* e0_h, double* ep_prev_h,
+                           const double* shear_h, const double* bulk_h, const double* sin_phi_h, const double* c_h,
+                           int accept,
+                           double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h);
+int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
+                          const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                          const double* e0_h, double* ep_prev_d,
+                          const double* shear_d, const double* bulk_d, const double* sin_phi_d, const double* c_d,
+                          int accept,
+                          double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
+
 /* ---- a6/a7: mesh context (static operands of the hot path) ----------------------------
  * Replaces the geometry / index part of get_elastic_stiffness_matrix
  * (DP:491-601, TSX:432-542, EL:368-477): Jacobians, dphi_1/dphi_2, weight = |det|*wf,
@@ -184,9 +230,11 @@ int fep_ctx_pattern_host(const fep_ctx* ctx, int32_t* indptr_h /* n_dof+1 */, in
  * read the arrays; results are bitwise the same either way. */
 int fep_ctx_set_materials_host(fep_ctx* ctx, const double* shear_h, const double* bulk_h,
                                const double* eta_h, const double* c_h);
-/* The material model of the context's steps: FEP_MODEL_DP (the default) or FEP_MODEL_VM; may be called before or after
- * fep_ctx_set_materials_host.  On a von Mises context the third and fourth arrays of fep_ctx_set_materials_host are a
- * and Y (fep_return_map_vm_*; the constant-parameter shortcut applies as for Drucker-Prager), and fep_step_* keep their
+/* The material model of the context's steps: FEP_MODEL_DP (the default), FEP_MODEL_VM or FEP_MODEL_MC; may be called
+ * before or after fep_ctx_set_materials_host.  On a von Mises context the third and fourth arrays of
+ * fep_ctx_set_materials_host are a and Y (fep_return_map_vm_*), on a Mohr-Coulomb context sin_phi and c
+ * (fep_return_map_mc_*; counts = {smooth face + both edges, apex}).  What follows holds for both alike.  The
+ * constant-parameter shortcut applies as for Drucker-Prager, and fep_step_* keep their
  * signature and every output: they run the model's point kernel (geometry from the node coordinates, strain, return map;
  * s / ds to the caller's arrays or a scratch of the context) and then what fep_assemble_dev launches for the context.
  * counts = {number of plastic points, 0}.  The call allocates that scratch itself, so fep_step_dev on a von Mises

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Step times of the two material models side by side, per element type: the fused Drucker-Prager step against the von Mises
-step (point kernel + the route's assembly from ds / s), each as the K,F-only step of a Newton iterate and with every point
-output.  HIP events around batches of steps, the four variants of a type interleaved pass by pass in one process (what
+"""Step times of the three material models side by side, per element type: the fused Drucker-Prager step against the von
+Mises and the Mohr-Coulomb step (point kernel + the route's assembly from ds / s), each as the K,F-only step of a Newton iterate
+and with every point output.  HIP events around batches of steps, the six variants of a type interleaved pass by pass in one process (what
 differs between them is then not the box or the session).  Prints one JSON line.
     python tools/model_bench.py [--types P1,P2,Q1,Q2,P4] [--steps 20] [--passes 5] [--scale 1.0]
 Mesh sizes as tools/elem_bench.py is run (cells per side: 708, P4 354); --scale shrinks them for a quick look."""
@@ -18,6 +18,7 @@ import bench  # noqa: E402
 import torch  # noqa: E402
 
 fep = importlib.import_module('fem-elastoplasticity_amd')
+MODELS = ('dp', 'vm', 'mc')
 CELLS = {'P1': 708, 'P2': 708, 'Q1': 708, 'Q2': 708, 'P4': 354}
 
 
@@ -38,11 +39,13 @@ def time_type(t, N, steps, passes):
     Uh = bench.displacement(coord)
     U = torch.from_numpy(np.ascontiguousarray(Uh.reshape(-1, order='F'))).to(dev)
     ctxs = {}
-    for model in ('dp', 'vm'):
+    # the same shear and bulk; the von Mises radius sqrt(2) c is the Drucker-Prager cone's at zero pressure, the Mohr-Coulomb
+    # friction angle and cohesion are those the cone was matched to (bench.dp_materials)
+    third_fourth = {'dp': (eta, c), 'vm': (0.05 * sh, np.sqrt(2) * c), 'mc': (np.sin(np.pi / 9), 450.0)}
+    for model in MODELS:
         ctx = fep.MeshContext(elem, coord)
         ctx.set_model(model)
-        # the same shear and bulk; the von Mises radius sqrt(2) c is the Drucker-Prager cone's at zero pressure
-        ctx.set_materials(sh, bu, eta if model == 'dp' else 0.05 * sh, c if model == 'dp' else np.sqrt(2) * c)
+        ctx.set_materials(sh, bu, *third_fourth[model])
         ctxs[model] = ctx
     n = ctxs['dp'].n_int
     f64 = dict(dtype=torch.float64, device=dev)
@@ -55,7 +58,7 @@ def time_type(t, N, steps, passes):
         kw = dict(s=S.data_ptr(), ds=DS.data_ptr(), ind_p=ind.data_ptr()) if full else {}
         ctxs[model].step_dev(st, U.data_ptr(), ep=Ep.data_ptr(), k_data=Kd.data_ptr(), f_out=F.data_ptr(),
                              counts=cnt.data_ptr(), **kw)
-    variants = [(m, full) for m in ('dp', 'vm') for full in (False, True)]
+    variants = [(m, full) for m in MODELS for full in (False, True)]
     plastic = {}
     for m, full in variants:
         for _ in range(3):
