@@ -190,11 +190,15 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
     const double tr = Et0 + Et1 + Et3;
     // in-plane eigen-decomposition
     const double m = (Et0 + Et1) / 2.0, dd = (Et0 - Et1) / 2.0, h = Et2 / 2.0;
-    const double r = sqrt(dd * dd + h * h);
+    // r = sqrt(dd^2 + h^2) with the squares kept out of the denormal range: below 2^-500 both are scaled by 2^600, which is exact
+    const bool tiny = fmax(fabs(dd), fabs(h)) < 0x1p-500;
+    const double dds = tiny ? dd * 0x1p+600 : dd, hs = tiny ? h * 0x1p+600 : h;
+    const double rsc = sqrt(dds * dds + hs * hs);
+    const double r = tiny ? rsc * 0x1p-600 : rsc;
     const double ea = m + r, eb = m - r, ez = Et3;
-    const bool rpos = r > 0.0;
-    const double rs = rpos ? r : 1.0;
-    const double ca = rpos ? dd / rs : 1.0, sa = rpos ? h / rs : 0.0;
+    const bool rpos = rsc > 0.0;
+    const double rs = rpos ? rsc : 1.0;
+    const double ca = rpos ? dds / rs : 1.0, sa = rpos ? hs / rs : 0.0;
     const double Pa0 = (1.0 + ca) / 2.0, Pa1 = (1.0 - ca) / 2.0, Pa2 = sa / 2.0;
     const double Pb0 = Pa1, Pb1 = Pa0, Pb2 = -Pa2;
     // stable descending sort: the place of ez
@@ -247,7 +251,11 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
     s[1] = sig_a * Pa1 + sig_b * Pb1;
     s[2] = sig_a * Pa2 + sig_b * Pb2;
     s[3] = sig_z;
-    const double theta = rpos ? (sig_a - sig_b) / (2.0 * rs) : Daa - Dab;
+    // theta = (sig_a - sig_b) / (2r) from the difference itself, sig_a - sig_b = 2G [(t_a - t_b) - L (n_a - n_b)] (lam tr and 2 lam sp
+    // cancel): a pair that no edge has merged has t_a - t_b = 2r, so an elastic point gives 2G and a merged (a, b) pair 0, exactly
+    const double ta = pick3(pz, t2, t1, t1), tb = pick3(pz, t3, t3, t2), na = pick3(pz, n2, n1, n1), nb = pick3(pz, n3, n3, n2);
+    const double dt = (ml || mr) ? ta - tb : 2.0 * r;
+    const double theta = branch == 4 ? 0.0 : (rpos ? G * ((dt - L * (na - nb)) / r) : Daa - Dab);
 #define FEP_MC_T(i, j, I) \
     (Daa * (Pa##i * Pa##j) + Dab * (Pa##i * Pb##j + Pb##i * Pa##j) + Dbb * (Pb##i * Pb##j) + theta * ((I) - Pa##i * Pa##j - Pb##i * Pb##j))
     d[0] = FEP_MC_T(0, 0, 1.0); d[1] = FEP_MC_T(0, 1, 0.0); d[2] = FEP_MC_T(0, 2, 0.0);

@@ -155,6 +155,7 @@ int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
  * Per point, with lam = K - 2G/3:
  *     Et = (e, 0) + z - p                    tr = Et0 + Et1 + Et3
  *     m = (Et0+Et1)/2, dd = (Et0-Et1)/2, h = Et2/2, r = sqrt(dd^2 + h^2)      ea = m + r, eb = m - r, ez = Et3
+ *     (where max(|dd|, |h|) < 2^-500, dd and h are scaled by 2^600 for r, ca and sa: the squares stay out of the denormal range)
  *     ca = dd/r, sa = h/r (1, 0 at r = 0)    Pa = ((1+ca)/2, (1-ca)/2, sa/2), Pb = ((1-ca)/2, (1+ca)/2, -sa/2)
  *     (e1, e2, e3) = (ea, eb, ez) sorted descending and stable
  *     f = 2G[(1+s)e1 - (1-s)e3] + 2 lam s tr - 2c cos;          f <= 0: elastic (branch 0), L = 0
@@ -171,12 +172,15 @@ int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
  *   Back through the permutation to (sig_a, sig_b, sig_z) and D over (a, b, z):
  *     (s11, s22, s12) = sig_a Pa + sig_b Pb,  s33 = sig_z
  *     ds = D_aa Pa Pa^T + D_ab (Pa Pb^T + Pb Pa^T) + D_bb Pb Pb^T + theta (diag(1, 1, 1/2) - Pa Pa^T - Pb Pb^T),
- *     theta = (sig_a - sig_b)/(2r)  (D_aa - D_ab at r = 0)                                (rows / columns 11, 22, 12)
+ *     theta = (sig_a - sig_b)/(2r) = G [(t_a - t_b) - L (n_a - n_b)]/r  (D_aa - D_ab at r = 0, 0 at the apex), formed from the
+ *     difference itself: t_a - t_b is 2r unless the branch is an edge, so an elastic point has theta = 2G exactly and an edge
+ *     that merges a and b theta = 0 exactly, whatever r                                  (rows / columns 11, 22, 12)
  *   accept, plastic points:  th = (sig_a+sig_b+sig_z)/(3K),  dp_i = e_i - (sig_i - lam th)/(2G) over (a, b, z),
  *     p += (dp_a Pa0 + dp_b Pb0,  dp_a Pa1 + dp_b Pb1,  2 (dp_a Pa2 + dp_b Pb2),  dp_z)
  * (An edge's L >= g_sl resp. g_sr needs no test: den (L - g) of the edge equals den (L - g) of the failed smooth test.)
- * ind_p = (branch != 0); counts = {smooth face + both edges, apex}.  ds is symmetric.  theta loses the digits of
- * max|Et| / r as r -> 0, and a point within rounding of a branch boundary may take either side (s is continuous there). */
+ * ind_p = (branch != 0); counts = {smooth face + both edges, apex}.  ds is symmetric.  On the smooth face theta loses the
+ * digits of max|Et| / r as r -> 0 (2r - L (n_a - n_b) is then a difference of two rounded numbers; nowhere else), and a point
+ * within rounding of a branch boundary may take either side (s is continuous there). */
 int fep_return_map_mc_host(int device_id, int64_t n_int,
                            const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
                            const double* e0_h, double* ep_prev_h,

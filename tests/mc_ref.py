@@ -45,10 +45,15 @@ def mc_return_map(e, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain=Fals
     tr = Et[0] + Et[1] + Et[3]
     # 2: in-plane eigen-decomposition
     m, dd, h = (Et[0] + Et[1]) / 2, (Et[0] - Et[1]) / 2, Et[2] / 2
-    r = np.sqrt(dd * dd + h * h)
+    tiny = np.maximum(np.abs(dd), np.abs(h)) < T(2.0) ** -500       # the squares kept out of the denormal range (exact scaling)
+    with np.errstate(over='ignore'):
+        dds, hs = np.where(tiny, dd * T(2.0) ** 600, dd), np.where(tiny, h * T(2.0) ** 600, h)
+    rsc = np.sqrt(dds * dds + hs * hs)
+    r = np.where(tiny, rsc * T(2.0) ** -600, rsc)
     ea, eb, ez = m + r, m - r, Et[3]
-    rs = np.where(r > 0, r, one)
-    ca, sa = np.where(r > 0, dd / rs, one), np.where(r > 0, h / rs, 0 * one)
+    rpos = rsc > 0
+    rs = np.where(rpos, rsc, one)
+    ca, sa = np.where(rpos, dds / rs, one), np.where(rpos, hs / rs, 0 * one)
     Pa = np.array([(1 + ca) / 2, (1 - ca) / 2, sa / 2])
     Pb = np.array([(1 - ca) / 2, (1 + ca) / 2, -sa / 2])
     # 3: stable descending sort; ea >= eb always, so only the place pz of ez varies
@@ -101,7 +106,10 @@ def mc_return_map(e, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain=Fals
     S = np.empty((4, n), dtype=T)
     S[0:3] = sig_a * Pa + sig_b * Pb
     S[3] = sig_z
-    theta = np.where(r > 0, (sig_a - sig_b) / (2 * rs), Daa - Dab)
+    # theta from the difference itself: sig_a - sig_b = 2G [(t_a - t_b) - L (n_a - n_b)], and t_a - t_b = 2r where no edge merges
+    ta, tb, na, nb = _pick(pz, t2, t1, t1), _pick(pz, t3, t3, t2), _pick(pz, n2, n1, n1), _pick(pz, n3, n3, n2)
+    dt = np.where(ml | mr, ta - tb, 2 * r)
+    theta = np.where(apex, 0 * one, np.where(rpos, G * ((dt - L * (na - nb)) / np.where(rpos, r, one)), Daa - Dab))
     I3 = (one, one, one / 2)
     idx = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
     d = {}
