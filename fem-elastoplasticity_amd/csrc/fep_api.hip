@@ -659,8 +659,6 @@ static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
                      (long long)P.n_wg, P.tile, P.n_segs, (long long)P.staged_total, (double)P.staged_total / (double)c->n_e,
                      P.L, P.NL, P.C, (int)P.lds, (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
     FEP_TRY(dmalloc(c, &c->geo, 6 * c->n_e));
-    for (int a = 0; a < 3; ++a) { c->p1tab.h1[a] = in.dh1[a]; c->p1tab.h2[a] = in.dh2[a]; }
-    c->p1tab.wf = in.wf[0];
     c->n_count_blocks = (int)grid_for(c->n_e, kBlock);
     return FEP_OK;
 }
@@ -845,6 +843,11 @@ static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& t
 static int choose_route(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& tstart) {
     const bool route_coo = env_is("FEP_ROUTE", "coo"), route_patch = env_is("FEP_ROUTE", "patch");
     bool taken = false;
+    if (c->elem_type == FEP_P1) {                       // the reference-element tables by value, on EVERY route: the node route's kernels
+                                                        // and the point kernel of a von Mises / Mohr-Coulomb step (step_model) take them
+        for (int a = 0; a < 3; ++a) { c->p1tab.h1[a] = in.dh1[a]; c->p1tab.h2[a] = in.dh2[a]; }
+        c->p1tab.wf = in.wf[0];
+    }
     if (c->elem_type == FEP_P1 && !route_coo && !route_patch) {
         FEP_TRY(setup_p1_node(c, in, &taken));
         if (taken) c->route = Route::P1Node;

@@ -4,6 +4,7 @@ test_sharding_gpu.py): the structured rectangles of every type, P4 included (a P
 create_midpoints_P4, the reference's numbering), Delaunay triangulations raised to P2 / P4, and the transformations the
 tests apply to them (jitter with curved edges, random renumbering, mixed orientation, trailing elements dropped).
 """
+import re
 from importlib import import_module
 
 import numpy as np
@@ -82,3 +83,31 @@ def mixed_orientation(elem, rng):
 def drop_last(elem, k):
     """The mesh without its last k elements (their nodes stay: nodes of no element)."""
     return np.ascontiguousarray(elem[:, :elem.shape[1] - k]) if k else elem
+
+
+def named(t, name, rng):
+    """The named meshes of the element-route tests (test_element_route_gpu.py, model_step_cases.py) -> (elem, coord,
+    typical element size h, state kind of the element-route test)."""
+    n = {'P1': 24, 'P2': 14, 'Q1': 24, 'Q2': 12, 'P4': 8}[t]
+    if name.startswith('structured'):
+        nx, ny, k = [int(v) for v in re.match(r'structured_(\d+)x(\d+)-(\d+)', name).groups()]
+        elem, coord = rect(t, nx, ny)
+        return drop_last(elem, k), coord, 10 / max(nx, ny), ('plain', 'wide', 'tsx', 'accept', 'plain')[nx % 5]
+    if name in ('strip1', 'strip2'):
+        nx = {'P1': 301, 'P2': 151, 'Q1': 601, 'Q2': 149, 'P4': 61}[t]
+        elem, coord = rect(t, nx, int(name[-1]), 10.0, 10.0 * int(name[-1]) / nx)
+        return elem, coord, 10 / nx, 'accept' if name == 'strip1' else 'wide'
+    if name == 'aniso':                                            # cells 1 : 1000
+        elem, coord = rect(t, 10, 10, 10.0, 0.01)
+        return elem, coord, 1e-3, 'plain'
+    if name == 'delaunay':
+        elem, coord = renumber(*delaunay(t, n, rng), rng)
+        return elem, coord, 10 / n, 'tsx'
+    elem, coord = square(t, n)
+    coord = jitter(elem, coord, 0.15 if name == 'curved' else 0.1, rng)
+    if name == 'renumbered':
+        elem, coord = renumber(elem, coord, rng)
+        return elem, coord, 10 / n, 'wide'
+    if name == 'mixed':
+        return mixed_orientation(elem, rng), coord, 10 / n, 'accept'
+    return elem, coord, 10 / n, 'plain'

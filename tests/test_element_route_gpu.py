@@ -23,6 +23,7 @@ import pytest
 import meshes
 from conftest import dp_materials, load_golden, relerr_points
 from elem_ref import ElemRef, ratio, reverse_elements
+from meshes import named as _mesh
 from oracle import fep_oracle as orc
 from routes import assert_route
 
@@ -69,33 +70,6 @@ def _cases():
                     continue
                 out.append((t, r, name))
     return out
-
-
-def _mesh(t, name, rng):
-    """(elem, coord, typical element size h, state)"""
-    n = {'P1': 24, 'P2': 14, 'Q1': 24, 'Q2': 12, 'P4': 8}[t]
-    if name.startswith('structured'):
-        nx, ny, k = [int(v) for v in re.match(r'structured_(\d+)x(\d+)-(\d+)', name).groups()]
-        elem, coord = meshes.rect(t, nx, ny)
-        return meshes.drop_last(elem, k), coord, 10 / max(nx, ny), ('plain', 'wide', 'tsx', 'accept', 'plain')[nx % 5]
-    if name in ('strip1', 'strip2'):
-        nx = {'P1': 301, 'P2': 151, 'Q1': 601, 'Q2': 149, 'P4': 61}[t]
-        elem, coord = meshes.rect(t, nx, int(name[-1]), 10.0, 10.0 * int(name[-1]) / nx)
-        return elem, coord, 10 / nx, 'accept' if name == 'strip1' else 'wide'
-    if name == 'aniso':                                            # cells 1 : 1000
-        elem, coord = meshes.rect(t, 10, 10, 10.0, 0.01)
-        return elem, coord, 1e-3, 'plain'
-    if name == 'delaunay':
-        elem, coord = meshes.renumber(*meshes.delaunay(t, n, rng), rng)
-        return elem, coord, 10 / n, 'tsx'
-    elem, coord = meshes.square(t, n)
-    coord = meshes.jitter(elem, coord, 0.15 if name == 'curved' else 0.1, rng)
-    if name == 'renumbered':
-        elem, coord = meshes.renumber(elem, coord, rng)
-        return elem, coord, 10 / n, 'wide'
-    if name == 'mixed':
-        return meshes.mixed_orientation(elem, rng), coord, 10 / n, 'accept'
-    return elem, coord, 10 / n, 'plain'
 
 
 def _state(kind, coord, h, n_int, rng):

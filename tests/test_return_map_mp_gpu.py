@@ -2,6 +2,9 @@
 through return_map_mp_cases.py; the reference itself is not imported here), per point, and the step of a Mohr-Coulomb context
 in a nearly hydrostatic state against the elastic stiffness.  Bounds: DESIGN.md section 7 (return_map_mp_cases.bound).
 
+The sum of the per-workgroup branch counters (counts_reduce_kernel, sum_block_counts) at its loop edges: the three device
+entry points at 1024 * 256 + 1 and 8192 * 256 + 1 points, tiled from 1000.
+
 The initial strain is one vector per call, so a fixture is two launches: its points without e0 (families A to E, several
 256-thread workgroups and a partial last one) and those with it."""
 import ctypes
@@ -9,7 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from conftest import relerr, relerr_rows
+from conftest import dp_materials, relerr, relerr_points, relerr_rows
 from mc_cases import COHESION, SIN_PHI, YOUNG
 from mc_ref import MCRefContext
 from meshes import jitter, rect
@@ -134,3 +137,69 @@ def test_nearly_hydrostatic_step_gives_the_elastic_stiffness(fep, t):
     assert ek <= TOL_K and relerr_rows(K, K_el) <= TOL_K_ROW
     assert firm.sum() >= 8
     assert relerr(F, F_el) <= TOL_K and (err / gross).max() <= TOL_K_ROW and (err / own)[firm].max() <= TOL_K_ROW
+
+
+# ---------------------------------------------------------------------------------------
+# the sum of the per-workgroup counters at its loop edges
+# ---------------------------------------------------------------------------------------
+def _thousand(model):
+    """(e, p, materials, the restatement's result, class per point: 0 elastic, 1 counts[0], 2 counts[1]) of the 1000-point set
+    of the model's mesh-free test (Drucker-Prager: test_parity_gpu's random points with a band at the apex)."""
+    n = 1000
+    if model == 'mc':
+        from mc_cases import points
+        from mc_ref import mc_return_map
+        e, p, _, *mats = points(n, False, 100 + n)
+        ref = mc_return_map(e, p, *mats)
+        return e, p, mats, ref, np.where(ref['branch'] == 0, 0, np.where(ref['branch'] == 4, 2, 1))
+    if model == 'vm':
+        from test_vm_gpu import _points
+        from vm_ref import vm_return_map
+        e, p, _, *mats = _points(n, False, 100 + n)
+        ref = vm_return_map(e, p, *mats)
+        return e, p, mats, ref, ref['ind_p'].astype(np.int64)
+    from oracle import fep_oracle as orc
+    rng = np.random.default_rng(99)
+    sh, bu, eta, c = dp_materials(n)
+    mats = [sh * rng.uniform(0.5, 2, n), bu * rng.uniform(0.5, 2, n), eta * rng.uniform(0.5, 1.5, n), c * rng.uniform(0.5, 2, n)]
+    e = rng.normal(0, 2e-4, size=(3, n))
+    e[:, : n // 20] += 4e-4                                                 # a band of apex points
+    p = rng.normal(0, 2e-5, size=(4, n))
+    ref = orc.return_map(e, p.copy(), *mats, False)
+    apex = ref['ind_p'] & (np.abs(ref['ds']).sum(axis=0) == 0)              # the apex tangent is zero
+    assert int(apex.sum()) == ref['n_apex']
+    return e, p, mats, ref, np.where(apex, 2, ref['ind_p'].astype(np.int64))
+
+
+@pytest.mark.parametrize('n_blocks', [1024, 8192])
+@pytest.mark.parametrize('model', ['dp', 'vm', 'mc'])
+def test_block_counters_are_summed_past_one_load_and_one_round(fep, model, n_blocks):
+    """sum_block_counts: 1024 lanes, 8 loads per lane and round.  n = 1024 * 256 + 1 points are 1025 workgroups (lane 0 takes
+    a second load), n = 8192 * 256 + 1 are 8193 (lane 0 enters a second round).  The points are the 1000 of the mesh-free
+    tests, tiled: every output of point i is that of point i mod 1000 bit for bit, and the counters are the classes'."""
+    import torch
+    n = n_blocks * 256 + 1
+    e1, p1, mats1, ref, cls1 = _thousand(model)
+    assert (np.bincount(cls1, minlength=3)[:2 if model == 'vm' else 3] > 0).all()
+    idx = np.arange(n) % 1000
+    dev = torch.device('cuda', 0)
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float64)[..., idx])).to(dev)     # noqa: E731
+    ed, pd = up(e1), up(p1)
+    md = [up(m) for m in mats1]
+    S = torch.zeros((4, n), dtype=torch.float64, device=dev)
+    ind = torch.zeros(n, dtype=torch.uint8, device=dev)
+    cnt = torch.full((2,), -1, dtype=torch.int64, device=dev)
+    rc = getattr(fep.lib(), DEV_ENTRY[model])(0, torch.cuda.current_stream().cuda_stream, n, ed.data_ptr(), 1, n, None,
+                                              pd.data_ptr(), *(m.data_ptr() for m in md), 0, S.data_ptr(), None,
+                                              ind.data_ptr(), cnt.data_ptr())
+    assert rc == 0
+    torch.cuda.synchronize()
+    s, ind_p, counts = S.cpu().numpy(), ind.cpu().numpy().astype(bool), cnt.cpu().numpy()
+    assert np.array_equal(pd.cpu().numpy(), p1[:, idx])                     # not accepting: ep untouched
+    per_class = np.bincount(cls1[idx], minlength=3)
+    print(model, n, counts, per_class)
+    assert counts[0] + counts[1] == int(ind_p.sum())
+    assert (counts[0], counts[1]) == (per_class[1], per_class[2])
+    assert np.array_equal(s, s[:, :1000][:, idx]) and np.array_equal(ind_p, ind_p[:1000][idx])
+    assert np.array_equal(ind_p[:1000], ref['ind_p'])
+    assert relerr(s[:, :1000], ref['s']) <= 1e-13 and relerr_points(s[:, :1000], ref['s']) <= 1e-12
