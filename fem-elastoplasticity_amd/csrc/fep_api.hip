@@ -304,6 +304,16 @@ static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) 
     return FEP_OK;
 }
 
+// The material models, one row each, indexed by FEP_MODEL_*: the tag a model puts into its kernels' names and its kernel of each
+// point-kernel family.  point_*_kernel<NP, NQ> has no Drucker-Prager row, that step being the fused element route: model - 1.
+constexpr int kModels = 3;
+static const char* const kModelTag[kModels] = {"", "vm_", "mc_"};
+static constexpr decltype(&return_map_kernel) kReturnMapKernel[kModels] = {return_map_kernel, return_map_vm_kernel, return_map_mc_kernel};
+static constexpr decltype(&p1_point_kernel) kP1PointKernel[kModels] = {p1_point_kernel, p1_point_vm_kernel, p1_point_mc_kernel};
+template <int NP, int NQ>
+static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>};
+static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == kModels - 1, "table order");
+
 // (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises or sin_phi, c of Mohr-Coulomb)
 static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n_int,
                                const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
@@ -318,8 +328,7 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     const unsigned n_blocks = grid_for(n_int, kBlock);
     uint2* blk = nullptr;
     if (counts_d) FEP_TRY(rm_scratch(device_id, st, n_blocks, &blk));
-    const auto kernel = model == FEP_MODEL_MC ? return_map_mc_kernel : model == FEP_MODEL_VM ? return_map_vm_kernel : return_map_kernel;
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(kReturnMapKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
                        n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
                        shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
     HIP_TRY(hipGetLastError());
@@ -950,39 +959,29 @@ extern "C" int fep_ctx_sizes(const fep_ctx* c, int64_t sizes[8]) {
 extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int64_t cap) {
     if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
     auto b = [](bool v) { return v ? "true" : "false"; };
-    char tmp[256];
-    if (c->model != FEP_MODEL_DP) {                     // point kernel + the route's assembly from ds / s (step_model)
-        char pt[64], el[96];
-        const char* law = c->model == FEP_MODEL_MC ? "mc" : "vm";
-        if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%s_kernel", law);
-        else std::snprintf(pt, sizeof pt, "point_%s_kernel<%d, %d>", law, c->n_p, c->n_q);
-        const bool patch = c->route == Route::Patch;
-        std::snprintf(el, sizeof el, "element_kernel<%d, %d, false, %s, %s, %d, %d>", c->n_p, c->n_q, b(c->elem_geo), b(patch),
-                      patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
-        if (c->route == Route::P1Node && c->p1_lds)
-            std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, c->tile, b(c->p1_rng), b(c->p1_pk));
-        else if (c->route == Route::P1Node) std::snprintf(tmp, sizeof tmp, "%s + p1_node_kernel", pt);
-        else if (patch) std::snprintf(tmp, sizeof tmp, "%s + %s + fixup_kernel", pt, el);
-        else if (c->route == Route::Coo)
-            std::snprintf(tmp, sizeof tmp, "%s + %s + %s", pt, el, c->pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
-        else return FEP_ESTATE;
+    const bool dp = c->model == FEP_MODEL_DP, patch = c->route == Route::Patch;
+    // `pt`: the model's point kernel; `el`: the element routes' kernel, for Drucker-Prager the whole step from U, for the other
+    // models the assembly from ds / s behind their point kernel (step_model)
+    char tmp[256], pt[64], el[192];
+    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", kModelTag[c->model]);
+    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", kModelTag[c->model], c->n_p, c->n_q);
+    std::snprintf(el, sizeof el, "%s%selement_kernel<%d, %d, %s, %s, %s, %d, %d>", dp ? "" : pt, dp ? "" : " + ", c->n_p, c->n_q, b(dp),
+                  b(c->elem_geo), b(patch), patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
+    if (c->route == Route::P1Node && c->p1_lds && dp && which == 1 && c->p1_fused && c->fused_mode >= 1) {
+        std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", c->tile, b(c->p1_fused_rng), b(c->p1_dma));
     } else if (c->route == Route::P1Node && c->p1_lds) {
-        if (which == 1 && c->p1_fused && c->fused_mode >= 1)
-            std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", c->tile, b(c->p1_fused_rng), b(c->p1_dma));
-        else
-            std::snprintf(tmp, sizeof tmp, "p1_point_kernel + p1_node_lds_kernel<%d, %s, 1, %s>", c->tile, b(c->p1_rng), b(c->p1_pk));
+        std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, c->tile, b(c->p1_rng), b(c->p1_pk));
     } else if (c->route == Route::P1Node) {
-        std::snprintf(tmp, sizeof tmp, "p1_point_kernel + p1_node_kernel");
+        std::snprintf(tmp, sizeof tmp, "%s + p1_node_kernel", pt);
 #ifdef FEP_ABLATION
-    } else if (c->route == Route::GenNode) {
+    } else if (c->route == Route::GenNode) {            // (Drucker-Prager only: fep_ctx_set_model)
+        if (!dp) return FEP_ESTATE;
         std::snprintf(tmp, sizeof tmp, "point_kernel<%d, %d> + node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, c->n_p, c->n_q, c->gn_tile);
 #endif
-    } else if (c->route == Route::Patch) {
-        std::snprintf(tmp, sizeof tmp, "element_kernel<%d, %d, true, %s, true, %d, %d> + fixup_kernel", c->n_p, c->n_q, b(c->elem_geo),
-                      c->patch_tpb, c->patch_js);
+    } else if (patch) {
+        std::snprintf(tmp, sizeof tmp, "%s + fixup_kernel", el);
     } else {
-        std::snprintf(tmp, sizeof tmp, "element_kernel<%d, %d, true, %s, false, 256, 1> + %s", c->n_p, c->n_q, b(c->elem_geo),
-                      c->pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
+        std::snprintf(tmp, sizeof tmp, "%s + %s", el, c->pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
     }
     std::snprintf(buf, (size_t)cap, "%s", tmp);
     return FEP_OK;
@@ -1043,7 +1042,7 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
 // The models besides Drucker-Prager run as point kernel + the route's assembly: the ds / s scratch and the point kernel's
 // per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
 extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
-    if (!c || (model != FEP_MODEL_DP && model != FEP_MODEL_VM && model != FEP_MODEL_MC)) return FEP_EINVAL;
+    if (!c || model < 0 || model >= kModels) return FEP_EINVAL;
     if (model != FEP_MODEL_DP) {
 #ifdef FEP_ABLATION
         if (c->route == Route::GenNode) return FEP_ESTATE;
@@ -1356,17 +1355,15 @@ static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, doub
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
     FEP_TRY(prof_mark(c, st));
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
-    const bool mc = c->model == FEP_MODEL_MC;
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
         if constexpr (ET::type == FEP_P1)
-            hipLaunchKernelGGL(mc ? p1_point_mc_kernel : p1_point_vm_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
-                               c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d,
-                               ds_d, ind_p_d, blk);
+            hipLaunchKernelGGL(kP1PointKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->p1tab,
+                               u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
         else
-            hipLaunchKernelGGL((mc ? point_mc_kernel<ET::NP, ET::NQ> : point_vm_kernel<ET::NP, ET::NQ>), dim3(n_blocks),
-                               dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear,
-                               c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
+            hipLaunchKernelGGL((kPointKernel<ET::NP, ET::NQ>[c->model - FEP_MODEL_VM]), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e,
+                               c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu,
+                               accept, e_out_d, s_d, ds_d, ind_p_d, blk);
         return FEP_OK;
     }));
     HIP_TRY(hipGetLastError());

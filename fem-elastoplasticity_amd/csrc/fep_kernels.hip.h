@@ -273,15 +273,17 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
     return branch;
 }
 
-// The return map of a model other than Drucker-Prager, and the counter its branch goes to (count_branches: 1 -> counts[0],
-// 2 -> counts[1]): von Mises counts its plastic points, Mohr-Coulomb face and edges together and the apex apart.
+// The return map of a material model, and the counter its branch goes to (count_branches: 1 -> counts[0], 2 -> counts[1]):
+// Drucker-Prager counts smooth and apex as they are, von Mises its plastic points, Mohr-Coulomb face and edges together and
+// the apex apart.  `m3` / `m4` = eta / c, a / Y or sin_phi / c.  A new model is a line in each of the two.
 template <int MODEL>
 __device__ __forceinline__ int model_return_map(const double e[3], const double z[4], double p[4],
                                                 double G, double K, double m3, double m4, bool accept,
                                                 double s[4], double d[6]) {
-    static_assert(MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC, "model");
+    static_assert(MODEL == FEP_MODEL_DP || MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC, "model");
     if constexpr (MODEL == FEP_MODEL_MC) return mc_return_map(e, z, p, G, K, m3, m4, accept, s, d);
-    else return vm_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+    else if constexpr (MODEL == FEP_MODEL_VM) return vm_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+    else return dp_return_map(e, z, p, G, K, m3, m4, accept, s, d);
 }
 template <int MODEL>
 __device__ __forceinline__ int count_class(int branch) {
@@ -396,34 +398,15 @@ __device__ __forceinline__ void store_point_off(unsigned kb, unsigned k32, int64
 // ---------------------------------------------------------------------------------------
 struct E0 { double v[4]; };
 
-__global__ void __launch_bounds__(kBlock)
-return_map_kernel(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, E0 e0,
-                  double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
-                  const double* __restrict__ eta, const double* __restrict__ cc, int accept,
-                  double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
-                  uint2* blk_counts) {
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    int branch = 0;
-    if (k < n) {
-        double ev[3] = {e[k * eps], e[k * eps + ecs], e[k * eps + 2 * ecs]};
-        double p[4] = {0.0, 0.0, 0.0, 0.0};
-        if (ep) { p[0] = ep[k]; p[1] = ep[n + k]; p[2] = ep[2 * n + k]; p[3] = ep[3 * n + k]; }
-        double s[4], d[6];
-        branch = dp_return_map(ev, e0.v, p, shear[k], bulk[k], eta[k], cc[k], accept != 0, s, d);
-        store_point(k, n, s, d, branch, S, DS, indp);
-        if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
-    }
-    count_branches(branch, nullptr, blk_counts);      // per-workgroup counters, summed by counts_reduce_kernel (no global atomics)
-}
-
-// The same for the other models (model_return_map): `m3` / `m4` = a / Y of von Mises or sin_phi / c of Mohr-Coulomb per point
+// One body for every model (model_return_map): `m3` / `m4` = the model's third and fourth material array per point.  Per-workgroup
+// counters, summed by counts_reduce_kernel (no global atomics).
 template <int MODEL>
 __device__ __forceinline__ void
-return_map_model_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, const E0& e0,
-                      double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
-                      const double* __restrict__ hard, const double* __restrict__ yld, int accept,
-                      double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
-                      uint2* blk_counts) {
+return_map_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, const E0& e0,
+                double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
+                const double* __restrict__ m3, const double* __restrict__ m4, int accept,
+                double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
+                uint2* blk_counts) {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (k < n) {
@@ -431,7 +414,7 @@ return_map_model_body(int64_t n, const double* __restrict__ e, int64_t eps, int6
         double p[4] = {0.0, 0.0, 0.0, 0.0};
         if (ep) { p[0] = ep[k]; p[1] = ep[n + k]; p[2] = ep[2 * n + k]; p[3] = ep[3 * n + k]; }
         double s[4], d[6];
-        branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], hard[k], yld[k], accept != 0, s, d);
+        branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
         store_point(k, n, s, d, branch, S, DS, indp);
         if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
     }
@@ -443,11 +426,14 @@ return_map_model_body(int64_t n, const double* __restrict__ e, int64_t eps, int6
     const double* __restrict__ shear, const double* __restrict__ bulk, const double* __restrict__ m3,                    \
     const double* __restrict__ m4, int accept, double* __restrict__ S, double* __restrict__ DS,                          \
     uint8_t* __restrict__ indp, uint2* blk_counts
+__global__ void __launch_bounds__(kBlock) return_map_kernel(FEP_RETURN_MAP_ARGS) {
+    return_map_body<FEP_MODEL_DP>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
 __global__ void __launch_bounds__(kBlock) return_map_vm_kernel(FEP_RETURN_MAP_ARGS) {
-    return_map_model_body<FEP_MODEL_VM>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+    return_map_body<FEP_MODEL_VM>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
 }
 __global__ void __launch_bounds__(kBlock) return_map_mc_kernel(FEP_RETURN_MAP_ARGS) {
-    return_map_model_body<FEP_MODEL_MC>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+    return_map_body<FEP_MODEL_MC>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
 }
 #undef FEP_RETURN_MAP_ARGS
 
@@ -1339,13 +1325,16 @@ __device__ __forceinline__ void p1_geometry(const P1Tab& tab, const double2 c0, 
 //   geo[e*6 + {0,1}] = dphi_1 of nodes 0, 1, {2,3} = dphi_2, [4] = weight (48-byte record; node 2 = -(0 + 1))
 //   perm2[t] = e*16 + a*4 + b ;  meta = (deg << 16) | (diag << 15) | slot
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock)
-p1_point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, P1Tab tab,
-                const double* __restrict__ U, E0 e0, double* __restrict__ ep,
-                const double* __restrict__ shear, const double* __restrict__ bulk,
-                const double* __restrict__ eta, const double* __restrict__ cc, MatU mu, int accept,
-                double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-                uint8_t* __restrict__ indp, uint2* blk_counts) {
+// Stage A of a P1 context's step, one body for every model: `m3` / `m4` = the model's third and fourth material array per
+// point (MatU: eta / c hold them).  Stage B is the context's own assembly.
+template <int MODEL>
+__device__ __forceinline__ void
+p1_point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, const P1Tab& tab,
+              const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
+              const double* __restrict__ shear, const double* __restrict__ bulk,
+              const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
+              double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+              uint8_t* __restrict__ indp, uint2* blk_counts) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (e < n_e) {
@@ -1366,48 +1355,8 @@ p1_point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __r
         if (ep) { p[0] = ep[e]; p[1] = ep[n_e + e]; p[2] = ep[2 * n_e + e]; p[3] = ep[3 * n_e + e]; }
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[e], m_bu = mu.on ? mu.bulk : bulk[e];
-        const double m_eta = mu.on ? mu.eta : eta[e], m_c = mu.on ? mu.c : cc[e];
-        branch = dp_return_map(ev, e0.v, p, m_sh, m_bu, m_eta, m_c, accept != 0, s, d);
-        store_point(e, n_e, s, d, branch, S, DS, indp);
-        if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
-        if (accept && ep && branch) { ep[e] = p[0]; ep[n_e + e] = p[1]; ep[2 * n_e + e] = p[2]; ep[3 * n_e + e] = p[3]; }
-    }
-    count_branches(branch, nullptr, blk_counts);
-}
-
-// Von Mises or Mohr-Coulomb step of a P1 context (FEP_MODEL_VM / _MC), stage A: p1_point_kernel with the model's return map —
-// one lane per element, same geometry and strain; `hard` / `yld` = a / Y or sin_phi / c per point (MatU: eta / c hold them).
-// Stage B is the context's own assembly.
-template <int MODEL>
-__device__ __forceinline__ void
-p1_point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, const P1Tab& tab,
-                    const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
-                    const double* __restrict__ shear, const double* __restrict__ bulk,
-                    const double* __restrict__ hard, const double* __restrict__ yld, const MatU& mu, int accept,
-                    double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-                    uint8_t* __restrict__ indp, uint2* blk_counts) {
-    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    int branch = 0;
-    if (e < n_e) {
-        const int64_t n0 = elem[e], n1 = elem[n_e + e], n2 = elem[2 * n_e + e];
-        const double2 c0 = *reinterpret_cast<const double2*>(xy + 2 * n0);
-        const double2 c1 = *reinterpret_cast<const double2*>(xy + 2 * n1);
-        const double2 c2 = *reinterpret_cast<const double2*>(xy + 2 * n2);
-        const double2 u0 = *reinterpret_cast<const double2*>(U + 2 * n0);
-        const double2 u1 = *reinterpret_cast<const double2*>(U + 2 * n1);
-        const double2 u2 = *reinterpret_cast<const double2*>(U + 2 * n2);
-        double d1[3], d2[3], w;
-        p1_geometry(tab, c0, c1, c2, d1, d2, w);
-        double ev[3];
-        ev[0] = d1[0] * u0.x + d1[1] * u1.x + d1[2] * u2.x;
-        ev[1] = d2[0] * u0.y + d2[1] * u1.y + d2[2] * u2.y;
-        ev[2] = (d2[0] * u0.x + d1[0] * u0.y) + (d2[1] * u1.x + d1[1] * u1.y) + (d2[2] * u2.x + d1[2] * u2.y);
-        double p[4] = {0.0, 0.0, 0.0, 0.0};
-        if (ep) { p[0] = ep[e]; p[1] = ep[n_e + e]; p[2] = ep[2 * n_e + e]; p[3] = ep[3 * n_e + e]; }
-        double s[4], d[6];
-        const double m_sh = mu.on ? mu.shear : shear[e], m_bu = mu.on ? mu.bulk : bulk[e];
-        const double m_a = mu.on ? mu.eta : hard[e], m_y = mu.on ? mu.c : yld[e];
-        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
+        const double m_3 = mu.on ? mu.eta : m3[e], m_4 = mu.on ? mu.c : m4[e];
+        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
         store_point(e, n_e, s, d, branch, S, DS, indp);
         if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
         if (accept && ep && branch) { ep[e] = p[0]; ep[n_e + e] = p[1]; ep[2 * n_e + e] = p[2]; ep[3 * n_e + e] = p[3]; }
@@ -1420,11 +1369,14 @@ p1_point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double*
     E0 e0, double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,                   \
     const double* __restrict__ m3, const double* __restrict__ m4, MatU mu, int accept, double* __restrict__ Eout,        \
     double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp, uint2* blk_counts
+__global__ void __launch_bounds__(kBlock) p1_point_kernel(FEP_P1_POINT_ARGS) {
+    p1_point_body<FEP_MODEL_DP>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+}
 __global__ void __launch_bounds__(kBlock) p1_point_vm_kernel(FEP_P1_POINT_ARGS) {
-    p1_point_model_body<FEP_MODEL_VM>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+    p1_point_body<FEP_MODEL_VM>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
 }
 __global__ void __launch_bounds__(kBlock) p1_point_mc_kernel(FEP_P1_POINT_ARGS) {
-    p1_point_model_body<FEP_MODEL_MC>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+    p1_point_body<FEP_MODEL_MC>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
 }
 #undef FEP_P1_POINT_ARGS
 
@@ -2019,6 +1971,8 @@ counts_finalize_kernel(unsigned long long* __restrict__ slot_counts, unsigned lo
 //                            sum_q w B_a^T DS B_b over its block's contributions in fixed order.
 //   gather code = local element << 8 | a << 4 | b  (uint16; <= 256 elements per tile, n_p <= 16)
 // ---------------------------------------------------------------------------------------
+// (Drucker-Prager on the GenNode route, reached only in the -DFEP_ABLATION build and by no test; not point_body: per-node arrays,
+// geometry_at_q and unfused strain sums are the arithmetic the ablation profiles were measured with.)
 template <int NP, int NQ>
 __global__ void __launch_bounds__(kBlock)
 point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
@@ -2065,8 +2019,8 @@ point_kernel(int64_t n_e, const int32_t* __restrict__ elem, const double* __rest
     count_branches(branch, nullptr, blk_counts);
 }
 
-// Von Mises step (FEP_MODEL_VM), stage A for P2, Q1, Q2 and P4: point_kernel's split with vm_return_map.  One lane per
-// integration point; writes s / ds (the caller's arrays or the context's scratch) for the context's own assembly.
+// Von Mises or Mohr-Coulomb step (FEP_MODEL_VM / _MC), stage A for P2, Q1, Q2 and P4: point_kernel's split with the model's
+// return map (Drucker-Prager takes the fused element route there, so it has no wrapper below).  One lane per integration point; writes s / ds (the caller's arrays or the context's scratch) for the context's own assembly.
 // Unlike point_kernel it holds no per-node array but the node ids: the Jacobian is summed while the coordinates are
 // gathered, the strain while the displacements are (the 15-node element would otherwise hold 90 doubles per lane).
 // Jacobian, inverse and gradients in geometry_kernel's operations and order without contraction, the strain sums in
@@ -2081,13 +2035,13 @@ __device__ __forceinline__ void inverse_jacobian(double j11, double j12, double 
 
 template <int MODEL, int NP, int NQ>
 __device__ __forceinline__ void
-point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
-                 const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
-                 const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
-                 const double* __restrict__ shear, const double* __restrict__ bulk,
-                 const double* __restrict__ hard, const double* __restrict__ yld, const MatU& mu, int accept,
-                 double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-                 uint8_t* __restrict__ indp, uint2* blk_counts) {
+point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
+           const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
+           const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
+           const double* __restrict__ shear, const double* __restrict__ bulk,
+           const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
+           double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
+           uint8_t* __restrict__ indp, uint2* blk_counts) {
     __shared__ double t1[NP * NQ], t2[NP * NQ], tw[NQ];
     for (int i = threadIdx.x; i < NP * NQ; i += kBlock) { t1[i] = dh1[i]; t2[i] = dh2[i]; }
     for (int i = threadIdx.x; i < NQ; i += kBlock) tw[i] = wf[i];
@@ -2132,8 +2086,8 @@ point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __
         if (ep) { p[0] = ep[k]; p[1] = ep[n_int + k]; p[2] = ep[2 * n_int + k]; p[3] = ep[3 * n_int + k]; }
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[k], m_bu = mu.on ? mu.bulk : bulk[k];
-        const double m_a = mu.on ? mu.eta : hard[k], m_y = mu.on ? mu.c : yld[k];
-        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_a, m_y, accept != 0, s, d);
+        const double m_3 = mu.on ? mu.eta : m3[k], m_4 = mu.on ? mu.c : m4[k];
+        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
         store_point(k, n_int, s, d, branch, S, DS, indp);
         if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
         if (accept && ep && branch) { ep[k] = p[0]; ep[n_int + k] = p[1]; ep[2 * n_int + k] = p[2]; ep[3 * n_int + k] = p[3]; }
@@ -2149,13 +2103,13 @@ point_model_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __
     double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp, uint2* blk_counts
 template <int NP, int NQ>
 __global__ void __launch_bounds__(kBlock) point_vm_kernel(FEP_POINT_ARGS) {
-    point_model_body<FEP_MODEL_VM, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
-                                           indp, blk_counts);
+    point_body<FEP_MODEL_VM, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                     indp, blk_counts);
 }
 template <int NP, int NQ>
 __global__ void __launch_bounds__(kBlock) point_mc_kernel(FEP_POINT_ARGS) {
-    point_model_body<FEP_MODEL_MC, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
-                                           indp, blk_counts);
+    point_body<FEP_MODEL_MC, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                     indp, blk_counts);
 }
 #undef FEP_POINT_ARGS
 

@@ -245,8 +245,30 @@ def make_ops(ctx, qf, linear_solver, pcg_rtol, pcg_forcing=None, pcg_forcing_cap
     raise ValueError("linear_solver must be 'direct', 'pcg' or 'amg'")
 
 
+def _newton_iteration(ops, K_elast, U_it, Ep, e0, rhs_of, hist, criterion, zero_dU_converged=False):
+    """The semismooth-Newton iteration of one load step, for every driver: at most 25 iterates from `U_it` at the plastic
+    strain `Ep` and initial strain `e0`, each solving for the right-hand side `rhs_of(F)`, stopped on the K_elast norms.
+    `criterion`: the previous step's (it steers the first inexact solve but one).  `zero_dU_converged`: an exactly zero
+    correction counts as criterion 0 instead of the quotient as it stands.  Returns (iterate, iterations, criterion)."""
+    its = 0
+    for _ in range(25):                                                                   # DP:1040
+        r = ops.step(U_it, Ep, e0=e0, want=('K', 'F'))                                    # DP:1043-1058, TSX:1771-1778
+        hist['n_calls'] += 1
+        its += 1
+        dU = ops.solve(r['K'], rhs_of(r['F']), criterion if its > 1 else 1.0)             # DP:1062-1066, TSX:1781
+        U_new = U_it + dU
+        q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)   # DP:1072-1074
+        criterion = 0.0 if zero_dU_converged and q1 == 0 else q1 / (q2 + q3)              # TSX:1788-1792
+        if np.isnan(criterion):                                                           # DP:1076
+            break
+        U_it = U_new
+        if criterion < 1e-12:                                                             # DP:1086
+            break
+    return U_it, its, criterion
+
+
 def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, accept_kw, accepted, finished):
-    """The load-step loop with its semismooth-Newton iteration, for both flavours (DP:1031-1127, TSX:1765-1826).
+    """The load-step loop around _newton_iteration, for both flavours (DP:1031-1127, TSX:1765-1826).
     `U_it`: the starting iterate.  Per flavour: `e0_of(zeta)` the initial strain of a step (or None), `accept_kw` the
     arguments of the accepting call of the step, `accepted(r, zeta, U, Ep_old, its, criterion)` records the step from
     that call's result `r` and returns (the plastic strain to go on with, whether the step may grow),
@@ -260,20 +282,7 @@ def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, acce
     while True:
         zeta = zeta_old + d_zeta                                                          # DP:1031
         e0 = e0_of(zeta)                                                                  # TSX:1765
-        its = 0
-        for _ in range(25):                                                               # DP:1040
-            r = ops.step(U_it, Ep_old, e0=e0, want=('K', 'F'))                            # DP:1043-1058, TSX:1771-1778
-            hist['n_calls'] += 1
-            its += 1
-            dU = ops.solve(r['K'], -r['F'], criterion if its > 1 else 1.0)                # DP:1062-1066, TSX:1781
-            U_new = U_it + dU
-            q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)   # DP:1072-1074
-            criterion = q1 / (q2 + q3)                                                    # TSX:1788-1792
-            if np.isnan(criterion):                                                       # DP:1076
-                break
-            U_it = U_new
-            if criterion < 1e-12:                                                         # DP:1086
-                break
+        U_it, its, criterion = _newton_iteration(ops, K_elast, U_it, Ep_old, e0, lambda F: -F, hist, criterion)
         if criterion < 1e-10:                                                             # DP:1091, TSX:1804
             U_old = U
             U = U_it
@@ -294,8 +303,7 @@ def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, acce
 
 def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted):
     """A prescribed history of load factors on an external load (no counterpart in the reference, whose plastic drivers
-    load through prescribed displacements or an initial stress): for every `zeta` of `zetas` the Newton iteration of
-    _load_step_loop — same iterate update, same stopping quantity in the K_elast norm — on the residual
+    load through prescribed displacements or an initial stress): for every `zeta` of `zetas` _newton_iteration on the residual
     zeta * f_ext - F(U), started from the last accepted U, then the accepting call, which updates the plastic strain in
     place: the state a load cycle carries.  The stopping quantity is 0 when the correction is exactly 0 (an elastic cycle
     returns to exactly U = 0 at zeta = 0, where the quotient is 0/0).  There is no sub-stepping: a step that does not
@@ -307,21 +315,8 @@ def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted):
     hist['failed_at'] = None
     for k, zeta in enumerate(zetas):
         zeta = float(zeta)
-        U_it = U
-        its = 0
-        for _ in range(25):
-            r = ops.step(U_it, Ep, want=('K', 'F'))
-            hist['n_calls'] += 1
-            its += 1
-            dU = ops.solve(r['K'], zeta * f_ext - r['F'], criterion if its > 1 else 1.0)
-            U_new = U_it + dU
-            q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)
-            criterion = 0.0 if q1 == 0 else q1 / (q2 + q3)
-            if np.isnan(criterion):
-                break
-            U_it = U_new
-            if criterion < 1e-12:
-                break
+        U_it, its, criterion = _newton_iteration(ops, K_elast, U, Ep, None, lambda F: zeta * f_ext - F, hist, criterion,
+                                                 zero_dU_converged=True)
         if not criterion < 1e-10:
             hist['failed_at'] = k
             break

@@ -17,6 +17,8 @@ with A = 2G I + lam 11^T:  A n = 2G n + 2 lam s,  den = n . A n = 2G |n|^2 + 4 l
 The computation runs in the dtype asked for (np.longdouble measures the float64 run's own error)."""
 import numpy as np
 
+from model_ref import RefContext
+
 BRANCHES = ('elastic', 'smooth', 'left', 'right', 'apex')
 
 
@@ -139,47 +141,6 @@ def mc_return_map(e, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain=Fals
             'principal': dict(e=(e1, e2, e3), sig=(sig1, sig2, sig3), pz=pz, Pa=Pa, Pb=Pb, abz=(sig_a, sig_b, sig_z))}
 
 
-class MCRefContext:
-    """Shaped like tests/vm_ref.VMRefContext; the model is Mohr-Coulomb whatever `set_model` is told last, except that
-    any other model is refused."""
-
-    def __init__(self, elem, coord, d1, d2, wf):
-        from oracle import fep_oracle as orc
-        self.orc, self.elem, self.coord, self.tab = orc, np.asarray(elem), np.asarray(coord, dtype=float), (d1, d2, wf)
-        self.n_int = self.elem.shape[1] * np.size(wf)
-        self.n_n = self.coord.shape[1]
-        self.model = 'mc'
-        self.branches = []                                  # per accepting call: the number of points per branch
-
-    def set_model(self, model):
-        if model != 'mc':
-            raise ValueError('MCRefContext restates the Mohr-Coulomb model only')
-
-    def set_materials(self, sh, bu, sin_phi, c):
-        one = np.ones(self.n_int)
-        self.m = tuple(np.asarray(v, dtype=float).ravel() * one for v in (sh, bu, sin_phi, c))
-        K, B, w, iD, jD, D = self.orc.elastic_setup(self.elem, self.coord, self.m[0], self.m[1], *self.tab)
-        self.c = dict(K_elast=K, B=B, D_elast=D, weight=w, iD=iD, jD=jD)
-
-    def geometry(self):
-        return None, None, self.c['weight'], None
-
-    def step(self, U, ep_prev=None, e0=None, apply_plastic_strain=False, want=()):
-        """As MeshContext.step on a Mohr-Coulomb context: `ep_prev` is updated in place on accept; every output is
-        returned whatever `want` names."""
-        c = self.c
-        U2 = np.asarray(U, dtype=float).reshape((2, -1), order='F') if np.ndim(U) == 1 else np.asarray(U, dtype=float)
-        E = self.orc.strain(c['B'], U2)
-        accept = bool(apply_plastic_strain) and ep_prev is not None
-        r = mc_return_map(E, ep_prev, *self.m, apply_plastic_strain=accept, e0=e0)
-        if accept:
-            ep_prev[...] = r['ep']
-            self.branches.append(np.bincount(r['branch'], minlength=5))
-        K_t = self.orc.tangent(c['K_elast'], c['B'], c['D_elast'], c['weight'], r['ds'], c['iD'], c['jD'])
-        F = self.orc.internal_force(c['B'], c['weight'], r['s'])
-        return {'E': np.asarray(E), 'K': K_t.tocsr(), 'F': F, 's': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'],
-                'branch': r['branch'], 'f': r['f'], 'r_rel': r['r_rel'], 'dist': r['dist'],
-                'n_smooth': r['n_smooth'], 'n_apex': r['n_apex']}
-
-    def close(self):
-        pass
+class MCRefContext(RefContext):
+    """The Mohr-Coulomb look-alike; `branches` holds, per accepting call, the number of points per branch."""
+    model, return_map, passed = 'mc', staticmethod(mc_return_map), ('branch', 'f', 'r_rel', 'dist')

@@ -23,6 +23,7 @@ import meshes
 from elem_ref import ElemRef
 from mc_cases import COHESION, DIST_FLOOR, EPS_Y, P_BULK, P_SHEAR, R_FLOOR, SIN_PHI
 from mc_ref import mc_return_map
+from model_ref import traceless
 from vm_cases import BULK, HARDENING, SHEAR, YIELD, fep
 from vm_ref import vm_return_map
 
@@ -70,12 +71,6 @@ def mesh(t, name, rng):
     return meshes.drop_last(elem, elem.shape[1] - n_e), coord
 
 
-def _traceless(rng, n, scale):
-    p = rng.normal(0, scale, size=(4, n))
-    p[[0, 1, 3]] -= (p[0] + p[1] + p[3]) / 3
-    return p
-
-
 def state(model, t, elem, coord, rng):
     """(U, ep, per-point materials, e0): every draw is made whatever the case's flags select."""
     ref = ElemRef(elem, coord, fep.element_tables(t))
@@ -84,7 +79,7 @@ def state(model, t, elem, coord, rng):
     if model == 'vm':
         nrm = vm_return_map(ref.strain(U)[0], None, *UNIFORM['vm'])['crit'] + YIELD
         U *= YIELD / np.median(nrm)                                         # the median point sits on the yield surface
-        ep = _traceless(rng, n, 0.1 * YIELD / (2 * SHEAR))
+        ep = traceless(rng, n, 0.1 * YIELD / (2 * SHEAR))
         f = rng.uniform(0.6, 1.4, n)
         per_point = (SHEAR * f, BULK * f[::-1], HARDENING * rng.uniform(0, 2, n), YIELD * rng.uniform(0.6, 1.4, n))
         e0 = rng.normal(0, 0.2 * YIELD / (2 * SHEAR), size=(4, 1))

@@ -13,6 +13,7 @@ from mc_cases import (COHESION, EPS_Y, FOOTING, MIN_SHARE, P_BULK, P_SHEAR, SIN_
                       well_conditioned)
 from mc_ref import MCRefContext, mc_return_map
 from meshes import jitter, rect
+from model_ref import bytes_equal, check_points, dev_return_map
 from vm_cases import BULK as VM_BULK, HARDENING, SHEAR as VM_SHEAR, YIELD
 
 pytestmark = pytest.mark.gpu
@@ -21,9 +22,7 @@ TOL, TOL_PT, TOL_K, TOL_K_ROW = 1e-13, 1e-12, 1e-12, 1e-11
 
 
 def _check_points(got, ref, keys=('s', 'ds')):
-    for k in keys:
-        print(k, relerr(got[k], ref[k]), relerr_points(got[k], ref[k]))
-        assert relerr(got[k], ref[k]) <= TOL and relerr_points(got[k], ref[k]) <= TOL_PT, k
+    check_points(got, ref, keys, TOL, TOL_PT)
 
 
 def _check_branches(got, ref):
@@ -35,29 +34,8 @@ def _check_branches(got, ref):
 # the mesh-free kernel
 # ---------------------------------------------------------------------------------------
 def _dev_return_map(fep, e, order, p, sh, bu, sp, c, accept, e0):
-    """fep_return_map_mc_dev on torch tensors -> the same dict as the host entry point, 'ep' the device copy of p."""
-    import torch
-    dev = torch.device('cuda', 0)
-    n = sh.size
-    up = lambda v: torch.from_numpy(np.array(v, dtype=np.float64, order='C')).to(dev)     # noqa: E731  (a writable copy)
-    ed = up(e.T if order == 'F' else e)
-    ps, cs = (3, 1) if order == 'F' else (1, n)
-    pd = None if p is None else up(p)
-    shd, bud, spd, cd = up(sh), up(bu), up(sp), up(c)
-    f64 = dict(dtype=torch.float64, device=dev)
-    S, DS = torch.zeros((4, n), **f64), torch.zeros((9, n), **f64)
-    ind, cnt = torch.zeros(n, dtype=torch.uint8, device=dev), torch.full((2,), -1, dtype=torch.int64, device=dev)
-    e0v = None if e0 is None else np.ascontiguousarray(e0, dtype=np.float64).ravel()
-    rc = fep.lib().fep_return_map_mc_dev(0, torch.cuda.current_stream().cuda_stream, n, ed.data_ptr(), ps, cs,
-                                         None if e0v is None else e0v.ctypes.data_as(ctypes.c_void_p),
-                                         None if pd is None else pd.data_ptr(), shd.data_ptr(), bud.data_ptr(),
-                                         spd.data_ptr(), cd.data_ptr(), int(accept), S.data_ptr(), DS.data_ptr(),
-                                         ind.data_ptr(), cnt.data_ptr())
-    assert rc == 0
-    torch.cuda.synchronize()
-    k = cnt.cpu().numpy()
-    return {'s': S.cpu().numpy(), 'ds': DS.cpu().numpy(), 'ind_p': ind.cpu().numpy().astype(bool), 'n_smooth': int(k[0]),
-            'n_apex': int(k[1]), 'ep': None if pd is None else pd.cpu().numpy()}
+    """fep_return_map_mc_dev -> the same dict as the host entry point, 'ep' the device copy of p."""
+    return dev_return_map(fep, 'mc', e, order, p, e0, (sh, bu, sp, c), accept)
 
 
 @pytest.mark.parametrize('order', ['C', 'F'])
@@ -194,11 +172,6 @@ def test_step_of_a_mohr_coulomb_context(fep, t):
 # ---------------------------------------------------------------------------------------
 # the interface of the model switch
 # ---------------------------------------------------------------------------------------
-def _bytes_equal(a, b, keys=('s', 'ds', 'ind_p', 'F')):
-    return all(np.array_equal(a[k], b[k]) for k in keys) and np.array_equal(a['K'].data, b['K'].data) \
-        and (a['n_smooth'], a['n_apex']) == (b['n_smooth'], b['n_apex'])
-
-
 @pytest.mark.parametrize('t', ['P1', 'Q1'])
 def test_model_switch_interface(fep, t):
     elem, coord, _, U, ep, _, _ = _case(fep, t)
@@ -221,15 +194,15 @@ def test_model_switch_interface(fep, t):
     try:
         ra, rb = a.step(U, ep.copy()), b.step(U, ep.copy())
         assert ra['n_smooth'] > 0 and ra['n_apex'] > 0
-        assert _bytes_equal(ra, rb)                                         # the model before or after the materials
-        assert _bytes_equal(ra, a.step(U, ep.copy()))                       # two calls
+        assert bytes_equal(ra, rb)                                         # the model before or after the materials
+        assert bytes_equal(ra, a.step(U, ep.copy()))                       # two calls
         for which in (0, 1):
             assert 'mc_kernel' in a.kernel_names(which)
             assert 'mc' not in dp.kernel_names(which) and 'mc' not in vm.kernel_names(which)
             assert 'vm_kernel' in vm.kernel_names(which) and 'vm' not in a.kernel_names(which)
         # the Drucker-Prager and the von Mises context beside them
-        assert _bytes_equal(dp_before, dp.step(Udp, np.zeros((4, n))))
-        assert _bytes_equal(vm_before, vm.step(Uvm, ep.copy()))
+        assert bytes_equal(dp_before, dp.step(Udp, np.zeros((4, n))))
+        assert bytes_equal(vm_before, vm.step(Uvm, ep.copy()))
         l = fep.lib()
         m = ctypes.c_int(-1)
         assert l.fep_ctx_model(a.handle, ctypes.byref(m)) == 0 and m.value == 2
@@ -243,7 +216,7 @@ def test_model_switch_interface(fep, t):
         # back to Drucker-Prager: a context that never was a Mohr-Coulomb one computes the same
         b.set_model('dp')
         b.set_materials(*dp_materials(n))
-        assert b.model == 'dp' and _bytes_equal(dp_before, b.step(Udp, np.zeros((4, n))))
+        assert b.model == 'dp' and bytes_equal(dp_before, b.step(Udp, np.zeros((4, n))))
     finally:
         for c in (a, b, dp, vm):
             c.close()

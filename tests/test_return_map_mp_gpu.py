@@ -16,13 +16,11 @@ from conftest import dp_materials, relerr, relerr_points, relerr_rows
 from mc_cases import COHESION, SIN_PHI, YOUNG
 from mc_ref import MCRefContext
 from meshes import jitter, rect
+from model_ref import DEV_ENTRY, dev_return_map
 from return_map_mp_cases import check, check_flags, errors, fixture, groups, merge
 from test_mc_gpu import MESHES, TOL_K, TOL_K_ROW
 
 pytestmark = pytest.mark.gpu
-
-DEV_ENTRY = {'dp': 'fep_return_map_dev', 'vm': 'fep_return_map_vm_dev', 'mc': 'fep_return_map_mc_dev'}
-
 
 def _host(fep, model, e, p, e0, mats, accept):
     if model == 'dp':
@@ -33,31 +31,6 @@ def _host(fep, model, e, p, e0, mats, accept):
         r = fep.construct_constitutive_problem_vm(e, p, *mats, apply_plastic_strain=accept, e0=e0)
         return dict(r, n_smooth=r['n_plast'], n_apex=0)
     return fep.construct_constitutive_problem_mc(e, p, *mats, apply_plastic_strain=accept, e0=e0)
-
-
-def _dev(fep, model, e, order, p, e0, mats, accept):
-    """The device entry point on torch tensors -> the same dict, 'ep' the device copy of p afterwards."""
-    import torch
-    dev = torch.device('cuda', 0)
-    n = mats[0].size
-    up = lambda v: torch.from_numpy(np.array(v, dtype=np.float64, order='C')).to(dev)     # noqa: E731  (a writable copy)
-    ed = up(e.T if order == 'F' else e)
-    ps, cs = (3, 1) if order == 'F' else (1, n)
-    pd = up(p)
-    md = [up(m) for m in mats]
-    f64 = dict(dtype=torch.float64, device=dev)
-    S, DS = torch.zeros((4, n), **f64), torch.zeros((9, n), **f64)
-    ind, cnt = torch.zeros(n, dtype=torch.uint8, device=dev), torch.full((2,), -1, dtype=torch.int64, device=dev)
-    e0v = None if e0 is None else np.ascontiguousarray(e0, dtype=np.float64).ravel()
-    rc = getattr(fep.lib(), DEV_ENTRY[model])(0, torch.cuda.current_stream().cuda_stream, n, ed.data_ptr(), ps, cs,
-                                              None if e0v is None else e0v.ctypes.data_as(ctypes.c_void_p), pd.data_ptr(),
-                                              *(m.data_ptr() for m in md), int(accept), S.data_ptr(), DS.data_ptr(),
-                                              ind.data_ptr(), cnt.data_ptr())
-    assert rc == 0
-    torch.cuda.synchronize()
-    k = cnt.cpu().numpy()
-    return {'s': S.cpu().numpy(), 'ds': DS.cpu().numpy(), 'ind_p': ind.cpu().numpy().astype(bool), 'n_smooth': int(k[0]),
-            'n_apex': int(k[1]), 'ep': pd.cpu().numpy()}
 
 
 @pytest.mark.parametrize('order', ['C', 'F'])
@@ -74,7 +47,7 @@ def test_kernels_against_the_high_precision_fixtures(fep, model, order):
         for accept in (False, True):
             ph = p.copy()
             host = _host(fep, model, ev, ph, e0, mats, accept)
-            dev = _dev(fep, model, e, order, p, e0, mats, accept)
+            dev = dev_return_map(fep, model, e, order, p, e0, mats, accept)
             for got, ep in ((host, ph), (dev, dev['ep'])):
                 check_flags(model, fix, idx, got)
                 if accept:

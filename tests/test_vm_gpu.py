@@ -10,6 +10,7 @@ import pytest
 
 from conftest import dp_materials, relerr, relerr_points, relerr_rows
 from meshes import jitter, rect
+from model_ref import bytes_equal, check_points, dev_return_map, traceless
 from vm_cases import BULK, HARDENING, SHEAR, YIELD, cpu_cycle
 from vm_ref import VMRefContext, vm_return_map
 
@@ -18,16 +19,8 @@ pytestmark = pytest.mark.gpu
 TOL, TOL_PT, TOL_K, TOL_K_ROW = 1e-13, 1e-12, 1e-12, 1e-11
 
 
-def _traceless(rng, n, scale):
-    p = rng.normal(0, scale, size=(4, n))
-    p[[0, 1, 3]] -= (p[0] + p[1] + p[3]) / 3
-    return p
-
-
 def _check_points(got, ref, keys=('s', 'ds')):
-    for k in keys:
-        print(k, relerr(got[k], ref[k]), relerr_points(got[k], ref[k]))
-        assert relerr(got[k], ref[k]) <= TOL and relerr_points(got[k], ref[k]) <= TOL_PT, k
+    check_points(got, ref, keys, TOL, TOL_PT)
 
 
 # ---------------------------------------------------------------------------------------
@@ -38,36 +31,16 @@ def _points(n, uniform, seed):
     one = np.ones(n)
     f = one if uniform else rng.uniform(0.6, 1.4, n)
     e = rng.normal(0, 3e-3, size=(3, n))
-    p = _traceless(rng, n, 1e-3)
+    p = traceless(rng, n, 1e-3)
     e0 = rng.normal(0, 1e-3, size=(4, 1))
     return e, p, e0, SHEAR * f, BULK * f[::-1], HARDENING * one if uniform else HARDENING * rng.uniform(0, 2, n), YIELD * f
 
 
 def _dev_return_map(fep, e, order, p, sh, bu, a, Y, accept, e0):
-    """fep_return_map_vm_dev on torch tensors -> the same dict as the host entry point, 'ep' the device copy of p."""
-    import torch
-    dev = torch.device('cuda', 0)
-    n = sh.size
-    up = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)    # noqa: E731
-    ed = up(e.T if order == 'F' else e)
-    ps, cs = (3, 1) if order == 'F' else (1, n)
-    pd = None if p is None else up(p)
-    shd, bud, ad, Yd = up(sh), up(bu), up(a), up(Y)
-    f64 = dict(dtype=torch.float64, device=dev)
-    S, DS = torch.zeros((4, n), **f64), torch.zeros((9, n), **f64)
-    ind, cnt = torch.zeros(n, dtype=torch.uint8, device=dev), torch.full((2,), -1, dtype=torch.int64, device=dev)
-    e0v = None if e0 is None else np.ascontiguousarray(e0, dtype=np.float64).ravel()
-    rc = fep.lib().fep_return_map_vm_dev(0, torch.cuda.current_stream().cuda_stream, n, ed.data_ptr(), ps, cs,
-                                         None if e0v is None else e0v.ctypes.data_as(ctypes.c_void_p),
-                                         None if pd is None else pd.data_ptr(), shd.data_ptr(), bud.data_ptr(),
-                                         ad.data_ptr(), Yd.data_ptr(), int(accept), S.data_ptr(), DS.data_ptr(),
-                                         ind.data_ptr(), cnt.data_ptr())
-    assert rc == 0
-    torch.cuda.synchronize()
-    c = cnt.cpu().numpy()
-    assert c[1] == 0
-    return {'s': S.cpu().numpy(), 'ds': DS.cpu().numpy(), 'ind_p': ind.cpu().numpy().astype(bool), 'n_plast': int(c[0]),
-            'ep': None if pd is None else pd.cpu().numpy()}
+    """fep_return_map_vm_dev -> the same dict as the host entry point, 'ep' the device copy of p."""
+    r = dev_return_map(fep, 'vm', e, order, p, e0, (sh, bu, a, Y), accept)
+    assert r['n_apex'] == 0
+    return dict(r, n_plast=r['n_smooth'])
 
 
 @pytest.mark.parametrize('order', ['C', 'F'])
@@ -107,7 +80,7 @@ def test_vm_kernel_without_hardening_is_the_dp_kernel_without_friction(fep):
     sh, bu, _, c = dp_materials(n)
     sh, c = sh * rng.uniform(0.7, 1.3, n), c * rng.uniform(0.7, 1.3, n)
     e = rng.normal(0, 1.2e-4, size=(3, n))
-    p = _traceless(rng, n, 4e-5)
+    p = traceless(rng, n, 4e-5)
     p_dp, p_vm = p.copy(), p.copy()
     dp = fep.construct_constitutive_problem(e, p_dp, sh, bu, np.zeros(n), c, apply_plastic_strain=True)
     vm = fep.construct_constitutive_problem_vm(e, p_vm, sh, bu, np.zeros(n), np.sqrt(2) * c, apply_plastic_strain=True)
@@ -137,7 +110,7 @@ def _case(fep, t):
     U = rng.normal(0, 1.0, size=(2, coord.shape[1]))
     nrm = vm_return_map(ref.orc.strain(ref.c['B'], U), None, *ref.m)['crit'] + YIELD
     U *= YIELD / np.median(nrm)                                             # the median point sits on the yield surface
-    ep = _traceless(rng, n, 0.1 * YIELD / (2 * SHEAR))
+    ep = traceless(rng, n, 0.1 * YIELD / (2 * SHEAR))
     f = rng.uniform(0.6, 1.4, n)
     per_point = (SHEAR * f, BULK * f[::-1], HARDENING * rng.uniform(0, 2, n), YIELD * rng.uniform(0.6, 1.4, n))
     e0 = rng.normal(0, 0.2 * YIELD / (2 * SHEAR), size=(4, 1))
@@ -198,11 +171,6 @@ def test_step_of_a_von_mises_context(fep, t):
 # ---------------------------------------------------------------------------------------
 # 8: the interface of the model switch
 # ---------------------------------------------------------------------------------------
-def _bytes_equal(a, b, keys=('s', 'ds', 'ind_p', 'F')):
-    return all(np.array_equal(a[k], b[k]) for k in keys) and np.array_equal(a['K'].data, b['K'].data) \
-        and (a['n_smooth'], a['n_apex']) == (b['n_smooth'], b['n_apex'])
-
-
 @pytest.mark.parametrize('t', ['P1', 'Q1'])
 def test_model_switch_interface(fep, t):
     elem, coord, _, U, ep, _, _ = _case(fep, t)
@@ -222,12 +190,12 @@ def test_model_switch_interface(fep, t):
     try:
         ra, rb = a.step(U, ep.copy()), b.step(U, ep.copy())
         assert ra['n_smooth'] > 0
-        assert _bytes_equal(ra, rb)                                         # the model before or after the materials
-        assert _bytes_equal(ra, a.step(U, ep.copy()))                       # two calls
+        assert bytes_equal(ra, rb)                                         # the model before or after the materials
+        assert bytes_equal(ra, a.step(U, ep.copy()))                       # two calls
         for which in (0, 1):
             assert a.kernel_names(which) != dp.kernel_names(which) and 'vm_kernel' in a.kernel_names(which)
             assert 'vm' not in dp.kernel_names(which)
-        assert _bytes_equal(before, dp.step(Udp, np.zeros((4, n))))         # the Drucker-Prager context beside them
+        assert bytes_equal(before, dp.step(Udp, np.zeros((4, n))))         # the Drucker-Prager context beside them
         l = fep.lib()
         m = ctypes.c_int(-1)
         assert l.fep_ctx_model(a.handle, ctypes.byref(m)) == 0 and m.value == 1
@@ -240,7 +208,7 @@ def test_model_switch_interface(fep, t):
         # back to Drucker-Prager: a context that never was a von Mises one computes the same
         b.set_model('dp')
         b.set_materials(*dp_materials(n))
-        assert b.model == 'dp' and _bytes_equal(before, b.step(Udp, np.zeros((4, n))))
+        assert b.model == 'dp' and bytes_equal(before, b.step(Udp, np.zeros((4, n))))
     finally:
         for c in (a, b, dp):
             c.close()

@@ -4,14 +4,9 @@ import numpy as np
 import pytest
 
 from conftest import relerr, relerr_points
+from model_ref import traceless
 from vm_cases import BULK, HARDENING, SHEAR, YIELD, cpu_cycle
 from vm_ref import vm_return_map
-
-
-def _traceless(rng, n, scale):
-    p = rng.normal(0, scale, size=(4, n))
-    p[[0, 1, 3]] -= (p[0] + p[1] + p[3]) / 3
-    return p
 
 
 def test_reduces_to_drucker_prager_without_friction():
@@ -23,7 +18,7 @@ def test_reduces_to_drucker_prager_without_friction():
     bu = 8.3e7 * rng.uniform(0.7, 1.3, n)
     c = 400.0 * rng.uniform(0.7, 1.3, n)
     e = rng.normal(0, 1.2e-4, size=(3, n))
-    p = _traceless(rng, n, 4e-5)
+    p = traceless(rng, n, 4e-5)
     ref = orc.return_map(e.copy(), p.copy(), sh, bu, np.zeros(n), c, apply_plastic_strain=True)
     got = vm_return_map(e, p, sh, bu, np.zeros(n), np.sqrt(2) * c, apply_plastic_strain=True)
     share = ref['ind_p'].mean()
@@ -37,7 +32,7 @@ def test_reduces_to_drucker_prager_without_friction():
 def _benchmark_points(rng, n):
     one = np.ones(n)
     e = rng.normal(0, 3e-3, size=(3, n))
-    p = _traceless(rng, n, 1e-3)
+    p = traceless(rng, n, 1e-3)
     return e, p, SHEAR * one, BULK * one, HARDENING * one, YIELD * one
 
 

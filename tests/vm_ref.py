@@ -7,6 +7,8 @@ Layout as for Drucker-Prager: strain e (3, n) = (eps11, eps22, gamma12); 4-vecto
 radius Y = sqrt(2/3) sigma_y > 0.  The back stress is a * p: the plastic strain is the only state."""
 import numpy as np
 
+from model_ref import RefContext
+
 IOTA = np.array([1.0, 1.0, 0.0, 1.0])
 
 
@@ -50,44 +52,12 @@ def vm_return_map(e, ep_prev, shear, bulk, a, Y, apply_plastic_strain=False, e0=
     return {'s': s, 'ds': ds, 'ind_p': ind, 'crit': crit, 'ep': ep, 'n_plast': int(ind.sum())}
 
 
-class VMRefContext:
-    """Shaped like tests/oracle_context.OracleContext; the model is von Mises whatever `set_model` is told last, except
-    that 'dp' is refused (the Drucker-Prager look-alike is OracleContext)."""
+def _vm_step_map(*a, **k):
+    """vm_return_map with the counters as a context's step reports them: the plastic count and no apex."""
+    r = vm_return_map(*a, **k)
+    return dict(r, n_smooth=r['n_plast'], n_apex=0)
 
-    def __init__(self, elem, coord, d1, d2, wf):
-        from oracle import fep_oracle as orc
-        self.orc, self.elem, self.coord, self.tab = orc, np.asarray(elem), np.asarray(coord, dtype=float), (d1, d2, wf)
-        self.n_int = self.elem.shape[1] * np.size(wf)
-        self.n_n = self.coord.shape[1]
-        self.model = 'vm'
 
-    def set_model(self, model):
-        if model != 'vm':
-            raise ValueError('VMRefContext restates the von Mises model only')
-
-    def set_materials(self, sh, bu, a, Y):
-        one = np.ones(self.n_int)
-        self.m = tuple(np.asarray(v, dtype=float).ravel() * one for v in (sh, bu, a, Y))
-        K, B, w, iD, jD, D = self.orc.elastic_setup(self.elem, self.coord, self.m[0], self.m[1], *self.tab)
-        self.c = dict(K_elast=K, B=B, D_elast=D, weight=w, iD=iD, jD=jD)
-
-    def geometry(self):
-        return None, None, self.c['weight'], None
-
-    def step(self, U, ep_prev=None, e0=None, apply_plastic_strain=False, want=()):
-        """As MeshContext.step on a von Mises context: `ep_prev` is updated in place on accept; every output is returned
-        whatever `want` names ('n_smooth' carries the plastic count, 'n_apex' is 0)."""
-        c = self.c
-        U2 = np.asarray(U, dtype=float).reshape((2, -1), order='F') if np.ndim(U) == 1 else np.asarray(U, dtype=float)
-        E = self.orc.strain(c['B'], U2)
-        accept = bool(apply_plastic_strain) and ep_prev is not None
-        r = vm_return_map(E, ep_prev, *self.m, apply_plastic_strain=accept, e0=e0)
-        if accept:
-            ep_prev[...] = r['ep']
-        K_t = self.orc.tangent(c['K_elast'], c['B'], c['D_elast'], c['weight'], r['ds'], c['iD'], c['jD'])
-        F = self.orc.internal_force(c['B'], c['weight'], r['s'])
-        return {'E': np.asarray(E), 'K': K_t.tocsr(), 'F': F, 's': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'],
-                'crit': r['crit'], 'n_smooth': r['n_plast'], 'n_apex': 0}
-
-    def close(self):
-        pass
+class VMRefContext(RefContext):
+    """The von Mises look-alike ('dp' is refused: the Drucker-Prager look-alike is OracleContext)."""
+    model, return_map, passed = 'vm', staticmethod(_vm_step_map), ('crit',)
