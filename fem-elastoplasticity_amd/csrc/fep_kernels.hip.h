@@ -45,7 +45,12 @@ __device__ __forceinline__ int dp_return_map(const double e[3], const double z[4
     const double Et1 = (e[1] + z[1]) - p[1];
     const double Et2 = (e[2] + z[2]) - p[2];
     const double Et3 = (0.0 + z[3]) - p[3];
-    const double tr = Et0 + Et1 + Et3;          // vol @ E_tr
+    // vol @ E_tr.  The reference forms it as a matrix product, whose zero times a non-finite shear strain is NaN; the term below
+    // is -0.0 for every finite Et2, which changes no bit of the sum (x + -0.0 == x, signed zeros included), and NaN otherwise,
+    // so that a NaN in the shear strain alone reaches Ktr and c1 and the point is elastic with a NaN stress, as in the reference
+    // (without it the clamp of n2 below swallowed the NaN, and a point the volume change puts at the apex came back with the
+    // finite stress c / eta)
+    const double tr = (Et0 + Et1 + Et3) + -fabs(0.0 * Et2);
     const double dv0 = DD * Et0 - I3 * Et1 - I3 * Et3;   // dev @ E_tr, DP:673
     const double dv1 = -I3 * Et0 + DD * Et1 - I3 * Et3;
     const double dv2 = 0.5 * Et2;
@@ -221,7 +226,9 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
     const double L_e = f_e / den_e;
     const double g_lo = left ? g_sl : g_sr;
     const double g_hi = left ? (e1 + e2 - 2.0 * e3) / (3.0 - sp) : (2.0 * e1 - e2 - e3) / (3.0 + sp);
-    const int branch = f <= 0.0 ? 0 : (L_s <= g_lo ? 1 : (L_e <= g_hi ? (left ? 2 : 3) : 4));
+    // (!(f > 0), not f <= 0: a NaN or Inf - Inf of the trial strain reaches f, and such a point is elastic with L = 0 and
+    // 1/den = 0, a NaN stress and the elastic tangent; under f <= 0 it fell through every test to the apex's finite stress)
+    const int branch = !(f > 0.0) ? 0 : (L_s <= g_lo ? 1 : (L_e <= g_hi ? (left ? 2 : 3) : 4));
     const bool ml = branch == 2, mr = branch == 3;
     // the branch's normal, strains and multiplier
     const double n1 = ml ? (1.0 + sp) / 2.0 : 1.0 + sp;

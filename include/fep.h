@@ -97,6 +97,22 @@ int fep_host_trim(void);
  *   shear,bulk,eta,c   (n_int) each
  *   s          out (4,n_int)   ds  out (9,n_int)   ind_p  out (n_int) 0/1 bytes
  *   counts     out [2] = {n_smooth, n_apex} (the numbers the reference logs at DP:730); may be NULL
+ *
+ * Non-finite inputs (all fep_return_map_* and, through them, fep_step_* and fep_assemble_*; tests/test_nonfinite_gpu.py).
+ * A NaN or an infinity in a DATA array is legal input; indices, tables and sizes must always be valid.
+ *   1. It is never hidden.  Von Mises and Mohr-Coulomb: a point whose trial strain (e + e0) - ep_prev has a NaN component
+ *      comes back with ind_p = 0, the elastic tangent, at least one NaN in s, its ep_prev untouched, and is counted nowhere
+ *      (every branch test is written so that a NaN fails it: crit > 0, !(f > 0)).  Drucker-Prager does what the reference
+ *      does: its products with the zeros of vol carry a non-finite shear strain into the trace, so a NaN in any strain
+ *      component gives an elastic point with a NaN stress, while +Inf in a normal strain passes crit1 > 0 and crit2 > 0 and
+ *      returns the apex's finite c / eta (DP:699): the reference's behaviour, kept.  A NaN in a material parameter is
+ *      outside this rule: it shows in s or ds only where the formulas of the point's branch read that parameter.
+ *   2. It is contained.  An output with no poisoned contributor (another point; in fep_step_*: a point of an element
+ *      without the poisoned node, an F entry or a K block no such element contributes to) is bit for bit what the same
+ *      call without the poison returns.  ds stays finite (the elastic tangent), so all of K does.
+ *   3. The solvers report it promptly: fep_solver_pcg_dev / fep_solver_amg_pcg_dev (below).
+ *   4. It leaves no trace: the same clean call on the same context, solver and hierarchy afterwards returns the same bits
+ *      as before (the ds / s scratch, the counters' scratch and the refreshed coarse operators are overwritten whole).
  */
 int fep_return_map_host(int device_id, int64_t n_int,
                         const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
@@ -158,7 +174,7 @@ int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
  *     (where max(|dd|, |h|) < 2^-500, dd and h are scaled by 2^600 for r, ca and sa: the squares stay out of the denormal range)
  *     ca = dd/r, sa = h/r (1, 0 at r = 0)    Pa = ((1+ca)/2, (1-ca)/2, sa/2), Pb = ((1-ca)/2, (1+ca)/2, -sa/2)
  *     (e1, e2, e3) = (ea, eb, ez) sorted descending and stable
- *     f = 2G[(1+s)e1 - (1-s)e3] + 2 lam s tr - 2c cos;          f <= 0: elastic (branch 0), L = 0
+ *     f = 2G[(1+s)e1 - (1-s)e3] + 2 lam s tr - 2c cos;          not f > 0 (f <= 0 or NaN): elastic (branch 0), L = 0
  *     g_sl = (e1-e2)/(1+s), g_sr = (e2-e3)/(1-s), g_la = (e1+e2-2e3)/(3-s), g_ra = (2e1-e2-e3)/(3+s)
  *   Every plastic branch but the apex is one formula on its normal n and its strains t:
  *     A n = 2G n + 2 lam s,  den = n.A n = 2G|n|^2 + 4 lam s^2,  L = (2G n.e + 2 lam s tr - 2c cos)/den,
@@ -265,7 +281,8 @@ int fep_ctx_device_ptr(const fep_ctx* ctx, int which, void** ptr_d);
  *   e0_h       4 host doubles (TSX initial strain zeta*e_init, TSX:1765) or NULL
  *   ep_prev    (4,n_int) or NULL; updated in place when accept != 0
  *   e_out      (3,n_int) C-order strain or NULL (not needed by the path itself)
- *   s, ds, ind_p   as in fep_return_map_*; any of them may be NULL when not wanted
+ *   s, ds, ind_p   as in fep_return_map_*; any of them may be NULL when not wanted (non-finite values in U, e0, ep_prev: the
+ *                  four rules stated there)
  *   k_data     out (nnz)     f_out  out (n_dof)
  *   counts     out [2] {n_smooth, n_apex} or NULL
  *
@@ -485,7 +502,11 @@ int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int3
  *                       iterations (<= 0: 50; sooner when the residual history says the test is about to be met) and the
  *                       iterate is frozen on the device at the iteration that met the test.
  *                       *state_out: 0 = max_iter reached, 1 = converged, 2 = breakdown (K[Q][:,Q] not positive
- *                       definite or non-finite values); x is 0 on constrained DOFs.  Synchronises `stream`. */
+ *                       definite or non-finite values); x is 0 on constrained DOFs.  Synchronises `stream`.
+ *                       A NaN in a K entry of a free row or in b at a free DOF is a breakdown at the FIRST read-back: the call
+ *                       returns FEP_OK with state 2 and *iters_out <= check_every, and x is the zero vector the call starts
+ *                       from, never a NaN.  b at constrained DOFs and K entries whose row and column are both constrained are
+ *                       selected away, not multiplied by zero: a NaN there changes no bit of x, iters or relres. */
 typedef struct fep_solver fep_solver;
 int fep_solver_create(fep_solver** solver_out, int device_id, int64_t n_n, const int32_t* indptr_h,
                       const int32_t* indices_h, const uint8_t* free_dof_h);

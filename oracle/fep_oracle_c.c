@@ -27,7 +27,7 @@ void oracle_return_map(int64_t n, const double* e, const double* e0, double* ep,
         if (ep) for (int i = 0; i < 4; ++i) p[i] = ep[i * n + k];
         for (int i = 0; i < 4; ++i) Et[i] = E[i] - p[i];                         /* DP:666-668 */
         const double G = shear[k], K = bulk[k], et = eta[k], cc = c[k];
-        const double tr = Et[0] + Et[1] + Et[3];
+        const double tr = (Et[0] + Et[1] + Et[3]) + -fabs(0.0 * Et[2]);           /* (0 * a non-finite shear strain is NaN, DP:682) */
         dv[0] = DD * Et[0] - I3 * Et[1] - I3 * Et[3];                            /* DP:673 */
         dv[1] = -I3 * Et[0] + DD * Et[1] - I3 * Et[3];
         dv[2] = 0.5 * Et[2];

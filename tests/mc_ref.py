@@ -78,7 +78,8 @@ def mc_return_map(e, ep_prev, shear, bulk, sin_phi, c, apply_plastic_strain=Fals
     g_lo, g_hi = np.where(left, g_sl, g_sr), np.where(left, g_la, g_ra)
     smooth = L_s <= g_lo
     edge = L_e <= g_hi                    # (g_lo <= L_e holds exactly when L_s >= g_lo: den_e (L_e - g_lo) = den_s (L_s - g_lo))
-    branch = np.where(f <= 0, 0, np.where(smooth, 1, np.where(edge, np.where(left, 2, 3), 4)))
+    # ~(f > 0), not f <= 0: a NaN f is elastic, and its stress NaN; it must not fall through every comparison to the apex
+    branch = np.where(~(f > 0), 0, np.where(smooth, 1, np.where(edge, np.where(left, 2, 3), 4)))
     ml, mr = branch == 2, branch == 3
     # the branch's normal, strains and multiplier
     n1 = np.where(ml, (1 + s) / 2, 1 + s)

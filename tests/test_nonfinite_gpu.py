@@ -1,0 +1,430 @@
+"""
+Non-finite values end to end (include/fep.h at fep_return_map_*): the cases of tests/nonfinite_cases.py,
+checked on the CPU by test_nonfinite_host.py, on the kernels.  Every poison is a NaN or an infinity in a data array; every
+index, table and size stays valid.
+
+  1. never hidden      von Mises, Mohr-Coulomb: a point whose trial strain has a NaN component is elastic, has the elastic
+                       tangent and a NaN in its stress, and no counter counts it.  Drucker-Prager: what the oracle does
+  2. contained         an output with no poisoned contributor equals the clean call's, bit for bit
+  3. reported promptly fep_solver_pcg_dev / fep_solver_amg_pcg_dev answer FEP_OK, state 2, at the first read-back
+  4. leaves no trace   the same clean call on the same context, solver and hierarchy afterwards returns the bits it returned before
+
+No new tolerance: values are compared under the bounds the same quantities already have (1e-13 of the array maximum and 1e-12
+per point for the return maps, C_K of test_element_route_gpu.py for K, 1e-9 for a Krylov run against the direct one).
+
+Where this module departs from a literal reading of what was asked of it, and why (each from the code):
+  - finiteness against the Drucker-Prager oracle and the von Mises restatement is compared up to the structural zeros of their
+    matrix products (nonfinite_cases.masks_agree): dev @ E and 2 Dev G + Vol K multiply zeros by the poison, the kernels write
+    dv2 = Et2 / 2, d02 = d12 = 0, d22 = G out.  The Mohr-Coulomb kernel and restatement agree entry for entry;
+  - a Krylov solve zeroes x before it iterates (pcg_init_kernel / mg_init; include/fep.h: "x = 0 on entry is implied"), so
+    "x as it was" is asserted of the zero vector it is handed: after a breakdown at the first read-back x holds +0.0 in every
+    entry, no iterate and no NaN;
+  - an accepting step cannot write a NaN into ep at a dirty point: rule 1 makes that point elastic, and only plastic points
+    write their plastic strain (`if (accept && ep && branch)`).  Asserted instead: ep at the dirty points is what went in, and
+    ep at every other point is the clean accepting step's, bit for bit.
+"""
+import ctypes as C
+from importlib import import_module
+
+import numpy as np
+import pytest
+
+import model_step_cases as msc
+import nonfinite_cases as nf
+import solver_cases as sc
+from conftest import dp_materials, relerr, relerr_points
+from elem_ref import ratio
+from model_ref import dev_return_map
+from routes import assert_route
+from test_element_route_gpu import C_K, C_RECORD
+from test_return_map_mp_gpu import _host
+from test_vcycle_gpu import _rhs
+
+pytestmark = pytest.mark.gpu
+
+EVERY = ('E', 's', 'ds', 'ind_p', 'K', 'F')
+POINT_KEYS = ('s', 'ds', 'ind_p', 'ep')
+
+
+# ---------------------------------------------------------------------------------------
+# 1. mesh-free return maps
+# ---------------------------------------------------------------------------------------
+def _call(fep, entry, model, e, order, p, e0, mats, accept):
+    """-> s, ds, ind_p, ep (the plastic strain after the call), n_smooth, n_apex of the `_host` or `_dev` entry point."""
+    if entry == 'host':
+        ev, ph = (np.asfortranarray(e) if order == 'F' else np.ascontiguousarray(e)), np.array(p, dtype=float)
+        r = _host(fep, model, ev, ph, e0, [np.ascontiguousarray(m) for m in mats], accept)
+        return dict(s=np.array(r['s']), ds=np.array(r['ds']), ind_p=np.asarray(r['ind_p']).astype(bool), ep=ph,
+                    n_smooth=int(r['n_smooth']), n_apex=int(r['n_apex']))
+    return dev_return_map(fep, model, e, order, p, e0, [np.asarray(m) for m in mats], accept)
+
+
+def _finite_close(got, ref, both):
+    """Per point (column): the entries at which both are finite agree to TOL_PT of the point's largest such reference entry."""
+    for j in range(ref.shape[1]):
+        m = both[:, j]
+        if m.any():
+            scale = np.abs(ref[m, j]).max()
+            assert np.abs(got[m, j] - ref[m, j]).max() <= nf.TOL_PT * scale, (j, got[:, j], ref[:, j])
+
+
+def _against_restatement(model, got, ref, at, accept, odd=None):
+    """The points `at` of a poisoned launch: flags, finiteness and the finite values against the restatement's.  `odd`: the
+    von Mises points with an infinite trial strain (nonfinite_cases.vm_infinite), held to what that function states."""
+    odd = np.zeros(got['ind_p'].size, dtype=bool) if odd is None else odd
+    at = np.flatnonzero(at) if np.asarray(at).dtype == bool else np.asarray(at)
+    at = at[~odd[at]]
+    assert np.array_equal(got['ind_p'][at], ref['ind_p'][at])
+    for key in ('s', 'ds') + (('ep',) if accept else ()):
+        g, r = {key: got[key][:, at]}, {key: ref[key][:, at]}
+        ok, both = nf.masks_agree(model, g, r, key)
+        assert ok, (model, key, np.isfinite(g[key]), np.isfinite(r[key]))
+        _finite_close(g[key], r[key], both)
+    assert got['ind_p'][odd].all() and not ref['ind_p'][odd].any()
+    assert np.isnan(got['s'][:, odd]).all() and np.isnan(got['ds'][:, odd]).all() and np.isnan(ref['s'][:, odd]).all()
+    assert (got['n_smooth'], got['n_apex']) == (ref['n_smooth'] + int(odd.sum()), ref['n_apex'])
+    assert got['n_smooth'] + got['n_apex'] == int(got['ind_p'].sum())
+
+
+def _rule_1(model, got, nan, mats):
+    assert not got['ind_p'][nan].any()
+    assert (~np.isfinite(got['s'][:, nan])).any(axis=0).all()               # no such point has an all-finite stress
+    assert np.isnan(got['s'][:, nan]).any(axis=0).all()
+    assert relerr_points(got['ds'][:, nan], nf.elastic_tangent(model, [np.asarray(m)[nan] for m in mats])) <= nf.TOL_PT
+    assert got['n_smooth'] + got['n_apex'] == int(got['ind_p'][~nan].sum())
+
+
+@pytest.mark.parametrize('order', ['C', 'F'])
+@pytest.mark.parametrize('model', nf.MODELS)
+def test_return_maps_with_poisoned_points(fep, model, order):
+    for k in range(len(nf.LAUNCHES)):
+        c = nf.point_launch(model, k)
+        (e, p, mats), (pe, pp, pm) = c['clean'], c['poisoned']
+        clean = np.ones(nf.N_POINTS, dtype=bool)
+        clean[c['lanes']] = False
+        nan = nf.trial_strain_nan(pe, pp)
+        for accept in (False, True):
+            ref = nf.restate(model, pe, pp, pm, None, accept)
+            for entry in ('host', 'dev'):
+                good = _call(fep, entry, model, e, order, p, None, mats, accept)
+                bad = _call(fep, entry, model, pe, order, pp, None, pm, accept)
+                for key in POINT_KEYS:                                      # rule 2
+                    assert np.array_equal(bad[key][..., clean], good[key][..., clean]), (entry, accept, key)
+                _against_restatement(model, bad, ref, c['lanes'], accept, nf.vm_infinite(model, pe, pp))
+                if model != 'dp':
+                    _rule_1(model, bad, nan, pm)
+                if not accept:                                              # a non-accepting call leaves ep alone, NaN and all
+                    assert np.array_equal(bad['ep'], pp, equal_nan=True) and np.array_equal(good['ep'], p)
+                else:                                                       # an elastic point never writes its plastic strain
+                    el = ~bad['ind_p']
+                    assert np.array_equal(bad['ep'][:, el], pp[:, el], equal_nan=True)
+                again = _call(fep, entry, model, e, order, p, None, mats, accept)      # rule 4
+                assert all(np.array_equal(again[key], good[key]) for key in POINT_KEYS)
+                assert (again['n_smooth'], again['n_apex']) == (good['n_smooth'], good['n_apex'])
+
+
+@pytest.mark.parametrize('model', nf.MODELS)
+def test_return_maps_with_a_nan_initial_strain(fep, model):
+    """Every point is poisoned: rules 1 and 4."""
+    e, p, mats = nf.point_launch(model, 0)['clean']
+    every = np.ones(nf.N_POINTS, dtype=bool)
+    z = np.array([1e-5, -2e-5, 3e-5, 1e-5])
+    for entry in ('host', 'dev'):
+        good = {a: _call(fep, entry, model, e, 'C', p, z, mats, a) for a in (False, True)}
+        for row in range(4):
+            e0 = z.copy()
+            e0[row] = nf.NAN
+            for accept in (False, True):
+                bad = _call(fep, entry, model, e, 'C', p, e0, mats, accept)
+                ref = nf.restate(model, e, p, mats, e0, accept)
+                _against_restatement(model, bad, ref, every, accept and model != 'dp')
+                if model != 'dp':
+                    _rule_1(model, bad, every, mats)
+                el = ~bad['ind_p']
+                assert np.array_equal(bad['ep'][:, el], p[:, el])
+                again = _call(fep, entry, model, e, 'C', p, z, mats, accept)
+                assert all(np.array_equal(again[key], good[accept][key]) for key in POINT_KEYS)
+                assert (again['n_smooth'], again['n_apex']) == (good[accept]['n_smooth'], good[accept]['n_apex'])
+
+
+# ---------------------------------------------------------------------------------------
+# 2. the step of a context
+# ---------------------------------------------------------------------------------------
+def _step_cases():
+    return [(m, t, kind, r) for m in nf.MODELS for t, kind in nf.mesh_cases() for r in msc.ROUTES[t]]
+
+
+def _same(a, b, keys=('E', 's', 'ds', 'ind_p', 'F')):
+    return all(np.array_equal(a[k], b[k]) for k in keys) and np.array_equal(a['K'].data, b['K'].data) \
+        and (a['n_smooth'], a['n_apex']) == (b['n_smooth'], b['n_apex'])
+
+
+def _flags_and_counters(model, got, Ep, mats, e0, dirty):
+    """ind_p and both counters against the restatement on the kernel's E, as test_element_route_gpu.py (Drucker-Prager) and
+    test_model_step_routes_gpu.py (points inside the floors left out) compare them."""
+    assert got['n_smooth'] + got['n_apex'] == int(got['ind_p'].sum())
+    if model == 'dp':
+        o = nf.restate(model, got['E'], Ep, mats, e0)
+        assert np.array_equal(got['ind_p'], o['ind_p']) and (got['n_smooth'], got['n_apex']) == (o['n_smooth'], o['n_apex'])
+        return
+    with np.errstate(all='ignore'):
+        o = msc.return_map(model, got['E'], Ep, mats, e0, False)
+        excl = msc.excluded(model, o, mats)
+    assert not excl[dirty].any()
+    keep = ~excl
+    msc.check_conditions(model, o, excl)
+    assert np.array_equal(got['ind_p'][keep], o['ind_p'][keep])
+    n_out = int(excl.sum())
+    assert int(got['ind_p'][keep].sum()) == int(o['ind_p'][keep].sum())
+    assert abs(got['n_smooth'] - o['n_smooth']) <= n_out and abs(got['n_apex'] - o['n_apex']) <= n_out
+
+
+@pytest.mark.parametrize('model,t,kind,route', _step_cases())
+def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, route):
+    c = nf.mesh_case(model, t, kind)
+    U, U_bad, Ep, mats, e0, dirty, dofs = (c[k] for k in ('U', 'U_bad', 'ep', 'mats', 'e0', 'points', 'dofs'))
+    if route in ('default', 'node'):
+        monkeypatch.delenv('FEP_ROUTE', raising=False)
+    else:
+        monkeypatch.setenv('FEP_ROUTE', route)
+    monkeypatch.setenv('FEP_VALIDATE_PLAN', '1')
+    ctx = fep.MeshContext(c['elem'], c['coord'])
+    try:
+        assert_route(ctx, 'patch' if route == 'default' else route)
+        if model != 'dp':
+            ctx.set_model(model)
+        ctx.set_materials(*mats)
+        kw = {} if e0 is None else {'e0': e0}
+        first = ctx.step(U, Ep.copy(), want=EVERY, **kw)
+        bad = ctx.step(U_bad, Ep.copy(), want=EVERY, **kw)
+        kf = ctx.step(U_bad, Ep.copy(), want=('K', 'F'), **kw)
+        k_only = ctx.step(U_bad, Ep.copy(), want=('K',), **kw)
+        f_only = ctx.step(U_bad, Ep.copy(), want=('F',), **kw)
+        K2, F2 = ctx.assemble(bad['ds'], bad['s'])
+        ep_bad, ep_good = Ep.copy(), Ep.copy()
+        acc_bad = ctx.step(U_bad, ep_bad, apply_plastic_strain=True, want=('ind_p',), **kw)
+        acc_good = ctx.step(U, ep_good, apply_plastic_strain=True, want=('ind_p',), **kw)
+        last = ctx.step(U, Ep.copy(), want=EVERY, **kw)
+        pattern = ctx.pattern()
+    finally:
+        ctx.close()
+    entries = nf.dirty_entries(c, pattern)
+    # rule 2: the clean locations
+    for key in ('E', 's', 'ds', 'ind_p'):
+        assert np.array_equal(bad[key][..., ~dirty], first[key][..., ~dirty]), key
+    assert np.array_equal(bad['F'][~dofs], first['F'][~dofs])
+    assert np.array_equal(bad['K'].data[~entries], first['K'].data[~entries])
+    # rule 1: the dirty locations
+    assert np.isnan(bad['E'][:, dirty]).all() and np.isnan(bad['s'][:, dirty]).any(axis=0).all()
+    assert not bad['ind_p'][dirty].any()
+    assert relerr_points(bad['ds'][:, dirty], nf.elastic_tangent(model, [np.asarray(m)[dirty] for m in mats])) <= nf.TOL_PT
+    assert np.array_equal(np.isnan(bad['F']), dofs) and np.isfinite(bad['F'][~dofs]).all()
+    assert np.isfinite(bad['K'].data).all()
+    with np.errstate(invalid='ignore'):
+        K, S_K, _, _ = nf.elem_ref(c, t, pattern, record=route == 'node').assemble(bad['ds'], None)
+    r_K, r_dirty = ratio(bad['K'].data, K, S_K), ratio(bad['K'].data[entries], K[entries], S_K[entries])
+    print(f'[K] {model} {t} {kind} {route}: ratio {r_K:.2f}, in the blocks with a dirty contributor {r_dirty:.2f}')
+    assert r_K <= C_K[t] and r_dirty <= C_K[t]
+    if route == 'node':
+        with np.errstate(invalid='ignore'):
+            Kx, W_K, _, _ = nf.elem_ref(c, t, pattern).assemble(bad['ds'], None, widened=True)
+        assert ratio(bad['K'].data, Kx, W_K) <= C_K[t] + C_RECORD
+    _flags_and_counters(model, bad, Ep, mats, e0, dirty)
+    _flags_and_counters(model, first, Ep, mats, e0, dirty)
+    assert bad['n_smooth'] + bad['n_apex'] == int(first['ind_p'][~dirty].sum())     # no dirty point is counted
+    assert bad['n_smooth'] <= first['n_smooth'] and bad['n_apex'] <= first['n_apex']
+    # the partial steps and assemble(ds, s) of the poisoned state
+    eq = lambda a, b: np.array_equal(a, b, equal_nan=True)                  # noqa: E731
+    assert eq(kf['K'].data, bad['K'].data) and eq(kf['F'], bad['F'])
+    assert eq(k_only['K'].data, bad['K'].data) and eq(f_only['F'], bad['F'])
+    assert eq(K2.data, bad['K'].data) and eq(F2, bad['F'])
+    for r in (kf, k_only, f_only):
+        assert (r['n_smooth'], r['n_apex']) == (bad['n_smooth'], bad['n_apex'])
+    # accepting: no NaN enters the state (module docstring)
+    assert np.array_equal(acc_bad['ind_p'], bad['ind_p']) and np.array_equal(acc_good['ind_p'], first['ind_p'])
+    assert np.array_equal(ep_bad[:, dirty], Ep[:, dirty]) and np.array_equal(ep_bad[:, ~dirty], ep_good[:, ~dirty])
+    assert first['ind_p'].any() and not np.array_equal(ep_good, Ep)
+    # rule 4
+    assert _same(last, first)
+
+
+# ---------------------------------------------------------------------------------------
+# 3. transform and the volume load
+# ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('t', ['P1', 'P4'])
+def test_transform_and_volume_load_with_a_poisoned_point(fep, t):
+    c = nf.mesh_case('dp', t, 'vertex')
+    elem, nq = c['elem'], msc.NQ[t]
+    rng = np.random.default_rng(5)
+    ctx = fep.MeshContext(elem, c['coord'])
+    try:
+        n_int, n_n = ctx.n_int, ctx.n_n
+        el = elem.shape[1] // 2
+        pt = el * nq + nq // 2
+        hit = np.zeros(n_n, dtype=bool)
+        hit[elem[:, el]] = True
+        lone = np.bincount(elem.ravel(), minlength=n_n) == 0                # nodes of the element the mesh has dropped
+        q, f = rng.normal(size=n_int), rng.normal(size=(2, n_int))
+        q_bad, f_bad = q.copy(), f.copy()
+        q_bad[pt] = f_bad[0, pt] = nf.NAN
+        t0, l0, u0 = ctx.transform(q), ctx.load_volume(f_v_int=f), ctx.load_volume(uniform=(0.37, -9.81))
+        t1, l1 = ctx.transform(q_bad), ctx.load_volume(f_v_int=f_bad)
+        u1 = ctx.load_volume(uniform=(nf.NAN, -9.81))
+        t2, l2, u2 = ctx.transform(q), ctx.load_volume(f_v_int=f), ctx.load_volume(uniform=(0.37, -9.81))
+    finally:
+        ctx.close()
+    # (a node of no element: transform's mean over nothing is 0 / 0, the load's sum over nothing 0)
+    assert np.array_equal(np.isnan(t0), lone) and np.isfinite(l0).all() and not l0[:, lone].any() and not (hit & lone).any()
+    assert np.array_equal(np.isnan(t1), hit | lone) and np.array_equal(t1[~hit], t0[~hit], equal_nan=True)
+    assert np.array_equal(np.isnan(l1[0]), hit) and np.array_equal(l1[0][~hit], l0[0][~hit]) and np.array_equal(l1[1], l0[1])
+    assert np.array_equal(np.isnan(u1[0]), ~lone) and np.array_equal(u1[1], u0[1])     # the uniform form: one component, every node
+    assert not u1[0][lone].any()
+    assert np.array_equal(t2, t0, equal_nan=True) and np.array_equal(l2, l0) and np.array_equal(u2, u0)
+
+
+# ---------------------------------------------------------------------------------------
+# 4. solvers
+# ---------------------------------------------------------------------------------------
+_PROBLEMS = {}
+FORMS = ('jacobi', 'amg-refresh', 'amg-stale')
+RTOL = 1e-10
+
+
+def _problem(fep, name):
+    """context, K_elast, the plastic tangent at solver_cases.displacement, free DOFs, coordinates, right-hand side; cached."""
+    if name not in _PROBLEMS:
+        elem, coord, et = sc.mesh(name)
+        ctx = fep.MeshContext(elem, coord, element_type=et)
+        ctx.set_materials(*dp_materials(ctx.n_int))
+        K_el = ctx.step(np.zeros(ctx.n_dof), want=('K',))['K']
+        r = ctx.step(sc.displacement(name), np.zeros((4, ctx.n_int)), want=('K',))
+        assert 0 < r['n_smooth'] + r['n_apex'] < ctx.n_int
+        qf = sc.free_dofs(name)
+        _PROBLEMS[name] = (ctx, K_el, r['K'], qf, coord, _rhs(qf)['random'])
+    return _PROBLEMS[name]
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _close_everything():
+    yield
+    for p in _PROBLEMS.values():
+        p[0].close()
+    _PROBLEMS.clear()
+
+
+def _solver(fep, name, form):
+    ctx, K_el, K, qf, coord, b = _problem(fep, name)
+    sol = fep.KrylovSolver(ctx, qf)
+    if form != 'jacobi':
+        sol.setup_amg(K_el, coord, coarse_nodes=sc.CASES[name]['coarse_nodes'], refresh=form == 'amg-refresh')
+        assert sol.amg_refresh is (form == 'amg-refresh') and len(sol.amg_levels) >= 2
+    return sol
+
+
+def _refresh(fep, sol, data):
+    """fep_solver_amg_refresh_dev on the values `data`: the coarse operators re-projected from them."""
+    import torch
+    k = torch.from_numpy(np.ascontiguousarray(data)).to(sol._dev)
+    rc = fep.lib().fep_solver_amg_refresh_dev(sol._h, C.c_void_p(torch.cuda.current_stream(sol._dev).cuda_stream),
+                                              C.c_void_p(k.data_ptr()))
+    torch.cuda.synchronize()
+    assert rc == 0
+
+
+def _solve(sol, form, data, b, **kw):
+    x = sol.solve_host(data, b, rtol=RTOL, precond='jacobi' if form == 'jacobi' else 'amg', **kw)
+    return x, sol.last['iters'], sol.last['relres'], sol.last['state']
+
+
+@pytest.mark.parametrize('form', FORMS)
+@pytest.mark.parametrize('name', nf.solver_names())
+def test_solvers_with_poisoned_operands(fep, name, form):
+    import torch
+    newton = import_module('fem-elastoplasticity_amd.newton')
+    ctx, K_el, K, qf, coord, b = _problem(fep, name)
+    sol = _solver(fep, name, form)
+    precond = 'jacobi' if form == 'jacobi' else 'amg'
+    try:
+        first = _solve(sol, form, K.data, b)
+        assert first[3] == 1 and first[1] > 0 and np.isfinite(first[0]).all()
+        for which in 'ab':                                                  # rule 3
+            data, rhs = nf.solver_poison(K, b, qf, which)
+            if form == 'amg-refresh' and which == 'a':
+                _refresh(fep, sol, data)
+            for ce in (5, 1):
+                x = torch.zeros(sol.n_dof, dtype=torch.float64, device=sol._dev)
+                out = sol.pcg(data, rhs, out=x, rtol=RTOL, max_iter=nf.MAX_ITER, check_every=ce, precond=precond)
+                assert out is x and sol.last['state'] == 2 and sol.last['iters'] <= ce, (which, ce, sol.last)
+                assert x.cpu().numpy().tobytes() == np.zeros(sol.n_dof).tobytes()
+            ops = newton._DeviceOps(ctx, sol, rtol=RTOL, max_iter=nf.MAX_ITER, amg=form != 'jacobi')
+            dU = ops.solve(ops.vec(data), ops.vec(rhs))
+            assert torch.isnan(dU).all() and ops.pcg_iters[-1] <= (50 if form == 'jacobi' else 10)     # the defaults of check_every
+        if form == 'amg-refresh':
+            _refresh(fep, sol, K.data)
+        for which in 'cd':                                                  # rule 2: the constrained DOFs
+            data, rhs = nf.solver_poison(K, b, qf, which)
+            got = _solve(sol, form, data, rhs)
+            assert np.array_equal(got[0], first[0]) and got[1:] == first[1:], (which, got[1:], first[1:])
+        last = _solve(sol, form, K.data, b)                                 # rule 4
+        assert np.array_equal(last[0], first[0]) and last[1:] == first[1:]
+    finally:
+        sol.close()
+
+
+@pytest.mark.parametrize('name', nf.solver_names())
+def test_spmv_with_a_poisoned_node(fep, name):
+    ctx, K_el, K, qf, coord, b = _problem(fep, name)
+    sol = fep.KrylovSolver(ctx, qf)
+    try:
+        rng = np.random.default_rng(8)
+        x = rng.normal(size=sol.n_dof)
+        j = int(np.flatnonzero(qf)[qf.sum() // 2]) // 2                     # the node of the middle free DOF
+        x_bad = x.copy()
+        x_bad[2 * j: 2 * j + 2] = nf.NAN
+        hit = np.zeros(sol.n_dof, dtype=bool)                               # the rows with a stored entry in the node's columns
+        rows = np.repeat(np.arange(sol.n_dof), np.diff(K.indptr))
+        hit[rows[K.indices // 2 == j]] = True
+        assert 4 <= hit.sum() < 0.1 * sol.n_dof
+        for masked in (False, True):
+            xs, xb = (x, x_bad) if not masked else (x * qf, np.where(qf, x_bad, 0.0))
+            y0 = sol.spmv(K.data, xs, masked=masked).cpu().numpy()
+            y1 = sol.spmv(K.data, xb, masked=masked).cpu().numpy()
+            y2 = sol.spmv(K.data, xs, masked=masked).cpu().numpy()
+            want = hit & qf if masked else hit
+            assert np.array_equal(np.isnan(y1), want) and np.array_equal(y1[~want], y0[~want]) and np.array_equal(y2, y0)
+    finally:
+        sol.close()
+
+
+# ---------------------------------------------------------------------------------------
+# 5. the load-step loop recovers
+# ---------------------------------------------------------------------------------------
+_RUNS = {}
+
+
+def _footing(fep, monkeypatch, linear_solver, k=None):
+    key = (linear_solver, k)
+    if key not in _RUNS:
+        calls = None if k is None else nf.failing_solve(monkeypatch, k)
+        _RUNS[key] = fep.solve_strip_footing(**nf.FOOTING, linear_solver=linear_solver)
+        monkeypatch.undo()
+        assert calls is None or calls[0] > k
+    return _RUNS[key]
+
+
+@pytest.mark.parametrize('linear_solver', ['direct', 'pcg', 'amg'])
+def test_load_step_loop_recovers_from_a_failed_solve(fep, monkeypatch, linear_solver):
+    """The first solve of the second load step returns what a failed solve returns, on the real ops and solver object: the
+    step is halved, the same solver goes on, and the run reaches zeta_max with the direct run's sequence and displacement
+    (1e-9: what test_solver_gpu.py holds a Krylov run to against the direct one)."""
+    clean = _footing(fep, monkeypatch, 'direct')
+    k = 1 + clean['newton_its'][0] + 1
+    direct = _footing(fep, monkeypatch, 'direct', k)
+    bad = _footing(fep, monkeypatch, linear_solver, k)
+    nf.check_recovery(clean, bad, nf.FOOTING['zeta_max'])
+    assert np.array_equal(bad['zeta'], direct['zeta']) and len(bad['U']) == len(direct['U'])
+    assert bad['counts'][-1] == direct['counts'][-1] and sum(bad['counts'][-1]) > 0
+    print(linear_solver, 'zeta', bad['zeta'][:4], 'U against direct', relerr(bad['U_last'], direct['U_last']))
+    assert relerr(bad['U_last'], direct['U_last']) <= 1e-9
+    for a, b in zip(bad['U'], direct['U']):
+        assert relerr(a, b) <= 1e-9

@@ -12,11 +12,12 @@ import ctypes
 import numpy as np
 import pytest
 
-from conftest import dp_materials, relerr, relerr_points, relerr_rows
+from conftest import relerr, relerr_points, relerr_rows
 from mc_cases import COHESION, SIN_PHI, YOUNG
 from mc_ref import MCRefContext
 from meshes import jitter, rect
 from model_ref import DEV_ENTRY, dev_return_map
+from nonfinite_cases import thousand as _thousand
 from return_map_mp_cases import check, check_flags, errors, fixture, groups, merge
 from test_mc_gpu import MESHES, TOL_K, TOL_K_ROW
 
@@ -115,35 +116,6 @@ def test_nearly_hydrostatic_step_gives_the_elastic_stiffness(fep, t):
 # ---------------------------------------------------------------------------------------
 # the sum of the per-workgroup counters at its loop edges
 # ---------------------------------------------------------------------------------------
-def _thousand(model):
-    """(e, p, materials, the restatement's result, class per point: 0 elastic, 1 counts[0], 2 counts[1]) of the 1000-point set
-    of the model's mesh-free test (Drucker-Prager: test_parity_gpu's random points with a band at the apex)."""
-    n = 1000
-    if model == 'mc':
-        from mc_cases import points
-        from mc_ref import mc_return_map
-        e, p, _, *mats = points(n, False, 100 + n)
-        ref = mc_return_map(e, p, *mats)
-        return e, p, mats, ref, np.where(ref['branch'] == 0, 0, np.where(ref['branch'] == 4, 2, 1))
-    if model == 'vm':
-        from test_vm_gpu import _points
-        from vm_ref import vm_return_map
-        e, p, _, *mats = _points(n, False, 100 + n)
-        ref = vm_return_map(e, p, *mats)
-        return e, p, mats, ref, ref['ind_p'].astype(np.int64)
-    from oracle import fep_oracle as orc
-    rng = np.random.default_rng(99)
-    sh, bu, eta, c = dp_materials(n)
-    mats = [sh * rng.uniform(0.5, 2, n), bu * rng.uniform(0.5, 2, n), eta * rng.uniform(0.5, 1.5, n), c * rng.uniform(0.5, 2, n)]
-    e = rng.normal(0, 2e-4, size=(3, n))
-    e[:, : n // 20] += 4e-4                                                 # a band of apex points
-    p = rng.normal(0, 2e-5, size=(4, n))
-    ref = orc.return_map(e, p.copy(), *mats, False)
-    apex = ref['ind_p'] & (np.abs(ref['ds']).sum(axis=0) == 0)              # the apex tangent is zero
-    assert int(apex.sum()) == ref['n_apex']
-    return e, p, mats, ref, np.where(apex, 2, ref['ind_p'].astype(np.int64))
-
-
 @pytest.mark.parametrize('n_blocks', [1024, 8192])
 @pytest.mark.parametrize('model', ['dp', 'vm', 'mc'])
 def test_block_counters_are_summed_past_one_load_and_one_round(fep, model, n_blocks):
