@@ -121,7 +121,7 @@ struct fep_ctx {
     double *s_int = nullptr, *ds_int = nullptr;     // used when the caller does not ask for s / ds
     uint2* blk_counts = nullptr;
     int n_count_blocks = 0;
-    // persistent device buffers of the *_host entry points (u, ep, e, s, ds, ind_p, k, f, counts, q)
+    // persistent device buffers of the *_host entry points (u, ep, e, s, ds, ind_p, k, f, counts, q, node values, e0_field)
     void* hbuf[12] = {};
     size_t hbuf_bytes[12] = {};
     // host copies of the pattern
@@ -269,6 +269,7 @@ extern "C" int fep_sync(int device_id, void* stream) {
 // ---------------------------------------------------------------------------------------
 // a2 mesh-free
 // ---------------------------------------------------------------------------------------
+constexpr int kFieldBuffer = 11;                        // staging buffer of a host entry point's e0_field (engine and context alike)
 static E0 make_e0(const double* e0_h) {
     E0 z;
     for (int i = 0; i < 4; ++i) z.v[i] = e0_h ? e0_h[i] : 0.0;
@@ -313,13 +314,23 @@ static constexpr decltype(&p1_point_kernel) kP1PointKernel[kModels] = {p1_point_
 template <int NP, int NQ>
 static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>};
 static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == kModels - 1, "table order");
+// The same families with an initial-strain field (fep_*_field_*): every model has a row in each, Drucker-Prager too, so these
+// are indexed by the model itself.
+static constexpr decltype(&return_map_field_kernel<FEP_MODEL_DP>) kReturnMapFieldKernel[kModels] = {
+    return_map_field_kernel<FEP_MODEL_DP>, return_map_field_kernel<FEP_MODEL_VM>, return_map_field_kernel<FEP_MODEL_MC>};
+static constexpr decltype(&p1_point_field_kernel<FEP_MODEL_DP>) kP1PointFieldKernel[kModels] = {
+    p1_point_field_kernel<FEP_MODEL_DP>, p1_point_field_kernel<FEP_MODEL_VM>, p1_point_field_kernel<FEP_MODEL_MC>};
+template <int NP, int NQ>
+static constexpr decltype(&point_field_kernel<FEP_MODEL_DP, NP, NQ>) kPointFieldKernel[kModels] = {
+    point_field_kernel<FEP_MODEL_DP, NP, NQ>, point_field_kernel<FEP_MODEL_VM, NP, NQ>, point_field_kernel<FEP_MODEL_MC, NP, NQ>};
 
 // (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises or sin_phi, c of Mohr-Coulomb)
 static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n_int,
                                const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                const double* e0_h, double* ep_prev_d,
                                const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
-                               int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+                               int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d,
+                               const double* field_d = nullptr, double scale = 0.0) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_d || !shear_d || !bulk_d || !eta_d || !c_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(device_id));
@@ -328,9 +339,14 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     const unsigned n_blocks = grid_for(n_int, kBlock);
     uint2* blk = nullptr;
     if (counts_d) FEP_TRY(rm_scratch(device_id, st, n_blocks, &blk));
-    hipLaunchKernelGGL(kReturnMapKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
-                       n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
-                       shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
+    if (field_d)
+        hipLaunchKernelGGL(kReturnMapFieldKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
+                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
+                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk, field_d, scale);
+    else
+        hipLaunchKernelGGL(kReturnMapKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
+                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
+                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
     HIP_TRY(hipGetLastError());
     if (counts_d) {
         hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)n_blocks, blk, (unsigned long long*)counts_d);
@@ -366,6 +382,16 @@ extern "C" int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
                                shear_d, bulk_d, sin_phi_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
 }
 
+extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, int64_t n_int,
+                                        const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                        const double* e0_h, const double* e0_field_d, double e0_scale, double* ep_prev_d,
+                                        const double* shear_d, const double* bulk_d, const double* m3_d, const double* m4_d,
+                                        int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    if (model < 0 || model >= kModels || !e0_field_d) return FEP_EINVAL;
+    return return_map_dev_impl(model, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, m3_d, m4_d, accept, s_d, ds_d, ind_p_d, counts_d, e0_field_d, e0_scale);
+}
+
 // persistent device buffer `idx` of a context's host entry points (sizes are fixed by the mesh: allocated once)
 static int ctx_buf(fep_ctx* c, int idx, int64_t bytes, void** out) {
     if (bytes <= 0) bytes = 1;
@@ -397,7 +423,8 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
                                 const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
                                 const double* e0_h, double* ep_prev_h,
                                 const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
-                                int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+                                int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h,
+                                const double* field_h = nullptr, double scale = 0.0) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_h || !shear_h || !bulk_h || !eta_h || !c_h)) return FEP_EINVAL;
     if (counts_h) { counts_h[0] = 0; counts_h[1] = 0; }
@@ -410,7 +437,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     fep_stage::Engine* E = nullptr;
     FEP_TRY(fep_stage::engine(device_id, &E));
     fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *e = nullptr, *ep = nullptr, *sh, *bu, *et, *cc, *s = nullptr, *ds = nullptr, *ip = nullptr, *cnt;
+    void *e = nullptr, *ep = nullptr, *sh, *bu, *et, *cc, *s = nullptr, *ds = nullptr, *ip = nullptr, *cnt, *fld = nullptr;
     FEP_TRY(E->buffer(0, span * (int64_t)sizeof(double), &e));
     if (ep_prev_h) FEP_TRY(E->buffer(1, 4 * nb, &ep));
     FEP_TRY(E->buffer(2, nb, &sh)); FEP_TRY(E->buffer(3, nb, &bu)); FEP_TRY(E->buffer(4, nb, &et)); FEP_TRY(E->buffer(5, nb, &cc));
@@ -418,12 +445,14 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     if (ds_h) FEP_TRY(E->buffer(7, 9 * nb, &ds));
     if (ind_p_h) FEP_TRY(E->buffer(8, n_int, &ip));
     FEP_TRY(E->buffer(9, 2 * sizeof(int64_t), &cnt));
+    if (field_h) FEP_TRY(E->buffer(kFieldBuffer, 4 * nb, &fld));
     static const bool timing = fep_tune("FEP_TIME_HOST") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     FEP_TRY(E->h2d(e, e_h, (size_t)span * sizeof(double)));
     if (ep_prev_h) FEP_TRY(E->h2d(ep, ep_prev_h, (size_t)(4 * nb)));
     FEP_TRY(E->h2d(sh, shear_h, (size_t)nb)); FEP_TRY(E->h2d(bu, bulk_h, (size_t)nb));
     FEP_TRY(E->h2d(et, eta_h, (size_t)nb)); FEP_TRY(E->h2d(cc, c_h, (size_t)nb));
+    if (field_h) FEP_TRY(E->h2d(fld, field_h, (size_t)(4 * nb)));
     if (timing) {
         (void)hipStreamSynchronize(E->stream);
         std::fprintf(stderr, "[fep] return_map_host: inputs on the device after %.3f ms\n",
@@ -431,7 +460,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     }
     FEP_TRY(return_map_dev_impl(model, device_id, E->stream, n_int, (const double*)e, e_pt_stride, e_comp_stride, e0_h,
                                 (double*)ep, (const double*)sh, (const double*)bu, (const double*)et, (const double*)cc, accept,
-                                (double*)s, (double*)ds, (uint8_t*)ip, (int64_t*)cnt));
+                                (double*)s, (double*)ds, (uint8_t*)ip, (int64_t*)cnt, (const double*)fld, scale));
     if (s_h) FEP_TRY(E->d2h(s_h, s, (size_t)(4 * nb)));
     if (ds_h) FEP_TRY(E->d2h(ds_h, ds, (size_t)(9 * nb)));
     if (ind_p_h) FEP_TRY(E->d2h(ind_p_h, ip, (size_t)n_int));
@@ -472,6 +501,16 @@ extern "C" int fep_return_map_mc_host(int device_id, int64_t n_int,
                                       int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_MC, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
                                    bulk_h, sin_phi_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
+}
+
+extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int,
+                                         const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                                         const double* e0_h, const double* e0_field_h, double e0_scale, double* ep_prev_h,
+                                         const double* shear_h, const double* bulk_h, const double* m3_h, const double* m4_h,
+                                         int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+    if (model < 0 || model >= kModels || !e0_field_h) return FEP_EINVAL;
+    FEP_GUARD(return_map_host_impl(model, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, m3_h, m4_h, accept, s_h, ds_h, ind_p_h, counts_h, e0_field_h, e0_scale))
 }
 
 using fep_host::Symbolic;
@@ -1344,8 +1383,10 @@ static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const d
 // Von Mises and Mohr-Coulomb contexts (FEP_MODEL_VM, _MC): stage A is the model's point kernel (geometry, strain, return map; s / ds to the
 // caller's arrays or the context's scratch), stage B exactly what fep_assemble_dev launches for the route (the element routes'
 // element_kernel in its assembly-only form, then the route's assembly kernel), stage C the COO form's force gather.
+// `field_d` (fep_step_field_*): the same three stages with the *_field_kernel of the context's model, Drucker-Prager included.
 static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
-                   double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt) {
+                   double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt,
+                   const double* field_d = nullptr, double scale = 0.0) {
     if (!c->ds_int || !c->s_int || !c->vm_blk) return FEP_ESTATE;
     if (k_data_d && !ds_d) ds_d = c->ds_int;
     if (f_out_d && !s_d) s_d = c->s_int;
@@ -1357,6 +1398,17 @@ static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, doub
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
+        if (field_d) {
+            if constexpr (ET::type == FEP_P1)
+                hipLaunchKernelGGL(kP1PointFieldKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
+                                   c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d,
+                                   ds_d, ind_p_d, blk, field_d, scale);
+            else
+                hipLaunchKernelGGL((kPointFieldKernel<ET::NP, ET::NQ>[c->model]), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e,
+                                   c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c,
+                                   c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale);
+            return FEP_OK;
+        }
         if constexpr (ET::type == FEP_P1)
             hipLaunchKernelGGL(kP1PointKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->p1tab,
                                u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
@@ -1464,6 +1516,28 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     return FEP_OK;
 }
 
+extern "C" int fep_step_field_dev(fep_ctx* c, void* stream, const double* u_d, const double* e0_h,
+                                  const double* e0_field_d, double e0_scale,
+                                  double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d,
+                                  uint8_t* ind_p_d, double* k_data_d, double* f_out_d, int64_t* counts_d) {
+    if (!c || !u_d || !e0_field_d) return FEP_EINVAL;
+    if (!fep_aligned16(u_d) || !fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
+    if (!c->have_materials) return FEP_ESTATE;
+#ifdef FEP_ABLATION
+    if (c->route == Route::GenNode) return FEP_ESTATE;
+#endif
+    FEP_TRY(fep_set_device(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    // (a von Mises / Mohr-Coulomb context holds all three since fep_ctx_set_model; Drucker-Prager gets them here, once)
+    FEP_TRY(point_scratch(c, st, true, true));
+    if (!c->vm_blk) {
+        FEP_TRY(scratch_alloc_allowed(st));
+        FEP_TRY(dmalloc(c, &c->vm_blk, (int64_t)grid_for(c->n_int, kBlock)));
+    }
+    return step_model(c, st, u_d, make_e0(e0_h), ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d,
+                      (unsigned long long*)counts_d, e0_field_d, e0_scale);
+}
+
 extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, const double* s_d,
                                 double* k_data_d, double* f_out_d) {
     if (!c) return FEP_EINVAL;
@@ -1488,14 +1562,15 @@ extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, co
 
 static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const double* e0_h, double* ep_prev_h, int accept,
                           double* e_out_h, double* s_h, double* ds_h, uint8_t* ind_p_h,
-                          double* k_data_h, double* f_out_h, int64_t* counts_h) {
+                          double* k_data_h, double* f_out_h, int64_t* counts_h,
+                          const double* field_h = nullptr, double scale = 0.0) {
     if (!c || !u_h) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
     const int64_t nb = c->n_int * (int64_t)sizeof(double);
     fep_stage::Engine* E = nullptr;
     FEP_TRY(fep_stage::engine(c->device, &E));
     fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *u, *ep = nullptr, *eo = nullptr, *s = nullptr, *ds = nullptr, *ip = nullptr, *kd = nullptr, *f = nullptr, *cnt;
+    void *u, *ep = nullptr, *eo = nullptr, *s = nullptr, *ds = nullptr, *ip = nullptr, *kd = nullptr, *f = nullptr, *cnt, *fld = nullptr;
     FEP_TRY(ctx_buf(c, 0, c->n_dof * (int64_t)sizeof(double), &u));
     if (ep_prev_h) FEP_TRY(ctx_buf(c, 1, 4 * nb, &ep));
     if (e_out_h) FEP_TRY(ctx_buf(c, 2, 3 * nb, &eo));
@@ -1508,8 +1583,15 @@ static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const do
     if (u_planar) FEP_TRY(E->h2d_interleave2(u, u_h, (size_t)c->n_n));
     else FEP_TRY(E->h2d(u, u_h, (size_t)c->n_dof * sizeof(double)));
     if (ep_prev_h) FEP_TRY(E->h2d(ep, ep_prev_h, (size_t)(4 * nb)));
-    FEP_TRY(fep_step_dev(c, E->stream, (const double*)u, e0_h, (double*)ep, accept, (double*)eo, (double*)s, (double*)ds,
-                         (uint8_t*)ip, (double*)kd, (double*)f, (int64_t*)cnt));
+    if (field_h) {
+        FEP_TRY(ctx_buf(c, kFieldBuffer, 4 * nb, &fld));
+        FEP_TRY(E->h2d(fld, field_h, (size_t)(4 * nb)));
+        FEP_TRY(fep_step_field_dev(c, E->stream, (const double*)u, e0_h, (const double*)fld, scale, (double*)ep, accept,
+                                   (double*)eo, (double*)s, (double*)ds, (uint8_t*)ip, (double*)kd, (double*)f, (int64_t*)cnt));
+    } else {
+        FEP_TRY(fep_step_dev(c, E->stream, (const double*)u, e0_h, (double*)ep, accept, (double*)eo, (double*)s, (double*)ds,
+                             (uint8_t*)ip, (double*)kd, (double*)f, (int64_t*)cnt));
+    }
     // the largest result first: its transfer hides the others' set-up
     if (k_data_h) FEP_TRY(E->d2h(k_data_h, kd, (size_t)c->nnz * sizeof(double)));
     if (f_out_h) FEP_TRY(E->d2h(f_out_h, f, (size_t)c->n_dof * sizeof(double)));
@@ -1526,6 +1608,14 @@ extern "C" int fep_step_host(fep_ctx* c, const double* u_h, const double* e0_h, 
                              double* e_out_h, double* s_h, double* ds_h, uint8_t* ind_p_h,
                              double* k_data_h, double* f_out_h, int64_t* counts_h) {
     FEP_GUARD(step_host_impl(c, false, u_h, e0_h, ep_prev_h, accept, e_out_h, s_h, ds_h, ind_p_h, k_data_h, f_out_h, counts_h))
+}
+
+extern "C" int fep_step_field_host(fep_ctx* c, const double* u_h, const double* e0_h, const double* e0_field_h, double e0_scale,
+                                   double* ep_prev_h, int accept, double* e_out_h, double* s_h, double* ds_h, uint8_t* ind_p_h,
+                                   double* k_data_h, double* f_out_h, int64_t* counts_h) {
+    if (!e0_field_h) return FEP_EINVAL;
+    FEP_GUARD(step_host_impl(c, false, u_h, e0_h, ep_prev_h, accept, e_out_h, s_h, ds_h, ind_p_h, k_data_h, f_out_h, counts_h,
+                             e0_field_h, e0_scale))
 }
 
 extern "C" int fep_step_host_planar(fep_ctx* c, const double* u2_h, const double* e0_h, double* ep_prev_h, int accept,
@@ -1671,6 +1761,38 @@ static int load_volume_host_impl(fep_ctx* c, const double* hatp_h, const double*
 extern "C" int fep_load_volume_host(fep_ctx* c, const double* hatp_h, const double* f_v_h, double fx, double fy,
                                     const double* weight_h, double* f_out_h) {
     FEP_GUARD(load_volume_host_impl(c, hatp_h, f_v_h, fx, fy, weight_h, f_out_h))
+}
+
+// Coordinates of the integration points (fep.h): point_coords_kernel, the table as a kernel argument
+extern "C" int fep_ctx_point_coords_dev(fep_ctx* c, void* stream, const double* hatp_h, double* xq_d) {
+    if (!c || !hatp_h || !xq_d) return FEP_EINVAL;
+    if (c->n_p * c->n_q > kLoadTabMax) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    if (c->n_int == 0) return FEP_OK;
+    LoadTab tab{};
+    for (int i = 0; i < c->n_p * c->n_q; ++i) tab.h[i] = hatp_h[i];
+    hipLaunchKernelGGL(point_coords_kernel, dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, c->n_e,
+                       c->n_n, c->n_p, c->n_q, c->elem, c->coords, tab, xq_d);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+static int point_coords_host_impl(fep_ctx* c, const double* hatp_h, double* xq_h) {
+    if (!c || !hatp_h || !xq_h) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    fep_stage::Engine* E = nullptr;
+    FEP_TRY(fep_stage::engine(c->device, &E));
+    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
+    const size_t nb = (size_t)c->n_int * sizeof(double);
+    void* o = nullptr;
+    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &o));
+    FEP_TRY(fep_ctx_point_coords_dev(c, E->stream, hatp_h, (double*)o));
+    if (c->n_int > 0) FEP_TRY(E->d2h(xq_h, o, 2 * nb));
+    return call.finish();
+}
+
+extern "C" int fep_ctx_point_coords_host(fep_ctx* c, const double* hatp_h, double* xq_h) {
+    FEP_GUARD(point_coords_host_impl(c, hatp_h, xq_h))
 }
 
 // Incidence of the loaded nodes, built per call (n_e_s is of the order of sqrt(n_e)), packed with the edge table into one

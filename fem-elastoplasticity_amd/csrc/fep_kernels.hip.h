@@ -405,15 +405,31 @@ __device__ __forceinline__ void store_point_off(unsigned kb, unsigned k32, int64
 // ---------------------------------------------------------------------------------------
 struct E0 { double v[4]; };
 
+// Initial strain of point k of n with a field: z_i = e0_i + scale * field[i * n + k], the product rounded before the sum (no
+// contraction), so that a host restatement reproduces it.  Four coalesced 8-byte loads per lane, as ep_prev.  An infinite z_i
+// becomes a NaN: the return maps give a point with a NaN trial strain the elastic tangent and a NaN stress (fep.h, non-finite
+// rules 1 and 2), while von Mises and Mohr-Coulomb turn an infinite one into N = Inf / Inf and a NaN tangent, which would carry
+// one bad value of the field into K.
+__device__ __forceinline__ void field_e0(const E0& e0, const double* __restrict__ field, double scale, int64_t n, int64_t k,
+                                         double z[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double v = e0.v[i] + scale * field[i * n + k];
+        z[i] = __builtin_isinf(v) ? __builtin_nan("") : v;
+    }
+}
+
 // One body for every model (model_return_map): `m3` / `m4` = the model's third and fourth material array per point.  Per-workgroup
-// counters, summed by counts_reduce_kernel (no global atomics).
-template <int MODEL>
+// counters, summed by counts_reduce_kernel (no global atomics).  FIELD: the initial strain of a point is field_e0 of `field`, `scale`
+// (the *_field_kernel wrappers); without it the two arguments are not read.
+template <int MODEL, bool FIELD = false>
 __device__ __forceinline__ void
 return_map_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ecs, const E0& e0,
                 double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
                 const double* __restrict__ m3, const double* __restrict__ m4, int accept,
                 double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
-                uint2* blk_counts) {
+                uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (k < n) {
@@ -421,7 +437,13 @@ return_map_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ec
         double p[4] = {0.0, 0.0, 0.0, 0.0};
         if (ep) { p[0] = ep[k]; p[1] = ep[n + k]; p[2] = ep[2 * n + k]; p[3] = ep[3 * n + k]; }
         double s[4], d[6];
-        branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
+        if constexpr (FIELD) {
+            double z[4];
+            field_e0(e0, field, scale, n, k, z);
+            branch = model_return_map<MODEL>(ev, z, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
+        } else {
+            branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
+        }
         store_point(k, n, s, d, branch, S, DS, indp);
         if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
     }
@@ -441,6 +463,11 @@ __global__ void __launch_bounds__(kBlock) return_map_vm_kernel(FEP_RETURN_MAP_AR
 }
 __global__ void __launch_bounds__(kBlock) return_map_mc_kernel(FEP_RETURN_MAP_ARGS) {
     return_map_body<FEP_MODEL_MC>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
+template <int MODEL>
+__global__ void __launch_bounds__(kBlock)
+return_map_field_kernel(FEP_RETURN_MAP_ARGS, const double* __restrict__ field, double scale) {
+    return_map_body<MODEL, true>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts, field, scale);
 }
 #undef FEP_RETURN_MAP_ARGS
 
@@ -1252,6 +1279,31 @@ load_volume_kernel(int64_t n_n, int64_t n_e, int n_p, int n_q, const int32_t* __
     *reinterpret_cast<double2*>(f_out + 2 * n) = make_double2(a1, a2);
 }
 
+// Coordinates of every integration point (what an initial-strain field is evaluated at): xq[c, e * n_q + q] = sum over a ascending
+// of hatp[a, q] * coords[c, elem[a, e]], no contraction.  One lane per point; `coords` is planar (2, n_n).
+__global__ void __launch_bounds__(kBlock)
+point_coords_kernel(int64_t n_e, int64_t n_n, int n_p, int n_q, const int32_t* __restrict__ elem,
+                    const double* __restrict__ coords, LoadTab tab, double* __restrict__ xq) {
+#pragma clang fp contract(off)
+    __shared__ double hat[kLoadTabMax];
+    for (int i = threadIdx.x; i < n_p * n_q; i += kBlock) hat[i] = tab.h[i];
+    __syncthreads();
+    const int64_t n_int = n_e * n_q;
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n_int) return;
+    const int64_t e = k / n_q;
+    const int q = (int)(k - e * n_q);
+    double x = 0.0, y = 0.0;
+    for (int a = 0; a < n_p; ++a) {
+        const int64_t nd = elem[(int64_t)a * n_e + e];
+        const double h = hat[a * n_q + q];
+        x = x + h * coords[nd];
+        y = y + h * coords[n_n + nd];
+    }
+    xq[k] = x;
+    xq[n_int + k] = y;
+}
+
 // Traction load over boundary edges (EL:295-364 with the full arc-length Jacobian and a value per surface point).
 // One lane per loaded node b: node id bnode[b], its (edge, local node) codes a * n_e_s + e in blist[bptr[b] .. bptr[b + 1])
 // ordered by (e, a).  f_out is zeroed by the caller beforehand.
@@ -1333,15 +1385,15 @@ __device__ __forceinline__ void p1_geometry(const P1Tab& tab, const double2 c0, 
 //   perm2[t] = e*16 + a*4 + b ;  meta = (deg << 16) | (diag << 15) | slot
 // ---------------------------------------------------------------------------------------
 // Stage A of a P1 context's step, one body for every model: `m3` / `m4` = the model's third and fourth material array per
-// point (MatU: eta / c hold them).  Stage B is the context's own assembly.
-template <int MODEL>
+// point (MatU: eta / c hold them).  Stage B is the context's own assembly.  FIELD as in return_map_body.
+template <int MODEL, bool FIELD = false>
 __device__ __forceinline__ void
 p1_point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy, const P1Tab& tab,
               const double* __restrict__ U, const E0& e0, double* __restrict__ ep,
               const double* __restrict__ shear, const double* __restrict__ bulk,
               const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
               double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-              uint8_t* __restrict__ indp, uint2* blk_counts) {
+              uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (e < n_e) {
@@ -1363,7 +1415,13 @@ p1_point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __res
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[e], m_bu = mu.on ? mu.bulk : bulk[e];
         const double m_3 = mu.on ? mu.eta : m3[e], m_4 = mu.on ? mu.c : m4[e];
-        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        if constexpr (FIELD) {
+            double z[4];
+            field_e0(e0, field, scale, n_e, e, z);
+            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        } else {
+            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        }
         store_point(e, n_e, s, d, branch, S, DS, indp);
         if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
         if (accept && ep && branch) { ep[e] = p[0]; ep[n_e + e] = p[1]; ep[2 * n_e + e] = p[2]; ep[3 * n_e + e] = p[3]; }
@@ -1384,6 +1442,12 @@ __global__ void __launch_bounds__(kBlock) p1_point_vm_kernel(FEP_P1_POINT_ARGS) 
 }
 __global__ void __launch_bounds__(kBlock) p1_point_mc_kernel(FEP_P1_POINT_ARGS) {
     p1_point_body<FEP_MODEL_MC>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+}
+template <int MODEL>
+__global__ void __launch_bounds__(kBlock)
+p1_point_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, double scale) {
+    p1_point_body<MODEL, true>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts,
+                               field, scale);
 }
 #undef FEP_P1_POINT_ARGS
 
@@ -2040,7 +2104,7 @@ __device__ __forceinline__ void inverse_jacobian(double j11, double j12, double 
     w = fabs(det) * wfq;                                 // DP:585
 }
 
-template <int MODEL, int NP, int NQ>
+template <int MODEL, int NP, int NQ, bool FIELD = false>
 __device__ __forceinline__ void
 point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restrict__ xy,
            const double* __restrict__ dh1, const double* __restrict__ dh2, const double* __restrict__ wf,
@@ -2048,7 +2112,7 @@ point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restri
            const double* __restrict__ shear, const double* __restrict__ bulk,
            const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
            double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-           uint8_t* __restrict__ indp, uint2* blk_counts) {
+           uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
     __shared__ double t1[NP * NQ], t2[NP * NQ], tw[NQ];
     for (int i = threadIdx.x; i < NP * NQ; i += kBlock) { t1[i] = dh1[i]; t2[i] = dh2[i]; }
     for (int i = threadIdx.x; i < NQ; i += kBlock) tw[i] = wf[i];
@@ -2094,7 +2158,13 @@ point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restri
         double s[4], d[6];
         const double m_sh = mu.on ? mu.shear : shear[k], m_bu = mu.on ? mu.bulk : bulk[k];
         const double m_3 = mu.on ? mu.eta : m3[k], m_4 = mu.on ? mu.c : m4[k];
-        branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        if constexpr (FIELD) {
+            double z[4];
+            field_e0(e0, field, scale, n_int, k, z);
+            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        } else {
+            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+        }
         store_point(k, n_int, s, d, branch, S, DS, indp);
         if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
         if (accept && ep && branch) { ep[k] = p[0]; ep[n_int + k] = p[1]; ep[2 * n_int + k] = p[2]; ep[3 * n_int + k] = p[3]; }
@@ -2117,6 +2187,14 @@ template <int NP, int NQ>
 __global__ void __launch_bounds__(kBlock) point_mc_kernel(FEP_POINT_ARGS) {
     point_body<FEP_MODEL_MC, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
                                      indp, blk_counts);
+}
+// The same with an initial-strain field, for every model: the only Drucker-Prager instantiation of point_body (a step with a field
+// runs staged on every route).
+template <int MODEL, int NP, int NQ>
+__global__ void __launch_bounds__(kBlock)
+point_field_kernel(FEP_POINT_ARGS, const double* __restrict__ field, double scale) {
+    point_body<MODEL, NP, NQ, true>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp,
+                                    blk_counts, field, scale);
 }
 #undef FEP_POINT_ARGS
 

@@ -439,14 +439,19 @@ def solve_strip_footing_sharded(element_type='P1', level=1, n_cells=None, size_x
 
 def solve_tsx_tunnel_sharded(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                              linear_solver='amg', pcg_rtol=1e-11, mesh_dir=None, pcg_inexact_rtol=None, refine=0,
-                             renumber=False, group=None, solve_rank=0, curves=None):
+                             renumber=False, group=None, solve_rank=0, curves=None, in_situ=None, body_force=None):
     """newton.solve_tsx_tunnel on the ranks of the process group (a single process works too), arguments as there
     (`linear_solver` 'pcg' or 'amg' as in solve_strip_footing_sharded; no `context_factory`, no forcing).  Every rank
     prepares the same mesh (`refine` / `renumber` run on each rank's device; the device refinement is bit-equal to the host
     one, so all ranks see one mesh), takes a contiguous range of its elements and enters newton's loop with its
     ShardedContext: the initial-stress force is made consistent by the interface exchange, the plastic-point counts are
     summed over the ranks.  `curves` as in solve_tsx_tunnel (each rank checks the determinants of its own elements).  Idle
-    ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on every rank."""
+    ranks (`min_elements_per_rank`) are not offered here.  Returns the same history on every rank.
+    `in_situ` / `body_force` (solve_tsx_tunnel's initial-strain field per point) are refused with ValueError: the field is
+    not sharded yet."""
+    if in_situ is not None or body_force is not None:
+        raise ValueError('in_situ / body_force: the sharded drivers do not shard an initial-strain field; '
+                         'use solve_tsx_tunnel on one device')
     rank, world = _ranks(group)
     p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, None, log, curves)
     clock = [time.perf_counter()]

@@ -54,7 +54,8 @@ def _strain_view(e, n_int):
 # ---------------------------------------------------------------------------------------
 # a2  construct_constitutive_problem
 # ---------------------------------------------------------------------------------------
-def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, device=None, entry='fep_return_map_host'):
+def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, device=None, entry='fep_return_map_host',
+                field=None):
     l = _lib.lib()
     dev = default_device() if device is None else device
     shear = _f64(shear).ravel()
@@ -77,9 +78,19 @@ def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, 
     ind = _lib.pinned_empty(n_int, np.uint8)
     counts = np.zeros(2, dtype=np.int64)
     accept = bool(apply_plastic_strain) and ep_prev is not None
-    _lib.check(getattr(l, entry)(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
-                                 _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), int(accept),
-                                 _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(counts)), entry)
+    if field is not None:                              # (model, e0_field, e0_scale): the one entry point of every model
+        model, fld, scale = field
+        fld = _f64(fld)
+        if fld.shape != (4, n_int):
+            raise ValueError(f'e0_field must be (4,{n_int}), got {fld.shape}')
+        _lib.check(l.fep_return_map_field_host(MODELS[model], dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(fld),
+                                               float(scale), _lib.ptr(ep_dev), _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta),
+                                               _lib.ptr(c), int(accept), _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind),
+                                               _lib.ptr(counts)), 'fep_return_map_field_host')
+    else:
+        _lib.check(getattr(l, entry)(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
+                                     _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), int(accept),
+                                     _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(counts)), entry)
     n_smooth, n_apex = int(counts[0]), int(counts[1])
     out = _Result({'s': s, 'ds': ds, 'ind_p': ind.view(np.bool_), 'n_smooth': n_smooth, 'n_apex': n_apex})
     early_out = tsx and n_smooth == 0 and n_apex == 0                  # TSX:1103
@@ -202,6 +213,59 @@ def construct_constitutive_problem_mc(e, ep_prev, shear, bulk, sin_phi, c, apply
 MODELS = {'dp': 0, 'vm': 1, 'mc': 2}                       # FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC
 
 
+def construct_constitutive_problem_field(model, e, e0_field, ep_prev, shear, bulk, m3, m4, apply_plastic_strain=False,
+                                         e0=None, e0_scale=1.0, device=None):
+    """The return map of `model` ('dp', 'vm' or 'mc') with an initial strain per point, no counterpart in the reference
+    (include/fep.h, fep_return_map_field_host): point k runs on `e0 + e0_scale * e0_field[:, k]`, `e0_field` (4, n_int) with
+    rows 11, 22, 12 (engineering shear), 33, `e0` an optional uniform (4,1) part.  `m3`, `m4` are the model's third and
+    fourth parameter arrays (eta, c / a, Y / sin_phi, c); the other arguments as construct_constitutive_problem.  Returns
+    {'s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex'} with the counts as the model's own wrapper reports them (von Mises:
+    its plastic points in 'n_smooth'); with `apply_plastic_strain`, `ep_prev` is updated in place and returned as 'ep'."""
+    if model not in MODELS:
+        raise ValueError(f"model must be one of {sorted(MODELS)}")
+    if e0_field is None:
+        raise ValueError('e0_field is required (the plain wrappers run without a field)')
+    r = _return_map(e, e0, ep_prev, shear, bulk, m3, m4, apply_plastic_strain, tsx=False, device=device,
+                    field=(model, e0_field, e0_scale))
+    return {k: r[k] for k in ('s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex')}
+
+
+def in_situ_strain(s0, shear, bulk):
+    """The strain whose elastic stress is `s0` ((4, n) rows 11, 22, 12, 33; `shear`, `bulk` scalars or (n,)): per point
+    e = dev(s0) / (2G) + tr(s0) / (9K) on the normal components and s12 / G for the engineering shear.  NumPy arrays in,
+    NumPy array out; torch tensors in, a tensor on their device out (elementwise: no kernel of its own)."""
+    if type(s0).__module__.split('.')[0] == 'torch':
+        import torch
+        G = torch.as_tensor(shear, dtype=s0.dtype, device=s0.device).reshape(-1)
+        K = torch.as_tensor(bulk, dtype=s0.dtype, device=s0.device).reshape(-1)
+        m = (s0[0] + s0[1] + s0[3]) / 3
+        return torch.stack([(s0[0] - m) / (2 * G) + m / (3 * K), (s0[1] - m) / (2 * G) + m / (3 * K), s0[2] / G,
+                            (s0[3] - m) / (2 * G) + m / (3 * K)])
+    s0 = np.asarray(s0, dtype=np.float64)
+    G = np.asarray(shear, dtype=np.float64).reshape(-1)
+    K = np.asarray(bulk, dtype=np.float64).reshape(-1)
+    m = (s0[0] + s0[1] + s0[3]) / 3
+    return np.stack([(s0[0] - m) / (2 * G) + m / (3 * K), (s0[1] - m) / (2 * G) + m / (3 * K), s0[2] / G,
+                     (s0[3] - m) / (2 * G) + m / (3 * K)])
+
+
+def linear_in_situ(s0_ref, y_ref, grad):
+    """The callable (x, y) -> s0_ref + grad * (y - y_ref), a (4, n) stress with rows 11, 22, 12, 33: an in-situ state that
+    grows linearly with depth (`s0_ref` at the height `y_ref`, `grad` its change per unit of y; scalars or 4 values each).
+    Works on NumPy arrays and on torch tensors alike."""
+    a = [float(v) for v in np.broadcast_to(np.asarray(s0_ref, dtype=np.float64).ravel(), (4,))]
+    g = [float(v) for v in np.broadcast_to(np.asarray(grad, dtype=np.float64).ravel(), (4,))]
+    y0 = float(y_ref)
+
+    def s0(x, y):
+        rows = [a[i] + g[i] * (y - y0) for i in range(4)]
+        if type(y).__module__.split('.')[0] == 'torch':
+            import torch
+            return torch.stack(rows)
+        return np.stack(rows)
+    return s0
+
+
 # ---------------------------------------------------------------------------------------
 # mesh context: static operands + fused step
 # ---------------------------------------------------------------------------------------
@@ -314,17 +378,24 @@ class MeshContext:
         return p.value
 
     # -- hot path on host arrays
-    def step(self, U, ep_prev=None, e0=None, apply_plastic_strain=False, want=('s', 'ds', 'ind_p', 'K', 'F')):
+    def step(self, U, ep_prev=None, e0=None, apply_plastic_strain=False, want=('s', 'ds', 'ind_p', 'K', 'F'),
+             e0_field=None, e0_scale=1.0):
         """One pass strain -> return map -> tangent -> internal force (DP:1043-1058) for the
         displacement `U` ((2,n_n), or flat DOF order).  Returns a dict with the requested keys among
         'E' (3,n_int), 's' (4,n_int), 'ds' (9,n_int), 'ind_p', 'K' (csr), 'F' (n_dof,), plus
-        'n_smooth', 'n_apex'.  `ep_prev` (4,n_int) is updated in place on accept."""
+        'n_smooth', 'n_apex'.  `ep_prev` (4,n_int) is updated in place on accept.  `e0_field` (4,n_int): an initial strain
+        per integration point, point k running on `e0 + e0_scale * e0_field[:, k]` (fep_step_field_host)."""
         U = np.asarray(U, dtype=np.float64)
         if U.size != self.n_dof:
             raise ValueError(f'U must hold {self.n_dof} values')
+        fld = None
+        if e0_field is not None:
+            fld = _f64(e0_field)
+            if fld.shape != (4, self.n_int):
+                raise ValueError(f'e0_field must be (4,{self.n_int}), got {fld.shape}')
         # the reference's (2, n_n) array goes down as it is: the library interleaves it while staging the transfer
         # (a NumPy `reshape(-1, order='F')` of 1 M nodes costs 2.5 ms, as much as the whole transfer)
-        planar = U.ndim == 2 and U.shape[0] == 2 and U.flags.c_contiguous
+        planar = fld is None and U.ndim == 2 and U.shape[0] == 2 and U.flags.c_contiguous
         u = U if planar else np.ascontiguousarray(U.reshape(-1, order='F') if U.ndim == 2 else U)
         n = self.n_int
         e0v = None if e0 is None else _f64(e0).ravel()
@@ -341,9 +412,15 @@ class MeshContext:
         F = _lib.pinned_empty(self.n_dof) if 'F' in want else None
         counts = np.zeros(2, dtype=np.int64)
         accept = bool(apply_plastic_strain) and ep is not None
-        fn = _lib.lib().fep_step_host_planar if planar else _lib.lib().fep_step_host
-        _lib.check(fn(self._h, _lib.ptr(u), _lib.ptr(e0v), _lib.ptr(ep), int(accept), _lib.ptr(E), _lib.ptr(s), _lib.ptr(ds),
-                      _lib.ptr(ind), _lib.ptr(kd), _lib.ptr(F), _lib.ptr(counts)), 'fep_step_host')
+        if fld is not None:
+            _lib.check(_lib.lib().fep_step_field_host(self._h, _lib.ptr(u), _lib.ptr(e0v), _lib.ptr(fld), float(e0_scale),
+                                                      _lib.ptr(ep), int(accept), _lib.ptr(E), _lib.ptr(s), _lib.ptr(ds),
+                                                      _lib.ptr(ind), _lib.ptr(kd), _lib.ptr(F), _lib.ptr(counts)),
+                       'fep_step_field_host')
+        else:
+            fn = _lib.lib().fep_step_host_planar if planar else _lib.lib().fep_step_host
+            _lib.check(fn(self._h, _lib.ptr(u), _lib.ptr(e0v), _lib.ptr(ep), int(accept), _lib.ptr(E), _lib.ptr(s),
+                          _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(kd), _lib.ptr(F), _lib.ptr(counts)), 'fep_step_host')
         if accept and ep is not ep_prev:
             ep_prev[...] = ep
         for k, v in (('E', E), ('s', s), ('ds', ds), ('F', F)):
@@ -370,8 +447,16 @@ class MeshContext:
         return (None if kd is None else self.csr(kd)), F
 
     # -- hot path on device-resident arrays (raw device pointers as ints; used by bench.py / torch)
-    def step_dev(self, stream, u, ep=0, accept=False, e0=None, e_out=0, s=0, ds=0, ind_p=0, k_data=0, f_out=0, counts=0):
+    def step_dev(self, stream, u, ep=0, accept=False, e0=None, e_out=0, s=0, ds=0, ind_p=0, k_data=0, f_out=0, counts=0,
+                 e0_field=None, e0_scale=1.0):
+        """`e0_field`: device pointer (int) of a (4, n_int) initial-strain field, or None (fep_step_field_dev / fep_step_dev)."""
         e0v = None if e0 is None else _f64(e0).ravel()
+        if e0_field is not None:
+            _lib.check(_lib.lib().fep_step_field_dev(self._h, stream, u, _lib.ptr(e0v), e0_field or None, float(e0_scale),
+                                                     ep or None, int(bool(accept)), e_out or None, s or None, ds or None,
+                                                     ind_p or None, k_data or None, f_out or None, counts or None),
+                       'fep_step_field_dev')
+            return
         _lib.check(_lib.lib().fep_step_dev(self._h, stream, u, _lib.ptr(e0v), ep or None, int(bool(accept)), e_out or None,
                                            s or None, ds or None, ind_p or None, k_data or None, f_out or None,
                                            counts or None), 'fep_step_dev')
@@ -400,6 +485,19 @@ class MeshContext:
                 self._hatp_own = np.ascontiguousarray(np.broadcast_to(np.asarray(own, dtype=np.float64), (self.n_p, self.n_q)))
             return self._hatp_own
         return np.ascontiguousarray(np.broadcast_to(np.asarray(hatp, dtype=np.float64), (self.n_p, self.n_q)))
+
+    def point_coords(self, hatp=None):
+        """Coordinates of the integration points -> (2, n_int) ndarray: what an `e0_field` is evaluated at
+        (fep_ctx_point_coords_host).  `hatp` as in load_volume."""
+        out = np.empty((2, self.n_int))
+        _lib.check(_lib.lib().fep_ctx_point_coords_host(self._h, _lib.ptr(self._hatp(hatp)), _lib.ptr(out)),
+                   'fep_ctx_point_coords_host')
+        return out
+
+    def point_coords_dev(self, stream, xq, hatp=None):
+        """The same into the device pointer `xq` (2, n_int).  Only enqueues one kernel."""
+        _lib.check(_lib.lib().fep_ctx_point_coords_dev(self._h, stream, _lib.ptr(self._hatp(hatp)), xq),
+                   'fep_ctx_point_coords_dev')
 
     def load_volume(self, f_v_int=None, uniform=None, hatp=None, weight=None):
         """Body-force vector (EL:246-292) -> (2, n_n) ndarray.  Either `f_v_int` (2, n_int), a value per integration

@@ -33,7 +33,7 @@ from contextlib import closing
 import numpy as np
 import scipy.sparse.linalg as sspl
 
-from .hotpath import MeshContext
+from .hotpath import MeshContext, in_situ_strain
 from .mesh import square_mesh
 from .tables import ELEMENT_SHAPE, _coerce, element_tables
 
@@ -73,9 +73,15 @@ class _HostOps:
     def new_ep(self):
         return np.zeros((4, self.ctx.n_int))
 
-    def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False):
+    def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False, e0_field=None, e0_scale=1.0):
         kw = {} if e0 is None else {'e0': e0}
+        if e0_field is not None:
+            kw.update(e0_field=e0_field, e0_scale=e0_scale)
         return self.ctx.step(U, Ep, apply_plastic_strain=accept, want=want, **kw)
+
+    def field(self, a):
+        """A (4, n_int) initial-strain field as these ops' step takes it."""
+        return np.ascontiguousarray(a, dtype=np.float64)
 
     def setup_amg(self, K, coordinates):
         pass
@@ -154,7 +160,11 @@ class _DeviceOps:
     def _global_counts(self):
         return self.counts
 
-    def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False):
+    def field(self, a):
+        """A (4, n_int) initial-strain field as these ops' step takes it: uploaded once, resident on the device."""
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
+
+    def step(self, U, Ep=None, accept=False, e0=None, want=('K', 'F'), keep_K=False, e0_field=None, e0_scale=1.0):
         t = self.torch
         kd = None
         if 'K' in want:
@@ -164,7 +174,8 @@ class _DeviceOps:
                           accept=accept and Ep is not None, e0=e0, s=self.s.data_ptr() if 's' in want else 0,
                           ind_p=self.ind.data_ptr() if 'ind_p' in want else 0,
                           k_data=0 if kd is None else kd.data_ptr(), f_out=self.F.data_ptr() if 'F' in want else 0,
-                          counts=self.counts.data_ptr() if logs else 0)
+                          counts=self.counts.data_ptr() if logs else 0,
+                          **({} if e0_field is None else {'e0_field': e0_field.data_ptr(), 'e0_scale': e0_scale}))
         if 'F' in want:
             self._finish_force()
         out = {'K': kd, 'F': self.F, 's': self.s, 'ind_p': self.ind}
@@ -245,20 +256,30 @@ def make_ops(ctx, qf, linear_solver, pcg_rtol, pcg_forcing=None, pcg_forcing_cap
     raise ValueError("linear_solver must be 'direct', 'pcg' or 'amg'")
 
 
-def _newton_iteration(ops, K_elast, U_it, Ep, e0, rhs_of, hist, criterion, zero_dU_converged=False):
+def _e0_keywords(e0):
+    """The keywords of ops.step for the initial strain of a load step: `e0` itself (four values or None), or, when a driver
+    hands a dict, the dict ({'e0_field': ..., 'e0_scale': ...}: a field per point and the step's factor)."""
+    return e0 if isinstance(e0, dict) else {'e0': e0}
+
+
+def _newton_iteration(ops, K_elast, U_it, Ep, e0, rhs_of, hist, criterion, zero_dU_converged=False, q_load=None):
     """The semismooth-Newton iteration of one load step, for every driver: at most 25 iterates from `U_it` at the plastic
     strain `Ep` and initial strain `e0`, each solving for the right-hand side `rhs_of(F)`, stopped on the K_elast norms.
     `criterion`: the previous step's (it steers the first inexact solve but one).  `zero_dU_converged`: an exactly zero
-    correction counts as criterion 0 instead of the quotient as it stands.  Returns (iterate, iterations, criterion)."""
+    correction counts as criterion 0 instead of the quotient as it stands.  `q_load`: the K_elast norm of the elastic response
+    to the step's external load, added to the quotient's denominator (a state that the load holds at rest has iterates of
+    rounding size, which the quotient alone compares with each other).  Returns (iterate, iterations, criterion)."""
     its = 0
+    e0_kw = _e0_keywords(e0)
     for _ in range(25):                                                                   # DP:1040
-        r = ops.step(U_it, Ep, e0=e0, want=('K', 'F'))                                    # DP:1043-1058, TSX:1771-1778
+        r = ops.step(U_it, Ep, want=('K', 'F'), **e0_kw)                                  # DP:1043-1058, TSX:1771-1778
         hist['n_calls'] += 1
         its += 1
         dU = ops.solve(r['K'], rhs_of(r['F']), criterion if its > 1 else 1.0)             # DP:1062-1066, TSX:1781
         U_new = U_it + dU
         q1, q2, q3 = ops.energy(K_elast, dU), ops.energy(K_elast, U_it), ops.energy(K_elast, U_new)   # DP:1072-1074
-        criterion = 0.0 if zero_dU_converged and q1 == 0 else q1 / (q2 + q3)              # TSX:1788-1792
+        den = q2 + q3 if q_load is None else q2 + q3 + q_load
+        criterion = 0.0 if zero_dU_converged and q1 == 0 else q1 / den                    # TSX:1788-1792
         if np.isnan(criterion):                                                           # DP:1076
             break
         U_it = U_new
@@ -267,12 +288,19 @@ def _newton_iteration(ops, K_elast, U_it, Ep, e0, rhs_of, hist, criterion, zero_
     return U_it, its, criterion
 
 
-def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, accept_kw, accepted, finished):
+def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, accept_kw, accepted, finished, external=None):
     """The load-step loop around _newton_iteration, for both flavours (DP:1031-1127, TSX:1765-1826).
     `U_it`: the starting iterate.  Per flavour: `e0_of(zeta)` the initial strain of a step (or None), `accept_kw` the
     arguments of the accepting call of the step, `accepted(r, zeta, U, Ep_old, its, criterion)` records the step from
     that call's result `r` and returns (the plastic strain to go on with, whether the step may grow),
-    `finished(zeta_old)` the flavour's stop besides `d_zeta_min`.  Returns the last accepted U and plastic strain."""
+    `finished(zeta_old)` the flavour's stop besides `d_zeta_min`, `external` = (f_ext, q_ext) an external load that follows
+    zeta: the Newton iterates of a step then solve for zeta * f_ext - F instead of -F, and zeta * q_ext (q_ext the K_elast
+    norm of the elastic response to f_ext) joins the stopping quotient's denominator.  Returns the last accepted U and
+    plastic strain."""
+    def rhs_at(zeta):
+        if external is None:
+            return lambda F: -F
+        return lambda F: zeta * external[0] - F
     d_zeta_old = d_zeta
     zeta_old = 0.0
     U = ops.zeros()
@@ -282,11 +310,12 @@ def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, acce
     while True:
         zeta = zeta_old + d_zeta                                                          # DP:1031
         e0 = e0_of(zeta)                                                                  # TSX:1765
-        U_it, its, criterion = _newton_iteration(ops, K_elast, U_it, Ep_old, e0, lambda F: -F, hist, criterion)
+        U_it, its, criterion = _newton_iteration(ops, K_elast, U_it, Ep_old, e0, rhs_at(zeta), hist, criterion,
+                                                 q_load=None if external is None else zeta * external[1])
         if criterion < 1e-10:                                                             # DP:1091, TSX:1804
             U_old = U
             U = U_it
-            r = ops.step(U, Ep_old, e0=e0, **accept_kw)                                   # DP:1095-1098, TSX:1809
+            r = ops.step(U, Ep_old, **_e0_keywords(e0), **accept_kw)                      # DP:1095-1098, TSX:1809
             hist['n_calls'] += 1
             zeta_old = zeta
             d_zeta_old = d_zeta
@@ -441,7 +470,8 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
-                     pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None):
+                     pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None, in_situ=None,
+                     body_force=None, materials=None):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
@@ -454,17 +484,31 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     'node_of_input' maps input node ids to it (None unless renumbered).
     `curves` (a sequence of Ellipse; tsx_tunnel.TSX_HOLE is the tunnel wall): refinement and enrichment put their new
     boundary nodes on these curves (prepare_tsx_mesh; with `mesh_dir` alone the midpoints of load_tsx_mesh), and a mesh with
-    a non-positive Jacobian determinant at any integration point (a P2 / P4 element folded by its curved side) is refused."""
+    a non-positive Jacobian determinant at any integration point (a P2 / P4 element folded by its curved side) is refused.
+    `in_situ` (no counterpart in the reference, whose s0 is one stress for the whole mesh): a callable (x, y) -> (4, n)
+    stress, rows 11, 22, 12, 33 (linear_in_situ builds the usual one), evaluated at the context's integration points
+    (`point_coords`).  Its strain in_situ_strain(s0, shear, bulk) replaces the uniform initial strain as a field per point,
+    handed to the ops once (on the device it stays resident); every step runs with e0_scale = zeta and the array is never
+    rescaled.  `body_force` = (fx, fy), uniform (self-weight), goes with it: F0 = B^T w s0 - f_V and every Newton residual
+    is F(U) - zeta f_V, so that a stress field in equilibrium with the body force (d s22 / dy = -fy) leaves the unexcavated
+    ground at rest; the stopping quantity of the Newton iterates is then taken relative to the elastic response to the body force as well
+    (_newton_iteration, q_load), since such a state has no displacement of its own to be relative to.  `materials` = (shear, bulk, eta, c), scalars or (n_int) arrays (layered ground), instead of the
+    reference's constants.  With all three None the run is the reference's, bit for bit.  The result carries 's0_field'
+    and the accepting calls' stress 's' ((4, n_int), list per step) when `in_situ` is given."""
+    if body_force is not None and in_situ is None:
+        raise ValueError('body_force goes with in_situ (the stress field it is in equilibrium with)')
     p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves)
     clock = [time.perf_counter()]
     ctx = _context_maker(context_factory, device)(p['elem'], p['coords'], *element_tables(p['type']))
     assert ctx.n_int == p['elem'].shape[1] * ELEMENT_SHAPE[p['type']][1]
+    if materials is not None:
+        p['materials'] = tuple(materials)
     ctx.set_materials(*p['materials'])
     clock.append(time.perf_counter())
     with closing(ctx), closing(make_ops(ctx, p['Q'].flatten(order='F'), linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
                                         pcg_inexact_rtol)) as ops:
         _refuse_folded(p, ctx)
-        return _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log)
+        return _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ, body_force)
 
 
 def _refuse_folded(p, ctx):
@@ -522,7 +566,7 @@ def _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, 
             'prepared': bool(refine or renumber), 'curved': curved}
 
 
-def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log):
+def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=None):
     """solve_tsx_tunnel once the problem `p` (_tsx_setup), context (materials set) and ops exist (dist_newton.py enters here
     with its sharded ones).  `clock`: the times before and after the context was made."""
     coords, monitor, s0, init_strain = p['coords'], p['monitor'], p['s0'], p['init_strain']
@@ -535,7 +579,18 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log):
     if log:
         log('setup: context %.2f s, solver + K_elast %.2f s, multigrid hierarchy %.2f s'
             % (t_setup['context'], t_setup['solver + K_elast'], t_setup['hierarchy']))
-    F0 = ops.assembled(ctx.assemble(None, s0 * np.ones((1, ctx.n_int)))[1])               # TSX:1737
+    field, external, s0_field = None, None, None
+    if in_situ is None:
+        F0 = ops.assembled(ctx.assemble(None, s0 * np.ones((1, ctx.n_int)))[1])           # TSX:1737
+    else:
+        xq = np.asarray(ctx.point_coords())
+        s0_field = np.ascontiguousarray(np.broadcast_to(np.asarray(in_situ(xq[0], xq[1]), dtype=np.float64), (4, ctx.n_int)))
+        field = ops.field(in_situ_strain(s0_field, p['materials'][0], p['materials'][1]))
+        F0 = ops.assembled(ctx.assemble(None, s0_field)[1])
+        if body_force is not None:
+            f_V = ops.load_volume((float(body_force[0]), float(body_force[1])))
+            F0 = F0 - f_V
+            external = (f_V, ops.energy(K, ops.solve(K, f_V)))
 
     d_zeta = 1 / n_load_steps                                                             # TSX:1730-1735
     U_elast = ops.solve(K, -F0)                                                           # TSX:1748
@@ -546,13 +601,22 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log):
         hist['displ'].append(Um[monitor])
         hist['n_plast'].append(ops.count(r['ind_p']))
         hist['U'].append(Um.copy())
+        if field is not None:
+            hist['s'].append(np.array(ops.host(r['s'])))
         if log:
             log(f'zeta={zeta:.6g} U{monitor}={Um[monitor]:.16g} n_plast={hist["n_plast"][-1]}')
         return ops.new_ep(), False                                   # 'ep' of a non-accepting call, TSX:1809
 
     # the accepting call leaves apply_plastic_strain False (C7)
-    _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
-                    accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
+    if field is None:
+        _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
+                        accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
+    else:
+        hist['s'], hist['s0_field'] = [], s0_field
+        _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist,
+                        e0_of=lambda zeta: {'e0_field': field, 'e0_scale': zeta},
+                        accept_kw=dict(want=('s', 'ind_p')), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1,
+                        external=external)
     hist['F0'] = np.asarray(ops.host(F0)).reshape((2, -1), order='F')
     hist['Q'] = p['Q']
     hist['pcg_iters'] = ops.pcg_iters

@@ -210,6 +210,33 @@ int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
                           int accept,
                           double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
 
+/* ---- initial strain per point, mesh-free: one pair for every model ----------------------
+ * No reference counterpart (its demo holds one s0 for the whole mesh, TSX:1675-1681).  `model` = FEP_MODEL_DP, _VM or _MC;
+ * every other argument as in fep_return_map_* of that model (the third and fourth parameter arrays are the model's), plus
+ *   e0_field   (4, n_int) C-order like ep_prev, rows 11, 22, 12 (engineering shear), 33; never modified, borrowed for the call
+ *   e0_scale   one factor for the whole field
+ * The initial strain of point k is
+ *     z_i(k) = e0u_i + e0_scale * e0_field[i * n_int + k],     e0u_i = e0_h[i], or 0.0 when e0_h is NULL,
+ * the product rounded before the sum (no fused multiply-add), and the point's return map then runs on z(k) exactly as the
+ * plain entry point runs on e0: a field whose columns all equal z with e0_scale = 1 and e0_h = NULL gives the bits of the
+ * plain call with e0_h = z.  The four non-finite rules above hold for the field as for e0: a NaN or an infinity at one
+ * point of the field is that point's and nobody else's.  One thing is stricter than for e0: an infinite z_i(k) counts as a NaN
+ * (it is replaced by one before the return map), so for every model the point comes back elastic, with the finite elastic
+ * tangent and a NaN in s, and ds and K stay finite whatever the field holds.
+ * FEP_EINVAL: e0_field == NULL (the plain entry points are the way to run without a field) or an unknown model. */
+int fep_return_map_field_host(int model, int device_id, int64_t n_int,
+                              const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                              const double* e0_h, const double* e0_field_h, double e0_scale, double* ep_prev_h,
+                              const double* shear_h, const double* bulk_h, const double* m3_h, const double* m4_h,
+                              int accept,
+                              double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h);
+int fep_return_map_field_dev(int model, int device_id, void* stream, int64_t n_int,
+                             const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                             const double* e0_h, const double* e0_field_d, double e0_scale, double* ep_prev_d,
+                             const double* shear_d, const double* bulk_d, const double* m3_d, const double* m4_d,
+                             int accept,
+                             double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
+
 /* ---- a6/a7: mesh context (static operands of the hot path) ----------------------------
  * Replaces the geometry / index part of get_elastic_stiffness_matrix
  * (DP:491-601, TSX:432-542, EL:368-477): Jacobians, dphi_1/dphi_2, weight = |det|*wf,
@@ -307,6 +334,37 @@ int fep_step_host_planar(fep_ctx* ctx, const double* u2_h, const double* e0_h,
                          double* ep_prev_h, int accept,
                          double* e_out_h, double* s_h, double* ds_h, uint8_t* ind_p_h,
                          double* k_data_h, double* f_out_h, int64_t* counts_h);
+
+/* ---- the same step with an initial strain per integration point -------------------------
+ * fep_step_dev / fep_step_host with `e0_field` ((4, n_int), device resp. host, borrowed for the call) and `e0_scale` after
+ * e0_h: the initial strain of point k is z(k) of fep_return_map_field_* (in-situ stress that varies over the mesh; a load
+ * factor goes into e0_scale, the array stays as it is).  Such a step always runs staged, for every model and on every
+ * route: the model's point kernel with the field (geometry from the node coordinates, strain, return map; s / ds to the
+ * caller's arrays or the context's scratch), then what fep_assemble_dev launches for the context, then the COO form's
+ * force gather.  The one-kernel P1 step and the fused element kernel do not read a field.  Outputs, counts and the four
+ * non-finite rules as fep_step_*: a NaN at one point of the field is that point's NaN and nobody else's.
+ * fep_step_field_dev neither allocates nor synchronises and can be captured into a hipGraph; e0_scale and e0_h are then
+ * baked into the captured launch (a replay reads the field's current contents with the captured factor).  One exception:
+ * a Drucker-Prager context gets its ds / s scratch and the point kernel's counters on the first such call; make that call
+ * once outside a capture (FEP_ESTATE inside one).
+ * FEP_EINVAL: e0_field == NULL; the plain entry points remain the way to step without a field. */
+int fep_step_field_dev(fep_ctx* ctx, void* stream, const double* u_d, const double* e0_h,
+                       const double* e0_field_d, double e0_scale,
+                       double* ep_prev_d, int accept,
+                       double* e_out_d, double* s_d, double* ds_d, uint8_t* ind_p_d,
+                       double* k_data_d, double* f_out_d, int64_t* counts_d);
+int fep_step_field_host(fep_ctx* ctx, const double* u_h, const double* e0_h,
+                        const double* e0_field_h, double e0_scale,
+                        double* ep_prev_h, int accept,
+                        double* e_out_h, double* s_h, double* ds_h, uint8_t* ind_p_h,
+                        double* k_data_h, double* f_out_h, int64_t* counts_h);
+
+/* Coordinates of the context's integration points, what such a field is evaluated at: xq (2, n_int) C-order,
+ *     xq[c, e*n_q + q] = sum over a ascending of hatp[a, q] * coords[c, elements[a, e]]      (no fused multiply-add)
+ * with `hatp_h` the (n_p, n_q) C-order table of basis-function VALUES on the host, as in fep_load_volume_* (it travels as a
+ * kernel argument).  Neither allocates nor synchronises in the _dev form.  FEP_EINVAL: a NULL argument. */
+int fep_ctx_point_coords_dev(fep_ctx* ctx, void* stream, const double* hatp_h, double* xq_d);
+int fep_ctx_point_coords_host(fep_ctx* ctx, const double* hatp_h, double* xq_h);
 
 /* ---- a3..a5 only: assembly from given ds / s ------------------------------------------
  * Replaces DP:1047-1050 + DP:1058 when the caller already holds `ds` (9,n_int) and `s` (>=3 rows

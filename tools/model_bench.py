@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Step times of the three material models side by side, per element type: the fused Drucker-Prager step against the von
 Mises and the Mohr-Coulomb step (point kernel + the route's assembly from ds / s), each as the K,F-only step of a Newton iterate
-and with every point output.  HIP events around batches of steps, the six variants of a type interleaved pass by pass in one process (what
-differs between them is then not the box or the session).  Prints one JSON line.
+and with every point output.  A fourth row, "DP, field" (keys dp_field_*) beside "DP, uniform" (dp_*): the same Drucker-Prager context
+stepped with an initial strain per point (a field of zeros, so the same points yield), which runs staged like the von Mises and
+Mohr-Coulomb rows it is to be compared with.  HIP events around batches of steps, the eight variants of a type interleaved pass
+by pass in one process (what differs between them is then not the box or the session).  Prints one JSON line.
     python tools/model_bench.py [--types P1,P2,Q1,Q2,P4] [--steps 20] [--passes 5] [--scale 1.0]
 Mesh sizes as tools/elem_bench.py is run (cells per side: 708, P4 354); --scale shrinks them for a quick look."""
 import argparse
@@ -53,12 +55,15 @@ def time_type(t, N, steps, passes):
     ind = torch.empty(n, dtype=torch.uint8, device=dev)
     Kd = torch.empty(ctxs['dp'].nnz, **f64); F = torch.empty(ctxs['dp'].n_dof, **f64)
     cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    Fld = torch.zeros((4, n), **f64)
 
     def step(model, full):
         kw = dict(s=S.data_ptr(), ds=DS.data_ptr(), ind_p=ind.data_ptr()) if full else {}
+        if model == 'dp_field':
+            model, kw = 'dp', dict(kw, e0_field=Fld.data_ptr(), e0_scale=1.0)
         ctxs[model].step_dev(st, U.data_ptr(), ep=Ep.data_ptr(), k_data=Kd.data_ptr(), f_out=F.data_ptr(),
                              counts=cnt.data_ptr(), **kw)
-    variants = [(m, full) for m in MODELS for full in (False, True)]
+    variants = [(m, full) for m in MODELS + ('dp_field',) for full in (False, True)]
     plastic = {}
     for m, full in variants:
         for _ in range(3):
