@@ -293,7 +293,43 @@ __global__ void __launch_bounds__(kBlock) enrich_p2_kernel(MeshView M, CurveSet 
     }
 }
 
-// grid.y = edge k = slot; lane k of an element also writes its interior node k (nearest vertex k, TSX:1374-1381)
+// the three new nodes of a P4 edge a -> b at their straight positions: midpoint, quarter point nearer a, nearer b
+__device__ __forceinline__ void p4_edge_points(double ax, double ay, double bx, double by, double* px, double* py) {
+    px[0] = (ax + bx) / 2; px[1] = 3 * ax / 4 + bx / 4; px[2] = ax / 4 + 3 * bx / 4;
+    py[0] = (ay + by) / 2; py[1] = 3 * ay / 4 + by / 4; py[2] = ay / 4 + 3 * by / 4;
+}
+
+// Blending weights of a P4 element's interior nodes for one curved edge a -> b (fep.h, fep_mesh_set_curves):
+// (l_a + l_b)^2 L_k(t) at t = l_b / (l_a + l_b) for the edge's midpoint and quarter points.
+constexpr double kBlendMid = 5.0 / 18.0, kBlendNear = 10.0 / 27.0, kBlendFar = -2.0 / 27.0, kBlendOpp = 1.0 / 4.0;
+
+// What the curved edge a -> b of an element adds to one of its interior nodes: `role` 0 = the node nearest a, 1 = the node
+// nearest the third vertex, 2 = the node nearest b.  Nothing for an edge on no curve.
+__device__ __forceinline__ void p4_blend(const CurveSet& S, int role, double ax, double ay, double bx, double by, double* ix, double* iy) {
+    const int q = edge_curve(S, ax, ay, bx, by);
+    if (q < 0) return;
+    double sx[3], sy[3], dx[3], dy[3];
+    p4_edge_points(ax, ay, bx, by, sx, sy);
+    for (int r = 0; r < 3; ++r) {
+        double px = sx[r], py = sy[r];
+        project(S.v[q], &px, &py);
+        dx[r] = px - sx[r];
+        dy[r] = py - sy[r];
+    }
+    if (role == 0) {
+        *ix = *ix + ((kBlendMid * dx[0] + kBlendNear * dx[1]) + kBlendFar * dx[2]);
+        *iy = *iy + ((kBlendMid * dy[0] + kBlendNear * dy[1]) + kBlendFar * dy[2]);
+    } else if (role == 2) {
+        *ix = *ix + ((kBlendMid * dx[0] + kBlendFar * dx[1]) + kBlendNear * dx[2]);
+        *iy = *iy + ((kBlendMid * dy[0] + kBlendFar * dy[1]) + kBlendNear * dy[2]);
+    } else {
+        *ix = *ix + kBlendOpp * dx[0];
+        *iy = *iy + kBlendOpp * dy[0];
+    }
+}
+
+// grid.y = edge k = slot; lane k of an element also writes its interior node k (nearest vertex k, TSX:1374-1381), moved by
+// the blending rule for every curved edge of the element: boundary edges are owned by their element, so the lane has all it needs
 __global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, CurveSet S, int32_t* __restrict__ elem_ext, double* __restrict__ coord_ext,
                                                            int32_t* __restrict__ surf) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -327,11 +363,21 @@ __global__ void __launch_bounds__(kBlock) enrich_p4_kernel(MeshView M, CurveSet 
     if (k == 0) { ix = ax / 2 + bx / 4 + cx / 4; iy = ay / 2 + by / 4 + cy / 4; }            // A = V1, B = V2, C = V3
     else if (k == 1) { ix = cx / 4 + ax / 2 + bx / 4; iy = cy / 4 + ay / 2 + by / 4; }       // C = V1, A = V2, B = V3
     else { ix = bx / 4 + cx / 4 + ax / 2; iy = by / 4 + cy / 4 + ay / 2; }                   // B = V1, C = V2, A = V3
+    if ((m >> 3) && S.n > 0) {
+        // the element's edges in the order V1V2, V2V3, V3V1; edge e is this lane's (A, B), (B, C) or (C, A)
+        for (int e = 0; e < 3; ++e) {
+            if (!((m >> (3 + e)) & 1)) continue;
+            const int rel = (e - k + 3) % 3;
+            if (rel == 0) p4_blend(S, 0, ax, ay, bx, by, &ix, &iy);
+            else if (rel == 1) p4_blend(S, 1, bx, by, cx, cy, &ix, &iy);
+            else p4_blend(S, 2, cx, cy, ax, ay, &ix, &iy);
+        }
+    }
     coord_ext[n_n + inner] = ix;
     coord_ext[n_tot + n_n + inner] = iy;
     if (!owned) return;
-    double px[3] = {(ax + bx) / 2, 3 * ax / 4 + bx / 4, ax / 4 + 3 * bx / 4};
-    double py[3] = {(ay + by) / 2, 3 * ay / 4 + by / 4, ay / 4 + 3 * by / 4};
+    double px[3], py[3];
+    p4_edge_points(ax, ay, bx, by, px, py);
     if (nb < 0 && S.n > 0) {
         const int q = edge_curve(S, ax, ay, bx, by);
         if (q >= 0)

@@ -25,8 +25,8 @@ class Ellipse(collections.namedtuple('Ellipse', 'cx cy a b tol', defaults=(1e-3,
     has a == b.  A vertex p is ON it iff |g(p) - 1| <= tol, g = sqrt(((x - cx) / a)**2 + ((y - cy) / b)**2).  Passed as
     `curves=[...]` (at most 4) to the enrichment and refinement functions: every node they create on a boundary edge with
     both ends on the same curve (the lowest index wins) is moved from its straight position along its ray from the centre
-    onto the curve; interior edges, existing vertices and P4 interior nodes are never moved (include/fep.h,
-    fep_mesh_set_curves)."""
+    onto the curve; interior edges and existing vertices are never moved, and the three interior nodes of a P4 element
+    follow its curved edges by the blending rule of create_midpoints_P4 (include/fep.h, fep_mesh_set_curves)."""
     __slots__ = ()
 
 
@@ -175,9 +175,19 @@ def create_midpoints_P2(coord, elem, device=None, curves=None):
     return out
 
 
+# Blending weights of a P4 element's interior nodes for one curved edge a -> b (include/fep.h): (l_a + l_b)^2 L_k(t) at
+# t = l_b / (l_a + l_b), L_k the quartic Lagrange basis on {0, 1/4, 1/2, 3/4, 1}, for the edge's midpoint and its quarter points.
+_W_MID, _W_NEAR, _W_FAR, _W_OPP = 5.0 / 18.0, 10.0 / 27.0, -2.0 / 27.0, 1.0 / 4.0
+
+
 def create_midpoints_P4(coord, elem, device=None, curves=None):
     """TSX:1354-1505.  Returns 'coord_mid', 'surf', 'coord_ext', 'elem_ext'.  `device` and `curves` as in
-    create_midpoints_P2: the midpoint and the two quarter points of a curved edge are moved, the interior nodes are not."""
+    create_midpoints_P2: the midpoint and the two quarter points of a curved edge are moved onto the curve, by the offsets
+    d_m, d_a, d_b (midpoint, quarter point nearer the edge's first vertex a, nearer its second vertex b) from their straight
+    positions.  The element's interior nodes follow, so that its map stays smooth enough for a quartic: for each curved edge
+    a -> b of the element in turn (V1V2, V2V3, V3V1), the interior node nearest a moves by (5/18 d_m + 10/27 d_a) - 2/27 d_b,
+    the one nearest b by (5/18 d_m - 2/27 d_a) + 10/27 d_b and the third by 1/4 d_m.  These are (l_a + l_b)^2 sum_k L_k(t) d_k
+    at the node's barycentric coordinates l, t = l_b / (l_a + l_b), L_k the quartic Lagrange basis on the edge's five nodes."""
     rows = _curve_rows(curves)
     if device is not None:
         with DeviceMesh(coord, elem, device) as m:
@@ -202,6 +212,7 @@ def create_midpoints_P4(coord, elem, device=None, curves=None):
         coord_mid[:, ind + 2] = c1 / 4 + c2 / 2 + c3 / 4
         coord_mid[:, ind + 3] = c1 / 4 + c2 / 4 + c3 / 2
         elem_mid[9, i], elem_mid[10, i], elem_mid[11, i] = n_n + ind + 1, n_n + ind + 2, n_n + ind + 3
+        inner = ind + 1
         ind += 3
         for s, (A, B) in enumerate(((V1, V2), (V2, V3), (V3, V1))):            # TSX:1386, 1424, 1463
             if elem_mid[s, i] != 0:
@@ -227,8 +238,15 @@ def create_midpoints_P4(coord, elem, device=None, curves=None):
                     q = _edge_curve(cv, cA, cB) if len(m[(A, B) if A < B else (B, A)]) == 1 else -1
                     surf_curve.append(q)
                     if q >= 0:
+                        d = []
                         for r in (1, 2, 3):
-                            coord_mid[:, ind + r] = _project(cv[q], coord_mid[:, ind + r])
+                            straight = coord_mid[:, ind + r].copy()
+                            coord_mid[:, ind + r] = _project(cv[q], straight)
+                            d.append(coord_mid[:, ind + r] - straight)
+                        a, b, c = inner + s, inner + (s + 1) % 3, inner + (s + 2) % 3
+                        coord_mid[:, a] = coord_mid[:, a] + ((_W_MID * d[0] + _W_NEAR * d[1]) + _W_FAR * d[2])
+                        coord_mid[:, b] = coord_mid[:, b] + ((_W_MID * d[0] + _W_FAR * d[1]) + _W_NEAR * d[2])
+                        coord_mid[:, c] = coord_mid[:, c] + _W_OPP * d[0]
             ind += 3
     coord_mid = coord_mid[:, 0:ind + 1]
     out = {'coord_mid': coord_mid, 'surf': surf[:, 0:ind_s + 1], 'coord_ext': np.concatenate([coord, coord_mid], axis=1),

@@ -517,8 +517,17 @@ int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* co
  * the same curve; the lowest curve index wins; an interior edge is never curved.  Every node the library creates on a
  * curved edge (the refinement / P2 midpoint, the P4 midpoint and its two quarter points) is computed as a straight point
  * exactly as above and then moved to (cx + dx / g, cy + dy / g), with dx, dy, g of that straight point; for g == 0 (a
- * chord through the centre) it stays.  Existing vertices and P4 interior nodes never move; ids, elem_ext, elem_ed, edge_el,
- * surf and the child table do not depend on the curves.  The host functions apply the same rule with the same operations.
+ * chord through the centre) it stays.  Existing vertices never move; ids, elem_ext, elem_ed, edge_el, surf and the child
+ * table do not depend on the curves.  The three interior nodes of a P4 element follow its curved edges, so that the
+ * element's map stays smooth enough for a quartic.  With d_m, d_a, d_b the offsets (moved minus straight) of the midpoint of
+ * a curved edge a -> b and of its quarter points nearer a and nearer b, and with every interior node starting at its
+ * straight position, for each curved edge of the element in the order V1V2, V2V3, V3V1 and per component:
+ *     node nearest a:         p = p + ((w_m d_m + w_n d_a) + w_f d_b)         w_m = 5 / 18, w_n = 10 / 27, w_f = -2 / 27,
+ *     node nearest b:         p = p + ((w_m d_m + w_f d_a) + w_n d_b)         w_o = 1 / 4 (each the double nearest to it),
+ *     node nearest the third: p = p + w_o d_m
+ * which is (l_a + l_b)^2 sum_k L_k(t) d_k at the node's barycentric coordinates l, t = l_b / (l_a + l_b), L_k the quartic
+ * Lagrange basis on {0, 1/4, 1/2, 3/4, 1}.  A boundary edge is owned by its element, so no other element's nodes are
+ * needed.  The host functions apply the same rules with the same operations in the same order.
  *
  *   fep_mesh_set_curves   curves_h: n_curves x 5 HOST doubles, copied; they travel to the enrichment / refinement kernels as
  *                         a by-value argument (no allocation: the _dev forms stay capturable).  n_curves = 0 clears them.

@@ -5,6 +5,8 @@ curved-boundary rule (include/fep.h, fep_mesh_set_curves) can go wrong, and the 
 Everything here recomputes the rule with vectorised NumPy (np.sqrt, /: correctly rounded, like the library's operations),
 independently of midpoints.py's scalar code.
 """
+from fractions import Fraction
+
 import numpy as np
 
 import fan_mesh
@@ -112,6 +114,44 @@ def curved_nodes(fep, op, coord, elem, curves):
     return rows.ravel(), np.broadcast_to(q[q >= 0], rows.shape).ravel(), h['surf'], q
 
 
+def p4_blend_weights():
+    """w[n][k]: the weight of the offset of node k of a curved edge a -> b (k = 0: its midpoint, 1: the quarter point nearer
+    a, 2: nearer b) in the move of the interior node n (0: nearest a, 1: nearest b, 2: nearest the third vertex):
+    (l_a + l_b)^2 L(t), t = l_b / (l_a + l_b), L the quartic Lagrange basis on {0, 1/4, 1/2, 3/4, 1}, in rational
+    arithmetic from the nodes' barycentric coordinates (1/2 at the nearest vertex, 1/4 at the others), rounded once."""
+    tn = [Fraction(k, 4) for k in range(5)]
+    w = []
+    for la, lb in ((Fraction(1, 2), Fraction(1, 4)), (Fraction(1, 4), Fraction(1, 2)), (Fraction(1, 4), Fraction(1, 4))):
+        s, t = la + lb, lb / (la + lb)
+        row = []
+        for k in (2, 1, 3):
+            L = Fraction(1)
+            for m in range(5):
+                if m != k:
+                    L *= (t - tn[m]) / (tn[k] - tn[m])
+            row.append(float(s * s * L))
+        w.append(row)
+    assert w[2][1] == 0 and w[2][2] == 0
+    return w
+
+
+def p4_interior_rule(elem_ext, straight, curved):
+    """The interior nodes of every P4 element by the rule of include/fep.h (fep_mesh_set_curves), from the straight
+    enrichment and the edge nodes of the curved one: (2, 3, n_e), node nearest V1, V2, V3.  Vectorised over the elements;
+    an edge that is not curved has the offset 0 and adds 0, so the sum runs over all three edges of every element, in the
+    rule's order and with its operations."""
+    w = p4_blend_weights()
+    e = np.asarray(elem_ext, dtype=np.int64)
+    out = straight[:, e[12:15]].copy()
+    for s in range(3):
+        d = [curved[:, e[r]] - straight[:, e[r]] for r in (3 + s, 6 + 2 * s, 7 + 2 * s)]
+        a, b, c = s, (s + 1) % 3, (s + 2) % 3
+        out[:, a] = out[:, a] + ((w[0][0] * d[0] + w[0][1] * d[1]) + w[0][2] * d[2])
+        out[:, b] = out[:, b] + ((w[1][0] * d[0] + w[1][1] * d[1]) + w[1][2] * d[2])
+        out[:, c] = out[:, c] + w[2][0] * d[0]
+    return out
+
+
 def check_curved(fep, name, coord, elem, curves, n_bnd, n_curved, device):
     """The assertions of one mesh for refine, P2 and P4 on the host (device=None) or a GPU.  Returns the curved results."""
     results = {}
@@ -136,6 +176,16 @@ def check_curved(fep, name, coord, elem, curves, n_bnd, n_curved, device):
         assert cc.shape == cb.shape and cc.dtype == cb.dtype
         other = np.ones(cc.shape[1], dtype=bool)
         other[ids] = False
+        if op == 'P4':                                                         # ... and of the P4 interior nodes, which follow the rule
+            inner = cur['elem_ext'][12:15].astype(np.int64)
+            other[inner] = False
+            want = p4_interior_rule(cur['elem_ext'], cb, cc)
+            assert cc[:, inner].tobytes() == want.tobytes(), (what, np.abs(cc[:, inner] - want).max())
+            holds = np.isin(cur['elem_ext'][3:12], ids).any(axis=0)            # elements with a curved edge
+            assert int(holds.sum()) == np.unique(surf_elements(cur['elem_ext'], surf[:, q >= 0])).size, what
+            assert cc[:, inner[:, ~holds]].tobytes() == cb[:, inner[:, ~holds]].tobytes(), what
+            if n_curved:
+                assert (cc[:, inner[:, holds]] != cb[:, inner[:, holds]]).any(axis=(0, 1)).all(), what   # each such element: a node moved
         assert cc[:, other].tobytes() == cb[:, other].tobytes(), what
         if op != 'refine':
             n_n = coord.shape[1]
@@ -161,6 +211,12 @@ def check_curved(fep, name, coord, elem, curves, n_bnd, n_curved, device):
                 assert (cc[:, mv] != cb[:, mv]).any(), what                # the projection did something
         results[op] = cur
     return results
+
+
+def surf_elements(elem_ext, surf):
+    """The element that holds the midpoint (row 2) of each P4 surf column."""
+    mids = np.asarray(elem_ext)[3:6]
+    return np.array([int(np.flatnonzero((mids == m).any(axis=0))[0]) for m in surf[2].astype(np.int64)], dtype=np.int64)
 
 
 def compare_device_host(name, dev, host):
