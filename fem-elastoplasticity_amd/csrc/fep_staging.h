@@ -11,9 +11,9 @@
 //     (hipMemcpyAsync); pageable outputs take the same ring the other way;
 //   * everything is ordered on one stream per device; one hipStreamSynchronize at the end of the call.
 // The three classes use six HIP calls (hipHostMalloc / hipHostFree / hipMalloc / hipFree / hipMemcpyAsync / stream and
-// event handling).  tests/host_san.cpp defines FEP_STAGING_HOST_STUB and supplies host stand-ins for them (plain memory,
-// synchronous copies, a switch that makes the next copy fail), so that PinnedCache, CopyPool and Engine run under
-// ThreadSanitizer / AddressSanitizer on the CPU.
+// event handling).  tests/staging_san.cpp defines FEP_STAGING_HOST_STUB and supplies host stand-ins for them (plain memory,
+// copies deferred to the synchronise that must wait for them, a switch that makes the next copy fail), so that PinnedCache,
+// CopyPool and Engine run under ThreadSanitizer / AddressSanitizer on the CPU and a missing wait changes the result.
 #pragma once
 #ifndef FEP_STAGING_HOST_STUB
 #include "fep_common.h"

@@ -27,6 +27,28 @@
  *     calls only enqueue work and return, *_host calls are synchronous (they run on a stream of the library's own,
  *     with persistent device buffers and pinned staging: no allocation per call after the first);
  *   - calls on one context are not re-entrant; one context per (host thread, GPU).
+ *
+ * Stream contract of the *_host entry points that move the caller's arrays through the staging engine
+ * (fep_return_map_host / _vm_host / _mc_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
+ * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host; not the fep_mesh_* and fep_load_traction_host forms):
+ *   - each call runs its copies and its kernels on ONE non-blocking stream per device that belongs to the library; that stream
+ *     is ordered against nothing else: not the default stream, not a stream the caller passed to a *_dev call;
+ *   - calls of all host threads on one device are serialised by a lock, and a call returns only after synchronising that
+ *     stream: on return every output is complete in the caller's memory, every input may be reused or freed, and nothing of
+ *     the call is in flight;
+ *   - a host array may lie anywhere and needs no more than its element's alignment: a block from fep_host_alloc, or a view
+ *     into one, is DMA-ed from / to directly, every other pointer goes through the engine's ring of pinned slots in chunks of
+ *     8 MiB, whatever its length;
+ *   - the context forms launch the same kernels as the *_dev forms and share the context's scratch with them (the ds / s scratch
+ *     of the assembly, the branch counters' per-workgroup partials, a von Mises / Mohr-Coulomb context's point scratch), next
+ *     to device buffers of their own that persist in the context (the first call that needs a larger one waits for the whole
+ *     device before it frees the smaller).
+ *   So: BEFORE a *_host call on a context, every *_dev call issued on that context must have COMPLETED: synchronise the
+ *   stream(s) they were enqueued on (fep_sync, hipStreamSynchronize, an event the host waited for).  Being enqueued earlier
+ *   is not enough, since the library's stream waits for no other.  AFTER a *_host call has returned, a *_dev call on the same
+ *   context may be enqueued at once on any stream.  tests/test_host_staging_gpu.py runs exactly this alternation.
+ *   The mesh-free fep_return_map_*_host calls use the engine's own device buffers and the counter scratch of the engine's
+ *   stream only: they need no synchronisation against *_dev calls of any kind.
  */
 #ifndef FEP_H
 #define FEP_H

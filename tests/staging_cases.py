@@ -1,0 +1,248 @@
+"""Shared by tests/test_host_staging_gpu.py: the sizes at which a *_host call is longer than the staging ring of
+fem-elastoplasticity_amd/csrc/fep_staging.h (four pinned slots of 8 MiB), the inputs of those calls, the ways a caller's
+array can lie in memory, and the raw C-ABI calls on them.
+
+Sizes.  A slot holds 1 048 576 doubles, the ring 4 194 304.
+  mesh-free return map, N_POINTS = 524 289 = 2^19 + 1 points: a material array (n doubles) is one chunk, the strain (3 n) two,
+      ep_prev / the field / s (4 n) three with a tail of 32 bytes, ds (9 n) five, the last 4 MiB + 72 bytes: it comes round to
+      the slot it started in inside one array.
+  context calls, square_mesh(MESH_N = 724, 'P1'): 525 625 nodes, 1 048 352 elements.  h2d_interleave2 splits at 524 288 nodes:
+      the planar U is two chunks, the second 1 337 nodes; K (14.7 M doubles) is fifteen chunks.
+The large mesh-free inputs are a base set of N_BASE = 1000 points (e0_field_cases.mesh_free: around the yield surface, per-point
+materials) tiled along the points.  Neither a slot nor the ring is a multiple of 1000 doubles, so a chunk that lands one slot or
+one ring off shows as a column that differs from column k mod 1000 of the call on the base set.
+
+Arrays.  'pageable': np.empty of the bytes wanted + 8, the array starting 8 bytes in (what a ctypes caller's malloc + header
+gives: 8- but not 16- or 64-byte aligned).  'pinned': fep_host_alloc through _lib.pinned_empty, the direct DMA path.  Outputs
+can carry a canary tail in the same allocation."""
+import ctypes as C
+import importlib
+
+import numpy as np
+
+import e0_field_cases as fcases
+
+fep = importlib.import_module('fem-elastoplasticity_amd')
+_lib = importlib.import_module('fem-elastoplasticity_amd._lib')
+
+SLOT_BYTES = 8 << 20
+SLOTS = 4
+N_BASE = 1000
+N_POINTS = (1 << 19) + 1
+MESH_N = 724
+SMALL_MESH_N = 40
+CANARY_BYTES = 4096
+CANARY = 0xC5
+MODELS = ('dp', 'vm', 'mc')
+MODEL_ID = {'dp': 0, 'vm': 1, 'mc': 2}
+ENTRY = {'dp': 'fep_return_map', 'vm': 'fep_return_map_vm', 'mc': 'fep_return_map_mc'}
+FIELD_SCALE = 0.37
+
+assert (SLOT_BYTES // 8) % N_BASE and (SLOTS * SLOT_BYTES // 8) % N_BASE
+
+
+def chunks(nbytes):
+    """(number of ring chunks, bytes in the last) of a pageable transfer"""
+    return -(-nbytes // SLOT_BYTES), nbytes - (nbytes - 1) // SLOT_BYTES * SLOT_BYTES
+
+
+assert chunks(8 * N_POINTS) == (1, 8 * N_POINTS) and chunks(24 * N_POINTS)[0] == 2
+assert chunks(32 * N_POINTS) == (3, 32) and chunks(72 * N_POINTS) == (5, (4 << 20) + 72)
+
+
+# ---- where a caller's array lies ---------------------------------------------------------------------------------------------
+def pageable(shape, dtype=np.float64, canary=False):
+    """Uninitialised array 8 bytes into an ordinary allocation; with `canary` the allocation goes on for CANARY_BYTES more."""
+    dt = np.dtype(dtype)
+    n = int(np.prod(shape)) * dt.itemsize
+    raw = np.empty(8 + n + (CANARY_BYTES if canary else 0), dtype=np.uint8)
+    raw[:8] = CANARY
+    raw[8 + n:] = CANARY
+    a = raw[8:8 + n].view(dt).reshape(shape)
+    assert a.ctypes.data % 16 == 8 and a.base is not None
+    return a
+
+
+def pinned(shape, dtype=np.float64, canary=False):
+    """The same inside one page-locked block of the library's cache (a view that starts 8 bytes into it).  The block comes
+    from fep_host_alloc itself (_lib._PinnedBlock raises when the runtime pins no more memory; _lib.pinned_empty would hand
+    out an ordinary array then, and a 'pinned' case would run the ring path under the name of the direct one)."""
+    dt = np.dtype(dtype)
+    n = int(np.prod(shape)) * dt.itemsize
+    nbytes = 8 + n + (CANARY_BYTES if canary else 0)
+    blk = _lib._PinnedBlock(nbytes)
+    assert blk.ptr
+    buf = (C.c_char * nbytes).from_address(blk.ptr)
+    buf._fep_owner = blk                               # the block returns to the cache with the last view of it
+    raw = np.frombuffer(buf, dtype=np.uint8, count=nbytes)
+    raw[:8] = CANARY
+    raw[8 + n:] = CANARY
+    return raw[8:8 + n].view(dt).reshape(shape)
+
+
+def _root(a):
+    while getattr(a, 'base', None) is not None and isinstance(a.base, np.ndarray):
+        a = a.base
+    return a
+
+
+def canary_intact(a):
+    """The 8 bytes in front of `a` and everything behind it in its allocation still hold the canary."""
+    raw = _root(a)
+    off = a.ctypes.data - raw.ctypes.data
+    return bool((raw[:off] == CANARY).all() and (raw[off + a.nbytes:] == CANARY).all())
+
+
+def place(kind, src, canary=False):
+    """A copy of `src` in memory of `kind` ('pageable' / 'pinned')."""
+    src = np.asarray(src)
+    a = (pageable if kind == 'pageable' else pinned)(src.shape, src.dtype, canary)
+    a[...] = src
+    return a
+
+
+# ---- mesh-free return map ----------------------------------------------------------------------------------------------------
+_BASE = {}
+
+
+def base(model):
+    """dict E (3, N_BASE), ep, mats (4 arrays), e0 (4,), field: computed once, never modified (callers copy)."""
+    if model not in _BASE:
+        E, ep, mats, e0, field = fcases.mesh_free(model, N_BASE, 'staging')
+        _BASE[model] = dict(E=np.ascontiguousarray(E), ep=np.ascontiguousarray(ep), mats=tuple(np.ascontiguousarray(m) for m in mats),
+                            e0=np.ascontiguousarray(e0).ravel(), field=np.ascontiguousarray(field))
+    return _BASE[model]
+
+
+def tile(a, n=N_POINTS):
+    """Columns k mod N_BASE of `a`, k < n."""
+    a = np.asarray(a)
+    reps = -(-n // a.shape[-1])
+    return np.ascontiguousarray(np.tile(a, reps)[..., :n])
+
+
+def tiled(model, n=N_POINTS):
+    b = base(model)
+    return dict(E=tile(b['E'], n), ep=tile(b['ep'], n), mats=tuple(tile(m, n) for m in b['mats']), e0=b['e0'], field=tile(b['field'], n))
+
+
+def _p(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def return_map_host(model, n, e, pt_stride, comp_stride, e0, ep, mats, accept, s, ds, ind, counts, field=None):
+    """The raw *_host call on NumPy arrays exactly where they lie (no copies, no conversions)."""
+    l = _lib.lib()
+    if field is None:
+        rc = getattr(l, ENTRY[model] + '_host')(0, n, _p(e), pt_stride, comp_stride, _p(e0), _p(ep), *[_p(m) for m in mats],
+                                                int(accept), _p(s), _p(ds), _p(ind), _p(counts))
+    else:
+        rc = l.fep_return_map_field_host(MODEL_ID[model], 0, n, _p(e), pt_stride, comp_stride, _p(e0), _p(field), FIELD_SCALE, _p(ep),
+                                         *[_p(m) for m in mats], int(accept), _p(s), _p(ds), _p(ind), _p(counts))
+    assert rc == 0, (model, rc)
+
+
+def return_map_dev(model, d, accept, with_field):
+    """The oracle: the same operation through the *_dev entry point on torch tensors (torch does every copy, the staging engine
+    is not involved), on torch's current stream, synchronised.  -> dict s, ds, ind, counts, ep as NumPy arrays."""
+    import torch
+    dev = torch.device('cuda', 0)
+    n = d['E'].shape[1]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    E, ep, mats = t(d['E']), t(d['ep']), [t(m) for m in d['mats']]
+    fld = t(d['field']) if with_field else None
+    s = torch.empty((4, n), dtype=torch.float64, device=dev)
+    ds = torch.empty((9, n), dtype=torch.float64, device=dev)
+    ind = torch.empty(n, dtype=torch.uint8, device=dev)
+    cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    l = _lib.lib()
+    e0 = np.ascontiguousarray(d['e0'])
+    if with_field:
+        rc = l.fep_return_map_field_dev(MODEL_ID[model], 0, st, n, E.data_ptr(), 1, n, _p(e0), fld.data_ptr(), FIELD_SCALE, ep.data_ptr(),
+                                        *[m.data_ptr() for m in mats], int(accept), s.data_ptr(), ds.data_ptr(), ind.data_ptr(),
+                                        cnt.data_ptr())
+    else:
+        rc = getattr(l, ENTRY[model] + '_dev')(0, st, n, E.data_ptr(), 1, n, _p(e0), ep.data_ptr(), *[m.data_ptr() for m in mats],
+                                               int(accept), s.data_ptr(), ds.data_ptr(), ind.data_ptr(), cnt.data_ptr())
+    assert rc == 0, (model, rc)
+    torch.cuda.synchronize()
+    return dict(s=s.cpu().numpy(), ds=ds.cpu().numpy(), ind=ind.cpu().numpy(), counts=cnt.cpu().numpy(), ep=ep.cpu().numpy())
+
+
+# ---- context calls -----------------------------------------------------------------------------------------------------------
+def displacement(coord):
+    """The displacement of the sharding test (tests/test_sharding_gpu.py), written on the mesh's own extent L: a smooth field
+    whose strains do not depend on the mesh size, elastic in one part of the square and on both plastic branches in others."""
+    x, y = coord
+    L = float(coord.max())
+    return np.array([2.5e-4 * y * (x / L) + 1.2e-4 * x * (y > L / 2), -1.5e-4 * y * (x < L / 2) + 2.0e-4 * y * (x >= L / 2)])
+
+
+def model_materials(model, n):
+    return fcases.uniform(model, n)
+
+
+# Factor on `displacement` per model, decided on the float64 restatement (e0_field_ref.return_map on the 40-cell square, whose
+# strains are those of any finer square): Drucker-Prager 1 (20 % smooth, 56 % apex), von Mises a quarter of the ratio of the
+# yield strains (45 % plastic; at the full ratio every point yields), Mohr-Coulomb the ratio (72 % face and edges, 24 % apex).
+_SCALE = {'dp': 1.0, 'vm': 0.25, 'mc': 1.0}
+
+
+def model_scale(model):
+    return _SCALE[model] * fcases.eps_y(model) / fcases.eps_y('dp')
+
+
+STEP_KEYS = ('E', 's', 'ds', 'ind_p', 'K', 'F')
+
+
+def step_shapes(ctx):
+    n = ctx.n_int
+    return {'E': ((3, n), np.float64), 's': ((4, n), np.float64), 'ds': ((9, n), np.float64), 'ind_p': ((n,), np.uint8),
+            'K': ((ctx.nnz,), np.float64), 'F': ((ctx.n_dof,), np.float64)}
+
+
+def step_host(ctx, u, ep, accept, want, kind='pageable', planar=False, e0=None, field=None, scale=1.0):
+    """Raw fep_step_host / _planar / _field_host with every output an array of `kind` followed by a canary tail.
+    `u`: DOF order, or the (2, n_n) array when `planar`.  -> dict of the outputs wanted + 'counts'; `ep` is updated in place."""
+    l = _lib.lib()
+    shp = step_shapes(ctx)
+    out = {k: (pageable if kind == 'pageable' else pinned)(*shp[k], canary=True) for k in want}
+    for v in out.values():
+        v.view(np.uint8).reshape(-1)[...] = 0x3C
+    out['counts'] = pageable((2,), np.int64, canary=True)
+    o = [_p(out.get(k)) for k in STEP_KEYS]
+    if field is not None:
+        rc = l.fep_step_field_host(ctx.handle, _p(u), _p(e0), _p(field), float(scale), _p(ep), int(accept), *o, _p(out['counts']))
+    else:
+        fn = l.fep_step_host_planar if planar else l.fep_step_host
+        rc = fn(ctx.handle, _p(u), _p(e0), _p(ep), int(accept), *o, _p(out['counts']))
+    assert rc == 0, rc
+    for k, v in out.items():
+        assert canary_intact(v), k
+    return out
+
+
+def step_dev(ctx, u, ep, accept, want, e0=None, field=None, scale=1.0, stream=None, sync=None):
+    """The oracle of step_host: fep_step_dev / fep_step_field_dev on torch tensors, torch's current stream, synchronised
+    (the whole device, or by `sync()` where a test wants no more than a wait for that stream).
+    `u` in DOF order.  -> dict of NumPy outputs + 'counts' + 'ep' (the plastic strain after the call)."""
+    import torch
+    dev = torch.device('cuda', 0)
+    shp = step_shapes(ctx)
+    tdt = {np.float64: torch.float64, np.uint8: torch.uint8}
+    U = torch.from_numpy(np.ascontiguousarray(u)).to(dev)
+    Ep = None if ep is None else torch.from_numpy(np.ascontiguousarray(ep)).to(dev)
+    F = None if field is None else torch.from_numpy(np.ascontiguousarray(field)).to(dev)
+    out = {k: torch.empty(shp[k][0], dtype=tdt[shp[k][1]], device=dev) for k in want}
+    cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    ctx.step_dev(torch.cuda.current_stream().cuda_stream if stream is None else stream, U.data_ptr(), ep=ptr(Ep), accept=accept, e0=e0,
+                 e_out=ptr(out.get('E')), s=ptr(out.get('s')), ds=ptr(out.get('ds')), ind_p=ptr(out.get('ind_p')),
+                 k_data=ptr(out.get('K')), f_out=ptr(out.get('F')), counts=cnt.data_ptr(),
+                 e0_field=None if F is None else F.data_ptr(), e0_scale=scale)
+    (torch.cuda.synchronize if sync is None else sync)()
+    r = {k: v.cpu().numpy() for k, v in out.items()}
+    r['counts'] = cnt.cpu().numpy()
+    r['ep'] = None if Ep is None else Ep.cpu().numpy()
+    return r

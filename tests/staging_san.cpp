@@ -1,16 +1,51 @@
 // Host-only driver of fem-elastoplasticity_amd/csrc/fep_staging.h for the sanitizer builds (tests/test_host_sanitizers.py:
-// g++ -fsanitize=address,undefined and -fsanitize=thread; CPU only).  The header's six kinds of HIP calls are replaced by
-// the host stand-ins below (FEP_STAGING_HOST_STUB): "device" memory is heap memory, copies are synchronous memcpy, and
+// g++ -fsanitize=address,undefined and -fsanitize=thread, FEP_COPY_THREADS = 1, 3 and 6; CPU only).  The header's six kinds
+// of HIP calls are replaced by the host stand-ins below (FEP_STAGING_HOST_STUB): "device" memory is heap memory, and
 // `g_fail_copy_after` / `g_fail_host_malloc` make the n-th copy / the next pinned allocation fail.
+//
+// The stand-ins DEFER every copy to the latest moment the API allows: hipMemcpyAsync only queues the copy on its stream,
+// hipEventRecord notes the queue position, and hipEventSynchronize / hipStreamSynchronize then run the queued copies up to
+// that position.  A slot that is refilled without waiting for its event, an event recorded before the copy it guards, or a
+// parked chunk that never leaves its slot therefore changes the bytes that arrive, on every run (with synchronous copies none
+// of them does).  A "kernel" is a function queued on the stream the same way (stub_launch).
 //   1. PinnedCache: reuse by size, double release refused, trim, allocation failure -> idle blocks given back -> retry
 //   2. CopyPool: copy / interleave2 from two threads at once (the pool is process-wide; ADVICE r2: jobs overwrote each other)
 //   3. Engine: pageable round trips through the ring; a copy that fails after a device -> host chunk was parked must leave
 //      no pending destination behind (the failed call's output array is freed right after: ASan sees any later write)
 //   4. two engines driven by two threads
+//   5. pageable transfers LONGER THAN THE RING, each direction alone and both together, at 0, 1, 8, slot - 8, slot, slot + 8,
+//      ring, ring + 8 and 5.5 slots + 1 bytes; h2d_interleave2 at 1, per - 1, per, per + 1, 4 per + 1 and 5 per + 1337 nodes
+//   6. a call shaped like return_map_host_impl (seven inputs of unequal sizes, a kernel, five outputs; pinned blocks, views
+//      into the middle of one, pageable arrays 8 bytes off their allocation, one pageable array both input and output), four
+//      times back to back so that the ring starts at each of its four positions
+//   7. small -> large -> small calls on one engine (Engine::buffer's grow path), and a buffer that grows while a copy into
+//      its old block is still queued
+// Every check of 5 - 7 compares every byte of the result, and every destination ends in a canary block (one slot long, so a
+// whole-slot overrun stays inside the allocation) that must come back untouched; sources have no slack, so ASan sees a read
+// past their end.
+//
+// What the checks catch (each mutant of the header built into this program; none is committed):
+//   mutant of fep_staging.h                                   first failing check (the same in both builds unless noted)
+//   settle(i) removed from Engine::h2d                         [h2d alone, 33554440 bytes] device block differs
+//   settle(i) removed from Engine::d2h                         [d2h alone, 33554440 bytes] output differs
+//   settle(i) removed from Engine::h2d_interleave2             [interleave2, 2097153 nodes] device block differs
+//   hipEventRecord before its hipMemcpyAsync, in h2d            [h2d alone, 33554440 bytes] device block differs
+//   hipEventRecord before its hipMemcpyAsync, in d2h            [engine error path] the round trip after the failed call differs
+//   hipEventRecord before its hipMemcpyAsync, in interleave2    [interleave2, 2097153 nodes] device block differs
+//   finish() synchronises without settling the parked chunks   [engine error path] the round trip after the failed call differs
+//   tail size min(kSlotBytes, bytes - off) -> kSlotBytes        h2d, d2h: [engine error path], interleave2: [interleave2, 1 nodes]:
+//     (in h2d, d2h, or min(per, n - off) -> per in interleave2)  the ASan build reports the access past the end of a heap block,
+//                                                              deterministically.  The TSan build checks no bounds: there the
+//                                                              mutants showed as a race report or a crash in the same place,
+//                                                              which is incidental and asserted nowhere; where a run survives
+//                                                              the overrun, the one-slot canary behind the destination catches it
 #include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -19,10 +54,29 @@
 #define FEP_STAGING_HOST_STUB 1
 typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
-typedef struct StubStream* hipStream_t;
-typedef struct StubEvent* hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
 enum { hipHostMallocDefault = 0, hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
+// A stream is the queue of its pending operations; positions count operations since the stream was made.
+struct StubOp { void* dst; const void* src; size_t bytes; void (*fn)(void*); void* arg; };
+struct StubStream {
+    std::mutex m;                                        // the two-engine test drives two streams from two threads
+    std::deque<StubOp> q;                                // queued and not yet run, oldest first
+    size_t queued = 0, done = 0;                         // operations queued / run so far
+    void push(const StubOp& op) { std::lock_guard<std::mutex> g(m); q.push_back(op); ++queued; }
+    size_t position() { std::lock_guard<std::mutex> g(m); return queued; }
+    void run_to(size_t pos) {
+        std::lock_guard<std::mutex> g(m);
+        while (done < pos && !q.empty()) {
+            const StubOp op = q.front();
+            q.pop_front();
+            if (op.fn) op.fn(op.arg); else std::memcpy(op.dst, op.src, op.bytes);
+            ++done;
+        }
+    }
+};
+struct StubEvent { StubStream* st = nullptr; size_t pos = 0; };       // never recorded: nothing to wait for
+typedef StubStream* hipStream_t;
+typedef StubEvent* hipEvent_t;
 static thread_local int fep_g_last_hip = 0;
 static std::atomic<long> g_copies{0}, g_fail_copy_after{-1};
 static std::atomic<int> g_fail_host_malloc{0};
@@ -35,18 +89,20 @@ static hipError_t hipHostMalloc(void** p, size_t b, unsigned) {
 static hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
 static hipError_t hipMalloc(void** p, size_t b) { *p = std::malloc(b); return *p ? hipSuccess : hipErrorOutOfMemory; }
 static hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
-static hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)std::malloc(1); return hipSuccess; }
-static hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)std::malloc(1); return hipSuccess; }
-static hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-static hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-static hipError_t hipMemcpyAsync(void* d, const void* s, size_t b, hipMemcpyKind, hipStream_t) {
+static hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new StubStream(); return hipSuccess; }
+static hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new StubEvent(); return hipSuccess; }
+static hipError_t hipStreamSynchronize(hipStream_t s) { s->run_to(s->position()); return hipSuccess; }
+static hipError_t hipEventSynchronize(hipEvent_t e) { if (e->st) e->st->run_to(e->pos); return hipSuccess; }
+static hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { e->st = s; e->pos = s->position(); return hipSuccess; }
+static hipError_t hipMemcpyAsync(void* d, const void* s, size_t b, hipMemcpyKind, hipStream_t st) {
     const long k = g_copies.fetch_add(1);
     const long f = g_fail_copy_after.load();
-    if (f >= 0 && k >= f) return hipErrorUnknown;
-    std::memcpy(d, s, b);
+    if (f >= 0 && k >= f) return hipErrorUnknown;        // a failing call queues nothing
+    st->push(StubOp{d, s, b, nullptr, nullptr});
     return hipSuccess;
 }
+// a "kernel": fn(arg) runs in stream order, when a synchronise reaches it
+static void stub_launch(hipStream_t st, void (*fn)(void*), void* arg) { st->push(StubOp{nullptr, nullptr, 0, fn, arg}); }
 #define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fep_g_last_hip = (int)_e; return _e == hipErrorOutOfMemory ? FEP_ENOMEM : FEP_EHIP; } } while (0)
 #define FEP_TRY(expr) do { int _r = (expr); if (_r != FEP_OK) return _r; } while (0)
 
@@ -54,9 +110,12 @@ static hipError_t hipMemcpyAsync(void* d, const void* s, size_t b, hipMemcpyKind
 
 using namespace fep_stage;
 
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } } while (0)
+static char g_what[96] = "start";                      // the check in progress, printed with a failure
+#define WHAT(...) std::snprintf(g_what, sizeof g_what, __VA_ARGS__)
+#define CHECK(cond) do { if (!(cond)) { std::printf("FAILED [%s] %s:%d: %s\n", g_what, __FILE__, __LINE__, #cond); return 1; } } while (0)
 
 static int test_pinned() {
+    WHAT("pinned cache");
     PinnedCache pc;
     void *a = nullptr, *b = nullptr, *c = nullptr;
     CHECK(pc.alloc(&a, 4096) == FEP_OK && pc.alloc(&b, 8192) == FEP_OK);
@@ -91,6 +150,7 @@ static int pool_worker(int seed, int* rc) {
 }
 
 static int test_pool_two_callers() {
+    WHAT("pool, two callers");
     int rc1 = 0, rc2 = 0;
     std::thread t1(pool_worker, 1, &rc1), t2(pool_worker, 2, &rc2);
     t1.join(); t2.join();
@@ -125,6 +185,7 @@ static int failing_call(Engine* E, double* out, size_t n, void* dbuf) {
 }
 
 static int test_engine_error_path() {
+    WHAT("engine error path");
     Engine* E = nullptr;
     CHECK(engine(7, &E) == FEP_OK);
     const size_t n = ((size_t)20 << 20) / sizeof(double);
@@ -154,10 +215,286 @@ static int test_engine_error_path() {
 }
 
 static int test_two_engines() {
+    WHAT("two engines");
     int rc1 = 0, rc2 = 0;
     std::thread t1(engine_round_trip, 0, &rc1), t2(engine_round_trip, 1, &rc2);
     t1.join(); t2.join();
     CHECK(rc1 == 0 && rc2 == 0);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// transfers longer than the ring
+// ---------------------------------------------------------------------------------------
+static constexpr size_t kSlot = Engine::kSlotBytes, kRing = Engine::kSlots * Engine::kSlotBytes;
+static constexpr size_t kCanary = kSlot;
+static constexpr unsigned char kCanaryByte = 0xC5;
+
+static uint64_t mix(uint64_t x) {                        // splitmix64: no period a slot or the ring could share
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// byte j of the pattern `seed` is byte j % 8 of mix(seed + j / 8); p is 8-byte aligned
+static void fill(void* p, size_t bytes, uint64_t seed) {
+    uint64_t* w = (uint64_t*)p;
+    const size_t nw = bytes / 8;
+    for (size_t i = 0; i < nw; ++i) w[i] = mix(seed + i);
+    if (bytes % 8) { const uint64_t v = mix(seed + nw); std::memcpy((char*)p + 8 * nw, &v, bytes % 8); }
+}
+static bool is_fill(const void* p, size_t bytes, uint64_t seed) {
+    const uint64_t* w = (const uint64_t*)p;
+    const size_t nw = bytes / 8;
+    for (size_t i = 0; i < nw; ++i) if (w[i] != mix(seed + i)) return false;
+    if (bytes % 8) { const uint64_t v = mix(seed + nw); if (std::memcmp((const char*)p + 8 * nw, &v, bytes % 8) != 0) return false; }
+    return true;
+}
+
+// [lead][bytes][tail]: p = base + lead.  Pageable: a heap block with p 8 bytes in (8- but not 64-byte aligned).  Pinned: a
+// block of the cache with p 4104 bytes in, a view into its middle.  lead and tail hold the canary byte; a source has no tail.
+struct Buf {
+    char *base = nullptr, *p = nullptr;
+    size_t bytes = 0, lead = 0, tail = 0;
+    bool pin = false;
+    Buf(size_t b, bool pinned_block, size_t tail_bytes) : bytes(b), lead(pinned_block ? 4104 : 8), tail(tail_bytes), pin(pinned_block) {
+        void* q = nullptr;
+        if (pin) { if (pinned().alloc(&q, lead + bytes + tail) != FEP_OK) q = nullptr; }
+        else q = std::malloc(lead + bytes + tail);
+        if (!q) { std::printf("FAILED: out of memory\n"); std::exit(1); }
+        base = (char*)q; p = base + lead;
+        std::memset(base, kCanaryByte, lead);
+        if (tail) std::memset(p, 0x3C, bytes);           // a destination starts out as neither the pattern nor the canary
+        std::memset(p + bytes, kCanaryByte, tail);
+    }
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { if (pin) (void)pinned().release(base); else std::free(base); }
+    bool canary_ok() const {
+        for (size_t i = 0; i < lead; ++i) if ((unsigned char)base[i] != kCanaryByte) return false;
+        const unsigned char* t = (const unsigned char*)p + bytes;
+        size_t i = 0;
+        for (; i < tail && ((uintptr_t)(t + i) & 7); ++i) if (t[i] != kCanaryByte) return false;
+        for (; i + 8 <= tail; i += 8) if (*(const uint64_t*)(t + i) != 0xC5C5C5C5C5C5C5C5ull) return false;
+        for (; i < tail; ++i) if (t[i] != kCanaryByte) return false;
+        return true;
+    }
+};
+
+static int round_trips(Engine* E, size_t bytes) {
+    const uint64_t seed = 3 * bytes + 1;
+    {
+        WHAT("h2d alone, %zu bytes", bytes);
+        Buf src(bytes, false, 0), dev(bytes, false, kCanary);
+        fill(src.p, bytes, seed);
+        {
+            EngineCall call(E);
+            CHECK(E->h2d(dev.p, src.p, bytes) == FEP_OK);
+            CHECK(call.finish() == FEP_OK);
+        }
+        CHECK(is_fill(dev.p, bytes, seed));              // device block differs
+        CHECK(dev.canary_ok());
+    }
+    {
+        WHAT("d2h alone, %zu bytes", bytes);
+        Buf dev(bytes, false, 0), out(bytes, false, kCanary);
+        fill(dev.p, bytes, seed + 1);
+        {
+            EngineCall call(E);
+            CHECK(E->d2h(out.p, dev.p, bytes) == FEP_OK);
+            CHECK(call.finish() == FEP_OK);
+        }
+        CHECK(is_fill(out.p, bytes, seed + 1));          // output differs
+        CHECK(out.canary_ok());
+    }
+    {
+        WHAT("h2d + d2h, %zu bytes", bytes);
+        Buf src(bytes, false, 0), out(bytes, false, kCanary);
+        fill(src.p, bytes, seed + 2);
+        {
+            EngineCall call(E);
+            void* dbuf = nullptr;
+            CHECK(E->buffer(0, bytes, &dbuf) == FEP_OK);
+            CHECK(E->h2d(dbuf, src.p, bytes) == FEP_OK);
+            CHECK(E->d2h(out.p, dbuf, bytes) == FEP_OK);
+            CHECK(call.finish() == FEP_OK);
+        }
+        CHECK(is_fill(out.p, bytes, seed + 2));
+        CHECK(out.canary_ok());
+    }
+    return 0;
+}
+
+static int interleave_case(Engine* E, size_t n) {
+    WHAT("interleave2, %zu nodes", n);
+    Buf src(16 * n, false, 0), dev(16 * n, false, kCanary);
+    double* x = (double*)src.p;
+    double* y = x + n;
+    for (size_t i = 0; i < n; ++i) { x[i] = (double)(mix(5 * n + i) >> 11); y[i] = -(double)(mix(7 * n + i + (1ull << 40)) >> 11); }
+    {
+        EngineCall call(E);
+        CHECK(E->h2d_interleave2(dev.p, x, n) == FEP_OK);
+        CHECK(call.finish() == FEP_OK);
+    }
+    const double* d = (const double*)dev.p;
+    size_t bad = 0;
+    for (size_t i = 0; i < n; ++i) bad += (d[2 * i] != x[i]) + (d[2 * i + 1] != y[i]);
+    CHECK(bad == 0);                                     // device block differs
+    CHECK(dev.canary_ok());
+    return 0;
+}
+
+static int test_longer_than_the_ring() {
+    Engine* E = nullptr;
+    CHECK(engine(11, &E) == FEP_OK);
+    const size_t sizes[] = {0, 1, 8, kSlot - 8, kSlot, kSlot + 8, kRing, kRing + 8, 5 * kSlot + kSlot / 2 + 1};
+    for (size_t b : sizes) if (round_trips(E, b)) return 1;
+    const size_t per = kSlot / 16;
+    const size_t nodes[] = {1, per - 1, per, per + 1, 4 * per + 1, 5 * per + 1337};
+    for (size_t n : nodes) if (interleave_case(E, n)) return 1;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// a call shaped like return_map_host_impl
+// ---------------------------------------------------------------------------------------
+// The "return map" on 64-bit words (integers: every bit pattern compares).  Reads all seven inputs, writes the five
+// outputs; ep is updated in place after s has read it.
+struct RmArgs {
+    size_t n;
+    const uint64_t *e, *sh, *bu, *et, *cc, *fld;         // 3n, n, n, n, n, 4n
+    uint64_t *ep, *s, *ds;                               // 4n (in and out), 4n, 9n
+    unsigned char* ip;                                   // n bytes
+    uint64_t* cnt;                                       // 2
+};
+static void rm_compute(void* a) {
+    const RmArgs& k = *(const RmArgs*)a;
+    const size_t n = k.n;
+    for (size_t i = 0; i < 4 * n; ++i) k.s[i] = k.e[i % (3 * n)] ^ (k.ep[i] << 7 | k.ep[i] >> 57) ^ k.sh[i % n];
+    for (size_t i = 0; i < 9 * n; ++i) k.ds[i] = (k.bu[i % n] + k.et[(7 * i) % n]) ^ k.fld[i % (4 * n)];
+    uint64_t c0 = 0, c1 = 0;
+    for (size_t i = 0; i < n; ++i) { k.ip[i] = (unsigned char)(k.cc[i] >> 3); c0 += k.sh[i]; c1 ^= k.fld[3 * n + i]; }
+    k.cnt[0] = c0; k.cnt[1] = c1;
+    for (size_t i = 0; i < 4 * n; ++i) k.ep[i] = 3 * k.ep[i] + k.fld[i];
+}
+
+struct RmHost {                                          // the caller's arrays: pageable (8 bytes off) and pinned, mixed
+    static constexpr size_t n = 300007;                  // e 0.86 slots, ep / field / s 1.14, ds 2.57: 7 pageable chunks in, 7 out
+    Buf e{3 * n * 8, false, 0}, ep{4 * n * 8, false, kCanary}, sh{n * 8, true, 0}, bu{n * 8, false, 0}, et{n * 8, false, 0},
+        cc{n * 8, true, 0}, fld{4 * n * 8, false, 0};
+    Buf s{4 * n * 8, true, kCanary}, ds{9 * n * 8, false, kCanary}, ip{n, false, kCanary}, cnt{16, false, kCanary};
+    Buf extra{8, false, 0};
+};
+
+static int rm_call(Engine* E, RmHost& h, uint64_t seed, bool extra_first, int* start_slot) {
+    const size_t n = RmHost::n, nb = n * 8;
+    fill(h.e.p, 3 * nb, seed); fill(h.sh.p, nb, seed + 1); fill(h.bu.p, nb, seed + 2); fill(h.et.p, nb, seed + 3);
+    fill(h.cc.p, nb, seed + 4); fill(h.fld.p, 4 * nb, seed + 5);
+    std::memset(h.s.p, 0x3C, 4 * nb); std::memset(h.ds.p, 0x3C, 9 * nb); std::memset(h.ip.p, 0x3C, n); std::memset(h.cnt.p, 0x3C, 16);
+    // what the call must return: the same function on copies of the inputs
+    std::vector<uint64_t> r_ep(4 * n), r_s(4 * n), r_ds(9 * n), r_cnt(2);
+    std::vector<unsigned char> r_ip(n);
+    std::memcpy(r_ep.data(), h.ep.p, 4 * nb);
+    RmArgs ref{n, (const uint64_t*)h.e.p, (const uint64_t*)h.sh.p, (const uint64_t*)h.bu.p, (const uint64_t*)h.et.p,
+               (const uint64_t*)h.cc.p, (const uint64_t*)h.fld.p, r_ep.data(), r_s.data(), r_ds.data(), r_ip.data(), r_cnt.data()};
+    rm_compute(&ref);
+    RmArgs dev{};
+    {
+        EngineCall call(E);
+        void *e, *ep, *sh, *bu, *et, *cc, *s, *ds, *ip, *cnt, *fld, *x;
+        CHECK(E->buffer(0, 3 * nb, &e) == FEP_OK && E->buffer(1, 4 * nb, &ep) == FEP_OK && E->buffer(2, nb, &sh) == FEP_OK);
+        CHECK(E->buffer(3, nb, &bu) == FEP_OK && E->buffer(4, nb, &et) == FEP_OK && E->buffer(5, nb, &cc) == FEP_OK);
+        CHECK(E->buffer(6, 4 * nb, &s) == FEP_OK && E->buffer(7, 9 * nb, &ds) == FEP_OK && E->buffer(8, n, &ip) == FEP_OK);
+        CHECK(E->buffer(9, 16, &cnt) == FEP_OK && E->buffer(10, 4 * nb, &fld) == FEP_OK && E->buffer(11, 8, &x) == FEP_OK);
+        if (extra_first) CHECK(E->h2d(x, h.extra.p, 8) == FEP_OK);      // one more chunk: the ring starts one slot further on
+        *start_slot = E->next;
+        CHECK(E->h2d(e, h.e.p, 3 * nb) == FEP_OK && E->h2d(ep, h.ep.p, 4 * nb) == FEP_OK);
+        CHECK(E->h2d(sh, h.sh.p, nb) == FEP_OK && E->h2d(bu, h.bu.p, nb) == FEP_OK);
+        CHECK(E->h2d(et, h.et.p, nb) == FEP_OK && E->h2d(cc, h.cc.p, nb) == FEP_OK && E->h2d(fld, h.fld.p, 4 * nb) == FEP_OK);
+        dev = RmArgs{n, (const uint64_t*)e, (const uint64_t*)sh, (const uint64_t*)bu, (const uint64_t*)et, (const uint64_t*)cc,
+                     (const uint64_t*)fld, (uint64_t*)ep, (uint64_t*)s, (uint64_t*)ds, (unsigned char*)ip, (uint64_t*)cnt};
+        stub_launch(E->stream, rm_compute, &dev);
+        CHECK(E->d2h(h.s.p, s, 4 * nb) == FEP_OK && E->d2h(h.ds.p, ds, 9 * nb) == FEP_OK && E->d2h(h.ip.p, ip, n) == FEP_OK);
+        CHECK(E->d2h(h.cnt.p, cnt, 16) == FEP_OK && E->d2h(h.ep.p, ep, 4 * nb) == FEP_OK);
+        CHECK(call.finish() == FEP_OK);
+    }
+    CHECK(std::memcmp(h.s.p, r_s.data(), 4 * nb) == 0);
+    CHECK(std::memcmp(h.ds.p, r_ds.data(), 9 * nb) == 0);
+    CHECK(std::memcmp(h.ip.p, r_ip.data(), n) == 0);
+    CHECK(std::memcmp(h.cnt.p, r_cnt.data(), 16) == 0);
+    CHECK(std::memcmp(h.ep.p, r_ep.data(), 4 * nb) == 0);
+    CHECK(h.s.canary_ok() && h.ds.canary_ok() && h.ip.canary_ok() && h.cnt.canary_ok() && h.ep.canary_ok());
+    // the inputs are the caller's: untouched
+    CHECK(is_fill(h.e.p, 3 * nb, seed) && is_fill(h.sh.p, nb, seed + 1) && is_fill(h.bu.p, nb, seed + 2));
+    CHECK(is_fill(h.et.p, nb, seed + 3) && is_fill(h.cc.p, nb, seed + 4) && is_fill(h.fld.p, 4 * nb, seed + 5));
+    return 0;
+}
+
+static int test_return_map_shaped_calls() {
+    Engine* E = nullptr;
+    CHECK(engine(12, &E) == FEP_OK);
+    RmHost h;
+    fill(h.ep.p, 4 * RmHost::n * 8, 99);
+    fill(h.extra.p, 8, 98);
+    unsigned starts = 0;
+    for (int run = 0; run < 4; ++run) {
+        WHAT("return-map-shaped call, run %d", run);
+        int start = -1;
+        if (rm_call(E, h, 1000 * (uint64_t)(run + 1), run > 0, &start)) return 1;
+        starts |= 1u << start;
+    }
+    WHAT("return-map-shaped calls: ring start positions");
+    CHECK(starts == (1u << Engine::kSlots) - 1);         // 14 pageable chunks per call + 1: starts at slots 0, 3, 2, 1
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Engine::buffer's grow path
+// ---------------------------------------------------------------------------------------
+static int sized_round_trip(Engine* E, size_t bytes, uint64_t seed, bool check_rest, size_t rest) {
+    Buf src(bytes, false, 0), out(bytes, false, kCanary);
+    fill(src.p, bytes, seed);
+    void* dbuf = nullptr;
+    {
+        EngineCall call(E);
+        CHECK(E->buffer(0, bytes, &dbuf) == FEP_OK);
+        if (check_rest) { CHECK(E->dev[0].second == bytes + rest); std::memset((char*)dbuf + bytes, kCanaryByte, rest); }
+        CHECK(E->h2d(dbuf, src.p, bytes) == FEP_OK);
+        CHECK(E->d2h(out.p, dbuf, bytes) == FEP_OK);
+        CHECK(call.finish() == FEP_OK);
+    }
+    CHECK(is_fill(out.p, bytes, seed));
+    CHECK(out.canary_ok());
+    if (check_rest)                                      // the block kept its larger size: nothing written past the small call's end
+        for (size_t i = 0; i < rest; ++i) CHECK(((unsigned char*)dbuf)[bytes + i] == kCanaryByte);
+    return 0;
+}
+
+static int test_buffer_growth() {
+    Engine* E = nullptr;
+    CHECK(engine(13, &E) == FEP_OK);
+    const size_t small = 8000, large = 5 * kSlot + kSlot / 2 + 1;
+    WHAT("small call on a new engine");
+    if (sized_round_trip(E, small, 1, false, 0)) return 1;
+    WHAT("large call after the small one");
+    if (sized_round_trip(E, large, 2, false, 0)) return 1;
+    WHAT("small call after the large one");
+    if (sized_round_trip(E, small, 3, true, large - small)) return 1;
+    WHAT("buffer grows while a copy into its old block is queued");
+    Buf src(small, false, 0), out(2 * small, false, kCanary);
+    fill(src.p, small, 4);
+    fill(out.p, 2 * small, 5);
+    {
+        EngineCall call(E);
+        void *a = nullptr, *b = nullptr;
+        CHECK(E->buffer(1, small, &a) == FEP_OK);
+        CHECK(E->h2d(a, src.p, small) == FEP_OK);        // queued; the block is freed by the next line: it must synchronise first
+        CHECK(E->buffer(1, 2 * small, &b) == FEP_OK);
+        CHECK(E->h2d(b, out.p, 2 * small) == FEP_OK);
+        CHECK(E->d2h(out.p, b, 2 * small) == FEP_OK);
+        CHECK(call.finish() == FEP_OK);
+    }
+    CHECK(is_fill(out.p, 2 * small, 5) && out.canary_ok());
     return 0;
 }
 
@@ -166,6 +503,10 @@ int main() {
     if (test_pool_two_callers()) return 1;
     if (test_engine_error_path()) return 1;
     if (test_two_engines()) return 1;
+    if (test_longer_than_the_ring()) return 1;
+    if (test_return_map_shaped_calls()) return 1;
+    if (test_buffer_growth()) return 1;
+    if (pinned().trim() != FEP_OK) return 1;             // the callers' pinned arrays went back to the cache: unpin them
     std::printf("staging ok\n");
     return 0;
 }

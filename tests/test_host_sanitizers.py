@@ -191,20 +191,36 @@ def test_node_row_over_256_blocks_is_erange(fep, binaries, tmp_path, t, k, block
     assert 'runtime error' not in res.stdout and 'Sanitizer' not in res.stdout, res.stdout[-3000:]
 
 
-@pytest.mark.parametrize('kind', ['asan', 'tsan'])
-def test_staging_classes_under_sanitizers(tmp_path, kind):
+@pytest.fixture(scope='module')
+def staging_binaries(tmp_path_factory):
+    """tests/staging_san.cpp under both sanitizer builds, compiled once for all copy-thread counts."""
+    if shutil.which('g++') is None:
+        pytest.skip('g++ not available')
+    tmp = tmp_path_factory.mktemp('staging_san')
+    out = {}
+    for kind in ('asan', 'tsan'):
+        exe = str(tmp / f'staging_{kind}')
+        flags = {'asan': ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'], 'tsan': ['-fsanitize=thread']}[kind]
+        res = subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-pthread'] + flags + ['-o', exe, os.path.join(ROOT, 'tests', 'staging_san.cpp')],
+                             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert res.returncode == 0, res.stdout[-3000:]
+        out[kind] = exe
+    return out
+
+
+# (the case of six copy threads keeps the id it had before the other counts came)
+@pytest.mark.parametrize('kind,threads', [pytest.param(k, t, id=k if t == 6 else f'{k}-{t}threads')
+                                          for k in ('asan', 'tsan') for t in (6, 1, 3)])
+def test_staging_classes_under_sanitizers(staging_binaries, kind, threads):
     """fep_staging.h (pinned cache, copy-thread pool, per-device staging engine) against a host stand-in of its HIP calls
     (tests/staging_san.cpp): two host threads through the process-wide pool, two engines, a copy that fails after a
     device -> host chunk was parked (no pending destination may survive the failed call), double release, allocation
-    failure with idle blocks to give back."""
-    if shutil.which('g++') is None:
-        pytest.skip('g++ not available')
-    exe = str(tmp_path / f'staging_{kind}')
-    flags = {'asan': ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'], 'tsan': ['-fsanitize=thread']}[kind]
-    res = subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-pthread'] + flags + ['-o', exe, os.path.join(ROOT, 'tests', 'staging_san.cpp')],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout[-3000:]
-    env = dict(os.environ, FEP_COPY_THREADS='6', ASAN_OPTIONS='detect_leaks=1', TSAN_OPTIONS='halt_on_error=1')
+    failure with idle blocks to give back.  The stand-in defers every copy to the synchronise that must wait for it, so a
+    slot reused too early, an event recorded too early or a parked chunk left behind changes the result; transfers longer
+    than the ring in each direction, h2d_interleave2, a call shaped like the return map's at every ring start position,
+    unaligned and mid-block views and the buffers' grow path, with 1, 3 and 6 copy threads (1: no worker thread at all)."""
+    exe = staging_binaries[kind]
+    env = dict(os.environ, FEP_COPY_THREADS=str(threads), ASAN_OPTIONS='detect_leaks=1', TSAN_OPTIONS='halt_on_error=1')
     res = subprocess.run([exe], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert res.returncode == 0 and 'staging ok' in res.stdout, res.stdout[-3000:]
     assert 'Sanitizer' not in res.stdout and 'runtime error' not in res.stdout, res.stdout[-3000:]
