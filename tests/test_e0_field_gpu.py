@@ -34,6 +34,7 @@ import e0_field_ref as fref
 import loads_exact
 from conftest import dp_materials, load_golden, relerr, relerr_points
 from elem_ref import U_RND, ElemRef, ratio
+from footprint import scrub
 from routes import assert_route
 from test_element_route_gpu import C_E, C_F, C_K, C_RECORD
 
@@ -122,9 +123,15 @@ def test_field_step_vs_reference_per_entry(fep, monkeypatch, model, t, route, na
             ctx.set_model(model)
         ctx.set_materials(*mats)
         ep = Ep.copy()
+        # scrub between the forms: none may pass its pin with what the call before left in the context's device buffers
+        if accept:
+            scrub(ctx, U, Ep, kw)
         full = ctx.step(U, ep, apply_plastic_strain=accept, want=EVERY, **kw)
+        scrub(ctx, U, Ep, kw)
         kf = ctx.step(U, Ep.copy(), want=('K', 'F'), **kw)
+        scrub(ctx, U, Ep, kw)
         k_only = ctx.step(U, Ep.copy(), want=('K',), **kw)
+        scrub(ctx, U, Ep, kw)
         f_only = ctx.step(U, Ep.copy(), want=('F',), **kw)
         none = ctx.step(U, None, want=EVERY, **kw)
         zero = ctx.step(U, np.zeros((4, n_int)), want=EVERY, **kw)

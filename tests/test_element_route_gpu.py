@@ -23,6 +23,7 @@ import pytest
 import meshes
 from conftest import dp_materials, load_golden, relerr_points
 from elem_ref import ElemRef, ratio, reverse_elements
+from footprint import scrub
 from meshes import named as _mesh
 from oracle import fep_oracle as orc
 from routes import assert_route
@@ -114,10 +115,17 @@ def _run_case(fep, monkeypatch, capfd, t, route, elem, coord, kind, h, rng, stru
     ctx.set_materials(*mats)
     kw = {} if e0 is None else {'e0': e0}
     ep = Ep.copy()                                                  # pageable, updated in place on accept
+    # scrub between the forms: none may pass its pin with what the call before left in the context's device buffers
+    if accept:
+        scrub(ctx, U, Ep, kw)
     full = ctx.step(U, ep, apply_plastic_strain=accept, want=('E', 's', 'ds', 'ind_p', 'K', 'F'), **kw)
+    scrub(ctx, U, Ep, kw)
     kf = ctx.step(U, Ep.copy(), want=('K', 'F'), **kw)
+    scrub(ctx, U, Ep, kw)
     k_only = ctx.step(U, Ep.copy(), want=('K',), **kw)
+    scrub(ctx, U, Ep, kw)
     f_only = ctx.step(U, Ep.copy(), want=('F',), **kw)
+    scrub(ctx, U, Ep, kw)
     K2, F2 = ctx.assemble(full['ds'], full['s'])
     pattern = ctx.pattern()
     ctx.close()

@@ -18,6 +18,7 @@ import pytest
 
 from conftest import dp_materials, relerr, relerr_points, relerr_rows
 from fan_mesh import centre_of, fan_mesh, row_blocks
+from footprint import scrub
 from oracle import fep_oracle as orc
 from routes import assert_route
 
@@ -62,9 +63,12 @@ def test_fan_mesh_vs_oracle(fep, monkeypatch, t, k, picked, route):
     assert_route(ctx, picked if route == 'default' else 'coo')
     ctx.set_materials(sh, bu, eta, c)
     full = ctx.step(U, Ep.copy(), want=('E', 's', 'ds', 'ind_p', 'K', 'F'))
+    scrub(ctx, U, Ep)                         # between the forms: none passes with what the one before left on the device
     kf = ctx.step(U, Ep.copy(), want=('K', 'F'))                         # the node route's one-kernel step
     ep = Ep.copy()
+    scrub(ctx, U, Ep)
     acc = ctx.step(U, ep, apply_plastic_strain=True, want=('s', 'K', 'F'))
+    scrub(ctx, U, Ep)
     K2, F2 = ctx.assemble(full['ds'], full['s'])
     ctx.close()
     for r in (kf, acc):

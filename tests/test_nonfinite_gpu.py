@@ -34,6 +34,7 @@ import nonfinite_cases as nf
 import solver_cases as sc
 from conftest import dp_materials, relerr, relerr_points
 from elem_ref import ratio
+from footprint import scrub
 from model_ref import dev_return_map
 from routes import assert_route
 from test_element_route_gpu import C_K, C_RECORD
@@ -197,12 +198,19 @@ def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, rou
         kw = {} if e0 is None else {'e0': e0}
         first = ctx.step(U, Ep.copy(), want=EVERY, **kw)
         bad = ctx.step(U_bad, Ep.copy(), want=EVERY, **kw)
+        # scrub between the forms: none may pass its pin with what the call before left in the context's device buffers
+        scrub(ctx, U_bad, Ep, kw)
         kf = ctx.step(U_bad, Ep.copy(), want=('K', 'F'), **kw)
+        scrub(ctx, U_bad, Ep, kw)
         k_only = ctx.step(U_bad, Ep.copy(), want=('K',), **kw)
+        scrub(ctx, U_bad, Ep, kw)
         f_only = ctx.step(U_bad, Ep.copy(), want=('F',), **kw)
+        scrub(ctx, U_bad, Ep, kw)
         K2, F2 = ctx.assemble(bad['ds'], bad['s'])
         ep_bad, ep_good = Ep.copy(), Ep.copy()
+        scrub(ctx, U_bad, Ep, kw)
         acc_bad = ctx.step(U_bad, ep_bad, apply_plastic_strain=True, want=('ind_p',), **kw)
+        scrub(ctx, U, Ep, kw)
         acc_good = ctx.step(U, ep_good, apply_plastic_strain=True, want=('ind_p',), **kw)
         last = ctx.step(U, Ep.copy(), want=EVERY, **kw)
         pattern = ctx.pattern()

@@ -15,6 +15,7 @@ import scipy.sparse as ssp
 
 from conftest import dp_materials, load_golden, relerr, relerr_points, relerr_rows
 from fan_mesh import fan_mesh
+from footprint import scrub
 from meshes import rect as rect_mesh_of, square as square_mesh_of
 from oracle import fep_oracle as orc
 from routes import assert_route
@@ -225,11 +226,16 @@ def test_p1_fused_step_is_bitwise_the_two_kernel_route(fep, monkeypatch, name):
     ep = Ep.copy()
     kw = {} if e0 is None else {'e0': e0}
     full = ctx.step(U, ep, want=('E', 's', 'ds', 'ind_p', 'K', 'F'), **kw)        # point outputs wanted: two kernels
+    scrub(ctx, U, Ep, kw)                     # between the forms: none passes with what the one before left on the device
     kf = ctx.step(U, ep, want=('K', 'F'), **kw)                                    # the one-kernel step
+    scrub(ctx, U, Ep, kw)
     k_only = ctx.step(U, ep, want=('K',), **kw)
+    scrub(ctx, U, Ep, kw)
     f_only = ctx.step(U, None, want=('F',), **kw)
+    scrub(ctx, U, Ep, kw)
     f_zero_ep = ctx.step(U, np.zeros_like(Ep), want=('s', 'F'), **kw)              # two kernels, the state f_only ran on
     assert np.array_equal(ep, Ep)
+    scrub(ctx, U, Ep, kw)
     K2, F2 = ctx.assemble(full['ds'], full['s'])                                   # assembly kernel alone on the stored ds / s
     ctx.close()
     assert full['n_smooth'] > 0 and full['n_apex'] > 0
