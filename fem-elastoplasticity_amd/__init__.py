@@ -17,6 +17,7 @@ from .tables import (ELEMENT_SHAPE, LagrangeElementType, element_tables, get_loc
 from .mesh import assemble_mesh, assemble_mesh_el, rect_mesh, renumber_for_locality, square_mesh
 from .hotpath import (MeshContext, assemble_tangent, construct_constitutive_problem,
                       construct_constitutive_problem_tsx, construct_constitutive_problem_vm, construct_constitutive_problem_mc,
+                      construct_constitutive_problem_vmps,
                       construct_constitutive_problem_field, in_situ_strain, linear_in_situ, default_device, get_elastic_stiffness_matrix,
                       get_elastic_stiffness_matrix_el, get_vector_traction, get_vector_volume, load_traction)
 from .elastic import solve_elasticity2d
@@ -40,6 +41,7 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'create_midpoints_P4', 'refine_uniform', 'DeviceMesh', 'Ellipse', 'area_stats', 'area_stats_dev', 'load_tsx_mesh', 'prepare_tsx_mesh', 'dump_free_dof_csv',
            'get_quadrature_surface', 'get_local_basis_surface', 'surface_tables', 'assemble_mesh_el', 'get_vector_volume',
            'get_vector_traction', 'load_traction', 'solve_elasticity2d',
-           'construct_constitutive_problem_vm', 'construct_constitutive_problem_mc', 'solve_cutout_cyclic',
+           'construct_constitutive_problem_vm', 'construct_constitutive_problem_mc', 'construct_constitutive_problem_vmps',
+           'solve_cutout_cyclic',
            'construct_constitutive_problem_field', 'in_situ_strain', 'linear_in_situ',
            'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d', 'vonmises']

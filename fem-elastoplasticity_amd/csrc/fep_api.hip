@@ -307,24 +307,32 @@ static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) 
 
 // The material models, one row each, indexed by FEP_MODEL_*: the tag a model puts into its kernels' names and its kernel of each
 // point-kernel family.  point_*_kernel<NP, NQ> has no Drucker-Prager row, that step being the fused element route: model - 1.
-constexpr int kModels = 3;
-static const char* const kModelTag[kModels] = {"", "vm_", "mc_"};
-static constexpr decltype(&return_map_kernel) kReturnMapKernel[kModels] = {return_map_kernel, return_map_vm_kernel, return_map_mc_kernel};
-static constexpr decltype(&p1_point_kernel) kP1PointKernel[kModels] = {p1_point_kernel, p1_point_vm_kernel, p1_point_mc_kernel};
+constexpr int kModels = 4;
+static const char* const kModelTag[kModels] = {"", "vm_", "mc_", "vmps_"};
+static constexpr decltype(&return_map_kernel) kReturnMapKernel[kModels] = {return_map_kernel, return_map_vm_kernel, return_map_mc_kernel,
+                                                                                   return_map_vmps_kernel};
+static constexpr decltype(&p1_point_kernel) kP1PointKernel[kModels] = {p1_point_kernel, p1_point_vm_kernel, p1_point_mc_kernel,
+                                                                               p1_point_vmps_kernel};
 template <int NP, int NQ>
-static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>};
-static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == kModels - 1, "table order");
+static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>,
+                                                                                    point_vmps_kernel<NP, NQ>};
+static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == 2 && FEP_MODEL_VMPS == kModels - 1, "table order");
 // The same families with an initial-strain field (fep_*_field_*): every model has a row in each, Drucker-Prager too, so these
 // are indexed by the model itself.
-static constexpr decltype(&return_map_field_kernel<FEP_MODEL_DP>) kReturnMapFieldKernel[kModels] = {
+// (The mesh-free pair fep_return_map_field_* keeps its three models: FEP_MODEL_VMPS is refused there, include/fep.h.)
+constexpr int kFieldFreeModels = 3;
+static constexpr decltype(&return_map_field_kernel<FEP_MODEL_DP>) kReturnMapFieldKernel[kFieldFreeModels] = {
     return_map_field_kernel<FEP_MODEL_DP>, return_map_field_kernel<FEP_MODEL_VM>, return_map_field_kernel<FEP_MODEL_MC>};
 static constexpr decltype(&p1_point_field_kernel<FEP_MODEL_DP>) kP1PointFieldKernel[kModels] = {
-    p1_point_field_kernel<FEP_MODEL_DP>, p1_point_field_kernel<FEP_MODEL_VM>, p1_point_field_kernel<FEP_MODEL_MC>};
+    p1_point_field_kernel<FEP_MODEL_DP>, p1_point_field_kernel<FEP_MODEL_VM>, p1_point_field_kernel<FEP_MODEL_MC>,
+    p1_point_field_kernel<FEP_MODEL_VMPS>};
 template <int NP, int NQ>
 static constexpr decltype(&point_field_kernel<FEP_MODEL_DP, NP, NQ>) kPointFieldKernel[kModels] = {
-    point_field_kernel<FEP_MODEL_DP, NP, NQ>, point_field_kernel<FEP_MODEL_VM, NP, NQ>, point_field_kernel<FEP_MODEL_MC, NP, NQ>};
+    point_field_kernel<FEP_MODEL_DP, NP, NQ>, point_field_kernel<FEP_MODEL_VM, NP, NQ>, point_field_kernel<FEP_MODEL_MC, NP, NQ>,
+    point_field_kernel<FEP_MODEL_VMPS, NP, NQ>};
 
-// (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises or sin_phi, c of Mohr-Coulomb)
+// (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises in plane strain or plane stress,
+// or sin_phi, c of Mohr-Coulomb)
 static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n_int,
                                const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                const double* e0_h, double* ep_prev_d,
@@ -382,12 +390,21 @@ extern "C" int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
                                shear_d, bulk_d, sin_phi_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
 }
 
+extern "C" int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_int,
+                                       const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                       const double* e0_h, double* ep_prev_d,
+                                       const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                                       int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    return return_map_dev_impl(FEP_MODEL_VMPS, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
+}
+
 extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, int64_t n_int,
                                         const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                         const double* e0_h, const double* e0_field_d, double e0_scale, double* ep_prev_d,
                                         const double* shear_d, const double* bulk_d, const double* m3_d, const double* m4_d,
                                         int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
-    if (model < 0 || model >= kModels || !e0_field_d) return FEP_EINVAL;
+    if (model < 0 || model >= kFieldFreeModels || !e0_field_d) return FEP_EINVAL;
     return return_map_dev_impl(model, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
                                shear_d, bulk_d, m3_d, m4_d, accept, s_d, ds_d, ind_p_d, counts_d, e0_field_d, e0_scale);
 }
@@ -503,12 +520,21 @@ extern "C" int fep_return_map_mc_host(int device_id, int64_t n_int,
                                    bulk_h, sin_phi_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
 }
 
+extern "C" int fep_return_map_vmps_host(int device_id, int64_t n_int,
+                                        const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                                        const double* e0_h, double* ep_prev_h,
+                                        const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                                        int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+    FEP_GUARD(return_map_host_impl(FEP_MODEL_VMPS, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
+}
+
 extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int,
                                          const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
                                          const double* e0_h, const double* e0_field_h, double e0_scale, double* ep_prev_h,
                                          const double* shear_h, const double* bulk_h, const double* m3_h, const double* m4_h,
                                          int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
-    if (model < 0 || model >= kModels || !e0_field_h) return FEP_EINVAL;
+    if (model < 0 || model >= kFieldFreeModels || !e0_field_h) return FEP_EINVAL;
     FEP_GUARD(return_map_host_impl(model, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
                                    bulk_h, m3_h, m4_h, accept, s_h, ds_h, ind_p_h, counts_h, e0_field_h, e0_scale))
 }
@@ -1380,7 +1406,7 @@ static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const d
     return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
 }
 
-// Von Mises and Mohr-Coulomb contexts (FEP_MODEL_VM, _MC): stage A is the model's point kernel (geometry, strain, return map; s / ds to the
+// Von Mises (plane strain and plane stress) and Mohr-Coulomb contexts (FEP_MODEL_VM, _VMPS, _MC): stage A is the model's point kernel (geometry, strain, return map; s / ds to the
 // caller's arrays or the context's scratch), stage B exactly what fep_assemble_dev launches for the route (the element routes'
 // element_kernel in its assembly-only form, then the route's assembly kernel), stage C the COO form's force gather.
 // `field_d` (fep_step_field_*): the same three stages with the *_field_kernel of the context's model, Drucker-Prager included.

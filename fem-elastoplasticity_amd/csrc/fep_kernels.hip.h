@@ -167,6 +167,106 @@ __device__ __forceinline__ int vm_return_map(const double e[3], const double z[4
 }
 
 // ---------------------------------------------------------------------------------------
+// Per-point von Mises return map in PLANE STRESS with linear kinematic hardening (the fourth material model,
+// FEP_MODEL_VMPS; no counterpart in the reference; include/fep.h, fep_return_map_vmps_*, has the law).  Arguments as
+// vm_return_map: a >= 0, Y = sqrt(2/3)*sigma_y > 0.  s[3] = 0; z[3] and p[3] enter only through the propagation of a
+// non-finite value.  Returns 0 elastic, 1 plastic.
+//
+// No closed-form radial return exists: the multiplier g is the root of
+//     phi(g) = hs^2 / (6 (1 + cs g)^2) + (hd^2 / 2 + 2 h12^2) / (1 + cd g)^2 - Y^2,
+// convex and decreasing on g >= 0, so Newton from a start left of the root is monotone.  The loop is the only statement that
+// diverges between the lanes of a wave: elastic lanes do not enter it and carry g = 0 and both denominators 1 through the
+// statements behind it, which are common to all lanes; their stress and tangent are chosen by selects.  It stops on the change of
+// 1 + cd g (a relative test on g never fires next to the yield surface, where the rounding of phi exceeds tol * g), and at
+// kVmpsMaxIter at the latest; its condition is false for a NaN, so a non-finite point leaves at the first test.
+// ---------------------------------------------------------------------------------------
+constexpr int kVmpsMaxIter = 16;          // the fixtures need at most 7, the mesh cases of the tests 8
+constexpr double kVmpsTol = 0x1p-51;      // 2 eps: on |d(1 + cd g)| / (1 + cd g)
+
+__device__ __forceinline__ int vmps_return_map(const double e[3], const double z[4], double p[4],
+                                               double G, double K, double a, double Y, bool accept,
+                                               double s[4], double d[6]) {
+    // No contraction: which products the compiler fuses into sums differs between the instantiations of this function (a uniform
+    // z in scalar registers, a z per lane with a field), a fused and an unfused f differ in the last bit, and with them the
+    // iterates and in the end the iteration count: the kernels of the model would no longer agree bit for bit
+#pragma clang fp contract(off)
+    const double ee0 = (e[0] + z[0]) - p[0];
+    const double ee1 = (e[1] + z[1]) - p[1];
+    const double ee2 = (e[2] + z[2]) - p[2];
+    const double Et3 = (0.0 + z[3]) - p[3];
+    const double G2 = 2.0 * G;
+    const double lam = K - G2 / 3.0;
+    const double lb = G2 * lam / (lam + G2);
+    const double c00 = lb + G2;
+    // trial stress C ee, C = [[lb + 2G, lb, 0], [lb, lb + 2G, 0], [0, 0, G]]
+    const double st0 = c00 * ee0 + lb * ee1, st1 = lb * ee0 + c00 * ee1, st2 = G * ee2;
+    // relative trial stress: minus the plane-stress image of the deviatoric back stress a*p
+    const double ab0 = a * (2.0 * p[0] + p[1]), ab1 = a * (2.0 * p[1] + p[0]), ab2 = a * (0.5 * p[2]);
+    const double h0 = st0 - ab0, h1 = st1 - ab1, h12 = st2 - ab2;
+    const double hs = h0 + h1, hd = h0 - h1;
+    const double cs = (2.0 * lb + G2) / 3.0 + a, cd = G2 + a;
+    const double qs = hs * hs / 6.0, qd = 0.5 * (hd * hd) + 2.0 * (h12 * h12);
+    const double Y2 = Y * Y;
+    // -0.0 for a finite trial strain (x + -0.0 == x: no finite result changes) and NaN when one of its FOUR components is a NaN
+    // or an infinity: the point is then elastic with a NaN in s[3].  The in-plane components alone would reach n2 too, but an
+    // infinity would leave the elastic point an infinite stress without a NaN, and component 3 enters the law nowhere else
+    const double poison = -fabs(0.0 * (((fabs(ee0) + fabs(ee1)) + fabs(ee2)) + fabs(Et3)));
+    const double n2 = (qs + qd) + poison;               // eta^T P eta = |dev xi|^2
+    const int branch = (n2 - Y2 > 0.0) ? 1 : 0;         // phi(0) > 0; a NaN is elastic
+    // Newton on phi.  Start left of the root: every mode shrinks by at most 1 + max(cs, cd) g
+    double g = branch ? (sqrt(n2) / Y - 1.0) / fmax(cs, cd) : 0.0;
+    double us = 1.0 + cs * g, ud = 1.0 + cd * g;
+    for (int it = 0; branch && it < kVmpsMaxIter; ++it) {
+        const double rs = 1.0 / us, rd = 1.0 / ud;
+        const double fs = qs * (rs * rs), fd = qd * (rd * rd);
+        const double f = (fs + fd) - Y2;
+        const double df = 2.0 * (cs * (fs * rs) + cd * (fd * rd));   // -phi'
+        const double dg = f / df;
+        g += dg;
+        us = 1.0 + cs * g; ud = 1.0 + cd * g;
+        if (!(fabs(dg) * cd > kVmpsTol * ud)) break;
+    }
+    // relaxed relative stress and the plastic increment g P eta' (engineering shear); elastic lanes: g = 0, us = ud = 1
+    const double hs1 = hs / us, hd1 = hd / ud, h121 = h12 / ud;
+    const double n0 = 0.5 * (hs1 + hd1), n1 = 0.5 * (hs1 - hd1);
+    const double I3 = 1.0 / 3.0;
+    const double Pn0 = (2.0 * n0 - n1) * I3, Pn1 = (2.0 * n1 - n0) * I3, Pn2 = 2.0 * h121;      // P eta'
+    const double dp0 = g * Pn0, dp1 = g * Pn1, dp2 = g * Pn2;
+    // The new stress st - C dp, formed without the cancellation of that difference (st grows with the overshoot, s does not): M P = I
+    // for the back stress's image M = [[2, 1, 0], [1, 2, 0], [0, 0, 1/2]], so the image of a (p + dp) is ab + a g eta' and
+    // s = eta' + a M (p + dp) = (1 + a g) eta' + ab.  Elastic lanes keep the trial stress itself
+    const double ag = 1.0 + a * g;
+    s[0] = branch ? ag * n0 + ab0 : st0;
+    s[1] = branch ? ag * n1 + ab1 : st1;
+    s[2] = branch ? ag * h121 + ab2 : st2;
+    s[3] = 0.0 + poison;
+    // consistent tangent: Xi = (C^-1 + th P)^-1 is diagonal in the (sum, difference, shear) modes; n = Xi P eta';
+    // dsig/deps = Xi - n n^T / (eta'^T P n + a Y^2 (1 + a g)).  Elastic lanes select C itself (a NaN strain included)
+    const double th = g / ag;
+    const double xs = 1.0 / (1.0 / (2.0 * lb + G2) + th * I3);
+    const double xd = 1.0 / (1.0 / G2 + th);
+    const double xh = 1.0 / (1.0 / G + 2.0 * th);
+    // P eta' in modes: sum hs'/3, difference hd', shear 2 h12'
+    const double ns = xs * (hs1 * I3), nd = xd * hd1, nh = xh * Pn2;
+    const double v0 = 0.5 * (ns + nd), v1 = 0.5 * (ns - nd), v2 = nh;
+    const double w = 1.0 / ((Pn0 * v0 + Pn1 * v1 + Pn2 * v2) + a * Y2 * ag);
+    const double xp = 0.5 * (xs + xd), xm = 0.5 * (xs - xd);
+    d[0] = branch ? xp - w * (v0 * v0) : c00;
+    d[1] = branch ? xm - w * (v0 * v1) : lb;
+    d[2] = branch ? 0.0 - w * (v0 * v2) : 0.0;
+    d[3] = branch ? xp - w * (v1 * v1) : c00;
+    d[4] = branch ? 0.0 - w * (v1 * v2) : 0.0;
+    d[5] = branch ? xh - w * (v2 * v2) : G;
+    if (accept && branch) {
+        p[0] += dp0;
+        p[1] += dp1;
+        p[2] += dp2;
+        p[3] -= dp0 + dp1;
+    }
+    return branch;
+}
+
+// ---------------------------------------------------------------------------------------
 // Per-point Mohr-Coulomb return map (the third material model, FEP_MODEL_MC; no counterpart in the reference):
 // associative, perfectly plastic, the closest-point projection in principal stresses with its spectral tangent
 // (include/fep.h, fep_return_map_mc_*, has the law).  sp = sin(phi) in (0, 1), c > 0; everything else as dp_return_map.
@@ -287,8 +387,9 @@ template <int MODEL>
 __device__ __forceinline__ int model_return_map(const double e[3], const double z[4], double p[4],
                                                 double G, double K, double m3, double m4, bool accept,
                                                 double s[4], double d[6]) {
-    static_assert(MODEL == FEP_MODEL_DP || MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC, "model");
-    if constexpr (MODEL == FEP_MODEL_MC) return mc_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+    static_assert(MODEL == FEP_MODEL_DP || MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC || MODEL == FEP_MODEL_VMPS, "model");
+    if constexpr (MODEL == FEP_MODEL_VMPS) return vmps_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+    else if constexpr (MODEL == FEP_MODEL_MC) return mc_return_map(e, z, p, G, K, m3, m4, accept, s, d);
     else if constexpr (MODEL == FEP_MODEL_VM) return vm_return_map(e, z, p, G, K, m3, m4, accept, s, d);
     else return dp_return_map(e, z, p, G, K, m3, m4, accept, s, d);
 }
@@ -463,6 +564,9 @@ __global__ void __launch_bounds__(kBlock) return_map_vm_kernel(FEP_RETURN_MAP_AR
 }
 __global__ void __launch_bounds__(kBlock) return_map_mc_kernel(FEP_RETURN_MAP_ARGS) {
     return_map_body<FEP_MODEL_MC>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
+__global__ void __launch_bounds__(kBlock) return_map_vmps_kernel(FEP_RETURN_MAP_ARGS) {
+    return_map_body<FEP_MODEL_VMPS>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
 }
 template <int MODEL>
 __global__ void __launch_bounds__(kBlock)
@@ -1443,6 +1547,9 @@ __global__ void __launch_bounds__(kBlock) p1_point_vm_kernel(FEP_P1_POINT_ARGS) 
 __global__ void __launch_bounds__(kBlock) p1_point_mc_kernel(FEP_P1_POINT_ARGS) {
     p1_point_body<FEP_MODEL_MC>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
 }
+__global__ void __launch_bounds__(kBlock) p1_point_vmps_kernel(FEP_P1_POINT_ARGS) {
+    p1_point_body<FEP_MODEL_VMPS>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
+}
 template <int MODEL>
 __global__ void __launch_bounds__(kBlock)
 p1_point_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, double scale) {
@@ -2187,6 +2294,11 @@ template <int NP, int NQ>
 __global__ void __launch_bounds__(kBlock) point_mc_kernel(FEP_POINT_ARGS) {
     point_body<FEP_MODEL_MC, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
                                      indp, blk_counts);
+}
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock) point_vmps_kernel(FEP_POINT_ARGS) {
+    point_body<FEP_MODEL_VMPS, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                       indp, blk_counts);
 }
 // The same with an initial-strain field, for every model: the only Drucker-Prager instantiation of point_body (a step with a field
 // runs staged on every route).

@@ -210,19 +210,31 @@ def construct_constitutive_problem_mc(e, ep_prev, shear, bulk, sin_phi, c, apply
     return {k: r[k] for k in ('s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex')}
 
 
-MODELS = {'dp': 0, 'vm': 1, 'mc': 2}                       # FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC
+def construct_constitutive_problem_vmps(e, ep_prev, shear, bulk, a, Y, apply_plastic_strain=False, e0=None, device=None):
+    """The fourth material model, no counterpart in the reference: von Mises plasticity with linear kinematic hardening in
+    plane stress (include/fep.h, fep_return_map_vmps_host): the law of construct_constitutive_problem_vm with s33 = 0 and
+    the out-of-plane strain free, the multiplier by a bounded Newton iteration per point.  Arguments and the returned
+    {'s' (row 3 = 0), 'ds', 'ind_p', 'ep', 'n_plast'} as construct_constitutive_problem_vm; row 3 of `e0` and `ep_prev`
+    does not enter (a non-finite value in it makes the point elastic with a NaN in 's'), and on accept row 3 of 'ep' takes
+    minus the sum of the in-plane normal increments."""
+    r = _return_map(e, e0, ep_prev, shear, bulk, a, Y, apply_plastic_strain, tsx=False, device=device,
+                    entry='fep_return_map_vmps_host')
+    return {'s': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'], 'ep': r['ep'], 'n_plast': r['n_smooth']}
+
+
+MODELS = {'dp': 0, 'vm': 1, 'mc': 2, 'vmps': 3}            # FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC, FEP_MODEL_VMPS
 
 
 def construct_constitutive_problem_field(model, e, e0_field, ep_prev, shear, bulk, m3, m4, apply_plastic_strain=False,
                                          e0=None, e0_scale=1.0, device=None):
-    """The return map of `model` ('dp', 'vm' or 'mc') with an initial strain per point, no counterpart in the reference
+    """The return map of `model` ('dp', 'vm' or 'mc'; 'vmps' takes a field in `MeshContext.step` only) with an initial strain per point, no counterpart in the reference
     (include/fep.h, fep_return_map_field_host): point k runs on `e0 + e0_scale * e0_field[:, k]`, `e0_field` (4, n_int) with
     rows 11, 22, 12 (engineering shear), 33, `e0` an optional uniform (4,1) part.  `m3`, `m4` are the model's third and
     fourth parameter arrays (eta, c / a, Y / sin_phi, c); the other arguments as construct_constitutive_problem.  Returns
     {'s', 'ds', 'ind_p', 'ep', 'n_smooth', 'n_apex'} with the counts as the model's own wrapper reports them (von Mises:
     its plastic points in 'n_smooth'); with `apply_plastic_strain`, `ep_prev` is updated in place and returned as 'ep'."""
-    if model not in MODELS:
-        raise ValueError(f"model must be one of {sorted(MODELS)}")
+    if model not in ('dp', 'vm', 'mc'):
+        raise ValueError("model must be one of ['dp', 'mc', 'vm']")
     if e0_field is None:
         raise ValueError('e0_field is required (the plain wrappers run without a field)')
     r = _return_map(e, e0, ep_prev, shear, bulk, m3, m4, apply_plastic_strain, tsx=False, device=device,
@@ -365,8 +377,9 @@ class MeshContext:
     def set_model(self, model):
         """'dp' (Drucker-Prager, the default), 'vm' (von Mises with linear kinematic hardening: `set_materials` then takes
         (shear, bulk, a, Y), the results carry the plastic count in 'n_smooth' and 'n_apex' is 0) or 'mc' (Mohr-Coulomb:
-        `set_materials` takes (shear, bulk, sin_phi, c), 'n_smooth' counts face and edges, 'n_apex' the apex).  Before or
-        after `set_materials`."""
+        `set_materials` takes (shear, bulk, sin_phi, c), 'n_smooth' counts face and edges, 'n_apex' the apex) or 'vmps' (von
+        Mises in plane stress: everything as 'vm', the stress has s33 = 0, and the context's K at U = 0 is the elastic
+        plane-stress stiffness).  Before or after `set_materials`."""
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}")
         _lib.check(_lib.lib().fep_ctx_set_model(self._h, MODELS[model]), 'fep_ctx_set_model')

@@ -23,13 +23,15 @@ def cycle_factors(steps_per_quarter):
 
 def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), steps_per_quarter=4, young=206900, poisson=0.29,
                         sigma_y=450, hardening=10000, linear_solver='amg', f_ext=None, zetas=None, context_factory=None,
-                        device=None, pcg_rtol=1e-11, log=None):
+                        device=None, pcg_rtol=1e-11, log=None, plane_stress=False):
     """A load cycle on the cut-out square (mesh.assemble_mesh_el: P1, Q1, Q2).  The DOFs outside the mesh's 'Q' are held
     at zero; the external load is `f_ext` (2, n_n) when given, else the traction `peak_traction` on the top side
     (load_traction), times the load factors `zetas` (default: cycle_factors(steps_per_quarter)).  Materials: shear and
     bulk from `young` / `poisson`, yield radius Y = sqrt(2/3) * `sigma_y`, and `hardening` is the modulus a of the back
     stress a * p.  Per load factor a Newton iteration from the last accepted state (newton._load_history_loop: at most 25
     iterates, converged below 1e-10, no sub-stepping), then the accepting call that updates the plastic strain.
+    `plane_stress=True` runs the plate in plane stress (the 'vmps' model: s33 = 0, the thickness strain free) instead of
+    the default plane strain ('vm': a thick prism).
 
     Returns a dict: 'zeta' (the accepted factors), 'U' (list of (2, n_n)), 'n_plast', 'newton_its', 'pcg_iters', 'Ep',
     'f_ext' (2, n_n), 'mesh', 'failed_at' (index of the step that did not converge, or None) and 'work' =
@@ -41,7 +43,7 @@ def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), step
     elem = mesh['elements'] - 1
     coord, Q = mesh['coordinates'], mesh['Q']
     ctx = _context_maker(context_factory, device)(elem, coord, *element_tables(t))
-    ctx.set_model('vm')
+    ctx.set_model('vmps' if plane_stress else 'vm')
     ctx.set_materials(young / (2 * (1 + poisson)), young / (3 * (1 - 2 * poisson)), float(hardening),
                       np.sqrt(2 / 3) * sigma_y)
     if f_ext is None:

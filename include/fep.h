@@ -29,7 +29,7 @@
  *   - calls on one context are not re-entrant; one context per (host thread, GPU).
  *
  * Stream contract of the *_host entry points that move the caller's arrays through the staging engine
- * (fep_return_map_host / _vm_host / _mc_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
+ * (fep_return_map_host / _vm_host / _mc_host / _vmps_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
  * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host; not the fep_mesh_* and fep_load_traction_host forms):
  *   - each call runs its copies and its kernels on ONE non-blocking stream per device that belongs to the library; that stream
  *     is ordered against nothing else: not the default stream, not a stream the caller passed to a *_dev call;
@@ -79,6 +79,7 @@ extern "C" {
 #define FEP_MODEL_DP 0        /* perfectly plastic Drucker-Prager (the reference's law; the default) */
 #define FEP_MODEL_VM 1        /* von Mises with linear kinematic hardening (no reference counterpart) */
 #define FEP_MODEL_MC 2        /* associative, perfectly plastic Mohr-Coulomb (no reference counterpart) */
+#define FEP_MODEL_VMPS 3      /* von Mises with linear kinematic hardening in plane stress (no reference counterpart) */
 
 typedef struct fep_ctx fep_ctx;
 
@@ -122,7 +123,7 @@ int fep_host_trim(void);
  *
  * Non-finite inputs (all fep_return_map_* and, through them, fep_step_* and fep_assemble_*; tests/test_nonfinite_gpu.py).
  * A NaN or an infinity in a DATA array is legal input; indices, tables and sizes must always be valid.
- *   1. It is never hidden.  Von Mises and Mohr-Coulomb: a point whose trial strain (e + e0) - ep_prev has a NaN component
+ *   1. It is never hidden.  Von Mises (plane strain and plane stress) and Mohr-Coulomb: a point whose trial strain (e + e0) - ep_prev has a NaN component
  *      comes back with ind_p = 0, the elastic tangent, at least one NaN in s, its ep_prev untouched, and is counted nowhere
  *      (every branch test is written so that a NaN fails it: crit > 0, !(f > 0)).  Drucker-Prager does what the reference
  *      does: its products with the zeros of vol carry a non-finite shear strain into the trace, so a NaN in any strain
@@ -232,8 +233,51 @@ int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
                           int accept,
                           double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
 
+/* ---- fourth material model: von Mises with linear kinematic hardening in PLANE STRESS, mesh-free ------
+ * No reference counterpart.  The law of fep_return_map_vm_* with the out-of-plane strain left free (s33 = 0) instead of
+ * prescribed: for a traceless ep_prev, fep_return_map_vm_* at the e0[3] that makes its s[3] vanish returns the same
+ * in-plane stress and the same new ep_prev.  Layout, strides, e0_h, ep_prev, outputs, the parameters a >= 0 and
+ * Y = sqrt(2/3)*sigma_y > 0 and the scratch rule of counts_d exactly as fep_return_map_vm_*.  Per point, with p = ep_prev
+ * (engineering shear in p[2]) and z = e0:
+ *     ee_i = (e_i + z_i) - p_i, i = 0..2     lam = K - 2G/3,  lb = 2G lam/(lam + 2G)
+ *     C = [[lb+2G, lb, 0], [lb, lb+2G, 0], [0, 0, G]]      st = C ee  (trial stress; C is the elastic tangent)
+ *     ab = a (2 p0 + p1, 2 p1 + p0, p2/2)                  (plane-stress image of the deviatoric back stress a p)
+ *     eta = st - ab,   hs = eta0 + eta1,  hd = eta0 - eta1,  h12 = eta2
+ *     P = (1/3) [[2,-1,0],[-1,2,0],[0,0,6]]:   eta^T P eta = hs^2/6 + hd^2/2 + 2 h12^2  (= |dev xi|^2)
+ *     cs = (2 lb + 2G)/3 + a,   cd = 2G + a
+ *     phi(g) = hs^2/(6 (1 + cs g)^2) + (hd^2/2 + 2 h12^2)/(1 + cd g)^2 - Y^2
+ *   not phi(0) > 0 (phi(0) <= 0 or NaN): elastic, g = 0, s = (st, 0), ds = C.
+ *   phi(0) > 0: g is the root of phi (convex and decreasing on g >= 0), by Newton's iteration from
+ *     g0 = (sqrt(eta^T P eta)/Y - 1)/max(cs, cd), which lies left of the root, so the iterates increase monotonically;
+ *     stopped when |dg| cd <= 2^-51 (1 + cd g) and after 16 iterations at the latest (8 is the most any tested point takes).
+ *     hs' = hs/(1 + cs g),  hd' = hd/(1 + cd g),  eta' = ((hs' + hd')/2, (hs' - hd')/2, h12/(1 + cd g))
+ *     dp = g P eta'  (engineering shear in row 2),    s = (st - C dp, 0), formed as ((1 + a g) eta' + ab, 0): the same
+ *          stress (M P = I for ab = a M p, so the image of a (p + dp) is ab + a g eta'), without the cancellation of st - C dp,
+ *          which loses the digits of the overshoot
+ *     th = g/(1 + a g),  Xi = (C^-1 + th P)^-1: diagonal in the (sum, difference, shear) modes with the entries
+ *          1/(1/(2 lb + 2G) + th/3),  1/(1/(2G) + th),  1/(1/G + 2 th)
+ *     n = Xi P eta',   ds = Xi - n n^T/(eta'^T P n + a Y^2 (1 + a g))              (rows / columns 11, 22, 12; symmetric)
+ *     accept:  p += (dp0, dp1, dp2, -(dp0 + dp1))
+ * ind_p = (phi(0) > 0); counts = {number of plastic points, 0}.  s[3] is +0.0.  e0[3] and ep_prev[3] enter the law only
+ * through the propagation of non-finite values: eta^T P eta and s[3] carry the term -|0 * (|ee0| + |ee1| + |ee2| + |z3 - p3|)|,
+ * which is -0.0 and changes no bit of a finite result, and NaN when one of the four components of the trial strain is a NaN
+ * or an infinity, so that rule 1 above holds for all four components, and an infinite strain leaves a NaN in s too. */
+int fep_return_map_vmps_host(int device_id, int64_t n_int,
+                             const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                             const double* e0_h, double* ep_prev_h,
+                             const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                             int accept,
+                             double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h);
+int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_int,
+                            const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                            const double* e0_h, double* ep_prev_d,
+                            const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                            int accept,
+                            double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
+
 /* ---- initial strain per point, mesh-free: one pair for every model ----------------------
- * No reference counterpart (its demo holds one s0 for the whole mesh, TSX:1675-1681).  `model` = FEP_MODEL_DP, _VM or _MC;
+ * No reference counterpart (its demo holds one s0 for the whole mesh, TSX:1675-1681).  `model` = FEP_MODEL_DP, _VM or _MC (the
+ * plane-stress model is not offered mesh-free with a field: FEP_EINVAL; fep_step_field_* of a FEP_MODEL_VMPS context take one);
  * every other argument as in fep_return_map_* of that model (the third and fourth parameter arrays are the model's), plus
  *   e0_field   (4, n_int) C-order like ep_prev, rows 11, 22, 12 (engineering shear), 33; never modified, borrowed for the call
  *   e0_scale   one factor for the whole field
@@ -299,10 +343,11 @@ int fep_ctx_pattern_host(const fep_ctx* ctx, int32_t* indptr_h /* n_dof+1 */, in
  * read the arrays; results are bitwise the same either way. */
 int fep_ctx_set_materials_host(fep_ctx* ctx, const double* shear_h, const double* bulk_h,
                                const double* eta_h, const double* c_h);
-/* The material model of the context's steps: FEP_MODEL_DP (the default), FEP_MODEL_VM or FEP_MODEL_MC; may be called
+/* The material model of the context's steps: FEP_MODEL_DP (the default), FEP_MODEL_VM, FEP_MODEL_MC or FEP_MODEL_VMPS; may be called
  * before or after fep_ctx_set_materials_host.  On a von Mises context the third and fourth arrays of
  * fep_ctx_set_materials_host are a and Y (fep_return_map_vm_*), on a Mohr-Coulomb context sin_phi and c
- * (fep_return_map_mc_*; counts = {smooth face + both edges, apex}).  What follows holds for both alike.  The
+ * (fep_return_map_mc_*; counts = {smooth face + both edges, apex}), on a plane-stress von Mises context a and Y again
+ * (fep_return_map_vmps_*; the elastic plane-stress stiffness is such a context's K at U = 0).  What follows holds for all alike.  The
  * constant-parameter shortcut applies as for Drucker-Prager, and fep_step_* keep their
  * signature and every output: they run the model's point kernel (geometry from the node coordinates, strain, return map;
  * s / ds to the caller's arrays or a scratch of the context) and then what fep_assemble_dev launches for the context.
