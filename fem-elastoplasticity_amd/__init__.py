@@ -29,7 +29,7 @@ from .newton import solve_strip_footing, solve_tsx_tunnel, transform
 from .solver import KrylovSolver, build_amg_hierarchy
 from .dist_newton import DistributedPCG, GatheredSolver, solve_strip_footing_sharded, solve_tsx_tunnel_sharded
 from .midpoints import (DeviceMesh, Ellipse, area_stats, area_stats_dev, create_midpoints, create_midpoints_P2, create_midpoints_P4,
-                        refine_uniform)
+                        mark_plastic, refine_marked, refine_uniform)
 from .meshio import dump_free_dof_csv, load_tsx_mesh, prepare_tsx_mesh
 from . import plasticity2d_dp, tsx_tunnel, elasticity2d, vonmises
 
@@ -38,7 +38,7 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'construct_constitutive_problem_tsx', 'get_elastic_stiffness_matrix', 'get_elastic_stiffness_matrix_el',
            'assemble_tangent', 'default_device', 'FepError', 'lib', 'lib_path', 'build',
            'solve_strip_footing', 'solve_tsx_tunnel', 'transform', 'KrylovSolver', 'DistributedPCG', 'solve_strip_footing_sharded', 'GatheredSolver', 'solve_tsx_tunnel_sharded', 'build_amg_hierarchy', 'create_midpoints', 'create_midpoints_P2',
-           'create_midpoints_P4', 'refine_uniform', 'DeviceMesh', 'Ellipse', 'area_stats', 'area_stats_dev', 'load_tsx_mesh', 'prepare_tsx_mesh', 'dump_free_dof_csv',
+           'create_midpoints_P4', 'refine_uniform', 'refine_marked', 'mark_plastic', 'DeviceMesh', 'Ellipse', 'area_stats', 'area_stats_dev', 'load_tsx_mesh', 'prepare_tsx_mesh', 'dump_free_dof_csv',
            'get_quadrature_surface', 'get_local_basis_surface', 'surface_tables', 'assemble_mesh_el', 'get_vector_volume',
            'get_vector_traction', 'load_traction', 'solve_elasticity2d',
            'construct_constitutive_problem_vm', 'construct_constitutive_problem_mc', 'construct_constitutive_problem_vmps',

@@ -103,6 +103,9 @@ PROTOTYPES = {
     'fep_mesh_enrich_host': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     'fep_mesh_refine_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_mesh_refine_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_mark': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_i64_p]),
+    'fep_mesh_refine_marked_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_refine_marked_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_mesh_set_curves': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'fep_mesh_surf_curve_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'fep_mesh_surf_curve_host': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

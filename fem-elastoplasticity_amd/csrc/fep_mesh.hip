@@ -433,6 +433,148 @@ __global__ void __launch_bounds__(kBlock) refine_kernel(MeshView M, CurveSet S, 
     r2[0] = m31;  r2[1] = m23;  r2[2] = v[2]; r2[3] = m31;
 }
 
+// ---- refinement of marked elements: conforming longest-edge bisection (fep.h, fep_mesh_mark) -------------------------------
+// bits[i]: bit k = half-edge k of element i says its edge is marked.  An edge IS marked iff either half-edge says so.
+// ref[i]: the reference edge, the longest one (squared chord in the element's walking direction, slots compared 0, 1, 2
+// with a strict >).  The closure — an element with any marked edge marks its reference edge — is the least fixpoint of a
+// monotone rule on the bits, so it does not depend on the order in which lanes, workgroups or sweeps evaluate it.
+__device__ __forceinline__ int edge_state(const int32_t* __restrict__ nbr, const uint8_t* bits, int64_t n_e, int64_t i, int k, int own) {
+    const int32_t nb = nbr[(int64_t)k * n_e + i];
+    return ((own >> k) & 1) | (nb < 0 ? 0 : ((bits[nb / 3] >> (nb % 3)) & 1));
+}
+
+__global__ void __launch_bounds__(kBlock) mark_init_kernel(MeshView M, const uint8_t* __restrict__ marked, uint8_t* __restrict__ bits,
+                                                           uint8_t* __restrict__ ref) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    double x[3], y[3], len[3];
+    for (int k = 0; k < 3; ++k) {
+        const int32_t v = M.elem[(int64_t)k * M.n_e + i];
+        x[k] = M.coord[v];
+        y[k] = M.coord[M.n_n + v];
+    }
+    for (int k = 0; k < 3; ++k) {
+        const double dx = x[(k + 1) % 3] - x[k], dy = y[(k + 1) % 3] - y[k];
+        len[k] = dx * dx + dy * dy;
+    }
+    int r = 0;
+    if (len[1] > len[r]) r = 1;
+    if (len[2] > len[r]) r = 2;
+    ref[i] = (uint8_t)r;
+    bits[i] = marked[i] ? 7 : 0;
+}
+
+// One sweep.  A workgroup iterates over its own kBlock bytes in LDS until none of them changes — a chain of reference edges
+// inside the workgroup closes in one launch — with the bits of neighbours in other workgroups read once, before the loop.
+// Those may be older than what their workgroup writes in this launch; bits are only ever added, so an old value delays a
+// mark and never loses one, and the workgroup that added it raises `changed`, which brings another launch.  A launch that
+// leaves `changed` at zero has evaluated the rule of every element on the final bytes: the fixpoint.  A lane writes its
+// own byte only.
+__global__ void __launch_bounds__(kBlock) mark_sweep_kernel(int64_t n_e, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ ref,
+                                                            uint8_t* bits, int32_t* __restrict__ changed) {
+    __shared__ int l_bits[kBlock];
+    const int64_t first = (int64_t)blockIdx.x * kBlock, i = first + threadIdx.x;
+    const bool active = i < n_e;
+    int b = 0, r = 0, outside = 0, at[3] = {-1, -1, -1}, shift[3] = {0, 0, 0};
+    if (active) {
+        b = bits[i];
+        r = ref[i];
+        for (int k = 0; k < 3; ++k) {
+            const int32_t nb = nbr[(int64_t)k * n_e + i];
+            if (nb < 0) continue;
+            const int64_t j = nb / 3;
+            if (j >= first && j < first + kBlock) {
+                at[k] = (int)(j - first);
+                shift[k] = nb % 3;
+            } else {
+                outside |= (bits[j] >> (nb % 3)) & 1;
+            }
+        }
+    }
+    const int b_in = b;
+    while (true) {
+        l_bits[threadIdx.x] = b;
+        __syncthreads();
+        int any = b | outside;
+        for (int k = 0; k < 3; ++k)
+            if (at[k] >= 0) any |= (l_bits[at[k]] >> shift[k]) & 1;
+        const int b_new = any ? (b | (1 << r)) : b;
+        const int moved = active && b_new != b;
+        if (active) b = b_new;
+        if (!__syncthreads_or(moved)) break;               // also the barrier between these reads and the next writes
+    }
+    if (b != b_in) bits[i] = (uint8_t)b;
+    if (__syncthreads_or(b != b_in) && threadIdx.x == 0) atomicOr(changed, 1);
+}
+
+// flag of every edge at its index (written by the owner), number of children per element, number of elements with a marked edge
+__global__ void __launch_bounds__(kBlock) mark_count_kernel(MeshView M, const uint8_t* __restrict__ bits, int32_t* __restrict__ eflag,
+                                                            int32_t* __restrict__ n_child, int32_t* __restrict__ n_touched) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int n = 0;
+    if (i < M.n_e) {
+        const int m = M.mask[i], own = bits[i];
+        for (int k = 0; k < 3; ++k) {
+            const int st = edge_state(M.nbr, bits, M.n_e, i, k, own);
+            n += st;
+            if ((m >> k) & 1) eflag[p2_index(M.base[i], m, k)] = st;
+        }
+        n_child[i] = 1 + n;
+    }
+    const int c = __syncthreads_count(n > 0);
+    if (threadIdx.x == 0 && c > 0) atomicAdd(n_touched, c);
+}
+
+// one lane per element: the nodes of its marked edges (coordinates by the owner, with refine_kernel's operations), its
+// 1 + (number of marked edges) children from cbase[i] on, their parent ids
+__global__ void __launch_bounds__(kBlock) refine_marked_kernel(MeshView M, CurveSet S, const uint8_t* __restrict__ bits,
+                                                               const uint8_t* __restrict__ ref, const int32_t* __restrict__ erank,
+                                                               const int32_t* __restrict__ cbase, int64_t n_tot, int64_t n_c,
+                                                               int32_t* __restrict__ child, double* __restrict__ coord_ext,
+                                                               int32_t* __restrict__ parent) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int m = M.mask[i], own = bits[i];
+    int32_t v[3], node[3];
+    for (int k = 0; k < 3; ++k) v[k] = M.elem[(int64_t)k * M.n_e + i];
+    for (int k = 0; k < 3; ++k) {
+        node[k] = -1;
+        if (!edge_state(M.nbr, bits, M.n_e, i, k, own)) continue;
+        bool owned;
+        int64_t j;
+        const int32_t ind = p2_edge(M, i, k, m, &owned, &j);
+        node[k] = (int32_t)(M.n_n + erank[ind]);
+        if (owned) {
+            const int32_t A = v[k], B = v[(k + 1) % 3];
+            const double ax = M.coord[A], ay = M.coord[M.n_n + A], bx = M.coord[B], by = M.coord[M.n_n + B];
+            double mx = (ax + bx) / 2, my = (ay + by) / 2;
+            if (j < 0 && S.n > 0) {
+                const int q = edge_curve(S, ax, ay, bx, by);
+                if (q >= 0) project(S.v[q], &mx, &my);
+            }
+            coord_ext[node[k]] = mx;
+            coord_ext[n_tot + node[k]] = my;
+        }
+    }
+    int64_t at = cbase[i];
+    auto put = [&](int32_t a, int32_t b, int32_t c) {
+        child[at] = a;
+        child[n_c + at] = b;
+        child[2 * n_c + at] = c;
+        if (parent) parent[at] = (int32_t)i;
+        ++at;
+    };
+    const int r = ref[i];
+    const int32_t mm = node[r];
+    if (mm < 0) {                                            // no marked edge (the closure marks r whenever one is)
+        put(v[0], v[1], v[2]);
+        return;
+    }
+    const int32_t a = v[r], b = v[(r + 1) % 3], c = v[(r + 2) % 3], p = node[(r + 1) % 3], q = node[(r + 2) % 3];
+    if (q >= 0) { put(a, mm, q); put(q, mm, c); } else put(a, mm, c);
+    if (p >= 0) { put(mm, b, p); put(mm, p, c); } else put(mm, b, c);
+}
+
 // curve index (-1: none) of every boundary edge, in the surf order of the element type (P2: visit order 1, 2, 0; P4: 0, 1, 2)
 __global__ void __launch_bounds__(kBlock) surf_curve_kernel(MeshView M, CurveSet S, int p2, int32_t* __restrict__ curve_of_surf) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -539,6 +681,16 @@ struct fep_mesh {
     int32_t* base = nullptr;
     int32_t* bbase = nullptr;
     CurveSet curves{};
+    // closed marks of fep_mesh_mark (scratch made by its first call, kept with the mesh)
+    bool has_marks = false, m_ready = false;
+    int64_t n_child = 0, n_new = 0;
+    uint8_t* m_in = nullptr;      // the caller's marks, when they came from the host
+    uint8_t* m_bits = nullptr;
+    uint8_t* m_ref = nullptr;
+    int32_t* m_erank = nullptr;   // (n_edges + 1) rank of every edge among the marked ones
+    int32_t* m_cbase = nullptr;   // (n_e + 1) first child of every element
+    int32_t* m_scan = nullptr;
+    int32_t* m_words = nullptr;   // {changed, elements with a marked edge}
     DeviceBlocks blocks;
 
     bool refused() const { return n_nonmanifold > 0 || n_inconsistent > 0 || n_degenerate > 0; }
@@ -641,6 +793,95 @@ static int mesh_refine_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_chi
     for (int r = 0; r < 2 && M->n_n > 0; ++r)
         HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(refine_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->curves, elem_child, coord_ext);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+// sweeps enqueued between two reads of the `changed` word: a chain of reference edges crosses at least one workgroup per sweep
+constexpr int kSweepsPerRead = 4;
+
+// 1 if p is memory of GPU `device` (or managed memory), 0 if it is host memory, pinned or not, -1 if it is another GPU's
+static int pointer_on_device(const void* p, int device) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();                             // runtimes that do not know a plain host pointer say so this way
+        return 0;
+    }
+    if (a.type == hipMemoryTypeManaged) return 1;
+    if (a.type != hipMemoryTypeDevice) return 0;
+    return a.device == device ? 1 : -1;
+}
+
+static int mesh_mark_impl(fep_mesh* M, hipStream_t st, const uint8_t* marked, int on_device, int64_t* out) {
+    if (!M || !marked || !out) return FEP_EINVAL;
+    if (M->refused()) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    if (pointer_on_device(marked, M->device) != (on_device ? 1 : 0)) return FEP_EINVAL;
+    const int64_t n_e = M->n_e, n_edges = M->n_edges;
+    if (!M->m_ready) {                                       // each block once, also when an earlier call ran out of memory half-way
+        const int64_t n_longest = (n_edges > n_e ? n_edges : n_e) + 1;
+        if (!M->m_bits) FEP_TRY(M->blocks.get(&M->m_bits, n_e));
+        if (!M->m_ref) FEP_TRY(M->blocks.get(&M->m_ref, n_e));
+        if (!M->m_erank) FEP_TRY(M->blocks.get(&M->m_erank, n_edges + 1));
+        if (!M->m_cbase) FEP_TRY(M->blocks.get(&M->m_cbase, n_e + 1));
+        if (!M->m_scan) FEP_TRY(M->blocks.get(&M->m_scan, scan_scratch_len(n_longest)));
+        if (!M->m_words) FEP_TRY(M->blocks.get(&M->m_words, 2));
+        M->m_ready = true;
+    }
+    if (!on_device && !M->m_in) FEP_TRY(M->blocks.get(&M->m_in, n_e));   // only meshes that are ever marked from the host
+    M->has_marks = false;
+    if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(M->m_in, marked, (size_t)n_e, hipMemcpyHostToDevice, st));
+        marked = M->m_in;
+    }
+    const dim3 grid(grid_for(n_e, kBlock)), block(kBlock);
+    hipLaunchKernelGGL(mark_init_kernel, grid, block, 0, st, M->view(), marked, M->m_bits, M->m_ref);
+    HIP_TRY(hipGetLastError());
+    int64_t n_sweeps = 0;
+    int32_t h_words[2] = {1, 0};
+    while (h_words[0]) {
+        HIP_TRY(hipMemsetAsync(M->m_words, 0, 2 * sizeof(int32_t), st));
+        for (int s = 0; s < kSweepsPerRead; ++s) {
+            hipLaunchKernelGGL(mark_sweep_kernel, grid, block, 0, st, n_e, M->nbr, M->m_ref, M->m_bits, M->m_words);
+            HIP_TRY(hipGetLastError());
+        }
+        n_sweeps += kSweepsPerRead;
+        HIP_TRY(hipMemcpyAsync(h_words, M->m_words, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipMemsetAsync(M->m_erank + n_edges, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(M->m_cbase + n_e, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(mark_count_kernel, grid, block, 0, st, M->view(), M->m_bits, M->m_erank, M->m_cbase, M->m_words + 1);
+    HIP_TRY(hipGetLastError());
+    FEP_TRY(scan_exclusive(st, n_edges + 1, M->m_erank, M->m_scan));
+    FEP_TRY(scan_exclusive(st, n_e + 1, M->m_cbase, M->m_scan));
+    int32_t h_new = 0, h_child = 0;
+    HIP_TRY(hipMemcpyAsync(&h_new, M->m_erank + n_edges, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_child, M->m_cbase + n_e, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_words, M->m_words, sizeof(h_words), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out[0] = h_child;
+    out[1] = h_new;
+    out[2] = h_words[1];
+    out[3] = n_sweeps;
+    // n_child <= 4 n_e < 2^31 - 1 (fep_mesh_create refuses larger meshes) and n_new <= n_edges <= 3 n_e, so neither int32 scan
+    // can wrap; only the sum with n_n can pass int32
+    if (M->n_n + (int64_t)h_new >= (int64_t)INT32_MAX) return FEP_ERANGE;
+    M->n_child = h_child;
+    M->n_new = h_new;
+    M->has_marks = true;
+    return FEP_OK;
+}
+
+static int mesh_refine_marked_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext, int32_t* parent) {
+    if (!M || !elem_child || !coord_ext) return FEP_EINVAL;
+    if (M->refused() || !M->has_marks) return FEP_ESTATE;
+    const int64_t n_tot = M->n_n + M->n_new;
+    FEP_TRY(fep_set_device(M->device));
+    for (int r = 0; r < 2 && M->n_n > 0; ++r)
+        HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(refine_marked_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->curves, M->m_bits,
+                       M->m_ref, M->m_erank, M->m_cbase, n_tot, M->n_child, elem_child, coord_ext, parent);
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
@@ -752,6 +993,25 @@ static int mesh_refine_host_impl(const fep_mesh* M, int32_t* elem_child_h, doubl
     return FEP_OK;
 }
 
+static int mesh_refine_marked_host_impl(const fep_mesh* M, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h) {
+    if (!M || !elem_child_h || !coord_ext_h) return FEP_EINVAL;
+    if (M->refused() || !M->has_marks) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(M->device));
+    const int64_t n_tot = M->n_n + M->n_new;
+    DeviceBlocks tmp;
+    int32_t *child = nullptr, *parent = nullptr;
+    double* coord_ext = nullptr;
+    FEP_TRY(tmp.get(&child, 3 * M->n_child));
+    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
+    if (parent_h) FEP_TRY(tmp.get(&parent, M->n_child));
+    FEP_TRY(mesh_refine_marked_impl(M, nullptr, child, coord_ext, parent));
+    FEP_TRY(fetch(elem_child_h, child, 3 * M->n_child));
+    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
+    FEP_TRY(fetch(parent_h, parent, M->n_child));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
 static int mesh_surf_curve_host_impl(const fep_mesh* M, int elem_type, int32_t* curve_of_surf_h) {
     if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || (!curve_of_surf_h && M->n_bnd > 0)) return FEP_EINVAL;
     if (M->refused()) return FEP_ESTATE;
@@ -826,6 +1086,18 @@ extern "C" int fep_mesh_refine_dev(const fep_mesh* mesh, void* stream, int32_t* 
 
 extern "C" int fep_mesh_refine_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h) {
     FEP_GUARD(mesh_refine_host_impl(mesh, elem_child_h, coord_ext_h))
+}
+
+extern "C" int fep_mesh_mark(fep_mesh* mesh, void* stream, const uint8_t* marked, int on_device, int64_t out[4]) {
+    FEP_GUARD(mesh_mark_impl(mesh, (hipStream_t)stream, marked, on_device, out))
+}
+
+extern "C" int fep_mesh_refine_marked_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d, int32_t* parent_d) {
+    FEP_GUARD(mesh_refine_marked_impl(mesh, (hipStream_t)stream, elem_child_d, coord_ext_d, parent_d))
+}
+
+extern "C" int fep_mesh_refine_marked_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h) {
+    FEP_GUARD(mesh_refine_marked_host_impl(mesh, elem_child_h, coord_ext_h, parent_h))
 }
 
 extern "C" int fep_mesh_set_curves(fep_mesh* mesh, int n_curves, const double* curves_h) {

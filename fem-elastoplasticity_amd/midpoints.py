@@ -282,7 +282,7 @@ class DeviceMesh:
 
     def __init__(self, coord, elem, device, on_device=False):
         from . import _lib
-        self._lib, self._h, self.device, self.n_curves = _lib, None, int(device), 0
+        self._lib, self._h, self.device, self.n_curves, self.marks = _lib, None, int(device), 0, None
         if on_device:
             if elem.dtype.itemsize != 4 or coord.dtype.itemsize != 8 or not (elem.is_contiguous() and coord.is_contiguous()):
                 raise ValueError('device meshes are contiguous int32 / float64 tensors')
@@ -423,6 +423,58 @@ class DeviceMesh:
                                                             C.c_void_p(coord_ext.data_ptr())), 'fep_mesh_refine_dev')
         return coord_ext, child
 
+    def mark(self, marked, on_device=False):
+        """Closes the marks `marked` (n_e; non-zero = marked; a host array, or — `on_device` — a uint8 / bool tensor of this
+        GPU) under the longest-edge rule and keeps them in the mesh for refine_marked (fep_mesh_mark; synchronises the
+        stream).  Returns {'n_child', 'n_new_nodes', 'n_marked_elements' (elements with a marked edge), 'n_sweeps'}."""
+        self._accepted()
+        n_e = self.info['n_e']
+        if on_device:
+            if marked.dtype.itemsize != 1 or tuple(marked.shape) != (n_e,) or not marked.is_contiguous():
+                raise ValueError(f'device marks are a contiguous uint8 / bool tensor of ({n_e},)')
+            pm, stream, keep = C.c_void_p(marked.data_ptr()), self._stream(), marked
+        else:
+            keep = np.ascontiguousarray(np.asarray(marked) != 0, dtype=np.uint8)
+            if keep.shape != (n_e,):
+                raise ValueError(f'marks: one entry per element ({n_e},), got {keep.shape}')
+            pm, stream = self._lib.ptr(keep), None
+        out = np.zeros(4, dtype=np.int64)
+        self._lib.check(self._lib.lib().fep_mesh_mark(self._h, stream, pm, int(bool(on_device)), out.ctypes.data_as(self._lib.c_i64_p)),
+                        'fep_mesh_mark')
+        self.marks = dict(zip(('n_child', 'n_new_nodes', 'n_marked_elements', 'n_sweeps'), (int(v) for v in out)))
+        return dict(self.marks)
+
+    def _marked(self):
+        self._accepted()
+        if self.marks is None:
+            raise ValueError('refine_marked needs the marks: call mark() first')
+        return self.marks['n_child'], self.info['n_n'] + self.marks['n_new_nodes']
+
+    def refine_marked(self):
+        """One level of longest-edge refinement of the marked elements -> (coordinates (2, n_n + n_new_nodes), elements
+        (3, n_child) int64, parent (n_child) int64), host arrays, bit-equal to refine_marked(device=None)."""
+        n_child, n_tot = self._marked()
+        child = np.empty((3, n_child), dtype=np.int32)
+        coord_ext = np.empty((2, n_tot))
+        parent = np.empty(n_child, dtype=np.int32)
+        ptr = self._lib.ptr
+        self._lib.check(self._lib.lib().fep_mesh_refine_marked_host(self._h, ptr(child), ptr(coord_ext), ptr(parent)),
+                        'fep_mesh_refine_marked_host')
+        return coord_ext, child.astype(np.int64), parent.astype(np.int64)
+
+    def refine_marked_dev(self):
+        """Device-resident form -> torch tensors (coordinates float64, elements int32, parent int32) on the current stream."""
+        import torch
+        n_child, n_tot = self._marked()
+        dev = torch.device('cuda', self.device)
+        child = torch.empty((3, n_child), dtype=torch.int32, device=dev)
+        coord_ext = torch.empty((2, n_tot), dtype=torch.float64, device=dev)
+        parent = torch.empty(n_child, dtype=torch.int32, device=dev)
+        self._lib.check(self._lib.lib().fep_mesh_refine_marked_dev(self._h, self._stream(), C.c_void_p(child.data_ptr()),
+                                                                   C.c_void_p(coord_ext.data_ptr()), C.c_void_p(parent.data_ptr())),
+                        'fep_mesh_refine_marked_dev')
+        return coord_ext, child, parent
+
 
 def area_stats_dev(coord_d, elem_d, device, out=None):
     """fep_mesh_area_stats_dev on torch tensors of GPU `device` (coord (2, n_n) float64, elem (3, n_e) int32, contiguous),
@@ -493,3 +545,161 @@ def refine_uniform(coord, elem, levels=1, device=None, curves=None):
             if st[2] > 0:
                 raise _folded(lv + 1, st)
     return coord, elem
+
+
+# ---------------------------------------------------------------------------------------
+# refinement of marked triangles: conforming longest-edge bisection (Rivara's 4T-LE; include/fep.h, fep_mesh_mark)
+# ---------------------------------------------------------------------------------------
+def _half_edges(elem):
+    """(nbr (3, n_e): 3 j + edge of j across edge k of i, -1 on the boundary; owned (3, n_e) bool) of an edge-manifold,
+    consistently oriented mesh without degenerate triangles — ValueError on any other, as the device path."""
+    n_e = elem.shape[1]
+    half = {}
+    for i in range(n_e):
+        v = (int(elem[0, i]), int(elem[1, i]), int(elem[2, i]))
+        if v[0] == v[1] or v[1] == v[2] or v[2] == v[0]:
+            raise ValueError(f'marked refinement: element {i} names a vertex twice')
+        for k in range(3):
+            if half.setdefault((v[k], v[(k + 1) % 3]), 3 * i + k) != 3 * i + k:
+                raise ValueError('marked refinement numbers edge-manifold, consistently oriented meshes only: '
+                                 f'two elements walk the edge {(v[k], v[(k + 1) % 3])} the same way')
+    nbr = np.full((3, n_e), -1, dtype=np.int64)
+    for (a, b), code in half.items():
+        nbr[code % 3, code // 3] = half.get((b, a), -1)
+    owned = (nbr < 0) | (np.arange(n_e)[None, :] < nbr // 3)
+    return nbr, owned
+
+
+def reference_edges(coord, elem):
+    """The reference (longest) edge of every triangle: edge k runs from vertex k to vertex (k + 1) % 3, its squared length
+    is dx dx + dy dy of the vertex chord in the element's own walking direction, and the slots are compared in the order
+    0, 1, 2 with a strict >, so the lowest slot wins a tie."""
+    x, y = np.asarray(coord, dtype=np.float64)
+    elem = np.asarray(elem)
+    L = []
+    for k in range(3):
+        dx, dy = x[elem[(k + 1) % 3]] - x[elem[k]], y[elem[(k + 1) % 3]] - y[elem[k]]
+        L.append(dx * dx + dy * dy)
+    r = np.zeros(elem.shape[1], dtype=np.int64)
+    best = L[0].copy()
+    for k in (1, 2):
+        longer = L[k] > best
+        r[longer] = k
+        best[longer] = L[k][longer]
+    return r
+
+
+def _closed_marks(nbr, ref, marked):
+    """Own-half-edge bits (n_e) uint8 of the least fixpoint: a marked element sets all three, and an element with any
+    marked edge (own bit or the neighbour's) sets its reference edge.  A work list; the fixpoint does not depend on the order."""
+    n_e = ref.size
+    bits = np.where(marked, 7, 0).astype(np.uint8)
+    todo = [int(i) for i in np.flatnonzero(marked)]
+    while todo:
+        i = todo.pop()
+        for k in range(3):                                   # every own bit may be new to the neighbour across it
+            nb = int(nbr[k, i])
+            if nb < 0 or not (bits[i] >> k) & 1:
+                continue
+            j = nb // 3
+            want = bits[j] | (1 << int(ref[j]))
+            if want != bits[j]:
+                bits[j] = want
+                todo.append(j)
+    return bits
+
+
+def _refine_marked_host(coord, elem, marked, rows):
+    coord = np.asarray(coord, dtype=np.float64)
+    elem = np.asarray(elem).astype(np.int64)
+    n_e, n_n = elem.shape[1], coord.shape[1]
+    marked = np.asarray(marked)
+    if marked.shape != (n_e,):
+        raise ValueError(f'marks: one entry per element ({n_e},), got {marked.shape}')
+    marked = marked != 0
+    nbr, owned = _half_edges(elem)
+    ref = reference_edges(coord, elem)
+    bits = _closed_marks(nbr, ref, marked)
+    state = np.zeros((3, n_e), dtype=bool)                   # edge k of element i is marked: own bit or the neighbour's
+    for k in range(3):
+        j, kj = nbr[k] // 3, nbr[k] % 3
+        state[k] = ((bits >> k) & 1).astype(bool) | ((nbr[k] >= 0) & (((bits[j] >> kj) & 1) != 0))
+    cv = _curve_rows_py(rows) if rows is not None else None
+    # the P2 edge order: owners in element order, their owned slots in the visit order 1, 2, 0
+    new_of = np.full((3, n_e), -1, dtype=np.int64)
+    new_xy = []
+    for i in range(n_e):
+        for k in (1, 2, 0):
+            if not (owned[k, i] and state[k, i]):
+                continue
+            A, B = int(elem[k, i]), int(elem[(k + 1) % 3, i])
+            mid = (coord[:, A] + coord[:, B]) / 2
+            if nbr[k, i] < 0 and cv is not None:
+                q = _edge_curve(cv, coord[:, A], coord[:, B])
+                if q >= 0:
+                    mid = _project(cv[q], mid)
+            new_of[k, i] = n_n + len(new_xy)
+            new_xy.append(mid)
+            if nbr[k, i] >= 0:
+                new_of[nbr[k, i] % 3, nbr[k, i] // 3] = new_of[k, i]
+    child, parent = [], []
+    for i in range(n_e):
+        if not state[:, i].any():
+            child.append((int(elem[0, i]), int(elem[1, i]), int(elem[2, i])))
+            parent.append(i)
+            continue
+        r = int(ref[i])
+        a, b, c = (int(elem[(r + s) % 3, i]) for s in range(3))
+        m, p, q = (int(new_of[(r + s) % 3, i]) for s in range(3))
+        rows_i = ([(a, m, q), (q, m, c)] if q >= 0 else [(a, m, c)]) + ([(m, b, p), (m, p, c)] if p >= 0 else [(m, b, c)])
+        child += rows_i
+        parent += [i] * len(rows_i)
+    coord_ext = np.concatenate([coord, np.array(new_xy, dtype=np.float64).reshape(-1, 2).T], axis=1)
+    return coord_ext, np.ascontiguousarray(np.array(child, dtype=np.int64).T), np.array(parent, dtype=np.int64)
+
+
+def refine_marked(coord, elem, marked, device=None, curves=None):
+    """One level of conforming longest-edge bisection (Rivara's 4T-LE) of the elements `marked` (n_e; non-zero = marked)
+    -> (coordinates (2, n_n + new), elements (3, n_child) int64, parent (n_child) int64).  No counterpart in the reference.
+    The rule (include/fep.h, fep_mesh_mark): a marked element marks its three edges; an element with any marked edge must
+    have its reference edge (reference_edges: the longest, lowest slot on a tie) marked — the least fixpoint, which does not
+    depend on the order of evaluation.  Every marked edge gets one node, numbered n_n + its rank among the marked edges in
+    the P2 edge order, at the coordinates of create_midpoints_P2's midside node (moved onto `curves` by the same rule), so
+    that with every element marked the coordinates equal refine_uniform's.  With a = vertex r (r the reference edge),
+    b, c the next two and m, p, q the nodes of ab, bc, ca, an element with marked edges becomes (a, m, q), (q, m, c) — or
+    (a, m, c) without q — followed by (m, b, p), (m, p, c) — or (m, b, c) without p; one without stays as it is.  Children
+    follow their parents in element order; orientation is preserved.  `device` (a GPU index): the kernels (DeviceMesh.mark,
+    .refine_marked), bit-equal to this loop.  With `curves` the result is checked with the area statistics and a child of
+    non-positive area raises ValueError."""
+    rows = _curve_rows(curves)
+    if device is not None:
+        with DeviceMesh(coord, elem, device) as m:
+            if rows is not None:
+                m.set_curves(curves)
+            m.mark(marked)
+            out = m.refine_marked()
+    else:
+        out = _refine_marked_host(coord, elem, marked, rows)
+    if rows is not None:
+        st = area_stats(out[0], out[1], device=device)
+        if st[2] > 0:
+            raise _folded(1, st)
+    return out
+
+
+def mark_plastic(ind_p, elem, n_q, rings=1):
+    """Marks for refine_marked from a step's plastic flags: `ind_p` (n_e n_q), element by element as the drivers' steps
+    return them.  An element is marked if any of its n_q integration points is plastic; then, `rings` times, so is every
+    element that shares a vertex (rows 0..2 of `elem`) with a marked one.  Returns a bool (n_e) array."""
+    elem = np.asarray(elem)
+    n_e = elem.shape[1]
+    flags = np.asarray(ind_p).reshape(-1) != 0
+    if flags.size != n_e * n_q:
+        raise ValueError(f'{flags.size} flags for {n_e} elements of {n_q} integration points')
+    marked = flags.reshape(n_e, n_q).any(axis=1)
+    n_n = int(elem[0:3].max()) + 1
+    for _ in range(rings):
+        touched = np.zeros(n_n, dtype=bool)
+        touched[elem[0:3][:, marked]] = True
+        marked = touched[elem[0:3]].any(axis=0)
+    return marked

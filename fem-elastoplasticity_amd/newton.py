@@ -35,7 +35,7 @@ import scipy.sparse.linalg as sspl
 
 from .hotpath import MeshContext, in_situ_strain
 from .mesh import square_mesh
-from .tables import ELEMENT_SHAPE, _coerce, element_tables
+from .tables import ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables
 
 
 def point_sums(q_int, elements, weight, n_n=None):
@@ -471,7 +471,7 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
                      pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None, in_situ=None,
-                     body_force=None, materials=None):
+                     body_force=None, materials=None, adapt=0, mark=None):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
@@ -494,10 +494,34 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     ground at rest; the stopping quantity of the Newton iterates is then taken relative to the elastic response to the body force as well
     (_newton_iteration, q_load), since such a state has no displacement of its own to be relative to.  `materials` = (shear, bulk, eta, c), scalars or (n_int) arrays (layered ground), instead of the
     reference's constants.  With all three None the run is the reference's, bit for bit.  The result carries 's0_field'
-    and the accepting calls' stress 's' ((4, n_int), list per step) when `in_situ` is given."""
+    and the accepting calls' stress 's' ((4, n_int), list per step) when `in_situ` is given.
+    `adapt` = k > 0 (no counterpart in the reference): the whole excavation runs k + 1 times; after each run but the last the
+    P1 vertex mesh is refined where `mark` says (midpoints.refine_marked: conforming longest-edge bisection, new wall nodes on
+    `curves`), renumbered again with `renumber`, raised to `element_type`, and the next run starts from zero on it (this
+    driver carries no plastic strain from step to step, so there is no state to transfer).  `mark`: None — mark_plastic of
+    the last accepted step's flags with one ring of neighbours — or a callable (hist, coords, elem_p1) -> bool (n_e) on the
+    P1 vertex mesh the run was solved on.  `refine` is applied first, once; `in_situ` is evaluated again on every mesh;
+    `materials` given as arrays raise ValueError (there is no parent-to-child rule for them yet).  The result is the last
+    run's history — 'coords', 'elem', 'node_of_input' included — plus 'adapt': per run {'n_e', 'n_n', 'n_marked', 'n_child',
+    'displ' (the last monitored value), 'n_steps' (accepted load steps), 'n_plast' (at the end), 'plastic' (elements with a plastic point at the end), 'marked', 'parent' (of the
+    refinement that followed; None after the last run), 'ind_p' (the last accepted step's flags per integration point), 'coords',
+    'elem' (the mesh of that run)}.  `monitor` keeps naming a node of the input mesh."""
     if body_force is not None and in_situ is None:
         raise ValueError('body_force goes with in_situ (the stress field it is in equilibrium with)')
+    if adapt:
+        return _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves,
+                             int(adapt), mark, materials,
+                             dict(n_load_steps=n_load_steps, linear_solver=linear_solver, pcg_rtol=pcg_rtol, pcg_forcing=pcg_forcing,
+                                  pcg_forcing_cap=pcg_forcing_cap, pcg_inexact_rtol=pcg_inexact_rtol, in_situ=in_situ,
+                                  body_force=body_force))
     p = _tsx_setup(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves)
+    return _tsx_run(p, device, context_factory, log, materials, n_load_steps, linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
+                    pcg_inexact_rtol, in_situ, body_force)
+
+
+def _tsx_run(p, device, context_factory, log, materials, n_load_steps, linear_solver, pcg_rtol, pcg_forcing, pcg_forcing_cap,
+             pcg_inexact_rtol, in_situ, body_force):
+    """solve_tsx_tunnel once the problem `p` (_tsx_setup) exists: context, ops, the load steps."""
     clock = [time.perf_counter()]
     ctx = _context_maker(context_factory, device)(p['elem'], p['coords'], *element_tables(p['type']))
     assert ctx.n_int == p['elem'].shape[1] * ELEMENT_SHAPE[p['type']][1]
@@ -509,6 +533,63 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
                                         pcg_inexact_rtol)) as ops:
         _refuse_folded(p, ctx)
         return _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ, body_force)
+
+
+def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves, adapt,
+                  mark, materials, run_kw):
+    """solve_tsx_tunnel(adapt > 0): solve, mark, refine the marked elements, again."""
+    from .hotpath import default_device
+    from .mesh import renumber_for_locality
+    from .meshio import load_tsx_mesh
+    from .midpoints import create_midpoints, mark_plastic, refine_marked, refine_uniform
+    if adapt < 0:
+        raise ValueError('adapt must be >= 0')
+    if materials is not None and any(np.ndim(m) > 0 for m in materials):
+        raise ValueError('adapt: materials per integration point have no parent-to-child rule yet; pass scalars')
+    t = _coerce(element_type)
+    if mesh_dir is not None:
+        coords, elem = load_tsx_mesh(mesh_dir, 'P1')
+    if coords is None or elem is None:
+        raise ValueError('pass the mesh (coords, elem) or mesh_dir')
+    c1, e1 = np.asarray(coords, dtype=np.float64), np.asarray(elem, dtype=np.int64)
+    if e1.shape[0] != 3:
+        raise ValueError(f'adapt starts from the P1 mesh: (3, n_e) vertex ids, got {e1.shape}')
+    mesh_device = None if context_factory is not None else (default_device() if device is None else device)
+    input_ids = np.arange(c1.shape[1])                         # where the input's nodes are in the current mesh
+    if refine:
+        c1, e1 = refine_uniform(c1, e1, levels=refine, device=mesh_device, curves=curves)
+    n_q = ELEMENT_SHAPE[t][1]
+    rounds = []
+    for k in range(adapt + 1):
+        if renumber:
+            e1, c1, node_perm, _ = renumber_for_locality(e1, c1)
+            inv = np.empty_like(node_perm)
+            inv[node_perm] = np.arange(node_perm.size)
+            input_ids = inv[input_ids]
+        ck, ek = c1, e1
+        if t is not LagrangeElementType.P1:
+            ext = create_midpoints(t, c1, e1, device=mesh_device, curves=curves)
+            ck, ek = np.asarray(ext['coord_ext'], dtype=np.float64), np.asarray(ext['elem_ext'], dtype=np.int64)
+        p = _tsx_setup(ck, ek, t, None, 0, False, (monitor[0], int(input_ids[monitor[1]])), device, context_factory, log, curves)
+        p['prepared'], p['node_of_input'], p['keep_flags'] = True, (input_ids.copy() if renumber else None), True
+        hist = _tsx_run(p, device, context_factory, log, materials, **run_kw)
+        flags = hist.pop('ind_p')
+        row = {'n_e': int(ek.shape[1]), 'n_n': int(ck.shape[1]), 'n_marked': None, 'n_child': None, 'displ': hist['displ'][-1],
+               'n_steps': len(hist['zeta']), 'n_plast': hist['n_plast'][-1],
+               'plastic': mark_plastic(flags, e1, n_q, rings=0), 'marked': None, 'parent': None,
+               'ind_p': flags, 'coords': ck, 'elem': ek}
+        rounds.append(row)
+        if log:
+            log(f'adapt {k}: {row["n_e"]} elements, {row["n_n"]} nodes, U{monitor}={row["displ"]:.16g}')
+        if k == adapt:
+            break
+        marked = mark_plastic(flags, e1, n_q, rings=1) if mark is None else np.asarray(mark(hist, c1, e1)) != 0
+        if marked.shape != (e1.shape[1],):
+            raise ValueError(f'mark: one entry per element ({e1.shape[1]},), got {marked.shape}')
+        c1, e1, parent = refine_marked(c1, e1, marked, device=mesh_device, curves=curves)
+        row.update(n_marked=int(marked.sum()), n_child=int(e1.shape[1]), marked=marked, parent=parent)
+    hist['adapt'] = rounds
+    return hist
 
 
 def _refuse_folded(p, ctx):
@@ -600,6 +681,8 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=
         Um = ops.host(U).reshape((2, -1), order='F')
         hist['displ'].append(Um[monitor])
         hist['n_plast'].append(ops.count(r['ind_p']))
+        if p.get('keep_flags'):                                      # the adaptive driver marks from the last accepted step
+            hist['ind_p'] = np.asarray(ops.host(r['ind_p'])).astype(bool).ravel()
         hist['U'].append(Um.copy())
         if field is not None:
             hist['s'].append(np.array(ops.host(r['s'])))

@@ -621,6 +621,42 @@ int fep_mesh_area_stats_dev(int device_id, void* stream, int64_t n_e, int64_t n_
 int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
                              double* out_h);
 
+/* Refinement of MARKED elements: one level of conforming longest-edge bisection (Rivara's 4T-LE), which the reference does
+ * not have.  Opt-in: without these calls every output above is byte for byte what it was.
+ *   reference edge  r of an element = its longest edge: squared length dx dx + dy dy with dx = x[B] - x[A], dy = y[B] - y[A]
+ *       of the vertex chord (also on a curved edge) in the element's own walking direction, without fused multiply-adds;
+ *       slots compared in the order 0, 1, 2 with a strict >, so the lowest slot wins a tie.  Both elements of an edge get
+ *       the same squared length (the signs cancel exactly).
+ *   closure  a marked element marks its three edges; an edge is marked if either half-edge says so; an element with any
+ *       marked edge must have its reference edge marked.  The least fixpoint of a monotone rule: unique, finite and
+ *       independent of the order of evaluation, so kernels and a sequential loop reach the same marks.
+ *   nodes  every marked edge gets one node, n_n + the rank of the edge among the marked edges in the P2 edge order (elem_ed),
+ *       at the coordinates fep_mesh_refine_* gives that edge's midside node (computed by the owner; moved onto the curves of
+ *       fep_mesh_set_curves by the same rule).  With every element marked coord_ext equals fep_mesh_refine_*'s bit for bit.
+ *   children  with a = V[r], b = V[(r + 1) % 3], c = V[(r + 2) % 3] and m, p, q the nodes of ab, bc, ca: an element without
+ *       a marked edge is one child, its row unchanged; any other is (a, m, q), (q, m, c) — or (a, m, c) when ca is not
+ *       marked — followed by (m, b, p), (m, p, c) — or (m, b, c) when bc is not.  1 + (marked edges) children per element,
+ *       from the exclusive prefix sum of these counts on; parent[child] = element.  Orientation is preserved.
+ *
+ *   fep_mesh_mark   marked (n_e) bytes, non-zero = marked: a host pointer (on_device == 0) or a device pointer of the mesh's
+ *                   device (FEP_EINVAL, and the mesh keeps the marks it had, when the pointer is NULL, on the other side
+ *                   than on_device says, or memory of another device).  Closes the marks, ranks the edges and counts the children on `stream`, stores
+ *                   the result in the mesh in place of any earlier one, and SYNCHRONISES `stream`, because the output sizes
+ *                   depend on it: not capturable.  Its first call on a mesh allocates the scratch the mesh keeps.
+ *                   out = {n_child, n_new_nodes, elements with a marked edge, n_sweeps}; n_sweeps (closure sweeps enqueued)
+ *                   is informational: each sweep lets a workgroup iterate over its own marks in LDS until they stand still
+ *                   and reads other workgroups' marks from memory; several sweeps are enqueued per read of the "changed"
+ *                   word.  The stored marks do not depend on any of this.  No marks at all is legal: the identity
+ *                   (n_child = n_e, no new node, parent = 0 .. n_e - 1).
+ *   fep_mesh_refine_marked_*  elem_child (3, n_child), coord_ext (2, n_n + n_new_nodes), parent (n_child; may be NULL).
+ *                   The _dev form enqueues on `stream` and allocates nothing; the _host form is synchronous.
+ *                   FEP_ESTATE, and nothing written: n_nonmanifold, n_inconsistent or n_degenerate > 0 (both calls), or no
+ *                   successful fep_mesh_mark before.  FEP_EINVAL: NULL pointers.  FEP_ERANGE (fep_mesh_mark): n_n +
+ *                   n_new_nodes beyond int32 (n_child <= 4 n_e cannot be: fep_mesh_create refuses such a mesh).  No floating-point atomics; two calls give the same bytes. */
+int fep_mesh_mark(fep_mesh* mesh, void* stream, const uint8_t* marked, int on_device, int64_t out[4]);
+int fep_mesh_refine_marked_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d, int32_t* parent_d);
+int fep_mesh_refine_marked_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h);
+
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on
  * the device; K is the `data` array fep_step_dev wrote, on the context's CSR pattern.  The Jacobi blocks are the 2x2

@@ -17,10 +17,16 @@ both sit in one record, and writes profiles/mesh_bench_curved.json unless `--out
 solves levels 0..R on the wall's polygon and on its ellipse and prints U[0, 40] of both.  Every run also times the refinement
 kernel alone and fep_mesh_area_stats_dev on its children (HIP events).
 
+`--marked` adds refine_marked (conforming longest-edge bisection of marked elements) on the same refined mesh with the
+elements within 4 of the tunnel's centre marked: the NumPy form (one run), the device path host arrays in / out, and,
+device-resident with HIP events, fep_mesh_mark (closure, scans; it synchronises) and the emit kernel alone; and the monitored
+displacement U[0, 40] of the P1 tunnel run unrefined, with adapt=2 and with refine=2 (direct solver).  Key 'marked';
+profiles/mesh_bench_marked.json unless `--out` says otherwise.
+
 `--solve R` adds the end-to-end TSX run solve_tsx_tunnel(refine=R, 'P1', linear_solver='amg', pcg_inexact_rtol=1e-2) with
 its set-up split, without and with renumbering.  One JSON line (and `--out FILE`).
 
-    python tools/mesh_bench.py [--refine 4] [--type P2] [--passes 5] [--solve 5] [--curved] [--out profiles/mesh_bench.json]
+    python tools/mesh_bench.py [--refine 4] [--type P2] [--passes 5] [--solve 5] [--curved] [--marked] [--out profiles/mesh_bench.json]
 """
 import argparse
 import importlib
@@ -128,6 +134,41 @@ def measure(fep, torch, a, coord0, elem0, curves, host=True):
     return res
 
 
+def measure_marked(fep, torch, a, coord0, elem0):
+    dev = a.device
+    coord, elem = fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev)
+    cx, cy = coord[0][elem].mean(axis=0), coord[1][elem].mean(axis=0)
+    marked = cx * cx + cy * cy < 16.0
+    res = {'n_e': int(elem.shape[1]), 'n_marked': int(marked.sum())}
+    t0 = time.perf_counter()
+    h = fep.refine_marked(coord, elem, marked)
+    res['host_ms'] = 1e3 * (time.perf_counter() - t0)
+    d = fep.refine_marked(coord, elem, marked, device=dev)                            # warm-up
+    res['bit_equal'] = bool(all(x.tobytes() == y.tobytes() and x.dtype == y.dtype for x, y in zip(h, d)))
+    res['n_child'], res['n_new_nodes'] = int(d[1].shape[1]), int(d[0].shape[1] - coord.shape[1])
+    res['device_host'] = wall(lambda: fep.refine_marked(coord, elem, marked, device=dev), a.passes)
+    res['speedup_device_host'] = res['host_ms'] / res['device_host']['median_ms']
+    tdev = torch.device('cuda', dev)
+    coord_d, elem_d = torch.from_numpy(coord).to(tdev), torch.from_numpy(elem.astype(np.int32)).to(tdev)
+    marked_d = torch.from_numpy(marked.view(np.uint8)).to(tdev)
+    with fep.DeviceMesh(coord_d, elem_d, dev, on_device=True) as m:
+        res['sweeps'] = m.mark(marked_d, on_device=True)['n_sweeps']                  # warm-up: makes the scratch
+        m.refine_marked_dev()
+        torch.cuda.synchronize(dev)
+        res['resident_mark'] = events(torch, lambda: m.mark(marked_d, on_device=True), a.passes)
+        res['resident_emit'] = events(torch, m.refine_marked_dev, a.passes)
+    runs = {'unrefined': {}, 'adapt2': {'adapt': 2}, 'refine2': {'refine': 2}}
+    res['displ'] = {}
+    for name, kw in runs.items():
+        r = fep.solve_tsx_tunnel(coord0, elem0, 'P1', device=dev, **kw)
+        res['displ'][name] = {'U_0_40': float(r['displ'][-1]), 'n_e': int(r['elem'].shape[1]) if 'elem' in r else int(elem0.shape[1]),
+                              'accepted_steps': len(r['zeta']), 'n_plast_last': int(r['n_plast'][-1])}
+        if 'adapt' in r:
+            res['displ'][name]['rounds'] = [{k: row[k] for k in ('n_e', 'n_n', 'n_marked', 'n_child', 'displ', 'n_steps', 'n_plast')}
+                                            for row in r['adapt']]
+    return res
+
+
 def solve(fep, a, mesh_dir, refine, renumber, curves):
     t0 = time.perf_counter()
     h = fep.solve_tsx_tunnel(mesh_dir=mesh_dir, element_type='P1', refine=refine, renumber=renumber, linear_solver='amg',
@@ -147,6 +188,7 @@ def main():
     ap.add_argument('--passes', type=int, default=5)
     ap.add_argument('--solve', type=int, default=None)
     ap.add_argument('--curved', action='store_true')
+    ap.add_argument('--marked', action='store_true')
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -163,6 +205,11 @@ def main():
         res['curved'] = measure(fep, torch, a, coord0, elem0, hole, host=False)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'mesh_bench_curved.json')
+
+    if a.marked:
+        res['marked'] = measure_marked(fep, torch, a, coord0, elem0)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'mesh_bench_marked.json')
 
     if a.solve is not None:
         d = tempfile.mkdtemp(prefix='tsx_csv_')
