@@ -30,6 +30,7 @@ from .solver import KrylovSolver, build_amg_hierarchy
 from .dist_newton import DistributedPCG, GatheredSolver, solve_strip_footing_sharded, solve_tsx_tunnel_sharded
 from .midpoints import (DeviceMesh, Ellipse, area_stats, area_stats_dev, create_midpoints, create_midpoints_P2, create_midpoints_P4,
                         mark_plastic, refine_marked, refine_uniform)
+from .estimate import estimate_np, indicator_stats, mark_bulk, recover_stress_np, tree_sum
 from .meshio import dump_free_dof_csv, load_tsx_mesh, prepare_tsx_mesh
 from . import plasticity2d_dp, tsx_tunnel, elasticity2d, vonmises
 
@@ -44,4 +45,5 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'construct_constitutive_problem_vm', 'construct_constitutive_problem_mc', 'construct_constitutive_problem_vmps',
            'solve_cutout_cyclic',
            'construct_constitutive_problem_field', 'in_situ_strain', 'linear_in_situ',
+           'tree_sum', 'recover_stress_np', 'estimate_np', 'indicator_stats', 'mark_bulk',
            'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d', 'vonmises']

@@ -106,6 +106,12 @@ PROTOTYPES = {
     'fep_mesh_mark': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_i64_p]),
     'fep_mesh_refine_marked_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_mesh_refine_marked_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_recover_stress_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_recover_stress_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_estimate_dev': (C.c_int, [C.c_void_p] * 7),
+    'fep_estimate_host': (C.c_int, [C.c_void_p] * 6),
+    'fep_mark_bulk_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    'fep_mark_bulk_host': (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     'fep_mesh_set_curves': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'fep_mesh_surf_curve_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'fep_mesh_surf_curve_host': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -121,9 +121,10 @@ struct fep_ctx {
     double *s_int = nullptr, *ds_int = nullptr;     // used when the caller does not ask for s / ds
     uint2* blk_counts = nullptr;
     int n_count_blocks = 0;
-    // persistent device buffers of the *_host entry points (u, ep, e, s, ds, ind_p, k, f, counts, q, node values, e0_field)
-    void* hbuf[12] = {};
-    size_t hbuf_bytes[12] = {};
+    // persistent device buffers of the *_host entry points (u, ep, e, s, ds, ind_p, k, f, counts, q, node values, e0_field,
+    // recovered nodal stress, eta2, indicator statistics)
+    void* hbuf[15] = {};
+    size_t hbuf_bytes[15] = {};
     // host copies of the pattern
     std::vector<int32_t> indptr, indices;
     // in-situ profiling: 4 events per call (fep_step_dev, fep_assemble_dev)
@@ -1819,6 +1820,87 @@ static int point_coords_host_impl(fep_ctx* c, const double* hatp_h, double* xq_h
 
 extern "C" int fep_ctx_point_coords_host(fep_ctx* c, const double* hatp_h, double* xq_h) {
     FEP_GUARD(point_coords_host_impl(c, hatp_h, xq_h))
+}
+
+// ---- recovered-stress error indicator (fep.h): recover_stress_kernel, estimate_kernel; the statistics are fep_mesh.hip's ----
+extern "C" int fep_recover_stress_dev(fep_ctx* c, void* stream, const double* s_d, double* s_node_d) {
+    if (!c || !s_d || !s_node_d) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    if (c->n_n == 0) return FEP_OK;
+    hipLaunchKernelGGL(recover_stress_kernel, dim3(grid_for(c->n_n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, c->n_n, c->n_e,
+                       c->n_q, c->iptr, c->ilist, c->weight, s_d, s_node_d);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+extern "C" int fep_estimate_dev(fep_ctx* c, void* stream, const double* hatp_h, const double* s_d, const double* s_node_d,
+                                double* eta2_d, double* stats_d) {
+    if (!c || !s_d || !s_node_d || !eta2_d) return FEP_EINVAL;
+    if (c->elem_type != FEP_P1 && !hatp_h) return FEP_EINVAL;
+    if (!c->have_materials) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (stats_d) FEP_TRY(fep_indicator_reserve(c->device, st, c->n_e));
+    LoadTab tab{};                                      // travels as a kernel argument, as in fep_load_volume_dev
+    if (c->elem_type != FEP_P1)
+        for (int i = 0; i < c->n_p * c->n_q; ++i) tab.h[i] = hatp_h[i];
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using E = decltype(et);
+        hipLaunchKernelGGL((estimate_kernel<E::NP, E::NQ>), dim3(grid_for(c->n_e, kBlock)), dim3(kBlock), 0, st, c->n_e, c->n_n,
+                           c->elem, c->weight, c->shear, c->bulk, c->matu, tab, s_d, s_node_d, eta2_d);
+        HIP_TRY(hipGetLastError());
+        return FEP_OK;
+    }));
+    if (stats_d) FEP_TRY(fep_indicator_stats(c->device, st, c->n_e, eta2_d, stats_d));
+    return FEP_OK;
+}
+
+static int recover_stress_host_impl(fep_ctx* c, const double* s_h, double* s_node_h) {
+    if (!c || !s_h || !s_node_h) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(c->device));
+    fep_stage::Engine* E = nullptr;
+    FEP_TRY(fep_stage::engine(c->device, &E));
+    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
+    const size_t nb = (size_t)c->n_int * sizeof(double), nn = (size_t)c->n_n * sizeof(double);
+    void *s = nullptr, *o = nullptr;
+    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &s));
+    FEP_TRY(ctx_buf(c, 12, (int64_t)(4 * nn), &o));
+    FEP_TRY(E->h2d(s, s_h, 4 * nb));
+    FEP_TRY(fep_recover_stress_dev(c, E->stream, (const double*)s, (double*)o));
+    if (c->n_n > 0) FEP_TRY(E->d2h(s_node_h, o, 4 * nn));
+    return call.finish();
+}
+
+extern "C" int fep_recover_stress_host(fep_ctx* c, const double* s_h, double* s_node_h) {
+    FEP_GUARD(recover_stress_host_impl(c, s_h, s_node_h))
+}
+
+static int estimate_host_impl(fep_ctx* c, const double* hatp_h, const double* s_h, const double* s_node_h, double* eta2_h,
+                              double* stats_h) {
+    if (!c || !s_h || !s_node_h || !eta2_h) return FEP_EINVAL;
+    if (c->elem_type != FEP_P1 && !hatp_h) return FEP_EINVAL;
+    if (!c->have_materials) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(c->device));
+    fep_stage::Engine* E = nullptr;
+    FEP_TRY(fep_stage::engine(c->device, &E));
+    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
+    const size_t nb = (size_t)c->n_int * sizeof(double), nn = (size_t)c->n_n * sizeof(double);
+    void *s = nullptr, *sn = nullptr, *o = nullptr, *st = nullptr;
+    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &s));
+    FEP_TRY(ctx_buf(c, 12, (int64_t)(4 * nn), &sn));
+    FEP_TRY(ctx_buf(c, 13, c->n_e * (int64_t)sizeof(double), &o));
+    if (stats_h) FEP_TRY(ctx_buf(c, 14, 4 * (int64_t)sizeof(double), &st));
+    FEP_TRY(E->h2d(s, s_h, 4 * nb));
+    if (c->n_n > 0) FEP_TRY(E->h2d(sn, s_node_h, 4 * nn));
+    FEP_TRY(fep_estimate_dev(c, E->stream, hatp_h, (const double*)s, (const double*)sn, (double*)o, (double*)st));
+    FEP_TRY(E->d2h(eta2_h, o, (size_t)c->n_e * sizeof(double)));
+    if (stats_h) FEP_TRY(E->d2h(stats_h, st, 4 * sizeof(double)));
+    return call.finish();
+}
+
+extern "C" int fep_estimate_host(fep_ctx* c, const double* hatp_h, const double* s_h, const double* s_node_h, double* eta2_h,
+                                 double* stats_h) {
+    FEP_GUARD(estimate_host_impl(c, hatp_h, s_h, s_node_h, eta2_h, stats_h))
 }
 
 // Incidence of the loaded nodes, built per call (n_e_s is of the order of sqrt(n_e)), packed with the edge table into one

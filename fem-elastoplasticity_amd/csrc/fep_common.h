@@ -22,6 +22,10 @@ extern __attribute__((visibility("hidden"))) thread_local int fep_g_last_hip;   
     } while (0)
 
 __attribute__((visibility("hidden"))) int fep_set_device(int dev);
+// fep_mesh.hip, for fep_estimate_dev: the statistics {total, max, non-finite, n} of an indicator array, enqueued on `st`;
+// _reserve makes sure of their scratch beforehand (FEP_ESTATE if it would have to grow during a capture)
+__attribute__((visibility("hidden"))) int fep_indicator_reserve(int device, hipStream_t st, int64_t n);
+__attribute__((visibility("hidden"))) int fep_indicator_stats(int device, hipStream_t st, int64_t n, const double* eta2_d, double* stats_d);
 
 #include <stdint.h>
 static inline bool fep_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // NULL counts as aligned              // hipSetDevice with range check -> FEP_ENODEV

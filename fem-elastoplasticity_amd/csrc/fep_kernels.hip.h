@@ -1408,6 +1408,103 @@ point_coords_kernel(int64_t n_e, int64_t n_n, int n_p, int n_q, const int32_t* _
     xq[n_int + k] = y;
 }
 
+// ---- error indicator (fep.h, "recovered-stress error indicator"): every operation below in the order written there, no
+// contraction into fused multiply-adds, so that the NumPy twin (estimate.py) gives the same bits ----
+
+// Recovered nodal stress: weighted mean of the four stress rows over the points of a node's elements.  One lane per node over
+// the incidence lists, as nodal_average_kernel, with four accumulators and one shared sum of the weights.
+__global__ void __launch_bounds__(kBlock)
+recover_stress_kernel(int64_t n_n, int64_t n_e, int n_q, const int32_t* __restrict__ iptr, const int32_t* __restrict__ ilist,
+                      const double* __restrict__ weight, const double* __restrict__ s, double* __restrict__ s_node) {
+#pragma clang fp contract(off)
+    const int64_t n = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (n >= n_n) return;
+    const int64_t n_int = n_e * n_q;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, ws = 0.0;
+    for (int32_t t = iptr[n]; t < iptr[n + 1]; ++t) {
+        const int64_t k0 = ((int64_t)ilist[t] % n_e) * n_q;
+        for (int q = 0; q < n_q; ++q) {
+            const double w = weight[k0 + q];
+            a0 = a0 + w * s[k0 + q];
+            a1 = a1 + w * s[n_int + k0 + q];
+            a2 = a2 + w * s[2 * n_int + k0 + q];
+            a3 = a3 + w * s[3 * n_int + k0 + q];
+            ws = ws + w;
+        }
+    }
+    s_node[n] = a0 / ws;
+    s_node[n_n + n] = a1 / ws;
+    s_node[2 * n_n + n] = a2 / ws;
+    s_node[3 * n_n + n] = a3 / ws;
+}
+
+// c(d) = d : C^-1 : d of a stress difference d (rows 11, 22, 12, 33)
+__device__ __forceinline__ double est_cnorm(double d0, double d1, double d2, double d3, double G, double K) {
+#pragma clang fp contract(off)
+    const double tr = (d0 + d1) + d3;
+    const double m = tr / 3.0;
+    const double e0 = d0 - m, e1 = d1 - m, e3 = d3 - m;
+    const double dev = ((e0 * e0 + e1 * e1) + e3 * e3) + 2.0 * (d2 * d2);
+    return dev / (2.0 * G) + (tr * tr) / (9.0 * K);
+}
+
+// eta_e^2, one lane per element.  P1 (NQ == 1): the exact integral of the linear difference over the triangle; the other
+// types: their quadrature, the recovered stress interpolated with the basis values `tab` (staged in LDS).  A lane keeps the
+// NQ x 4 interpolated values in registers and walks the element's nodes once (a ascending for every point).
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock)
+estimate_kernel(int64_t n_e, int64_t n_n, const int32_t* __restrict__ elem, const double* __restrict__ weight,
+                const double* __restrict__ shear, const double* __restrict__ bulk, MatU mu, LoadTab tab,
+                const double* __restrict__ s, const double* __restrict__ s_node, double* __restrict__ eta2) {
+#pragma clang fp contract(off)
+    __shared__ double hat[NP * NQ];
+    if (NQ > 1) {
+        for (int i = threadIdx.x; i < NP * NQ; i += kBlock) hat[i] = tab.h[i];
+        __syncthreads();
+    }
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n_e) return;
+    const int64_t n_int = n_e * NQ;
+    if (NQ == 1) {
+        const double G = mu.on ? mu.shear : shear[e], K = mu.on ? mu.bulk : bulk[e];
+        double d[3][4], b[4];
+        for (int a = 0; a < 3; ++a) {
+            const int64_t nd = elem[(int64_t)a * n_e + e];
+            for (int i = 0; i < 4; ++i) d[a][i] = s_node[i * n_n + nd] - s[i * n_int + e];
+        }
+        for (int i = 0; i < 4; ++i) b[i] = ((d[0][i] + d[1][i]) + d[2][i]) / 3.0;
+        const double c0 = est_cnorm(d[0][0] - b[0], d[0][1] - b[1], d[0][2] - b[2], d[0][3] - b[3], G, K);
+        const double c1 = est_cnorm(d[1][0] - b[0], d[1][1] - b[1], d[1][2] - b[2], d[1][3] - b[3], G, K);
+        const double c2 = est_cnorm(d[2][0] - b[0], d[2][1] - b[1], d[2][2] - b[2], d[2][3] - b[3], G, K);
+        eta2[e] = weight[e] * (est_cnorm(b[0], b[1], b[2], b[3], G, K) + ((c0 + c1) + c2) / 12.0);
+        return;
+    }
+    double r[NQ][4];
+    for (int q = 0; q < NQ; ++q)
+        for (int i = 0; i < 4; ++i) r[q][i] = 0.0;
+    for (int a = 0; a < NP; ++a) {
+        const int64_t nd = elem[(int64_t)a * n_e + e];
+        const double v0 = s_node[nd], v1 = s_node[n_n + nd], v2 = s_node[2 * n_n + nd], v3 = s_node[3 * n_n + nd];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const double h = hat[a * NQ + q];
+            r[q][0] = r[q][0] + h * v0;
+            r[q][1] = r[q][1] + h * v1;
+            r[q][2] = r[q][2] + h * v2;
+            r[q][3] = r[q][3] + h * v3;
+        }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int64_t k = e * NQ + q;
+        const double G = mu.on ? mu.shear : shear[k], K = mu.on ? mu.bulk : bulk[k];
+        acc = acc + weight[k] * est_cnorm(r[q][0] - s[k], r[q][1] - s[n_int + k], r[q][2] - s[2 * n_int + k],
+                                          r[q][3] - s[3 * n_int + k], G, K);
+    }
+    eta2[e] = acc;
+}
+
 // Traction load over boundary edges (EL:295-364 with the full arc-length Jacobian and a value per surface point).
 // One lane per loaded node b: node id bnode[b], its (edge, local node) codes a * n_e_s + e in blist[bptr[b] .. bptr[b + 1])
 // ordered by (e, a).  f_out is zeroed by the caller beforehand.

@@ -9,6 +9,9 @@
 //
 // Edge k of an element runs from vertex k to vertex (k + 1) % 3.  P2 visits the edges in the order 1, 2, 0 (slots V2V3, V3V1,
 // V1V2: TSX:1530, 1561, 1591), P4 in the order 0, 1, 2 (TSX:1386, 1424, 1463).
+//
+// Also here, because it is context-free and produces what fep_mesh_mark reads: the fixed-order sums, the statistics and the
+// bulk marking of the error indicator (include/fep.h, "recovered-stress error indicator"; ind_level_kernel, fep_mark_bulk_*).
 #include "fep_common.h"
 
 #include <cmath>
@@ -656,6 +659,92 @@ __global__ void __launch_bounds__(kBlock) area_final_kernel(int n_part, const do
     }
 }
 
+// ---- error indicator: fixed-order sums, statistics and bulk marking (include/fep.h, "recovered-stress error indicator") ----
+// T(v): in every block of kBlock consecutive values x[i] = x[i] + x[i + s] for s = 128, 64, ..., 1 (i < s), then T of the block
+// sums.  One launch per level; the workgroup that finds itself alone on its level finishes the pass.  A pass carries three
+// values per block: the tree sum, the maximum and a count (a tree sum of small integers, exact in any order).
+struct IndState {                                            // one per (device, stream), at the head of the scratch
+    unsigned long long cand;                                 // bits of the largest t found so far with tail(t) >= goal
+    double total, vmax, goal;
+};
+enum { kIndStats = 0, kIndTrial = 1, kIndFinal = 2 };
+
+__device__ __forceinline__ void ind_tree(double* __restrict__ l_sum, double* __restrict__ l_max, double* __restrict__ l_cnt) {
+    for (int d = kBlock / 2; d > 0; d /= 2) {
+        __syncthreads();
+        if (threadIdx.x < (unsigned)d) {
+            const double o = l_max[threadIdx.x + d];
+            l_sum[threadIdx.x] = l_sum[threadIdx.x] + l_sum[threadIdx.x + d];
+            l_max[threadIdx.x] = o > l_max[threadIdx.x] ? o : l_max[threadIdx.x];
+            l_cnt[threadIdx.x] = l_cnt[threadIdx.x] + l_cnt[threadIdx.x + d];
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double ind_threshold(const IndState* __restrict__ state, int mode, int bit) {
+    if (mode == kIndTrial) return __longlong_as_double((long long)(state->cand | (1ull << bit)));
+    return state->total > 0 ? __longlong_as_double((long long)state->cand) : INFINITY;        // kIndFinal: t*
+}
+
+// kLeaf: the values come from eta2 (filtered as the mode says); else from the partials of the level below.
+template <bool kLeaf>
+__global__ void __launch_bounds__(kBlock) ind_level_kernel(int64_t n, const double* __restrict__ eta2, const double* __restrict__ in,
+                                                           int64_t n_in, int mode, int bit, double theta, IndState* __restrict__ state,
+                                                           uint8_t* __restrict__ marked, double* __restrict__ part,
+                                                           double* __restrict__ stats, double* __restrict__ out) {
+    __shared__ double l_sum[kBlock], l_max[kBlock], l_cnt[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double v = 0.0, mx = 0.0, cnt = 0.0;                     // the padding
+    if (kLeaf) {
+        if (i < n) {
+            const double x = eta2[i];
+            const bool fin = x - x == 0.0;                   // false for NaN and both infinities
+            if (mode == kIndStats) {
+                v = fin ? x : 0.0;
+                mx = v > 0.0 ? v : 0.0;
+                cnt = fin ? 0.0 : 1.0;
+            } else {
+                const bool keep = fin && x >= ind_threshold(state, mode, bit);
+                v = keep ? x : 0.0;
+                if (mode == kIndFinal) {
+                    const bool mk = keep && x > 0.0;
+                    marked[i] = mk ? 1 : 0;
+                    cnt = mk ? 1.0 : 0.0;
+                }
+            }
+        }
+    } else if (i < n_in) {
+        v = in[i];
+        mx = in[n_in + i];
+        cnt = in[2 * n_in + i];
+    }
+    l_sum[threadIdx.x] = v;
+    l_max[threadIdx.x] = mx;
+    l_cnt[threadIdx.x] = cnt;
+    ind_tree(l_sum, l_max, l_cnt);
+    if (threadIdx.x != 0) return;
+    if (gridDim.x > 1) {
+        part[blockIdx.x] = l_sum[0];
+        part[gridDim.x + blockIdx.x] = l_max[0];
+        part[2 * gridDim.x + blockIdx.x] = l_cnt[0];
+        return;
+    }
+    const double sum = l_sum[0];
+    if (mode == kIndStats) {
+        if (stats) { stats[0] = sum; stats[1] = l_max[0]; stats[2] = l_cnt[0]; stats[3] = (double)n; }
+        if (state) { state->cand = 0; state->total = sum; state->vmax = l_max[0]; state->goal = theta * sum; }
+    } else if (mode == kIndTrial) {
+        const unsigned long long t = state->cand | (1ull << bit);
+        if (state->total > 0 && t <= (unsigned long long)__double_as_longlong(state->vmax) && sum >= state->goal) state->cand = t;
+    } else {
+        out[0] = ind_threshold(state, kIndFinal, 0);
+        out[1] = sum;
+        out[2] = l_cnt[0];
+        out[3] = state->total;
+    }
+}
+
 struct DeviceBlocks {
     std::vector<void*> p;
     ~DeviceBlocks() { for (void* q : p) (void)hipFree(q); }
@@ -944,6 +1033,102 @@ static int area_stats_impl(int device_id, hipStream_t st, int64_t n_e, int64_t n
     return FEP_OK;
 }
 
+// Scratch of the indicator's passes: IndState, then three partials per block of every level above the leaves.  One grow-only
+// block per (device, stream), by the rule of the return map's counter scratch: growing is an allocation, refused
+// (FEP_ESTATE) while the stream is being captured, and a block handed out is never freed.
+constexpr int64_t kIndHead = 8;                             // doubles reserved for IndState
+static int64_t ind_scratch_len(int64_t n) {
+    int64_t len = kIndHead;
+    for (int64_t nb = (n + kBlock - 1) / kBlock; nb > 1; nb = (nb + kBlock - 1) / kBlock) len += 3 * nb;
+    return len;
+}
+
+static int ind_scratch(int device, hipStream_t st, int64_t n, double** out) {
+    static std::mutex m;
+    static auto& bufs = *new std::map<std::pair<int, void*>, std::pair<double*, int64_t>>();
+    const int64_t len = ind_scratch_len(n);
+    std::lock_guard<std::mutex> g(m);
+    auto& b = bufs[{device, (void*)st}];
+    if (b.second < len) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
+        double* p = nullptr;
+        const int64_t cap = len + len / 4;
+        HIP_TRY(hipMalloc((void**)&p, (size_t)cap * sizeof(double)));
+        b = {p, cap};                                        // the smaller block stays allocated: captured graphs may name it
+    }
+    *out = b.first;
+    return FEP_OK;
+}
+
+// One pass over eta2: the leaves, then one launch per level until a single workgroup is left, which finishes the pass.
+static int ind_pass(hipStream_t st, int64_t n, const double* eta2, int mode, int bit, double theta, double* scratch, bool use_state,
+                    uint8_t* marked, double* stats, double* out) {
+    IndState* state = use_state ? (IndState*)scratch : nullptr;
+    double* part = scratch + kIndHead;
+    int64_t nb = (n + kBlock - 1) / kBlock;
+    if (nb < 1) nb = 1;
+    hipLaunchKernelGGL(ind_level_kernel<true>, dim3((unsigned)nb), dim3(kBlock), 0, st, n, eta2, (const double*)nullptr, (int64_t)0,
+                       mode, bit, theta, state, marked, part, stats, out);
+    HIP_TRY(hipGetLastError());
+    while (nb > 1) {
+        const int64_t nb_up = (nb + kBlock - 1) / kBlock;
+        double* part_up = part + 3 * nb;
+        hipLaunchKernelGGL(ind_level_kernel<false>, dim3((unsigned)nb_up), dim3(kBlock), 0, st, n, (const double*)nullptr,
+                           (const double*)part, nb, mode, bit, theta, state, (uint8_t*)nullptr, part_up, stats, out);
+        HIP_TRY(hipGetLastError());
+        part = part_up;
+        nb = nb_up;
+    }
+    return FEP_OK;
+}
+
+// fep_api.hip's fep_estimate_dev: `reserve` before its own kernel (a refusal writes nothing), `stats` after it
+__attribute__((visibility("hidden"))) int fep_indicator_reserve(int device, hipStream_t st, int64_t n) {
+    double* scratch = nullptr;
+    return ind_scratch(device, st, n, &scratch);
+}
+
+__attribute__((visibility("hidden"))) int fep_indicator_stats(int device, hipStream_t st, int64_t n, const double* eta2_d,
+                                                              double* stats_d) {
+    double* scratch = nullptr;
+    FEP_TRY(ind_scratch(device, st, n, &scratch));
+    return ind_pass(st, n, eta2_d, kIndStats, 0, 0.0, scratch, false, nullptr, stats_d, nullptr);
+}
+
+constexpr int kIndValueBits = 63;                           // trial passes of the descent: the bits of a non-negative double
+
+static int mark_bulk_impl(int device_id, hipStream_t st, int64_t n, const double* eta2, double theta, uint8_t* marked, double* out) {
+    if (n < 0 || !out || (n > 0 && (!eta2 || !marked)) || !(theta > 0.0 && theta <= 1.0)) return FEP_EINVAL;
+    if (n >= (int64_t)INT32_MAX * kBlock) return FEP_ERANGE;
+    FEP_TRY(fep_set_device(device_id));
+    double* scratch = nullptr;
+    FEP_TRY(ind_scratch(device_id, st, n, &scratch));
+    FEP_TRY(ind_pass(st, n, eta2, kIndStats, 0, theta, scratch, true, nullptr, nullptr, nullptr));
+    if (n > 0)
+        for (int bit = kIndValueBits - 1; bit >= 0; --bit)
+            FEP_TRY(ind_pass(st, n, eta2, kIndTrial, bit, theta, scratch, true, nullptr, nullptr, nullptr));
+    return ind_pass(st, n, eta2, kIndFinal, 0, theta, scratch, true, marked, nullptr, out);
+}
+
+static int mark_bulk_host_impl(int device_id, int64_t n, const double* eta2_h, double theta, uint8_t* marked_h, double* out_h) {
+    if (n < 0 || !out_h || (n > 0 && (!eta2_h || !marked_h)) || !(theta > 0.0 && theta <= 1.0)) return FEP_EINVAL;
+    FEP_TRY(fep_set_device(device_id));
+    DeviceBlocks tmp;
+    double *eta2 = nullptr, *out = nullptr;
+    uint8_t* marked = nullptr;
+    FEP_TRY(tmp.get(&eta2, n));
+    FEP_TRY(tmp.get(&marked, n));
+    FEP_TRY(tmp.get(&out, 4));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(eta2, eta2_h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    FEP_TRY(mark_bulk_impl(device_id, nullptr, n, eta2, theta, marked, out));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(marked_h, marked, (size_t)n, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(out_h, out, 4 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return FEP_OK;
+}
+
 // host forms: device outputs of this call, copied back, released on every exit
 template <class T>
 static int fetch(T* dst_h, const T* src_d, int64_t count) {
@@ -1120,4 +1305,13 @@ extern "C" int fep_mesh_area_stats_dev(int device_id, void* stream, int64_t n_e,
 extern "C" int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
                                         double* out_h) {
     FEP_GUARD(area_stats_host_impl(device_id, n_e, n_n, elem_h, coord_h, out_h))
+}
+
+extern "C" int fep_mark_bulk_dev(int device_id, void* stream, int64_t n, const double* eta2_d, double theta, uint8_t* marked_d,
+                                 double* out_d) {
+    FEP_GUARD(mark_bulk_impl(device_id, (hipStream_t)stream, n, eta2_d, theta, marked_d, out_d))
+}
+
+extern "C" int fep_mark_bulk_host(int device_id, int64_t n, const double* eta2_h, double theta, uint8_t* marked_h, double* out_h) {
+    FEP_GUARD(mark_bulk_host_impl(device_id, n, eta2_h, theta, marked_h, out_h))
 }

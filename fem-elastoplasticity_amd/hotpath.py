@@ -490,6 +490,58 @@ class MeshContext:
     def transform_dev(self, stream, q_int, q_node):
         _lib.check(_lib.lib().fep_transform_dev(self._h, stream, q_int, q_node), 'fep_transform_dev')
 
+    # -- recovered-stress error indicator (include/fep.h; the NumPy twin is estimate.py)
+    def recover_stress(self, s):
+        """Recovered nodal stress of the point stress `s` (4, n_int) -> (4, n_n) ndarray (fep_recover_stress_host)."""
+        sv = _f64(s, (4, self.n_int))
+        out = np.empty((4, self.n_n))
+        _lib.check(_lib.lib().fep_recover_stress_host(self._h, _lib.ptr(sv), _lib.ptr(out)), 'fep_recover_stress_host')
+        return out
+
+    def estimate(self, s, hatp=None):
+        """The indicator of the point stress `s` (4, n_int): {'eta2' (n_e,), 'total' (their fixed-order sum), 'max',
+        'n_nonfinite', 's_node' (4, n_n)} (fep_recover_stress_host, fep_estimate_host).  `hatp` as in load_volume."""
+        sv = _f64(s, (4, self.n_int))
+        sn = self.recover_stress(sv)
+        eta2, stats = np.empty(self.n_e), np.empty(4)
+        _lib.check(_lib.lib().fep_estimate_host(self._h, _lib.ptr(self._hatp(hatp)), _lib.ptr(sv), _lib.ptr(sn), _lib.ptr(eta2),
+                                                _lib.ptr(stats)), 'fep_estimate_host')
+        return {'eta2': eta2, 'total': float(stats[0]), 'max': float(stats[1]), 'n_nonfinite': int(stats[2]), 's_node': sn}
+
+    def _torch_stream(self):
+        import torch
+        return torch, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def recover_stress_dev(self, s, out=None):
+        """The same on a float64 torch tensor `s` (4, n_int) of the context's GPU, on the current stream -> a (4, n_n) tensor
+        (`out`, or a new one).  Only enqueues one kernel."""
+        torch, stream = self._torch_stream()
+        if s.dtype != torch.float64 or tuple(s.shape) != (4, self.n_int) or not s.is_contiguous():
+            raise ValueError(f's must be a contiguous float64 tensor of (4, {self.n_int})')
+        if out is None:
+            out = torch.empty((4, self.n_n), dtype=torch.float64, device=s.device)
+        _lib.check(_lib.lib().fep_recover_stress_dev(self._h, stream, C.c_void_p(s.data_ptr()), C.c_void_p(out.data_ptr())),
+                   'fep_recover_stress_dev')
+        return out
+
+    def estimate_dev(self, s, s_node=None, hatp=None, stats=True):
+        """Device-resident indicator of the tensor `s` (4, n_int) -> (eta2 (n_e,), stats (4,) = [total, max, n_nonfinite, n_e]
+        or None, s_node (4, n_n)), float64 tensors written on the current stream; nothing is read back or synchronised.
+        `s_node`: the recovered stress if the caller already has it."""
+        torch, stream = self._torch_stream()
+        if s_node is None:
+            s_node = self.recover_stress_dev(s)
+        elif s_node.dtype != torch.float64 or tuple(s_node.shape) != (4, self.n_n) or not s_node.is_contiguous():
+            raise ValueError(f's_node must be a contiguous float64 tensor of (4, {self.n_n})')
+        if s.dtype != torch.float64 or tuple(s.shape) != (4, self.n_int) or not s.is_contiguous():
+            raise ValueError(f's must be a contiguous float64 tensor of (4, {self.n_int})')
+        eta2 = torch.empty(self.n_e, dtype=torch.float64, device=s.device)
+        st = torch.empty(4, dtype=torch.float64, device=s.device) if stats else None
+        _lib.check(_lib.lib().fep_estimate_dev(self._h, stream, _lib.ptr(self._hatp(hatp)), C.c_void_p(s.data_ptr()),
+                                               C.c_void_p(s_node.data_ptr()), C.c_void_p(eta2.data_ptr()),
+                                               None if st is None else C.c_void_p(st.data_ptr())), 'fep_estimate_dev')
+        return eta2, st, s_node
+
     # -- external loads (EL:246-292)
     def _hatp(self, hatp):
         if hatp is None:

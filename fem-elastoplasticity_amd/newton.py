@@ -35,7 +35,8 @@ import scipy.sparse.linalg as sspl
 
 from .hotpath import MeshContext, in_situ_strain
 from .mesh import square_mesh
-from .tables import ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables
+from .tables import (ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables, get_local_basis_volume,
+                     get_quadrature_volume)
 
 
 def point_sums(q_int, elements, weight, n_n=None):
@@ -116,6 +117,18 @@ class _HostOps:
 
     def count(self, flags):
         return int(self.host(flags).astype(bool).sum())
+
+    def estimate(self, s, p):
+        """The error indicator of the point stress `s` on the problem `p` (_tsx_setup): on the context's GPU, or — a context
+        without `estimate`, a `context_factory`'s — with the NumPy twin.  {'eta2', 'total', 'max', 'n_nonfinite'}."""
+        s = np.ascontiguousarray(self.host(s), dtype=np.float64)
+        if hasattr(self.ctx, 'estimate'):
+            r = self.ctx.estimate(s)
+        else:
+            from .estimate import estimate_np
+            hatp = get_local_basis_volume(p['type'], get_quadrature_volume(p['type'])[0])[0]
+            r = estimate_np(p['elem'], self.ctx.geometry()[2], p['materials'][0], p['materials'][1], hatp, s, p['coords'].shape[1])
+        return {k: r[k] for k in ('eta2', 'total', 'max', 'n_nonfinite')}
 
     def close(self):
         pass
@@ -238,6 +251,13 @@ class _DeviceOps:
         f = self.zeros()
         self.ctx.load_volume_dev(self._stream(), f.data_ptr(), uniform=uniform)
         return f
+
+    def estimate(self, s, p):
+        """The error indicator of the device-resident point stress `s`: recovery, indicator and statistics on the device, read
+        back once.  {'eta2', 'total', 'max', 'n_nonfinite'}."""
+        eta2, st, _ = self.ctx.estimate_dev(s.contiguous())
+        st = st.cpu()
+        return {'eta2': eta2.cpu().numpy(), 'total': float(st[0]), 'max': float(st[1]), 'n_nonfinite': int(st[2])}
 
     def close(self):
         self.solver.close()
@@ -471,7 +491,7 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
                      pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None, in_situ=None,
-                     body_force=None, materials=None, adapt=0, mark=None):
+                     body_force=None, materials=None, adapt=0, mark=None, theta=0.5):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
@@ -500,7 +520,12 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     `curves`), renumbered again with `renumber`, raised to `element_type`, and the next run starts from zero on it (this
     driver carries no plastic strain from step to step, so there is no state to transfer).  `mark`: None — mark_plastic of
     the last accepted step's flags with one ring of neighbours — or a callable (hist, coords, elem_p1) -> bool (n_e) on the
-    P1 vertex mesh the run was solved on.  `refine` is applied first, once; `in_situ` is evaluated again on every mesh;
+    P1 vertex mesh the run was solved on — or 'zz': the recovered-stress error indicator of the last accepted step's stress
+    (MeshContext.estimate on the context's GPU, estimate.estimate_np under a `context_factory`) with bulk marking of the
+    fraction `theta` of its total (estimate.mark_bulk; the element ids of a P2 / P4 mesh are those of its P1 vertex mesh, so
+    the indicator marks that directly).  Every row of 'adapt' then also holds 'eta' (the square root of the indicator's total),
+    'n_nonfinite', 'theta' and 'eta2' (the indicator per element), and a non-finite indicator raises ValueError.
+    `refine` is applied first, once; `in_situ` is evaluated again on every mesh;
     `materials` given as arrays raise ValueError (there is no parent-to-child rule for them yet).  The result is the last
     run's history — 'coords', 'elem', 'node_of_input' included — plus 'adapt': per run {'n_e', 'n_n', 'n_marked', 'n_child',
     'displ' (the last monitored value), 'n_steps' (accepted load steps), 'n_plast' (at the end), 'plastic' (elements with a plastic point at the end), 'marked', 'parent' (of the
@@ -510,7 +535,7 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
         raise ValueError('body_force goes with in_situ (the stress field it is in equilibrium with)')
     if adapt:
         return _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves,
-                             int(adapt), mark, materials,
+                             int(adapt), mark, theta, materials,
                              dict(n_load_steps=n_load_steps, linear_solver=linear_solver, pcg_rtol=pcg_rtol, pcg_forcing=pcg_forcing,
                                   pcg_forcing_cap=pcg_forcing_cap, pcg_inexact_rtol=pcg_inexact_rtol, in_situ=in_situ,
                                   body_force=body_force))
@@ -536,14 +561,20 @@ def _tsx_run(p, device, context_factory, log, materials, n_load_steps, linear_so
 
 
 def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves, adapt,
-                  mark, materials, run_kw):
+                  mark, theta, materials, run_kw):
     """solve_tsx_tunnel(adapt > 0): solve, mark, refine the marked elements, again."""
     from .hotpath import default_device
     from .mesh import renumber_for_locality
     from .meshio import load_tsx_mesh
+    from .estimate import _check_theta, mark_bulk
     from .midpoints import create_midpoints, mark_plastic, refine_marked, refine_uniform
     if adapt < 0:
         raise ValueError('adapt must be >= 0')
+    zz = isinstance(mark, str)
+    if zz and mark != 'zz':
+        raise ValueError(f"mark: None, a callable or 'zz', got {mark!r}")
+    if zz:
+        theta = _check_theta(theta)
     if materials is not None and any(np.ndim(m) > 0 for m in materials):
         raise ValueError('adapt: materials per integration point have no parent-to-child rule yet; pass scalars')
     t = _coerce(element_type)
@@ -572,18 +603,27 @@ def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monito
             ck, ek = np.asarray(ext['coord_ext'], dtype=np.float64), np.asarray(ext['elem_ext'], dtype=np.int64)
         p = _tsx_setup(ck, ek, t, None, 0, False, (monitor[0], int(input_ids[monitor[1]])), device, context_factory, log, curves)
         p['prepared'], p['node_of_input'], p['keep_flags'] = True, (input_ids.copy() if renumber else None), True
+        p['estimate'] = zz
         hist = _tsx_run(p, device, context_factory, log, materials, **run_kw)
         flags = hist.pop('ind_p')
+        est = hist.pop('estimate', None)
         row = {'n_e': int(ek.shape[1]), 'n_n': int(ck.shape[1]), 'n_marked': None, 'n_child': None, 'displ': hist['displ'][-1],
                'n_steps': len(hist['zeta']), 'n_plast': hist['n_plast'][-1],
                'plastic': mark_plastic(flags, e1, n_q, rings=0), 'marked': None, 'parent': None,
                'ind_p': flags, 'coords': ck, 'elem': ek}
+        if zz:
+            row.update(eta=float(np.sqrt(est['total'])), n_nonfinite=est['n_nonfinite'], theta=theta, eta2=est['eta2'])
         rounds.append(row)
         if log:
             log(f'adapt {k}: {row["n_e"]} elements, {row["n_n"]} nodes, U{monitor}={row["displ"]:.16g}')
         if k == adapt:
             break
-        marked = mark_plastic(flags, e1, n_q, rings=1) if mark is None else np.asarray(mark(hist, c1, e1)) != 0
+        if zz:
+            if est['n_nonfinite']:
+                raise ValueError(f"adapt {k}: {est['n_nonfinite']} of {e1.shape[1]} error indicators are not finite")
+            marked = np.asarray(mark_bulk(est['eta2'], theta, device=mesh_device)[0], dtype=bool)
+        else:
+            marked = mark_plastic(flags, e1, n_q, rings=1) if mark is None else np.asarray(mark(hist, c1, e1)) != 0
         if marked.shape != (e1.shape[1],):
             raise ValueError(f'mark: one entry per element ({e1.shape[1]},), got {marked.shape}')
         c1, e1, parent = refine_marked(c1, e1, marked, device=mesh_device, curves=curves)
@@ -676,6 +716,7 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=
     d_zeta = 1 / n_load_steps                                                             # TSX:1730-1735
     U_elast = ops.solve(K, -F0)                                                           # TSX:1748
     hist = {'zeta': [], 'displ': [], 'n_plast': [], 'U': [], 'n_calls': 0}
+    kept = {}
 
     def accepted(r, zeta, U, Ep_old, its, criterion):
         Um = ops.host(U).reshape((2, -1), order='F')
@@ -683,6 +724,8 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=
         hist['n_plast'].append(ops.count(r['ind_p']))
         if p.get('keep_flags'):                                      # the adaptive driver marks from the last accepted step
             hist['ind_p'] = np.asarray(ops.host(r['ind_p'])).astype(bool).ravel()
+        if p.get('estimate'):                                        # ... or from its stress (the ops' own array: not copied)
+            kept['s'] = r['s']
         hist['U'].append(Um.copy())
         if field is not None:
             hist['s'].append(np.array(ops.host(r['s'])))
@@ -693,7 +736,8 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=
     # the accepting call leaves apply_plastic_strain False (C7)
     if field is None:
         _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist, e0_of=lambda zeta: zeta * init_strain,
-                        accept_kw=dict(want=('ind_p',)), accepted=accepted, finished=lambda zeta_old: zeta_old >= 1)  # TSX:1824
+                        accept_kw=dict(want=('s', 'ind_p') if p.get('estimate') else ('ind_p',)), accepted=accepted,
+                        finished=lambda zeta_old: zeta_old >= 1)                                                     # TSX:1824
     else:
         hist['s'], hist['s0_field'] = [], s0_field
         _load_step_loop(ops, K, d_zeta * U_elast, d_zeta, d_zeta / 10, hist,
@@ -704,6 +748,8 @@ def _tsx_tunnel(p, ctx, ops, clock, n_load_steps, log, in_situ=None, body_force=
     hist['Q'] = p['Q']
     hist['pcg_iters'] = ops.pcg_iters
     hist['t_setup'] = t_setup
+    if p.get('estimate'):
+        hist['estimate'] = ops.estimate(kept['s'], p)
     if p['prepared']:
         hist['coords'], hist['elem'], hist['node_of_input'] = coords, p['elem'], p['node_of_input']
     return hist

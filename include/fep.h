@@ -30,7 +30,7 @@
  *
  * Stream contract of the *_host entry points that move the caller's arrays through the staging engine
  * (fep_return_map_host / _vm_host / _mc_host / _vmps_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
- * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host; not the fep_mesh_* and fep_load_traction_host forms):
+ * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host, fep_recover_stress_host, fep_estimate_host; not the fep_mesh_* and fep_load_traction_host forms):
  *   - each call runs its copies and its kernels on ONE non-blocking stream per device that belongs to the library; that stream
  *     is ordered against nothing else: not the default stream, not a stream the caller passed to a *_dev call;
  *   - calls of all host threads on one device are serialised by a lock, and a call returns only after synchronising that
@@ -656,6 +656,68 @@ int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int3
 int fep_mesh_mark(fep_mesh* mesh, void* stream, const uint8_t* marked, int on_device, int64_t out[4]);
 int fep_mesh_refine_marked_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d, int32_t* parent_d);
 int fep_mesh_refine_marked_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h);
+
+/* ---- recovered-stress error indicator and bulk marking: what decides the marks of fep_mesh_mark ----------------------
+ * No reference counterpart.  Opt-in: without these calls every output above is byte for byte what it was.  Zienkiewicz-Zhu:
+ * the step's stress s ((4, n_int), rows 11, 22, 12, 33) is averaged to the nodes, and the indicator of an element is the
+ * complementary-energy norm of (recovered - computed) over it.  Every operation below is one IEEE double operation in the
+ * order written (parentheses bind, otherwise left to right), nothing is contracted into a fused multiply-add, and there are no
+ * floating-point atomics: two calls give the same bytes, and so does the NumPy twin estimate.py.
+ *
+ *   recovery    s_node (4, n_n) planar.  For node n, with a0..a3 = ws = 0.0: for each entry of the node's incidence list in
+ *               ascending (element, local node) order, for q = 0 .. n_q - 1, k = e n_q + q, w = weight[k] (the context's
+ *               |det J| * wf, as in fep_transform_*):  a_i = a_i + w * s[i, k] (i = 0..3),  ws = ws + w.
+ *               s_node[i, n] = a_i / ws.  A node of no element gets 0/0 = NaN, as fep_transform_* gives (a NaN is a NaN: its
+ *               sign bit is the machine's, the one thing in which the twin's bytes may differ).
+ *   norm        for a 4-vector d and moduli G, K:  tr = (d0 + d1) + d3,  m = tr / 3,  e_i = d_i - m (i = 0, 1, 3),
+ *               c(d) = (((e0 e0 + e1 e1) + e3 e3) + 2 (d2 d2)) / (2 G) + (tr tr) / (9 K)        (= d : C^-1 : d)
+ *               It serves plane strain and plane stress (s33 = 0) alike: the indicator does not depend on the context's
+ *               model.  G, K are the context's shear and bulk at the point (or its constants: the same bits).
+ *   P1          one point per element, s constant, weight[e] the area; V_a the vertices, i = 0..3:
+ *               d_a[i] = s_node[i, V_a] - s[i, e],   b[i] = ((d_0[i] + d_1[i]) + d_2[i]) / 3,
+ *               eta2[e] = weight[e] * (c(b) + ((c(d_0 - b) + c(d_1 - b)) + c(d_2 - b)) / 12)
+ *               — the exact integral of the linear difference, not the one-point rule.
+ *   P2 Q1 Q2 P4 r_q[i] = 0.0, then for a = 0 .. n_p - 1:  r_q[i] = r_q[i] + hatp[a, q] * s_node[i, elements[a, e]];
+ *               acc = 0.0, then for q = 0 .. n_q - 1, k = e n_q + q:  acc = acc + weight[k] * c(r_q - s[:, k]);  eta2[e] = acc.
+ *               hatp_h: the (n_p, n_q) basis-function VALUES on the host, as in fep_load_volume_* (a kernel argument).
+ *   T(v)        the fixed-order sum of n values: pad v with +0.0 to a multiple of 256; in every block of 256 consecutive values,
+ *               for s = 128, 64, ..., 1:  x[i] = x[i] + x[i + s] for i < s; the block's sum is x[0]; T(v) = T(block sums), until
+ *               one value is left (T of nothing is +0.0).  One launch per level.
+ *   stats       v_e = eta2[e] where that is finite, else +0.0.  stats = {T(v), the largest positive v_e (+0.0 if there is
+ *               none), the number of non-finite eta2[e], n_e}.
+ *   marking     for eta2 (n) and theta in (0, 1]:  total = T(v),  goal = theta * total,
+ *               tail(t) = T(v_e where eta2[e] is finite and >= t, else +0.0).  If total > 0, t* is the largest double
+ *               t <= max (of stats) with tail(t) >= goal, else t* = +inf.  marked[e] = 1 iff eta2[e] is finite, > 0 and >= t*, else 0.
+ *               Rounding is monotone and the tree is the same for every t, so tail never increases with t: t* exists, is one
+ *               of the values and does not depend on how it is looked for, and all values tied at t* are marked, so the set
+ *               depends on no ordering.  The library walks the 63 value bits of t from the top, one pass over eta2 per bit
+ *               (a bit stays set if the candidate is <= max and its tail >= goal), every decision taken on the device.
+ *               out = {t*, tail(t*), number marked, total}.
+ * Non-finite values (the four rules of fep_return_map_*): a NaN or an infinity in s at one point makes eta2 non-finite for
+ * exactly the elements that share a node with that point's element; it stays in eta2 and is counted in stats[2], enters no
+ * sum and is never marked; every other eta2, and the marks among the finite values, are bit for bit those of the clean call
+ * wherever the poisoned elements contribute nothing to them; a clean call afterwards returns the same bytes as before.
+ *
+ *   fep_recover_stress_*  s (4, n_int) -> s_node (4, n_n).  One lane per node.  The _dev form enqueues one kernel.
+ *   fep_estimate_*        s, s_node (of fep_recover_stress_*; an input in both forms) -> eta2 (n_e); stats (4 doubles) may be
+ *                         NULL; hatp_h is ignored for P1.  One lane per element.  FEP_ESTATE: materials not set.
+ *   fep_mark_bulk_*       context-free.  marked (n bytes) is what fep_mesh_mark(..., on_device = 1) takes.  n = 0 is legal:
+ *                         out = {+inf, 0, 0, 0}.  63 + 2 passes of 1 + (levels above the leaves) launches.
+ * The _dev forms only enqueue: no read-back, no synchronisation.  The partials of the tree levels and the descent's state
+ * live in one grow-only block per (device, stream), by the rule of counts_d (fep_return_map_dev): FEP_ESTATE if it would have
+ * to grow while the stream is being captured (fep_estimate_dev with stats, fep_mark_bulk_dev; run the call once outside the
+ * capture first).  FEP_EINVAL: NULL pointers (hatp_h for any type but P1), n < 0, theta outside (0, 1] or NaN; FEP_ERANGE:
+ * n of 2^39 or more.  A refused call writes nothing.  The _host forms are synchronous; the two context forms follow the stream
+ * contract of fep_transform_host. */
+int fep_recover_stress_dev(fep_ctx* ctx, void* stream, const double* s_d, double* s_node_d);
+int fep_recover_stress_host(fep_ctx* ctx, const double* s_h, double* s_node_h);
+int fep_estimate_dev(fep_ctx* ctx, void* stream, const double* hatp_h, const double* s_d, const double* s_node_d,
+                     double* eta2_d, double* stats_d);
+int fep_estimate_host(fep_ctx* ctx, const double* hatp_h, const double* s_h, const double* s_node_h, double* eta2_h,
+                      double* stats_h);
+int fep_mark_bulk_dev(int device_id, void* stream, int64_t n, const double* eta2_d, double theta, uint8_t* marked_d,
+                      double* out_d);
+int fep_mark_bulk_host(int device_id, int64_t n, const double* eta2_h, double theta, uint8_t* marked_h, double* out_h);
 
 /* Linear solve of a Newton iterate, K[Q][:,Q] dU[Q] = b[Q]  (np.linalg.solve on the dense boolean-masked block at
  * DP:1062-1066 / TSX:1781).  Preconditioned conjugate gradients (2x2 node-block Jacobi) entirely on

@@ -23,6 +23,11 @@ device-resident with HIP events, fep_mesh_mark (closure, scans; it synchronises)
 displacement U[0, 40] of the P1 tunnel run unrefined, with adapt=2 and with refine=2 (direct solver).  Key 'marked';
 profiles/mesh_bench_marked.json unless `--out` says otherwise.
 
+`--estimate` (meant for `--refine 5`: 908 288 triangles) runs nothing of the above: it times the error indicator — recovery,
+indicator, statistics, bulk marking — resident on the device (HIP events) against its NumPy twin in the same process, checks
+that they agree bit for bit, and records next to each time the bytes the pass has to move (s, the node gathers, 8 B per
+element per tail pass) and the launches the marking took.  Key 'estimate'; profiles/estimate_bench.json unless `--out`.
+
 `--solve R` adds the end-to-end TSX run solve_tsx_tunnel(refine=R, 'P1', linear_solver='amg', pcg_inexact_rtol=1e-2) with
 its set-up split, without and with renumbering.  One JSON line (and `--out FILE`).
 
@@ -169,6 +174,67 @@ def measure_marked(fep, torch, a, coord0, elem0):
     return res
 
 
+def measure_estimate(fep, torch, a, coord0, elem0):
+    """Recovery, indicator and bulk marking (include/fep.h, "recovered-stress error indicator") on the P1 tunnel mesh refined
+    a.refine times, with the stress of one elastic step of a smooth displacement: resident on the device (HIP events)
+    against the NumPy twin in the same process, the bytes every pass has to move and the launches of the marking."""
+    from contextlib import closing
+    est = importlib.import_module('fem-elastoplasticity_amd.estimate')
+    dev = a.device
+    coord, elem = fep.refine_uniform(coord0, elem0, levels=a.refine, device=dev)
+    n_e, n_n = int(elem.shape[1]), int(coord.shape[1])
+    shear, bulk = 60000 / (2 * 1.2), 60000 / (3 * 0.6)
+    res = {'n_e': n_e, 'n_n': n_n, 'theta': 0.5}
+    tdev = torch.device('cuda', dev)
+    with closing(fep.MeshContext(elem, coord, *fep.element_tables('P1'), device=dev)) as ctx:
+        ctx.set_materials(shear, bulk, 0.5, 1e9)
+        w = np.asarray(ctx.geometry()[2], dtype=float).ravel()
+        u = 1e-3 * np.stack([np.sin(coord[0] / 7) * np.cos(coord[1] / 9), np.cos(coord[0] / 5) * np.sin(coord[1] / 11)])
+        u_d = torch.from_numpy(np.ascontiguousarray(u.T).ravel()).to(tdev)
+        s_d = torch.empty((4, n_e), dtype=torch.float64, device=tdev)
+        ind_d = torch.empty(n_e, dtype=torch.uint8, device=tdev)
+        ctx.step_dev(torch.cuda.current_stream(dev).cuda_stream, u_d.data_ptr(), s=s_d.data_ptr(), ind_p=ind_d.data_ptr())
+        sn_d = ctx.recover_stress_dev(s_d)                                            # warm-ups: make the scratch
+        eta2_d, st_d, _ = ctx.estimate_dev(s_d, s_node=sn_d)
+        marked_d, out_d = fep.mark_bulk(eta2_d, 0.5)
+        torch.cuda.synchronize(dev)
+        res['resident_recover'] = events(torch, lambda: ctx.recover_stress_dev(s_d, out=sn_d), a.passes)
+        res['resident_indicator'] = events(torch, lambda: ctx.estimate_dev(s_d, s_node=sn_d, stats=False), a.passes)
+        res['resident_indicator_stats'] = events(torch, lambda: ctx.estimate_dev(s_d, s_node=sn_d), a.passes)
+        res['resident_mark_bulk'] = events(torch, lambda: fep.mark_bulk(eta2_d, 0.5), a.passes)
+        s = s_d.cpu().numpy()
+    t0 = time.perf_counter()
+    sn = est.recover_stress_np(elem, w, s, n_n)
+    t1 = time.perf_counter()
+    twin = est.estimate_np(elem, w, shear, bulk, None, s, n_n)
+    t2 = time.perf_counter()
+    marked, out = est.mark_bulk(twin['eta2'], 0.5)
+    t3 = time.perf_counter()
+    res['twin_ms'] = {'recover': 1e3 * (t1 - t0), 'indicator': 1e3 * ((t2 - t1) - (t1 - t0)), 'mark_bulk': 1e3 * (t3 - t2)}
+    res['bit_equal'] = {'s_node': sn_d.cpu().numpy().tobytes() == sn.tobytes(), 'eta2': eta2_d.cpu().numpy().tobytes() == twin['eta2'].tobytes(),
+                        'stats': st_d.cpu().numpy().tolist() == [twin['total'], twin['max'], float(twin['n_nonfinite']), float(n_e)],
+                        'marked': marked_d.cpu().numpy().tobytes() == marked.view(np.uint8).tobytes(),
+                        'out': out_d.cpu().numpy().tobytes() == out.tobytes()}
+    res['eta'], res['n_marked'], res['t_star'] = float(np.sqrt(twin['total'])), int(marked.sum()), float(out[0])
+    passes = est.VALUE_BITS + 2
+    res['launches'] = {'mark_bulk': est.mark_bulk_launches(n_e), 'tree_levels': est.tree_levels(n_e), 'passes': passes,
+                       'recover': 1, 'indicator': 1, 'stats': est.tree_levels(n_e)}
+    # what each pass has to move at the least (every array once) and what its lanes ask for (the gathers, served by the caches)
+    res['bytes'] = {'recover': {'once': 40 * n_e + 32 * n_n + 4 * (3 * n_e + n_n + 1), 'gathers': 3 * n_e * 40},
+                    'indicator': {'once': (32 + 8 + 12 + 8) * n_e + 32 * n_n, 'gathers': 3 * n_e * 32},
+                    'mark_bulk': {'per_tail_pass': 8 * n_e, 'all_passes': passes * 8 * n_e + n_e}}
+    for k, b in (('resident_recover', res['bytes']['recover']['once']), ('resident_indicator', res['bytes']['indicator']['once']),
+                 ('resident_mark_bulk', res['bytes']['mark_bulk']['all_passes'])):
+        res[k]['GB_per_s_of_least_bytes'] = b / (1e6 * res[k]['median_ms'])
+    # the tunnel driven by the indicator: two rounds from the 887-triangle mesh, next to the default marking (mark_plastic)
+    res['tunnel'] = {}
+    for name, kw in (('zz', {'mark': 'zz', 'theta': 0.5}), ('plastic', {})):
+        r = fep.solve_tsx_tunnel(coord0, elem0, 'P1', device=dev, adapt=2, **kw)
+        res['tunnel'][name] = [{k: (row[k] if row[k] is None else float(row[k]) if k in ('displ', 'eta') else int(row[k]))
+                                for k in ('n_e', 'n_marked', 'displ', 'n_plast', 'eta') if k in row} for row in r['adapt']]
+    return res
+
+
 def solve(fep, a, mesh_dir, refine, renumber, curves):
     t0 = time.perf_counter()
     h = fep.solve_tsx_tunnel(mesh_dir=mesh_dir, element_type='P1', refine=refine, renumber=renumber, linear_solver='amg',
@@ -189,6 +255,7 @@ def main():
     ap.add_argument('--solve', type=int, default=None)
     ap.add_argument('--curved', action='store_true')
     ap.add_argument('--marked', action='store_true')
+    ap.add_argument('--estimate', action='store_true')
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -200,6 +267,13 @@ def main():
     coord0, elem0 = g['coord'], g['elem']
     hole = [fep.tsx_tunnel.TSX_HOLE]
     res = {'tool': 'mesh_bench', 'refine': a.refine, 'device_name': torch.cuda.get_device_name(dev)}
+    if a.estimate:                                                                    # a record of its own: none of the passes a-d
+        res['estimate'] = measure_estimate(fep, torch, a, coord0, elem0)
+        line = json.dumps(res)
+        print(line)
+        with open(a.out or os.path.join(ROOT, 'profiles', 'estimate_bench.json'), 'w') as fh:
+            fh.write(line + '\n')
+        return
     res.update(measure(fep, torch, a, coord0, elem0, None))
     if a.curved:
         res['curved'] = measure(fep, torch, a, coord0, elem0, hole, host=False)
