@@ -79,6 +79,7 @@ struct fep_ctx {
     int64_t n_patch = 0;
 #ifdef FEP_ABLATION
     unsigned long long* phase_clk = nullptr;            // FEP_PHASE_CLK=1: phase stamps of the last element_kernel launch (reported at destroy)
+    unsigned long long* p1_clk = nullptr;               // FEP_P1_CLK=1: 8 stamps per tile of the last p1_node_lds_kernel launch, then of the last p1_fused_kernel launch
 #endif
     double *Pc = nullptr, *Pf = nullptr;                // partial blocks / forces of the open items (scratch, rewritten by every step)
     bool elem_geo = true;                               // element_kernel: geometry from coordinates instead of the dphi arrays
@@ -95,10 +96,10 @@ struct fep_ctx {
     double *geo = nullptr, *xy = nullptr;               // xy: interleaved (x,y) per node
     P1Tab p1tab{};
     int32_t *perm2 = nullptr, *ncol = nullptr;
-    int32_t *wg_elist = nullptr, *wg_rng = nullptr;     // wg_rng: <= 8 (start, cum) runs per tile
+    int32_t* wg_elist = nullptr;                        // list form (p1_rng false); the runs of the run form ride in trec
     bool p1_rng = false, p1_pk = false;
     uint2* pk = nullptr;                                // packed block descriptors, lanes sorted by segment length
-    int4* tdesc = nullptr;                              // P1 tiles: (1 + kSegMax) int4 per tile (fep_host.h, P1Plan)
+    int32_t* trec = nullptr;                            // P1 tiles: one record of kRecInts ints per tile (fep_host.h, P1Plan::rec)
     int32_t* tstart = nullptr;                          // COO route: first block of every tile of csr_reduce_kernel
     int n_wg_p1 = 0;   // LDS-staged variant: per-workgroup element lists
     // one-kernel step (p1_fused_kernel): per-tile node lists / runs, per staged element its tile-local node indices + owner bit
@@ -107,7 +108,7 @@ struct fep_ctx {
     bool p1_dma = false;                                // FEP_P1_DMA=1: node data and gather codes of the one-kernel step by LDS-DMA
     int fused_mode = 1;                                 // FEP_P1_FUSED=off|kf|all: 0 = never, 1 = only when no point output is wanted (default), 2 = always
     int lds_NL = 0;                                     // staged nodes per tile (max)
-    int32_t *wg_nlist = nullptr, *wg_nrng = nullptr;
+    int32_t* wg_nlist = nullptr;
     uint32_t* el_nodes = nullptr;
     unsigned long long* slot_counts = nullptr;          // 256 slots x 16 words, zero between steps
     bool has_orphans = false;                           // nodes that belong to no element (their F entries are zeroed per step)
@@ -626,6 +627,29 @@ extern "C" int fep_ctx_destroy(fep_ctx* c) {
                              real > 0 ? cyc / real * 100.0 : 0.0);
             }
         }
+        if (c->p1_clk && c->n_wg_p1 > 0) {               // mean shader clocks per phase of the LAST launch of each P1 tile kernel
+            const int64_t n = c->n_wg_p1;
+            std::vector<unsigned long long> h((size_t)(16 * n));
+            if (hipDeviceSynchronize() == hipSuccess &&
+                hipMemcpy(h.data(), c->p1_clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
+                for (int k = 0; k < 2; ++k) {
+                    double acc[5] = {0, 0, 0, 0, 0}, cyc = 0.0, real = 0.0;
+                    int64_t seen = 0;
+                    for (int64_t g = 0; g < n; ++g) {
+                        const unsigned long long* s = h.data() + 8 * (k * n + g);
+                        if (s[5] == 0) continue;            // the kernel did not run
+                        ++seen;
+                        for (int i = 0; i < 5; ++i) acc[i] += (double)(s[i + 1] - s[i]);
+                        cyc += (double)(s[5] - s[0]); real += (double)(s[7] - s[6]);
+                    }
+                    if (seen == 0) continue;
+                    std::fprintf(stderr, "[fep] %s tile clocks, mean per workgroup of %lld (entry -> tables, -> first operand, -> first barrier, "
+                                 "-> gather done, -> end): %.0f %.0f %.0f %.0f %.0f  sum %.0f; shader clock %.0f MHz\n",
+                                 k == 0 ? "p1_node_lds_kernel" : "p1_fused_kernel", (long long)seen, acc[0] / seen, acc[1] / seen,
+                                 acc[2] / seen, acc[3] / seen, acc[4] / seen, cyc / seen, real > 0 ? cyc / real * 100.0 : 0.0);
+                }
+            }
+        }
 #endif
         for (void* p : c->owned) (void)hipFree(p);
         for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
@@ -711,20 +735,24 @@ static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
     if (const char* dm = fep_tune("FEP_P1_DMA")) c->p1_dma = std::strcmp(dm, "0") != 0;
     if (const char* fm = fep_tune("FEP_P1_FUSED"))
         c->fused_mode = std::strcmp(fm, "off") == 0 ? 0 : std::strcmp(fm, "kf") == 0 ? 1 : 2;
+    if (fep_tune("FEP_P1_CLK") && P.n_wg > 0) {
+        FEP_TRY(dmalloc(c, &c->p1_clk, 16 * P.n_wg));
+        (void)hipMemset(c->p1_clk, 0, (size_t)(16 * P.n_wg) * sizeof(unsigned long long));
+    }
 #endif
     FEP_TRY(upload(c, &c->perm2, P.perm2.data(), (int64_t)P.perm2.size()));
     FEP_TRY(upload(c, &c->ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
-    FEP_TRY(upload(c, &c->tdesc, (const int4*)P.tdesc.data(), (int64_t)P.tdesc.size() / 4));
+    static_assert(fep_host::kRecInts == kRecInts && fep_host::kRecRng == kRecRng && fep_host::kRecNrng == kRecNrng &&
+                  fep_host::kDescInts == 4 * (1 + kSegMax), "host and kernels agree on the tile record");
+    FEP_TRY(upload(c, &c->trec, P.rec.data(), (int64_t)P.rec.size()));
     if (P.lds) {
         FEP_TRY(upload(c, &c->wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
         FEP_TRY(upload(c, &c->perm_l, P.codes_pad.data(), (int64_t)P.codes_pad.size()));
-        if (P.rng) FEP_TRY(upload(c, &c->wg_rng, P.rng_tab.data(), (int64_t)P.rng_tab.size()));
         if (P.pk) FEP_TRY(upload(c, &c->pk, (const uint2*)P.pkv.data(), (int64_t)P.pkv.size()));
     }
     if (P.fused) {
         FEP_TRY(upload(c, &c->el_nodes, P.elnodes.data(), (int64_t)P.elnodes.size()));
-        if (P.fused_rng) FEP_TRY(upload(c, &c->wg_nrng, P.nrng_tab.data(), (int64_t)P.nrng_tab.size()));
-        else FEP_TRY(upload(c, &c->wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size()));
+        if (!P.fused_rng) FEP_TRY(upload(c, &c->wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size()));
         FEP_TRY(dmalloc(c, &c->slot_counts, 256 * 16));
         HIP_TRY(hipMemset(c->slot_counts, 0, 256 * 16 * sizeof(unsigned long long)));
     }
@@ -1269,11 +1297,12 @@ static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const do
         if (c->lds_L > 256 || c->lds_NL > 256) return FEP_ESTATE;
         FEP_TRY(with_bool(c->p1_fused_rng, [&](auto rng) {
             return launch_lds(p1_fused_kernel<false, 256, decltype(rng)::value, 1, 1, true>, grid, 256, lds, kLdsDefault, st,
-                              c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist, (const int4*)c->wg_rng,
-                              c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes, c->pk, c->tdesc, c->xy, c->p1tab,
+                              c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist,
+                              c->wg_nlist, c->el_nodes, c->pk, c->trec, c->xy, c->p1tab,
                               (const double*)nullptr, make_e0(nullptr), (const double*)nullptr, c->shear, c->bulk, c->eta,
                               c->c, c->matu, (double*)nullptr, (double*)nullptr, (double*)nullptr, (uint8_t*)nullptr,
-                              k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, c->n_count_blocks, c->blk_counts, counts_d);
+                              k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, c->n_count_blocks, c->blk_counts, counts_d,
+                              c->p1_clk ? c->p1_clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr);
         }));
         *counted = counts_d != nullptr;
         return FEP_OK;
@@ -1307,8 +1336,12 @@ static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const do
             return with_ablation_bool<true>(c->p1_pk, [&](auto pk) {
                 return launch_lds(p1_node_lds_kernel<TPB, decltype(rng)::value, 1, decltype(pk)::value>, grid, TPB, lds,
                                   kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol,
-                                  c->wg_elist, (const int4*)c->wg_rng, c->pk, c->tdesc, c->geo, ds, s, k_data, f_out, n_wg,
-                                  c->n_count_blocks, c->blk_counts, counts_d);
+                                  c->wg_elist, c->pk, c->trec, c->geo, ds, s, k_data, f_out, n_wg,
+                                  c->n_count_blocks, c->blk_counts, counts_d
+#ifdef FEP_ABLATION
+                                  , c->p1_clk
+#endif
+                                  );
             });
         });
     }));
@@ -1377,11 +1410,15 @@ static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, c
                     constexpr int TPB = decltype(t128)::value ? 128 : 256;
                     return launch_lds(p1_fused_kernel<decltype(full_c)::value, TPB, decltype(rng)::value, 1, 1, false, decltype(dma_c)::value>,
                                       grid, TPB, lds, kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l,
-                                      c->wg_elist, (const int4*)c->wg_rng, c->wg_nlist, (const int4*)c->wg_nrng, c->el_nodes,
-                                      c->pk, c->tdesc, c->xy, c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
+                                      c->wg_elist, c->wg_nlist, c->el_nodes,
+                                      c->pk, c->trec, c->xy, c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
                                       eout, s, ds, indp, k_data, f_out, n_wg,
                                       counts_d ? c->slot_counts : (unsigned long long*)nullptr, (const double*)nullptr,
-                                      (const double*)nullptr, 0, (const uint2*)nullptr, (unsigned long long*)nullptr);
+                                      (const double*)nullptr, 0, (const uint2*)nullptr, (unsigned long long*)nullptr
+#ifdef FEP_ABLATION
+                                      , c->p1_clk ? c->p1_clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr
+#endif
+                                      );
                 });
             });
         });

@@ -172,6 +172,11 @@ inline int row_tiles(const Symbolic& S, int64_t n_n, int tile, std::vector<int32
 //
 //   tdesc  kDescInts int32 per tile: [pk_base, n_blocks, n_nodes, n_segments | staged elements << 4 | staged nodes << 16]
 //          then kSegMax x [first_block, n_blocks, first_node, n_nodes]  (scalar loads in the kernels)
+//   rec    what the kernels read of the three per-tile tables: ONE record of kRecInts int32 (256 bytes, so 64-byte aligned
+//          in an allocation that is) per tile, fetched in one scalar round trip at kernel entry:
+//          [0, kDescInts) the tile's tdesc, [kRecRng, +16) its element runs (rng_tab), [kRecNrng, +16) its node runs
+//          (nrng_tab); everything else zero.  A plan in list form (rng / fused_rng false) leaves the run part zero:
+//          eight runs of cumulative count 0, none of them live.
 //   elist_pad / rng_tab   sorted unique elements of the tile, padded to L with its first element / as <= 8 runs
 //   codes_pad             gather codes (local element << 4 | a << 2 | b) in tile block order, padded to C
 //   pkv                   per lane of the tile (lanes sorted by descending segment length) the packed descriptor
@@ -181,6 +186,8 @@ inline int row_tiles(const Symbolic& S, int64_t n_n, int tile, std::vector<int32
 // ---------------------------------------------------------------------------------------
 constexpr int kSegMax = 4;
 constexpr int kDescInts = 4 * (1 + kSegMax);
+constexpr int kRecInts = 64, kRecRng = 32, kRecNrng = 48;
+static_assert(kDescInts <= kRecRng && kRecRng + 16 <= kRecNrng && kRecNrng + 16 <= kRecInts, "the tile record's parts do not overlap");
 
 struct P1Options {
     int tile = 256;
@@ -193,6 +200,7 @@ struct P1Plan {
     int tile = 256, n_segs = 1;
     int64_t n_wg = 0, staged_total = 0, staged_nodes_total = 0;
     std::vector<int32_t> tdesc;
+    std::vector<int32_t> rec;                // tile records (see above): the device copy of tdesc, rng_tab and nrng_tab
     std::vector<int32_t> perm2;              // global gather list (e << 4 | a << 2 | b), block order: direct kernel
     bool lds = false, rng = false, pk = false, fused = false, fused_rng = false;
     int L = 0, C = 0, NL = 0;
@@ -283,8 +291,20 @@ inline void runs_of(const std::vector<int32_t>& l, int32_t* d /* 16 ints */, boo
     for (; nr < 8; ++nr) { d[2 * nr] = l.empty() ? 0 : l[0]; d[2 * nr + 1] = cum; }
 }
 
-inline int build_p1_plan_segs(const Symbolic& S, int64_t n_e, int64_t n_n, const int32_t* elem, const P1Options& opt,
-                              int max_segs, P1Plan& P) {
+// The tile records of a finished plan.
+inline void pack_tile_records(P1Plan& P) {
+    P.rec.assign((size_t)P.n_wg * kRecInts, 0);
+    const bool er = P.lds && P.rng, nr = P.fused && P.fused_rng;
+    for (int64_t g = 0; g < P.n_wg; ++g) {
+        int32_t* r = P.rec.data() + g * kRecInts;
+        std::copy(P.tdesc.begin() + g * kDescInts, P.tdesc.begin() + (g + 1) * kDescInts, r);
+        if (er) std::copy(P.rng_tab.begin() + g * 16, P.rng_tab.begin() + (g + 1) * 16, r + kRecRng);
+        if (nr) std::copy(P.nrng_tab.begin() + g * 16, P.nrng_tab.begin() + (g + 1) * 16, r + kRecNrng);
+    }
+}
+
+inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, const int32_t* elem, const P1Options& opt,
+                                int max_segs, P1Plan& P) {
     P = P1Plan();
     P.tile = opt.tile;
     const int TILE = opt.tile;
@@ -526,6 +546,13 @@ inline int build_p1_plan_segs(const Symbolic& S, int64_t n_e, int64_t n_n, const
     return FEP_OK;
 }
 
+inline int build_p1_plan_segs(const Symbolic& S, int64_t n_e, int64_t n_n, const int32_t* elem, const P1Options& opt,
+                              int max_segs, P1Plan& P) {
+    const int r = build_p1_tables_segs(S, n_e, n_n, elem, opt, max_segs, P);
+    if (r == FEP_OK) pack_tile_records(P);
+    return r;
+}
+
 // The plan the kernels run: the multi-segment tiling when it has every compression the fast kernels need AND stages
 // at least 5 % fewer elements than the row strips, else the row strips.
 inline int build_p1_plan(const Symbolic& S, int64_t n_e, int64_t n_n, const int32_t* elem, const P1Options& opt, P1Plan& P) {
@@ -545,6 +572,17 @@ inline int build_p1_plan(const Symbolic& S, int64_t n_e, int64_t n_n, const int3
 inline int validate_p1_plan(const P1Plan& P, const Symbolic& S, int64_t n_e, int64_t n_n, const int32_t* elem) {
     const int64_t n_blk = (int64_t)S.ncol.size();
     if ((int64_t)P.tdesc.size() != P.n_wg * kDescInts) return 1;
+    if ((int64_t)P.rec.size() != P.n_wg * kRecInts) return 20;
+    for (int64_t g = 0; g < P.n_wg; ++g) {                                           // the record is the three tables and zeros
+        const int32_t* r = P.rec.data() + g * kRecInts;
+        for (int i = 0; i < kRecInts; ++i) {
+            int32_t want = 0;
+            if (i < kDescInts) want = P.tdesc[(size_t)g * kDescInts + i];
+            else if (i >= kRecRng && i < kRecRng + 16 && P.lds && P.rng) want = P.rng_tab[(size_t)g * 16 + (i - kRecRng)];
+            else if (i >= kRecNrng && i < kRecNrng + 16 && P.fused && P.fused_rng) want = P.nrng_tab[(size_t)g * 16 + (i - kRecNrng)];
+            if (r[i] != want) return 20;
+        }
+    }
     std::vector<uint8_t> seen((size_t)n_blk, 0);
     std::vector<int> owners((size_t)n_e, 0);
     int64_t pk_base = 0;

@@ -1720,11 +1720,13 @@ p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, c
 // a tile are SORTED by descending segment length: the diagonal blocks (one contribution per incident element, 6 on
 // a regular mesh, against 2 for an edge block) fill the first wave instead of setting the trip count of all four.
 //
-// Tiles (fep_host.h, P1Plan): up to kSegMax segments of consecutive nodes; `tdesc` holds, per tile, 1 + kSegMax int4:
-// (pk_base, n_blocks, n_nodes, n_segments) and per segment (first_block, n_blocks, first_node, n_nodes), read with
-// scalar loads.  The tile's CSR values and forces leave as one contiguous range per segment.  Without PK every tile
-// has exactly one segment (its blocks are first_block + lane).
+// Tiles (fep_host.h, P1Plan): up to kSegMax segments of consecutive nodes; the tile's record `trec` (kRecInts ints, 256
+// bytes) holds 1 + kSegMax int4: (pk_base, n_blocks, n_nodes, n_segments) and per segment (first_block, n_blocks,
+// first_node, n_nodes), then at kRecRng the element runs and at kRecNrng the node runs of RNG plans, all read with scalar
+// loads in ONE round trip at kernel entry (load_tile_rec).  The tile's CSR values and forces leave as one contiguous range
+// per segment.  Without PK every tile has exactly one segment (its blocks are first_block + lane).
 constexpr int kSegMax = 4;
+constexpr int kRecInts = 64, kRecRng = 32, kRecNrng = 48;
 
 // LDS-DMA (global_load_lds): the lane's 16 / 4 bytes at `g` go straight to LDS at wave_base + lane * size — no VGPR, no
 // ds_write.  `wave_base` must be wave-uniform; the data is visible to ds_read after s_waitcnt vmcnt + a barrier
@@ -1740,18 +1742,52 @@ static_assert(kSegMax == 4, "the tile descriptor names its four segments");
 // plain ints (no HIP vector types, no arrays): the descriptor stays in scalar registers
 struct TileDesc {
     int pk_base, nb, nn, nseg, n_el, n_nd, n_own;       // n_el / n_nd: staged elements / nodes of THIS tile (<= L / NL); the first n_own staged elements are the tile's own
-    int fb0, nb0, fn0, nn0, fb1, nb1, fn1, nn1, fb2, nb2, fn2, nn2, fb3, nb3, fn3, nn3;
+    int fb0, fn0, fb1, fn1, fb2, fn2, fb3, fn3;         // first block / first node of the segments
+    // where the first three segments end in the tile's output image, which is all the stores at the end of the kernel need of
+    // the segments' sizes: 3 x 10 bits in double2 of CSR values (<= 2 * 256), 3 x 8 bits in nodes (<= 255).  Two scalar
+    // registers instead of eight through the whole kernel, whose scalar file the one-kernel step fills.
+    int bends, nends;
 };
 
-__device__ __forceinline__ TileDesc load_tile_desc(const int4* __restrict__ tdesc, int wg) {
-    const int32_t* d = reinterpret_cast<const int32_t*>(tdesc) + (int64_t)wg * 4 * (1 + kSegMax);   // uniform address: scalar loads
+// The tile's record -> scalar registers.  Every table of the tile depends on the tile index alone, so all of it is asked
+// for back to back and waited for once: a descriptor fetched piecewise, each run table behind a wait of its own, put
+// one cold memory round trip per piece at the head of every tile's dependent chain.  The empty asm takes all parts as
+// scalar operands at one point, which keeps the compiler from sinking a part of the fetch below the kernel's wave-uniform
+// branches (where it would wait again); plain ints throughout (a vector type here is kept, spilled and
+// reloaded as one 16-register tuple).  er / nr: the 16 ints of the element / node runs (read when ER / NR).
+#define FEP_PIN4(v, k) "+s"(v[k]), "+s"(v[k + 1]), "+s"(v[k + 2]), "+s"(v[k + 3])
+#define FEP_PIN16(v) FEP_PIN4(v, 0), FEP_PIN4(v, 4), FEP_PIN4(v, 8), FEP_PIN4(v, 12)
+
+template <bool ER, bool NR>
+__device__ __forceinline__ TileDesc load_tile_rec(const int32_t* __restrict__ trec, int wg, int (&er)[16], int (&nr)[16]) {
+    // uniform address in the constant address space (the records are written once, by the host): scalar loads
+    typedef const __attribute__((address_space(4))) int32_t* cptr_t;
+    const cptr_t d = (cptr_t)(trec + (int64_t)wg * kRecInts);
+    int a[16], b[4];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { a[k] = d[k]; er[k] = ER ? d[kRecRng + k] : 0; nr[k] = NR ? d[kRecNrng + k] : 0; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k] = d[16 + k];
+    if (ER && NR) asm volatile("" : FEP_PIN16(a), FEP_PIN4(b, 0), FEP_PIN16(er), FEP_PIN16(nr));
+    else if (ER) asm volatile("" : FEP_PIN16(a), FEP_PIN4(b, 0), FEP_PIN16(er));
+    else asm volatile("" : FEP_PIN16(a), FEP_PIN4(b, 0));
     TileDesc t;
-    t.pk_base = d[0]; t.nb = d[1]; t.nn = d[2] & 255; t.n_own = d[2] >> 8; t.nseg = d[3] & 15; t.n_el = (d[3] >> 4) & 4095; t.n_nd = (d[3] >> 16) & 4095;
-    t.fb0 = d[4]; t.nb0 = d[5]; t.fn0 = d[6]; t.nn0 = d[7];
-    t.fb1 = d[8]; t.nb1 = d[9]; t.fn1 = d[10]; t.nn1 = d[11];
-    t.fb2 = d[12]; t.nb2 = d[13]; t.fn2 = d[14]; t.nn2 = d[15];
-    t.fb3 = d[16]; t.nb3 = d[17]; t.fn3 = d[18]; t.nn3 = d[19];
+    t.pk_base = a[0]; t.nb = a[1]; t.nn = a[2] & 255; t.n_own = a[2] >> 8; t.nseg = a[3] & 15; t.n_el = (a[3] >> 4) & 4095; t.n_nd = (a[3] >> 16) & 4095;
+    t.fb0 = a[4]; t.fn0 = a[6]; t.fb1 = a[8]; t.fn1 = a[10]; t.fb2 = a[12]; t.fn2 = a[14]; t.fb3 = b[0]; t.fn3 = b[2];
+    const int be0 = 2 * a[5], be1 = be0 + 2 * a[9], be2 = be1 + 2 * a[13];
+    const int ne0 = a[7], ne1 = ne0 + a[11], ne2 = ne1 + a[15];
+    t.bends = be0 | (be1 << 10) | (be2 << 20);
+    t.nends = ne0 | (ne1 << 8) | (ne2 << 16);
+    asm volatile("" : "+s"(t.bends), "+s"(t.nends));   // (opaque: unpacking must not lead back to the eight sizes)
     return t;
+}
+
+// Slot i of a list given as <= 8 runs (start_r, cumulative count_r); slots past the list repeat its first entry.
+__device__ __forceinline__ int run_entry(const int (&r)[16], int i) {
+    int e = r[0] + i;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) e = i >= r[2 * k - 1] ? r[2 * k] + (i - r[2 * k - 1]) : e;
+    return i < r[15] ? e : r[0];
 }
 
 // The tile's LDS output image -> HBM: CSR values (2*nb double2 in tile block order) and forces (nn double2 in tile
@@ -1761,7 +1797,7 @@ __device__ __forceinline__ void store_tile_outputs(const TileDesc t, const doubl
                                                    double* __restrict__ data, double* __restrict__ F) {
     if (data) {
         const int n2 = 2 * t.nb;
-        const int e0 = 2 * t.nb0, e1 = e0 + 2 * t.nb1, e2 = e1 + 2 * t.nb2;          // ends of the segments' images
+        const int e0 = t.bends & 1023, e1 = (t.bends >> 10) & 1023, e2 = (t.bends >> 20) & 1023;   // ends of the segments' images
         for (int i = threadIdx.x; i < n2; i += TPB) {
             const int64_t fb = i < e0 ? t.fb0 : i < e1 ? t.fb1 : i < e2 ? t.fb2 : t.fb3;
             const int j = i < e0 ? i : i < e1 ? i - e0 : i < e2 ? i - e1 : i - e2;
@@ -1770,38 +1806,62 @@ __device__ __forceinline__ void store_tile_outputs(const TileDesc t, const doubl
     }
     if (F && (int)threadIdx.x < t.nn) {
         const int i = threadIdx.x;
-        const int e0 = t.nn0, e1 = e0 + t.nn1, e2 = e1 + t.nn2;
+        const int e0 = t.nends & 255, e1 = (t.nends >> 8) & 255, e2 = (t.nends >> 16) & 255;
         const int64_t fn = i < e0 ? t.fn0 : i < e1 ? t.fn1 : i < e2 ? t.fn2 : t.fn3;
         const int j = i < e0 ? i : i < e1 ? i - e0 : i < e2 ? i - e1 : i - e2;
         reinterpret_cast<double2*>(F + 2 * fn)[j] = fo2[i];
     }
 }
 
+// Phase stamps of the P1 tile kernels in the ablation build (FEP_P1_CLK; thread 0 of every workgroup, 8 words per tile):
+// [0] kernel entry, [1] the tile's tables in registers, [2] first operand landed (just before the LDS fill), [3] after the
+// first barrier, [4] after the gather, [5] before the end: s_memtime (shader clock); [6], [7] s_memrealtime (100 MHz) at
+// entry / end.  They go to a buffer of their own; no output is computed from them.
+#ifdef FEP_ABLATION
+#define FEP_P1_CLK_PARAM , unsigned long long* __restrict__ clk
+#define FEP_P1_STAMP(wg, i) do { if (clk && threadIdx.x == 0) { clk[(size_t)(wg) * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
+        if ((i) == 5) clk[(size_t)(wg) * 8 + 7] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#define FEP_P1_STAMP_AFTER(wg, i, val) do { if (clk && threadIdx.x == 0) { asm volatile("" :: "v"(val)); FEP_P1_STAMP(wg, i); } } while (0)
+// entry: read before the tile index is known to be live, written once it is
+#define FEP_P1_STAMP_ENTRY() const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime()
+#define FEP_P1_STAMP_ENTRY_WRITE(wg) do { if (clk && threadIdx.x == 0) { clk[(size_t)(wg) * 8] = clk_t0; clk[(size_t)(wg) * 8 + 6] = clk_r0; } } while (0)
+#else
+#define FEP_P1_CLK_PARAM
+#define FEP_P1_STAMP(wg, i) do { } while (0)
+#define FEP_P1_STAMP_AFTER(wg, i, val) do { } while (0)
+#define FEP_P1_STAMP_ENTRY() do { } while (0)
+#define FEP_P1_STAMP_ENTRY_WRITE(wg) do { } while (0)
+#endif
+
 template <int TPB, bool RNG, int EPT, bool PK>
 __global__ void __launch_bounds__(TPB)
 p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr,
                    const uint16_t* __restrict__ perm_l, const uint32_t* __restrict__ meta,
                    const int32_t* __restrict__ ncol,
-                   const int32_t* __restrict__ wg_elist, const int4* __restrict__ rng,
-                   const uint2* __restrict__ pk, const int4* __restrict__ tdesc,
+                   const int32_t* __restrict__ wg_elist,
+                   const uint2* __restrict__ pk, const int32_t* __restrict__ trec,
                    const double* __restrict__ geo,
                    const double* __restrict__ DS, const double* __restrict__ S,
                    double* __restrict__ data, double* __restrict__ F,
                    int n_wg, int n_count_blocks, const uint2* __restrict__ blk_counts,
-                   unsigned long long* __restrict__ counts_out) {
+                   unsigned long long* __restrict__ counts_out FEP_P1_CLK_PARAM) {
     extern __shared__ __attribute__((aligned(16))) double rec[];      // [15][L]
+    FEP_P1_STAMP_ENTRY();
     // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with a
     // private L2.  Give every XCD one contiguous eighth of the tiles, so that the element rows
     // re-staged by the workgroups of the next node row hit in the SAME L2 instead of the fabric.
+    // the arguments the head needs, fetched as one batch (one wait for them, one for the tile's record below)
+    if (RNG) asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)geo), "s"((uint64_t)DS), "s"((uint64_t)S), "s"(n_e));
+    else asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)wg_elist), "s"(L));
     const int chunk = (n_wg + 7) >> 3;
     const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
-    if (counts_out != nullptr && blockIdx.x == 0) sum_block_counts(n_count_blocks, blk_counts, counts_out);
     if (wg >= n_wg) return;
     // Two dependent memory levels only: every table is padded to a fixed per-tile stride (element list:
     // L entries, gather codes: C entries, unused slots repeat a valid entry), so all first-level
     // addresses are functions of (tile, lane) and go out together at kernel entry; the operand loads
     // follow as soon as the list entries land.
-    const TileDesc td = load_tile_desc(tdesc, wg);
+    int er[16], nr[16];
+    const TileDesc td = load_tile_rec<RNG, false>(trec, wg, er, nr);
     const int nb = td.nb;
     const int64_t sb = PK ? (int64_t)td.pk_base + threadIdx.x : (int64_t)td.fb0 + threadIdx.x;
     const bool live = (int)threadIdx.x < nb;
@@ -1810,18 +1870,8 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     // (1) element ids of the lane's staging slots
     int64_t el[EPT];
     if (RNG) {
-        const int4* d = rng + (int64_t)wg * 4;          // uniform address: scalar loads
-        const int4 d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
-        const int st[8] = {d0.x, d0.z, d1.x, d1.z, d2.x, d2.z, d3.x, d3.z};
-        const int cu[8] = {d0.y, d0.w, d1.y, d1.w, d2.y, d2.w, d3.y, d3.w};
 #pragma unroll
-        for (int r = 0; r < EPT; ++r) {
-            const int i = r * TPB + (int)threadIdx.x;
-            int e = st[0] + i;
-#pragma unroll
-            for (int k = 1; k < 8; ++k) e = i >= cu[k - 1] ? st[k] + (i - cu[k - 1]) : e;
-            el[r] = i < cu[7] ? e : st[0];
-        }
+        for (int r = 0; r < EPT; ++r) el[r] = run_entry(er, r * TPB + (int)threadIdx.x);
     } else {
 #pragma unroll
         for (int r = 0; r < EPT; ++r) {
@@ -1829,6 +1879,8 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
             el[r] = wg_elist[(int64_t)wg * L + (i < L ? i : 0)];
         }
     }
+    FEP_P1_STAMP_ENTRY_WRITE(wg);
+    FEP_P1_STAMP_AFTER(wg, 1, el[0]);
     // (2) operand loads.  Wave-uniform guard: a wave whose 64 slots all lie past the list issues nothing
     // (with L = 150 of 256 slots that is one wave in four: the kernel's time follows its vector-memory
     // instruction count); inside a wave every lane loads (slots past the list repeat a valid element).
@@ -1877,6 +1929,7 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     }
     // (4) operands -> LDS
     uint16_t* codes = reinterpret_cast<uint16_t*>(rec + 15 * L);
+    FEP_P1_STAMP_AFTER(wg, 2, g0[0].x);
 #pragma unroll
     for (int r = 0; r < EPT; ++r) {
         const int i = r * TPB + (int)threadIdx.x;
@@ -1902,6 +1955,7 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     const bool is_diag = (m >> 15) & 1u;
     if (!PK && threadIdx.x == 0) t0_sh = beg;
     __syncthreads();
+    FEP_P1_STAMP(wg, 3);
     int32_t t0, fnode_k = -1;
     if (PK) {
         t0 = 0;                                        // pk holds tile-local code offsets
@@ -1933,6 +1987,7 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
             }
         }
     }
+    FEP_P1_STAMP_AFTER(wg, 4, k00 + f0);
     // Results leave through LDS: a lane's two 16-byte pieces belong to two different CSR rows, so direct stores
     // write every 128-byte line in two half-filled passes (measured ~14 us per launch); staged, the tile's
     // 4*nb values (and its nodes' forces) go out as full, consecutive lines.
@@ -1950,6 +2005,10 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     __syncthreads();
     store_tile_outputs<TPB>(td, out2, fo2, data, (PK && S != nullptr) ? F : nullptr);
     if (!PK && want_f) *reinterpret_cast<double2*>(F + 2 * (int64_t)ncol_sb) = make_double2(f0, f1);
+    FEP_P1_STAMP(wg, 5);
+    // the first workgroup also sums the point kernel's branch counters: behind its own tile, so that no branch but the
+    // grid's rounding stands before any tile's table fetch and the sum's registers are not live beside the operands
+    if (counts_out != nullptr && blockIdx.x == 0) sum_block_counts(n_count_blocks, blk_counts, counts_out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1981,9 +2040,9 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
 template <bool FULL, int TPB, bool RNG, int EPT, int NPT, bool FROM_DS = false, bool DMA = false>
 __global__ void __launch_bounds__(TPB, (!FULL && EPT == 1) ? 8 : 1)     // K/F-only: 64 VGPRs, 8 tiles of 4 waves per CU
 p1_fused_kernel(int64_t n_e, int L, int C, int NL,
-                const uint16_t* __restrict__ perm_l, const int32_t* __restrict__ wg_elist, const int4* __restrict__ rng,
-                const int32_t* __restrict__ wg_nlist, const int4* __restrict__ nrng,
-                const uint32_t* __restrict__ el_nodes, const uint2* __restrict__ pk, const int4* __restrict__ tdesc,
+                const uint16_t* __restrict__ perm_l, const int32_t* __restrict__ wg_elist,
+                const int32_t* __restrict__ wg_nlist,
+                const uint32_t* __restrict__ el_nodes, const uint2* __restrict__ pk, const int32_t* __restrict__ trec,
                 const double* __restrict__ xy, P1Tab tab, const double* __restrict__ U, E0 e0,
                 const double* __restrict__ ep,
                 const double* __restrict__ shear, const double* __restrict__ bulk,
@@ -1991,16 +2050,20 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
                 double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
                 double* __restrict__ data, double* __restrict__ F, int n_wg, unsigned long long* __restrict__ slot_counts,
                 const double* __restrict__ DSin, const double* __restrict__ Sin,
-                int n_count_blocks, const uint2* __restrict__ blk_counts, unsigned long long* __restrict__ counts_out) {
+                int n_count_blocks, const uint2* __restrict__ blk_counts, unsigned long long* __restrict__ counts_out
+                FEP_P1_CLK_PARAM) {
     static_assert(!(FULL && FROM_DS), "the assembly-only form has no point outputs");
     extern __shared__ __attribute__((aligned(16))) double rec[];      // [15][L] | codes | node coordinates | node displacements
-    // assembly-only form after p1_point_kernel: the first workgroup also sums that kernel's per-workgroup branch counters
-    if (FROM_DS && counts_out != nullptr && blockIdx.x == 0) sum_block_counts(n_count_blocks, blk_counts, counts_out);
+    FEP_P1_STAMP_ENTRY();
     __shared__ unsigned int sc[2];
+    // the arguments the head needs, fetched as one batch (one wait for them, one for the tile's record below)
+    if (RNG) asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)xy), "s"((uint64_t)U));
+    else asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)wg_elist), "s"((uint64_t)wg_nlist), "s"(L), "s"(NL));
     const int chunk = (n_wg + 7) >> 3;                                // XCD-aware tile order (see p1_node_lds_kernel)
     const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
     if (wg >= n_wg) return;
-    const TileDesc td = load_tile_desc(tdesc, wg);
+    int er[16], nr[16];
+    const TileDesc td = load_tile_rec<RNG, RNG>(trec, wg, er, nr);
     const int nb = td.nb;
     const int64_t sb = (int64_t)td.pk_base + threadIdx.x;                  // lane of the tile -> its packed descriptor
     const bool live = (int)threadIdx.x < nb;
@@ -2010,30 +2073,10 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
     int64_t el[EPT];
     int64_t nd[NPT];
     if (RNG) {
-        const int4* d = rng + (int64_t)wg * 4;
-        const int4 d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
-        const int st[8] = {d0.x, d0.z, d1.x, d1.z, d2.x, d2.z, d3.x, d3.z};
-        const int cu[8] = {d0.y, d0.w, d1.y, d1.w, d2.y, d2.w, d3.y, d3.w};
 #pragma unroll
-        for (int r = 0; r < EPT; ++r) {
-            const int i = r * TPB + (int)threadIdx.x;
-            int e = st[0] + i;
+        for (int r = 0; r < EPT; ++r) el[r] = run_entry(er, r * TPB + (int)threadIdx.x);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) e = i >= cu[k - 1] ? st[k] + (i - cu[k - 1]) : e;
-            el[r] = i < cu[7] ? e : st[0];
-        }
-        const int4* dn = nrng + (int64_t)wg * 4;
-        const int4 n0 = dn[0], n1 = dn[1], n2 = dn[2], n3 = dn[3];
-        const int sn[8] = {n0.x, n0.z, n1.x, n1.z, n2.x, n2.z, n3.x, n3.z};
-        const int cn[8] = {n0.y, n0.w, n1.y, n1.w, n2.y, n2.w, n3.y, n3.w};
-#pragma unroll
-        for (int r = 0; r < NPT; ++r) {
-            const int i = r * TPB + (int)threadIdx.x;
-            int n = sn[0] + i;
-#pragma unroll
-            for (int k = 1; k < 8; ++k) n = i >= cn[k - 1] ? sn[k] + (i - cn[k - 1]) : n;
-            nd[r] = i < cn[7] ? n : sn[0];
-        }
+        for (int r = 0; r < NPT; ++r) nd[r] = run_entry(nr, r * TPB + (int)threadIdx.x);
     } else {
 #pragma unroll
         for (int r = 0; r < EPT; ++r) {
@@ -2046,6 +2089,8 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
             nd[r] = wg_nlist[(int64_t)wg * NL + (i < NL ? i : 0)];
         }
     }
+    FEP_P1_STAMP_ENTRY_WRITE(wg);
+    FEP_P1_STAMP_AFTER(wg, 1, el[0] + nd[0]);
     // (2) loads, all issued before the first use: node data, the slots' node words / plastic strain / materials
     const int n_el = td.n_el, n_nd = td.n_nd;           // this tile's staged elements / nodes (<= L / NL)
     const int Cp = DMA ? (C + 127) & ~127 : C, NLp = DMA ? (NL + 63) & ~63 : NL;      // padded code / node regions (see above)
@@ -2101,6 +2146,7 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
         }
     }
     // (4) node data and codes -> LDS (already on their way with DMA)
+    if (DMA) FEP_P1_STAMP_AFTER(wg, 2, enw[0]); else FEP_P1_STAMP_AFTER(wg, 2, nxy[0].x);
     if (!DMA) {
 #pragma unroll
         for (int r = 0; r < NPT; ++r) {
@@ -2114,6 +2160,7 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
         }
     }
     __syncthreads();                                    // (waits for vmcnt(0): the DMA has landed)
+    FEP_P1_STAMP(wg, 3);
     // (5) per staged element: geometry, strain, return map (p1_point_kernel's statements), operands -> LDS
     unsigned int n_sm = 0u, n_ap = 0u;
 #pragma unroll
@@ -2203,6 +2250,7 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
             }
         }
     }
+    FEP_P1_STAMP_AFTER(wg, 4, k00 + f0);
     __syncthreads();                                   // every lane is done reading the staged operands
     double2* out2 = reinterpret_cast<double2*>(rec);
     if (live && data) {
@@ -2215,6 +2263,10 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
     if (want_f) fo2[fnode_k] = make_double2(f0, f1);
     __syncthreads();
     store_tile_outputs<TPB>(td, out2, fo2, data, F);
+    FEP_P1_STAMP(wg, 5);
+    // assembly-only form after p1_point_kernel: the first workgroup also sums that kernel's per-workgroup branch counters
+    // (behind its own tile: see p1_node_lds_kernel)
+    if (FROM_DS && counts_out != nullptr && blockIdx.x == 0) sum_block_counts(n_count_blocks, blk_counts, counts_out);
 }
 
 // counts_out[0..1] = sum of the 256 slots (stride 16 words) of p1_fused_kernel; the slots are zeroed for the next step.
