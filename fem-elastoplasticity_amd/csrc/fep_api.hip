@@ -52,6 +52,17 @@ enum class Route {
 #endif
 };
 
+// Persistent device buffers of a context's *_host entry points (fep_ctx::hbuf; their sizes: size_host_buffers).  One block
+// per enumerator before kCtxBufCount; the names after it share the block of a call that never runs at the same time (the
+// calls of one device hold its engine's lock in turn): load_volume's f_v and point_coords' result (2 n_int each) lie in the
+// block of s, load_volume's result in that of F, its weights in that of the transform's input.
+enum CtxBuf {
+    kBufU, kBufEp, kBufE, kBufS, kBufDs, kBufIndP, kBufK, kBufF, kBufCounts, kBufQ, kBufNode, kBufField, kBufSNode, kBufEta2,
+    kBufStats, kCtxBufCount, kBufFv = kBufS, kBufXq = kBufS, kBufLoad = kBufF, kBufWeight = kBufQ,
+};
+// Device buffers of the mesh-free return map, in its engine's store (sized by each call)
+enum RmBuf { kRmE, kRmEp, kRmShear, kRmBulk, kRmM3, kRmM4, kRmS, kRmDs, kRmIndP, kRmCounts, kRmField };
+
 struct fep_ctx {
     int device = 0;
     int elem_type = 0;
@@ -122,10 +133,7 @@ struct fep_ctx {
     double *s_int = nullptr, *ds_int = nullptr;     // used when the caller does not ask for s / ds
     uint2* blk_counts = nullptr;
     int n_count_blocks = 0;
-    // persistent device buffers of the *_host entry points (u, ep, e, s, ds, ind_p, k, f, counts, q, node values, e0_field,
-    // recovered nodal stress, eta2, indicator statistics)
-    void* hbuf[15] = {};
-    size_t hbuf_bytes[15] = {};
+    fep_stage::DeviceStore hbuf{kCtxBufCount};          // persistent device buffers of the *_host entry points, by CtxBuf
     // host copies of the pattern
     std::vector<int32_t> indptr, indices;
     // in-situ profiling: 4 events per call (fep_step_dev, fep_assemble_dev)
@@ -133,6 +141,17 @@ struct fep_ctx {
     std::vector<hipEvent_t> events;
     bool verbose = false;                               // FEP_VERBOSE at creation
 };
+
+// The size of every host staging buffer, fixed by the mesh: each block is allocated once, at this size, by the first call
+// that uses it (a shared block at the size of its largest user: kBufS holds 4 n_int although assemble copies 3 n_int in)
+static void size_host_buffers(fep_ctx* c) {
+    const size_t d = sizeof(double), n_int = (size_t)c->n_int, n_n = (size_t)c->n_n, n_dof = (size_t)c->n_dof;
+    auto size = [&](CtxBuf b, size_t bytes) { c->hbuf[b].cap = bytes; };
+    size(kBufU, n_dof * d);       size(kBufEp, 4 * n_int * d);   size(kBufE, 3 * n_int * d);   size(kBufS, 4 * n_int * d);
+    size(kBufDs, 9 * n_int * d);  size(kBufIndP, n_int);         size(kBufK, (size_t)c->nnz * d);  size(kBufF, n_dof * d);
+    size(kBufCounts, 2 * sizeof(int64_t));                       size(kBufQ, n_int * d);       size(kBufNode, n_n * d);
+    size(kBufField, 4 * n_int * d);  size(kBufSNode, 4 * n_n * d);  size(kBufEta2, (size_t)c->n_e * d);  size(kBufStats, 4 * d);
+}
 
 __attribute__((visibility("hidden"))) int fep_set_device(int dev) {
     int n = 0;
@@ -271,7 +290,6 @@ extern "C" int fep_sync(int device_id, void* stream) {
 // ---------------------------------------------------------------------------------------
 // a2 mesh-free
 // ---------------------------------------------------------------------------------------
-constexpr int kFieldBuffer = 11;                        // staging buffer of a host entry point's e0_field (engine and context alike)
 static E0 make_e0(const double* e0_h) {
     E0 z;
     for (int i = 0; i < 4; ++i) z.v[i] = e0_h ? e0_h[i] : 0.0;
@@ -411,18 +429,6 @@ extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, 
                                shear_d, bulk_d, m3_d, m4_d, accept, s_d, ds_d, ind_p_d, counts_d, e0_field_d, e0_scale);
 }
 
-// persistent device buffer `idx` of a context's host entry points (sizes are fixed by the mesh: allocated once)
-static int ctx_buf(fep_ctx* c, int idx, int64_t bytes, void** out) {
-    if (bytes <= 0) bytes = 1;
-    if (c->hbuf_bytes[idx] < (size_t)bytes) {
-        if (c->hbuf[idx]) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->hbuf[idx])); c->hbuf[idx] = nullptr; c->hbuf_bytes[idx] = 0; }
-        HIP_TRY(hipMalloc(&c->hbuf[idx], (size_t)bytes));
-        c->hbuf_bytes[idx] = (size_t)bytes;
-    }
-    *out = c->hbuf[idx];
-    return FEP_OK;
-}
-
 extern "C" int fep_host_alloc(void** ptr_h, int64_t bytes) {
     if (!ptr_h || bytes < 0) return FEP_EINVAL;
     *ptr_h = nullptr;
@@ -448,52 +454,35 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     if (n_int > 0 && (!e_h || !shear_h || !bulk_h || !eta_h || !c_h)) return FEP_EINVAL;
     if (counts_h) { counts_h[0] = 0; counts_h[1] = 0; }
     if (n_int == 0) return FEP_OK;
-    FEP_TRY(fep_set_device(device_id));
+    fep_stage::HostCall call(device_id);
+    FEP_TRY(call.status());
     // the strain is copied as the dense block that contains the strided view
     const int64_t span = (n_int - 1) * e_pt_stride + 2 * e_comp_stride + 1;
     if (e_pt_stride <= 0 || e_comp_stride <= 0 || span < 3 * n_int) return FEP_EINVAL;
-    const int64_t nb = n_int * (int64_t)sizeof(double);
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(device_id, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *e = nullptr, *ep = nullptr, *sh, *bu, *et, *cc, *s = nullptr, *ds = nullptr, *ip = nullptr, *cnt, *fld = nullptr;
-    FEP_TRY(E->buffer(0, span * (int64_t)sizeof(double), &e));
-    if (ep_prev_h) FEP_TRY(E->buffer(1, 4 * nb, &ep));
-    FEP_TRY(E->buffer(2, nb, &sh)); FEP_TRY(E->buffer(3, nb, &bu)); FEP_TRY(E->buffer(4, nb, &et)); FEP_TRY(E->buffer(5, nb, &cc));
-    if (s_h) FEP_TRY(E->buffer(6, 4 * nb, &s));
-    if (ds_h) FEP_TRY(E->buffer(7, 9 * nb, &ds));
-    if (ind_p_h) FEP_TRY(E->buffer(8, n_int, &ip));
-    FEP_TRY(E->buffer(9, 2 * sizeof(int64_t), &cnt));
-    if (field_h) FEP_TRY(E->buffer(kFieldBuffer, 4 * nb, &fld));
+    const size_t n = (size_t)n_int;
     static const bool timing = fep_tune("FEP_TIME_HOST") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    FEP_TRY(E->h2d(e, e_h, (size_t)span * sizeof(double)));
-    if (ep_prev_h) FEP_TRY(E->h2d(ep, ep_prev_h, (size_t)(4 * nb)));
-    FEP_TRY(E->h2d(sh, shear_h, (size_t)nb)); FEP_TRY(E->h2d(bu, bulk_h, (size_t)nb));
-    FEP_TRY(E->h2d(et, eta_h, (size_t)nb)); FEP_TRY(E->h2d(cc, c_h, (size_t)nb));
-    if (field_h) FEP_TRY(E->h2d(fld, field_h, (size_t)(4 * nb)));
+    auto ms = [t0 = std::chrono::steady_clock::now()] {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    const double* e = call.in(kRmE, e_h, (size_t)span);
+    double* ep = call.inout(kRmEp, ep_prev_h, 4 * n, accept != 0);
+    const double *sh = call.in(kRmShear, shear_h, n), *bu = call.in(kRmBulk, bulk_h, n);
+    const double *m3 = call.in(kRmM3, eta_h, n), *m4 = call.in(kRmM4, c_h, n), *fld = call.in(kRmField, field_h, 4 * n);
     if (timing) {
-        (void)hipStreamSynchronize(E->stream);
-        std::fprintf(stderr, "[fep] return_map_host: inputs on the device after %.3f ms\n",
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        (void)hipStreamSynchronize(call.stream());
+        std::fprintf(stderr, "[fep] return_map_host: inputs on the device after %.3f ms\n", ms());
     }
-    FEP_TRY(return_map_dev_impl(model, device_id, E->stream, n_int, (const double*)e, e_pt_stride, e_comp_stride, e0_h,
-                                (double*)ep, (const double*)sh, (const double*)bu, (const double*)et, (const double*)cc, accept,
-                                (double*)s, (double*)ds, (uint8_t*)ip, (int64_t*)cnt, (const double*)fld, scale));
-    if (s_h) FEP_TRY(E->d2h(s_h, s, (size_t)(4 * nb)));
-    if (ds_h) FEP_TRY(E->d2h(ds_h, ds, (size_t)(9 * nb)));
-    if (ind_p_h) FEP_TRY(E->d2h(ind_p_h, ip, (size_t)n_int));
-    if (counts_h) FEP_TRY(E->d2h(counts_h, cnt, 2 * sizeof(int64_t)));
-    if (accept && ep_prev_h) FEP_TRY(E->d2h(ep_prev_h, ep, (size_t)(4 * nb)));
-    const int rf = call.finish();
-    if (timing)
-        std::fprintf(stderr, "[fep] return_map_host: done after %.3f ms\n",
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    double *s = call.out(kRmS, s_h, 4 * n), *ds = call.out(kRmDs, ds_h, 9 * n);
+    uint8_t* ip = call.out(kRmIndP, ind_p_h, n);
+    int64_t* cnt = call.scratch<int64_t>(kRmCounts, 2);     // the kernels always count; copied back only if asked for
+    call.out(kRmCounts, counts_h, 2);
+    const int rf = call.run([&] {
+        return return_map_dev_impl(model, device_id, call.stream(), n_int, e, e_pt_stride, e_comp_stride, e0_h, ep, sh, bu, m3, m4,
+                                   accept, s, ds, ip, cnt, fld, scale);
+    });
+    if (timing) std::fprintf(stderr, "[fep] return_map_host: done after %.3f ms\n", ms());
     return rf;
 }
-
-#define FEP_GUARD(call) \
-    try { return call; } catch (const std::bad_alloc&) { return FEP_ENOMEM; } catch (...) { return FEP_EINVAL; }
 
 extern "C" int fep_return_map_host(int device_id, int64_t n_int,
                                    const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
@@ -653,8 +642,7 @@ extern "C" int fep_ctx_destroy(fep_ctx* c) {
 #endif
         for (void* p : c->owned) (void)hipFree(p);
         for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
-        for (void* p : c->hbuf)
-            if (p) (void)hipFree(p);
+        c->hbuf.release();
     }
     delete c;
     return FEP_OK;
@@ -993,6 +981,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     c->verbose = env_now("FEP_VERBOSE") != nullptr;
     c->n_e = n_e; c->n_n = n_n; c->n_int = n_e * n_q; c->n_dof = 2 * n_n;
     c->n_blk = (int64_t)S.ncol.size(); c->nnz = 4 * c->n_blk;
+    size_host_buffers(c);
     for (int64_t n = 0; n < n_n && !c->has_orphans; ++n) c->has_orphans = S.iptr[n + 1] == S.iptr[n];
     // host CSR pattern on DOFs
     c->indptr.resize(c->n_dof + 1);
@@ -1629,43 +1618,21 @@ static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const do
                           double* k_data_h, double* f_out_h, int64_t* counts_h,
                           const double* field_h = nullptr, double scale = 0.0) {
     if (!c || !u_h) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    const int64_t nb = c->n_int * (int64_t)sizeof(double);
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *u, *ep = nullptr, *eo = nullptr, *s = nullptr, *ds = nullptr, *ip = nullptr, *kd = nullptr, *f = nullptr, *cnt, *fld = nullptr;
-    FEP_TRY(ctx_buf(c, 0, c->n_dof * (int64_t)sizeof(double), &u));
-    if (ep_prev_h) FEP_TRY(ctx_buf(c, 1, 4 * nb, &ep));
-    if (e_out_h) FEP_TRY(ctx_buf(c, 2, 3 * nb, &eo));
-    if (s_h) FEP_TRY(ctx_buf(c, 3, 4 * nb, &s));
-    if (ds_h) FEP_TRY(ctx_buf(c, 4, 9 * nb, &ds));
-    if (ind_p_h) FEP_TRY(ctx_buf(c, 5, c->n_int, &ip));
-    if (k_data_h) FEP_TRY(ctx_buf(c, 6, c->nnz * (int64_t)sizeof(double), &kd));
-    if (f_out_h) FEP_TRY(ctx_buf(c, 7, c->n_dof * (int64_t)sizeof(double), &f));
-    FEP_TRY(ctx_buf(c, 8, 2 * sizeof(int64_t), &cnt));
-    if (u_planar) FEP_TRY(E->h2d_interleave2(u, u_h, (size_t)c->n_n));
-    else FEP_TRY(E->h2d(u, u_h, (size_t)c->n_dof * sizeof(double)));
-    if (ep_prev_h) FEP_TRY(E->h2d(ep, ep_prev_h, (size_t)(4 * nb)));
-    if (field_h) {
-        FEP_TRY(ctx_buf(c, kFieldBuffer, 4 * nb, &fld));
-        FEP_TRY(E->h2d(fld, field_h, (size_t)(4 * nb)));
-        FEP_TRY(fep_step_field_dev(c, E->stream, (const double*)u, e0_h, (const double*)fld, scale, (double*)ep, accept,
-                                   (double*)eo, (double*)s, (double*)ds, (uint8_t*)ip, (double*)kd, (double*)f, (int64_t*)cnt));
-    } else {
-        FEP_TRY(fep_step_dev(c, E->stream, (const double*)u, e0_h, (double*)ep, accept, (double*)eo, (double*)s, (double*)ds,
-                             (uint8_t*)ip, (double*)kd, (double*)f, (int64_t*)cnt));
-    }
-    // the largest result first: its transfer hides the others' set-up
-    if (k_data_h) FEP_TRY(E->d2h(k_data_h, kd, (size_t)c->nnz * sizeof(double)));
-    if (f_out_h) FEP_TRY(E->d2h(f_out_h, f, (size_t)c->n_dof * sizeof(double)));
-    if (ds_h) FEP_TRY(E->d2h(ds_h, ds, (size_t)(9 * nb)));
-    if (s_h) FEP_TRY(E->d2h(s_h, s, (size_t)(4 * nb)));
-    if (e_out_h) FEP_TRY(E->d2h(e_out_h, eo, (size_t)(3 * nb)));
-    if (ind_p_h) FEP_TRY(E->d2h(ind_p_h, ip, (size_t)c->n_int));
-    if (counts_h) FEP_TRY(E->d2h(counts_h, cnt, 2 * sizeof(int64_t)));
-    if (accept && ep_prev_h) FEP_TRY(E->d2h(ep_prev_h, ep, (size_t)(4 * nb)));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const size_t n = (size_t)c->n_int, n_dof = (size_t)c->n_dof;
+    const double* u = u_planar ? call.in_interleave2(kBufU, u_h, (size_t)c->n_n) : call.in(kBufU, u_h, n_dof);
+    double* ep = call.inout(kBufEp, ep_prev_h, 4 * n, accept != 0);
+    const double* fld = call.in(kBufField, field_h, 4 * n);
+    // copied back in this order: the largest result first, its transfer hides the others' set-up
+    double *kd = call.out(kBufK, k_data_h, (size_t)c->nnz), *f = call.out(kBufF, f_out_h, n_dof);
+    double *ds = call.out(kBufDs, ds_h, 9 * n), *s = call.out(kBufS, s_h, 4 * n), *eo = call.out(kBufE, e_out_h, 3 * n);
+    uint8_t* ip = call.out(kBufIndP, ind_p_h, n);
+    int64_t* cnt = call.scratch<int64_t>(kBufCounts, 2);    // the kernels always count; copied back only if asked for
+    call.out(kBufCounts, counts_h, 2);
+    return call.run([&] {
+        return field_h ? fep_step_field_dev(c, call.stream(), u, e0_h, fld, scale, ep, accept, eo, s, ds, ip, kd, f, cnt)
+                       : fep_step_dev(c, call.stream(), u, e0_h, ep, accept, eo, s, ds, ip, kd, f, cnt);
+    });
 }
 
 extern "C" int fep_step_host(fep_ctx* c, const double* u_h, const double* e0_h, double* ep_prev_h, int accept,
@@ -1691,20 +1658,11 @@ extern "C" int fep_step_host_planar(fep_ctx* c, const double* u2_h, const double
 static int assemble_host_impl(fep_ctx* c, const double* ds_h, const double* s_h, double* k_data_h, double* f_out_h) {
     if (!c) return FEP_EINVAL;
     if ((k_data_h && !ds_h) || (f_out_h && !s_h)) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    const int64_t nb = c->n_int * (int64_t)sizeof(double);
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *ds = nullptr, *s = nullptr, *kd = nullptr, *f = nullptr;
-    if (ds_h) { FEP_TRY(ctx_buf(c, 4, 9 * nb, &ds)); FEP_TRY(E->h2d(ds, ds_h, (size_t)(9 * nb))); }
-    if (s_h) { FEP_TRY(ctx_buf(c, 3, 4 * nb, &s)); FEP_TRY(E->h2d(s, s_h, (size_t)(3 * nb))); }
-    if (k_data_h) FEP_TRY(ctx_buf(c, 6, c->nnz * (int64_t)sizeof(double), &kd));
-    if (f_out_h) FEP_TRY(ctx_buf(c, 7, c->n_dof * (int64_t)sizeof(double), &f));
-    FEP_TRY(fep_assemble_dev(c, E->stream, (const double*)ds, (const double*)s, (double*)kd, (double*)f));
-    if (k_data_h) FEP_TRY(E->d2h(k_data_h, kd, (size_t)c->nnz * sizeof(double)));
-    if (f_out_h) FEP_TRY(E->d2h(f_out_h, f, (size_t)c->n_dof * sizeof(double)));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const size_t n = (size_t)c->n_int;
+    const double *ds = call.in(kBufDs, ds_h, 9 * n), *s = call.in(kBufS, s_h, 3 * n);     // (s: 3 n_int into the 4 n_int block)
+    double *kd = call.out(kBufK, k_data_h, (size_t)c->nnz), *f = call.out(kBufF, f_out_h, (size_t)c->n_dof);
+    return call.run([&] { return fep_assemble_dev(c, call.stream(), ds, s, kd, f); });
 }
 
 extern "C" int fep_assemble_host(fep_ctx* c, const double* ds_h, const double* s_h, double* k_data_h, double* f_out_h) {
@@ -1766,17 +1724,10 @@ extern "C" int fep_transform_dev(fep_ctx* c, void* stream, const double* q_int_d
 
 static int transform_host_impl(fep_ctx* c, const double* q_int_h, double* q_node_h) {
     if (!c || !q_int_h || !q_node_h) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    void *q, *o;
-    FEP_TRY(ctx_buf(c, 9, c->n_int * (int64_t)sizeof(double), &q));
-    FEP_TRY(ctx_buf(c, 10, c->n_n * (int64_t)sizeof(double), &o));
-    FEP_TRY(E->h2d(q, q_int_h, (size_t)c->n_int * sizeof(double)));
-    FEP_TRY(fep_transform_dev(c, E->stream, (const double*)q, (double*)o));
-    FEP_TRY(E->d2h(q_node_h, o, (size_t)c->n_n * sizeof(double)));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const double* q = call.in(kBufQ, q_int_h, (size_t)c->n_int);
+    double* o = call.out(kBufNode, q_node_h, (size_t)c->n_n);
+    return call.run([&] { return fep_transform_dev(c, call.stream(), q, o); });
 }
 
 extern "C" int fep_transform_host(fep_ctx* c, const double* q_int_h, double* q_node_h) {
@@ -1808,18 +1759,11 @@ extern "C" int fep_load_volume_dev(fep_ctx* c, void* stream, const double* hatp_
 static int load_volume_host_impl(fep_ctx* c, const double* hatp_h, const double* f_v_h, double fx, double fy,
                                  const double* weight_h, double* f_out_h) {
     if (!c || !hatp_h || !f_out_h) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    const size_t nb = (size_t)c->n_int * sizeof(double);
-    void *f = nullptr, *w = nullptr, *o = nullptr;
-    if (f_v_h) { FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &f)); FEP_TRY(E->h2d(f, f_v_h, 2 * nb)); }
-    if (weight_h) { FEP_TRY(ctx_buf(c, 9, (int64_t)nb, &w)); FEP_TRY(E->h2d(w, weight_h, nb)); }
-    FEP_TRY(ctx_buf(c, 7, c->n_dof * (int64_t)sizeof(double), &o));
-    FEP_TRY(fep_load_volume_dev(c, E->stream, hatp_h, (const double*)f, fx, fy, (const double*)w, (double*)o));
-    FEP_TRY(E->d2h(f_out_h, o, (size_t)c->n_dof * sizeof(double)));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const size_t n = (size_t)c->n_int;
+    const double *f = call.in(kBufFv, f_v_h, 2 * n), *w = call.in(kBufWeight, weight_h, n);
+    double* o = call.out(kBufLoad, f_out_h, (size_t)c->n_dof);
+    return call.run([&] { return fep_load_volume_dev(c, call.stream(), hatp_h, f, fx, fy, w, o); });
 }
 
 extern "C" int fep_load_volume_host(fep_ctx* c, const double* hatp_h, const double* f_v_h, double fx, double fy,
@@ -1843,16 +1787,9 @@ extern "C" int fep_ctx_point_coords_dev(fep_ctx* c, void* stream, const double* 
 
 static int point_coords_host_impl(fep_ctx* c, const double* hatp_h, double* xq_h) {
     if (!c || !hatp_h || !xq_h) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    const size_t nb = (size_t)c->n_int * sizeof(double);
-    void* o = nullptr;
-    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &o));
-    FEP_TRY(fep_ctx_point_coords_dev(c, E->stream, hatp_h, (double*)o));
-    if (c->n_int > 0) FEP_TRY(E->d2h(xq_h, o, 2 * nb));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    double* o = call.out(kBufXq, xq_h, 2 * (size_t)c->n_int);
+    return call.run([&] { return fep_ctx_point_coords_dev(c, call.stream(), hatp_h, o); });
 }
 
 extern "C" int fep_ctx_point_coords_host(fep_ctx* c, const double* hatp_h, double* xq_h) {
@@ -1894,18 +1831,10 @@ extern "C" int fep_estimate_dev(fep_ctx* c, void* stream, const double* hatp_h, 
 
 static int recover_stress_host_impl(fep_ctx* c, const double* s_h, double* s_node_h) {
     if (!c || !s_h || !s_node_h) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(c->device));
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    const size_t nb = (size_t)c->n_int * sizeof(double), nn = (size_t)c->n_n * sizeof(double);
-    void *s = nullptr, *o = nullptr;
-    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &s));
-    FEP_TRY(ctx_buf(c, 12, (int64_t)(4 * nn), &o));
-    FEP_TRY(E->h2d(s, s_h, 4 * nb));
-    FEP_TRY(fep_recover_stress_dev(c, E->stream, (const double*)s, (double*)o));
-    if (c->n_n > 0) FEP_TRY(E->d2h(s_node_h, o, 4 * nn));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const double* s = call.in(kBufS, s_h, 4 * (size_t)c->n_int);
+    double* o = call.out(kBufSNode, s_node_h, 4 * (size_t)c->n_n);
+    return call.run([&] { return fep_recover_stress_dev(c, call.stream(), s, o); });
 }
 
 extern "C" int fep_recover_stress_host(fep_ctx* c, const double* s_h, double* s_node_h) {
@@ -1917,22 +1846,10 @@ static int estimate_host_impl(fep_ctx* c, const double* hatp_h, const double* s_
     if (!c || !s_h || !s_node_h || !eta2_h) return FEP_EINVAL;
     if (c->elem_type != FEP_P1 && !hatp_h) return FEP_EINVAL;
     if (!c->have_materials) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(c->device));
-    fep_stage::Engine* E = nullptr;
-    FEP_TRY(fep_stage::engine(c->device, &E));
-    fep_stage::EngineCall call(E);                      // drains the engine on every exit that is not a completed finish()
-    const size_t nb = (size_t)c->n_int * sizeof(double), nn = (size_t)c->n_n * sizeof(double);
-    void *s = nullptr, *sn = nullptr, *o = nullptr, *st = nullptr;
-    FEP_TRY(ctx_buf(c, 3, (int64_t)(4 * nb), &s));
-    FEP_TRY(ctx_buf(c, 12, (int64_t)(4 * nn), &sn));
-    FEP_TRY(ctx_buf(c, 13, c->n_e * (int64_t)sizeof(double), &o));
-    if (stats_h) FEP_TRY(ctx_buf(c, 14, 4 * (int64_t)sizeof(double), &st));
-    FEP_TRY(E->h2d(s, s_h, 4 * nb));
-    if (c->n_n > 0) FEP_TRY(E->h2d(sn, s_node_h, 4 * nn));
-    FEP_TRY(fep_estimate_dev(c, E->stream, hatp_h, (const double*)s, (const double*)sn, (double*)o, (double*)st));
-    FEP_TRY(E->d2h(eta2_h, o, (size_t)c->n_e * sizeof(double)));
-    if (stats_h) FEP_TRY(E->d2h(stats_h, st, 4 * sizeof(double)));
-    return call.finish();
+    fep_stage::HostCall call(c->device, &c->hbuf);
+    const double *s = call.in(kBufS, s_h, 4 * (size_t)c->n_int), *sn = call.in(kBufSNode, s_node_h, 4 * (size_t)c->n_n);
+    double *o = call.out(kBufEta2, eta2_h, (size_t)c->n_e), *st = call.out(kBufStats, stats_h, 4);
+    return call.run([&] { return fep_estimate_dev(c, call.stream(), hatp_h, s, sn, o, st); });
 }
 
 extern "C" int fep_estimate_host(fep_ctx* c, const double* hatp_h, const double* s_h, const double* s_node_h, double* eta2_h,

@@ -1,6 +1,7 @@
 // Shared by the translation units of libfep_hip.so: error plumbing of the C ABI (include/fep.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <new>
 
 #include "../../include/fep.h"
 
@@ -20,6 +21,9 @@ extern __attribute__((visibility("hidden"))) thread_local int fep_g_last_hip;   
         int _r = (expr);               \
         if (_r != FEP_OK) return _r;   \
     } while (0)
+// Body of an extern "C" entry point: nothing may leave it by exception
+#define FEP_GUARD(call) \
+    try { return call; } catch (const std::bad_alloc&) { return FEP_ENOMEM; } catch (...) { return FEP_EINVAL; }
 
 __attribute__((visibility("hidden"))) int fep_set_device(int dev);
 // fep_mesh.hip, for fep_estimate_dev: the statistics {total, max, non-finite, n} of an indicator array, enqueued on `st`;

@@ -1228,9 +1228,6 @@ static int area_stats_host_impl(int device_id, int64_t n_e, int64_t n_n, const i
     return FEP_OK;
 }
 
-#define FEP_GUARD(call) \
-    try { return call; } catch (const std::bad_alloc&) { return FEP_ENOMEM; } catch (...) { return FEP_EINVAL; }
-
 extern "C" int fep_mesh_create(fep_mesh** mesh_out, int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem,
                                const double* coord, int on_device) {
     FEP_GUARD(mesh_create_impl(mesh_out, device_id, (hipStream_t)stream, n_e, n_n, elem, coord, on_device))

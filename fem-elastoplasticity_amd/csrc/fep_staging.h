@@ -17,6 +17,8 @@
 #pragma once
 #ifndef FEP_STAGING_HOST_STUB
 #include "fep_common.h"
+#else
+inline int fep_set_device(int) { return FEP_OK; }       // the host build has no device to select
 #endif
 
 #include <algorithm>
@@ -194,6 +196,30 @@ public:
 };
 inline CopyPool& pool() { static CopyPool p; return p; }
 
+// Persistent device blocks by index, grow-only: the staging buffers of the *_host entry points
+struct DeviceStore {
+    // (block, its bytes), as Engine::dev always held them; cap: the size the owner states for the block (0: none)
+    struct Block : std::pair<void*, size_t> { size_t cap = 0; Block() : std::pair<void*, size_t>(nullptr, 0) {} };
+    std::vector<Block> blocks;
+    explicit DeviceStore(int n = 0) : blocks((size_t)n) {}
+    Block& operator[](size_t idx) { return blocks[idx]; }
+    // Block `idx` with room for `bytes` (and never less than its stated size).  A block that has to grow is freed first;
+    // only work queued on `stream` can still be using it (its users hold that stream's Engine::call), so that is the wait.
+    int reserve(int idx, size_t bytes, hipStream_t stream, void** out) {
+        if ((int)blocks.size() <= idx) blocks.resize((size_t)idx + 1);
+        Block& b = blocks[(size_t)idx];
+        bytes = std::max({bytes, b.cap, (size_t)1});
+        if (b.second < bytes) {
+            if (b.first) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(b.first)); b.first = nullptr; b.second = 0; }
+            HIP_TRY(hipMalloc(&b.first, bytes));
+            b.second = bytes;
+        }
+        *out = b.first;
+        return FEP_OK;
+    }
+    void release() { for (Block& b : blocks) { if (b.first) (void)hipFree(b.first); b.first = nullptr; b.second = 0; } }
+};
+
 // ---------------------------------------------------------------------------------------
 // per-device engine: one stream, a ring of pinned slots, persistent device buffers
 // ---------------------------------------------------------------------------------------
@@ -207,7 +233,7 @@ struct Engine {
     hipEvent_t ev[kSlots] = {};
     struct Pending { void* dst = nullptr; size_t bytes = 0; } pend[kSlots];
     int next = 0;
-    std::vector<std::pair<void*, size_t>> dev;           // persistent device buffers by index (grow-only)
+    DeviceStore dev;                                     // staging buffers of the calls that have no context (the return map)
 
     int init(int d) {
         device = d;
@@ -218,18 +244,7 @@ struct Engine {
         }
         return FEP_OK;
     }
-    int buffer(int idx, size_t bytes, void** out) {
-        if ((int)dev.size() <= idx) dev.resize(idx + 1, {nullptr, 0});
-        if (bytes == 0) bytes = 1;
-        if (dev[idx].second < bytes) {
-            if (dev[idx].first) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(dev[idx].first)); dev[idx] = {nullptr, 0}; }
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, bytes));
-            dev[idx] = {p, bytes};
-        }
-        *out = dev[idx].first;
-        return FEP_OK;
-    }
+    int buffer(int idx, size_t bytes, void** out) { return dev.reserve(idx, bytes, stream, out); }
     // the slot's DMA has finished; a device -> host chunk parked in it goes to its pageable destination
     int settle(int i) {
         HIP_TRY(hipEventSynchronize(ev[i]));
@@ -291,17 +306,6 @@ struct Engine {
     }
 };
 
-// Scope of one *_host entry point: holds the engine's call lock; unless finish() succeeded (disarm) the engine is drained
-// on the way out, whatever the exit path (error return or exception).
-struct EngineCall {
-    Engine* E;
-    std::unique_lock<std::mutex> lock;
-    bool armed = true;
-    explicit EngineCall(Engine* e) : E(e), lock(e->call) {}
-    ~EngineCall() { if (armed) E->drain(); }
-    int finish() { const int r = E->finish(); if (r == FEP_OK) armed = false; return r; }
-};
-
 // engine of a device (created on first use, lives as long as the library)
 inline int engine(int device, Engine** out) {
     static std::mutex m;
@@ -318,5 +322,82 @@ inline int engine(int device, Engine** out) {
     *out = it->second;
     return FEP_OK;
 }
+
+// Scope of one *_host entry point: holds the engine's call lock; unless finish() succeeded (disarm) the engine is drained
+// on the way out, whatever the exit path (error return or exception).
+struct EngineCall {
+    Engine* E = nullptr;
+    std::unique_lock<std::mutex> lock;
+    bool armed = false;
+    explicit EngineCall(Engine* e = nullptr) { if (e) open(e); }            // without an engine: nothing held until open()
+    void open(Engine* e) { E = e; lock = std::unique_lock<std::mutex>(e->call); armed = true; }
+    ~EngineCall() { if (armed) E->drain(); }
+    int finish() { const int r = E->finish(); if (r == FEP_OK) armed = false; return r; }
+};
+
+// One *_host entry point from end to end: selects the device, looks up its engine, holds its call lock (EngineCall), stages
+// the caller's arrays into the blocks of `store` (the engine's own if none is given) and copies the results back.  A NULL
+// host array yields a NULL device pointer and no transfer.  The first error sticks: later operations do nothing, status()
+// and run() return it.  in: reserve the block (at its stated size if that is larger) and copy `count` elements in now;
+// out: reserve now, copy back in run(), in the order of the out() calls; inout: as in, copied back after every out() if
+// `back`; scratch: reserve only.
+class HostCall {
+    Engine* E = nullptr;
+    DeviceStore* store = nullptr;
+    EngineCall scope;
+    int rc;
+    struct Back { void* h = nullptr; const void* d = nullptr; size_t bytes = 0; };
+    static constexpr int kMaxOut = 8;
+    Back outs[kMaxOut], last;
+    int n_out = 0;
+
+public:
+    explicit HostCall(int device, DeviceStore* s = nullptr) {
+        rc = fep_set_device(device);
+        if (rc == FEP_OK) rc = engine(device, &E);
+        if (rc != FEP_OK) return;
+        scope.open(E);
+        store = s ? s : &E->dev;
+    }
+    int status() const { return rc; }
+    hipStream_t stream() const { return E->stream; }
+
+    template <class T> T* scratch(int buf, size_t count) {
+        void* p = nullptr;
+        if (rc == FEP_OK) rc = store->reserve(buf, count * sizeof(T), E->stream, &p);
+        return rc == FEP_OK ? (T*)p : nullptr;
+    }
+    template <class T> const T* in(int buf, const T* h, size_t count) {
+        T* d = h ? scratch<T>(buf, count) : nullptr;
+        if (d) rc = E->h2d(d, h, count * sizeof(T));
+        return rc == FEP_OK ? d : nullptr;
+    }
+    // the (2, n) planar host array as n interleaved pairs (Engine::h2d_interleave2)
+    const double* in_interleave2(int buf, const double* h, size_t n) {
+        double* d = h ? scratch<double>(buf, 2 * n) : nullptr;
+        if (d) rc = E->h2d_interleave2(d, h, n);
+        return rc == FEP_OK ? d : nullptr;
+    }
+    template <class T> T* out(int buf, T* h, size_t count) {
+        T* d = h ? scratch<T>(buf, count) : nullptr;
+        if (!d) return nullptr;
+        if (n_out == kMaxOut) { rc = FEP_ESTATE; return nullptr; }
+        outs[n_out++] = Back{h, d, count * sizeof(T)};
+        return d;
+    }
+    template <class T> T* inout(int buf, T* h, size_t count, bool back) {
+        T* d = const_cast<T*>(in<T>(buf, h, count));
+        if (d && back) last = Back{h, d, count * sizeof(T)};
+        return d;
+    }
+    // the kernels (`dev`, unless an operation before it failed), then the copies back and the engine's finish()
+    template <class F> int run(F&& dev) {
+        if (rc == FEP_OK) rc = dev();
+        for (int i = 0; i < n_out && rc == FEP_OK; ++i) rc = E->d2h(outs[i].h, outs[i].d, outs[i].bytes);
+        if (rc == FEP_OK && last.h) rc = E->d2h(last.h, last.d, last.bytes);
+        if (rc == FEP_OK) rc = scope.finish();
+        return rc;
+    }
+};
 
 }  // namespace fep_stage

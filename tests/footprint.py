@@ -154,7 +154,7 @@ def unchanged(view, snapshot, name='input'):
 
 
 def scrub(ctx, U, Ep, mats_kw=None):
-    """Leaves nothing of an earlier call in the context's persistent device buffers (fep_api.hip: ctx_buf), so that a
+    """Leaves nothing of an earlier call in the context's persistent device buffers (fep_api.hip: fep_ctx::hbuf), so that a
     following K,F-only / K-only / F-only / accepting step or assemble() cannot pass a bitwise pin with what the call before
     it left there: one full-output host step on another state (-1.7 U, another plastic strain; `mats_kw`: the step's e0 /
     e0_field / e0_scale keywords), then assemble() of all-NaN ds and s.  Afterwards the K and F buffers hold NaN and the

@@ -15,10 +15,11 @@
 //   4. two engines driven by two threads
 //   5. pageable transfers LONGER THAN THE RING, each direction alone and both together, at 0, 1, 8, slot - 8, slot, slot + 8,
 //      ring, ring + 8 and 5.5 slots + 1 bytes; h2d_interleave2 at 1, per - 1, per, per + 1, 4 per + 1 and 5 per + 1337 nodes
-//   6. a call shaped like return_map_host_impl (seven inputs of unequal sizes, a kernel, five outputs; pinned blocks, views
-//      into the middle of one, pageable arrays 8 bytes off their allocation, one pageable array both input and output), four
-//      times back to back so that the ring starts at each of its four positions
-//   7. small -> large -> small calls on one engine (Engine::buffer's grow path), and a buffer that grows while a copy into
+//   6. a call shaped like return_map_host_impl, made through the scope that function uses (HostCall: seven inputs of unequal
+//      sizes, a kernel, five outputs; pinned blocks, views into the middle of one, pageable arrays 8 bytes off their
+//      allocation, one pageable array both input and output), four times back to back so that the ring starts at each of
+//      its four positions
+//   7. small -> large -> small calls on one engine (DeviceStore's grow path), and a buffer that grows while a copy into
 //      its old block is still queued
 // Every check of 5 - 7 compares every byte of the result, and every destination ends in a canary block (one slot long, so a
 // whole-slot overrun stays inside the allocation) that must come back untouched; sources have no slack, so ASan sees a read
@@ -33,6 +34,9 @@
 //   hipEventRecord before its hipMemcpyAsync, in d2h            [engine error path] the round trip after the failed call differs
 //   hipEventRecord before its hipMemcpyAsync, in interleave2    [interleave2, 2097153 nodes] device block differs
 //   finish() synchronises without settling the parked chunks   [engine error path] the round trip after the failed call differs
+//   HostCall::run() without the copy back of the inout array    [return-map-shaped call, run 0] ep differs
+//   DeviceStore::reserve frees a block without synchronising   [buffer grows while a copy into its old block is queued]: the
+//                                                              ASan build reports the queued copy's write into the freed block
 //   tail size min(kSlotBytes, bytes - off) -> kSlotBytes        h2d, d2h: [engine error path], interleave2: [interleave2, 1 nodes]:
 //     (in h2d, d2h, or min(per, n - off) -> per in interleave2)  the ASan build reports the access past the end of a heap block,
 //                                                              deterministically.  The TSan build checks no bounds: there the
@@ -386,6 +390,7 @@ struct RmHost {                                          // the caller's arrays:
     Buf extra{8, false, 0};
 };
 
+static constexpr int kRmDevice = 12;                     // the engine of check 6
 static int rm_call(Engine* E, RmHost& h, uint64_t seed, bool extra_first, int* start_slot) {
     const size_t n = RmHost::n, nb = n * 8;
     fill(h.e.p, 3 * nb, seed); fill(h.sh.p, nb, seed + 1); fill(h.bu.p, nb, seed + 2); fill(h.et.p, nb, seed + 3);
@@ -400,23 +405,25 @@ static int rm_call(Engine* E, RmHost& h, uint64_t seed, bool extra_first, int* s
     rm_compute(&ref);
     RmArgs dev{};
     {
-        EngineCall call(E);
-        void *e, *ep, *sh, *bu, *et, *cc, *s, *ds, *ip, *cnt, *fld, *x;
-        CHECK(E->buffer(0, 3 * nb, &e) == FEP_OK && E->buffer(1, 4 * nb, &ep) == FEP_OK && E->buffer(2, nb, &sh) == FEP_OK);
-        CHECK(E->buffer(3, nb, &bu) == FEP_OK && E->buffer(4, nb, &et) == FEP_OK && E->buffer(5, nb, &cc) == FEP_OK);
-        CHECK(E->buffer(6, 4 * nb, &s) == FEP_OK && E->buffer(7, 9 * nb, &ds) == FEP_OK && E->buffer(8, n, &ip) == FEP_OK);
-        CHECK(E->buffer(9, 16, &cnt) == FEP_OK && E->buffer(10, 4 * nb, &fld) == FEP_OK && E->buffer(11, 8, &x) == FEP_OK);
-        if (extra_first) CHECK(E->h2d(x, h.extra.p, 8) == FEP_OK);      // one more chunk: the ring starts one slot further on
+        enum { kE, kEp, kSh, kBu, kEt, kCc, kS, kDs, kIp, kCnt, kFld, kExtra };
+        HostCall call(kRmDevice);
+        CHECK(call.status() == FEP_OK);
+        if (extra_first) call.in(kExtra, (const uint64_t*)h.extra.p, 1);    // one more chunk: the ring starts one slot further on
         *start_slot = E->next;
-        CHECK(E->h2d(e, h.e.p, 3 * nb) == FEP_OK && E->h2d(ep, h.ep.p, 4 * nb) == FEP_OK);
-        CHECK(E->h2d(sh, h.sh.p, nb) == FEP_OK && E->h2d(bu, h.bu.p, nb) == FEP_OK);
-        CHECK(E->h2d(et, h.et.p, nb) == FEP_OK && E->h2d(cc, h.cc.p, nb) == FEP_OK && E->h2d(fld, h.fld.p, 4 * nb) == FEP_OK);
-        dev = RmArgs{n, (const uint64_t*)e, (const uint64_t*)sh, (const uint64_t*)bu, (const uint64_t*)et, (const uint64_t*)cc,
-                     (const uint64_t*)fld, (uint64_t*)ep, (uint64_t*)s, (uint64_t*)ds, (unsigned char*)ip, (uint64_t*)cnt};
-        stub_launch(E->stream, rm_compute, &dev);
-        CHECK(E->d2h(h.s.p, s, 4 * nb) == FEP_OK && E->d2h(h.ds.p, ds, 9 * nb) == FEP_OK && E->d2h(h.ip.p, ip, n) == FEP_OK);
-        CHECK(E->d2h(h.cnt.p, cnt, 16) == FEP_OK && E->d2h(h.ep.p, ep, 4 * nb) == FEP_OK);
-        CHECK(call.finish() == FEP_OK);
+        dev.n = n;
+        dev.e = call.in(kE, (const uint64_t*)h.e.p, 3 * n);
+        dev.ep = call.inout(kEp, (uint64_t*)h.ep.p, 4 * n, true);
+        dev.sh = call.in(kSh, (const uint64_t*)h.sh.p, n);
+        dev.bu = call.in(kBu, (const uint64_t*)h.bu.p, n);
+        dev.et = call.in(kEt, (const uint64_t*)h.et.p, n);
+        dev.cc = call.in(kCc, (const uint64_t*)h.cc.p, n);
+        dev.fld = call.in(kFld, (const uint64_t*)h.fld.p, 4 * n);
+        dev.s = call.out(kS, (uint64_t*)h.s.p, 4 * n);
+        dev.ds = call.out(kDs, (uint64_t*)h.ds.p, 9 * n);
+        dev.ip = call.out(kIp, (unsigned char*)h.ip.p, n);
+        dev.cnt = call.scratch<uint64_t>(kCnt, 2);
+        call.out(kCnt, (uint64_t*)h.cnt.p, 2);
+        CHECK(call.run([&] { stub_launch(call.stream(), rm_compute, &dev); return (int)FEP_OK; }) == FEP_OK);
     }
     CHECK(std::memcmp(h.s.p, r_s.data(), 4 * nb) == 0);
     CHECK(std::memcmp(h.ds.p, r_ds.data(), 9 * nb) == 0);
@@ -432,7 +439,7 @@ static int rm_call(Engine* E, RmHost& h, uint64_t seed, bool extra_first, int* s
 
 static int test_return_map_shaped_calls() {
     Engine* E = nullptr;
-    CHECK(engine(12, &E) == FEP_OK);
+    CHECK(engine(kRmDevice, &E) == FEP_OK);              // the engine HostCall(kRmDevice) finds: its ring position is read below
     RmHost h;
     fill(h.ep.p, 4 * RmHost::n * 8, 99);
     fill(h.extra.p, 8, 98);
@@ -449,7 +456,7 @@ static int test_return_map_shaped_calls() {
 }
 
 // ---------------------------------------------------------------------------------------
-// Engine::buffer's grow path
+// DeviceStore's grow path
 // ---------------------------------------------------------------------------------------
 static int sized_round_trip(Engine* E, size_t bytes, uint64_t seed, bool check_rest, size_t rest) {
     Buf src(bytes, false, 0), out(bytes, false, kCanary);

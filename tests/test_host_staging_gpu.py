@@ -311,6 +311,29 @@ def test_assemble_transform_loads_and_point_coords(big):
     assert np.array_equal(xq, XQ.cpu().numpy()) and sc.canary_intact(xq)
 
 
+@pytest.mark.parametrize('stats', [True, False], ids=['stats', 'no-stats'])
+def test_recover_stress_and_estimate(big, stats):
+    """fep_recover_stress_host and fep_estimate_host on the step's own s against their _dev forms, with the statistics and
+    with a NULL stats_h (no statistics kernel, nothing copied back for it).  Pageable arrays, canary tails."""
+    import torch
+    ctx, l = big['ctx'], _lib.lib()
+    use_model(ctx, 'dp')
+    step = dev_step(big, 'dp', sc.STEP_KEYS)
+    eta2_d, stats_d, sn_d = ctx.estimate_dev(_t(step['s']), stats=stats)
+    torch.cuda.synchronize()
+    s = sc.place('pageable', step['s'])
+    sn = sc.pageable((4, ctx.n_n), canary=True)
+    assert l.fep_recover_stress_host(ctx.handle, _p(s), _p(sn)) == 0
+    assert np.array_equal(sn, sn_d.cpu().numpy()) and sc.canary_intact(sn)
+    eta2 = sc.pageable(ctx.n_e, canary=True)
+    st = sc.pageable(4, canary=True) if stats else None
+    assert l.fep_estimate_host(ctx.handle, _p(ctx._hatp(None)), _p(s), _p(sn), _p(eta2), _p(st)) == 0
+    assert np.array_equal(eta2, eta2_d.cpu().numpy()) and sc.canary_intact(eta2)
+    if stats:
+        assert np.array_equal(st, stats_d.cpu().numpy()) and sc.canary_intact(st)
+    assert np.array_equal(s, step['s'])                                              # the input is the caller's
+
+
 # ---- sequences ---------------------------------------------------------------------------------------------------------------
 def _small_case():
     mesh = fep.square_mesh(sc.SMALL_MESH_N, 'P1', 10)
