@@ -296,35 +296,6 @@ static E0 make_e0(const double* e0_h) {
     return z;
 }
 
-// Allocating is illegal while the stream is being captured into a graph: such a call is refused (FEP_ESTATE) instead of
-// breaking the capture — run the same call once outside the capture first (fep.h, fep_step_dev).
-static int scratch_alloc_allowed(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_OK; }
-    return cs == hipStreamCaptureStatusNone ? FEP_OK : FEP_ESTATE;
-}
-
-// Per-workgroup branch counters of the mesh-free return map (summed by counts_reduce_kernel): one grow-only buffer per
-// (device, stream), so that calls on different streams never share it.  The kernel used to add its two counters to the
-// caller's counts with global atomics — one contended pair per workgroup, the pattern that cost the P1 kernels 70 us per
-// launch in round 1.  Growing the buffer is an allocation: refused (FEP_ESTATE) while the stream is being captured.
-static int rm_scratch(int device, hipStream_t st, size_t n_blocks, uint2** out) {
-    static std::mutex m;
-    static auto& bufs = *new std::map<std::pair<int, void*>, std::pair<uint2*, size_t>>();
-    std::lock_guard<std::mutex> g(m);
-    auto& b = bufs[{device, (void*)st}];
-    if (b.second < n_blocks) {
-        FEP_TRY(scratch_alloc_allowed(st));
-        static auto& retired = *new std::vector<uint2*>();
-        if (b.first) { retired.push_back(b.first); b = {nullptr, 0}; }
-        const size_t cap = n_blocks + n_blocks / 4 + 64;
-        HIP_TRY(hipMalloc((void**)&b.first, cap * sizeof(uint2)));
-        b.second = cap;
-    }
-    *out = b.first;
-    return FEP_OK;
-}
-
 // The material models, one row each, indexed by FEP_MODEL_*: the tag a model puts into its kernels' names and its kernel of each
 // point-kernel family.  point_*_kernel<NP, NQ> has no Drucker-Prager row, that step being the fused element route: model - 1.
 constexpr int kModels = 4;
@@ -365,8 +336,13 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     hipStream_t st = (hipStream_t)stream;
     if (n_int == 0) { if (counts_d) HIP_TRY(hipMemsetAsync(counts_d, 0, 2 * sizeof(int64_t), st)); return FEP_OK; }
     const unsigned n_blocks = grid_for(n_int, kBlock);
+    // Per-workgroup branch counters (summed by counts_reduce_kernel): the grow-only scratch of (device, stream).  The kernel used
+    // to add its two counters to the caller's counts with global atomics — one contended pair per workgroup, the pattern that
+    // cost the P1 kernels 70 us per launch in round 1.
     uint2* blk = nullptr;
-    if (counts_d) FEP_TRY(rm_scratch(device_id, st, n_blocks, &blk));
+    if (counts_d)
+        FEP_TRY(stream_scratch(kScratchRmCounts, device_id, st, n_blocks * sizeof(uint2),
+                               ((size_t)n_blocks + n_blocks / 4 + 64) * sizeof(uint2), (void**)&blk));
     if (field_d)
         hipLaunchKernelGGL(kReturnMapFieldKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
                            n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,

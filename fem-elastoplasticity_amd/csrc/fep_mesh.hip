@@ -13,13 +13,10 @@
 // Also here, because it is context-free and produces what fep_mesh_mark reads: the fixed-order sums, the statistics and the
 // bulk marking of the error indicator (include/fep.h, "recovered-stress error indicator"; ind_level_kernel, fep_mark_bulk_*).
 #include "fep_common.h"
+#include "fep_staging.h"
 
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <new>
-#include <utility>
-#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -745,18 +742,16 @@ __global__ void __launch_bounds__(kBlock) ind_level_kernel(int64_t n, const doub
     }
 }
 
-struct DeviceBlocks {
-    std::vector<void*> p;
-    ~DeviceBlocks() { for (void* q : p) (void)hipFree(q); }
-    template <class T>
-    int get(T** out, int64_t count) {
-        void* q = nullptr;
-        HIP_TRY(hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(T)));
-        p.push_back(q);
-        *out = (T*)q;
-        return FEP_OK;
-    }
-};
+using fep_stage::reserve_as;
+using fep_stage::ScopedStore;
+
+// Device blocks of a mesh (fep_mesh::blocks: made once at their final size, released with the mesh), ...
+enum MeshBuf { kMeshElem, kMeshCoord, kMeshNbr, kMeshMask, kMeshBase, kMeshBbase, kMeshMarkIn, kMeshMarkBits, kMeshMarkRef,
+               kMeshMarkErank, kMeshMarkCbase, kMeshMarkScan, kMeshMarkWords };
+// ... of the analysis in fep_mesh_create (released when it returns) ...
+enum CreateBuf { kTmpPtr, kTmpCursor, kTmpList, kTmpCounters, kTmpScan };
+// ... and of one host-form call (a store of the call: allocated by it, released when it returns; nothing persists)
+enum CallBuf { kCallElem, kCallCoord, kCallSurf, kCallElemEd, kCallEdgeEl, kCallParent, kCallEta2, kCallMarked, kCallStats };
 
 }  // namespace
 
@@ -780,7 +775,7 @@ struct fep_mesh {
     int32_t* m_cbase = nullptr;   // (n_e + 1) first child of every element
     int32_t* m_scan = nullptr;
     int32_t* m_words = nullptr;   // {changed, elements with a marked edge}
-    DeviceBlocks blocks;
+    ScopedStore blocks;
 
     bool refused() const { return n_nonmanifold > 0 || n_inconsistent > 0 || n_degenerate > 0; }
     MeshView view() const { return MeshView{n_e, n_n, n_edges, n_bnd, elem, coord, nbr, mask, base, bbase}; }
@@ -802,23 +797,23 @@ static int mesh_create_impl(fep_mesh** out, int device_id, hipStream_t st, int64
     M->n_e = n_e;
     M->n_n = n_n;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    FEP_TRY(M->blocks.get(&M->elem, 3 * n_e));
-    FEP_TRY(M->blocks.get(&M->coord, 2 * n_n));
-    FEP_TRY(M->blocks.get(&M->nbr, 3 * n_e));
-    FEP_TRY(M->blocks.get(&M->mask, n_e));
-    FEP_TRY(M->blocks.get(&M->base, n_e + 1));
-    FEP_TRY(M->blocks.get(&M->bbase, n_e + 1));
+    FEP_TRY(reserve_as(M->blocks, kMeshElem, 3 * n_e, st, &M->elem));
+    FEP_TRY(reserve_as(M->blocks, kMeshCoord, 2 * n_n, st, &M->coord));
+    FEP_TRY(reserve_as(M->blocks, kMeshNbr, 3 * n_e, st, &M->nbr));
+    FEP_TRY(reserve_as(M->blocks, kMeshMask, n_e, st, &M->mask));
+    FEP_TRY(reserve_as(M->blocks, kMeshBase, n_e + 1, st, &M->base));
+    FEP_TRY(reserve_as(M->blocks, kMeshBbase, n_e + 1, st, &M->bbase));
     HIP_TRY(hipMemcpyAsync(M->elem, elem, (size_t)(3 * n_e) * sizeof(int32_t), kind, st));
     if (n_n > 0) HIP_TRY(hipMemcpyAsync(M->coord, coord, (size_t)(2 * n_n) * sizeof(double), kind, st));
     // scratch of the analysis: released when this function returns (it synchronises first)
-    DeviceBlocks tmp;
+    ScopedStore tmp;
     int32_t *ptr = nullptr, *cursor = nullptr, *list = nullptr, *counters = nullptr, *scan = nullptr;
     const int64_t n_longest = (n_n > n_e ? n_n : n_e) + 1;
-    FEP_TRY(tmp.get(&ptr, n_n + 1));
-    FEP_TRY(tmp.get(&cursor, n_n));
-    FEP_TRY(tmp.get(&list, 3 * n_e));
-    FEP_TRY(tmp.get(&counters, C_COUNT));
-    FEP_TRY(tmp.get(&scan, scan_scratch_len(n_longest)));
+    FEP_TRY(reserve_as(tmp, kTmpPtr, n_n + 1, st, &ptr));
+    FEP_TRY(reserve_as(tmp, kTmpCursor, n_n, st, &cursor));
+    FEP_TRY(reserve_as(tmp, kTmpList, 3 * n_e, st, &list));
+    FEP_TRY(reserve_as(tmp, kTmpCounters, C_COUNT, st, &counters));
+    FEP_TRY(reserve_as(tmp, kTmpScan, scan_scratch_len(n_longest), st, &scan));
     HIP_TRY(hipMemsetAsync(ptr, 0, (size_t)(n_n + 1) * sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(cursor, 0, (size_t)(n_n > 0 ? n_n : 1) * sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(counters, 0, C_COUNT * sizeof(int32_t), st));
@@ -855,12 +850,17 @@ static int64_t mesh_new_nodes(const fep_mesh* M, int elem_type) {
     return elem_type == FEP_P2 ? M->n_edges : 3 * M->n_e + 3 * M->n_edges;
 }
 
-static int mesh_enrich_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* elem_ext, double* coord_ext, int32_t* surf,
-                            int32_t* elem_ed, int32_t* edge_el) {
+// check_*: the arguments of an entry point's two forms, in one place (host or device pointers: only tested for NULL)
+static int check_enrich(const fep_mesh* M, int elem_type, const int32_t* elem_ext, const double* coord_ext, const int32_t* surf) {
     if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || !elem_ext || !coord_ext || (!surf && M->n_bnd > 0)) return FEP_EINVAL;
     if (M->refused()) return FEP_ESTATE;
+    return M->n_n + mesh_new_nodes(M, elem_type) >= (int64_t)INT32_MAX ? FEP_ERANGE : FEP_OK;
+}
+
+static int mesh_enrich_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* elem_ext, double* coord_ext, int32_t* surf,
+                            int32_t* elem_ed, int32_t* edge_el) {
+    FEP_TRY(check_enrich(M, elem_type, elem_ext, coord_ext, surf));
     const int64_t n_tot = M->n_n + mesh_new_nodes(M, elem_type);
-    if (n_tot >= (int64_t)INT32_MAX) return FEP_ERANGE;
     FEP_TRY(fep_set_device(M->device));
     for (int r = 0; r < 2 && M->n_n > 0; ++r)
         HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -873,11 +873,15 @@ static int mesh_enrich_impl(const fep_mesh* M, hipStream_t st, int elem_type, in
     return FEP_OK;
 }
 
-static int mesh_refine_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext) {
+static int check_refine(const fep_mesh* M, const int32_t* elem_child, const double* coord_ext) {
     if (!M || !elem_child || !coord_ext) return FEP_EINVAL;
     if (M->refused()) return FEP_ESTATE;
+    return M->n_n + M->n_edges >= (int64_t)INT32_MAX ? FEP_ERANGE : FEP_OK;
+}
+
+static int mesh_refine_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext) {
+    FEP_TRY(check_refine(M, elem_child, coord_ext));
     const int64_t n_tot = M->n_n + M->n_edges;
-    if (n_tot >= (int64_t)INT32_MAX) return FEP_ERANGE;
     FEP_TRY(fep_set_device(M->device));
     for (int r = 0; r < 2 && M->n_n > 0; ++r)
         HIP_TRY(hipMemcpyAsync(coord_ext + r * n_tot, M->coord + r * M->n_n, (size_t)M->n_n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -907,17 +911,17 @@ static int mesh_mark_impl(fep_mesh* M, hipStream_t st, const uint8_t* marked, in
     FEP_TRY(fep_set_device(M->device));
     if (pointer_on_device(marked, M->device) != (on_device ? 1 : 0)) return FEP_EINVAL;
     const int64_t n_e = M->n_e, n_edges = M->n_edges;
-    if (!M->m_ready) {                                       // each block once, also when an earlier call ran out of memory half-way
+    if (!M->m_ready) {                                       // each block once (those an earlier call made before it ran out of memory are kept)
         const int64_t n_longest = (n_edges > n_e ? n_edges : n_e) + 1;
-        if (!M->m_bits) FEP_TRY(M->blocks.get(&M->m_bits, n_e));
-        if (!M->m_ref) FEP_TRY(M->blocks.get(&M->m_ref, n_e));
-        if (!M->m_erank) FEP_TRY(M->blocks.get(&M->m_erank, n_edges + 1));
-        if (!M->m_cbase) FEP_TRY(M->blocks.get(&M->m_cbase, n_e + 1));
-        if (!M->m_scan) FEP_TRY(M->blocks.get(&M->m_scan, scan_scratch_len(n_longest)));
-        if (!M->m_words) FEP_TRY(M->blocks.get(&M->m_words, 2));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkBits, n_e, st, &M->m_bits));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkRef, n_e, st, &M->m_ref));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkErank, n_edges + 1, st, &M->m_erank));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkCbase, n_e + 1, st, &M->m_cbase));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkScan, scan_scratch_len(n_longest), st, &M->m_scan));
+        FEP_TRY(reserve_as(M->blocks, kMeshMarkWords, 2, st, &M->m_words));
         M->m_ready = true;
     }
-    if (!on_device && !M->m_in) FEP_TRY(M->blocks.get(&M->m_in, n_e));   // only meshes that are ever marked from the host
+    if (!on_device) FEP_TRY(reserve_as(M->blocks, kMeshMarkIn, n_e, st, &M->m_in));   // only meshes that are ever marked from the host
     M->has_marks = false;
     if (!on_device) {
         HIP_TRY(hipMemcpyAsync(M->m_in, marked, (size_t)n_e, hipMemcpyHostToDevice, st));
@@ -962,9 +966,13 @@ static int mesh_mark_impl(fep_mesh* M, hipStream_t st, const uint8_t* marked, in
     return FEP_OK;
 }
 
-static int mesh_refine_marked_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext, int32_t* parent) {
+static int check_refine_marked(const fep_mesh* M, const int32_t* elem_child, const double* coord_ext) {
     if (!M || !elem_child || !coord_ext) return FEP_EINVAL;
-    if (M->refused() || !M->has_marks) return FEP_ESTATE;
+    return M->refused() || !M->has_marks ? FEP_ESTATE : FEP_OK;
+}
+
+static int mesh_refine_marked_impl(const fep_mesh* M, hipStream_t st, int32_t* elem_child, double* coord_ext, int32_t* parent) {
+    FEP_TRY(check_refine_marked(M, elem_child, coord_ext));
     const int64_t n_tot = M->n_n + M->n_new;
     FEP_TRY(fep_set_device(M->device));
     for (int r = 0; r < 2 && M->n_n > 0; ++r)
@@ -990,9 +998,13 @@ static int mesh_set_curves_impl(fep_mesh* M, int n_curves, const double* curves_
     return FEP_OK;
 }
 
-static int mesh_surf_curve_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* curve_of_surf) {
+static int check_surf_curve(const fep_mesh* M, int elem_type, const int32_t* curve_of_surf) {
     if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || (!curve_of_surf && M->n_bnd > 0)) return FEP_EINVAL;
-    if (M->refused()) return FEP_ESTATE;
+    return M->refused() ? FEP_ESTATE : FEP_OK;
+}
+
+static int mesh_surf_curve_impl(const fep_mesh* M, hipStream_t st, int elem_type, int32_t* curve_of_surf) {
+    FEP_TRY(check_surf_curve(M, elem_type, curve_of_surf));
     FEP_TRY(fep_set_device(M->device));
     if (M->n_bnd == 0) return FEP_OK;
     hipLaunchKernelGGL(surf_curve_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->curves,
@@ -1001,29 +1013,20 @@ static int mesh_surf_curve_impl(const fep_mesh* M, hipStream_t st, int elem_type
     return FEP_OK;
 }
 
-// partials of fep_mesh_area_stats_dev: one fixed-size block per (device, stream), made by the first call on it (an
-// allocation: refused, FEP_ESTATE, while that stream is being captured) and kept
-static int area_scratch(int device, hipStream_t st, double** out) {
-    static std::mutex m;
-    static auto& bufs = *new std::map<std::pair<int, void*>, double*>();
-    std::lock_guard<std::mutex> g(m);
-    double*& b = bufs[{device, (void*)st}];
-    if (!b) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
-        HIP_TRY(hipMalloc((void**)&b, 3 * kAreaMaxBlocks * sizeof(double)));
-    }
-    *out = b;
-    return FEP_OK;
+// the arguments of both forms (host or device pointers: only tested for NULL)
+static int check_area_stats(int64_t n_e, int64_t n_n, const int32_t* elem, const double* coord, const double* out) {
+    return n_e < 0 || n_n < 0 || !out || (n_e > 0 && (!elem || (!coord && n_n > 0))) ? FEP_EINVAL : FEP_OK;
 }
 
 static int area_stats_impl(int device_id, hipStream_t st, int64_t n_e, int64_t n_n, const int32_t* elem, const double* coord,
                            double* out) {
-    if (n_e < 0 || n_n < 0 || !out || (n_e > 0 && (!elem || (!coord && n_n > 0)))) return FEP_EINVAL;
+    FEP_TRY(check_area_stats(n_e, n_n, elem, coord, out));
     FEP_TRY(fep_set_device(device_id));
+    // the partials: the fixed-size scratch of (device, stream), made by the first call on it (an allocation: refused,
+    // FEP_ESTATE, while that stream is being captured) and kept
     double* part = nullptr;
-    FEP_TRY(area_scratch(device_id, st, &part));
+    const size_t part_bytes = 3 * kAreaMaxBlocks * sizeof(double);
+    FEP_TRY(stream_scratch(kScratchArea, device_id, st, part_bytes, part_bytes, (void**)&part));
     int64_t n_part = (n_e + kBlock - 1) / kBlock;
     n_part = n_part < 1 ? 1 : (n_part > kAreaMaxBlocks ? kAreaMaxBlocks : n_part);
     hipLaunchKernelGGL(area_partial_kernel, dim3((unsigned)n_part), dim3(kBlock), 0, st, n_e, n_n, elem, coord, part);
@@ -1033,9 +1036,9 @@ static int area_stats_impl(int device_id, hipStream_t st, int64_t n_e, int64_t n
     return FEP_OK;
 }
 
-// Scratch of the indicator's passes: IndState, then three partials per block of every level above the leaves.  One grow-only
-// block per (device, stream), by the rule of the return map's counter scratch: growing is an allocation, refused
-// (FEP_ESTATE) while the stream is being captured, and a block handed out is never freed.
+// Scratch of the indicator's passes: IndState, then three partials per block of every level above the leaves.  The grow-only
+// scratch of its (device, stream) (stream_scratch, fep_staging.h): growing is an allocation, refused (FEP_ESTATE) while the
+// stream is being captured, and a block handed out is never freed.
 constexpr int64_t kIndHead = 8;                             // doubles reserved for IndState
 static int64_t ind_scratch_len(int64_t n) {
     int64_t len = kIndHead;
@@ -1044,22 +1047,8 @@ static int64_t ind_scratch_len(int64_t n) {
 }
 
 static int ind_scratch(int device, hipStream_t st, int64_t n, double** out) {
-    static std::mutex m;
-    static auto& bufs = *new std::map<std::pair<int, void*>, std::pair<double*, int64_t>>();
-    const int64_t len = ind_scratch_len(n);
-    std::lock_guard<std::mutex> g(m);
-    auto& b = bufs[{device, (void*)st}];
-    if (b.second < len) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
-        double* p = nullptr;
-        const int64_t cap = len + len / 4;
-        HIP_TRY(hipMalloc((void**)&p, (size_t)cap * sizeof(double)));
-        b = {p, cap};                                        // the smaller block stays allocated: captured graphs may name it
-    }
-    *out = b.first;
-    return FEP_OK;
+    const size_t len = (size_t)ind_scratch_len(n);
+    return stream_scratch(kScratchIndicator, device, st, len * sizeof(double), (len + len / 4) * sizeof(double), (void**)out);
 }
 
 // One pass over eta2: the leaves, then one launch per level until a single workgroup is left, which finishes the pass.
@@ -1099,8 +1088,12 @@ __attribute__((visibility("hidden"))) int fep_indicator_stats(int device, hipStr
 
 constexpr int kIndValueBits = 63;                           // trial passes of the descent: the bits of a non-negative double
 
+static int check_mark_bulk(int64_t n, const double* eta2, double theta, const uint8_t* marked, const double* out) {
+    return n < 0 || !out || (n > 0 && (!eta2 || !marked)) || !(theta > 0.0 && theta <= 1.0) ? FEP_EINVAL : FEP_OK;
+}
+
 static int mark_bulk_impl(int device_id, hipStream_t st, int64_t n, const double* eta2, double theta, uint8_t* marked, double* out) {
-    if (n < 0 || !out || (n > 0 && (!eta2 || !marked)) || !(theta > 0.0 && theta <= 1.0)) return FEP_EINVAL;
+    FEP_TRY(check_mark_bulk(n, eta2, theta, marked, out));
     if (n >= (int64_t)INT32_MAX * kBlock) return FEP_ERANGE;
     FEP_TRY(fep_set_device(device_id));
     double* scratch = nullptr;
@@ -1112,120 +1105,70 @@ static int mark_bulk_impl(int device_id, hipStream_t st, int64_t n, const double
     return ind_pass(st, n, eta2, kIndFinal, 0, theta, scratch, true, marked, nullptr, out);
 }
 
+// Host forms: the caller's arrays staged through the device's engine (fep_stage::HostCall) into device blocks of this call
+// (`store`, declared before the call: released after its scope has finished or drained the engine).  Outputs are as large as
+// the mesh and a driver makes one mesh per level, so nothing is kept.  A NULL optional array gives a NULL device pointer.
 static int mark_bulk_host_impl(int device_id, int64_t n, const double* eta2_h, double theta, uint8_t* marked_h, double* out_h) {
-    if (n < 0 || !out_h || (n > 0 && (!eta2_h || !marked_h)) || !(theta > 0.0 && theta <= 1.0)) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(device_id));
-    DeviceBlocks tmp;
-    double *eta2 = nullptr, *out = nullptr;
-    uint8_t* marked = nullptr;
-    FEP_TRY(tmp.get(&eta2, n));
-    FEP_TRY(tmp.get(&marked, n));
-    FEP_TRY(tmp.get(&out, 4));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(eta2, eta2_h, (size_t)n * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    FEP_TRY(mark_bulk_impl(device_id, nullptr, n, eta2, theta, marked, out));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(marked_h, marked, (size_t)n, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(out_h, out, 4 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
-}
-
-// host forms: device outputs of this call, copied back, released on every exit
-template <class T>
-static int fetch(T* dst_h, const T* src_d, int64_t count) {
-    if (dst_h && count > 0) HIP_TRY(hipMemcpyAsync(dst_h, src_d, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, nullptr));
-    return FEP_OK;
+    FEP_TRY(check_mark_bulk(n, eta2_h, theta, marked_h, out_h));
+    ScopedStore store;
+    fep_stage::HostCall call(device_id, &store);
+    const double* eta2 = call.in(kCallEta2, eta2_h, (size_t)n);
+    uint8_t* marked = call.out(kCallMarked, marked_h, (size_t)n);
+    double* out = call.out(kCallStats, out_h, 4);
+    return call.run([&] { return mark_bulk_impl(device_id, call.stream(), n, eta2, theta, marked, out); });
 }
 
 static int mesh_enrich_host_impl(const fep_mesh* M, int elem_type, int32_t* elem_ext_h, double* coord_ext_h, int32_t* surf_h,
                                  int32_t* elem_ed_h, int32_t* edge_el_h) {
-    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || !elem_ext_h || !coord_ext_h || (!surf_h && M->n_bnd > 0)) return FEP_EINVAL;
-    if (M->refused()) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(M->device));
+    FEP_TRY(check_enrich(M, elem_type, elem_ext_h, coord_ext_h, surf_h));
     const bool p2 = elem_type == FEP_P2;
     const int64_t n_tot = M->n_n + mesh_new_nodes(M, elem_type), n_p = p2 ? 6 : 15, n_s = p2 ? 3 : 5;
-    DeviceBlocks tmp;
-    int32_t *elem_ext = nullptr, *surf = nullptr, *elem_ed = nullptr, *edge_el = nullptr;
-    double* coord_ext = nullptr;
-    FEP_TRY(tmp.get(&elem_ext, n_p * M->n_e));
-    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
-    FEP_TRY(tmp.get(&surf, n_s * M->n_bnd));
-    if (p2 && elem_ed_h) FEP_TRY(tmp.get(&elem_ed, 3 * M->n_e));
-    if (p2 && edge_el_h) FEP_TRY(tmp.get(&edge_el, 2 * M->n_edges));
-    FEP_TRY(mesh_enrich_impl(M, nullptr, elem_type, elem_ext, coord_ext, surf, elem_ed, edge_el));
-    FEP_TRY(fetch(elem_ext_h, elem_ext, n_p * M->n_e));
-    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
-    FEP_TRY(fetch(surf_h, surf, n_s * M->n_bnd));
-    if (elem_ed) FEP_TRY(fetch(elem_ed_h, elem_ed, 3 * M->n_e));
-    if (edge_el) FEP_TRY(fetch(edge_el_h, edge_el, 2 * M->n_edges));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
+    ScopedStore store;
+    fep_stage::HostCall call(M->device, &store);
+    int32_t* elem_ext = call.out(kCallElem, elem_ext_h, (size_t)(n_p * M->n_e));
+    double* coord_ext = call.out(kCallCoord, coord_ext_h, (size_t)(2 * n_tot));
+    int32_t* surf = call.out(kCallSurf, surf_h, (size_t)(n_s * M->n_bnd));
+    int32_t* elem_ed = call.out(kCallElemEd, p2 ? elem_ed_h : nullptr, (size_t)(3 * M->n_e));
+    int32_t* edge_el = call.out(kCallEdgeEl, p2 ? edge_el_h : nullptr, (size_t)(2 * M->n_edges));
+    return call.run([&] { return mesh_enrich_impl(M, call.stream(), elem_type, elem_ext, coord_ext, surf, elem_ed, edge_el); });
 }
 
 static int mesh_refine_host_impl(const fep_mesh* M, int32_t* elem_child_h, double* coord_ext_h) {
-    if (!M || !elem_child_h || !coord_ext_h) return FEP_EINVAL;
-    if (M->refused()) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(M->device));
-    const int64_t n_tot = M->n_n + M->n_edges;
-    DeviceBlocks tmp;
-    int32_t* child = nullptr;
-    double* coord_ext = nullptr;
-    FEP_TRY(tmp.get(&child, 12 * M->n_e));
-    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
-    FEP_TRY(mesh_refine_impl(M, nullptr, child, coord_ext));
-    FEP_TRY(fetch(elem_child_h, child, 12 * M->n_e));
-    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
+    FEP_TRY(check_refine(M, elem_child_h, coord_ext_h));
+    ScopedStore store;
+    fep_stage::HostCall call(M->device, &store);
+    int32_t* child = call.out(kCallElem, elem_child_h, (size_t)(12 * M->n_e));
+    double* coord_ext = call.out(kCallCoord, coord_ext_h, (size_t)(2 * (M->n_n + M->n_edges)));
+    return call.run([&] { return mesh_refine_impl(M, call.stream(), child, coord_ext); });
 }
 
 static int mesh_refine_marked_host_impl(const fep_mesh* M, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h) {
-    if (!M || !elem_child_h || !coord_ext_h) return FEP_EINVAL;
-    if (M->refused() || !M->has_marks) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(M->device));
-    const int64_t n_tot = M->n_n + M->n_new;
-    DeviceBlocks tmp;
-    int32_t *child = nullptr, *parent = nullptr;
-    double* coord_ext = nullptr;
-    FEP_TRY(tmp.get(&child, 3 * M->n_child));
-    FEP_TRY(tmp.get(&coord_ext, 2 * n_tot));
-    if (parent_h) FEP_TRY(tmp.get(&parent, M->n_child));
-    FEP_TRY(mesh_refine_marked_impl(M, nullptr, child, coord_ext, parent));
-    FEP_TRY(fetch(elem_child_h, child, 3 * M->n_child));
-    FEP_TRY(fetch(coord_ext_h, coord_ext, 2 * n_tot));
-    FEP_TRY(fetch(parent_h, parent, M->n_child));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
+    FEP_TRY(check_refine_marked(M, elem_child_h, coord_ext_h));
+    ScopedStore store;
+    fep_stage::HostCall call(M->device, &store);
+    int32_t* child = call.out(kCallElem, elem_child_h, (size_t)(3 * M->n_child));
+    double* coord_ext = call.out(kCallCoord, coord_ext_h, (size_t)(2 * (M->n_n + M->n_new)));
+    int32_t* parent = call.out(kCallParent, parent_h, (size_t)M->n_child);
+    return call.run([&] { return mesh_refine_marked_impl(M, call.stream(), child, coord_ext, parent); });
 }
 
 static int mesh_surf_curve_host_impl(const fep_mesh* M, int elem_type, int32_t* curve_of_surf_h) {
-    if (!M || (elem_type != FEP_P2 && elem_type != FEP_P4) || (!curve_of_surf_h && M->n_bnd > 0)) return FEP_EINVAL;
-    if (M->refused()) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(M->device));
-    DeviceBlocks tmp;
-    int32_t* out = nullptr;
-    FEP_TRY(tmp.get(&out, M->n_bnd));
-    FEP_TRY(mesh_surf_curve_impl(M, nullptr, elem_type, out));
-    FEP_TRY(fetch(curve_of_surf_h, out, M->n_bnd));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
+    FEP_TRY(check_surf_curve(M, elem_type, curve_of_surf_h));
+    ScopedStore store;
+    fep_stage::HostCall call(M->device, &store);
+    int32_t* out = call.out(kCallSurf, curve_of_surf_h, (size_t)M->n_bnd);
+    return call.run([&] { return mesh_surf_curve_impl(M, call.stream(), elem_type, out); });
 }
 
 static int area_stats_host_impl(int device_id, int64_t n_e, int64_t n_n, const int32_t* elem_h, const double* coord_h,
                                 double* out_h) {
-    if (n_e < 0 || n_n < 0 || !out_h || (n_e > 0 && (!elem_h || (!coord_h && n_n > 0)))) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(device_id));
-    DeviceBlocks tmp;
-    int32_t* elem = nullptr;
-    double *coord = nullptr, *out = nullptr;
-    FEP_TRY(tmp.get(&elem, 3 * n_e));
-    FEP_TRY(tmp.get(&coord, 2 * n_n));
-    FEP_TRY(tmp.get(&out, 4));
-    if (n_e > 0) HIP_TRY(hipMemcpyAsync(elem, elem_h, (size_t)(3 * n_e) * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-    if (n_n > 0 && coord_h) HIP_TRY(hipMemcpyAsync(coord, coord_h, (size_t)(2 * n_n) * sizeof(double), hipMemcpyHostToDevice, nullptr));
-    FEP_TRY(area_stats_impl(device_id, nullptr, n_e, n_n, elem, coord, out));
-    FEP_TRY(fetch(out_h, out, 4));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return FEP_OK;
+    FEP_TRY(check_area_stats(n_e, n_n, elem_h, coord_h, out_h));
+    ScopedStore store;
+    fep_stage::HostCall call(device_id, &store);
+    const int32_t* elem = call.in(kCallElem, elem_h, (size_t)(3 * n_e));
+    const double* coord = call.in(kCallCoord, coord_h, (size_t)(2 * n_n));
+    double* out = call.out(kCallStats, out_h, 4);
+    return call.run([&] { return area_stats_impl(device_id, call.stream(), n_e, n_n, elem, coord, out); });
 }
 
 extern "C" int fep_mesh_create(fep_mesh** mesh_out, int device_id, void* stream, int64_t n_e, int64_t n_n, const int32_t* elem,

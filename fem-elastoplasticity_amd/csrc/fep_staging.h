@@ -2,7 +2,8 @@
 //
 // Round 1 allocated ~10 device buffers per call and copied pageable memory synchronously: 13 ms for a 1 M-point call
 // whose kernels take 0.1 ms.  Here:
-//   * device buffers persist (per context for the fused step, per device for the mesh-free return map, grow-only);
+//   * device buffers persist (per context for the fused step, per device for the mesh-free return map, grow-only); the mesh
+//     forms, whose outputs are as large as the mesh, use blocks of the call instead (ScopedStore);
 //   * pinned host memory comes from a size-keyed cache (fep_host_alloc / fep_host_free): the Python layer allocates
 //     every OUTPUT array (s, ds, ind_p, K data, F ...) there, so results are DMA-ed straight into the NumPy array the
 //     caller receives — no staging copy on the way back;
@@ -11,7 +12,8 @@
 //     (hipMemcpyAsync); pageable outputs take the same ring the other way;
 //   * everything is ordered on one stream per device; one hipStreamSynchronize at the end of the call.
 // The three classes use six HIP calls (hipHostMalloc / hipHostFree / hipMalloc / hipFree / hipMemcpyAsync / stream and
-// event handling).  tests/staging_san.cpp defines FEP_STAGING_HOST_STUB and supplies host stand-ins for them (plain memory,
+// event handling); the per-stream scratch at the end of the file adds a seventh, hipStreamIsCapturing.
+// tests/staging_san.cpp defines FEP_STAGING_HOST_STUB and supplies host stand-ins for them (plain memory,
 // copies deferred to the synchronise that must wait for them, a switch that makes the next copy fail), so that PinnedCache,
 // CopyPool and Engine run under ThreadSanitizer / AddressSanitizer on the CPU and a missing wait changes the result.
 #pragma once
@@ -23,12 +25,14 @@ inline int fep_set_device(int) { return FEP_OK; }       // the host build has no
 
 #include <algorithm>
 #include <condition_variable>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <new>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 namespace fep_stage {
@@ -219,6 +223,21 @@ struct DeviceStore {
     }
     void release() { for (Block& b : blocks) { if (b.first) (void)hipFree(b.first); b.first = nullptr; b.second = 0; } }
 };
+// The device blocks of one call (or one object): released with it.  As the store of a HostCall it is declared BEFORE the
+// call, so that the call's scope has finished or drained the engine by the time the blocks are freed.
+struct ScopedStore : DeviceStore {
+    using DeviceStore::DeviceStore;
+    ScopedStore(const ScopedStore&) = delete;
+    ScopedStore& operator=(const ScopedStore&) = delete;
+    ~ScopedStore() { release(); }
+};
+// reserve() for `count` elements of T, at least one
+template <class T> int reserve_as(DeviceStore& s, int idx, int64_t count, hipStream_t stream, T** out) {
+    void* p = nullptr;
+    FEP_TRY(s.reserve(idx, (size_t)(count > 0 ? count : 1) * sizeof(T), stream, &p));
+    *out = (T*)p;
+    return FEP_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // per-device engine: one stream, a ring of pinned slots, persistent device buffers
@@ -401,3 +420,40 @@ public:
 };
 
 }  // namespace fep_stage
+
+// ---------------------------------------------------------------------------------------
+// kernel scratch per (device, stream)
+// ---------------------------------------------------------------------------------------
+// A seventh HIP call, hipStreamIsCapturing: a host-stub driver that has a stand-in for it says so with
+// FEP_STAGING_STUB_CAPTURE; one without (it tests the classes above only) does not get this part.
+#if !defined(FEP_STAGING_HOST_STUB) || defined(FEP_STAGING_STUB_CAPTURE)
+// Allocating is illegal while the stream is being captured into a graph: such a call is refused (FEP_ESTATE) instead of
+// breaking the capture — run the same call once outside the capture first (fep.h, fep_step_dev).
+inline int scratch_alloc_allowed(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_OK; }
+    return cs == hipStreamCaptureStatusNone ? FEP_OK : FEP_ESTATE;
+}
+enum ScratchTag { kScratchRmCounts, kScratchArea, kScratchIndicator };
+// The block of `tag` on (device, stream), with room for `bytes`: calls on different streams never share one.  A block that
+// is too small is superseded by one of `grow_bytes` (each user has its own growth rule; never less than `bytes`); that is an
+// allocation, refused (FEP_ESTATE) while the stream is being captured.  The superseded block is never freed: captured graphs
+// may name it.
+inline int stream_scratch(ScratchTag tag, int device, hipStream_t st, size_t bytes, size_t grow_bytes, void** out) {
+    static std::mutex m;
+    static auto& all = *new std::map<std::tuple<int, int, void*>, std::pair<void*, size_t>>();
+    std::lock_guard<std::mutex> g(m);
+    auto& b = all[std::make_tuple((int)tag, device, (void*)st)];
+    if (b.second < bytes) {
+        FEP_TRY(scratch_alloc_allowed(st));
+        grow_bytes = std::max(grow_bytes, bytes);
+        void* p = nullptr;
+        HIP_TRY(hipMalloc(&p, grow_bytes));
+        static auto& superseded = *new std::vector<void*>();                 // (keeps them in a leak checker's sight)
+        if (b.first) superseded.push_back(b.first);
+        b = {p, grow_bytes};
+    }
+    *out = b.first;
+    return FEP_OK;
+}
+#endif

@@ -24,13 +24,16 @@
  *     aligned (hipMalloc and every tensor library deliver that; checked, FEP_EINVAL otherwise): the kernels move
  *     them as (x, y) pairs;
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); *_dev
- *     calls only enqueue work and return, *_host calls are synchronous (they run on a stream of the library's own,
- *     with persistent device buffers and pinned staging: no allocation per call after the first);
+ *     calls only enqueue work and return, *_host calls are synchronous (all but fep_load_traction_host run on a stream of
+ *     the library's own, with pinned staging; the context and return-map forms keep their device buffers, so they allocate
+ *     nothing per call after the first, the mesh forms use device blocks of the call);
  *   - calls on one context are not re-entrant; one context per (host thread, GPU).
  *
  * Stream contract of the *_host entry points that move the caller's arrays through the staging engine
  * (fep_return_map_host / _vm_host / _mc_host / _vmps_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
- * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host, fep_recover_stress_host, fep_estimate_host; not the fep_mesh_* and fep_load_traction_host forms):
+ * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host, fep_recover_stress_host, fep_estimate_host,
+ * fep_mesh_enrich_host, fep_mesh_refine_host, fep_mesh_refine_marked_host, fep_mesh_surf_curve_host, fep_mesh_area_stats_host,
+ * fep_mark_bulk_host; not fep_load_traction_host, which allocates per call and copies on the default stream):
  *   - each call runs its copies and its kernels on ONE non-blocking stream per device that belongs to the library; that stream
  *     is ordered against nothing else: not the default stream, not a stream the caller passed to a *_dev call;
  *   - calls of all host threads on one device are serialised by a lock, and a call returns only after synchronising that
@@ -49,6 +52,11 @@
  *   context may be enqueued at once on any stream.  tests/test_host_staging_gpu.py runs exactly this alternation.
  *   The mesh-free fep_return_map_*_host calls use the engine's own device buffers and the counter scratch of the engine's
  *   stream only: they need no synchronisation against *_dev calls of any kind.
+ *   The mesh forms (the last six of the list) use device blocks of the call: their outputs are as large as the
+ *   mesh and a driver makes one mesh per level, so every call allocates its blocks and frees them before it returns, and
+ *   nothing persists.  No *_dev call needs synchronising against them either: they only read the mesh, and what writes it
+ *   (fep_mesh_create, fep_mesh_mark) synchronises before it returns.  Their kernel scratch (area statistics, the indicator's
+ *   partials) is that of the engine's stream.
  */
 #ifndef FEP_H
 #define FEP_H

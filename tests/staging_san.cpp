@@ -1,5 +1,5 @@
 // Host-only driver of fem-elastoplasticity_amd/csrc/fep_staging.h for the sanitizer builds (tests/test_host_sanitizers.py:
-// g++ -fsanitize=address,undefined and -fsanitize=thread, FEP_COPY_THREADS = 1, 3 and 6; CPU only).  The header's six kinds
+// g++ -fsanitize=address,undefined and -fsanitize=thread, FEP_COPY_THREADS = 1, 3 and 6; CPU only).  The header's seven kinds
 // of HIP calls are replaced by the host stand-ins below (FEP_STAGING_HOST_STUB): "device" memory is heap memory, and
 // `g_fail_copy_after` / `g_fail_host_malloc` make the n-th copy / the next pinned allocation fail.
 //
@@ -21,7 +21,12 @@
 //      its four positions
 //   7. small -> large -> small calls on one engine (DeviceStore's grow path), and a buffer that grows while a copy into
 //      its old block is still queued
-// Every check of 5 - 7 compares every byte of the result, and every destination ends in a canary block (one slot long, so a
+//   8. a call shaped like the mesh host forms (HostCall on a ScopedStore of the call: two pageable inputs, a kernel, three
+//      outputs of which one is NULL), four times back to back, the device blocks released after each; then once with a copy
+//      that fails after a device -> host chunk was queued, while copies into the call's blocks are still queued
+//   9. stream_scratch: a smaller need returns the same block, growth returns a new one and leaves the old one allocated, a
+//      capturing stream is refused with nothing allocated
+// Every check of 5 - 8 compares every byte of the result, and every destination ends in a canary block (one slot long, so a
 // whole-slot overrun stays inside the allocation) that must come back untouched; sources have no slack, so ASan sees a read
 // past their end.
 //
@@ -37,6 +42,10 @@
 //   HostCall::run() without the copy back of the inout array    [return-map-shaped call, run 0] ep differs
 //   DeviceStore::reserve frees a block without synchronising   [buffer grows while a copy into its old block is queued]: the
 //                                                              ASan build reports the queued copy's write into the freed block
+//   ScopedStore declared after its HostCall (released before   [mesh-shaped call, a copy fails]: the ASan build reports the queued copy's
+//     the scope drains)                                          write into the freed block
+//   HostCall::run() without the copy back of its second out()   [return-map-shaped call, run 0] ds differs; with check 6 taken out,
+//     array                                                      [mesh-shaped call, run 0] coord_ext differs
 //   tail size min(kSlotBytes, bytes - off) -> kSlotBytes        h2d, d2h: [engine error path], interleave2: [interleave2, 1 nodes]:
 //     (in h2d, d2h, or min(per, n - off) -> per in interleave2)  the ASan build reports the access past the end of a heap block,
 //                                                              deterministically.  The TSan build checks no bounds: there the
@@ -56,6 +65,7 @@
 #include "../include/fep.h"
 
 #define FEP_STAGING_HOST_STUB 1
+#define FEP_STAGING_STUB_CAPTURE 1                      // hipStreamIsCapturing has a stand-in below: the scratch helper is built too
 typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
@@ -66,6 +76,7 @@ struct StubStream {
     std::mutex m;                                        // the two-engine test drives two streams from two threads
     std::deque<StubOp> q;                                // queued and not yet run, oldest first
     size_t queued = 0, done = 0;                         // operations queued / run so far
+    bool capturing = false;                              // what hipStreamIsCapturing reports
     void push(const StubOp& op) { std::lock_guard<std::mutex> g(m); q.push_back(op); ++queued; }
     size_t position() { std::lock_guard<std::mutex> g(m); return queued; }
     void run_to(size_t pos) {
@@ -84,6 +95,7 @@ typedef StubEvent* hipEvent_t;
 static thread_local int fep_g_last_hip = 0;
 static std::atomic<long> g_copies{0}, g_fail_copy_after{-1};
 static std::atomic<int> g_fail_host_malloc{0};
+static std::atomic<long> g_dev_live{0};                  // "device" blocks allocated and not freed
 static hipError_t hipGetLastError() { return hipSuccess; }
 static hipError_t hipHostMalloc(void** p, size_t b, unsigned) {
     if (g_fail_host_malloc.load() > 0) { g_fail_host_malloc.fetch_sub(1); *p = nullptr; return hipErrorOutOfMemory; }
@@ -91,8 +103,10 @@ static hipError_t hipHostMalloc(void** p, size_t b, unsigned) {
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
-static hipError_t hipMalloc(void** p, size_t b) { *p = std::malloc(b); return *p ? hipSuccess : hipErrorOutOfMemory; }
-static hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
+static hipError_t hipMalloc(void** p, size_t b) { *p = std::malloc(b); if (*p) ++g_dev_live; return *p ? hipSuccess : hipErrorOutOfMemory; }
+static hipError_t hipFree(void* p) { if (p) --g_dev_live; std::free(p); return hipSuccess; }
+enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive = 1 };
+static hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus* cs);
 static hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new StubStream(); return hipSuccess; }
 static hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new StubEvent(); return hipSuccess; }
 static hipError_t hipStreamSynchronize(hipStream_t s) { s->run_to(s->position()); return hipSuccess; }
@@ -103,6 +117,10 @@ static hipError_t hipMemcpyAsync(void* d, const void* s, size_t b, hipMemcpyKind
     const long f = g_fail_copy_after.load();
     if (f >= 0 && k >= f) return hipErrorUnknown;        // a failing call queues nothing
     st->push(StubOp{d, s, b, nullptr, nullptr});
+    return hipSuccess;
+}
+static hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus* cs) {
+    *cs = s->capturing ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
     return hipSuccess;
 }
 // a "kernel": fn(arg) runs in stream order, when a synchronise reaches it
@@ -505,6 +523,140 @@ static int test_buffer_growth() {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// a call shaped like the mesh host forms: device blocks of the call
+// ---------------------------------------------------------------------------------------
+struct MeshArgs {
+    size_t ne, nc, nch, nx, np;
+    const uint64_t *elem, *coord;                        // ne, nc
+    uint64_t *child, *coord_ext, *parent;                // nch, nx, np (parent may be NULL)
+};
+static void mesh_compute(void* a) {
+    const MeshArgs& k = *(const MeshArgs*)a;
+    for (size_t i = 0; i < k.nch; ++i) k.child[i] = k.elem[i % k.ne] ^ (k.coord[i % k.nc] << 9 | k.coord[i % k.nc] >> 55);
+    for (size_t i = 0; i < k.nx; ++i) k.coord_ext[i] = k.coord[i % k.nc] + k.elem[(5 * i) % k.ne];
+    if (k.parent) for (size_t i = 0; i < k.np; ++i) k.parent[i] = k.elem[i % k.ne] >> 3;
+}
+
+// words: elem 1.25 slots + 3 (2 chunks), coord half a slot + 1 (1), child 2.3 slots (3), coord_ext 0.7 slots (1): 7 pageable
+// chunks per call, so four calls start the ring at slots 0, 3, 2, 1
+static constexpr size_t kMeshNe = 1310723, kMeshNc = 524289, kMeshNch = 2411725, kMeshNx = 734003, kMeshNp = 1000;
+static constexpr int kMeshDevice = 14;
+
+// `child_h`, `coord_ext_h`: the caller's output arrays (8 bytes into their allocations)
+static int mesh_call(const Buf& elem, const Buf& coord, uint64_t* child_h, uint64_t* coord_ext_h, int* start_slot, long fail_after) {
+    enum { kElem, kCoord, kChild, kCoordExt, kParent };
+    MeshArgs dev{kMeshNe, kMeshNc, kMeshNch, kMeshNx, kMeshNp, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ScopedStore store;                                   // before the call: released after its scope has finished or drained
+    HostCall call(kMeshDevice, &store);
+    FEP_TRY(call.status());
+    Engine* E = nullptr;
+    FEP_TRY(engine(kMeshDevice, &E));
+    *start_slot = E->next;
+    if (fail_after >= 0) g_fail_copy_after = g_copies.load() + fail_after;
+    dev.elem = call.in(kElem, (const uint64_t*)elem.p, kMeshNe);
+    dev.coord = call.in(kCoord, (const uint64_t*)coord.p, kMeshNc);
+    dev.child = call.out(kChild, child_h, kMeshNch);
+    dev.coord_ext = call.out(kCoordExt, coord_ext_h, kMeshNx);
+    dev.parent = call.out(kParent, (uint64_t*)nullptr, kMeshNp);
+    if (dev.parent || store.blocks.size() > (size_t)kParent) return FEP_ESTATE;     // a NULL array: no block, no transfer
+    return call.run([&] { stub_launch(call.stream(), mesh_compute, &dev); return (int)FEP_OK; });
+}
+
+static int test_mesh_shaped_calls() {
+    Engine* E = nullptr;
+    CHECK(engine(kMeshDevice, &E) == FEP_OK);
+    const long live0 = g_dev_live.load();
+    Buf elem(kMeshNe * 8, false, 0), coord(kMeshNc * 8, false, 0);
+    std::vector<uint64_t> r_child(kMeshNch), r_x(kMeshNx);
+    unsigned starts = 0;
+    for (int run = 0; run < 4; ++run) {
+        WHAT("mesh-shaped call, run %d", run);
+        fill(elem.p, kMeshNe * 8, 77 + run);
+        fill(coord.p, kMeshNc * 8, 177 + run);
+        MeshArgs ref{kMeshNe, kMeshNc, kMeshNch, kMeshNx, kMeshNp, (const uint64_t*)elem.p, (const uint64_t*)coord.p, r_child.data(),
+                     r_x.data(), nullptr};
+        mesh_compute(&ref);
+        Buf child(kMeshNch * 8, false, kCanary), x(kMeshNx * 8, false, kCanary);
+        int start = -1;
+        CHECK(mesh_call(elem, coord, (uint64_t*)child.p, (uint64_t*)x.p, &start, -1) == FEP_OK);
+        starts |= 1u << start;
+        CHECK(std::memcmp(child.p, r_child.data(), kMeshNch * 8) == 0);            // child differs
+        CHECK(std::memcmp(x.p, r_x.data(), kMeshNx * 8) == 0);                     // coord_ext differs
+        CHECK(child.canary_ok() && x.canary_ok());
+        CHECK(is_fill(elem.p, kMeshNe * 8, 77 + run) && is_fill(coord.p, kMeshNc * 8, 177 + run));
+        CHECK(g_dev_live.load() == live0);               // the call's device blocks are gone
+    }
+    WHAT("mesh-shaped calls: ring start positions");
+    CHECK(starts == (1u << Engine::kSlots) - 1);
+    WHAT("mesh-shaped call, a copy fails");
+    {
+        // three chunks in, the first chunk of child out, then the failure: the copies into the call's blocks and the kernel
+        // are still queued when the call gives up, and run when its scope drains the engine, before the blocks are released
+        std::vector<uint64_t>*child = new std::vector<uint64_t>(kMeshNch + 1), *x = new std::vector<uint64_t>(kMeshNx + 1);
+        int start = -1;
+        CHECK(mesh_call(elem, coord, child->data() + 1, x->data() + 1, &start, 4) == FEP_EHIP);
+        g_fail_copy_after = -1;
+        delete child;                                     // the caller frees its output arrays on the error
+        delete x;
+    }
+    for (int i = 0; i < Engine::kSlots; ++i) CHECK(E->pend[i].dst == nullptr);
+    CHECK(E->next == 0 && g_dev_live.load() == live0);
+    WHAT("mesh-shaped call after the failed one");
+    {
+        MeshArgs ref{kMeshNe, kMeshNc, kMeshNch, kMeshNx, kMeshNp, (const uint64_t*)elem.p, (const uint64_t*)coord.p, r_child.data(),
+                     r_x.data(), nullptr};
+        mesh_compute(&ref);
+        Buf child(kMeshNch * 8, false, kCanary), x(kMeshNx * 8, false, kCanary);
+        int start = -1;
+        CHECK(mesh_call(elem, coord, (uint64_t*)child.p, (uint64_t*)x.p, &start, -1) == FEP_OK);
+        CHECK(std::memcmp(child.p, r_child.data(), kMeshNch * 8) == 0 && std::memcmp(x.p, r_x.data(), kMeshNx * 8) == 0);
+        CHECK(child.canary_ok() && x.canary_ok());
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// kernel scratch per (device, stream)
+// ---------------------------------------------------------------------------------------
+static int test_stream_scratch() {
+    WHAT("stream scratch");
+    StubStream st, other, cap;
+    const long live0 = g_dev_live.load();
+    void *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr;
+    CHECK(stream_scratch(kScratchArea, 0, &st, 1000, 1500, &a) == FEP_OK && a && g_dev_live.load() == live0 + 1);
+    CHECK(stream_scratch(kScratchArea, 0, &st, 800, 1200, &b) == FEP_OK && b == a);          // a smaller need: the same block
+    CHECK(stream_scratch(kScratchArea, 0, &st, 1500, 1875, &b) == FEP_OK && b == a);         // up to what growing allocated
+    CHECK(g_dev_live.load() == live0 + 1);
+    CHECK(stream_scratch(kScratchArea, 0, &st, 1501, 2000, &c) == FEP_OK && c && c != a);    // growth: a new block
+    CHECK(g_dev_live.load() == live0 + 2);
+    std::memset(a, 0x11, 1500);                           // the old one is still allocated (a captured graph may name it)
+    std::memset(c, 0x22, 2000);
+    // another tag, stream or device: blocks of their own
+    CHECK(stream_scratch(kScratchIndicator, 0, &st, 64, 64, &d) == FEP_OK && d != c && d != a);
+    CHECK(stream_scratch(kScratchArea, 0, &other, 64, 64, &b) == FEP_OK && b != c && b != d);
+    CHECK(stream_scratch(kScratchArea, 1, &st, 64, 64, &b) == FEP_OK && b != c && b != d);
+    CHECK(g_dev_live.load() == live0 + 5);
+    WHAT("stream scratch, capturing");
+    cap.capturing = true;
+    void* e = nullptr;
+    CHECK(stream_scratch(kScratchArea, 0, &cap, 100, 100, &e) == FEP_ESTATE && e == nullptr && g_dev_live.load() == live0 + 5);
+    cap.capturing = false;                                // the same call once outside the capture ...
+    CHECK(stream_scratch(kScratchArea, 0, &cap, 100, 100, &e) == FEP_OK && e && g_dev_live.load() == live0 + 6);
+    cap.capturing = true;                                 // ... then it needs no allocation; a larger one is still refused
+    void* f = nullptr;
+    CHECK(stream_scratch(kScratchArea, 0, &cap, 100, 100, &f) == FEP_OK && f == e);
+    f = nullptr;
+    CHECK(stream_scratch(kScratchArea, 0, &cap, 101, 200, &f) == FEP_ESTATE && f == nullptr && g_dev_live.load() == live0 + 6);
+    WHAT("stream scratch, growth rule below the need");
+    void* g = nullptr;                                    // never a block smaller than the need
+    CHECK(stream_scratch(kScratchRmCounts, 0, &st, 4096, 16, &g) == FEP_OK && g);
+    std::memset(g, 0x33, 4096);
+    void* h = nullptr;
+    CHECK(stream_scratch(kScratchRmCounts, 0, &st, 4096, 16, &h) == FEP_OK && h == g && g_dev_live.load() == live0 + 7);
+    return 0;
+}
+
 int main() {
     if (test_pinned()) return 1;
     if (test_pool_two_callers()) return 1;
@@ -513,6 +665,8 @@ int main() {
     if (test_longer_than_the_ring()) return 1;
     if (test_return_map_shaped_calls()) return 1;
     if (test_buffer_growth()) return 1;
+    if (test_mesh_shaped_calls()) return 1;
+    if (test_stream_scratch()) return 1;
     if (pinned().trim() != FEP_OK) return 1;             // the callers' pinned arrays went back to the cache: unpin them
     std::printf("staging ok\n");
     return 0;

@@ -15,6 +15,9 @@ reused without waiting for its DMA may well deliver the right bytes on the day. 
 waits, that every parked chunk reaches its destination and that every tail is sized right is tests/staging_san.cpp, where the
 stand-in runtime defers each copy to the latest moment the API allows.  This file proves that the REAL runtime, at chunk sizes
 where the DMA is still in flight when the copy threads return, delivers the same bytes as torch's copies.
+
+The mesh host forms (fep_mesh_*_host, fep_mark_bulk_host) take the same engine with device
+blocks of the call; their section is at the end, with the same reference (the *_dev form on torch tensors) and the same rule.
 """
 import threading
 
@@ -168,7 +171,7 @@ def big():
     ctx = fep.MeshContext(elem, coord)
     assert (ctx.n_n, ctx.n_e) == (525625, 1048352)
     U2 = np.ascontiguousarray(sc.displacement(coord))
-    yield dict(ctx=ctx, coord=coord, U2=U2, U=np.ascontiguousarray(U2.reshape(-1, order='F')), dev={})
+    yield dict(ctx=ctx, coord=coord, elem=elem, U2=U2, U=np.ascontiguousarray(U2.reshape(-1, order='F')), dev={})
     ctx.close()
 
 
@@ -439,3 +442,193 @@ def test_dev_and_host_steps_alternate_on_one_context(big):
         same_step(d, ref, want)
         same_step(h, ref, want)
         assert sc.canary_intact(ep_h)
+
+
+# ---- mesh host forms: the engine, device blocks of the call -------------------------------------------------------
+FEP_TYPE = {'P2': 2, 'P4': 5}
+
+
+def _out(kind, shape, dtype):
+    """An output array of `kind` with a canary tail, holding neither a result nor the canary."""
+    a = (sc.pageable if kind == 'pageable' else sc.pinned)(shape, dtype, canary=True)
+    a.view(np.uint8).reshape(-1)[...] = 0x3C
+    return a
+
+
+def _bits(got, ref, what):
+    """Host arrays against the tensors of the *_dev form: shape, dtype and every byte."""
+    assert len(got) == len(ref), what
+    for j, (a, b) in enumerate(zip(got, ref)):
+        b = b.cpu().numpy() if hasattr(b, 'cpu') else b
+        assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), (what, j)
+        assert sc.canary_intact(a), (what, j)
+
+
+def _enrich_host(m, t, kind='pageable', with_ed=True):
+    """Raw fep_mesh_enrich_host -> [elem_ext, coord_ext, surf[, elem_ed, edge_el]]."""
+    i, p2 = m.info, t == 'P2'
+    out = [_out(kind, (6 if p2 else 15, i['n_e']), np.int32), _out(kind, (2, i['n_n'] + m.new_nodes(t)), np.float64),
+           _out(kind, (3 if p2 else 5, i['n_boundary_edges']), np.int32)]
+    if p2 and with_ed:
+        out += [_out(kind, (3, i['n_e']), np.int32), _out(kind, (2, i['n_edges']), np.int32)]
+    assert _lib.lib().fep_mesh_enrich_host(m._h, FEP_TYPE[t], *([_p(a) for a in out] + [None] * (5 - len(out)))) == 0
+    return out
+
+
+def _refine_host(m, kind='pageable'):
+    """Raw fep_mesh_refine_host -> [coord_ext, child], the order of DeviceMesh.refine_dev."""
+    i = m.info
+    child, coord_ext = _out(kind, (3, 4 * i['n_e']), np.int32), _out(kind, (2, i['n_n'] + i['n_edges']), np.float64)
+    assert _lib.lib().fep_mesh_refine_host(m._h, _p(child), _p(coord_ext)) == 0
+    return [coord_ext, child]
+
+
+@pytest.fixture(scope='module')
+def big_mesh(big):
+    """The large mesh analysed once; 'refine': its refine_dev result as NumPy arrays, computed once, never modified."""
+    import torch
+    m = fep.DeviceMesh(big['coord'], big['elem'], 0)
+    assert m.info['n_e'] == 1048352 and m.info['n_nonmanifold'] + m.info['n_inconsistent'] + m.info['n_degenerate'] == 0
+    ref = [a.cpu().numpy() for a in m.refine_dev()]
+    torch.cuda.synchronize()
+    yield dict(m=m, refine=ref)
+    m.close()
+
+
+@pytest.fixture(scope='module')
+def small_mesh():
+    """The 40-cell square: (DeviceMesh, coord, elem)."""
+    mesh = fep.square_mesh(sc.SMALL_MESH_N, 'P1', 10)
+    m = fep.DeviceMesh(mesh['coordinates'], mesh['elements'], 0)
+    yield m, mesh['coordinates'], mesh['elements']
+    m.close()
+
+
+def _p4_ref(big_mesh):
+    """enrich_dev('P4') of the large mesh as NumPy arrays: computed once, never modified."""
+    import torch
+    if 'P4' not in big_mesh:
+        big_mesh['P4'] = [a.cpu().numpy() for a in big_mesh['m'].enrich_dev('P4')]
+        torch.cuda.synchronize()
+    return big_mesh['P4']
+
+
+def test_enrich_p4_on_the_large_mesh(big_mesh):
+    """elem_ext is 62.9 MB, eight chunks, coord_ext 134 MB: the ring comes round inside each."""
+    m = big_mesh['m']
+    assert sc.chunks(15 * 4 * m.info['n_e'])[0] == 8
+    _bits(_enrich_host(m, 'P4'), _p4_ref(big_mesh), 'P4')
+
+
+def test_refine_on_the_large_mesh(big_mesh):
+    """child is 50.3 MB, six chunks."""
+    m = big_mesh['m']
+    assert sc.chunks(12 * 4 * m.info['n_e'])[0] == 6
+    _bits(_refine_host(m), big_mesh['refine'], 'refine')
+
+
+@pytest.mark.parametrize('kind', ['pageable', 'pinned'])
+@pytest.mark.parametrize('with_ed', [True, False], ids=['ed', 'no-ed'])
+def test_enrich_p2_with_and_without_the_edge_tables(small_mesh, kind, with_ed):
+    """P2 with and without elem_ed / edge_el (NULL: no block, no transfer), into pageable arrays 8 bytes off their allocation
+    and into pinned ones: the bits of enrich_dev, the values of the NumPy create_midpoints_P2, and DeviceMesh.enrich's dict
+    equal to the NumPy one key by key (shape, dtype, values), as tests/test_mesh_gpu.py compares them."""
+    import torch
+    m, coord, elem = small_mesh
+    ref = m.enrich_dev('P2')
+    torch.cuda.synchronize()
+    got = _enrich_host(m, 'P2', kind, with_ed)
+    _bits(got, ref[:len(got)], ('P2', kind, with_ed))
+    h = fep.create_midpoints_P2(coord, elem)
+    for a, k in zip(got, ('elem_ext', 'coord_ext', 'surf', 'elem_ed', 'edge_el')):
+        assert a.shape == h[k].shape and np.array_equal(a, h[k]), k
+    d = m.enrich('P2')
+    assert sorted(d) == sorted(h)
+    for k in h:
+        assert d[k].shape == h[k].shape and d[k].dtype == h[k].dtype and np.array_equal(d[k], h[k]), k
+
+
+def test_area_stats_with_two_chunks_each(big):
+    """elem (12.6 MB) and coord (8.4 MB) are two chunks each."""
+    import torch
+    e32 = np.ascontiguousarray(big['elem'][0:3], dtype=np.int32)
+    coord = np.ascontiguousarray(big['coord'], dtype=np.float64)
+    assert sc.chunks(e32.nbytes)[0] == 2 and sc.chunks(coord.nbytes)[0] == 2
+    ref = fep.area_stats_dev(_t(coord), _t(e32), 0)
+    torch.cuda.synchronize()
+    out = _out('pageable', (4,), np.float64)
+    e_h, c_h = sc.place('pageable', e32), sc.place('pageable', coord)
+    assert _lib.lib().fep_mesh_area_stats_host(0, e32.shape[1], coord.shape[1], _p(e_h), _p(c_h), _p(out)) == 0
+    _bits([out], [ref], 'area_stats')
+    assert out[2] == 0 and out[3] == e32.shape[1] and out[1] > 0
+    assert np.array_equal(e_h, e32) and np.array_equal(c_h, coord)                  # the inputs are the caller's
+
+
+def test_mark_bulk_on_five_chunks():
+    """n = 4 * 2^20 + 1000 doubles: four full slots and 8000 bytes.  The values are the 1000 indicators of the marking tests
+    tiled by the rule of staging_cases, so equal values share a fate and a chunk that lands a slot off shows: marked[k] must
+    equal marked[k mod 1000]."""
+    import torch
+    import estimate_cases as ec
+    n = 4 * (1 << 20) + 1000
+    x = sc.tile(ec.value_set(sc.N_BASE), n)
+    assert sc.chunks(x.nbytes) == (5, 8000)
+    l = _lib.lib()
+    X = _t(x)
+    M = torch.empty(n, dtype=torch.uint8, device=X.device)
+    O = torch.empty(4, dtype=torch.float64, device=X.device)
+    assert l.fep_mark_bulk_dev(0, _stream(), n, X.data_ptr(), 0.5, M.data_ptr(), O.data_ptr()) == 0
+    torch.cuda.synchronize()
+    x_h, marked, out = sc.place('pageable', x), _out('pageable', (n,), np.uint8), _out('pageable', (4,), np.float64)
+    assert l.fep_mark_bulk_host(0, n, _p(x_h), 0.5, _p(marked), _p(out)) == 0
+    _bits([marked, out], [M, O], 'mark_bulk')
+    assert 0 < int(marked.sum()) < n and out[2] == marked.sum()
+    assert np.array_equal(marked, sc.tile(marked[:sc.N_BASE], n))
+    assert np.array_equal(x_h, x)
+
+
+@pytest.mark.parametrize('with_parent', [True, False], ids=['parent', 'no-parent'])
+def test_refine_marked_with_and_without_parent(with_parent):
+    """The 40-cell square with the marks of marked_cases' first round (the elements at node 0 and 10 % at random)."""
+    import torch
+    import marked_cases as mc
+    mesh = fep.square_mesh(sc.SMALL_MESH_N, 'P1', 10)
+    elem = mesh['elements']
+    with fep.DeviceMesh(mesh['coordinates'], elem, 0) as m:
+        info = m.mark(mc.round_marks(1, elem, np.random.default_rng(40)))
+        assert elem.shape[1] < info['n_child'] < 4 * elem.shape[1]
+        ref = m.refine_marked_dev()
+        torch.cuda.synchronize()
+        n_child, n_tot = info['n_child'], m.info['n_n'] + info['n_new_nodes']
+        child, coord_ext = _out('pageable', (3, n_child), np.int32), _out('pageable', (2, n_tot), np.float64)
+        parent = _out('pageable', (n_child,), np.int32) if with_parent else None
+        assert _lib.lib().fep_mesh_refine_marked_host(m._h, _p(child), _p(coord_ext), _p(parent)) == 0
+        _bits([coord_ext, child] + ([parent] if with_parent else []), ref[:2 + with_parent], 'refine_marked')
+
+
+def test_mesh_host_forms_alternate_with_dev_forms_and_the_return_map(big_mesh, small_mesh):
+    """What include/fep.h states for these forms.  A *_dev P4 enrich of the large mesh (197 MB written) enqueued on a side stream
+    and a host P4 enrich of the same mesh with nothing between them (both only read the mesh; the host form waits for its own
+    stream alone): both right.  Then, on
+    the engine the mesh-free return map keeps its buffers in: a 1000-point return map, the large refine, the return map again,
+    the small enrich (small -> large -> small through one ring), each equal to its result alone."""
+    import torch
+    m, coord, elem = small_mesh
+    ref = [a.cpu().numpy() for a in m.enrich_dev('P2')]
+    torch.cuda.synchronize()
+    big, ref4 = big_mesh['m'], _p4_ref(big_mesh)
+    side = torch.cuda.Stream()
+    for rep in range(2):
+        with torch.cuda.stream(side):
+            d = big.enrich_dev('P4')
+            got = _enrich_host(big, 'P4')
+        side.synchronize()
+        _bits(got, ref4, ('host beside dev', rep))
+        _bits([a.cpu().numpy() for a in d], ref4, ('dev beside host', rep))
+        del d, got
+    base_rm = oracle('dp', False)[1]
+    for rep in range(2):
+        r = _host_call('dp', sc.base('dp'), sc.N_BASE, 'pageable', True, False)
+        assert all(np.array_equal(r[k], base_rm[k]) for k in OUT)
+        _bits(_refine_host(big_mesh['m']), big_mesh['refine'], ('refine after the return map', rep))
+        _bits(_enrich_host(m, 'P2'), ref, ('small enrich after the large refine', rep))
