@@ -11,6 +11,7 @@
 // masked out (rows and columns), the solution is 0 there.  M = the 2x2 node blocks of K[Q][:,Q].
 #include "fep_common.h"
 #include "fep_host.h"
+#include "fep_solver_levels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -19,9 +20,13 @@
 #include <cstring>
 #include <new>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 namespace {
+
+using fep_levels::DeviceArray;
+using fep_levels::Term;
 
 constexpr int TPB = 256;
 constexpr int NODES_PER_WAVE = 8;           // 8 lanes per NODE (both of its DOF rows), 8 nodes per wave and pass
@@ -335,7 +340,7 @@ csr_kernel(int64_t n_rows, const int32_t* __restrict__ indptr, const int32_t* __
     }
 }
 
-// Transfers in node blocks, single-precision values (Level::Blocks).
+// Transfers in node blocks, single-precision values (fep_levels::Blocks).
 // Prolongation, one lane per fine node:  y(node) = z(node) + sum_blocks B (BF x 3) xc(coarse node)      (y may alias z)
 template <int BF>
 __global__ void __launch_bounds__(TPB)
@@ -480,8 +485,7 @@ mg_scalar_kernel(Scal* sc, int which, const double* part_a, int n_a, const doubl
 // One entry of a sparse product on fixed patterns per thread: out[c] = sum_t coef[t] * V[idx[t]] over the entry's terms
 // (fep_host.h: product_plan), in the plan's order.  One factor of either product is a transfer matrix, fixed since the
 // set-up: its value rides in the term (one 16-byte load per term and one gather instead of two index loads and two gathers:
-// 5.4 -> ... ms per refresh at 1 M DOFs).
-struct Term { double coef; int32_t idx; int32_t pad; };
+// 5.4 -> ... ms per refresh at 1 M DOFs): fep_levels::Term.
 // set-up: the terms from the plan's index pairs; the constant factor's values are on the device already (`first`: it is the
 // first factor — R in R * T — else the second — P in A * P)
 __global__ void __launch_bounds__(TPB)
@@ -640,7 +644,7 @@ constexpr int kTailCoarse = 128;           // DOFs of the coarsest level
 struct TailArgs {
     int n_nodes, n_c;                      // nodes of the level (3 DOFs each), DOFs of the coarsest level
     const int32_t *nbp, *nbc; const float* A; const double* D;        // operator in node blocks, 3x3 block-Jacobi inverses
-    const int32_t *rptr, *rcol; const float* rval;                    // restriction to the coarsest level (Level::Blocks, BF = 3)
+    const int32_t *rptr, *rcol; const float* rval;                    // restriction to the coarsest level (fep_levels::Blocks, BF = 3)
     const int32_t *pptr, *pcol; const float* pval;                    // prolongation from it
     const double* Ainv;                                               // dense inverse, row-major n_c x n_c
     double c1, a2, cp, w2;                                            // Chebyshev coefficients of the level
@@ -782,118 +786,32 @@ dense_inverse_kernel(int n, double* __restrict__ A) {
 
 }  // namespace
 
-struct fep_solver {
+// Every device array below and in the hierarchy (fep_solver_levels.h) frees itself: deleting the solver releases them all.
+struct fep_solver : fep_levels::Multigrid {
     int device = 0;
     int64_t n_n = 0, n_dof = 0, n_blk = 0, n_free = 0;
-    int32_t *nptr = nullptr, *ncol = nullptr;
-    uint8_t* free_dof = nullptr;
-    double *minv = nullptr, *r = nullptr, *u = nullptr, *w = nullptr, *p = nullptr, *s = nullptr;
-    double *part_g = nullptr, *part_r = nullptr, *part_d = nullptr;
-    Scal* scal = nullptr;
+    DeviceArray<int32_t> nptr, ncol;
+    DeviceArray<uint8_t> free_dof;
+    DeviceArray<double> minv, r, u, w, p, s;
+    DeviceArray<double> part_g, part_r, part_d;
+    DeviceArray<Scal> scal;
     int n_vec_blocks = 0, n_mv_blocks = 0;
-    // multigrid preconditioner: level k (k = 0 is the mesh) -> level k+1
-    struct Csr { int64_t n_rows = 0, nnz = 0; int32_t *indptr = nullptr, *indices = nullptr; double* vals = nullptr; };
-    struct Plan { int64_t n_out = 0, n_terms = 0; int32_t* tptr = nullptr; void* terms = nullptr; };      // terms: (coefficient, value index) x 16 bytes
-    struct Level {
-        int64_t n_fine = 0, n_coarse = 0;
-        Csr P, R, A, D;                       // A, D: operator of level k+1 (A = its inverse when last) and its block-Jacobi inverse
-        double omega = 0.0;                   // damping of the smoother on level k
-        bool last = false;
-        double *x = nullptr, *b = nullptr, *r = nullptr, *t = nullptr;      // vectors of level k+1 (t: Chebyshev smoother)
-        std::vector<int32_t> hPp, hPi, hRp, hRi;                            // host patterns of the transfers (refresh plans)
-        // refresh: T = A_k P (values only), A_{k+1} = R T, positions of the 3x3 diagonal blocks in A_{k+1}
-        Plan ap, rt;
-        double* T = nullptr;
-        float* A32 = nullptr;                                               // single-precision copy of A's values for node3_kernel
-        int32_t* d9 = nullptr;
-        int32_t *nbp = nullptr, *nbc = nullptr;                             // node blocks of the padded A (node3_kernel)
-        double* xcur = nullptr;                                             // which of x / t / r holds the level's iterate
-        // The transfers once more for the V-cycle, in node blocks and single precision (the refresh plans keep the double-precision
-        // CSR): a fine node (BF = 2 DOFs on the mesh level, 3 below) against a coarse node (3 DOFs) is one BF x 3 block — one
-        // column id per block instead of one per entry, 4-byte values: P_0 at 1 M DOFs 36 instead of 92 MB per pass.
-        struct Blocks {
-            int bf = 0; int64_t nf = 0, nc = 0, nblk = 0;
-            int32_t *pptr = nullptr, *pcol = nullptr; float* pval = nullptr;   // per fine node: (coarse node, BF x 3 values, row-major)
-            int32_t *rptr = nullptr, *rcol = nullptr; float* rval = nullptr;   // per coarse node: (fine node, 3 x BF values) = the transposes
-        } tb;
-    };
     std::vector<int32_t> ip0, ix0;            // scalar pattern of K on the host (refresh plans)
-    bool refresh = false;                     // every multigrid solve re-projects the coarse operators from its tangent
-    std::vector<Level> levels;
-    double *t0 = nullptr, *q = nullptr;       // level-0 residual of the V-cycle, q = K p
-    // single-precision copy of the solve's K for the V-cycle's four level-0 passes (the preconditioner need not see more than
-    // seven digits of the matrix; CG's own product stays in double precision).  Measured at 1 M DOFs on the LOAD STEPS of BASELINE
-    // configs[3], same session, twice each: 5.93 / 5.95 s with it, 6.20 / 6.43 s without, iteration counts 10 873 / 10 910 (the
-    // first comparison of the round looked at the whole wall, set-up jitter included, and saw 1 %).  On; FEP_AMG_FP32=0 turns it off.
-    float* k32 = nullptr;
-    bool fp32 = true;
     bool tail = true;                         // bottom of the V-cycle in one workgroup (tail_kernel; FEP_AMG_TAIL=0: the launches it replaces)
-    bool block_transfers = true;              // Level::Blocks for the V-cycle's transfers (FEP_AMG_BLOCK_TRANSFERS=0: the CSR forms)
     // smoother of the V-cycle: degree-2 Chebyshev (default) or two damped block-Jacobi sweeps (FEP_AMG_SMOOTHER=jacobi)
     bool cheb = true;
     double cheb_alpha = 20.0, cheb_safety = 1.2;          // K_elast at 1 M DOFs: alpha 5 / 10 / 20 / 30 -> 77 / 70 / 67 / 66 iterations (Jacobi: 90)
 };
 
-static void free_csr(fep_solver::Csr& m) {
-    if (m.indptr) (void)hipFree(m.indptr);
-    if (m.indices) (void)hipFree(m.indices);
-    if (m.vals) (void)hipFree(m.vals);
-    m = fep_solver::Csr();
-}
-static void free_plan(fep_solver::Plan& p) {
-    if (p.tptr) (void)hipFree(p.tptr);
-    if (p.terms) (void)hipFree(p.terms);
-    p = fep_solver::Plan();
-}
-static void free_blocks(fep_solver::Level::Blocks& b) {
-    for (void* v : {(void*)b.pptr, (void*)b.pcol, (void*)b.pval, (void*)b.rptr, (void*)b.rcol, (void*)b.rval}) if (v) (void)hipFree(v);
-    b = fep_solver::Level::Blocks();
-}
-static void free_levels(fep_solver* s) {
-    for (auto& l : s->levels) {
-        free_csr(l.P); free_csr(l.R); free_csr(l.A); free_csr(l.D);
-        for (double* v : {l.x, l.b, l.r, l.t, l.T}) if (v) (void)hipFree(v);
-        if (l.A32) (void)hipFree(l.A32);
-        free_plan(l.ap); free_plan(l.rt);
-        for (int32_t* v : {l.d9, l.nbp, l.nbc}) if (v) (void)hipFree(v);
-        free_blocks(l.tb);
-    }
-    s->levels.clear();
-    s->refresh = false;
-}
-
 extern "C" int fep_solver_destroy(fep_solver* s) {
     if (!s) return FEP_OK;
-    if (fep_set_device(s->device) == FEP_OK) {
-        void* ptrs[] = {s->nptr, s->ncol, s->free_dof, s->minv, s->r, s->u, s->w, s->p, s->s,
-                        s->part_g, s->part_r, s->part_d, s->scal};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        if (s->t0) (void)hipFree(s->t0);
-        if (s->q) (void)hipFree(s->q);
-        if (s->k32) (void)hipFree(s->k32);
-        free_levels(s);
-    }
+    (void)fep_set_device(s->device);                    // (the arrays are freed either way: a pointer of any device can be freed)
     delete s;
     return FEP_OK;
 }
 
-static int solver_create_impl(fep_solver** out, int device_id, int64_t n_n, const int32_t* indptr_h,
-                              const int32_t* indices_h, const uint8_t* free_dof_h);
-
-extern "C" int fep_solver_create(fep_solver** out, int device_id, int64_t n_n, const int32_t* indptr_h,
-                                 const int32_t* indices_h, const uint8_t* free_dof_h) {
-    try {                                               // host vectors of the pattern check: no exception leaves the C ABI
-        return solver_create_impl(out, device_id, n_n, indptr_h, indices_h, free_dof_h);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
-}
-
-static int solver_create_impl(fep_solver** out, int device_id, int64_t n_n, const int32_t* indptr_h,
-                              const int32_t* indices_h, const uint8_t* free_dof_h) {
+static int solver_create(fep_solver** out, int device_id, int64_t n_n, const int32_t* indptr_h,
+                         const int32_t* indices_h, const uint8_t* free_dof_h) {
     if (!out) return FEP_EINVAL;
     *out = nullptr;
     if (n_n <= 0 || !indptr_h || !indices_h || !free_dof_h) return FEP_EINVAL;
@@ -921,7 +839,7 @@ static int solver_create_impl(fep_solver** out, int device_id, int64_t n_n, cons
         }
     }
     FEP_TRY(fep_set_device(device_id));
-    fep_solver* s = new (std::nothrow) fep_solver();
+    std::unique_ptr<fep_solver> s(new (std::nothrow) fep_solver());
     if (!s) return FEP_ENOMEM;
     if (const char* sm = fep_tune("FEP_AMG_SMOOTHER")) s->cheb = std::strcmp(sm, "jacobi") != 0;
     if (const char* al = fep_tune("FEP_AMG_CHEB_ALPHA")) { const double v = std::atof(al); if (v > 1.0) s->cheb_alpha = v; }
@@ -935,25 +853,22 @@ static int solver_create_impl(fep_solver** out, int device_id, int64_t n_n, cons
     for (int64_t i = 0; i < n_dof; ++i) s->n_free += free_dof_h[i] != 0;
     s->n_vec_blocks = (int)((n_n + TPB - 1) / TPB);
     s->n_mv_blocks = (int)((n_n + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK);
-    int rc = FEP_OK;
-    auto up = [&](void** dst, const void* src, size_t bytes) {
-        if (rc != FEP_OK) return;
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 8);
-        if (e == hipSuccess && src) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { fep_g_last_hip = (int)e; (void)hipGetLastError(); rc = e == hipErrorOutOfMemory ? FEP_ENOMEM : FEP_EHIP; }
-    };
-    up((void**)&s->nptr, nptr.data(), nptr.size() * sizeof(int32_t));
-    up((void**)&s->ncol, ncol.data(), ncol.size() * sizeof(int32_t));
-    up((void**)&s->free_dof, free_dof_h, (size_t)n_dof);
-    up((void**)&s->minv, nullptr, (size_t)n_n * 3 * sizeof(double));
-    for (double** v : {&s->r, &s->u, &s->w, &s->p, &s->s}) up((void**)v, nullptr, (size_t)n_dof * sizeof(double));
-    up((void**)&s->part_g, nullptr, (size_t)s->n_vec_blocks * sizeof(double));
-    up((void**)&s->part_r, nullptr, (size_t)s->n_vec_blocks * sizeof(double));
-    up((void**)&s->part_d, nullptr, (size_t)s->n_mv_blocks * sizeof(double));
-    up((void**)&s->scal, nullptr, sizeof(Scal));
-    if (rc != FEP_OK) { fep_solver_destroy(s); return rc; }
-    *out = s;
+    FEP_TRY(s->nptr.upload(nptr));
+    FEP_TRY(s->ncol.upload(ncol));
+    FEP_TRY(s->free_dof.upload(free_dof_h, n_dof));
+    FEP_TRY(s->minv.alloc(3 * n_n));
+    for (DeviceArray<double>* v : {&s->r, &s->u, &s->w, &s->p, &s->s}) FEP_TRY(v->alloc(n_dof));
+    FEP_TRY(s->part_g.alloc(s->n_vec_blocks));
+    FEP_TRY(s->part_r.alloc(s->n_vec_blocks));
+    FEP_TRY(s->part_d.alloc(s->n_mv_blocks));
+    FEP_TRY(s->scal.alloc(1));
+    *out = s.release();
     return FEP_OK;
+}
+
+extern "C" int fep_solver_create(fep_solver** out, int device_id, int64_t n_n, const int32_t* indptr_h,
+                                 const int32_t* indices_h, const uint8_t* free_dof_h) {
+    FEP_GUARD(solver_create(out, device_id, n_n, indptr_h, indices_h, free_dof_h))      // (host vectors of the pattern check)
 }
 
 extern "C" int fep_solver_sizes(const fep_solver* s, int64_t sizes[4]) {
@@ -994,29 +909,23 @@ inline int next_batch(int check_every, double rr_prev, int n_prev, double rr, do
     const int n = (int)std::ceil(need);
     return n < 1 ? 1 : n;
 }
-}  // namespace
 
-extern "C" int fep_solver_pcg_dev(fep_solver* s, void* stream, const double* k_data_d, const double* b_d, double* x_d,
-                                  double rtol, int max_iter, int check_every, int* iters_out, double* relres_out,
-                                  int* state_out) {
-    if (!s || !k_data_d || !b_d || !x_d || !(rtol >= 0.0) || max_iter < 0) return FEP_EINVAL;
+// Host side of both conjugate-gradient solves (s != NULL): the other argument checks, `start(st, tol2)` (enqueues everything
+// up to the first scalar step; its error code ends the solve), then batches of `iterate(st, tol2)` (enqueues one iteration)
+// with the 48-byte read-back of the device-side state between them, and the three outputs.  default_every: check_every where
+// the caller gave none; needs_hierarchy: FEP_ESTATE unless the multigrid hierarchy is complete.
+template <class Start, class Iterate>
+int cg_host_loop(fep_solver* s, void* stream, const double* k_data_d, const double* b_d, double* x_d, double rtol, int max_iter,
+                 int check_every, int default_every, bool needs_hierarchy, int* iters_out, double* relres_out, int* state_out,
+                 Start&& start, Iterate&& iterate) {
+    if (!k_data_d || !b_d || !x_d || !(rtol >= 0.0) || max_iter < 0) return FEP_EINVAL;
     if (!fep_aligned16(k_data_d) || !fep_aligned16(b_d) || !fep_aligned16(x_d)) return FEP_EINVAL;
-    if (check_every <= 0) check_every = 50;
+    if (needs_hierarchy && (s->levels.empty() || !s->levels.back().last)) return FEP_ESTATE;
+    if (check_every <= 0) check_every = default_every;
     FEP_TRY(fep_set_device(s->device));
     hipStream_t st = (hipStream_t)stream;
-    const dim3 gv(s->n_vec_blocks), gm(s->n_mv_blocks), tb(TPB);
     const double tol2 = rtol * rtol;
-    double2 *x = (double2*)x_d, *r = (double2*)s->r, *u = (double2*)s->u, *p = (double2*)s->p, *sv = (double2*)s->s;
-    auto spmv_dot = [&]() {
-        hipLaunchKernelGGL(spmv_kernel<true>, gm, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof,
-                           (const double2*)k_data_d, (const double2*)s->u, s->w, (const double*)s->u, s->part_d);
-    };
-    hipLaunchKernelGGL(block_jacobi_kernel, gv, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof, k_data_d, s->minv);
-    hipLaunchKernelGGL(pcg_init_kernel, gv, tb, 0, st, s->n_n, (const double2*)b_d, s->free_dof, s->minv, x, r, u, p, sv,
-                       s->part_g, s->part_r);
-    spmv_dot();
-    hipLaunchKernelGGL(pcg_scalar_kernel, dim3(1), dim3(1024), 0, st, s->scal, s->part_g, s->part_r, s->n_vec_blocks,
-                       s->part_d, s->n_mv_blocks, tol2, 1);
+    FEP_TRY(start(st, tol2));
     HIP_TRY(hipGetLastError());
     Scal h;
     std::memset(&h, 0, sizeof h);
@@ -1028,13 +937,7 @@ extern "C" int fep_solver_pcg_dev(fep_solver* s, void* stream, const double* k_d
         if (h.state != 0 || launched >= max_iter) break;
         const int n = std::min(next_batch(check_every, rr_prev, n_prev, h.rr, tol2 * h.bb), max_iter - launched);
         rr_prev = h.rr; n_prev = n;
-        for (int i = 0; i < n; ++i) {
-            hipLaunchKernelGGL(pcg_update_kernel, gv, tb, 0, st, s->n_n, s->scal, (const double2*)s->w, s->minv, x, r, u, p,
-                               sv, s->part_g, s->part_r);
-            spmv_dot();
-            hipLaunchKernelGGL(pcg_scalar_kernel, dim3(1), dim3(1024), 0, st, s->scal, s->part_g, s->part_r,
-                               s->n_vec_blocks, s->part_d, s->n_mv_blocks, tol2, 0);
-        }
+        for (int i = 0; i < n; ++i) iterate(st, tol2);
         HIP_TRY(hipGetLastError());
         launched += n;
     }
@@ -1043,6 +946,37 @@ extern "C" int fep_solver_pcg_dev(fep_solver* s, void* stream, const double* k_d
     if (state_out) *state_out = h.state;
     return FEP_OK;
 }
+}  // namespace
+
+extern "C" int fep_solver_pcg_dev(fep_solver* s, void* stream, const double* k_data_d, const double* b_d, double* x_d,
+                                  double rtol, int max_iter, int check_every, int* iters_out, double* relres_out,
+                                  int* state_out) {
+    if (!s) return FEP_EINVAL;
+    const dim3 gv(s->n_vec_blocks), gm(s->n_mv_blocks), tb(TPB);
+    double2 *x = (double2*)x_d, *r = s->r.as<double2>(), *u = s->u.as<double2>(), *p = s->p.as<double2>(), *sv = s->s.as<double2>();
+    auto spmv_dot = [&](hipStream_t st) {
+        hipLaunchKernelGGL(spmv_kernel<true>, gm, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof,
+                           (const double2*)k_data_d, (const double2*)u, s->w, (const double*)s->u, s->part_d);
+    };
+    return cg_host_loop(
+        s, stream, k_data_d, b_d, x_d, rtol, max_iter, check_every, 50, false, iters_out, relres_out, state_out,
+        [&](hipStream_t st, double tol2) {
+            hipLaunchKernelGGL(block_jacobi_kernel, gv, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof, k_data_d, s->minv);
+            hipLaunchKernelGGL(pcg_init_kernel, gv, tb, 0, st, s->n_n, (const double2*)b_d, s->free_dof, s->minv, x, r, u, p, sv,
+                               s->part_g, s->part_r);
+            spmv_dot(st);
+            hipLaunchKernelGGL(pcg_scalar_kernel, dim3(1), dim3(1024), 0, st, s->scal, s->part_g, s->part_r, s->n_vec_blocks,
+                               s->part_d, s->n_mv_blocks, tol2, 1);
+            return (int)FEP_OK;
+        },
+        [&](hipStream_t st, double tol2) {
+            hipLaunchKernelGGL(pcg_update_kernel, gv, tb, 0, st, s->n_n, s->scal, s->w.as<const double2>(), s->minv, x, r, u, p,
+                               sv, s->part_g, s->part_r);
+            spmv_dot(st);
+            hipLaunchKernelGGL(pcg_scalar_kernel, dim3(1), dim3(1024), 0, st, s->scal, s->part_g, s->part_r,
+                               s->n_vec_blocks, s->part_d, s->n_mv_blocks, tol2, 0);
+        });
+}
 
 // ---------------------------------------------------------------------------------------
 // Multigrid-preconditioned conjugate gradients
@@ -1050,168 +984,20 @@ extern "C" int fep_solver_pcg_dev(fep_solver* s, void* stream, const double* k_d
 extern "C" int fep_solver_amg_clear(fep_solver* s) {
     if (!s) return FEP_EINVAL;
     FEP_TRY(fep_set_device(s->device));
-    free_levels(s);
+    fep_levels::drop_levels(*s);
     return FEP_OK;
 }
 
-static int upload_csr(fep_solver::Csr& m, int64_t n_rows, int64_t n_cols, const int32_t* ip, const int32_t* ix,
-                      const double* v) {
-    if (!ip || !ix || !v || ip[0] != 0) return FEP_EINVAL;
-    const int64_t nnz = ip[n_rows];
-    for (int64_t i = 0; i < n_rows; ++i)
-        if (ip[i + 1] < ip[i]) return FEP_EINVAL;
-    for (int64_t t = 0; t < nnz; ++t)
-        if (ix[t] < 0 || ix[t] >= n_cols) return FEP_ERANGE;
-    m.n_rows = n_rows; m.nnz = nnz;
-    HIP_TRY(hipMalloc((void**)&m.indptr, (size_t)(n_rows + 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&m.indices, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&m.vals, (size_t)std::max<int64_t>(nnz, 1) * sizeof(double)));
-    HIP_TRY(hipMemcpy(m.indptr, ip, (size_t)(n_rows + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m.indices, ix, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m.vals, v, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-    return FEP_OK;
-}
-
-static int push_level_impl(fep_solver* s, int64_t n_fine, int64_t n_coarse,
-                           const int32_t* p_indptr, const int32_t* p_indices, const double* p_vals,
-                           const int32_t* r_indptr, const int32_t* r_indices, const double* r_vals,
-                           const int32_t* a_indptr, const int32_t* a_indices, const double* a_vals,
-                           const int32_t* d_indptr, const int32_t* d_indices, const double* d_vals,
-                           double omega_fine, int last);
-
+// (the upload itself: fep_solver_levels.h)
 extern "C" int fep_solver_amg_push_level(fep_solver* s, int64_t n_fine, int64_t n_coarse,
                                          const int32_t* p_indptr, const int32_t* p_indices, const double* p_vals,
                                          const int32_t* r_indptr, const int32_t* r_indices, const double* r_vals,
                                          const int32_t* a_indptr, const int32_t* a_indices, const double* a_vals,
                                          const int32_t* d_indptr, const int32_t* d_indices, const double* d_vals,
                                          double omega_fine, int last) {
-    try {                                               // (host copies of the transfers' patterns: no exception leaves the C ABI)
-        return push_level_impl(s, n_fine, n_coarse, p_indptr, p_indices, p_vals, r_indptr, r_indices, r_vals, a_indptr, a_indices,
-                               a_vals, d_indptr, d_indices, d_vals, omega_fine, last);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
-}
-
-// Level::Blocks from the prolongation in CSR (host): the blocks of a fine node = the coarse nodes any of its BF rows reaches
-// (ascending), entries a row does not hold are zero; the restriction's blocks are the transposes, fine nodes ascending.
-// A level whose sizes are not whole nodes keeps the CSR form (tb.bf stays 0).
-static int build_transfer_blocks(fep_solver::Level& l, int bf, const int32_t* Pp, const int32_t* Pi, const double* Pv) {
-    if (l.n_fine % bf || l.n_coarse % 3) return FEP_OK;
-    const int64_t nf = l.n_fine / bf, nc = l.n_coarse / 3;
-    // two passes over the fine nodes on the host's cores: blocks per node, then (after the running sum) their ids and values
-    std::vector<int32_t> pptr((size_t)nf + 1, 0), pcol;
-    std::vector<float> pval;
-    std::atomic<int> bad{0};
-    auto node_cols = [&](int64_t i, std::vector<int32_t>& cols) {
-        cols.clear();
-        for (int32_t t = Pp[bf * i]; t < Pp[bf * i + bf]; ++t) {
-            if (Pi[t] < 0 || Pi[t] >= l.n_coarse) { bad = 1; return; }
-            cols.push_back(Pi[t] / 3);
-        }
-        std::sort(cols.begin(), cols.end());
-        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-    };
-    fep_host::parallel_chunks(nf, [&](int64_t lo, int64_t hi, int) {
-        std::vector<int32_t> cols;
-        for (int64_t i = lo; i < hi && !bad; ++i) { node_cols(i, cols); pptr[(size_t)i + 1] = (int32_t)cols.size(); }
-    });
-    if (bad) return FEP_ERANGE;
-    for (int64_t i = 0; i < nf; ++i) {
-        const int64_t t = (int64_t)pptr[(size_t)i] + pptr[(size_t)i + 1];
-        if (t >= INT32_MAX / 9) return FEP_ERANGE;
-        pptr[(size_t)i + 1] = (int32_t)t;
-    }
-    pcol.resize((size_t)pptr[(size_t)nf]);
-    pval.assign(pcol.size() * (size_t)(3 * bf), 0.0f);
-    fep_host::parallel_chunks(nf, [&](int64_t lo, int64_t hi, int) {
-        std::vector<int32_t> cols;
-        for (int64_t i = lo; i < hi; ++i) {
-            node_cols(i, cols);
-            const size_t b0 = (size_t)pptr[(size_t)i];
-            std::copy(cols.begin(), cols.end(), pcol.begin() + (std::ptrdiff_t)b0);
-            for (int r = 0; r < bf; ++r)
-                for (int32_t t = Pp[bf * i + r]; t < Pp[bf * i + r + 1]; ++t) {
-                    const size_t b = b0 + (size_t)(std::lower_bound(cols.begin(), cols.end(), Pi[t] / 3) - cols.begin());
-                    pval[b * (size_t)(3 * bf) + (size_t)(3 * r + Pi[t] % 3)] = (float)Pv[t];
-                }
-        }
-    });
-    const size_t nblk = pcol.size();
-    std::vector<int32_t> rptr((size_t)nc + 1, 0), rcol(nblk), fill;
-    std::vector<float> rval(nblk * (size_t)(3 * bf));
-    for (size_t b = 0; b < nblk; ++b) ++rptr[(size_t)pcol[b] + 1];
-    for (int64_t J = 0; J < nc; ++J) rptr[(size_t)J + 1] += rptr[(size_t)J];
-    fill.assign(rptr.begin(), rptr.end() - 1);
-    for (int64_t i = 0; i < nf; ++i)
-        for (int32_t b = pptr[(size_t)i]; b < pptr[(size_t)i + 1]; ++b) {
-            const size_t q = (size_t)fill[(size_t)pcol[(size_t)b]]++;
-            rcol[q] = (int32_t)i;
-            for (int r = 0; r < bf; ++r)
-                for (int c = 0; c < 3; ++c) rval[q * (size_t)(3 * bf) + (size_t)(c * bf + r)] = pval[(size_t)b * (size_t)(3 * bf) + (size_t)(3 * r + c)];
-        }
-    fep_solver::Level::Blocks& B = l.tb;
-    auto up = [&](void** dst, const void* src, size_t bytes) {
-        if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) { (void)hipGetLastError(); return FEP_ENOMEM; }
-        if (bytes && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return FEP_EHIP; }
-        return FEP_OK;
-    };
-    int rc = up((void**)&B.pptr, pptr.data(), pptr.size() * 4);
-    if (rc == FEP_OK) rc = up((void**)&B.pcol, pcol.data(), pcol.size() * 4);
-    if (rc == FEP_OK) rc = up((void**)&B.pval, pval.data(), pval.size() * 4);
-    if (rc == FEP_OK) rc = up((void**)&B.rptr, rptr.data(), rptr.size() * 4);
-    if (rc == FEP_OK) rc = up((void**)&B.rcol, rcol.data(), rcol.size() * 4);
-    if (rc == FEP_OK) rc = up((void**)&B.rval, rval.data(), rval.size() * 4);
-    if (rc != FEP_OK) { free_blocks(B); return rc; }
-    B.bf = bf; B.nf = nf; B.nc = nc; B.nblk = (int64_t)nblk;
-    return FEP_OK;
-}
-
-static int push_level_impl(fep_solver* s, int64_t n_fine, int64_t n_coarse,
-                           const int32_t* p_indptr, const int32_t* p_indices, const double* p_vals,
-                           const int32_t* r_indptr, const int32_t* r_indices, const double* r_vals,
-                           const int32_t* a_indptr, const int32_t* a_indices, const double* a_vals,
-                           const int32_t* d_indptr, const int32_t* d_indices, const double* d_vals,
-                           double omega_fine, int last) {
-    if (!s || n_fine <= 0 || n_coarse <= 0 || !(omega_fine > 0.0)) return FEP_EINVAL;
-    if (!s->levels.empty() && (s->levels.back().last || s->levels.back().n_coarse != n_fine)) return FEP_ESTATE;
-    if (s->levels.empty() && n_fine != s->n_dof) return FEP_EINVAL;
-    if (!last && !d_indptr) return FEP_EINVAL;
-    FEP_TRY(fep_set_device(s->device));
-    s->levels.emplace_back();
-    fep_solver::Level& l = s->levels.back();
-    l.n_fine = n_fine; l.n_coarse = n_coarse; l.omega = omega_fine; l.last = last != 0;
-    int rc = upload_csr(l.P, n_fine, n_coarse, p_indptr, p_indices, p_vals);
-    if (rc == FEP_OK) {
-        l.hPp.assign(p_indptr, p_indptr + n_fine + 1); l.hPi.assign(p_indices, p_indices + p_indptr[n_fine]);
-    }
-    if (rc == FEP_OK) rc = upload_csr(l.R, n_coarse, n_fine, r_indptr, r_indices, r_vals);
-    if (rc == FEP_OK) {
-        l.hRp.assign(r_indptr, r_indptr + n_coarse + 1); l.hRi.assign(r_indices, r_indices + r_indptr[n_coarse]);
-    }
-    if (rc == FEP_OK) rc = upload_csr(l.A, n_coarse, n_coarse, a_indptr, a_indices, a_vals);
-    if (rc == FEP_OK && !last) rc = upload_csr(l.D, n_coarse, n_coarse, d_indptr, d_indices, d_vals);
-    if (rc == FEP_OK && s->block_transfers) rc = build_transfer_blocks(l, s->levels.size() == 1 ? 2 : 3, p_indptr, p_indices, p_vals);
-    for (double** v : {&l.x, &l.b, &l.r, &l.t})
-        if (rc == FEP_OK && hipMalloc((void**)v, (size_t)n_coarse * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = FEP_ENOMEM;
-        }
-    if (rc == FEP_OK && !s->t0) {
-        if (hipMalloc((void**)&s->t0, (size_t)s->n_dof * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&s->q, (size_t)s->n_dof * sizeof(double)) != hipSuccess ||
-            (s->fp32 && hipMalloc((void**)&s->k32, (size_t)s->n_blk * 4 * sizeof(float)) != hipSuccess)) { (void)hipGetLastError(); rc = FEP_ENOMEM; }
-    }
-    if (rc != FEP_OK) {
-        fep_solver::Level& b = s->levels.back();
-        free_csr(b.P); free_csr(b.R); free_csr(b.A); free_csr(b.D);
-        free_blocks(b.tb);
-        for (double* v : {b.x, b.b, b.r, b.t}) if (v) (void)hipFree(v);
-        s->levels.pop_back();
-    }
-    return rc;
+    if (!s) return FEP_EINVAL;
+    FEP_GUARD(fep_levels::push_level(*s, s->device, s->n_dof, s->n_blk, n_fine, n_coarse, p_indptr, p_indices, p_vals, r_indptr,
+                                     r_indices, r_vals, a_indptr, a_indices, a_vals, d_indptr, d_indices, d_vals, omega_fine, last))
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1224,39 +1010,27 @@ static int push_level_impl(fep_solver* s, int64_t n_fine, int64_t n_coarse,
 // ---------------------------------------------------------------------------------------
 namespace {
 
-// RAII for the set-up's temporary device arrays
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)) == hipSuccess ? FEP_OK : ((void)hipGetLastError(), FEP_ENOMEM); }
-    int upload(const std::vector<int32_t>& v) {
-        FEP_TRY(alloc(v.size() * sizeof(int32_t)));
-        if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return FEP_EHIP; }
-        return FEP_OK;
-    }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
 // The terms of C = X * Y on the device (plan_rows_kernel); every pattern is in device memory.  cv_d: values of the constant
 // factor (x_const: X).  Leaves out.tptr / out.terms / out.n_out; *n_terms for the log.
 int device_plan(int64_t n_rows, int64_t n_mid, const int32_t* Xp, const int32_t* Xi, const int32_t* Yp, const int32_t* Yi,
                 const int32_t* Cp, const int32_t* Ci, int64_t dense_cols, int64_t n_out, const double* cv_d, bool x_const,
-                fep_solver::Plan& out, size_t* n_terms) {
+                fep_levels::Plan& out, size_t* n_terms) {
     if (n_out >= INT32_MAX) return FEP_ERANGE;
-    DevTmp cnt, bad;
-    FEP_TRY(cnt.alloc((size_t)n_out * sizeof(int32_t)));
-    FEP_TRY(bad.alloc(sizeof(int)));
-    HIP_TRY(hipMemset(cnt.p, 0, std::max<size_t>((size_t)n_out * sizeof(int32_t), 16)));
-    HIP_TRY(hipMemset(bad.p, 0, sizeof(int)));
+    DeviceArray<int32_t> cnt;
+    DeviceArray<int> bad;
+    FEP_TRY(cnt.alloc(n_out));
+    FEP_TRY(bad.alloc(1));
+    HIP_TRY(hipMemset(cnt, 0, (size_t)cnt.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemset(bad, 0, sizeof(int)));
     const dim3 grid((unsigned)((n_rows + TPB - 1) / TPB)), tb(TPB);
     if (n_rows > 0)
         hipLaunchKernelGGL((plan_rows_kernel<false, false>), grid, tb, 0, 0, n_rows, n_mid, Xp, Xi, Yp, Yi, Cp, Ci, dense_cols,
-                           cnt.as<int32_t>(), (const int32_t*)nullptr, (const double*)nullptr, (Term*)nullptr, bad.as<int>());
+                           cnt, (const int32_t*)nullptr, (const double*)nullptr, (Term*)nullptr, bad);
     HIP_TRY(hipGetLastError());
     std::vector<int32_t> h((size_t)n_out + 1, 0);
     int hb = 0;
-    if (n_out > 0) HIP_TRY(hipMemcpy(h.data() + 1, cnt.p, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&hb, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (n_out > 0) HIP_TRY(hipMemcpy(h.data() + 1, cnt, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hb, bad, sizeof(int), hipMemcpyDeviceToHost));
     if (hb) return hb == 1 ? FEP_EINVAL : FEP_ERANGE;
     int64_t tot = 0;
     for (int64_t c = 1; c <= n_out; ++c) {
@@ -1266,17 +1040,16 @@ int device_plan(int64_t n_rows, int64_t n_mid, const int32_t* Xp, const int32_t*
     }
     out.n_out = n_out;
     out.n_terms = tot;
-    if (hipMalloc((void**)&out.tptr, h.size() * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return FEP_ENOMEM; }
-    HIP_TRY(hipMemcpy(out.tptr, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (hipMalloc(&out.terms, std::max<size_t>((size_t)tot, 1) * sizeof(Term)) != hipSuccess) { (void)hipGetLastError(); return FEP_ENOMEM; }
-    HIP_TRY(hipMemset(cnt.p, 0, std::max<size_t>((size_t)n_out * sizeof(int32_t), 16)));
+    FEP_TRY(out.tptr.upload(h));
+    FEP_TRY(out.terms.alloc(tot));
+    HIP_TRY(hipMemset(cnt, 0, (size_t)cnt.size() * sizeof(int32_t)));
     if (n_rows > 0 && tot > 0) {
         if (x_const)
             hipLaunchKernelGGL((plan_rows_kernel<true, true>), grid, tb, 0, 0, n_rows, n_mid, Xp, Xi, Yp, Yi, Cp, Ci, dense_cols,
-                               cnt.as<int32_t>(), (const int32_t*)out.tptr, cv_d, (Term*)out.terms, bad.as<int>());
+                               cnt, out.tptr, cv_d, out.terms, bad);
         else
             hipLaunchKernelGGL((plan_rows_kernel<true, false>), grid, tb, 0, 0, n_rows, n_mid, Xp, Xi, Yp, Yi, Cp, Ci, dense_cols,
-                               cnt.as<int32_t>(), (const int32_t*)out.tptr, cv_d, (Term*)out.terms, bad.as<int>());
+                               cnt, out.tptr, cv_d, out.terms, bad);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -1284,9 +1057,107 @@ int device_plan(int64_t n_rows, int64_t n_mid, const int32_t* Xp, const int32_t*
     return FEP_OK;
 }
 
+// A plan listed on the host (FEP_AMG_PLAN=host) onto the device: the constant factor's value goes into the term (composed
+// on the device from the index pairs)
+int upload_plan(fep_levels::Plan& d, const fep_host::ProductPlan& h, const double* cv_d, bool first) {
+    d.n_out = (int64_t)h.tptr.size() - 1;
+    d.n_terms = (int64_t)h.xa.size();
+    FEP_TRY(d.tptr.upload(h.tptr));
+    DeviceArray<int32_t> xa, ya;
+    FEP_TRY(xa.upload(h.xa));
+    FEP_TRY(ya.upload(h.ya));
+    const int64_t n = (int64_t)h.xa.size();
+    FEP_TRY(d.terms.alloc(n));
+    if (n > 0) {
+        hipLaunchKernelGGL(compose_terms_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, 0, n, xa, ya, cv_d, first ? 1 : 0, d.terms);
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    return FEP_OK;
+}
+
+// The refresh's patterns, plans and arrays of every level (enable_refresh below drops the hierarchy if this fails)
+int build_refresh(fep_solver* s, bool host_plan, std::vector<size_t>& n_ap, std::vector<size_t>& n_rt) {
+    std::vector<int32_t> Xp = s->ip0, Xi = s->ix0;                       // pattern of the operator of level k, host ...
+    DeviceArray<int32_t> Xp0_d, Xi0_d;                                   // ... and device (level 0: uploaded for the set-up only)
+    if (!host_plan) { FEP_TRY(Xp0_d.upload(Xp)); FEP_TRY(Xi0_d.upload(Xi)); }
+    const int32_t *Xp_d = Xp0_d, *Xi_d = Xi0_d;
+    for (size_t k = 0; k < s->levels.size(); ++k) {
+        fep_levels::Level& l = s->levels[k];
+        std::vector<int32_t> Ap, Ai, d9, nbp, nbc, Tp, Ti;
+        fep_host::ProductPlan ap, rt;
+        FEP_TRY(fep_host::product_pattern(l.n_fine, l.n_fine, l.n_coarse, Xp.data(), Xi.data(), l.hPp.data(), l.hPi.data(), Tp, Ti));
+        if (host_plan) FEP_TRY(fep_host::product_plan(l.n_fine, l.n_fine, Xp.data(), Xi.data(), l.hPp.data(), l.hPi.data(), Tp.data(), Ti.data(), 0, ap));
+        if (l.last) {                                                    // the coarsest operator is dense (it is inverted)
+            if (host_plan) FEP_TRY(fep_host::product_plan(l.n_coarse, l.n_fine, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), nullptr, nullptr, l.n_coarse, rt));
+            Ap.resize((size_t)l.n_coarse + 1); Ai.resize((size_t)(l.n_coarse * l.n_coarse));
+            for (int64_t i = 0; i <= l.n_coarse; ++i) Ap[(size_t)i] = (int32_t)(i * l.n_coarse);
+            for (int64_t i = 0; i < l.n_coarse * l.n_coarse; ++i) Ai[(size_t)i] = (int32_t)(i % l.n_coarse);
+        } else {
+            if (l.n_coarse % 3 || l.D.nnz != 3 * l.n_coarse) return FEP_EINVAL;
+            // the operator of level k+1 moves onto the pattern of the product (SciPy's may have dropped entries)
+            FEP_TRY(fep_host::product_pattern(l.n_coarse, l.n_fine, l.n_coarse, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), Ap, Ai));
+            // padded to whole 3x3 node blocks, the three rows of a node on the same block columns (node3_kernel)
+            {
+                const int64_t nn = l.n_coarse / 3;
+                std::vector<int32_t> Ap2((size_t)l.n_coarse + 1, 0), Ai2, cols;
+                nbp.assign((size_t)nn + 1, 0);
+                for (int64_t I = 0; I < nn; ++I) {
+                    cols.clear();
+                    for (int32_t t = Ap[(size_t)(3 * I)]; t < Ap[(size_t)(3 * I + 3)]; ++t) cols.push_back(Ai[(size_t)t] / 3);
+                    std::sort(cols.begin(), cols.end());
+                    cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+                    nbc.insert(nbc.end(), cols.begin(), cols.end());
+                    if (nbc.size() * 9 >= (size_t)INT32_MAX) return FEP_ERANGE;
+                    nbp[(size_t)I + 1] = (int32_t)nbc.size();
+                    for (int a = 0; a < 3; ++a) {
+                        for (int32_t J : cols) { Ai2.push_back(3 * J); Ai2.push_back(3 * J + 1); Ai2.push_back(3 * J + 2); }
+                        Ap2[(size_t)(3 * I + a + 1)] = (int32_t)Ai2.size();
+                    }
+                }
+                Ap.swap(Ap2); Ai.swap(Ai2);
+            }
+            if (host_plan) FEP_TRY(fep_host::product_plan(l.n_coarse, l.n_fine, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), Ap.data(), Ai.data(), 0, rt));
+            d9.assign((size_t)l.n_coarse * 3, -1);
+            for (int64_t r = 0; r < l.n_coarse; ++r) {
+                const int64_t c0 = r - r % 3;
+                for (int32_t t = Ap[(size_t)r]; t < Ap[(size_t)r + 1]; ++t)
+                    if (Ai[(size_t)t] >= c0 && Ai[(size_t)t] < c0 + 3) d9[(size_t)(3 * r + (Ai[(size_t)t] - c0))] = t;
+            }
+        }
+        // onto the device: the operator on the product's pattern replaces the uploaded one (values come with every refresh)
+        fep_levels::Csr A;
+        A.n_rows = l.n_coarse; A.nnz = (int64_t)Ai.size();
+        FEP_TRY(A.indptr.upload(Ap));
+        FEP_TRY(A.indices.upload(Ai));
+        FEP_TRY(A.vals.alloc(A.nnz));
+        l.A = std::move(A);
+        FEP_TRY(l.T.alloc((int64_t)Ti.size()));
+        if (s->fp32 && !l.last) FEP_TRY(l.A32.alloc(l.A.nnz));
+        if (host_plan) {
+            FEP_TRY(upload_plan(l.ap, ap, l.P.vals, false));
+            FEP_TRY(upload_plan(l.rt, rt, l.R.vals, true));
+            n_ap[k] = ap.xa.size(); n_rt[k] = rt.xa.size();
+        } else {
+            DeviceArray<int32_t> Tp_d, Ti_d;
+            FEP_TRY(Tp_d.upload(Tp));
+            FEP_TRY(Ti_d.upload(Ti));
+            // T = A_k P_k: the constant factor is the second one
+            FEP_TRY(device_plan(l.n_fine, l.n_fine, Xp_d, Xi_d, l.P.indptr, l.P.indices, Tp_d, Ti_d, 0, (int64_t)Ti.size(), l.P.vals, false,
+                                l.ap, &n_ap[k]));
+            // A_{k+1} = R_k T: the first one
+            FEP_TRY(device_plan(l.n_coarse, l.n_fine, l.R.indptr, l.R.indices, Tp_d, Ti_d, l.A.indptr, l.A.indices,
+                                l.last ? l.n_coarse : 0, l.A.nnz, l.R.vals, true, l.rt, &n_rt[k]));
+        }
+        if (!l.last) { FEP_TRY(l.d9.upload(d9)); FEP_TRY(l.nbp.upload(nbp)); FEP_TRY(l.nbc.upload(nbc)); }
+        Xp.swap(Ap); Xi.swap(Ai);
+        Xp_d = l.A.indptr; Xi_d = l.A.indices;
+    }
+    return FEP_OK;
+}
+
 }  // namespace
 
-static int enable_refresh_impl(fep_solver* s) {
+static int enable_refresh(fep_solver* s) {
     if (s->levels.empty() || !s->levels.back().last) return FEP_ESTATE;
     if (s->refresh) return FEP_OK;
     if (s->levels.back().n_coarse > kDenseMax) return FEP_ERANGE;          // (nothing touched: the hierarchy stays usable)
@@ -1297,112 +1168,10 @@ static int enable_refresh_impl(fep_solver* s) {
     // term lists, 0.8 s more of set-up at 1 M DOFs.
     const char* pm = fep_tune("FEP_AMG_PLAN");
     const bool host_plan = pm && std::strcmp(pm, "host") == 0;
-    int rc = FEP_OK;
-    auto up = [&](int32_t** dst, const std::vector<int32_t>& v) {
-        if (rc != FEP_OK) return;
-        hipError_t e = hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(int32_t));
-        if (e == hipSuccess && !v.empty()) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = e == hipErrorOutOfMemory ? FEP_ENOMEM : FEP_EHIP; }
-    };
-    // host plans: the constant factor's value goes into the term (composed on the device from the index pairs)
-    auto up_plan = [&](fep_solver::Plan& d, const fep_host::ProductPlan& h, const double* cv_d, bool first) {
-        d.n_out = (int64_t)h.tptr.size() - 1;
-        d.n_terms = (int64_t)h.xa.size();
-        up(&d.tptr, h.tptr);
-        int32_t *xa = nullptr, *ya = nullptr;
-        up(&xa, h.xa); up(&ya, h.ya);
-        const int64_t n = (int64_t)h.xa.size();
-        if (rc == FEP_OK && hipMalloc(&d.terms, std::max<size_t>((size_t)n, 1) * sizeof(Term)) != hipSuccess) { (void)hipGetLastError(); rc = FEP_ENOMEM; }
-        if (rc == FEP_OK && n > 0) {
-            hipLaunchKernelGGL(compose_terms_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, 0, n, xa, ya, cv_d, first ? 1 : 0, (Term*)d.terms);
-            if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); rc = FEP_EHIP; }
-        }
-        if (xa) (void)hipFree(xa);
-        if (ya) (void)hipFree(ya);
-    };
-    auto dalloc = [&](double** dst, size_t n) {
-        if (rc == FEP_OK && hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); rc = FEP_ENOMEM; }
-    };
     std::vector<size_t> n_ap(s->levels.size(), 0), n_rt(s->levels.size(), 0);
-    std::vector<int32_t> Xp = s->ip0, Xi = s->ix0;                       // pattern of the operator of level k, host ...
-    DevTmp Xp0_d, Xi0_d;                                                 // ... and device (level 0: uploaded for the set-up only)
-    if (!host_plan) { rc = Xp0_d.upload(Xp); if (rc == FEP_OK) rc = Xi0_d.upload(Xi); }
-    const int32_t *Xp_d = Xp0_d.as<int32_t>(), *Xi_d = Xi0_d.as<int32_t>();
-    for (size_t k = 0; k < s->levels.size() && rc == FEP_OK; ++k) {
-        fep_solver::Level& l = s->levels[k];
-        std::vector<int32_t> Ap, Ai, d9, nbp, nbc, Tp, Ti;
-        fep_host::ProductPlan ap, rt;
-        rc = fep_host::product_pattern(l.n_fine, l.n_fine, l.n_coarse, Xp.data(), Xi.data(), l.hPp.data(), l.hPi.data(), Tp, Ti);
-        if (rc != FEP_OK) break;
-        if (host_plan) rc = fep_host::product_plan(l.n_fine, l.n_fine, Xp.data(), Xi.data(), l.hPp.data(), l.hPi.data(), Tp.data(), Ti.data(), 0, ap);
-        if (rc != FEP_OK) break;
-        if (l.last) {                                                    // the coarsest operator is dense (it is inverted)
-            if (host_plan) rc = fep_host::product_plan(l.n_coarse, l.n_fine, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), nullptr, nullptr, l.n_coarse, rt);
-            if (rc != FEP_OK) break;
-            Ap.resize((size_t)l.n_coarse + 1); Ai.resize((size_t)(l.n_coarse * l.n_coarse));
-            for (int64_t i = 0; i <= l.n_coarse; ++i) Ap[(size_t)i] = (int32_t)(i * l.n_coarse);
-            for (int64_t i = 0; i < l.n_coarse * l.n_coarse; ++i) Ai[(size_t)i] = (int32_t)(i % l.n_coarse);
-        } else {
-            if (l.n_coarse % 3 || l.D.nnz != 3 * l.n_coarse) { rc = FEP_EINVAL; break; }
-            // the operator of level k+1 moves onto the pattern of the product (SciPy's may have dropped entries)
-            rc = fep_host::product_pattern(l.n_coarse, l.n_fine, l.n_coarse, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), Ap, Ai);
-            if (rc != FEP_OK) break;
-            // padded to whole 3x3 node blocks, the three rows of a node on the same block columns (node3_kernel)
-            {
-                const int64_t nn = l.n_coarse / 3;
-                std::vector<int32_t> Ap2((size_t)l.n_coarse + 1, 0), Ai2, cols;
-                nbp.assign((size_t)nn + 1, 0);
-                for (int64_t I = 0; I < nn && rc == FEP_OK; ++I) {
-                    cols.clear();
-                    for (int32_t t = Ap[(size_t)(3 * I)]; t < Ap[(size_t)(3 * I + 3)]; ++t) cols.push_back(Ai[(size_t)t] / 3);
-                    std::sort(cols.begin(), cols.end());
-                    cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-                    nbc.insert(nbc.end(), cols.begin(), cols.end());
-                    if (nbc.size() * 9 >= (size_t)INT32_MAX) rc = FEP_ERANGE;
-                    nbp[(size_t)I + 1] = (int32_t)nbc.size();
-                    for (int a = 0; a < 3; ++a) {
-                        for (int32_t J : cols) { Ai2.push_back(3 * J); Ai2.push_back(3 * J + 1); Ai2.push_back(3 * J + 2); }
-                        Ap2[(size_t)(3 * I + a + 1)] = (int32_t)Ai2.size();
-                    }
-                }
-                if (rc != FEP_OK) break;
-                Ap.swap(Ap2); Ai.swap(Ai2);
-            }
-            if (host_plan) rc = fep_host::product_plan(l.n_coarse, l.n_fine, l.hRp.data(), l.hRi.data(), Tp.data(), Ti.data(), Ap.data(), Ai.data(), 0, rt);
-            if (rc != FEP_OK) break;
-            d9.assign((size_t)l.n_coarse * 3, -1);
-            for (int64_t r = 0; r < l.n_coarse; ++r) {
-                const int64_t c0 = r - r % 3;
-                for (int32_t t = Ap[(size_t)r]; t < Ap[(size_t)r + 1]; ++t)
-                    if (Ai[(size_t)t] >= c0 && Ai[(size_t)t] < c0 + 3) d9[(size_t)(3 * r + (Ai[(size_t)t] - c0))] = t;
-            }
-        }
-        // onto the device
-        free_csr(l.A);
-        l.A.n_rows = l.n_coarse; l.A.nnz = (int64_t)Ai.size();
-        up(&l.A.indptr, Ap); up(&l.A.indices, Ai);
-        dalloc(&l.A.vals, Ai.size()); dalloc(&l.T, Ti.size());
-        if (rc == FEP_OK && s->fp32 && !l.last && hipMalloc((void**)&l.A32, std::max<size_t>(Ai.size(), 4) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); rc = FEP_ENOMEM; }
-        if (host_plan) {
-            up_plan(l.ap, ap, l.P.vals, false); up_plan(l.rt, rt, l.R.vals, true);
-            n_ap[k] = ap.xa.size(); n_rt[k] = rt.xa.size();
-        } else if (rc == FEP_OK) {
-            DevTmp Tp_d, Ti_d;
-            rc = Tp_d.upload(Tp);
-            if (rc == FEP_OK) rc = Ti_d.upload(Ti);
-            if (rc == FEP_OK)                                            // T = A_k P_k: the constant factor is the second one
-                rc = device_plan(l.n_fine, l.n_fine, Xp_d, Xi_d, l.P.indptr, l.P.indices, Tp_d.as<int32_t>(), Ti_d.as<int32_t>(), 0,
-                                 (int64_t)Ti.size(), l.P.vals, false, l.ap, &n_ap[k]);
-            if (rc == FEP_OK)                                            // A_{k+1} = R_k T: the first one
-                rc = device_plan(l.n_coarse, l.n_fine, l.R.indptr, l.R.indices, Tp_d.as<int32_t>(), Ti_d.as<int32_t>(), l.A.indptr, l.A.indices,
-                                 l.last ? l.n_coarse : 0, (int64_t)Ai.size(), l.R.vals, true, l.rt, &n_rt[k]);
-        }
-        if (!l.last) { up(&l.d9, d9); up(&l.nbp, nbp); up(&l.nbc, nbc); }
-        Xp.swap(Ap); Xi.swap(Ai);
-        Xp_d = l.A.indptr; Xi_d = l.A.indices;
-    }
     // a failure leaves no half-converted hierarchy behind: it is dropped
-    if (rc != FEP_OK) { free_levels(s); return rc; }
+    const int rc = build_refresh(s, host_plan, n_ap, n_rt);
+    if (rc != FEP_OK) { fep_levels::drop_levels(*s); return rc; }
     if (std::getenv("FEP_VERBOSE")) {
         std::fprintf(stderr, "[fep] multigrid refresh plans (%s):", host_plan ? "host" : "device");
         for (size_t k = 0; k < s->levels.size(); ++k)
@@ -1417,23 +1186,17 @@ static int enable_refresh_impl(fep_solver* s) {
 
 extern "C" int fep_solver_amg_enable_refresh(fep_solver* s) {
     if (!s) return FEP_EINVAL;
-    try {
-        return enable_refresh_impl(s);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
+    FEP_GUARD(enable_refresh(s))
 }
 
 // numeric phase of one product: lanes per output entry by the plan's mean term count (A P: ~7 terms, R (A P): ~19)
-static void product_apply(hipStream_t st, const fep_solver::Plan& p, const double* V, double* out) {
+static void product_apply(hipStream_t st, const fep_levels::Plan& p, const double* V, double* out) {
     if (p.n_out <= 0) return;
     const double mean = (double)p.n_terms / (double)p.n_out;
     auto grid = [&](int lpe) { return dim3((unsigned)((p.n_out * lpe + TPB - 1) / TPB)); };
-    if (mean >= 12.0) hipLaunchKernelGGL(product_kernel<8>, grid(8), dim3(TPB), 0, st, p.n_out, p.tptr, (const Term*)p.terms, V, out);
-    else if (mean >= 3.0) hipLaunchKernelGGL(product_kernel<4>, grid(4), dim3(TPB), 0, st, p.n_out, p.tptr, (const Term*)p.terms, V, out);
-    else hipLaunchKernelGGL(product_kernel<1>, grid(1), dim3(TPB), 0, st, p.n_out, p.tptr, (const Term*)p.terms, V, out);
+    if (mean >= 12.0) hipLaunchKernelGGL(product_kernel<8>, grid(8), dim3(TPB), 0, st, p.n_out, p.tptr, p.terms, V, out);
+    else if (mean >= 3.0) hipLaunchKernelGGL(product_kernel<4>, grid(4), dim3(TPB), 0, st, p.n_out, p.tptr, p.terms, V, out);
+    else hipLaunchKernelGGL(product_kernel<1>, grid(1), dim3(TPB), 0, st, p.n_out, p.tptr, p.terms, V, out);
 }
 
 extern "C" int fep_solver_amg_refresh_dev(fep_solver* s, void* stream, const double* k_data_d) {
@@ -1442,7 +1205,7 @@ extern "C" int fep_solver_amg_refresh_dev(fep_solver* s, void* stream, const dou
     FEP_TRY(fep_set_device(s->device));
     hipStream_t st = (hipStream_t)stream;
     const double* A = k_data_d;
-    for (fep_solver::Level& l : s->levels) {
+    for (fep_levels::Level& l : s->levels) {
         product_apply(st, l.ap, A, l.T);
         product_apply(st, l.rt, (const double*)l.T, l.A.vals);
         if (l.last)
@@ -1462,7 +1225,7 @@ extern "C" int fep_solver_amg_refresh_dev(fep_solver* s, void* stream, const dou
 
 namespace {
 
-inline void csr_apply(hipStream_t st, const fep_solver::Csr& m, const double* x, const double* z, double c0, double c1,
+inline void csr_apply(hipStream_t st, const fep_levels::Csr& m, const double* x, const double* z, double c0, double c1,
                       double* y) {
     if (m.nnz < 12 * m.n_rows)
         hipLaunchKernelGGL((csr_kernel<false, 2>), dim3((unsigned)((m.n_rows * 2 + TPB - 1) / TPB)), dim3(TPB), 0, st, m.n_rows, m.indptr,
@@ -1472,22 +1235,22 @@ inline void csr_apply(hipStream_t st, const fep_solver::Csr& m, const double* x,
                            m.indices, m.vals, x, z, c0, c1, y, (const double*)nullptr, 0.0);
 }
 
-inline void csr_apply2(hipStream_t st, const fep_solver::Csr& m, const double* x, const double* z, double c0, const double* z2,
+inline void csr_apply2(hipStream_t st, const fep_levels::Csr& m, const double* x, const double* z, double c0, const double* z2,
                        double c2, double c1, double* y) {
     const unsigned grid = (unsigned)((m.n_rows * 8 + TPB - 1) / TPB);
     hipLaunchKernelGGL((csr_kernel<true, 8>), dim3(grid), dim3(TPB), 0, st, m.n_rows, m.indptr, m.indices, m.vals, x, z, c0, c1, y, z2, c2);
 }
 
 // restriction b_coarse = R r and prolongation x = x + P x_coarse of one transfer: node blocks when the level has them
-inline void restrict_apply(hipStream_t st, const fep_solver::Level& l, const double* r, double* bc) {
-    const fep_solver::Level::Blocks& B = l.tb;
+inline void restrict_apply(hipStream_t st, const fep_levels::Level& l, const double* r, double* bc) {
+    const fep_levels::Blocks& B = l.tb;
     if (!B.bf) { csr_apply(st, l.R, r, nullptr, 0.0, 1.0, bc); return; }
     const dim3 g((unsigned)((B.nc * 8 + TPB - 1) / TPB)), tb(TPB);
     if (B.bf == 2) hipLaunchKernelGGL(restrict_block_kernel<2>, g, tb, 0, st, B.nc, B.rptr, B.rcol, B.rval, r, bc);
     else hipLaunchKernelGGL(restrict_block_kernel<3>, g, tb, 0, st, B.nc, B.rptr, B.rcol, B.rval, r, bc);
 }
-inline void prolong_apply(hipStream_t st, const fep_solver::Level& l, const double* xc, double* x) {
-    const fep_solver::Level::Blocks& B = l.tb;
+inline void prolong_apply(hipStream_t st, const fep_levels::Level& l, const double* xc, double* x) {
+    const fep_levels::Blocks& B = l.tb;
     if (!B.bf) { csr_apply(st, l.P, xc, x, 1.0, 1.0, x); return; }
     const dim3 g((unsigned)((B.nf + TPB - 1) / TPB)), tb(TPB);
     if (B.bf == 2) hipLaunchKernelGGL(prolong_block_kernel<2>, g, tb, 0, st, B.nf, B.pptr, B.pcol, B.pval, xc, x, x);
@@ -1501,7 +1264,7 @@ inline void block_pass(fep_solver* s, hipStream_t st, const double* K, const dou
     const dim3 gm(s->n_mv_blocks), tb(TPB);
     if (s->fp32 && s->k32)
         hipLaunchKernelGGL((block_residual_kernel<SMOOTH, float2>), gm, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof,
-                           (const float2*)s->k32, (const double2*)x, b, s->minv, omega, out, ca, cprev, (const double2*)xprev);
+                           s->k32.as<const float2>(),(const double2*)x, b, s->minv, omega, out, ca, cprev, (const double2*)xprev);
     else
         hipLaunchKernelGGL((block_residual_kernel<SMOOTH, double2>), gm, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof,
                            (const double2*)K, (const double2*)x, b, s->minv, omega, out, ca, cprev, (const double2*)xprev);
@@ -1526,7 +1289,7 @@ double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const d
 double* vcycle(fep_solver* s, hipStream_t st, const double* K, const double* b0) {
     if (s->cheb) return vcycle_chebyshev(s, st, K, b0);
     const dim3 gv(s->n_vec_blocks), tb(TPB);
-    std::vector<fep_solver::Level>& L = s->levels;
+    std::vector<fep_levels::Level>& L = s->levels;
     const int nl = (int)L.size();
     double *xa = s->u, *xb = s->w;
     const double w0 = L[0].omega;
@@ -1537,7 +1300,7 @@ double* vcycle(fep_solver* s, hipStream_t st, const double* K, const double* b0)
     restrict_apply(st, L[0], s->t0, L[0].b);
     // coarse levels down: level k+1 lives in L[k].{A, D, x, b, r}; its smoother weight is L[k+1].omega
     for (int k = 0; k + 1 < nl; ++k) {
-        fep_solver::Level& c = L[k];
+        fep_levels::Level& c = L[k];
         const double w = L[k + 1].omega;
         csr_apply(st, c.D, c.b, nullptr, 0.0, w, c.x);               // x = w D b
         csr_apply(st, c.A, c.x, c.b, 1.0, -1.0, c.r);                // r = b - A x
@@ -1549,7 +1312,7 @@ double* vcycle(fep_solver* s, hipStream_t st, const double* K, const double* b0)
     csr_apply(st, L[nl - 1].A, L[nl - 1].b, nullptr, 0.0, 1.0, L[nl - 1].x);
     // up
     for (int k = nl - 2; k >= 0; --k) {
-        fep_solver::Level& c = L[k];
+        fep_levels::Level& c = L[k];
         const double w = L[k + 1].omega;
         prolong_apply(st, L[k + 1], L[k + 1].x, c.x);                // x += P x_coarse
         for (int sw = 0; sw < 2; ++sw) {
@@ -1569,7 +1332,7 @@ double* vcycle(fep_solver* s, hipStream_t st, const double* K, const double* b0)
 // hierarchy was built with; a tangent's own largest eigenvalue measured 3.5 % above its elastic matrix's).
 double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const double* b0) {
     const dim3 gv(s->n_vec_blocks), tb(TPB);
-    std::vector<fep_solver::Level>& L = s->levels;
+    std::vector<fep_levels::Level>& L = s->levels;
     const int nl = (int)L.size();
     double *xa = s->u, *xb = s->w;
     const Cheb c0 = cheb_coefficients(L[0].omega, s->cheb_alpha, s->cheb_safety);
@@ -1581,7 +1344,7 @@ double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const d
     // with the refresh the coarse operators sit on whole 3x3 node blocks: node3_kernel does an operator pass and the
     // block-Jacobi step behind it in one launch (7 launches per level and cycle instead of 10)
     const bool n3 = s->refresh;
-    auto node3 = [&](int mode, const fep_solver::Level& c, const double* x, double om, double ca, double cp, const double* xp,
+    auto node3 = [&](int mode, const fep_levels::Level& c, const double* x, double om, double ca, double cp, const double* xp,
                      double* out) {
         const int64_t nn = c.n_coarse / 3;
         // four nodes per lane group only where that still leaves a few thousand workgroups
@@ -1605,16 +1368,16 @@ double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const d
     // the last smoothed level and the coarsest solve under it in one launch when they are small enough (tail_kernel)
     int kt = -1;
     if (s->tail && n3 && nl >= 2) {
-        const fep_solver::Level &c = L[nl - 2], &lst = L[nl - 1];
+        const fep_levels::Level &c = L[nl - 2], &lst = L[nl - 1];
         if (c.A32 && c.n_coarse / 3 <= kTailNodes && lst.n_coarse <= kTailCoarse && lst.n_coarse % 3 == 0 && lst.tb.bf == 3 &&
             lst.tb.nf == c.n_coarse / 3 && lst.A.nnz == lst.n_coarse * lst.n_coarse)
             kt = nl - 2;
     }
     for (int k = 0; k + 1 < nl; ++k) {
-        fep_solver::Level& c = L[k];
+        fep_levels::Level& c = L[k];
         const Cheb ch = cheb_coefficients(L[k + 1].omega, s->cheb_alpha, s->cheb_safety);
         if (k == kt) {
-            const fep_solver::Level& lst = L[nl - 1];
+            const fep_levels::Level& lst = L[nl - 1];
             TailArgs ta;
             ta.n_nodes = (int)(c.n_coarse / 3); ta.n_c = (int)lst.n_coarse;
             ta.nbp = c.nbp; ta.nbc = c.nbc; ta.A = c.A32; ta.D = c.D.vals;
@@ -1645,7 +1408,7 @@ double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const d
         L[nl - 1].xcur = L[nl - 1].x;
     }
     for (int k = kt >= 0 ? kt - 1 : nl - 2; k >= 0; --k) {
-        fep_solver::Level& c = L[k];
+        fep_levels::Level& c = L[k];
         const Cheb ch = cheb_coefficients(L[k + 1].omega, s->cheb_alpha, s->cheb_safety);
         prolong_apply(st, L[k + 1], L[k + 1].xcur, c.xcur);         // x0 = x + P x_coarse
         if (n3) {
@@ -1671,93 +1434,56 @@ double* vcycle_chebyshev(fep_solver* s, hipStream_t st, const double* K, const d
 extern "C" int fep_solver_amg_pcg_dev(fep_solver* s, void* stream, const double* k_data_d, const double* b_d, double* x_d,
                                       double rtol, int max_iter, int check_every, int* iters_out, double* relres_out,
                                       int* state_out) {
-    if (!s || !k_data_d || !b_d || !x_d || !(rtol >= 0.0) || max_iter < 0) return FEP_EINVAL;
-    if (!fep_aligned16(k_data_d) || !fep_aligned16(b_d) || !fep_aligned16(x_d)) return FEP_EINVAL;
-    if (s->levels.empty() || !s->levels.back().last) return FEP_ESTATE;
-    if (check_every <= 0) check_every = 10;
-    FEP_TRY(fep_set_device(s->device));
-    hipStream_t st = (hipStream_t)stream;
+    if (!s) return FEP_EINVAL;
     const dim3 gv(s->n_vec_blocks), gm(s->n_mv_blocks), tb(TPB), one(1), big(1024);
-    const double tol2 = rtol * rtol;
-    double2 *x = (double2*)x_d, *r = (double2*)s->r, *p = (double2*)s->p;
-    if (s->refresh) FEP_TRY(fep_solver_amg_refresh_dev(s, stream, k_data_d));
-    if (s->fp32 && s->k32)
-        hipLaunchKernelGGL(to_float_kernel, dim3((unsigned)((s->n_blk + TPB - 1) / TPB)), tb, 0, st, s->n_blk, (const double4*)k_data_d,
-                           (float4*)s->k32);
-    hipLaunchKernelGGL(block_jacobi_kernel, gv, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof, k_data_d, s->minv);
-    hipLaunchKernelGGL(mg_init_kernel, gv, tb, 0, st, s->n_n, (const double2*)b_d, s->free_dof, x, r, s->part_r);
-    double* z = vcycle(s, st, k_data_d, s->r);
-    hipLaunchKernelGGL(mg_dot_kernel<true>, gv, tb, 0, st, s->n_n, (const double2*)z, (const double2*)r, p, s->part_g);
-    hipLaunchKernelGGL(mg_scalar_kernel, one, big, 0, st, s->scal, 0, s->part_g, s->n_vec_blocks, s->part_r,
-                       s->n_vec_blocks, tol2);
-    HIP_TRY(hipGetLastError());
-    Scal h;
-    std::memset(&h, 0, sizeof h);
-    int launched = 0, n_prev = 0;
-    double rr_prev = 0.0;
-    for (;;) {
-        HIP_TRY(hipMemcpyAsync(&h, s->scal, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h.state != 0 || launched >= max_iter) break;
-        const int n = std::min(next_batch(check_every, rr_prev, n_prev, h.rr, tol2 * h.bb), max_iter - launched);
-        rr_prev = h.rr; n_prev = n;
-        for (int i = 0; i < n; ++i) {
+    double2 *x = (double2*)x_d, *r = s->r.as<double2>(), *p = s->p.as<double2>();
+    return cg_host_loop(
+        s, stream, k_data_d, b_d, x_d, rtol, max_iter, check_every, 10, true, iters_out, relres_out, state_out,
+        [&](hipStream_t st, double tol2) {
+            if (s->refresh) FEP_TRY(fep_solver_amg_refresh_dev(s, stream, k_data_d));
+            if (s->fp32 && s->k32)
+                hipLaunchKernelGGL(to_float_kernel, dim3((unsigned)((s->n_blk + TPB - 1) / TPB)), tb, 0, st, s->n_blk, (const double4*)k_data_d,
+                                   s->k32.as<float4>());
+            hipLaunchKernelGGL(block_jacobi_kernel, gv, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof, k_data_d, s->minv);
+            hipLaunchKernelGGL(mg_init_kernel, gv, tb, 0, st, s->n_n, (const double2*)b_d, s->free_dof, x, r, s->part_r);
+            const double* z = vcycle(s, st, k_data_d, s->r);
+            hipLaunchKernelGGL(mg_dot_kernel<true>, gv, tb, 0, st, s->n_n, (const double2*)z, (const double2*)r, p, s->part_g);
+            hipLaunchKernelGGL(mg_scalar_kernel, one, big, 0, st, s->scal, 0, s->part_g, s->n_vec_blocks, s->part_r,
+                               s->n_vec_blocks, tol2);
+            return (int)FEP_OK;
+        },
+        [&](hipStream_t st, double tol2) {
             hipLaunchKernelGGL(spmv_kernel<true>, gm, tb, 0, st, s->n_n, s->nptr, s->ncol, s->free_dof,
                                (const double2*)k_data_d, (const double2*)p, s->q, (const double*)s->p, s->part_d);
             hipLaunchKernelGGL(mg_scalar_kernel, one, big, 0, st, s->scal, 1, s->part_d, s->n_mv_blocks,
                                (const double*)nullptr, 0, tol2);
-            hipLaunchKernelGGL(mg_update_kernel, gv, tb, 0, st, s->n_n, s->scal, (const double2*)p, (const double2*)s->q,
+            hipLaunchKernelGGL(mg_update_kernel, gv, tb, 0, st, s->n_n, s->scal, (const double2*)p, s->q.as<const double2>(),
                                x, r, s->part_r);
-            z = vcycle(s, st, k_data_d, s->r);
+            const double* z = vcycle(s, st, k_data_d, s->r);
             hipLaunchKernelGGL(mg_dot_kernel<false>, gv, tb, 0, st, s->n_n, (const double2*)z, (const double2*)r,
                                (double2*)nullptr, s->part_g);
             hipLaunchKernelGGL(mg_scalar_kernel, one, big, 0, st, s->scal, 2, s->part_g, s->n_vec_blocks, s->part_r,
                                s->n_vec_blocks, tol2);
             hipLaunchKernelGGL(mg_direction_kernel, gv, tb, 0, st, s->n_n, s->scal, (const double2*)z, p);
-        }
-        HIP_TRY(hipGetLastError());
-        launched += n;
-    }
-    if (iters_out) *iters_out = h.it;
-    if (relres_out) *relres_out = h.bb > 0.0 ? std::sqrt(h.rr / h.bb) : 0.0;
-    if (state_out) *state_out = h.state;
-    return FEP_OK;
+        });
 }
 
 // Greedy aggregation of a node graph (CSR, self loops allowed): pass 1 makes an aggregate of every node whose
 // neighbours are all free, pass 2 attaches the rest to a neighbouring aggregate (or makes singletons).
 extern "C" int fep_aggregate_host(int64_t n, const int32_t* indptr, const int32_t* indices, int32_t* agg_out,
                                   int64_t* n_agg_out) {
-    try {
-        return fep_host::aggregate(n, indptr, indices, agg_out, n_agg_out);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
+    FEP_GUARD(fep_host::aggregate(n, indptr, indices, agg_out, n_agg_out))
 }
 
 // Host sparse product for the multigrid set-up (fep_host.h spgemm_count / spgemm_fill): no GPU involved.
 extern "C" int fep_spgemm_count_host(int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t* x_indptr, const int32_t* x_indices,
                                      const int32_t* y_indptr, const int32_t* y_indices, int32_t* c_indptr_out) {
-    try {
-        return fep_host::spgemm_count(n_rows, n_mid, n_cols, x_indptr, x_indices, y_indptr, y_indices, c_indptr_out);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
+    FEP_GUARD(fep_host::spgemm_count(n_rows, n_mid, n_cols, x_indptr, x_indices, y_indptr, y_indices, c_indptr_out))
 }
 
 extern "C" int fep_spgemm_fill_host(int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t* x_indptr, const int32_t* x_indices,
                                     const double* x_vals, const int32_t* y_indptr, const int32_t* y_indices, const double* y_vals,
                                     const int32_t* c_indptr, int32_t* c_indices_out, double* c_vals_out) {
-    try {
-        return fep_host::spgemm_fill(n_rows, n_mid, n_cols, x_indptr, x_indices, x_vals, y_indptr, y_indices, y_vals, c_indptr,
-                                     c_indices_out, c_vals_out);
-    } catch (const std::bad_alloc&) {
-        return FEP_ENOMEM;
-    } catch (...) {
-        return FEP_EINVAL;
-    }
+    FEP_GUARD(fep_host::spgemm_fill(n_rows, n_mid, n_cols, x_indptr, x_indices, x_vals, y_indptr, y_indices, y_vals, c_indptr,
+                                     c_indices_out, c_vals_out))
 }

@@ -26,6 +26,14 @@
 //      that fails after a device -> host chunk was queued, while copies into the call's blocks are still queued
 //   9. stream_scratch: a smaller need returns the same block, growth returns a new one and leaves the old one allocated, a
 //      capturing stream is refused with nothing allocated
+//  10. DeviceArray (fep_solver_levels.h, the solver's device memory; the stand-ins add a synchronous hipMemcpy and
+//      `g_fail_dev_malloc_after`, which makes the n-th device allocation from now fail): move-construct and move-assign empty
+//      the source and free the overwritten block, a failed alloc leaves the array empty, every block is freed in the end
+//  11. the upload of a multigrid level (push_level, with build_transfer_blocks at BF = 2 and 3) on a hierarchy of 12 -> 6 -> 3
+//      DOFs: every one of a push's device allocations made to fail in turn — FEP_ENOMEM, the level count and the live blocks
+//      as before the call, t0 / q / k32 all set or all empty — then the push itself, the node blocks against the prolongation;
+//      a push after the last level (FEP_ESTATE), a column index out of range (FEP_ERANGE, nothing left allocated), drop_levels,
+//      and the live blocks back at their starting count after destruction
 // Every check of 5 - 8 compares every byte of the result, and every destination ends in a canary block (one slot long, so a
 // whole-slot overrun stays inside the allocation) that must come back untouched; sources have no slack, so ASan sees a read
 // past their end.
@@ -52,6 +60,10 @@
 //                                                              mutants showed as a race report or a crash in the same place,
 //                                                              which is incidental and asserted nowhere; where a run survives
 //                                                              the overrun, the one-slot canary behind the destination catches it
+//   mutant of fep_solver_levels.h
+//   push_level allocates t0 / q / k32 straight into the          [level upload, push 0, allocation 24 of 25 fails] all_or_none(m): t0 stays
+//     hierarchy (`if (!m.t0)`, as before the arrays owned          set without q and k32 (the next push would skip all three)
+//     their blocks) instead of into locals moved in at the end
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -103,7 +115,16 @@ static hipError_t hipHostMalloc(void** p, size_t b, unsigned) {
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
-static hipError_t hipMalloc(void** p, size_t b) { *p = std::malloc(b); if (*p) ++g_dev_live; return *p ? hipSuccess : hipErrorOutOfMemory; }
+static std::atomic<long> g_dev_mallocs{0};               // hipMalloc calls so far
+static std::atomic<long> g_fail_dev_malloc_after{0};     // n > 0: the n-th hipMalloc from now fails (that one only)
+static hipError_t hipMalloc(void** p, size_t b) {
+    ++g_dev_mallocs;
+    if (g_fail_dev_malloc_after.load() > 0 && g_fail_dev_malloc_after.fetch_sub(1) == 1) { *p = nullptr; return hipErrorOutOfMemory; }
+    *p = std::malloc(b);
+    if (*p) ++g_dev_live;
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+static hipError_t hipMemcpy(void* d, const void* s, size_t b, hipMemcpyKind) { std::memcpy(d, s, b); return hipSuccess; }   // synchronous
 static hipError_t hipFree(void* p) { if (p) --g_dev_live; std::free(p); return hipSuccess; }
 enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive = 1 };
 static hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus* cs);
@@ -129,6 +150,7 @@ static void stub_launch(hipStream_t st, void (*fn)(void*), void* arg) { st->push
 #define FEP_TRY(expr) do { int _r = (expr); if (_r != FEP_OK) return _r; } while (0)
 
 #include "../fem-elastoplasticity_amd/csrc/fep_staging.h"
+#include "../fem-elastoplasticity_amd/csrc/fep_solver_levels.h"
 
 using namespace fep_stage;
 
@@ -657,6 +679,169 @@ static int test_stream_scratch() {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// the solver's device arrays and the upload of a multigrid level (fep_solver_levels.h)
+// ---------------------------------------------------------------------------------------
+using fep_levels::DeviceArray;
+
+static int test_device_array() {
+    WHAT("device array");
+    const long live0 = g_dev_live.load();
+    {
+        DeviceArray<double> a, b;
+        CHECK(!a && a.size() == 0);
+        CHECK(a.alloc(0) == FEP_OK && a && a.size() == 1);                   // at least one element
+        CHECK(a.alloc(100) == FEP_OK && a.size() == 100 && g_dev_live.load() == live0 + 1);     // the former block is freed
+        const std::vector<double> v{1.0, 2.0, 3.0};
+        CHECK(b.upload(v) == FEP_OK && b.size() == 3 && std::memcmp(b, v.data(), 24) == 0);
+        double* pb = b;
+        DeviceArray<double> c(std::move(b));                                // move-construct: the source is empty
+        CHECK(!b && b.size() == 0 && c == pb && c.size() == 3 && g_dev_live.load() == live0 + 2);
+        a = std::move(c);                                                   // move-assign: the overwritten block is freed
+        CHECK(!c && c.size() == 0 && a == pb && a.size() == 3 && g_dev_live.load() == live0 + 1);
+        a = std::move(*&a);                                                 // onto itself: nothing happens
+        CHECK(a == pb && g_dev_live.load() == live0 + 1);
+        g_fail_dev_malloc_after = 1;                                        // a failed alloc leaves the array empty
+        fep_g_last_hip = 0;
+        CHECK(a.alloc(50) == FEP_ENOMEM && !a && a.size() == 0 && g_dev_live.load() == live0 && fep_g_last_hip == hipErrorOutOfMemory);
+        g_fail_dev_malloc_after = 1;
+        CHECK(c.upload(v) == FEP_ENOMEM && !c);
+        CHECK(c.upload(v.data(), 0) == FEP_OK && c && c.size() == 1);       // nothing to copy: one element, no read of the source
+        a.reset();
+        CHECK(!a && g_dev_live.load() == live0 + 1);
+    }
+    CHECK(g_dev_live.load() == live0);                                      // the destructors freed the rest
+    return 0;
+}
+
+struct HostCsr {
+    int64_t n_rows = 0, n_cols = 0;
+    std::vector<int32_t> ip, ix;
+    std::vector<double> v;
+    HostCsr(int64_t r, int64_t c) : n_rows(r), n_cols(c), ip(1, 0) {}
+    void entry(int32_t col, double val) { ix.push_back(col); v.push_back(val); }
+    void end_row() { ip.push_back((int32_t)ix.size()); }
+    HostCsr transposed() const {
+        HostCsr t(n_cols, n_rows);
+        for (int64_t c = 0; c < n_cols; ++c) {
+            for (int64_t r = 0; r < n_rows; ++r)
+                for (int32_t k = ip[(size_t)r]; k < ip[(size_t)r + 1]; ++k) if (ix[(size_t)k] == c) t.entry((int32_t)r, v[(size_t)k]);
+            t.end_row();
+        }
+        return t;
+    }
+    double at(int64_t r, int64_t c) const {
+        for (int32_t k = ip[(size_t)r]; k < ip[(size_t)r + 1]; ++k) if (ix[(size_t)k] == c) return v[(size_t)k];
+        return 0.0;
+    }
+};
+static HostCsr dense_csr(int64_t n, double diag, double off) {
+    HostCsr a(n, n);
+    for (int64_t r = 0; r < n; ++r) { for (int64_t c = 0; c < n; ++c) a.entry((int32_t)c, r == c ? diag : off); a.end_row(); }
+    return a;
+}
+// The hierarchy of check 11: 6 mesh nodes (12 DOFs) -> 2 coarse nodes (6 DOFs) -> 1 (3 DOFs); every value is exact in float
+struct TinyHierarchy {
+    static constexpr int64_t kDof = 12, kBlk = 16;
+    HostCsr P0{12, 6}, R0{6, 12}, A1 = dense_csr(6, 4.0, -0.5), D1{6, 6}, P1{6, 3}, R1{3, 6}, A2 = dense_csr(3, 2.0, 0.25);
+    TinyHierarchy() {
+        for (int i = 0; i < 12; ++i) {                   // DOF i = (node i / 2, component i % 2) -> aggregate node / 3: its
+            const int a = i / 6, c = i % 2;              // own component and the rotation
+            P0.entry(3 * a + c, 1.0); P0.entry(3 * a + 2, 0.25 * (i + 1)); P0.end_row();
+        }
+        R0 = P0.transposed();
+        for (int r = 0; r < 6; ++r) { for (int c = 0; c < 3; ++c) D1.entry(3 * (r / 3) + c, r % 3 == c ? 0.5 : 0.125); D1.end_row(); }
+        for (int i = 0; i < 6; ++i) { P1.entry(i % 3, 1.0); if (i % 3 != 2) P1.entry(2, 0.5 * (i + 1)); P1.end_row(); }
+        R1 = P1.transposed();
+    }
+    int push(fep_levels::Multigrid& m, int level, const HostCsr* p = nullptr, const HostCsr* a = nullptr) const {
+        const HostCsr &P = p ? *p : (level == 0 ? P0 : P1), &R = level == 0 ? R0 : R1, &A = a ? *a : (level == 0 ? A1 : A2);
+        return fep_levels::push_level(m, 0, kDof, kBlk, P.n_rows, P.n_cols, P.ip.data(), P.ix.data(), P.v.data(), R.ip.data(), R.ix.data(),
+                                      R.v.data(), A.ip.data(), A.ix.data(), A.v.data(), level == 0 ? D1.ip.data() : nullptr,
+                                      level == 0 ? D1.ix.data() : nullptr, level == 0 ? D1.v.data() : nullptr, 0.7, level == 1);
+    }
+};
+static bool all_or_none(const fep_levels::Multigrid& m) {
+    const int set = (m.t0 ? 1 : 0) + (m.q ? 1 : 0) + (m.k32 ? 1 : 0);
+    return set == 0 || set == 3;
+}
+// the node blocks of a level's transfers hold exactly the prolongation (and the restriction its transposes)
+static bool blocks_match(const fep_levels::Level& l, const HostCsr& P, int bf) {
+    const fep_levels::Blocks& B = l.tb;
+    if (B.bf != bf || B.nf != P.n_rows / bf || B.nc != P.n_cols / 3 || B.pptr[B.nf] != B.nblk || B.rptr[B.nc] != B.nblk) return false;
+    std::vector<double> dp((size_t)(P.n_rows * P.n_cols), 0.0), dr(dp.size(), 0.0);
+    for (int64_t i = 0; i < B.nf; ++i)
+        for (int32_t t = B.pptr[i]; t < B.pptr[i + 1]; ++t)
+            for (int r = 0; r < bf; ++r)
+                for (int c = 0; c < 3; ++c) dp[(size_t)((bf * i + r) * P.n_cols + 3 * B.pcol[t] + c)] = B.pval[(int64_t)t * 3 * bf + 3 * r + c];
+    for (int64_t J = 0; J < B.nc; ++J)
+        for (int32_t t = B.rptr[J]; t < B.rptr[J + 1]; ++t)
+            for (int c = 0; c < 3; ++c)
+                for (int r = 0; r < bf; ++r) dr[(size_t)((bf * B.rcol[t] + r) * P.n_cols + 3 * J + c)] = B.rval[(int64_t)t * 3 * bf + c * bf + r];
+    for (int64_t r = 0; r < P.n_rows; ++r)
+        for (int64_t c = 0; c < P.n_cols; ++c)
+            if (dp[(size_t)(r * P.n_cols + c)] != P.at(r, c) || dr[(size_t)(r * P.n_cols + c)] != P.at(r, c)) return false;
+    return true;
+}
+
+static int test_level_upload() {
+    const TinyHierarchy H;
+    const long live0 = g_dev_live.load();
+    {
+        fep_levels::Multigrid m;                         // (block transfers and the single-precision copy are on by default)
+        CHECK(m.block_transfers && m.fp32);
+        for (int level = 0; level < 2; ++level) {
+            // how many device allocations the push makes: from a push into a copy of the state that is thrown away
+            long n_alloc = 0;
+            {
+                fep_levels::Multigrid probe;
+                if (level == 1) { WHAT("level upload, probe"); CHECK(H.push(probe, 0) == FEP_OK); }
+                const long before = g_dev_mallocs.load();
+                WHAT("level upload, probe of push %d", level);
+                CHECK(H.push(probe, level) == FEP_OK);
+                n_alloc = g_dev_mallocs.load() - before;
+            }
+            CHECK(n_alloc == (level == 0 ? 4 * 3 + 6 + 4 + 3 : 3 * 3 + 6 + 4));     // P R A D, blocks, vectors, t0 q k32 / P R A, ...
+            for (long k = 1; k <= n_alloc; ++k) {
+                WHAT("level upload, push %d, allocation %ld of %ld fails", level, k, n_alloc);
+                const long live = g_dev_live.load();
+                g_fail_dev_malloc_after = k;
+                const int rc = H.push(m, level);
+                CHECK(g_fail_dev_malloc_after.load() == 0);                   // the failure was reached
+                CHECK(rc == FEP_ENOMEM);
+                CHECK((int)m.levels.size() == level);
+                CHECK(all_or_none(m));                                        // t0, q, k32: all set or all empty
+                CHECK(level == 0 ? !m.t0 : !!m.t0);
+                CHECK(g_dev_live.load() == live);
+            }
+            WHAT("level upload, push %d", level);
+            CHECK(H.push(m, level) == FEP_OK && (int)m.levels.size() == level + 1);
+            CHECK(m.t0 && m.q && m.k32 && m.t0.size() == H.kDof && m.q.size() == H.kDof && m.k32.size() == 4 * H.kBlk);
+            CHECK(blocks_match(m.levels[(size_t)level], level == 0 ? H.P0 : H.P1, level == 0 ? 2 : 3));
+            const fep_levels::Level& l = m.levels[(size_t)level];
+            CHECK(l.last == (level == 1) && l.A.nnz == l.n_coarse * l.n_coarse && l.x.size() == l.n_coarse && !l.D.vals == (level == 1));
+            CHECK(std::memcmp(l.P.vals, (level == 0 ? H.P0 : H.P1).v.data(), (size_t)l.P.nnz * 8) == 0 && l.hPi == (level == 0 ? H.P0 : H.P1).ix);
+        }
+        WHAT("level upload, push after the last level");
+        const long live = g_dev_live.load();
+        CHECK(H.push(m, 1) == FEP_ESTATE && m.levels.size() == 2 && g_dev_live.load() == live);
+        WHAT("level upload, drop all levels");
+        fep_levels::drop_levels(m);
+        CHECK(m.levels.empty() && !m.refresh && m.t0 && g_dev_live.load() == live0 + 3);        // t0, q, k32 stay for the next hierarchy
+        WHAT("level upload, column index out of range");
+        HostCsr badP = H.P0, badA = H.A1;
+        badP.ix[5] = 6;                                  // P has 6 columns: refused before anything is allocated
+        badA.ix[7] = -1;                                 // A is checked after P and R are on the device: they are freed again
+        CHECK(H.push(m, 0, &badP, nullptr) == FEP_ERANGE && m.levels.empty() && g_dev_live.load() == live0 + 3);
+        CHECK(H.push(m, 0, nullptr, &badA) == FEP_ERANGE && m.levels.empty() && g_dev_live.load() == live0 + 3);
+        WHAT("level upload, a hierarchy after the dropped one");
+        CHECK(H.push(m, 0) == FEP_OK && H.push(m, 1) == FEP_OK && m.levels.size() == 2);
+    }
+    WHAT("level upload, destruction");
+    CHECK(g_dev_live.load() == live0);
+    return 0;
+}
+
 int main() {
     if (test_pinned()) return 1;
     if (test_pool_two_callers()) return 1;
@@ -667,6 +852,8 @@ int main() {
     if (test_buffer_growth()) return 1;
     if (test_mesh_shaped_calls()) return 1;
     if (test_stream_scratch()) return 1;
+    if (test_device_array()) return 1;
+    if (test_level_upload()) return 1;
     if (pinned().trim() != FEP_OK) return 1;             // the callers' pinned arrays went back to the cache: unpin them
     std::printf("staging ok\n");
     return 0;

@@ -120,6 +120,36 @@ def test_multigrid_pcg_matches_sparse_direct(fep, et, n):
     ctx.close()
 
 
+def test_hierarchy_replaced_on_a_live_solver(fep):
+    """`setup_amg` again on the same solver drops the levels and pushes new ones, here of other sizes (coarse_nodes 30 ->
+    60 -> 30, refresh on: every level's operator is replaced by the one on the product's pattern as well).  The solver then
+    solves as one that never held another hierarchy: bit for bit, in as many iterations."""
+    mesh, ctx, r, qf, rng = _problem(fep, 'P1', 48, True)
+    K_el = ctx.step(np.zeros(ctx.n_dof), want=('K',))['K']
+    b = rng.normal(size=ctx.n_dof)
+
+    def setup_and_solve(sol, coarse_nodes):
+        levels = sol.setup_amg(K_el, mesh['coordinates'], coarse_nodes=coarse_nodes, refresh=True)
+        assert sol.amg_refresh is True
+        x = sol.solve_host(r['K'], b, rtol=1e-11)
+        assert sol.last['state'] == 1 and sol.last['precond'] == 'amg'
+        return levels, x, sol.last['iters']
+
+    sol = fep.KrylovSolver(ctx, qf)
+    lv1, x1, it1 = setup_and_solve(sol, 30)
+    lv2, x2, it2 = setup_and_solve(sol, 60)
+    lv3, x3, it3 = setup_and_solve(sol, 30)
+    assert len(lv1) >= 3 and lv2 != lv1 and lv3 == lv1                      # rebuilt at other sizes in between
+    assert np.linalg.norm((r['K'] @ x2 - b)[qf]) <= 1e-9 * np.linalg.norm(b[qf])
+    assert np.array_equal(x1, x3) and it1 == it3
+    sol.close()
+    fresh = fep.KrylovSolver(ctx, qf)
+    lvf, xf, itf = setup_and_solve(fresh, 30)
+    assert lvf == lv1 and np.array_equal(xf, x1) and np.array_equal(xf, x3) and itf == it1 == it3
+    fresh.close()
+    ctx.close()
+
+
 @pytest.mark.parametrize('et,n', [('P1', 64), ('P2', 16), ('Q1', 32)])
 def test_multigrid_refresh_reprojects_the_coarse_operators(fep, et, n):
     """`setup_amg(..., refresh=True)` (the default): every solve forms its coarse operators from ITS matrix with the
