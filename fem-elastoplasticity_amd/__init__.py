@@ -31,8 +31,11 @@ from .dist_newton import DistributedPCG, GatheredSolver, solve_strip_footing_sha
 from .midpoints import (DeviceMesh, Ellipse, area_stats, area_stats_dev, create_midpoints, create_midpoints_P2, create_midpoints_P4,
                         mark_plastic, refine_marked, refine_uniform)
 from .estimate import estimate_np, indicator_stats, mark_bulk, recover_stress_np, tree_sum
+from .midpoints import child_corners
+from .transfer import (transfer_nodes, transfer_nodes_dev, transfer_nodes_np, transfer_points, transfer_points_dev,
+                       transfer_points_np, transfer_tables, uniform_corners)
 from .meshio import dump_free_dof_csv, load_tsx_mesh, prepare_tsx_mesh
-from . import plasticity2d_dp, tsx_tunnel, elasticity2d, vonmises
+from . import plasticity2d_dp, tsx_tunnel, elasticity2d, vonmises, transfer
 
 __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get_local_basis_volume',
            'element_tables', 'assemble_mesh', 'square_mesh', 'rect_mesh', 'renumber_for_locality', 'Partition', 'ShardedContext', 'element_ranges', 'GatherPlan', 'global_pattern', 'merge_host', 'MeshContext', 'construct_constitutive_problem',
@@ -46,4 +49,6 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'solve_cutout_cyclic',
            'construct_constitutive_problem_field', 'in_situ_strain', 'linear_in_situ',
            'tree_sum', 'recover_stress_np', 'estimate_np', 'indicator_stats', 'mark_bulk',
-           'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d', 'vonmises']
+           'child_corners', 'uniform_corners', 'transfer_tables', 'transfer_nodes_np', 'transfer_points_np', 'transfer_nodes',
+           'transfer_points', 'transfer_nodes_dev', 'transfer_points_dev',
+           'plasticity2d_dp', 'tsx_tunnel', 'elasticity2d', 'vonmises', 'transfer']

@@ -106,6 +106,12 @@ PROTOTYPES = {
     'fep_mesh_mark': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_i64_p]),
     'fep_mesh_refine_marked_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_mesh_refine_marked_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_child_corners_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fep_mesh_child_corners_host': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'fep_transfer_nodes_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 8),
+    'fep_transfer_nodes_host': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_int64] * 4 + [C.c_void_p] * 8),
+    'fep_transfer_points_dev': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
+    'fep_transfer_points_host': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] + [C.c_void_p] * 6),
     'fep_recover_stress_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_recover_stress_host': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'fep_estimate_dev': (C.c_int, [C.c_void_p] * 7),

@@ -9,8 +9,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libfep_hip.so')
-SOURCES = ['fep_api.hip', 'fep_solver.hip', 'fep_mesh.hip']
-DEPS = ['fep_api.hip', 'fep_solver.hip', 'fep_mesh.hip','fep_common.h', 'fep_host.h', 'fep_kernels.hip.h', 'fep_staging.h', 'fep_solver_levels.h', os.path.join('..', '..', 'include', 'fep.h')]
+SOURCES = ['fep_api.hip', 'fep_solver.hip', 'fep_mesh.hip', 'fep_transfer.hip']
+DEPS = ['fep_api.hip', 'fep_solver.hip', 'fep_mesh.hip', 'fep_transfer.hip', 'fep_common.h', 'fep_host.h', 'fep_kernels.hip.h', 'fep_staging.h', 'fep_solver_levels.h', os.path.join('..', '..', 'include', 'fep.h')]
 
 
 def hipcc_path():

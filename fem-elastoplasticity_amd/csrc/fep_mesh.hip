@@ -575,6 +575,32 @@ __global__ void __launch_bounds__(kBlock) refine_marked_kernel(MeshView M, Curve
     if (p >= 0) { put(mm, b, p); put(mm, p, c); } else put(mm, b, c);
 }
 
+// refine_marked_kernel's child logic with the ids replaced by corner codes (fep.h, fep_mesh_child_corners_*): code k = the
+// parent's vertex row k, code 3 + k = the node on its edge k.  One lane per element, from cbase[i] on.
+__global__ void __launch_bounds__(kBlock) child_corners_kernel(MeshView M, const uint8_t* __restrict__ bits, const uint8_t* __restrict__ ref,
+                                                               const int32_t* __restrict__ cbase, int64_t n_c, uint8_t* __restrict__ corners) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= M.n_e) return;
+    const int own = bits[i];
+    int st[3];
+    for (int k = 0; k < 3; ++k) st[k] = edge_state(M.nbr, bits, M.n_e, i, k, own);
+    int64_t at = cbase[i];
+    auto put = [&](int a, int b, int c) {
+        corners[at] = (uint8_t)a;
+        corners[n_c + at] = (uint8_t)b;
+        corners[2 * n_c + at] = (uint8_t)c;
+        ++at;
+    };
+    const int r = ref[i];
+    if (!st[r]) {                                            // no marked edge (the closure marks r whenever one is)
+        put(0, 1, 2);
+        return;
+    }
+    const int a = r, b = (r + 1) % 3, c = (r + 2) % 3, mm = 3 + r, p = 3 + (r + 1) % 3, q = 3 + (r + 2) % 3;
+    if (st[(r + 2) % 3]) { put(a, mm, q); put(q, mm, c); } else put(a, mm, c);
+    if (st[(r + 1) % 3]) { put(mm, b, p); put(mm, p, c); } else put(mm, b, c);
+}
+
 // curve index (-1: none) of every boundary edge, in the surf order of the element type (P2: visit order 1, 2, 0; P4: 0, 1, 2)
 __global__ void __launch_bounds__(kBlock) surf_curve_kernel(MeshView M, CurveSet S, int p2, int32_t* __restrict__ curve_of_surf) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -751,7 +777,8 @@ enum MeshBuf { kMeshElem, kMeshCoord, kMeshNbr, kMeshMask, kMeshBase, kMeshBbase
 // ... of the analysis in fep_mesh_create (released when it returns) ...
 enum CreateBuf { kTmpPtr, kTmpCursor, kTmpList, kTmpCounters, kTmpScan };
 // ... and of one host-form call (a store of the call: allocated by it, released when it returns; nothing persists)
-enum CallBuf { kCallElem, kCallCoord, kCallSurf, kCallElemEd, kCallEdgeEl, kCallParent, kCallEta2, kCallMarked, kCallStats };
+enum CallBuf { kCallElem, kCallCoord, kCallSurf, kCallElemEd, kCallEdgeEl, kCallParent, kCallEta2, kCallMarked, kCallStats,
+               kCallCorners };
 
 }  // namespace
 
@@ -983,6 +1010,20 @@ static int mesh_refine_marked_impl(const fep_mesh* M, hipStream_t st, int32_t* e
     return FEP_OK;
 }
 
+static int check_child_corners(const fep_mesh* M, const uint8_t* corners) {
+    if (!M || !corners) return FEP_EINVAL;
+    return M->refused() || !M->has_marks ? FEP_ESTATE : FEP_OK;
+}
+
+static int mesh_child_corners_impl(const fep_mesh* M, hipStream_t st, uint8_t* corners) {
+    FEP_TRY(check_child_corners(M, corners));
+    FEP_TRY(fep_set_device(M->device));
+    hipLaunchKernelGGL(child_corners_kernel, dim3(grid_for(M->n_e, kBlock)), dim3(kBlock), 0, st, M->view(), M->m_bits, M->m_ref, M->m_cbase,
+                       M->n_child, corners);
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
 static int mesh_set_curves_impl(fep_mesh* M, int n_curves, const double* curves_h) {
     if (!M || n_curves < 0 || n_curves > FEP_MAX_CURVES || (n_curves > 0 && !curves_h)) return FEP_EINVAL;
     CurveSet S{};
@@ -1152,6 +1193,14 @@ static int mesh_refine_marked_host_impl(const fep_mesh* M, int32_t* elem_child_h
     return call.run([&] { return mesh_refine_marked_impl(M, call.stream(), child, coord_ext, parent); });
 }
 
+static int mesh_child_corners_host_impl(const fep_mesh* M, uint8_t* corners_h) {
+    FEP_TRY(check_child_corners(M, corners_h));
+    ScopedStore store;
+    fep_stage::HostCall call(M->device, &store);
+    uint8_t* corners = call.out(kCallCorners, corners_h, (size_t)(3 * M->n_child));
+    return call.run([&] { return mesh_child_corners_impl(M, call.stream(), corners); });
+}
+
 static int mesh_surf_curve_host_impl(const fep_mesh* M, int elem_type, int32_t* curve_of_surf_h) {
     FEP_TRY(check_surf_curve(M, elem_type, curve_of_surf_h));
     ScopedStore store;
@@ -1223,6 +1272,14 @@ extern "C" int fep_mesh_refine_marked_dev(const fep_mesh* mesh, void* stream, in
 
 extern "C" int fep_mesh_refine_marked_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h) {
     FEP_GUARD(mesh_refine_marked_host_impl(mesh, elem_child_h, coord_ext_h, parent_h))
+}
+
+extern "C" int fep_mesh_child_corners_dev(const fep_mesh* mesh, void* stream, uint8_t* corners_d) {
+    FEP_GUARD(mesh_child_corners_impl(mesh, (hipStream_t)stream, corners_d))
+}
+
+extern "C" int fep_mesh_child_corners_host(const fep_mesh* mesh, uint8_t* corners_h) {
+    FEP_GUARD(mesh_child_corners_host_impl(mesh, corners_h))
 }
 
 extern "C" int fep_mesh_set_curves(fep_mesh* mesh, int n_curves, const double* curves_h) {

@@ -434,7 +434,7 @@ inline int scratch_alloc_allowed(hipStream_t st) {
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_OK; }
     return cs == hipStreamCaptureStatusNone ? FEP_OK : FEP_ESTATE;
 }
-enum ScratchTag { kScratchRmCounts, kScratchArea, kScratchIndicator };
+enum ScratchTag { kScratchRmCounts, kScratchArea, kScratchIndicator, kScratchTransfer };
 // The block of `tag` on (device, stream), with room for `bytes`: calls on different streams never share one.  A block that
 // is too small is superseded by one of `grow_bytes` (each user has its own growth rule; never less than `bytes`); that is an
 // allocation, refused (FEP_ESTATE) while the stream is being captured.  The superseded block is never freed: captured graphs

@@ -475,6 +475,23 @@ class DeviceMesh:
                         'fep_mesh_refine_marked_dev')
         return coord_ext, child, parent
 
+    def child_corners(self):
+        """Corner codes (3, n_child) uint8 of refine_marked's children (fep_mesh_child_corners_host), a host array bit-equal
+        to child_corners(coord, elem, marked)."""
+        n_child, _ = self._marked()
+        corners = np.empty((3, n_child), dtype=np.uint8)
+        self._lib.check(self._lib.lib().fep_mesh_child_corners_host(self._h, self._lib.ptr(corners)), 'fep_mesh_child_corners_host')
+        return corners
+
+    def child_corners_dev(self):
+        """Device-resident form -> a (3, n_child) uint8 tensor written on the current stream; nothing is synchronised."""
+        import torch
+        n_child, _ = self._marked()
+        corners = torch.empty((3, n_child), dtype=torch.uint8, device=torch.device('cuda', self.device))
+        self._lib.check(self._lib.lib().fep_mesh_child_corners_dev(self._h, self._stream(), C.c_void_p(corners.data_ptr())),
+                        'fep_mesh_child_corners_dev')
+        return corners
+
 
 def area_stats_dev(coord_d, elem_d, device, out=None):
     """fep_mesh_area_stats_dev on torch tensors of GPU `device` (coord (2, n_n) float64, elem (3, n_e) int32, contiguous),
@@ -609,10 +626,12 @@ def _closed_marks(nbr, ref, marked):
     return bits
 
 
-def _refine_marked_host(coord, elem, marked, rows):
+def _marked_edges(coord, elem, marked):
+    """What _refine_marked_host and child_corners share: (coord float64, elem int64, nbr, owned, ref, state), state (3, n_e)
+    bool = edge k of element i is marked under the closed marks (own bit or the neighbour's)."""
     coord = np.asarray(coord, dtype=np.float64)
     elem = np.asarray(elem).astype(np.int64)
-    n_e, n_n = elem.shape[1], coord.shape[1]
+    n_e = elem.shape[1]
     marked = np.asarray(marked)
     if marked.shape != (n_e,):
         raise ValueError(f'marks: one entry per element ({n_e},), got {marked.shape}')
@@ -620,10 +639,35 @@ def _refine_marked_host(coord, elem, marked, rows):
     nbr, owned = _half_edges(elem)
     ref = reference_edges(coord, elem)
     bits = _closed_marks(nbr, ref, marked)
-    state = np.zeros((3, n_e), dtype=bool)                   # edge k of element i is marked: own bit or the neighbour's
+    state = np.zeros((3, n_e), dtype=bool)
     for k in range(3):
         j, kj = nbr[k] // 3, nbr[k] % 3
         state[k] = ((bits >> k) & 1).astype(bool) | ((nbr[k] >= 0) & (((bits[j] >> kj) & 1) != 0))
+    return coord, elem, nbr, owned, ref, state
+
+
+def child_corners(coord, elem, marked):
+    """Corner codes (3, n_child) uint8 of refine_marked(coord, elem, marked)'s children (include/fep.h, "state transfer across
+    refinement"): corners[k, ch] says what vertex row k of child ch is in its parent — 0, 1, 2 the parent's vertex row,
+    3, 4, 5 the node on the parent's edge 0, 1, 2.  With r the reference edge, a = r, b = (r + 1) % 3, c = (r + 2) % 3,
+    m = 3 + a, p = 3 + b, q = 3 + c the child rows (a, m, q), (q, m, c) | (a, m, c) and (m, b, p), (m, p, c) | (m, b, c) of
+    refine_marked hold exactly those codes; an element without a marked edge gets (0, 1, 2).  The codes do not depend on
+    curves.  The twin of DeviceMesh.child_corners, bit-equal to it."""
+    coord, elem, nbr, owned, ref, state = _marked_edges(coord, elem, marked)
+    out = []
+    for i in range(elem.shape[1]):
+        if not state[:, i].any():
+            out.append((0, 1, 2))
+            continue
+        a, b, c = ((int(ref[i]) + s) % 3 for s in range(3))
+        m, p, q = 3 + a, 3 + b, 3 + c
+        out += ([(a, m, q), (q, m, c)] if state[c, i] else [(a, m, c)]) + ([(m, b, p), (m, p, c)] if state[b, i] else [(m, b, c)])
+    return np.ascontiguousarray(np.array(out, dtype=np.uint8).T)
+
+
+def _refine_marked_host(coord, elem, marked, rows):
+    coord, elem, nbr, owned, ref, state = _marked_edges(coord, elem, marked)
+    n_e, n_n = elem.shape[1], coord.shape[1]
     cv = _curve_rows_py(rows) if rows is not None else None
     # the P2 edge order: owners in element order, their owned slots in the visit order 1, 2, 0
     new_of = np.full((3, n_e), -1, dtype=np.int64)

@@ -350,16 +350,18 @@ def _load_step_loop(ops, K_elast, U_it, d_zeta, d_zeta_min, hist, *, e0_of, acce
             return U, Ep_old
 
 
-def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted):
+def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted, U=None, Ep=None, accept_want=('ind_p',)):
     """A prescribed history of load factors on an external load (no counterpart in the reference, whose plastic drivers
     load through prescribed displacements or an initial stress): for every `zeta` of `zetas` _newton_iteration on the residual
     zeta * f_ext - F(U), started from the last accepted U, then the accepting call, which updates the plastic strain in
     place: the state a load cycle carries.  The stopping quantity is 0 when the correction is exactly 0 (an elastic cycle
     returns to exactly U = 0 at zeta = 0, where the quotient is 0/0).  There is no sub-stepping: a step that does not
     converge ends the history and its index goes to hist['failed_at'].  `accepted(r, zeta, U, its)` records a step from
-    the accepting call's result.  Returns the last accepted U and the plastic strain."""
-    U = ops.zeros()
-    Ep = ops.new_ep()
+    the accepting call's result.  `U`, `Ep`: the state the history goes on from (vectors of `ops`; `Ep` is updated in place),
+    instead of zero: a history that was refined on the way (vonmises.solve_cutout_cyclic, adapt_at); `accept_want`: what the
+    accepting calls return.  Returns the last accepted U and the plastic strain."""
+    U = ops.zeros() if U is None else U
+    Ep = ops.new_ep() if Ep is None else Ep
     criterion = None
     hist['failed_at'] = None
     for k, zeta in enumerate(zetas):
@@ -370,7 +372,7 @@ def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted):
             hist['failed_at'] = k
             break
         U = U_it
-        r = ops.step(U, Ep, accept=True, want=('ind_p',))
+        r = ops.step(U, Ep, accept=True, want=accept_want)
         hist['n_calls'] += 1
         hist['zeta'].append(float(zeta))
         accepted(r, zeta, U, its)
@@ -491,7 +493,7 @@ def _strip_footing(*, mesh, ctx, ops, c0, t_setup, max_steps, zeta_max, keep_U, 
 def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17, monitor=(0, 40), device=None, log=None,
                      linear_solver='direct', pcg_rtol=1e-11, pcg_forcing=None, mesh_dir=None, pcg_inexact_rtol=None,
                      pcg_forcing_cap=1e-4, context_factory=None, refine=0, renumber=False, curves=None, in_situ=None,
-                     body_force=None, materials=None, adapt=0, mark=None, theta=0.5):
+                     body_force=None, materials=None, adapt=0, mark=None, theta=0.5, transfer_materials=False):
     """TSX tunnel excavation (TSX:1637-1832) on a given mesh (`coords` (2,n_n), `elem` (n_p,n_e) 0-based), or — as the
     reference does at TSX:1687-1690 — on the mesh read from `mesh_dir`/coord.csv, elem.csv with the midpoints of
     `element_type` added.  Returns the history of the monitored displacement, plastic-point counts and accepted
@@ -526,7 +528,10 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
     the indicator marks that directly).  Every row of 'adapt' then also holds 'eta' (the square root of the indicator's total),
     'n_nonfinite', 'theta' and 'eta2' (the indicator per element), and a non-finite indicator raises ValueError.
     `refine` is applied first, once; `in_situ` is evaluated again on every mesh;
-    `materials` given as arrays raise ValueError (there is no parent-to-child rule for them yet).  The result is the last
+    `materials` given as arrays raise ValueError unless `transfer_materials` is set: then every array (n_int) goes from each
+    round's mesh to the next by the nearest-point rule of transfer.transfer_points (a copied modulus is one the caller gave;
+    layer interfaces along element edges stay exact), with the element permutation of `renumber` applied to the parents and
+    corner codes first, and every row of 'adapt' holds the round's 'materials' and the refinement's 'corners'.  The result is the last
     run's history — 'coords', 'elem', 'node_of_input' included — plus 'adapt': per run {'n_e', 'n_n', 'n_marked', 'n_child',
     'displ' (the last monitored value), 'n_steps' (accepted load steps), 'n_plast' (at the end), 'plastic' (elements with a plastic point at the end), 'marked', 'parent' (of the
     refinement that followed; None after the last run), 'ind_p' (the last accepted step's flags per integration point), 'coords',
@@ -535,7 +540,7 @@ def solve_tsx_tunnel(coords=None, elem=None, element_type='P1', n_load_steps=17,
         raise ValueError('body_force goes with in_situ (the stress field it is in equilibrium with)')
     if adapt:
         return _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves,
-                             int(adapt), mark, theta, materials,
+                             int(adapt), mark, theta, materials, bool(transfer_materials),
                              dict(n_load_steps=n_load_steps, linear_solver=linear_solver, pcg_rtol=pcg_rtol, pcg_forcing=pcg_forcing,
                                   pcg_forcing_cap=pcg_forcing_cap, pcg_inexact_rtol=pcg_inexact_rtol, in_situ=in_situ,
                                   body_force=body_force))
@@ -561,13 +566,13 @@ def _tsx_run(p, device, context_factory, log, materials, n_load_steps, linear_so
 
 
 def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monitor, device, context_factory, log, curves, adapt,
-                  mark, theta, materials, run_kw):
+                  mark, theta, materials, transfer_materials, run_kw):
     """solve_tsx_tunnel(adapt > 0): solve, mark, refine the marked elements, again."""
     from .hotpath import default_device
     from .mesh import renumber_for_locality
     from .meshio import load_tsx_mesh
     from .estimate import _check_theta, mark_bulk
-    from .midpoints import create_midpoints, mark_plastic, refine_marked, refine_uniform
+    from .midpoints import DeviceMesh, child_corners, create_midpoints, mark_plastic, refine_marked, refine_uniform
     if adapt < 0:
         raise ValueError('adapt must be >= 0')
     zz = isinstance(mark, str)
@@ -575,8 +580,9 @@ def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monito
         raise ValueError(f"mark: None, a callable or 'zz', got {mark!r}")
     if zz:
         theta = _check_theta(theta)
-    if materials is not None and any(np.ndim(m) > 0 for m in materials):
+    if materials is not None and any(np.ndim(m) > 0 for m in materials) and not transfer_materials:
         raise ValueError('adapt: materials per integration point have no parent-to-child rule yet; pass scalars')
+    carry = None                                               # (parent, corners) of the refinement before the round
     t = _coerce(element_type)
     if mesh_dir is not None:
         coords, elem = load_tsx_mesh(mesh_dir, 'P1')
@@ -593,10 +599,16 @@ def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monito
     rounds = []
     for k in range(adapt + 1):
         if renumber:
-            e1, c1, node_perm, _ = renumber_for_locality(e1, c1)
+            e1, c1, node_perm, elem_perm = renumber_for_locality(e1, c1)
             inv = np.empty_like(node_perm)
             inv[node_perm] = np.arange(node_perm.size)
             input_ids = inv[input_ids]
+            if carry is not None:                              # new element j is old element elem_perm[j]
+                carry = (carry[0][elem_perm], np.ascontiguousarray(carry[1][:, elem_perm]))
+        if carry is not None:
+            from .transfer import transfer_points
+            materials = tuple(m if np.ndim(m) == 0 else transfer_points(t, carry[0], carry[1], np.asarray(m, dtype=np.float64).ravel(),
+                                                                        device=mesh_device) for m in materials)
         ck, ek = c1, e1
         if t is not LagrangeElementType.P1:
             ext = create_midpoints(t, c1, e1, device=mesh_device, curves=curves)
@@ -613,6 +625,8 @@ def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monito
                'ind_p': flags, 'coords': ck, 'elem': ek}
         if zz:
             row.update(eta=float(np.sqrt(est['total'])), n_nonfinite=est['n_nonfinite'], theta=theta, eta2=est['eta2'])
+        if transfer_materials and materials is not None:
+            row['materials'] = materials
         rounds.append(row)
         if log:
             log(f'adapt {k}: {row["n_e"]} elements, {row["n_n"]} nodes, U{monitor}={row["displ"]:.16g}')
@@ -626,8 +640,18 @@ def _tsx_adaptive(coords, elem, element_type, mesh_dir, refine, renumber, monito
             marked = mark_plastic(flags, e1, n_q, rings=1) if mark is None else np.asarray(mark(hist, c1, e1)) != 0
         if marked.shape != (e1.shape[1],):
             raise ValueError(f'mark: one entry per element ({e1.shape[1]},), got {marked.shape}')
+        if transfer_materials and materials is not None:
+            if mesh_device is None:
+                corners = child_corners(c1, e1, marked)
+            else:
+                with DeviceMesh(c1, e1, mesh_device) as m:
+                    m.mark(marked)
+                    corners = m.child_corners()
+            row['corners'] = corners
         c1, e1, parent = refine_marked(c1, e1, marked, device=mesh_device, curves=curves)
         row.update(n_marked=int(marked.sum()), n_child=int(e1.shape[1]), marked=marked, parent=parent)
+        if 'corners' in row:
+            carry = (parent, row['corners'])
     hist['adapt'] = rounds
     return hist
 

@@ -202,6 +202,78 @@ def surface_tables(el_type):
             np.ascontiguousarray(np.asarray(wf_s, dtype=float).ravel()))
 
 
+# ---- state transfer across refinement (include/fep.h, "state transfer across refinement") -------------------------------------
+#: barycentric coordinates (V1, V2, V3) of a corner code: 0..2 the parent's vertices, 3..5 the nodes on its edges 0..2
+CORNER_BARYCENTRICS = np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [.5, .5, 0], [0, .5, .5], [.5, 0, .5]])
+#: children 4 i .. 4 i + 3 of uniform refinement (refine_uniform), one row of codes per child
+UNIFORM_CORNERS = ((0, 3, 5), (3, 1, 4), (5, 4, 2), (3, 4, 5))
+N_TRANSFER_SHAPES = 21                                                     # FEP_TRANSFER_SHAPES of include/fep.h
+
+
+def transfer_shapes():
+    """The corner triples that occur, (21, 3) uint8, in ascending order of c0 + 6 c1 + 36 c2: the identity (0, 1, 2); for
+    every reference edge r, with a = r, b = (r + 1) % 3, c = (r + 2) % 3, m = 3 + r, p = 3 + b, q = 3 + c, the six rows
+    (a, m, q), (q, m, c), (a, m, c), (m, b, p), (m, p, c), (m, b, c) of marked refinement; the four of uniform refinement,
+    two of which marked refinement has as well."""
+    found = {(0, 1, 2)} | set(UNIFORM_CORNERS)
+    for r in range(3):
+        a, b, c = r, (r + 1) % 3, (r + 2) % 3
+        m, p, q = 3 + a, 3 + b, 3 + c
+        found |= {(a, m, q), (q, m, c), (a, m, c), (m, b, p), (m, p, c), (m, b, c)}
+    shapes = np.array(sorted(found, key=lambda s: s[0] + 6 * s[1] + 36 * s[2]), dtype=np.uint8)
+    assert shapes.shape == (N_TRANSFER_SHAPES, 3)
+    return shapes
+
+
+def child_node_barycentrics(el_type):
+    """Barycentric coordinates (n_p, 3) of the local nodes of a triangle type, in its local node order."""
+    t = _coerce(el_type)
+    if t is LagrangeElementType.P1:
+        return np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1]], dtype=float)
+    if t is LagrangeElementType.P2:                                        # vertices, then m23, m31, m12
+        return np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [0, .5, .5], [.5, 0, .5], [.5, .5, 0]])
+    if t is LagrangeElementType.P4:
+        return np.array([ms for _, ms in _P4_TERMS], dtype=float) / 4
+    raise ValueError(f'state transfer covers P1, P2 and P4 triangles, not {t}')
+
+
+def transfer_tables(el_type):
+    """What the state transfer needs to know about a triangle type, per SHAPE (a triple of corner codes: where a child
+    sits in its parent), computed once in float64:
+      'shapes'        (21, 3) uint8, transfer_shapes()
+      'shape_of_code' (216,) int8, indexed c0 + 6 c1 + 36 c2; -1 for a triple that is no shape
+      'W'             (21, n_p, n_p): W[s, j, a] = basis function a of the parent at the parent coordinates of the child's
+                      node j.  A point with barycentrics l in the child has L = (l0 B[c0] + l1 B[c1]) + l2 B[c2] in the parent
+                      (B = CORNER_BARYCENTRICS) and reference coordinates (L[1], L[2]); the node points are multiples of 1/8
+                      after the map, so they are exact doubles, and P1 / P2 weights are exact as well
+      'near'          (21, n_q) uint8: for the child's integration point k, the parent's point with the smallest
+                      (x1 - xi1')^2 + (x2 - xi2')^2, searched in ascending order with a strict <, so the lowest index wins a
+                      tie.  P1: all zero."""
+    t = _coerce(el_type)
+    nodes = child_node_barycentrics(t)
+    n_p, n_q = ELEMENT_SHAPE[t]
+    shapes = transfer_shapes()
+    shape_of_code = np.full(216, -1, dtype=np.int8)
+    xi, _ = get_quadrature_volume(t)
+    lq = np.array([1 - xi[0] - xi[1], xi[0], xi[1]]).T                     # (n_q, 3)
+    W = np.zeros((shapes.shape[0], n_p, n_p))
+    near = np.zeros((shapes.shape[0], n_q), dtype=np.uint8)
+    for s, (c0, c1, c2) in enumerate(shapes):
+        shape_of_code[int(c0) + 6 * int(c1) + 36 * int(c2)] = s
+        B0, B1, B2 = CORNER_BARYCENTRICS[c0], CORNER_BARYCENTRICS[c1], CORNER_BARYCENTRICS[c2]
+        L = (nodes[:, 0:1] * B0 + nodes[:, 1:2] * B1) + nodes[:, 2:3] * B2
+        W[s] = np.broadcast_to(get_local_basis_volume(t, L[:, 1:3].T)[0], (n_p, n_p)).T
+        Lq = (lq[:, 0:1] * B0 + lq[:, 1:2] * B1) + lq[:, 2:3] * B2
+        for k in range(n_q):
+            best, d_best = 0, np.inf
+            for kk in range(n_q):
+                d = (Lq[k, 1] - xi[0, kk]) ** 2 + (Lq[k, 2] - xi[1, kk]) ** 2
+                if d < d_best:
+                    best, d_best = kk, d
+            near[s, k] = best
+    return {'shapes': shapes, 'shape_of_code': shape_of_code, 'W': np.ascontiguousarray(W), 'near': near}
+
+
 def element_tables(el_type):
     """(dhatp1, dhatp2, wf) as C-contiguous (n_p,n_q), (n_p,n_q), (n_q,) float64 arrays —
     the form the C ABI takes (include/fep.h: fep_ctx_create)."""

@@ -56,7 +56,8 @@
  *   mesh and a driver makes one mesh per level, so every call allocates its blocks and frees them before it returns, and
  *   nothing persists.  No *_dev call needs synchronising against them either: they only read the mesh, and what writes it
  *   (fep_mesh_create, fep_mesh_mark) synchronises before it returns.  Their kernel scratch (area statistics, the indicator's
- *   partials) is that of the engine's stream.
+ *   partials) is that of the engine's stream.  fep_mesh_child_corners_host, fep_transfer_nodes_host and
+ *   fep_transfer_points_host follow the mesh forms in all of this (the owners of the node transfer are such kernel scratch).
  */
 #ifndef FEP_H
 #define FEP_H
@@ -664,6 +665,74 @@ int fep_mesh_area_stats_host(int device_id, int64_t n_e, int64_t n_n, const int3
 int fep_mesh_mark(fep_mesh* mesh, void* stream, const uint8_t* marked, int on_device, int64_t out[4]);
 int fep_mesh_refine_marked_dev(const fep_mesh* mesh, void* stream, int32_t* elem_child_d, double* coord_ext_d, int32_t* parent_d);
 int fep_mesh_refine_marked_host(const fep_mesh* mesh, int32_t* elem_child_h, double* coord_ext_h, int32_t* parent_h);
+
+/* ---- state transfer across refinement: displacement and per-point state from parents to children --------------------
+ * No reference counterpart.  Opt-in: without these calls every output above is byte for byte what it was.  Triangles only
+ * (FEP_P1, FEP_P2, FEP_P4), the same element type on both meshes.
+ *
+ *   corner codes  parent[child] does not say WHICH part of the parent a child is; corners (3, n_child) uint8 does:
+ *       corners[k, ch] describes vertex row k of child ch: 0, 1, 2 = the parent's vertex row 0, 1, 2; 3, 4, 5 = the node on the
+ *       parent's edge 0, 1, 2 (edge k runs from vertex k to vertex (k + 1) % 3).  Marked refinement, in the names of
+ *       fep_mesh_mark's "children" with a = r, b = (r + 1) % 3, c = (r + 2) % 3, m = 3 + r, p = 3 + (r + 1) % 3,
+ *       q = 3 + (r + 2) % 3: the rows (a, m, q), (q, m, c) | (a, m, c) and (m, b, p), (m, p, c) | (m, b, c) hold exactly those
+ *       codes; an element without a marked edge gets (0, 1, 2).  Uniform refinement (fep_mesh_refine_*): children 4 i .. 4 i + 3
+ *       are (0, 3, 5), (3, 1, 4), (5, 4, 2), (3, 4, 5) with parent = child / 4: a constant table, no kernel.  The codes do not
+ *       depend on curves: the reference edge is decided on vertex chords.
+ *   fep_mesh_child_corners_*  corners (3, n_child) of the marks the mesh holds.  FEP_ESTATE on the conditions of
+ *       fep_mesh_refine_marked_*; FEP_EINVAL: NULL pointers.  The _dev form enqueues one kernel (one lane per element, writing
+ *       from the first child of the element on) and allocates nothing; the _host form is synchronous.
+ *
+ *   barycentrics of a code, in the order (V1, V2, V3):  B[0] = (1, 0, 0), B[1] = (0, 1, 0), B[2] = (0, 0, 1),
+ *       B[3] = (1/2, 1/2, 0), B[4] = (0, 1/2, 1/2), B[5] = (1/2, 0, 1/2).  A point with barycentrics l in the child has
+ *       L = l0 B[c0] + l1 B[c1] + l2 B[c2] in the parent, reference coordinates (x1, x2) = (L[1], L[2]).
+ *   shape   a triple of codes.  FEP_TRANSFER_SHAPES = 21 occur (the identity, 18 of marked refinement, 4 uniform, 2 of them
+ *       shared), numbered in ascending order of c0 + 6 c1 + 36 c2.  What depends on the shape alone is data, computed on the host
+ *       in float64 (tables.py, transfer_tables) and handed over; the library knows no basis function:
+ *         shape_of_code (216) int8   indexed c0 + 6 c1 + 36 c2; -1 for a triple that is no shape
+ *         w    (FEP_TRANSFER_SHAPES, n_p, n_p)   w[s, j, a] = basis function a of the parent at the parent coordinates of the
+ *                                                child's node j
+ *         near (FEP_TRANSFER_SHAPES, n_q) uint8  the parent's integration point nearest (in reference coordinates, the lowest
+ *                                                index on a tie) to the child's point k
+ *   nodes   u (n_n_parent, n_comp) row-major, n_comp in 1..4 (the interleaved U of the drivers is n_comp = 2), u_child
+ *       (n_n_child, n_comp).  For child ch with e = parent[ch], s = shape_of_code[corners[:, ch]], local node j, component i:
+ *       acc = 0.0, then for a = 0 .. n_p - 1:  acc = acc + w[s, j, a] * u[elem_parent[a, e], i]  — one IEEE double product and
+ *       one addition per term, terms with a zero weight like any other, nothing contracted.  A child node is written once, by
+ *       the lowest pair index ch n_p + j among the (child element, local node) pairs that hold it: an integer minimum, the
+ *       only atomic.  A node of no child element gets NaN (fep_transform_*).  So an old vertex keeps its value: == the input
+ *       and bit-equal to it, except that -0.0 becomes +0.0.
+ *   points  q (n_rows, n_e n_q) planar (a plastic strain is 4 rows, a material 1), q_child (n_rows, n_child n_q):
+ *       q_child[:, ch n_q + k] = q[:, e n_q + near[s, k]], a bitwise copy: a copied value is one the model has produced or
+ *       accepted, an extrapolated one can leave the yield surface or turn a modulus negative.
+ *   bad input never reads out of bounds: a child whose parent is outside [0, n_e), whose triple has a code above 5 or is no
+ *       shape, or whose parent element names a node outside [0, n_n_parent), gets NaN in all its point values and in the nodes
+ *       it owns; a child node id outside [0, n_n_child) is skipped.  Nothing else changes.
+ *   non-finite values (the four rules of fep_return_map_*): a NaN at a parent node reaches exactly the nodes owned by children of
+ *       the elements that hold it (0 * NaN is NaN: also where its weight is 0), a NaN at a parent point exactly the child
+ *       points that copy it; a clean call afterwards gives the clean bytes.
+ *
+ * The _dev forms only enqueue: no read-back, no synchronisation.  The owners (8 bytes per child node) live in one grow-only
+ * block per (device, stream), by the rule of counts_d (fep_return_map_dev): FEP_ESTATE if it would have to grow while the stream
+ * is being captured (run the call once outside the capture first).  The _host forms are synchronous, on the library's stream
+ * with device blocks of the call, as the mesh forms.  FEP_EINVAL: NULL pointers (of arrays that are not empty), elem_type not
+ * P1 / P2 / P4, n_comp outside 1..4, n_rows < 1, negative counts, an output that shares bytes with an input; FEP_ERANGE: a count
+ * of 2^31 - 1 or more.  n_child = 0 is legal (every child node is then a node of no element).  A refused call writes nothing. */
+#define FEP_TRANSFER_SHAPES 21
+int fep_mesh_child_corners_dev(const fep_mesh* mesh, void* stream, uint8_t* corners_d);
+int fep_mesh_child_corners_host(const fep_mesh* mesh, uint8_t* corners_h);
+int fep_transfer_nodes_dev(int device_id, void* stream, int elem_type, int n_comp, int64_t n_e, int64_t n_n_parent, int64_t n_child,
+                           int64_t n_n_child, const int32_t* elem_parent_d, const int32_t* elem_child_d, const int32_t* parent_d,
+                           const uint8_t* corners_d, const int8_t* shape_of_code_d, const double* w_d, const double* u_d,
+                           double* u_child_d);
+int fep_transfer_nodes_host(int device_id, int elem_type, int n_comp, int64_t n_e, int64_t n_n_parent, int64_t n_child,
+                            int64_t n_n_child, const int32_t* elem_parent_h, const int32_t* elem_child_h, const int32_t* parent_h,
+                            const uint8_t* corners_h, const int8_t* shape_of_code_h, const double* w_h, const double* u_h,
+                            double* u_child_h);
+int fep_transfer_points_dev(int device_id, void* stream, int elem_type, int n_rows, int64_t n_e, int64_t n_child,
+                            const int32_t* parent_d, const uint8_t* corners_d, const int8_t* shape_of_code_d, const uint8_t* near_d,
+                            const double* q_d, double* q_child_d);
+int fep_transfer_points_host(int device_id, int elem_type, int n_rows, int64_t n_e, int64_t n_child, const int32_t* parent_h,
+                             const uint8_t* corners_h, const int8_t* shape_of_code_h, const uint8_t* near_h, const double* q_h,
+                             double* q_child_h);
 
 /* ---- recovered-stress error indicator and bulk marking: what decides the marks of fep_mesh_mark ----------------------
  * No reference counterpart.  Opt-in: without these calls every output above is byte for byte what it was.  Zienkiewicz-Zhu:
