@@ -17,11 +17,12 @@ from .tables import (ELEMENT_SHAPE, LagrangeElementType, element_tables, get_loc
 from .mesh import assemble_mesh, assemble_mesh_el, rect_mesh, renumber_for_locality, square_mesh
 from .hotpath import (MeshContext, assemble_tangent, construct_constitutive_problem,
                       construct_constitutive_problem_tsx, construct_constitutive_problem_vm, construct_constitutive_problem_mc,
-                      construct_constitutive_problem_vmps,
+                      construct_constitutive_problem_vmps, construct_constitutive_problem_vmi,
                       construct_constitutive_problem_field, in_situ_strain, linear_in_situ, default_device, get_elastic_stiffness_matrix,
                       get_elastic_stiffness_matrix_el, get_vector_traction, get_vector_volume, load_traction)
 from .elastic import solve_elasticity2d
 from .vonmises import solve_cutout_cyclic
+from .hardening import hardening_curve, voce_curve
 from ._lib import FepError, lib, lib_path
 from .build import build
 from .sharding import GatherPlan, Partition, ShardedContext, element_ranges, global_pattern, merge_host
@@ -46,6 +47,7 @@ __all__ = ['LagrangeElementType', 'ELEMENT_SHAPE', 'get_quadrature_volume', 'get
            'get_quadrature_surface', 'get_local_basis_surface', 'surface_tables', 'assemble_mesh_el', 'get_vector_volume',
            'get_vector_traction', 'load_traction', 'solve_elasticity2d',
            'construct_constitutive_problem_vm', 'construct_constitutive_problem_mc', 'construct_constitutive_problem_vmps',
+           'construct_constitutive_problem_vmi', 'hardening_curve', 'voce_curve',
            'solve_cutout_cyclic',
            'construct_constitutive_problem_field', 'in_situ_strain', 'linear_in_situ',
            'tree_sum', 'recover_stress_np', 'estimate_np', 'indicator_stats', 'mark_bulk',

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -63,6 +64,38 @@ enum CtxBuf {
 // Device buffers of the mesh-free return map, in its engine's store (sized by each call)
 enum RmBuf { kRmE, kRmEp, kRmShear, kRmBulk, kRmM3, kRmM4, kRmS, kRmDs, kRmIndP, kRmCounts, kRmField };
 
+// The hardening curve of the fifth model as its kernels take it (fep.h, fep_return_map_vmi_*): R[0] = 0,
+// R[j + 1] = R[j] + slope[j] * (kappa[j + 1] - kappa[j]) in this order without contraction, the segments behind the last padded
+// with kappa = +Inf, R = 0, slope = 0.  FEP_EINVAL, with *out untouched, unless n_seg is 1 .. FEP_MAX_HARDENING_SEGMENTS,
+// kappa[0] == 0, kappa strictly increasing and finite, slope finite.
+static int make_hard(int n_seg, const double* kappa_h, const double* slope_h, Hard* out) {
+#pragma clang fp contract(off)
+    if (n_seg < 1 || n_seg > kHardSeg || !kappa_h || !slope_h) return FEP_EINVAL;
+    if (!(kappa_h[0] == 0.0)) return FEP_EINVAL;
+    for (int j = 0; j < n_seg; ++j) {
+        if (!std::isfinite(kappa_h[j]) || !std::isfinite(slope_h[j])) return FEP_EINVAL;
+        if (j > 0 && !(kappa_h[j] > kappa_h[j - 1])) return FEP_EINVAL;
+    }
+    Hard h;
+    for (int j = 0; j < kHardSeg; ++j) { h.kappa[j] = HUGE_VAL; h.R[j] = 0.0; h.slope[j] = 0.0; }
+    for (int j = 0; j < n_seg; ++j) {
+        h.kappa[j] = kappa_h[j];
+        h.slope[j] = slope_h[j];
+        if (j > 0) {
+            const double step = slope_h[j - 1] * (kappa_h[j] - kappa_h[j - 1]);
+            h.R[j] = h.R[j - 1] + step;
+        }
+    }
+    *out = h;
+    return FEP_OK;
+}
+static Hard flat_hard() {
+    const double zero = 0.0;
+    Hard h;
+    (void)make_hard(1, &zero, &zero, &h);
+    return h;
+}
+
 struct fep_ctx {
     int device = 0;
     int elem_type = 0;
@@ -72,6 +105,7 @@ struct fep_ctx {
     bool have_materials = false;
     int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
     uint2* vm_blk = nullptr;                            // FEP_MODEL_VM / _MC: per-workgroup plastic counts of the point kernel
+    Hard hard = flat_hard();                            // FEP_MODEL_VMI: fep_ctx_set_hardening (one segment of slope 0 until then)
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
     int csr_gathers = 4;                                // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
@@ -308,6 +342,11 @@ template <int NP, int NQ>
 static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>,
                                                                                     point_vmps_kernel<NP, NQ>};
 static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == 2 && FEP_MODEL_VMPS == kModels - 1, "table order");
+// The fifth model, FEP_MODEL_VMI, is in none of the tables: its kernels have a signature of their own (the hardening curve as
+// one more argument), so the launches below name them, and the tables stay dense with id 4 outside them, refused as before.
+static_assert(FEP_MODEL_VMI > kModels, "id 4 stays unassigned");
+static bool known_model(int model) { return (model >= 0 && model < kModels) || model == FEP_MODEL_VMI; }
+static const char* model_tag(int model) { return model == FEP_MODEL_VMI ? "vmi_" : kModelTag[model]; }
 // The same families with an initial-strain field (fep_*_field_*): every model has a row in each, Drucker-Prager too, so these
 // are indexed by the model itself.
 // (The mesh-free pair fep_return_map_field_* keeps its three models: FEP_MODEL_VMPS is refused there, include/fep.h.)
@@ -329,9 +368,10 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
                                const double* e0_h, double* ep_prev_d,
                                const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
                                int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d,
-                               const double* field_d = nullptr, double scale = 0.0) {
+                               const double* field_d = nullptr, double scale = 0.0, const Hard* hard = nullptr) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_d || !shear_d || !bulk_d || !eta_d || !c_d)) return FEP_EINVAL;
+    if (model == FEP_MODEL_VMI && (!hard || field_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(device_id));
     hipStream_t st = (hipStream_t)stream;
     if (n_int == 0) { if (counts_d) HIP_TRY(hipMemsetAsync(counts_d, 0, 2 * sizeof(int64_t), st)); return FEP_OK; }
@@ -343,7 +383,11 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     if (counts_d)
         FEP_TRY(stream_scratch(kScratchRmCounts, device_id, st, n_blocks * sizeof(uint2),
                                ((size_t)n_blocks + n_blocks / 4 + 64) * sizeof(uint2), (void**)&blk));
-    if (field_d)
+    if (model == FEP_MODEL_VMI)
+        hipLaunchKernelGGL(return_map_vmi_kernel, dim3(n_blocks), dim3(kBlock), 0, st,
+                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
+                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk, *hard);
+    else if (field_d)
         hipLaunchKernelGGL(kReturnMapFieldKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
                            n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
                            shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk, field_d, scale);
@@ -395,6 +439,18 @@ extern "C" int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_in
                                shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
 }
 
+extern "C" int fep_return_map_vmi_dev(int device_id, void* stream, int64_t n_int,
+                                      const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                                      const double* e0_h, double* ep_prev_d,
+                                      const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                                      int n_seg, const double* kappa_h, const double* slope_h,
+                                      int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
+    Hard hard;
+    FEP_TRY(make_hard(n_seg, kappa_h, slope_h, &hard));
+    return return_map_dev_impl(FEP_MODEL_VMI, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d, nullptr, 0.0, &hard);
+}
+
 extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, int64_t n_int,
                                         const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                         const double* e0_h, const double* e0_field_d, double e0_scale, double* ep_prev_d,
@@ -425,7 +481,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
                                 const double* e0_h, double* ep_prev_h,
                                 const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
                                 int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h,
-                                const double* field_h = nullptr, double scale = 0.0) {
+                                const double* field_h = nullptr, double scale = 0.0, const Hard* hard = nullptr) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_h || !shear_h || !bulk_h || !eta_h || !c_h)) return FEP_EINVAL;
     if (counts_h) { counts_h[0] = 0; counts_h[1] = 0; }
@@ -454,7 +510,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     call.out(kRmCounts, counts_h, 2);
     const int rf = call.run([&] {
         return return_map_dev_impl(model, device_id, call.stream(), n_int, e, e_pt_stride, e_comp_stride, e0_h, ep, sh, bu, m3, m4,
-                                   accept, s, ds, ip, cnt, fld, scale);
+                                   accept, s, ds, ip, cnt, fld, scale, hard);
     });
     if (timing) std::fprintf(stderr, "[fep] return_map_host: done after %.3f ms\n", ms());
     return rf;
@@ -494,6 +550,18 @@ extern "C" int fep_return_map_vmps_host(int device_id, int64_t n_int,
                                         int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_VMPS, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
                                    bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
+}
+
+extern "C" int fep_return_map_vmi_host(int device_id, int64_t n_int,
+                                       const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                                       const double* e0_h, double* ep_prev_h,
+                                       const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                                       int n_seg, const double* kappa_h, const double* slope_h,
+                                       int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
+    Hard hard;
+    FEP_TRY(make_hard(n_seg, kappa_h, slope_h, &hard));
+    FEP_GUARD(return_map_host_impl(FEP_MODEL_VMI, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h, nullptr, 0.0, &hard))
 }
 
 extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int,
@@ -1022,8 +1090,8 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     // `pt`: the model's point kernel; `el`: the element routes' kernel, for Drucker-Prager the whole step from U, for the other
     // models the assembly from ds / s behind their point kernel (step_model)
     char tmp[256], pt[64], el[192];
-    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", kModelTag[c->model]);
-    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", kModelTag[c->model], c->n_p, c->n_q);
+    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", model_tag(c->model));
+    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", model_tag(c->model), c->n_p, c->n_q);
     std::snprintf(el, sizeof el, "%s%selement_kernel<%d, %d, %s, %s, %s, %d, %d>", dp ? "" : pt, dp ? "" : " + ", c->n_p, c->n_q, b(dp),
                   b(c->elem_geo), b(patch), patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
     if (c->route == Route::P1Node && c->p1_lds && dp && which == 1 && c->p1_fused && c->fused_mode >= 1) {
@@ -1101,7 +1169,7 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
 // The models besides Drucker-Prager run as point kernel + the route's assembly: the ds / s scratch and the point kernel's
 // per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
 extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
-    if (!c || model < 0 || model >= kModels) return FEP_EINVAL;
+    if (!c || !known_model(model)) return FEP_EINVAL;
     if (model != FEP_MODEL_DP) {
 #ifdef FEP_ABLATION
         if (c->route == Route::GenNode) return FEP_ESTATE;
@@ -1117,6 +1185,16 @@ extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
         if (!c->vm_blk) FEP_TRY(dmalloc(c, &c->vm_blk, (int64_t)grid_for(c->n_int, kBlock)));
     }
     c->model = model;
+    return FEP_OK;
+}
+
+// (the curve of a context outlives a change of its model and back: only this call writes it)
+extern "C" int fep_ctx_set_hardening(fep_ctx* c, int n_seg, const double* kappa_h, const double* slope_h) {
+    if (!c) return FEP_EINVAL;
+    if (c->model != FEP_MODEL_VMI) return FEP_ESTATE;
+    Hard hard;
+    FEP_TRY(make_hard(n_seg, kappa_h, slope_h, &hard));
+    c->hard = hard;
     return FEP_OK;
 }
 
@@ -1427,6 +1505,28 @@ static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, doub
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
+        if (c->model == FEP_MODEL_VMI) {                 // the kernels with the hardening curve (not in the tables)
+            if constexpr (ET::type == FEP_P1) {
+                if (field_d)
+                    hipLaunchKernelGGL(p1_point_vmi_field_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
+                                       c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
+                                       e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale, c->hard);
+                else
+                    hipLaunchKernelGGL(p1_point_vmi_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
+                                       c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d,
+                                       s_d, ds_d, ind_p_d, blk, c->hard);
+            } else {
+                if (field_d)
+                    hipLaunchKernelGGL((point_vmi_field_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st,
+                                       c->n_e, c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk,
+                                       c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale, c->hard);
+                else
+                    hipLaunchKernelGGL((point_vmi_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
+                                       c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c,
+                                       c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, c->hard);
+            }
+            return FEP_OK;
+        }
         if (field_d) {
             if constexpr (ET::type == FEP_P1)
                 hipLaunchKernelGGL(kP1PointFieldKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,

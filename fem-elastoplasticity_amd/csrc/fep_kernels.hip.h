@@ -167,6 +167,96 @@ __device__ __forceinline__ int vm_return_map(const double e[3], const double z[4
 }
 
 // ---------------------------------------------------------------------------------------
+// Per-point von Mises return map with isotropic hardening on a piecewise-linear curve next to the linear kinematic one (the
+// fifth material model, FEP_MODEL_VMI; no counterpart in the reference; include/fep.h, fep_return_map_vmi_*, has the law).
+// Arguments as vm_return_map, plus the curve.  The state rows are (p11, p22, gamma12, kappa): p33 = -(p11 + p22) is implied
+// and row 3 holds the sum of the plastic multipliers.  Returns 0 elastic, 1 plastic.
+//
+// The curve is the same for every point of a launch and travels as a kernel argument: breakpoints kappa[j], the yield-radius
+// increase R[j] reached there and the slope of segment j, padded by the host behind the last segment with kappa = +Inf, R = 0,
+// slope = 0.  Every index below is a compile-time constant, so the 24 numbers are scalar loads of the kernel-argument segment
+// and the walk over the segments is eight rounds of selects, with no branch that depends on the lane: a padded segment is never
+// the accepted one of a finite point (segment n_seg - 1 passes its test against kappa = +Inf first).
+// ---------------------------------------------------------------------------------------
+constexpr int kHardSeg = FEP_MAX_HARDENING_SEGMENTS;
+struct Hard { double kappa[kHardSeg], R[kHardSeg], slope[kHardSeg]; };
+
+__device__ __forceinline__ int vmi_return_map(const double e[3], const double z[4], double p[4],
+                                              double G, double K, double a, double Y, const Hard& hc, bool accept,
+                                              double s[4], double d[6]) {
+    // No contraction: the kernels of the model (a uniform z in scalar registers, a z per lane with a field) then agree bit for
+    // bit, and a host restatement can follow the map operation by operation
+#pragma clang fp contract(off)
+    const double I3 = 1.0 / 3.0;
+    const double DD = 1.0 - 1.0 / 3.0;
+    const double k0 = p[3];
+    const double p3 = -(p[0] + p[1]);
+    const double Et0 = (e[0] + z[0]) - p[0];
+    const double Et1 = (e[1] + z[1]) - p[1];
+    const double Et2 = (e[2] + z[2]) - p[2];
+    const double Et3 = (0.0 + z[3]) - p3;
+    const double tr = Et0 + Et1 + Et3;
+    const double dv0 = DD * Et0 - I3 * Et1 - I3 * Et3;
+    const double dv1 = -I3 * Et0 + DD * Et1 - I3 * Et3;
+    const double dv2 = 0.5 * Et2;
+    const double dv3 = -I3 * Et0 - I3 * Et1 + DD * Et3;
+    const double G2 = 2.0 * G;
+    // -0.0 for a finite kappa (x + -0.0 == x: no finite result changes) and NaN for a NaN or an infinite one, which an infinite
+    // yield radius would otherwise hide behind an elastic point with a finite stress: kappa counts as a fifth component of the
+    // trial state (fep.h, non-finite rule 1)
+    const double poison = -fabs(0.0 * k0);
+    const double Ktr = K * tr + poison;
+    double s0 = G2 * dv0 + Ktr, s1 = G2 * dv1 + Ktr, s2 = G2 * dv2, s3 = G2 * dv3 + Ktr;   // trial stress
+    const double x0 = G2 * dv0 - a * p[0], x1 = G2 * dv1 - a * p[1], x2 = G2 * dv2 - a * (0.5 * p[2]), x3 = G2 * dv3 - a * p3;
+    const double nrm = sqrt(x0 * x0 + x1 * x1 + 2.0 * (x2 * x2) + x3 * x3) + poison;
+    // yield radius of the start segment j0 = the largest j with kappa[j] <= k0 (0 when none is): the breakpoints increase, so
+    // the last comparison that holds is j0's
+    double crit = nrm - (Y + (hc.R[0] + hc.slope[0] * (k0 - hc.kappa[0])));
+#pragma unroll
+    for (int j = 1; j < kHardSeg; ++j)
+        crit = (hc.kappa[j] <= k0) ? nrm - (Y + (hc.R[j] + hc.slope[j] * (k0 - hc.kappa[j]))) : crit;
+    double d00 = 2.0 * DD * G + K, d01 = 2.0 * (-I3) * G + K, d02 = 0.0;
+    double d11 = d00, d12 = 0.0, d22 = 2.0 * 0.5 * G;
+    int branch = 0;
+    if (crit > 0.0) {
+        branch = 1;
+        // the first segment from j0 on whose own multiplier stays inside it (the last one always does)
+        double lam = 0.0, H = 1.0;
+        bool open = true;
+#pragma unroll
+        for (int j = 0; j < kHardSeg; ++j) {
+            const double Hj = (G2 + a) + hc.slope[j];
+            const double lj = (nrm - (Y + (hc.R[j] + hc.slope[j] * (k0 - hc.kappa[j])))) / Hj;
+            bool take = open;
+            if (j + 1 < kHardSeg) take = take && !(hc.kappa[j + 1] <= k0) && (k0 + lj <= hc.kappa[j + 1]);
+            lam = take ? lj : lam;
+            H = take ? Hj : H;
+            open = open && !take;
+        }
+        const double N0 = x0 / nrm, N1 = x1 / nrm, N2 = x2 / nrm, N3 = x3 / nrm;
+        const double g = G2 * lam;
+        s0 -= g * N0; s1 -= g * N1; s2 -= g * N2; s3 -= g * N3;
+        const double cn = G2 * G2 / H;                    // along N (x) N
+        const double cf = G2 * G2 * lam / nrm;            // along Dev - N (x) N
+        d00 = d00 - cn * (N0 * N0) - cf * (DD - N0 * N0);
+        d01 = d01 - cn * (N0 * N1) - cf * (-I3 - N0 * N1);
+        d02 = d02 - cn * (N0 * N2) - cf * (0.0 - N0 * N2);
+        d11 = d11 - cn * (N1 * N1) - cf * (DD - N1 * N1);
+        d12 = d12 - cn * (N1 * N2) - cf * (0.0 - N1 * N2);
+        d22 = d22 - cn * (N2 * N2) - cf * (0.5 - N2 * N2);
+        if (accept) {
+            p[0] += lam * N0;
+            p[1] += lam * N1;
+            p[2] += 2.0 * lam * N2;
+            p[3] = k0 + lam;
+        }
+    }
+    s[0] = s0; s[1] = s1; s[2] = s2; s[3] = s3;
+    d[0] = d00; d[1] = d01; d[2] = d02; d[3] = d11; d[4] = d12; d[5] = d22;
+    return branch;
+}
+
+// ---------------------------------------------------------------------------------------
 // Per-point von Mises return map in PLANE STRESS with linear kinematic hardening (the fourth material model,
 // FEP_MODEL_VMPS; no counterpart in the reference; include/fep.h, fep_return_map_vmps_*, has the law).  Arguments as
 // vm_return_map: a >= 0, Y = sqrt(2/3)*sigma_y > 0.  s[3] = 0; z[3] and p[3] enter only through the propagation of a
@@ -386,9 +476,11 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
 template <int MODEL>
 __device__ __forceinline__ int model_return_map(const double e[3], const double z[4], double p[4],
                                                 double G, double K, double m3, double m4, bool accept,
-                                                double s[4], double d[6]) {
-    static_assert(MODEL == FEP_MODEL_DP || MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC || MODEL == FEP_MODEL_VMPS, "model");
-    if constexpr (MODEL == FEP_MODEL_VMPS) return vmps_return_map(e, z, p, G, K, m3, m4, accept, s, d);
+                                                double s[4], double d[6], const Hard* hc = nullptr) {
+    static_assert(MODEL == FEP_MODEL_DP || MODEL == FEP_MODEL_VM || MODEL == FEP_MODEL_MC || MODEL == FEP_MODEL_VMPS ||
+                  MODEL == FEP_MODEL_VMI, "model");
+    if constexpr (MODEL == FEP_MODEL_VMI) return vmi_return_map(e, z, p, G, K, m3, m4, *hc, accept, s, d);
+    else if constexpr (MODEL == FEP_MODEL_VMPS) return vmps_return_map(e, z, p, G, K, m3, m4, accept, s, d);
     else if constexpr (MODEL == FEP_MODEL_MC) return mc_return_map(e, z, p, G, K, m3, m4, accept, s, d);
     else if constexpr (MODEL == FEP_MODEL_VM) return vm_return_map(e, z, p, G, K, m3, m4, accept, s, d);
     else return dp_return_map(e, z, p, G, K, m3, m4, accept, s, d);
@@ -530,7 +622,8 @@ return_map_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ec
                 double* __restrict__ ep, const double* __restrict__ shear, const double* __restrict__ bulk,
                 const double* __restrict__ m3, const double* __restrict__ m4, int accept,
                 double* __restrict__ S, double* __restrict__ DS, uint8_t* __restrict__ indp,
-                uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
+                uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0,
+              const Hard* hc = nullptr) {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (k < n) {
@@ -541,9 +634,9 @@ return_map_body(int64_t n, const double* __restrict__ e, int64_t eps, int64_t ec
         if constexpr (FIELD) {
             double z[4];
             field_e0(e0, field, scale, n, k, z);
-            branch = model_return_map<MODEL>(ev, z, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, z, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d, hc);
         } else {
-            branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, e0.v, p, shear[k], bulk[k], m3[k], m4[k], accept != 0, s, d, hc);
         }
         store_point(k, n, s, d, branch, S, DS, indp);
         if (accept && ep && branch) { ep[k] = p[0]; ep[n + k] = p[1]; ep[2 * n + k] = p[2]; ep[3 * n + k] = p[3]; }
@@ -567,6 +660,10 @@ __global__ void __launch_bounds__(kBlock) return_map_mc_kernel(FEP_RETURN_MAP_AR
 }
 __global__ void __launch_bounds__(kBlock) return_map_vmps_kernel(FEP_RETURN_MAP_ARGS) {
     return_map_body<FEP_MODEL_VMPS>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts);
+}
+// (the fifth model's kernels take its hardening curve as one more argument by value; no other kernel has or reads it)
+__global__ void __launch_bounds__(kBlock) return_map_vmi_kernel(FEP_RETURN_MAP_ARGS, Hard hc) {
+    return_map_body<FEP_MODEL_VMI>(n, e, eps, ecs, e0, ep, shear, bulk, m3, m4, accept, S, DS, indp, blk_counts, nullptr, 0.0, &hc);
 }
 template <int MODEL>
 __global__ void __launch_bounds__(kBlock)
@@ -1594,7 +1691,8 @@ p1_point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __res
               const double* __restrict__ shear, const double* __restrict__ bulk,
               const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
               double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-              uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
+              uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0,
+              const Hard* hc = nullptr) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int branch = 0;
     if (e < n_e) {
@@ -1619,9 +1717,9 @@ p1_point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __res
         if constexpr (FIELD) {
             double z[4];
             field_e0(e0, field, scale, n_e, e, z);
-            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d, hc);
         } else {
-            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d, hc);
         }
         store_point(e, n_e, s, d, branch, S, DS, indp);
         if (Eout) { Eout[e] = ev[0]; Eout[n_e + e] = ev[1]; Eout[2 * n_e + e] = ev[2]; }
@@ -1647,11 +1745,22 @@ __global__ void __launch_bounds__(kBlock) p1_point_mc_kernel(FEP_P1_POINT_ARGS) 
 __global__ void __launch_bounds__(kBlock) p1_point_vmps_kernel(FEP_P1_POINT_ARGS) {
     p1_point_body<FEP_MODEL_VMPS>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts);
 }
+__global__ void __launch_bounds__(kBlock) p1_point_vmi_kernel(FEP_P1_POINT_ARGS, Hard hc) {
+    p1_point_body<FEP_MODEL_VMI>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts,
+                                 nullptr, 0.0, &hc);
+}
 template <int MODEL>
 __global__ void __launch_bounds__(kBlock)
 p1_point_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, double scale) {
     p1_point_body<MODEL, true>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts,
                                field, scale);
+}
+// The field wrapper of the model with a hardening curve (FEP_MODEL_VMI), the curve behind the field.  It has a name of its own:
+// an overload of the template above would make the address in the dispatch tables of the other models ambiguous
+__global__ void __launch_bounds__(kBlock)
+p1_point_vmi_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, double scale, Hard hc) {
+    p1_point_body<FEP_MODEL_VMI, true>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts,
+                               field, scale, &hc);
 }
 #undef FEP_P1_POINT_ARGS
 
@@ -2368,7 +2477,8 @@ point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restri
            const double* __restrict__ shear, const double* __restrict__ bulk,
            const double* __restrict__ m3, const double* __restrict__ m4, const MatU& mu, int accept,
            double* __restrict__ Eout, double* __restrict__ S, double* __restrict__ DS,
-           uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0) {
+           uint8_t* __restrict__ indp, uint2* blk_counts, const double* __restrict__ field = nullptr, double scale = 0.0,
+              const Hard* hc = nullptr) {
     __shared__ double t1[NP * NQ], t2[NP * NQ], tw[NQ];
     for (int i = threadIdx.x; i < NP * NQ; i += kBlock) { t1[i] = dh1[i]; t2[i] = dh2[i]; }
     for (int i = threadIdx.x; i < NQ; i += kBlock) tw[i] = wf[i];
@@ -2417,9 +2527,9 @@ point_body(int64_t n_e, const int32_t* __restrict__ elem, const double* __restri
         if constexpr (FIELD) {
             double z[4];
             field_e0(e0, field, scale, n_int, k, z);
-            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, z, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d, hc);
         } else {
-            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d);
+            branch = model_return_map<MODEL>(ev, e0.v, p, m_sh, m_bu, m_3, m_4, accept != 0, s, d, hc);
         }
         store_point(k, n_int, s, d, branch, S, DS, indp);
         if (Eout) { Eout[k] = ev[0]; Eout[n_int + k] = ev[1]; Eout[2 * n_int + k] = ev[2]; }
@@ -2449,6 +2559,11 @@ __global__ void __launch_bounds__(kBlock) point_vmps_kernel(FEP_POINT_ARGS) {
     point_body<FEP_MODEL_VMPS, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
                                        indp, blk_counts);
 }
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock) point_vmi_kernel(FEP_POINT_ARGS, Hard hc) {
+    point_body<FEP_MODEL_VMI, NP, NQ>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS,
+                                      indp, blk_counts, nullptr, 0.0, &hc);
+}
 // The same with an initial-strain field, for every model: the only Drucker-Prager instantiation of point_body (a step with a field
 // runs staged on every route).
 template <int MODEL, int NP, int NQ>
@@ -2456,6 +2571,13 @@ __global__ void __launch_bounds__(kBlock)
 point_field_kernel(FEP_POINT_ARGS, const double* __restrict__ field, double scale) {
     point_body<MODEL, NP, NQ, true>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp,
                                     blk_counts, field, scale);
+}
+// (FEP_MODEL_VMI: its own wrapper with the hardening curve, as p1_point_vmi_field_kernel)
+template <int NP, int NQ>
+__global__ void __launch_bounds__(kBlock)
+point_vmi_field_kernel(FEP_POINT_ARGS, const double* __restrict__ field, double scale, Hard hc) {
+    point_body<FEP_MODEL_VMI, NP, NQ, true>(n_e, elem, xy, dh1, dh2, wf, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp,
+                                    blk_counts, field, scale, &hc);
 }
 #undef FEP_POINT_ARGS
 

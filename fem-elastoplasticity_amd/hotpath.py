@@ -17,6 +17,7 @@ import numpy as np
 import scipy.sparse as ssp
 
 from . import _lib
+from .hardening import check_curve
 from .tables import (ELEMENT_SHAPE, LagrangeElementType, _coerce, element_tables, get_local_basis_volume,
                      get_quadrature_volume)
 
@@ -55,7 +56,7 @@ def _strain_view(e, n_int):
 # a2  construct_constitutive_problem
 # ---------------------------------------------------------------------------------------
 def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, device=None, entry='fep_return_map_host',
-                field=None):
+                field=None, curve=None):
     l = _lib.lib()
     dev = default_device() if device is None else device
     shear = _f64(shear).ravel()
@@ -87,6 +88,12 @@ def _return_map(e, e0, ep_prev, shear, bulk, eta, c, apply_plastic_strain, tsx, 
                                                float(scale), _lib.ptr(ep_dev), _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta),
                                                _lib.ptr(c), int(accept), _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind),
                                                _lib.ptr(counts)), 'fep_return_map_field_host')
+    elif curve is not None:                            # (kappa, slope): the model with a hardening curve
+        kap, slo = curve
+        _lib.check(getattr(l, entry)(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
+                                     _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), kap.size, _lib.ptr(kap),
+                                     _lib.ptr(slo), int(accept), _lib.ptr(s), _lib.ptr(ds), _lib.ptr(ind), _lib.ptr(counts)),
+                   entry)
     else:
         _lib.check(getattr(l, entry)(dev, n_int, _lib.ptr(ev), ps, cs, _lib.ptr(e0v), _lib.ptr(ep_dev),
                                      _lib.ptr(shear), _lib.ptr(bulk), _lib.ptr(eta), _lib.ptr(c), int(accept),
@@ -222,12 +229,27 @@ def construct_constitutive_problem_vmps(e, ep_prev, shear, bulk, a, Y, apply_pla
     return {'s': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'], 'ep': r['ep'], 'n_plast': r['n_smooth']}
 
 
-MODELS = {'dp': 0, 'vm': 1, 'mc': 2, 'vmps': 3}            # FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC, FEP_MODEL_VMPS
+def construct_constitutive_problem_vmi(e, ep_prev, shear, bulk, a, Y, curve, apply_plastic_strain=False, e0=None, device=None):
+    """The fifth material model, no counterpart in the reference: von Mises plasticity with isotropic hardening on a
+    piecewise-linear curve next to the linear kinematic one (include/fep.h, fep_return_map_vmi_host).  `curve` = (kappa, slope),
+    1 .. 8 segments (hardening.hardening_curve / voce_curve build one from a uniaxial table), the same for every point; `Y` is
+    the INITIAL yield radius and the current one is Y + R(kappa).  The rows of `ep_prev` are (p11, p22, gamma12, kappa): p33 =
+    -(p11 + p22) is implied and row 3 holds the accumulated plastic multiplier (equivalent plastic strain sqrt(2/3) kappa).
+    The other arguments and the returned {'s', 'ds', 'ind_p', 'ep', 'n_plast'} as construct_constitutive_problem_vm.  A curve
+    that breaks the law's preconditions for these materials (hardening.check_curve) is refused with ValueError."""
+    curve = check_curve(*curve, shear=shear, a=a, Y=Y)
+    r = _return_map(e, e0, ep_prev, shear, bulk, a, Y, apply_plastic_strain, tsx=False, device=device,
+                    entry='fep_return_map_vmi_host', curve=curve)
+    return {'s': r['s'], 'ds': r['ds'], 'ind_p': r['ind_p'], 'ep': r['ep'], 'n_plast': r['n_smooth']}
+
+
+# FEP_MODEL_DP, FEP_MODEL_VM, FEP_MODEL_MC, FEP_MODEL_VMPS, FEP_MODEL_VMI (4 is not a model)
+MODELS = {'dp': 0, 'vm': 1, 'mc': 2, 'vmps': 3, 'vmi': 5}
 
 
 def construct_constitutive_problem_field(model, e, e0_field, ep_prev, shear, bulk, m3, m4, apply_plastic_strain=False,
                                          e0=None, e0_scale=1.0, device=None):
-    """The return map of `model` ('dp', 'vm' or 'mc'; 'vmps' takes a field in `MeshContext.step` only) with an initial strain per point, no counterpart in the reference
+    """The return map of `model` ('dp', 'vm' or 'mc'; 'vmps' and 'vmi' take a field in `MeshContext.step` only) with an initial strain per point, no counterpart in the reference
     (include/fep.h, fep_return_map_field_host): point k runs on `e0 + e0_scale * e0_field[:, k]`, `e0_field` (4, n_int) with
     rows 11, 22, 12 (engineering shear), 33, `e0` an optional uniform (4,1) part.  `m3`, `m4` are the model's third and
     fourth parameter arrays (eta, c / a, Y / sin_phi, c); the other arguments as construct_constitutive_problem.  Returns
@@ -319,6 +341,8 @@ class MeshContext:
         self._geom = None
         self._hatp_own = None
         self.model = 'dp'
+        self._hardening = (np.zeros(1), np.zeros(1))       # fep_ctx_set_hardening's default: one segment of slope 0
+        self._mats = None                                   # (shear, bulk, third, fourth) of the last set_materials
 
     # -- lifetime
     def close(self):
@@ -372,18 +396,42 @@ class MeshContext:
 
     def set_materials(self, shear, bulk, eta, c):
         a = [_f64(np.broadcast_to(np.asarray(v, dtype=np.float64).ravel(), (self.n_int,))) for v in (shear, bulk, eta, c)]
+        if self.model == 'vmi':
+            check_curve(*self._hardening, shear=a[0], a=a[2], Y=a[3])
         _lib.check(_lib.lib().fep_ctx_set_materials_host(self._h, *[_lib.ptr(v) for v in a]), 'fep_ctx_set_materials_host')
+        self._mats = a
 
     def set_model(self, model):
         """'dp' (Drucker-Prager, the default), 'vm' (von Mises with linear kinematic hardening: `set_materials` then takes
         (shear, bulk, a, Y), the results carry the plastic count in 'n_smooth' and 'n_apex' is 0) or 'mc' (Mohr-Coulomb:
         `set_materials` takes (shear, bulk, sin_phi, c), 'n_smooth' counts face and edges, 'n_apex' the apex) or 'vmps' (von
         Mises in plane stress: everything as 'vm', the stress has s33 = 0, and the context's K at U = 0 is the elastic
-        plane-stress stiffness).  Before or after `set_materials`."""
+        plane-stress stiffness) or 'vmi' (von Mises with isotropic hardening on the curve of `set_hardening` next to the
+        kinematic one: materials as 'vm' with Y the initial yield radius, row 3 of the plastic strain is kappa).  Before or
+        after `set_materials`."""
         if model not in MODELS:
             raise ValueError(f"model must be one of {sorted(MODELS)}")
         _lib.check(_lib.lib().fep_ctx_set_model(self._h, MODELS[model]), 'fep_ctx_set_model')
         self.model = model
+
+    def set_hardening(self, kappa, slope):
+        """The hardening curve of a 'vmi' context (fep_ctx_set_hardening): breakpoints `kappa` (kappa[0] = 0, increasing) and
+        one slope dR/dkappa per segment, 1 .. 8 segments, the last running to infinity; before or after `set_materials`.
+        Without a call the context holds one segment of slope 0.  ValueError for a curve that is not as stated or, once the
+        materials are known, breaks the law's preconditions (hardening.check_curve); FepError (FEP_ESTATE) on a context of
+        another model.  A refused call changes nothing."""
+        if self.model == 'vmi' and self._mats is not None:
+            curve = check_curve(kappa, slope, shear=self._mats[0], a=self._mats[2], Y=self._mats[3])
+        else:
+            curve = check_curve(kappa, slope)
+        _lib.check(_lib.lib().fep_ctx_set_hardening(self._h, curve[0].size, _lib.ptr(curve[0]), _lib.ptr(curve[1])),
+                   'fep_ctx_set_hardening')
+        self._hardening = curve
+
+    @property
+    def hardening(self):
+        """(kappa, slope) of a 'vmi' context's curve (copies); None on a context of another model."""
+        return (self._hardening[0].copy(), self._hardening[1].copy()) if self.model == 'vmi' else None
 
     def device_ptr(self, which):
         p = C.c_void_p()

@@ -8,6 +8,7 @@ from contextlib import closing
 
 import numpy as np
 
+from .hardening import check_curve, hardening_curve
 from .hotpath import load_traction
 from .mesh import assemble_mesh_el
 from .newton import _context_maker, _load_history_loop, make_ops
@@ -23,7 +24,8 @@ def cycle_factors(steps_per_quarter):
 
 def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), steps_per_quarter=4, young=206900, poisson=0.29,
                         sigma_y=450, hardening=10000, linear_solver='amg', f_ext=None, zetas=None, context_factory=None,
-                        device=None, pcg_rtol=1e-11, log=None, plane_stress=False, adapt_at=None, mark='zz', theta=0.5):
+                        device=None, pcg_rtol=1e-11, log=None, plane_stress=False, adapt_at=None, mark='zz', theta=0.5,
+                        isotropic=None):
     """A load cycle on the cut-out square (mesh.assemble_mesh_el: P1, Q1, Q2).  The DOFs outside the mesh's 'Q' are held
     at zero; the external load is `f_ext` (2, n_n) when given, else the traction `peak_traction` on the top side
     (load_traction), times the load factors `zetas` (default: cycle_factors(steps_per_quarter)).  Materials: shear and
@@ -32,6 +34,12 @@ def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), step
     iterates, converged below 1e-10, no sub-stepping), then the accepting call that updates the plastic strain.
     `plane_stress=True` runs the plate in plane stress (the 'vmps' model: s33 = 0, the thickness strain free) instead of
     the default plane strain ('vm': a thick prism).
+    `isotropic` adds isotropic hardening (the 'vmi' model, plane strain only: ValueError with `plane_stress`), `hardening`
+    staying the kinematic modulus a: a number is a linear modulus d sigma_y / d eps_p_bar, a pair of arrays (eps_p_bar, sigma_y)
+    a uniaxial table (hardening.hardening_curve; its first stress is then the initial yield stress and `sigma_y` is not
+    used).  The yield surface grows with the accumulated plastic flow, so reverse yielding comes later than with the same
+    modulus put into the back stress: cyclic hardening instead of the Bauschinger effect.  Row 3 of 'Ep' is then the
+    accumulated multiplier, returned as 'kappa' too, with 'eps_p_bar' = sqrt(2/3) kappa.
 
     Returns a dict: 'zeta' (the accepted factors), 'U' (list of (2, n_n)), 'n_plast', 'newton_its', 'pcg_iters', 'Ep',
     'f_ext' (2, n_n), 'mesh', 'failed_at' (index of the step that did not converge, or None) and 'work' =
@@ -56,23 +64,33 @@ def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), step
     accepted on, 'work' is summed per segment with that segment's 'f_ext' from the transferred U on, and 'mesh', 'f_ext' are
     the last mesh's.  Without `adapt_at` the run is what it was, bit for bit."""
     t = _coerce(element_type)
+    shear, bulk = young / (2 * (1 + poisson)), young / (3 * (1 - 2 * poisson))
+    model, Y, curve = 'vmps' if plane_stress else 'vm', np.sqrt(2 / 3) * sigma_y, None
+    if isotropic is not None:
+        if plane_stress:
+            raise ValueError('isotropic hardening runs in plane strain only (the plane-stress model has no hardening curve)')
+        if np.ndim(isotropic) == 0:                        # R = sqrt(2/3) h eps_p_bar = (2/3) h kappa
+            curve = (np.zeros(1), np.array([2 * float(isotropic) / 3]))
+        else:
+            Y, *curve = hardening_curve(*isotropic)
+        model, curve = 'vmi', check_curve(*curve, shear=shear, a=float(hardening), Y=Y)
     if adapt_at is not None:
         if t is not LagrangeElementType.P1:
             raise ValueError(f'adapt_at refines P1 meshes only (marked refinement has no {t.name} form)')
         if f_ext is not None:
             raise ValueError('adapt_at computes the traction again on every mesh: pass peak_traction, not f_ext')
         zetas = cycle_factors(steps_per_quarter) if zetas is None else np.asarray(zetas, dtype=float).ravel()
-        return _cutout_adaptive(assemble_mesh_el(level, t), zetas, adapt_at, mark, theta, peak_traction,
-                                ('vmps' if plane_stress else 'vm',
-                                 (young / (2 * (1 + poisson)), young / (3 * (1 - 2 * poisson)), float(hardening), np.sqrt(2 / 3) * sigma_y)),
-                                linear_solver, context_factory, device, pcg_rtol, log)
+        return _with_kappa(_cutout_adaptive(assemble_mesh_el(level, t), zetas, adapt_at, mark, theta, peak_traction,
+                                            (model, (shear, bulk, float(hardening), Y), curve),
+                                            linear_solver, context_factory, device, pcg_rtol, log), curve)
     mesh = assemble_mesh_el(level, t)
     elem = mesh['elements'] - 1
     coord, Q = mesh['coordinates'], mesh['Q']
     ctx = _context_maker(context_factory, device)(elem, coord, *element_tables(t))
-    ctx.set_model('vmps' if plane_stress else 'vm')
-    ctx.set_materials(young / (2 * (1 + poisson)), young / (3 * (1 - 2 * poisson)), float(hardening),
-                      np.sqrt(2 / 3) * sigma_y)
+    ctx.set_model(model)
+    ctx.set_materials(shear, bulk, float(hardening), Y)
+    if curve is not None:
+        ctx.set_hardening(*curve)
     if f_ext is None:
         edges = mesh['neumann_nodes'].astype(np.int64)
         hatp_s, dhatp1_s, wf_s = surface_tables(t)
@@ -100,6 +118,14 @@ def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), step
         work += 0.5 * (z + z_old) * float(np.sum(f_ext * (U - U_old)))
         z_old, U_old = z, U
     hist.update(work=work, f_ext=f_ext, mesh=mesh)
+    return _with_kappa(hist, curve)
+
+
+def _with_kappa(hist, curve):
+    """The accumulated multiplier of a run with isotropic hardening (row 3 of the state) under its own names."""
+    if curve is not None and 'Ep' in hist:
+        hist['kappa'] = hist['Ep'][3].copy()
+        hist['eps_p_bar'] = np.sqrt(2 / 3) * hist['kappa']
     return hist
 
 
@@ -159,6 +185,8 @@ def _cutout_adaptive(mesh, zetas, adapt_at, mark, theta, peak_traction, model, l
         ctx = _context_maker(context_factory, device)(elem, coord, *tables)
         ctx.set_model(model[0])
         ctx.set_materials(*model[1])
+        if model[2] is not None:                            # every segment's context runs on the same hardening curve
+            ctx.set_hardening(*model[2])
         if context_factory is None:
             t_int = np.repeat(traction.reshape(2, 1), edges.shape[1] * surf[2].size, axis=1)
             f_ext = load_traction(edges, coord, t_int, *surf, device=ctx.device)

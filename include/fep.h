@@ -30,7 +30,7 @@
  *   - calls on one context are not re-entrant; one context per (host thread, GPU).
  *
  * Stream contract of the *_host entry points that move the caller's arrays through the staging engine
- * (fep_return_map_host / _vm_host / _mc_host / _vmps_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
+ * (fep_return_map_host / _vm_host / _mc_host / _vmps_host / _vmi_host / _field_host, fep_step_host / _host_planar / _field_host, fep_assemble_host,
  * fep_transform_host, fep_load_volume_host, fep_ctx_point_coords_host, fep_recover_stress_host, fep_estimate_host,
  * fep_mesh_enrich_host, fep_mesh_refine_host, fep_mesh_refine_marked_host, fep_mesh_surf_curve_host, fep_mesh_area_stats_host,
  * fep_mark_bulk_host; not fep_load_traction_host, which allocates per call and copies on the default stream):
@@ -89,6 +89,9 @@ extern "C" {
 #define FEP_MODEL_VM 1        /* von Mises with linear kinematic hardening (no reference counterpart) */
 #define FEP_MODEL_MC 2        /* associative, perfectly plastic Mohr-Coulomb (no reference counterpart) */
 #define FEP_MODEL_VMPS 3      /* von Mises with linear kinematic hardening in plane stress (no reference counterpart) */
+#define FEP_MODEL_VMI 5       /* von Mises with isotropic hardening on a piecewise-linear curve next to the kinematic one, plane
+                                * strain (no reference counterpart).  4 is not a model and is refused */
+#define FEP_MAX_HARDENING_SEGMENTS 8   /* segments of a hardening curve (fep_return_map_vmi_*, fep_ctx_set_hardening) */
 
 typedef struct fep_ctx fep_ctx;
 
@@ -284,9 +287,67 @@ int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_int,
                             int accept,
                             double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
 
+/* ---- fifth material model: von Mises with isotropic hardening on a piecewise-linear curve, mesh-free ------
+ * No reference counterpart.  The law of fep_return_map_vm_* (plane strain, radial return, symmetric consistent tangent, the
+ * kinematic back stress a*p) with a yield radius Y + R(kappa) that follows the accumulated plastic multiplier kappa along a
+ * curve the caller enters, e.g. from a tensile test.  Layout, strides, e0_h, outputs, the parameters a >= 0 and
+ * Y = sqrt(2/3)*sigma_y0 > 0 (the INITIAL radius) and the scratch rule of counts_d exactly as fep_return_map_vm_*.
+ *
+ * State.  ep_prev keeps its shape (4,n_int), with the rows (p11, p22, gamma12, kappa).  Plane-strain von Mises flow is
+ * traceless, so p33 = -(p11 + p22) is implied and row 3 is free for kappa, the sum of the multipliers lambda (the equivalent
+ * plastic strain is sqrt(2/3)*kappa).  NULL = zeros; updated in place when `accept`.
+ *
+ * Curve, uniform over the points of a call, in host memory in both forms (as e0_h):
+ *   n_seg      1 .. FEP_MAX_HARDENING_SEGMENTS
+ *   kappa_h    [n_seg] breakpoints: kappa[0] == 0, strictly increasing, finite
+ *   slope_h    [n_seg] dR/dkappa of segment j = [kappa[j], kappa[j+1]), finite; the last segment extends to +infinity
+ * The library forms R[0] = 0, R[j+1] = R[j] + slope[j]*(kappa[j+1] - kappa[j]) in double, in this order, without fused
+ * multiply-add, and the kernel reads kappa, R and slope.  FEP_EINVAL for a curve that is not as stated.  Preconditions on the
+ * caller (as eta > 0 is for Drucker-Prager):  2G + a + slope[j] > 0 for every j and every point (softening is allowed within
+ * that), and Y + R(kappa) > 0 wherever the state gets.
+ *
+ * Per point, with p = ep_prev, k0 = p[3], p3 = -(p[0] + p[1]) and z = e0:
+ *     Et, tr, dv, s_tr, xi, nrm    the formulas of fep_return_map_vm_* with p3 in the place of p[3]
+ *     j0 = the largest j with kappa[j] <= k0 (0 when no comparison holds: a point on a breakpoint starts in the segment to
+ *          its right, a negative k0 on the first segment extended to the left)
+ *     crit = nrm - (Y + (R[j0] + slope[j0]*(k0 - kappa[j0])))
+ *     not crit > 0:  s = s_tr,  ds = 2G*Dev + K*Vol,  the state untouched
+ *     crit > 0:  for j = j0, j0+1, ...:  H_j = (2G + a) + slope[j],
+ *                    lambda_j = (nrm - (Y + (R[j] + slope[j]*(k0 - kappa[j])))) / H_j,
+ *                the first j that is the last segment or has k0 + lambda_j <= kappa[j+1] is taken (the residual
+ *                nrm - H lambda - Y - R(k0 + lambda) decreases monotonically under the precondition, so this j exists and is
+ *                the segment of its root);  lambda = lambda_j, H = H_j,  N = xi/nrm,  s = s_tr - 2G*lambda*N,
+ *                ds = 2G*Dev + K*Vol - (2G)^2/H N(x)N - (2G)^2*lambda/nrm (Dev - N(x)N)           (rows / columns 11, 22, 12)
+ *                accept:  p0 += lambda*N0,  p1 += lambda*N1,  p2 += 2*lambda*N2,  p[3] = k0 + lambda
+ * ind_p = (crit > 0); counts = {number of plastic points, 0}.  ds is symmetric.  No product is fused into a sum, in any
+ * kernel of the model, so tests/vmi_ref.py follows the map operation by operation.  A point whose return lands within
+ * rounding of a breakpoint may take either of the two segments: s is continuous there, ds is not (H jumps with the slope).
+ * With one segment of slope 0 the map is fep_return_map_vm_* on p = (p0, p1, p2, -(p0 + p1)).
+ * Non-finite values: the four rules above hold with k0 counted as a fifth component of the trial state.  K*tr and nrm carry
+ * the term -|0*k0|, which is -0.0 and changes no bit of a finite result, and NaN for a NaN or an infinite k0 (whose infinite
+ * yield radius would otherwise give an elastic point with a finite stress): such a point, like one with a NaN strain, comes
+ * back with ind_p = 0, the elastic tangent, a NaN in s and its state untouched, and is counted nowhere. */
+int fep_return_map_vmi_host(int device_id, int64_t n_int,
+                            const double* e_h, int64_t e_pt_stride, int64_t e_comp_stride,
+                            const double* e0_h, double* ep_prev_h,
+                            const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
+                            int n_seg, const double* kappa_h, const double* slope_h,
+                            int accept,
+                            double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h);
+/* (kappa_h and slope_h are read during the call and travel as a kernel argument: a hipGraph captured from this call has the
+ * curve baked into the launch, as it has e0_h) */
+int fep_return_map_vmi_dev(int device_id, void* stream, int64_t n_int,
+                           const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
+                           const double* e0_h, double* ep_prev_d,
+                           const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
+                           int n_seg, const double* kappa_h, const double* slope_h,
+                           int accept,
+                           double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d);
+
 /* ---- initial strain per point, mesh-free: one pair for every model ----------------------
  * No reference counterpart (its demo holds one s0 for the whole mesh, TSX:1675-1681).  `model` = FEP_MODEL_DP, _VM or _MC (the
- * plane-stress model is not offered mesh-free with a field: FEP_EINVAL; fep_step_field_* of a FEP_MODEL_VMPS context take one);
+ * plane-stress model and the model with a hardening curve are not offered mesh-free with a field: FEP_EINVAL; fep_step_field_*
+ * of a FEP_MODEL_VMPS or FEP_MODEL_VMI context take one);
  * every other argument as in fep_return_map_* of that model (the third and fourth parameter arrays are the model's), plus
  *   e0_field   (4, n_int) C-order like ep_prev, rows 11, 22, 12 (engineering shear), 33; never modified, borrowed for the call
  *   e0_scale   one factor for the whole field
@@ -352,7 +413,7 @@ int fep_ctx_pattern_host(const fep_ctx* ctx, int32_t* indptr_h /* n_dof+1 */, in
  * read the arrays; results are bitwise the same either way. */
 int fep_ctx_set_materials_host(fep_ctx* ctx, const double* shear_h, const double* bulk_h,
                                const double* eta_h, const double* c_h);
-/* The material model of the context's steps: FEP_MODEL_DP (the default), FEP_MODEL_VM, FEP_MODEL_MC or FEP_MODEL_VMPS; may be called
+/* The material model of the context's steps: FEP_MODEL_DP (the default), FEP_MODEL_VM, FEP_MODEL_MC, FEP_MODEL_VMPS or FEP_MODEL_VMI (below); may be called
  * before or after fep_ctx_set_materials_host.  On a von Mises context the third and fourth arrays of
  * fep_ctx_set_materials_host are a and Y (fep_return_map_vm_*), on a Mohr-Coulomb context sin_phi and c
  * (fep_return_map_mc_*; counts = {smooth face + both edges, apex}), on a plane-stress von Mises context a and Y again
@@ -366,6 +427,16 @@ int fep_ctx_set_materials_host(fep_ctx* ctx, const double* shear_h, const double
  * is in progress. */
 int fep_ctx_set_model(fep_ctx* ctx, int model);
 int fep_ctx_model(const fep_ctx* ctx, int* model);
+/* FEP_MODEL_VMI is a model of fep_ctx_set_model too (4 is none: FEP_EINVAL): the third and fourth arrays of
+ * fep_ctx_set_materials_host are a and Y as for von Mises, row 3 of ep_prev is kappa (fep_return_map_vmi_*), and the steps run
+ * on the hardening curve of the context, one segment of slope 0 until this call sets another (n_seg, kappa_h, slope_h as in
+ * fep_return_map_vmi_*; copied, so the arrays may be freed).  Before or after the materials.  fep_step_* and fep_step_field_* of
+ * such a context run as for von Mises (the model's point kernel, then the context's own assembly), allocate nothing and can be
+ * captured; the curve travels as a kernel argument, so it is baked into a captured launch as e0_h is: a replay runs on the
+ * curve of the capture, whatever has been set since.
+ * FEP_EINVAL: NULL context or a curve that is not as stated; FEP_ESTATE: the context's model is not FEP_MODEL_VMI.  A refused
+ * call changes nothing. */
+int fep_ctx_set_hardening(fep_ctx* ctx, int n_seg, const double* kappa_h, const double* slope_h);
 
 /* Device pointers of the context's static per-point arrays (for the mesh-free entry points):
  * which = 0 shear, 1 bulk, 2 eta, 3 c, 4 weight, 5 dphi1, 6 dphi2. */

@@ -3,7 +3,9 @@
 Mises (plane strain, and plane stress with its per-point Newton loop) and the Mohr-Coulomb step (point kernel + the route's assembly from ds / s), each as the K,F-only step of a Newton iterate
 and with every point output.  A fourth row, "DP, field" (keys dp_field_*) beside "DP, uniform" (dp_*): the same Drucker-Prager context
 stepped with an initial strain per point (a field of zeros, so the same points yield), which runs staged like the von Mises and
-Mohr-Coulomb rows it is to be compared with.  HIP events around batches of steps, the ten variants of a type interleaved pass
+Mohr-Coulomb rows it is to be compared with.  'vmi' (von Mises with isotropic hardening on an eight-segment Voce curve, the materials
+of 'vm') runs beside 'vm', and 'vm' is timed a second time in every pass ('vm_repeat'): the spread between the two is what a
+difference between 'vmi' and 'vm' has to exceed to mean anything.  HIP events around batches of steps, the ten variants of a type interleaved pass
 by pass in one process (what differs between them is then not the box or the session).  Prints one JSON line.
     python tools/model_bench.py [--types P1,P2,Q1,Q2,P4] [--steps 20] [--passes 5] [--scale 1.0]
 Mesh sizes as tools/elem_bench.py is run (cells per side: 708, P4 354); --scale shrinks them for a quick look."""
@@ -20,7 +22,7 @@ import bench  # noqa: E402
 import torch  # noqa: E402
 
 fep = importlib.import_module('fem-elastoplasticity_amd')
-MODELS = ('dp', 'vm', 'mc', 'vmps')
+MODELS = ('dp', 'vm', 'mc', 'vmps', 'vmi')
 CELLS = {'P1': 708, 'P2': 708, 'Q1': 708, 'Q2': 708, 'P4': 354}
 
 
@@ -44,11 +46,14 @@ def time_type(t, N, steps, passes):
     # the same shear and bulk; the von Mises radius sqrt(2) c is the Drucker-Prager cone's at zero pressure, the Mohr-Coulomb
     # friction angle and cohesion are those the cone was matched to (bench.dp_materials)
     third_fourth = {'dp': (eta, c), 'vm': (0.05 * sh, np.sqrt(2) * c), 'mc': (np.sin(np.pi / 9), 450.0),
-                    'vmps': (0.05 * sh, np.sqrt(2) * c)}
+                    'vmps': (0.05 * sh, np.sqrt(2) * c), 'vmi': (0.05 * sh, np.sqrt(2) * c)}
+    sigma_0 = float(np.sqrt(1.5) * np.sqrt(2) * np.min(c))               # the yield stress of the radius sqrt(2) c
     for model in MODELS:
         ctx = fep.MeshContext(elem, coord)
         ctx.set_model(model)
         ctx.set_materials(sh, bu, *third_fourth[model])
+        if model == 'vmi':
+            ctx.set_hardening(*fep.voce_curve(sigma_0, 1.5 * sigma_0, 60.0)[1:])
         ctxs[model] = ctx
     n = ctxs['dp'].n_int
     f64 = dict(dtype=torch.float64, device=dev)
@@ -62,9 +67,11 @@ def time_type(t, N, steps, passes):
         kw = dict(s=S.data_ptr(), ds=DS.data_ptr(), ind_p=ind.data_ptr()) if full else {}
         if model == 'dp_field':
             model, kw = 'dp', dict(kw, e0_field=Fld.data_ptr(), e0_scale=1.0)
+        if model == 'vm_repeat':
+            model = 'vm'
         ctxs[model].step_dev(st, U.data_ptr(), ep=Ep.data_ptr(), k_data=Kd.data_ptr(), f_out=F.data_ptr(),
                              counts=cnt.data_ptr(), **kw)
-    variants = [(m, full) for m in MODELS + ('dp_field',) for full in (False, True)]
+    variants = [(m, full) for m in MODELS + ('dp_field', 'vm_repeat') for full in (False, True)]
     plastic = {}
     for m, full in variants:
         for _ in range(3):
