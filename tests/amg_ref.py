@@ -1,7 +1,8 @@
 """
 Float64 restatement of the GPU solver's preconditioners and of both conjugate-gradient forms
 (fem-elastoplasticity_amd/csrc/fep_solver.hip), for the tests that compare the device's iterates with it
-(test_vcycle_gpu.py) and the tests of the restatement itself (test_amg_ref.py).  Plain NumPy / SciPy, no GPU.
+(test_vcycle_gpu.py, test_solver_shapes_gpu.py, test_solver_forms_gpu.py) and the tests of the restatement itself
+(test_amg_ref.py).  Plain NumPy / SciPy, no GPU (push_hierarchy alone talks to the device).
 
 What the device computes, and what this module therefore does:
   - block_jacobi_kernel: the 2x2 node blocks of the DOUBLE K, constrained DOFs replaced by identity rows and columns, the
@@ -110,6 +111,99 @@ def tail_runs(level_sizes, refresh=True, fp32=True, tail=True, block_transfers=T
         return False
     n_last_smoothed, n_coarsest = level_sizes[-2][0], level_sizes[-1][0]
     return n_last_smoothed // 3 <= TAIL_NODES and n_coarsest <= TAIL_COARSE and n_coarsest % 3 == 0
+
+
+FOUR_PASS_NODES = 128 * 2048                 # NODES_PER_BLOCK * 2048 of vcycle_chebyshev's `big`
+
+
+def node3_four_pass(level_sizes):
+    """Per smoothed coarse level (levels 1 .. of `level_sizes` = KrylovSolver.amg_levels, the coarsest left out), whether
+    vcycle_chebyshev launches node3_kernel<MODE, AV, 4> there: its `big` condition, from 262 144 nodes of three DOFs."""
+    return [n // 3 >= FOUR_PASS_NODES for n, _ in level_sizes[1:-1]]
+
+
+def product_lanes(n_terms, n_out):
+    """Lanes per output entry of product_apply: product_kernel<8> from a mean of 12 terms per entry, <4> from 3, <1> below
+    (0: no launch on an empty plan)."""
+    if n_out <= 0:
+        return 0
+    mean = float(n_terms) / float(n_out)
+    return 8 if mean >= 12.0 else 4 if mean >= 3.0 else 1
+
+
+def singleton_hierarchy(K, free_dof, coordinates, coarse_nodes=64, max_levels=8):
+    """A hierarchy whose level 1 has one node per mesh node, in the level dicts setup_amg pushes.  Transfer 0 gives every
+    mesh node an aggregate of its own and leaves the prolongator unsmoothed: the 2x3 block of a free node is (I_2 | 0)
+    (the aggregate's centre is the node, so the rotation column is empty), of a constrained DOF a zero row.  Level 1's
+    operator then has the mesh's own node-block pattern (rows and columns of constrained DOFs and of every rotation empty)
+    and both refresh products have about one term per entry.  Transfers 1 and up are build_amg_hierarchy's for bs = 3:
+    aggregation, rigid-body modes, one damped-Jacobi step on the prolongator, Galerkin products, the same `last` rule.
+    Reaches the forms the device chooses by a level's size (node3_four_pass) and by a plan's mean term count
+    (product_lanes) with meshes of 2.6 * 10^5 nodes instead of 2.6 * 10^6."""
+    f = np.asarray(free_dof, dtype=bool).ravel().astype(np.float64)
+    A = solver._masked_operator(K, f)
+    xy = np.asarray(coordinates, dtype=np.float64)
+    n_n = A.shape[0] // 2
+    Di = solver._block_diag_inverse(A, 2)
+    rho = solver._rho(A, Di)
+    out = []
+    for level in range(max_levels):
+        if level == 0:
+            na = n_n
+            Pt, cxy = solver._tentative(np.arange(n_n), na, xy, 2)
+            P = (ssp.diags(f) @ Pt).tocsr()
+            P.eliminate_zeros()                          # -(y - cy), x - cx: stored zeros
+            last = False
+        else:
+            agg, na = solver._aggregate(A, 3)
+            Pt, cxy = solver._tentative(agg, na, xy, 3)
+            P = (Pt - (4.0 / (3.0 * rho)) * (Di @ solver._spgemm(A, Pt))).tocsr()
+            last = na <= coarse_nodes or level == max_levels - 1 or 3 * na > 0.7 * A.shape[0]
+        R = P.T.tocsr()
+        Ac = solver._spgemm(R, solver._spgemm(A, P))
+        if last:
+            dense = Ac.toarray()
+            dense += 1e-10 * np.abs(dense).max() * np.eye(dense.shape[0])
+            Aop, Dc = ssp.csr_matrix(np.linalg.inv(dense)), None
+        else:
+            Aop, Dc = Ac, solver._block_diag_inverse(Ac, 3)
+        for M in (P, R, Aop, Dc):
+            if M is not None:
+                M.sort_indices()
+        out.append({'P': P, 'R': R, 'A': Aop, 'D': Dc, 'omega': 4.0 / (3.0 * 1.05 * rho), 'last': last,
+                    'size': (Ac.shape[0], Ac.nnz)})
+        if last:
+            break
+        A, xy, Di = Ac, cxy, Dc
+        rho = solver._rho(A, Di)
+    return out
+
+
+def push_hierarchy(sol, levels, refresh=True):
+    """KrylovSolver.setup_amg's upload for a given list of level dicts: fep_solver_amg_clear, one fep_solver_amg_push_level
+    per transfer, fep_solver_amg_enable_refresh.  Sets sol.amg_hierarchy / amg_levels / amg_refresh and returns amg_levels.
+    A refresh the device declines (FEP_ERANGE) is an error here: the caller chose the hierarchy so that it cannot."""
+    l, ptr, check = solver._lib.lib(), solver._lib.ptr, solver._lib.check
+    check(l.fep_solver_amg_clear(sol._h), 'fep_solver_amg_clear')
+    for lv in levels:
+        mats = []
+        for M in (lv['P'], lv['R'], lv['A'], lv['D']):
+            if M is None:
+                mats += [None, None, None]
+            else:
+                mats += [np.ascontiguousarray(M.indptr, dtype=np.int32), np.ascontiguousarray(M.indices, dtype=np.int32),
+                         np.ascontiguousarray(M.data, dtype=np.float64)]
+        check(l.fep_solver_amg_push_level(sol._h, lv['P'].shape[0], lv['P'].shape[1], *[ptr(m) for m in mats],
+                                          float(lv['omega']), int(lv['last'])), 'fep_solver_amg_push_level')
+    sol.amg_hierarchy = levels
+    sol.amg_levels = [(sol.n_dof, sol.nnz)] + [lv['size'] for lv in levels]
+    sol.amg_refresh = False
+    if refresh:
+        rc = l.fep_solver_amg_enable_refresh(sol._h)
+        assert rc != -5, 'fep_solver_amg_enable_refresh answered FEP_ERANGE'
+        check(rc, 'fep_solver_amg_enable_refresh')
+        sol.amg_refresh = True
+    return sol.amg_levels
 
 
 class VCycle:

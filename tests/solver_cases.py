@@ -10,7 +10,10 @@ Free DOFs: tsx cases carry the rollers of newton._tsx_setup; Delaunay cases roll
 node of radius > 1.7 (the outer ring and, raised, the nodes between its vertices); the small rectangles pin the lower right
 corner and put the lower left one on a roller (a 1 x 1 cell then keeps 5 free DOFs and, under this choice of the three, four
 distinct CG iterates for every right-hand side: with rollers on the left edge the one-node right-hand side converges in
-four); a node of no element is fixed in both DOFs whatever its case.
+four); a node of no element is fixed in both DOFs whatever its case; the rectangles of FORMS (test_solver_forms_gpu.py) have
+their bottom row fixed vertically and their left column horizontally (only the corner in both: a node fixed in both
+directions is isolated on level 1 and below, fep_aggregate_host keeps it as an aggregate of its own on every level, and a
+whole row of them would put the coarsest level beyond the refresh's 256 DOFs).
 
 The displacement of `displacement()` gives a plastic tangent with dp_materials: with x, y the coordinates shifted to the
 bounding box's corner and divided by its larger side L,
@@ -74,6 +77,23 @@ SMALL = {
 }
 ALL = dict(CASES, **SMALL)
 FULL_SOLVES = ('tsx-P4', 'delaunay58-P1', 'fan250-P1', 'orphans-P1')
+# The kernel forms the device picks by size (test_solver_forms_gpu.py): rectangles of fep.rect_mesh under
+# amg_ref.singleton_hierarchy, whose level 1 has as many nodes as the mesh (the names give nodes per side for P1, cells for P2);
+# four_pass: whether level 1 takes node3_kernel's four-nodes-per-lane-group form (from 128 * 2048 = 262 144 nodes);
+# nodes, tail, sens_vcycle as above, on the oracle's matrices (test_solver_cases_host.py).  Not in ALL: block Jacobi and spmv have no such form.
+FORMS = {
+    'P1-511x513': dict(kind='form', et='P1', cells=(510, 512), n_nodes=262143, four_pass=False, amp=AMP,
+                       nodes=(262143, 262143, 29242, 2431, 157, 12), tail=True, sens_vcycle=9.6e-13),
+    'P1-512x512': dict(kind='form', et='P1', cells=(511, 511), n_nodes=262144, four_pass=True, amp=AMP,
+                       nodes=(262144, 262144, 29242, 2491, 173, 13), tail=True, sens_vcycle=1.1e-12),
+    'P1-517x508': dict(kind='form', et='P1', cells=(516, 507), n_nodes=262636, four_pass=True, amp=AMP,
+                       nodes=(262636, 262636, 29410, 2441, 158, 13), tail=True, sens_vcycle=2.1e-12, sens_full=4.9e-13),
+    'P2-256':     dict(kind='form', et='P2', cells=(256, 256), n_nodes=263169, four_pass=True, amp=AMP,
+                       nodes=(263169, 263169, 16513, 703, 37), tail=False, sens_vcycle=2.8e-12),
+}
+FORMS_FULL_SOLVE = 'P1-517x508'              # sens_full: the same sensitivity of the full solve's last iterate
+FORMS_COARSE_NODES = 64                      # (what setup_amg caps coarse_nodes at under the refresh)
+EVERY = dict(ALL, **FORMS)
 
 _MESH = {}
 
@@ -81,7 +101,7 @@ _MESH = {}
 def mesh(name):
     """(elements (n_p, n_e) int64, coordinates (2, n_n), element type); cached, read-only."""
     if name not in _MESH:
-        c = ALL[name]
+        c = EVERY[name]
         et = c['et']
         if c['kind'] == 'tsx':
             g = load_golden('tsx')
@@ -97,6 +117,9 @@ def mesh(name):
             elem, coord = meshes.renumber(meshes.drop_last(elem, 40), coord, rng)
         elif c['kind'] == 'fan':
             elem, coord = fan_mesh.fan_mesh(c['k'], et, shuffle=True)
+        elif c['kind'] == 'form':
+            m = import_module('fem-elastoplasticity_amd').rect_mesh(*c['cells'], et)
+            elem, coord = m['elements'], m['coordinates']
         else:
             elem, coord = meshes.rect(et, *c['cells'])
         elem = np.ascontiguousarray(elem, dtype=np.int64)
@@ -115,7 +138,7 @@ def orphan_nodes(name):
 def free_dofs(name):
     """bool (n_dof,), DOF = 2 * node + component."""
     elem, coord, _ = mesh(name)
-    kind = ALL[name]['kind']
+    kind = EVERY[name]['kind']
     x, y = coord
     Q = np.ones(coord.shape, dtype=bool)
     if kind == 'tsx':                                        # newton._tsx_setup, TSX:1695-1699
@@ -128,6 +151,9 @@ def free_dofs(name):
         Q[1, (y == y.min()) | (y == y.max())] = False
     elif kind == 'fan':
         Q[:, np.hypot(x, y) > 1.7] = False
+    elif kind == 'form':                                     # bottom row fixed vertically, left column horizontally
+        Q[1, y == y.min()] = False
+        Q[0, x == x.min()] = False
     else:                                                    # statically determinate: a pin and a roller
         Q[:, (x == x.max()) & (y == y.min())] = False
         Q[1, (x == x.min()) & (y == y.min())] = False
@@ -141,7 +167,7 @@ def displacement(name):
     lo = coord.min(axis=1)
     L = (coord.max(axis=1) - lo).max()
     x, y = (coord[0] - lo[0]) / L, (coord[1] - lo[1]) / L
-    U = ALL[name]['amp'] * L * np.stack([-0.4 * x + 1.5 * x * y * (y > 0.4), -0.5 * y - 0.5 * y * (x >= 0.5)])
+    U = EVERY[name]['amp'] * L * np.stack([-0.4 * x + 1.5 * x * y * (y > 0.4), -0.5 * y - 0.5 * y * (x >= 0.5)])
     return U.flatten(order='F')
 
 
@@ -210,6 +236,13 @@ def ulp_sensitivity(K, qf, make_M, cg):
             return np.inf
         worst = max([worst] + [relerr(a[0], c[0]) for a, c in zip(hp, h)])
     return worst
+
+
+def forms_full_solve_rhs(K, qf):
+    """(x, b = Q K x) for a random x, 0 on constrained DOFs: the right-hand side of the forms' full solve (the restated CG
+    takes 45 iterations to rtol 1e-10 on K_elast with it, against 300 with a random b on the plastic tangent)."""
+    x = np.where(qf, np.random.default_rng(31).normal(size=qf.size), 0.0)
+    return x, np.where(qf, K @ x, 0.0)
 
 
 def bound(floor, sensitivity):

@@ -40,7 +40,8 @@ Full solves to rtol = 1e-10 (iterations of device = restatement; x against the r
 2.8e-14, 6.2e-11; delaunay58-P1 62, 1.6e-14, 4.5e-11; fan250-P1 109, 2.0e-14, 1.1e-11; orphans-P1 43, 1.1e-15, 6.7e-12.  spmv: at most
 0.19 of its per-entry bound.  Power iteration: device and host equal to 2.2e-16.
 
-Not reached: node3_kernel's four-nodes-per-lane-group form, taken from 262 144 coarse nodes (multi-million-DOF meshes).
+node3_kernel's four-nodes-per-lane-group form (coarse levels of 262 144 nodes and more) and product_kernel's one-lane form
+are compared in the same way by test_solver_forms_gpu.py, on a hierarchy made for them (amg_ref.singleton_hierarchy).
 """
 import ctypes as C
 

@@ -7,7 +7,8 @@ independence of `check_every`, and the device-side power iteration of the set-up
 
 Tolerances: the kernels do their arithmetic in double on the operands the restatement rounds the same way, so the two
 differ by summation order and by the pivoting of the coarsest inverse only; each bound is next to its measured value.
-Not reached: node3_kernel's four-nodes-per-lane-group form, taken from 262 144 coarse nodes (multi-million-DOF meshes).
+node3_kernel's four-nodes-per-lane-group form (coarse levels of 262 144 nodes and more) and product_kernel's one-lane form
+are compared in the same way by test_solver_forms_gpu.py, on a hierarchy made for them (amg_ref.singleton_hierarchy).
 """
 import numpy as np
 import pytest
