@@ -5,7 +5,8 @@ float64 reference strain, decided on the CPU (test_e0_field_host.py) before a ke
 
 Meshes: per type the three block-edge meshes of model_step_cases.py (255, 256, 257 elements: n_int modulo the point kernels'
 256 lanes is 256 - NQ, 0 and NQ) and one unstructured named mesh ('delaunay' for the triangles, 'renumbered' for the
-quadrilaterals).  State: model_step_cases.state for von Mises and Mohr-Coulomb, its von Mises generator restated for
+quadrilaterals).  State: model_step_cases.state for von Mises, Mohr-Coulomb and 'vmi' (isotropic hardening: on one of the five
+curves of that module, by the case's number; the field is scaled by the von Mises yield strain), its von Mises generator restated for
 Drucker-Prager (a random displacement scaled so that the median point sits on the cone).  The field is eps_y * normal(0, 0.2),
 drawn independently in all four rows and at every point, so that a wrong row stride or point index cannot cancel; in half of
 the cases it is combined with a non-zero uniform e0 and scale = 0.37, in the others it stands alone with scale = 1.
@@ -21,7 +22,7 @@ from elem_ref import ElemRef
 from mc_cases import EPS_Y
 from vm_cases import SHEAR, YIELD, fep
 
-MODELS = ('dp', 'vm', 'mc')
+MODELS = ('dp', 'vm', 'mc', 'vmi')
 TYPES, ROUTES, NQ, BLOCK = cases.TYPES, cases.ROUTES, cases.NQ, cases.BLOCK
 MAX_EXCLUDED, MAX_DRAWS = cases.MAX_EXCLUDED, cases.MAX_DRAWS
 DP_CRIT_FLOOR = cases.VM_CRIT_FLOOR                                      # |crit1|, |crit2| over c: the von Mises floor
@@ -47,8 +48,21 @@ def flags(model, t, name):
     return bool(k & 1), bool(k & 2), bool(k & 4)
 
 
+def curve_id(model, t, name):
+    """The hardening curve of a 'vmi' case (model_step_cases.CURVES), by the case's number as in that module."""
+    return cases.CURVES[(TYPES.index(t) + names(t).index(name)) % len(cases.CURVES)] if model == 'vmi' else None
+
+
+def curve_of(model, t, name):
+    c = curve_id(model, t, name)
+    return None if c is None else cases.vmi_cases.curve(c)
+
+
+MESH_FREE_CURVE = 2                                                      # of the mesh-free 'vmi' points
+
+
 def eps_y(model):
-    if model == 'vm':
+    if model in ('vm', 'vmi'):
         return YIELD / (2 * SHEAR)
     if model == 'mc':
         return EPS_Y
@@ -79,27 +93,29 @@ def uniform(model, n):
     return tuple(v * np.ones(n) for v in cases.UNIFORM[model])
 
 
-def excluded(model, r, mats):
-    """The points at which rounding of the strain may decide the flag (or, Mohr-Coulomb, amplify into the tangent)."""
+def excluded(model, r, mats, curve=None):
+    """The points at which rounding of the strain may decide the flag (or, Mohr-Coulomb, amplify into the tangent; 'vmi': the
+    segment of the curve)."""
     if model == 'dp':
         c = np.asarray(mats[3])
         return (np.abs(r['crit1']) < DP_CRIT_FLOOR * c) | ((r['crit1'] > 0) & (np.abs(r['crit2']) < DP_CRIT_FLOOR * c))
-    return cases.excluded(model, r, mats)
+    return cases.excluded(model, r, mats, curve)
 
 
-def check_conditions(model, r, excl):
+def check_conditions(model, r, excl, curve=None):
     assert excl.mean() <= MAX_EXCLUDED, ('excluded', int(excl.sum()), excl.size)
     if model == 'dp':
         assert 0.2 <= r['ind_p'].mean() <= 0.8, ('plastic share', r['ind_p'].mean())
     else:
-        cases.check_conditions(model, r, excl)
+        cases.check_conditions(model, r, excl, curve)
 
 
 _BUILT = {}
 
 
 def build(model, t, name):
-    """-> dict elem, coord, U, ep, mats, e0 (or None), field, scale, accept, draw: the same on every route, computed once
+    """-> dict elem, coord, U, ep, mats, e0 (or None), field, scale, accept, draw, curve ('vmi': (kappa, slope) or None for
+    the context's default; None for the other models): the same on every route, computed once
     per session and never modified by the tests (they copy what a call updates)."""
     key = (model, t, name)
     if key in _BUILT:
@@ -109,18 +125,19 @@ def build(model, t, name):
     pp, with_e0, accept = flags(model, t, name)
     ref = ElemRef(elem, coord, fep.element_tables(t))
     n = ref.n_int
+    curve = curve_of(model, t, name)
     for draw in range(MAX_DRAWS):
-        U, ep, per_point, e0 = dp_state(elem, coord, ref, rng) if model == 'dp' else cases.state(model, t, elem, coord, rng)
+        U, ep, per_point, e0 = dp_state(elem, coord, ref, rng) if model == 'dp' else cases.state(model, t, elem, coord, rng, curve)
         field = eps_y(model) * rng.normal(0, 0.2, size=(4, n))
         mats = per_point if pp else uniform(model, n)
         c = dict(elem=elem, coord=coord, U=U, ep=ep, mats=mats, e0=e0 if with_e0 else None, field=field,
-                 scale=SCALE if with_e0 else 1.0, accept=accept, draw=draw)
+                 scale=SCALE if with_e0 else 1.0, accept=accept, draw=draw, curve=curve)
         try:
             E = ref.strain(U)[0]
             z = fref.z_of(c['e0'], field, c['scale'])
             for p in (ep, None):
-                r = fref.return_map(model, E, p, mats, z, False)
-                check_conditions(model, r, excluded(model, r, mats))
+                r = fref.return_map(model, E, p, mats, z, False, curve=curve)
+                check_conditions(model, r, excluded(model, r, mats, curve), curve)
             _BUILT[key] = c
             return c
         except AssertionError:
@@ -129,7 +146,8 @@ def build(model, t, name):
 
 
 def mesh_free(model, n, seed_):
-    """Mesh-free points of `model`: (E (3, n), ep, mats, e0, field) around the yield surface, per-point materials."""
+    """Mesh-free points of `model`: (E (3, n), ep, mats, e0, field) around the yield surface, per-point materials; 'vmi': kappa
+    spread over curve MESH_FREE_CURVE."""
     rng = np.random.default_rng(zlib.crc32(f'mesh-free {model} {n} {seed_}'.encode()))
     ey = eps_y(model)
     E = ey * rng.normal(0, 1.5, size=(3, n))
@@ -140,6 +158,8 @@ def mesh_free(model, n, seed_):
     mats = (u[0] * f, u[1] * f[::-1], third, u[3] * rng.uniform(0.6, 1.4, n))
     e0 = rng.normal(0, 0.2 * ey, size=(4, 1))
     field = ey * rng.normal(0, 0.2, size=(4, n))
+    if model == 'vmi':
+        ep[3] = rng.uniform(0, 1.3 * cases.vmi_cases.curve(MESH_FREE_CURVE)[0][-1], n)
     return E, ep, mats, e0, field
 
 

@@ -20,7 +20,8 @@ from oracle_context import OracleContext
 from vm_ref import vm_return_map
 
 SQRT2 = np.sqrt(2.0)
-PER_POINT_KEYS = {'vm': ('crit',), 'mc': ('branch', 'f', 'r_rel', 'dist')}
+PER_POINT_KEYS = {'vm': ('crit',), 'mc': ('branch', 'f', 'r_rel', 'dist'),
+                  'vmi': ('crit', 'seg', 'lam', 'seg0', 'kappa_new')}
 
 
 def z_of(e0, field, scale):
@@ -60,7 +61,7 @@ def _dp(E, ep, mats, z, accept):
     return dict(r, crit1=crit1, crit2=crit2, branch=np.where(crit1 > 0, np.where(crit2 > 0, 2, 1), 0))
 
 
-def _merge(model, E, ep, mats, z, accept, per_point):
+def _merge(model, E, ep, mats, z, accept, per_point, curve=None):
     n = E.shape[1]
     if per_point:
         groups = [np.array([k]) for k in range(n)]
@@ -71,23 +72,27 @@ def _merge(model, E, ep, mats, z, accept, per_point):
     out = {'s': np.empty((4, n)), 'ds': np.empty((9, n)), 'ind_p': np.zeros(n, dtype=bool),
            'ep': np.zeros((4, n)), 'n_smooth': 0, 'n_apex': 0}
     for k in PER_POINT_KEYS[model]:
-        out[k] = np.zeros(n, dtype=np.int64 if k == 'branch' else float)
+        out[k] = np.zeros(n, dtype=np.int64 if k in ('branch', 'seg', 'seg0') else float)
     for idx in groups:
         m = tuple(np.asarray(v, dtype=float)[idx] for v in mats)
-        r = cases.return_map(model, E[:, idx], None if ep is None else ep[:, idx], m, z[:, idx[0]].reshape(4, 1), accept)
+        r = cases.return_map(model, E[:, idx], None if ep is None else ep[:, idx], m, z[:, idx[0]].reshape(4, 1), accept, curve)
         for k in ('s', 'ds', 'ind_p', 'ep') + PER_POINT_KEYS[model]:
             out[k][..., idx] = r[k]
         out['n_smooth'] += int(r['n_smooth'])
         out['n_apex'] += int(r['n_apex'])
-    if model == 'vm':
+    if model in ('vm', 'vmi'):
         out['n_plast'] = out['n_smooth']
+    if model == 'vmi':
+        out['with_state'] = ep is not None
     return out
 
 
-def return_map(model, E, ep, mats, z, accept, per_point=False):
+def return_map(model, E, ep, mats, z, accept, per_point=False, curve=None):
     """The model's restatement with the initial strain z[:, k] at point k -> dict s, ds, ind_p, ep (as the restatement
     returns it: the updated copy when `accept`), n_smooth, n_apex as a context's step counts them, and what the floors
-    read (dp: crit1, crit2; vm: crit; mc: branch, f, r_rel, dist).  No argument is modified."""
+    read (dp: crit1, crit2; vm: crit; mc: branch, f, r_rel, dist; vmi: crit, seg, seg0, kappa_new).  No argument is modified.
+    'vmi' runs on `curve`; its restatement (tests/vmi_ref.py) takes one initial strain per point, so unless `per_point` asks
+    for the calls point by point it is called once with the whole z."""
     E = np.asarray(E, dtype=float)
     z = np.asarray(z, dtype=float)
     assert z.shape == (4, E.shape[1])
@@ -95,15 +100,17 @@ def return_map(model, E, ep, mats, z, accept, per_point=False):
     accept = bool(accept) and ep is not None
     if model == 'dp':
         return _dp(E, ep, mats, z, accept)
-    return _merge(model, E, ep, mats, z, accept, per_point)
+    if model == 'vmi' and not per_point:
+        return cases.return_map(model, E, ep, mats, z, accept, curve)
+    return _merge(model, E, ep, mats, z, accept, per_point, curve)
 
 
-def plain_return_map(model, E, ep, mats, e0, accept):
+def plain_return_map(model, E, ep, mats, e0, accept, curve=None):
     """The existing restatement with one (4, 1) initial strain, as the tests of the plain steps call it."""
     if model == 'dp':
         return _dp(np.asarray(E, dtype=float), ep, tuple(np.asarray(v, dtype=float) * np.ones(E.shape[1]) for v in mats),
                    np.asarray(e0, dtype=float).reshape(4, 1), bool(accept) and ep is not None)
-    return cases.return_map(model, E, ep, mats, e0, bool(accept) and ep is not None)
+    return cases.return_map(model, E, ep, mats, e0, bool(accept) and ep is not None, curve)
 
 
 def point_coords(fep, t, elem, coord):

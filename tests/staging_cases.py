@@ -33,7 +33,9 @@ MESH_N = 724
 SMALL_MESH_N = 40
 CANARY_BYTES = 4096
 CANARY = 0xC5
-MODELS = ('dp', 'vm', 'mc')
+MODELS = ('dp', 'vm', 'mc')                                             # of the mesh-free calls, which take no curve
+STEP_MODELS = ('vm', 'mc', 'vmi')                                       # of the context calls beside Drucker-Prager
+VMI_CURVE = 2                                                           # 'vmi' contexts: the fixture's eight segments
 MODEL_ID = {'dp': 0, 'vm': 1, 'mc': 2}
 ENTRY = {'dp': 'fep_return_map', 'vm': 'fep_return_map_vm', 'mc': 'fep_return_map_mc'}
 FIELD_SCALE = 0.37
@@ -186,7 +188,8 @@ def model_materials(model, n):
 # Factor on `displacement` per model, decided on the float64 restatement (e0_field_ref.return_map on the 40-cell square, whose
 # strains are those of any finer square): Drucker-Prager 1 (20 % smooth, 56 % apex), von Mises a quarter of the ratio of the
 # yield strains (45 % plastic; at the full ratio every point yields), Mohr-Coulomb the ratio (72 % face and edges, 24 % apex).
-_SCALE = {'dp': 1.0, 'vm': 0.25, 'mc': 1.0}
+# 'vmi' from kappa = 0 has the yield surface of von Mises: its factor.
+_SCALE = {'dp': 1.0, 'vm': 0.25, 'mc': 1.0, 'vmi': 0.25}
 
 
 def model_scale(model):

@@ -4,8 +4,9 @@ element-by-element float64 reference (tests/elem_ref.py) and the models' restate
 (tests/e0_field_ref.py), entry by entry; then solve_tsx_tunnel with `in_situ` / `body_force` end to end.
 
 A step with a field runs staged for every model, Drucker-Prager too: p1_point_field_kernel<MODEL> / point_field_kernel<MODEL,
-NP, NQ>, then what fep_assemble_dev launches for the route.  The cases (tests/e0_field_cases.py, decided on the CPU by
-test_e0_field_host.py): dp, vm, mc x P1, P2, Q1, Q2, P4 x every route of the type x the block255 / block256 / block257 meshes
+NP, NQ>, then what fep_assemble_dev launches for the route; the 'vmi' model (von Mises with isotropic hardening) through two
+wrappers with names of their own, p1_point_vmi_field_kernel and point_vmi_field_kernel<NP, NQ>, which take the curve.  The cases (tests/e0_field_cases.py, decided on the CPU by
+test_e0_field_host.py): dp, vm, mc, vmi (on the five curves of model_step_cases.py) x P1, P2, Q1, Q2, P4 x every route of the type x the block255 / block256 / block257 meshes
 (n_int modulo the 256 lanes: 256 - NQ, 0, NQ) and one unstructured mesh; a field drawn independently in all four rows at
 every point, in half of the cases beside a uniform e0 with scale = 0.37.
 
@@ -15,7 +16,8 @@ The three decoupled stages of test_model_step_routes_gpu.py, with its bounds as 
      1e-12 per point; points under the floors (at most 0.5 %) left out of flag / ds / counters
   3. K, F against ElemRef.assemble of the kernel's ds / s within C_K / C_F (C_RECORD on the node route)
 and bit for bit: K,F-only / K-only / F-only = full output; ep_prev None = zeros; scale 0 with any finite field = a field of
-zeros; a field whose columns all equal z (scale 1, no uniform part) = the plain step with e0 = z (vm, mc: every route; dp: the P1
+zeros; a field whose columns all equal z (scale 1, no uniform part) = the plain step with e0 = z (vm, mc, vmi: every type and
+route, in E, s, ds, ind_p, K, F and the counters: the return maps are compiled without contraction for this claim; dp: the P1
 node route, whose plain full-output step runs the same point body; dp on the element routes, whose plain step forms its strain
 in element_kernel, is held to stages 2 and 3 instead).
 Containment: a NaN, and an infinity, at the last lane of workgroup 0 and at the first lane of workgroup 1.
@@ -61,13 +63,21 @@ def _context(fep, monkeypatch, c, model, route):
     return ctx
 
 
-def _check_points(model, got, ep_got, E, Ep, mats, z, accept, what, generator_conditions=True):
+def _set_curve(ctx, model, curve):
+    if model == 'vmi':
+        tag = 'p1_point_vmi_kernel' if ctx.n_p == 3 else f'point_vmi_kernel<{ctx.n_p}, {ctx.n_q}>'
+        assert ctx.kernel_names(0).startswith(tag + ' + '), ctx.kernel_names(0)
+        if curve is not None:
+            ctx.set_hardening(*curve)
+
+
+def _check_points(model, got, ep_got, E, Ep, mats, z, accept, what, generator_conditions=True, curve=None):
     """Stage 2: the outputs of a step against the restatement on the kernel's strain E."""
-    o = fref.return_map(model, E, Ep, mats, z, accept)
-    excl = fcases.excluded(model, o, mats)
+    o = fref.return_map(model, E, Ep, mats, z, accept, curve=curve)
+    excl = fcases.excluded(model, o, mats, curve)
     keep = ~excl
     if generator_conditions:
-        fcases.check_conditions(model, o, excl)
+        fcases.check_conditions(model, o, excl, curve)
     assert excl.mean() <= fcases.MAX_EXCLUDED
     assert np.array_equal(got['ind_p'][keep], o['ind_p'][keep])
     assert got['n_smooth'] + got['n_apex'] == int(got['ind_p'].sum())
@@ -85,6 +95,11 @@ def _check_points(model, got, ep_got, E, Ep, mats, z, accept, what, generator_co
         print(f'[points] ep {e_p[0]:.1e} / {e_p[1]:.1e}')
         assert e_p[0] <= TOL and e_p[1] <= TOL_PT
         assert not np.array_equal(ep_got, Ep)
+        if model == 'vmi':                                              # kappa beside strains a thousandth of its size: each alone too
+            for rows in (slice(0, 3), slice(3, 4)):
+                assert relerr(ep_got[rows], o['ep'][rows]) <= TOL and relerr_points(ep_got[rows], o['ep'][rows]) <= TOL_PT
+            el = ~got['ind_p'] & keep
+            assert np.array_equal(ep_got[3][el], Ep[3][el]) and (ep_got[3] > Ep[3])[got['ind_p'] & keep].all()
     elif Ep is not None:
         assert np.array_equal(ep_got, Ep)
 
@@ -110,7 +125,7 @@ def _check_assembly(t, route, got, elem, coord, tab, pattern, what):
 def test_field_step_vs_reference_per_entry(fep, monkeypatch, model, t, route, name):
     c = fcases.build(model, t, name)
     elem, coord, U, Ep, mats, e0, accept = (c[k] for k in ('elem', 'coord', 'U', 'ep', 'mats', 'e0', 'accept'))
-    field, scale = c['field'], c['scale']
+    field, scale, curve = c['field'], c['scale'], c['curve']
     kw = dict(e0_field=field, e0_scale=scale, **({} if e0 is None else {'e0': e0}))
     rng = np.random.default_rng(fcases.seed(model, t, name) + 1)
     zc = fcases.eps_y(model) * rng.normal(0, 0.2, size=(4, 1))              # the constant field of the pin
@@ -122,6 +137,7 @@ def test_field_step_vs_reference_per_entry(fep, monkeypatch, model, t, route, na
         if model != 'dp':
             ctx.set_model(model)
         ctx.set_materials(*mats)
+        _set_curve(ctx, model, curve)
         ep = Ep.copy()
         # scrub between the forms: none may pass its pin with what the call before left in the context's device buffers
         if accept:
@@ -168,7 +184,7 @@ def test_field_step_vs_reference_per_entry(fep, monkeypatch, model, t, route, na
     if t != 'P1' or route == 'node':
         assert np.array_equal(full['E'], E_dp)
     # 2. return map on the kernel's strain, 3. assembly of the kernel's ds and s
-    _check_points(model, full, ep, full['E'], Ep, mats, fref.z_of(e0, field, scale), accept, what)
+    _check_points(model, full, ep, full['E'], Ep, mats, fref.z_of(e0, field, scale), accept, what, curve=curve)
     _check_assembly(t, route, full, elem, coord, tab, pattern, what)
 
 
@@ -198,6 +214,7 @@ def _poisoned(fep, monkeypatch, model, t, bad):
         if model != 'dp':
             ctx.set_model(model)
         ctx.set_materials(*mats)
+        _set_curve(ctx, model, c['curve'])
         pattern = ctx.pattern()
 
         def run(f):
@@ -265,10 +282,41 @@ def _dev_field_return_map(fep, model, e, order, p, e0, field, scale, mats, accep
             'n_apex': int(k[1]), 'ep': None if pd is None else pd.cpu().numpy()}
 
 
+def _refused(fep, n):
+    import torch
+    E, Ep, mats, e0, field = fcases.mesh_free('vmi', n, 0)
+    dev = torch.device('cuda', 0)
+    up = lambda v: torch.from_numpy(np.array(v, dtype=np.float64, order='C')).to(dev)     # noqa: E731
+    ed, pd, fd, md = up(E), up(Ep), up(field), [up(m) for m in mats]
+    S, DS = torch.full((4, n), 7.0, dtype=torch.float64, device=dev), torch.full((9, n), 7.0, dtype=torch.float64, device=dev)
+    ind, cnt = torch.full((n,), 7, dtype=torch.uint8, device=dev), torch.full((2,), -1, dtype=torch.int64, device=dev)
+    e0v = np.ascontiguousarray(e0, dtype=np.float64).ravel()
+    assert fep.hotpath.MODELS['vmi'] == 5
+    for accept in (0, 1):
+        rc = fep.lib().fep_return_map_field_dev(5, 0, torch.cuda.current_stream().cuda_stream, n, ed.data_ptr(), 1, n,
+                                                e0v.ctypes.data_as(ctypes.c_void_p), fd.data_ptr(), fcases.SCALE, pd.data_ptr(),
+                                                *(m.data_ptr() for m in md), accept, S.data_ptr(), DS.data_ptr(), ind.data_ptr(),
+                                                cnt.data_ptr())
+        torch.cuda.synchronize()
+        assert rc == -1                                                                   # FEP_EINVAL
+        assert bool((S == 7.0).all()) and bool((DS == 7.0).all()) and bool((ind == 7).all()) and cnt.tolist() == [-1, -1]
+        assert np.array_equal(pd.cpu().numpy(), Ep) and np.array_equal(fd.cpu().numpy(), field)
+        ep_h = Ep.copy()
+        with pytest.raises(ValueError):
+            fep.construct_constitutive_problem_field('vmi', E, field, ep_h, *mats, apply_plastic_strain=bool(accept), e0=e0,
+                                                     e0_scale=fcases.SCALE)
+        assert np.array_equal(ep_h, Ep)
+
+
 @pytest.mark.parametrize('model', fcases.MODELS)
 @pytest.mark.parametrize('n', fcases.MESH_FREE_N)
 def test_mesh_free_field_return_map(fep, model, n):
-    """fep_return_map_field_dev and _host: both strain orders, accept on and off, with and without the uniform part."""
+    """fep_return_map_field_dev and _host: both strain orders, accept on and off, with and without the uniform part.  The pair
+    has no place for a curve and refuses 'vmi' (a field reaches that model through a context's step): FEP_EINVAL, nothing
+    written."""
+    if model == 'vmi':
+        _refused(fep, n)
+        return
     for seed in range(8):                                               # the first draw without a point under the floors
         E, Ep, mats, e0, field = fcases.mesh_free(model, n, seed)
         o = fref.return_map(model, E, Ep, mats, fref.z_of(e0, field, fcases.SCALE), False)

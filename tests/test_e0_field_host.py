@@ -24,6 +24,7 @@ POINT_CASES = sorted({(m, t, n) for m, t, _, n in fcases.grid()})
 @pytest.mark.parametrize('model,t,name', POINT_CASES)
 def test_case_meets_its_conditions(model, t, name):
     c = fcases.build(model, t, name)
+    assert (c['curve'] is None) == (fcases.curve_id(model, t, name) is None)
     n = c['field'].shape[1]
     assert c['field'].shape == (4, n) == c['ep'].shape and c['draw'] < fcases.MAX_DRAWS
     assert (c['e0'] is None) == (c['scale'] == 1.0)
@@ -32,6 +33,14 @@ def test_case_meets_its_conditions(model, t, name):
         assert n % fcases.BLOCK == {'block255': fcases.BLOCK - nq, 'block256': 0, 'block257': nq}[name] % fcases.BLOCK
     # every row of the field differs from every other at every point: no stride or index error can cancel
     assert len(np.unique(c['field'])) == 4 * n
+
+
+def test_every_type_meets_a_curve_of_several_segments_and_the_default():
+    for t in fcases.TYPES:
+        ids = [fcases.curve_id('vmi', t, n) for n in fcases.names(t)]
+        assert len(set(ids)) == 4 and ({2, 3} & set(ids)), (t, ids)
+    assert {fcases.curve_id('vmi', t, n) for t in fcases.TYPES for n in fcases.names(t)} == {0, 1, 2, 3, None}
+    assert all(fcases.curve_id(m, t, n) is None for m, t, _, n in fcases.grid() if m != 'vmi')
 
 
 def test_grid_covers_flags_for_every_model():
@@ -45,10 +54,11 @@ def test_grid_covers_flags_for_every_model():
 def test_restatement_on_constant_field_is_the_existing_one_bit_for_bit(model, accept):
     E, ep, mats, e0, _ = fcases.mesh_free(model, 257, 0)
     z = np.repeat(e0, 257, axis=1)
+    crv = fcases.cases.vmi_cases.curve(fcases.MESH_FREE_CURVE) if model == 'vmi' else None
     for p in (ep, None):
-        got = fref.return_map(model, E, p, mats, z, accept, per_point=True)
-        grouped = fref.return_map(model, E, p, mats, z, accept)
-        ref = fref.plain_return_map(model, E, p, mats, e0, accept)
+        got = fref.return_map(model, E, p, mats, z, accept, per_point=True, curve=crv)
+        grouped = fref.return_map(model, E, p, mats, z, accept, curve=crv)
+        ref = fref.plain_return_map(model, E, p, mats, e0, accept, crv)
         assert 0 < ref['ind_p'].sum() < 257
         for k in ('s', 'ds', 'ind_p', 'ep'):
             assert np.array_equal(got[k], ref[k]) and np.array_equal(grouped[k], ref[k]), k

@@ -297,6 +297,19 @@ def _model_mesh(t, name):
     return meshes.named(t, name, np.random.default_rng(0))[:2]
 
 
+def _curve(model):
+    """'vmi' runs on the eight-segment curve of its fixture (kappa of the state spread over all of it); rule 6 then covers
+    row 3 of ep, kappa, like the other three: _accepting compares whole columns."""
+    import vmi_cases
+    return vmi_cases.curve(2) if model == 'vmi' else None
+
+
+def _set_curve(ctx, model):
+    if model == 'vmi':
+        ctx.set_hardening(*_curve(model))
+        assert 'vmi_kernel' in ctx.kernel_names(0) and len(ctx.hardening[0]) == 8
+
+
 MODEL_MESHES = [('P1', 'node', 'rect53x10'), ('P1', 'node', 'tsx'), ('P2', 'default', _first_structured('P2')),
                 ('P2', 'coo', _first_structured('P2')), ('Q2', 'default', _first_structured('Q2'))]
 
@@ -306,11 +319,12 @@ MODEL_MESHES = [('P1', 'node', 'rect53x10'), ('P1', 'node', 'tsx'), ('P2', 'defa
 def test_model_step_forms_write_their_outputs_and_nothing_else(fep, monkeypatch, model, t, route, name):
     elem, coord = _model_mesh(t, name)
     rng = np.random.default_rng(zlib.crc32(f'footprint {model} {t} {name}'.encode()))
-    U, Ep, mats, e0 = model_step_cases.state(model, t, elem, coord, rng)
+    U, Ep, mats, e0 = model_step_cases.state(model, t, elem, coord, rng, _curve(model))
     ctx = _context(fep, monkeypatch, route, elem, coord)
     try:
         ctx.set_model(model)
         ctx.set_materials(*mats)
+        _set_curve(ctx, model)
         A = _all_forms(ctx, f'{model} {t} {route} {name}', U, Ep, e0=e0, forms='ABFH')
         n_plastic = int(A['ind_p'].sum())
         assert 0 < n_plastic < ctx.n_int
@@ -327,11 +341,12 @@ def test_field_step_forms_write_their_outputs_and_nothing_else(fep, monkeypatch,
         from elem_ref import ElemRef
         U, Ep, mats, e0 = e0_field_cases.dp_state(elem, coord, ElemRef(elem, coord, fep.element_tables(t)), rng)
     else:
-        U, Ep, mats, e0 = model_step_cases.state(model, t, elem, coord, rng)
+        U, Ep, mats, e0 = model_step_cases.state(model, t, elem, coord, rng, _curve(model))
     ctx = _context(fep, monkeypatch, route, elem, coord)
     try:
         ctx.set_model(model)
         ctx.set_materials(*mats)
+        _set_curve(ctx, model)
         field = e0_field_cases.eps_y(model) * rng.normal(0, 0.2, size=(4, ctx.n_int))
         A = _all_forms(ctx, f'field {model} {t} {route} {name}', U, Ep, e0=e0, forms='AB', field=field,
                        scale=e0_field_cases.SCALE)

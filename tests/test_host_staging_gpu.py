@@ -178,6 +178,10 @@ def big():
 def use_model(ctx, model):
     ctx.set_model(model)
     ctx.set_materials(*sc.model_materials(model, ctx.n_int))
+    if model == 'vmi':
+        import vmi_cases
+        ctx.set_hardening(*vmi_cases.curve(sc.VMI_CURVE))
+        assert 'p1_point_vmi_kernel' in ctx.kernel_names(0)
 
 
 def dev_step(big, model, want, accept=False, field=None, scale=1.0, e0=None):
@@ -188,7 +192,7 @@ def dev_step(big, model, want, accept=False, field=None, scale=1.0, e0=None):
         use_model(ctx, model)
         r = sc.step_dev(ctx, sc.model_scale(model) * big['U'], np.zeros((4, ctx.n_int)), accept, want, e0=e0, field=field, scale=scale)
         n0, n1 = (int(v) for v in r['counts'])
-        if model == 'vm':                                   # {plastic points, 0}
+        if model in ('vm', 'vmi'):                          # {plastic points, 0}
             assert 0 < n0 < ctx.n_int and n1 == 0, ('the generator', model, n0, n1)
         else:                                               # a failure here blames the generator, not the engine
             assert n0 > 0 and n1 > 0 and n0 + n1 < ctx.n_int, ('the generator', model, n0, n1)
@@ -235,7 +239,7 @@ def test_step_planar_displacement_is_the_interleaved_one(big):
     same_step(host_step(big, 'dp', want, planar=True, kind='pinned'), ref, want)
 
 
-@pytest.mark.parametrize('model', ['vm', 'mc'])
+@pytest.mark.parametrize('model', sc.STEP_MODELS)
 def test_step_of_the_other_models_on_the_large_mesh(big, model):
     """set_model on the same context, every output (E comes from the model's own point kernel), accepting."""
     want = sc.STEP_KEYS

@@ -4,7 +4,9 @@ checked on the CPU by test_nonfinite_host.py, on the kernels.  Every poison is a
 index, table and size stays valid.
 
   1. never hidden      von Mises, Mohr-Coulomb: a point whose trial strain has a NaN component is elastic, has the elastic
-                       tangent and a NaN in its stress, and no counter counts it.  Drucker-Prager: what the oracle does
+                       tangent and a NaN in its stress, and no counter counts it.  Drucker-Prager: what the oracle does.
+                       'vmi' (von Mises with isotropic hardening): the same, and a NaN or infinite kappa (row 3 of its
+                       state) counts like a NaN strain, in the mesh-free kernel and inside a step on every route
   2. contained         an output with no poisoned contributor equals the clean call's, bit for bit
   3. reported promptly fep_solver_pcg_dev / fep_solver_amg_pcg_dev answer FEP_OK, state 2, at the first read-back
   4. leaves no trace   the same clean call on the same context, solver and hierarchy afterwards returns the bits it returned before
@@ -15,7 +17,8 @@ per point for the return maps, C_K of test_element_route_gpu.py for K, 1e-9 for 
 Where this module departs from a literal reading of what was asked of it, and why (each from the code):
   - finiteness against the Drucker-Prager oracle and the von Mises restatement is compared up to the structural zeros of their
     matrix products (nonfinite_cases.masks_agree): dev @ E and 2 Dev G + Vol K multiply zeros by the poison, the kernels write
-    dv2 = Et2 / 2, d02 = d12 = 0, d22 = G out.  The Mohr-Coulomb kernel and restatement agree entry for entry;
+    dv2 = Et2 / 2, d02 = d12 = 0, d22 = G out.  The Mohr-Coulomb kernel and restatement agree entry for entry; the 'vmi'
+    restatement needs the allowance like the von Mises one (shown on the CPU by test_nonfinite_host.py);
   - a Krylov solve zeroes x before it iterates (pcg_init_kernel / mg_init; include/fep.h: "x = 0 on entry is implied"), so
     "x as it was" is asserted of the zero vector it is handed: after a breakdown at the first read-back x holds +0.0 in every
     entry, no iterate and no NaN;
@@ -36,6 +39,7 @@ from conftest import dp_materials, relerr, relerr_points
 from elem_ref import ratio
 from footprint import scrub
 from model_ref import dev_return_map
+from vmi_cases import dev_return_map as vmi_dev_return_map
 from routes import assert_route
 from test_element_route_gpu import C_K, C_RECORD
 from test_return_map_mp_gpu import _host
@@ -52,12 +56,38 @@ POINT_KEYS = ('s', 'ds', 'ind_p', 'ep')
 # ---------------------------------------------------------------------------------------
 def _call(fep, entry, model, e, order, p, e0, mats, accept):
     """-> s, ds, ind_p, ep (the plastic strain after the call), n_smooth, n_apex of the `_host` or `_dev` entry point."""
+    if model == 'vmi':                                                      # its entry points take the curve
+        crv, z = nf.point_curve(model), None if e0 is None else np.asarray(e0, dtype=float).reshape(4, 1)
+        if entry == 'host':
+            return _vmi_host(fep, e, order, p, z, mats, crv, accept)
+        return vmi_dev_return_map(e, order, p, z, [np.asarray(m) for m in mats], crv, accept)
     if entry == 'host':
         ev, ph = (np.asfortranarray(e) if order == 'F' else np.ascontiguousarray(e)), np.array(p, dtype=float)
         r = _host(fep, model, ev, ph, e0, [np.ascontiguousarray(m) for m in mats], accept)
         return dict(s=np.array(r['s']), ds=np.array(r['ds']), ind_p=np.asarray(r['ind_p']).astype(bool), ep=ph,
                     n_smooth=int(r['n_smooth']), n_apex=int(r['n_apex']))
     return dev_return_map(fep, model, e, order, p, e0, [np.asarray(m) for m in mats], accept)
+
+
+def _vmi_host(fep, e, order, p, z, mats, crv, accept):
+    """fep_return_map_vmi_host through the C ABI: the Python wrapper checks 2G + a + slope > 0 against the materials first and
+    so refuses a NaN shear modulus or hardening modulus with a ValueError, before any kernel sees it."""
+    n = np.shape(e)[1]
+    ev = np.ascontiguousarray(np.asarray(e, dtype=float).T if order == 'F' else e, dtype=np.float64)
+    ps, cs = (3, 1) if order == 'F' else (1, n)
+    ph = np.array(p, dtype=np.float64, order='C')
+    md = [np.ascontiguousarray(m, dtype=np.float64) for m in mats]
+    kap, slo = (np.ascontiguousarray(v, dtype=np.float64) for v in crv)
+    s, ds, ind, cnt = np.zeros((4, n)), np.zeros((9, n)), np.zeros(n, dtype=np.uint8), np.full(2, -1, dtype=np.int64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)                             # noqa: E731
+    rc = fep.lib().fep_return_map_vmi_host(0, n, vp(ev), ps, cs, None if z is None else vp(np.ascontiguousarray(z).ravel()),
+                                           vp(ph), *(vp(m) for m in md), kap.size, vp(kap), vp(slo), int(accept), vp(s), vp(ds),
+                                           vp(ind), vp(cnt))
+    assert rc == 0
+    if np.isnan(md[0]).any():
+        with pytest.raises(ValueError):
+            fep.construct_constitutive_problem_vmi(np.asarray(e, dtype=float), ph.copy(), *md, crv)
+    return dict(s=s, ds=ds, ind_p=ind.astype(bool), ep=ph, n_smooth=int(cnt[0]), n_apex=int(cnt[1]))
 
 
 def _finite_close(got, ref, both):
@@ -98,12 +128,12 @@ def _rule_1(model, got, nan, mats):
 @pytest.mark.parametrize('order', ['C', 'F'])
 @pytest.mark.parametrize('model', nf.MODELS)
 def test_return_maps_with_poisoned_points(fep, model, order):
-    for k in range(len(nf.LAUNCHES)):
+    for k in range(len(nf.launches(model))):
         c = nf.point_launch(model, k)
         (e, p, mats), (pe, pp, pm) = c['clean'], c['poisoned']
         clean = np.ones(nf.N_POINTS, dtype=bool)
         clean[c['lanes']] = False
-        nan = nf.trial_strain_nan(pe, pp)
+        nan = nf.trial_strain_nan(pe, pp, model=model)
         for accept in (False, True):
             ref = nf.restate(model, pe, pp, pm, None, accept)
             for entry in ('host', 'dev'):
@@ -152,7 +182,7 @@ def test_return_maps_with_a_nan_initial_strain(fep, model):
 # 2. the step of a context
 # ---------------------------------------------------------------------------------------
 def _step_cases():
-    return [(m, t, kind, r) for m in nf.MODELS for t, kind in nf.mesh_cases() for r in msc.ROUTES[t]]
+    return [(m, t, kind, r) for m, t, kind in nf.model_mesh_cases() for r in msc.ROUTES[t]]
 
 
 def _same(a, b, keys=('E', 's', 'ds', 'ind_p', 'F')):
@@ -160,7 +190,7 @@ def _same(a, b, keys=('E', 's', 'ds', 'ind_p', 'F')):
         and (a['n_smooth'], a['n_apex']) == (b['n_smooth'], b['n_apex'])
 
 
-def _flags_and_counters(model, got, Ep, mats, e0, dirty):
+def _flags_and_counters(model, got, Ep, mats, e0, dirty, curve=None):
     """ind_p and both counters against the restatement on the kernel's E, as test_element_route_gpu.py (Drucker-Prager) and
     test_model_step_routes_gpu.py (points inside the floors left out) compare them."""
     assert got['n_smooth'] + got['n_apex'] == int(got['ind_p'].sum())
@@ -169,11 +199,11 @@ def _flags_and_counters(model, got, Ep, mats, e0, dirty):
         assert np.array_equal(got['ind_p'], o['ind_p']) and (got['n_smooth'], got['n_apex']) == (o['n_smooth'], o['n_apex'])
         return
     with np.errstate(all='ignore'):
-        o = msc.return_map(model, got['E'], Ep, mats, e0, False)
-        excl = msc.excluded(model, o, mats)
+        o = msc.return_map(model, got['E'], Ep, mats, e0, False, curve)
+        excl = msc.excluded(model, o, mats, curve)
     assert not excl[dirty].any()
     keep = ~excl
-    msc.check_conditions(model, o, excl)
+    msc.check_conditions(model, o, excl, curve)
     assert np.array_equal(got['ind_p'][keep], o['ind_p'][keep])
     n_out = int(excl.sum())
     assert int(got['ind_p'][keep].sum()) == int(o['ind_p'][keep].sum())
@@ -182,8 +212,11 @@ def _flags_and_counters(model, got, Ep, mats, e0, dirty):
 
 @pytest.mark.parametrize('model,t,kind,route', _step_cases())
 def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, route):
+    """(and, the kind 'kappa' of 'vmi', with a clean displacement and a NaN kappa at one point: Ep_bad; for every other kind
+    Ep_bad is Ep)"""
     c = nf.mesh_case(model, t, kind)
     U, U_bad, Ep, mats, e0, dirty, dofs = (c[k] for k in ('U', 'U_bad', 'ep', 'mats', 'e0', 'points', 'dofs'))
+    Ep_bad, curve = c['ep_bad'], c['curve']
     if route in ('default', 'node'):
         monkeypatch.delenv('FEP_ROUTE', raising=False)
     else:
@@ -195,19 +228,21 @@ def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, rou
         if model != 'dp':
             ctx.set_model(model)
         ctx.set_materials(*mats)
+        if curve is not None:
+            ctx.set_hardening(*curve)
         kw = {} if e0 is None else {'e0': e0}
         first = ctx.step(U, Ep.copy(), want=EVERY, **kw)
-        bad = ctx.step(U_bad, Ep.copy(), want=EVERY, **kw)
+        bad = ctx.step(U_bad, Ep_bad.copy(), want=EVERY, **kw)
         # scrub between the forms: none may pass its pin with what the call before left in the context's device buffers
         scrub(ctx, U_bad, Ep, kw)
-        kf = ctx.step(U_bad, Ep.copy(), want=('K', 'F'), **kw)
+        kf = ctx.step(U_bad, Ep_bad.copy(), want=('K', 'F'), **kw)
         scrub(ctx, U_bad, Ep, kw)
-        k_only = ctx.step(U_bad, Ep.copy(), want=('K',), **kw)
+        k_only = ctx.step(U_bad, Ep_bad.copy(), want=('K',), **kw)
         scrub(ctx, U_bad, Ep, kw)
-        f_only = ctx.step(U_bad, Ep.copy(), want=('F',), **kw)
+        f_only = ctx.step(U_bad, Ep_bad.copy(), want=('F',), **kw)
         scrub(ctx, U_bad, Ep, kw)
         K2, F2 = ctx.assemble(bad['ds'], bad['s'])
-        ep_bad, ep_good = Ep.copy(), Ep.copy()
+        ep_bad, ep_good = Ep_bad.copy(), Ep.copy()
         scrub(ctx, U_bad, Ep, kw)
         acc_bad = ctx.step(U_bad, ep_bad, apply_plastic_strain=True, want=('ind_p',), **kw)
         scrub(ctx, U, Ep, kw)
@@ -223,7 +258,11 @@ def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, rou
     assert np.array_equal(bad['F'][~dofs], first['F'][~dofs])
     assert np.array_equal(bad['K'].data[~entries], first['K'].data[~entries])
     # rule 1: the dirty locations
-    assert np.isnan(bad['E'][:, dirty]).all() and np.isnan(bad['s'][:, dirty]).any(axis=0).all()
+    if kind == 'kappa':                                                     # the strain is clean: the poison enters behind it
+        assert np.array_equal(bad['E'], first['E']) and dirty.sum() == 1
+    else:
+        assert np.isnan(bad['E'][:, dirty]).all()
+    assert np.isnan(bad['s'][:, dirty]).any(axis=0).all()
     assert not bad['ind_p'][dirty].any()
     assert relerr_points(bad['ds'][:, dirty], nf.elastic_tangent(model, [np.asarray(m)[dirty] for m in mats])) <= nf.TOL_PT
     assert np.array_equal(np.isnan(bad['F']), dofs) and np.isfinite(bad['F'][~dofs]).all()
@@ -237,8 +276,8 @@ def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, rou
         with np.errstate(invalid='ignore'):
             Kx, W_K, _, _ = nf.elem_ref(c, t, pattern).assemble(bad['ds'], None, widened=True)
         assert ratio(bad['K'].data, Kx, W_K) <= C_K[t] + C_RECORD
-    _flags_and_counters(model, bad, Ep, mats, e0, dirty)
-    _flags_and_counters(model, first, Ep, mats, e0, dirty)
+    _flags_and_counters(model, bad, Ep_bad, mats, e0, dirty, curve)
+    _flags_and_counters(model, first, Ep, mats, e0, dirty, curve)
     assert bad['n_smooth'] + bad['n_apex'] == int(first['ind_p'][~dirty].sum())     # no dirty point is counted
     assert bad['n_smooth'] <= first['n_smooth'] and bad['n_apex'] <= first['n_apex']
     # the partial steps and assemble(ds, s) of the poisoned state
@@ -250,7 +289,7 @@ def test_step_with_a_poisoned_displacement(fep, monkeypatch, model, t, kind, rou
         assert (r['n_smooth'], r['n_apex']) == (bad['n_smooth'], bad['n_apex'])
     # accepting: no NaN enters the state (module docstring)
     assert np.array_equal(acc_bad['ind_p'], bad['ind_p']) and np.array_equal(acc_good['ind_p'], first['ind_p'])
-    assert np.array_equal(ep_bad[:, dirty], Ep[:, dirty]) and np.array_equal(ep_bad[:, ~dirty], ep_good[:, ~dirty])
+    assert np.array_equal(ep_bad[:, dirty], Ep_bad[:, dirty], equal_nan=True) and np.array_equal(ep_bad[:, ~dirty], ep_good[:, ~dirty])
     assert first['ind_p'].any() and not np.array_equal(ep_good, Ep)
     # rule 4
     assert _same(last, first)

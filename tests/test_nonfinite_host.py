@@ -9,7 +9,11 @@ with f <= 0 such a point fell through every comparison to the apex and came back
 Drucker-Prager keeps what the reference does, recorded here from the oracle: a NaN in a strain component gives an elastic
 point with a NaN stress (a NaN in the shear strain alone is lost to the branch decision in the clamp of the squared norm,
 DP:676, and such a point is judged by its volume change; point 0 is elastic by it), a +Inf in e[0] the apex with the finite
-stress c / eta."""
+stress c / eta.  'vmi' (von Mises with isotropic hardening): the von Mises rule, with kappa as a fifth component of the trial
+state; a NaN or an infinite kappa makes the point elastic with a NaN stress.  Its restatement's finiteness masks, settled here:
+it is NaN in s[2] and in the shear entries of the tangent where only a normal strain, kappa or a material is poisoned (it
+multiplies the zeros of (1, 1, 0, 1) and of 2 Dev G + Vol K by the poison), where the kernel's formulas s2 = 2G dv2, d02 = d12 =
+0 are finite: it needs the structural-zero allowance of nonfinite_cases.masks_agree, as von Mises does and Mohr-Coulomb does not."""
 import numpy as np
 import pytest
 import scipy.sparse as ssp
@@ -32,24 +36,25 @@ def _rule_1(model, r, bad, mats):
     assert r['n_smooth'] + r['n_apex'] == int(r['ind_p'].sum()) == int(r['ind_p'][~bad].sum())    # counted nowhere
 
 
-@pytest.mark.parametrize('k', range(len(nf.LAUNCHES)))
-@pytest.mark.parametrize('model', nf.MODELS)
+@pytest.mark.parametrize('model,k', nf.launch_ids())
 def test_point_launches_reach_what_they_exist_for(model, k):
     c = nf.point_launch(model, k)
     n = nf.N_POINTS
-    assert n == 3 * 256 + 1 and set(c['lanes']) == {0, 63, 64, 255, 256, n - 1}
-    assert len(set(c['poisons'])) == len(c['lanes']) == 6 and set(sum(nf.LAUNCHES, ())) == set(nf.POISONS)
+    n_poisons = 2 if (model, k) == ('vmi', 2) else 6
+    assert n == 3 * 256 + 1 and set(c['lanes']) == ({0, 63, 64, 255, 256, n - 1} if n_poisons == 6 else {255, 256})
+    assert len(set(c['poisons'])) == len(c['lanes']) == n_poisons and set(sum(nf.LAUNCHES, ())) == set(nf.POISONS)
+    assert nf.launches(model)[:2] == nf.LAUNCHES and len(nf.launches(model)) == (3 if model == 'vmi' else 2)
     assert len(c['lanes']) <= nf.MAX_POISONED_POINTS * n
     clean = np.ones(n, dtype=bool)
     clean[c['lanes']] = False
-    assert (np.bincount(c['cls'][clean], minlength=3)[:2 if model == 'vm' else 3] > 0).all()
+    assert (np.bincount(c['cls'][clean], minlength=3)[:2 if model in ('vm', 'vmi') else 3] > 0).all()
     if model == 'mc':
         from mc_ref import mc_return_map
         assert (np.bincount(mc_return_map(*c['clean'][:2], *c['clean'][2])['branch'][clean], minlength=5) > 0).all()
     (e, p, mats), (pe, pp, pm) = c['clean'], c['poisoned']
     for a, b in zip([e, p] + mats, [pe, pp] + pm):                           # the poison and nothing else
         assert np.array_equal(a[..., clean], b[..., clean])
-    assert sum(int((~np.isfinite(a)).sum()) for a in [pe, pp] + pm) == 6
+    assert sum(int((~np.isfinite(a)).sum()) for a in [pe, pp] + pm) == n_poisons
     for accept in (False, True):
         good, bad = nf.restate(model, e, p, mats, None, accept), nf.restate(model, pe, pp, pm, None, accept)
         for key in ('s', 'ds', 'ind_p', 'ep'):                              # the restatement contains the poison (rule 2)
@@ -60,10 +65,25 @@ def test_point_launches_reach_what_they_exist_for(model, k):
                 assert np.array_equal(good[key][..., clean], bad[key][..., clean]), key
         assert np.isfinite(good['s']).all() and np.isfinite(good['ds']).all()
         if model != 'dp':
-            nan = nf.trial_strain_nan(pe, pp)
-            assert not nan[clean].any() and nan.sum() == sum(arr in 'ep' and v != v for arr, _, v in c['poisons'])
+            nan = nf.trial_strain_nan(pe, pp, model=model)
+            assert not nan[clean].any() and nan.sum() == sum((arr in 'ep' and v != v) or (model == 'vmi' and (arr, row) == ('p', 3))
+                                                             for arr, row, v in c['poisons'])
             _rule_1(model, bad, nan, pm)
-    if model == 'vm':                                                       # nonfinite_cases.vm_infinite: the restatement's side
+            if model == 'vmi':                                              # a non-finite kappa leaves the column of ep as it went in
+                assert np.array_equal(bad['ep'][:, nan], pp[:, nan], equal_nan=True)
+    if model == 'vmi':                                                      # the restatement's finiteness masks (module docstring)
+        bad = nf.restate(model, pe, pp, pm)
+        for lane, (arr, row, val) in zip(c['lanes'], c['poisons']):
+            if (arr, row) in (('e', 0), ('e', 1), ('p', 0), ('p', 3)):      # the shear strain itself is finite
+                kernel_s2 = 2 * pm[0][lane] * ((pe[2, lane] - pp[2, lane]) / 2)
+                assert np.isnan(bad['s'][2, lane]) and np.isfinite(kernel_s2)
+                assert not nf.masks_agree('mc', {'s': np.where(np.arange(4) == 2, kernel_s2, bad['s'][:, lane]).reshape(4, 1)},
+                                          {'s': bad['s'][:, [lane]]}, 's')[0]
+                assert nf.masks_agree(model, {'s': np.where(np.arange(4) == 2, kernel_s2, bad['s'][:, lane]).reshape(4, 1)},
+                                      {'s': bad['s'][:, [lane]]}, 's')[0]
+            if arr == 'm' and row in (0, 1):                                # 2 Dev G + Vol K: the zeros of Dev and Vol times NaN
+                assert np.isnan(bad['ds'][[2, 5, 6, 7], lane]).all()
+    if model in ('vm', 'vmi'):                                              # nonfinite_cases.vm_infinite: the restatement's side
         odd, bad = nf.vm_infinite(model, pe, pp), nf.restate(model, pe, pp, pm)
         assert odd.sum() == sum(arr == 'e' and abs(v) == nf.INF for arr, _, v in c['poisons']) and not odd[clean].any()
         assert not bad['ind_p'][odd].any() and np.isnan(bad['s'][:, odd]).all() and np.isfinite(bad['ds'][:, odd]).all()
@@ -84,7 +104,7 @@ def test_a_nan_initial_strain_poisons_every_point(model):
     for row in range(4):
         e0 = np.array([1e-5, -2e-5, 3e-5, 1e-5])
         e0[row] = nf.NAN
-        assert nf.trial_strain_nan(e, p, e0).all()
+        assert nf.trial_strain_nan(e, p, e0, model=model).all()
         for accept in (False, True):
             r = nf.restate(model, e, p, mats, e0, accept)
             if model != 'dp':
@@ -109,10 +129,42 @@ def test_the_structural_zeros_are_the_only_disagreement_allowed():
                 assert not nf.masks_agree(model, got, ref, key)[0]
 
 
-@pytest.mark.parametrize('t,kind', nf.mesh_cases())
-@pytest.mark.parametrize('model', nf.MODELS)
+@pytest.mark.parametrize('t', nf.msc.TYPES)
+def test_a_nan_kappa_in_a_mesh_step_reaches_what_it_exists_for(t):
+    """The 'kappa' kind of 'vmi': one point of one interior element, a clean strain everywhere; on the restatement the point is
+    elastic with the elastic tangent and a NaN stress, F is NaN at the DOFs of that element alone and K finite, changed at most
+    in that element's blocks."""
+    c = nf.mesh_case('vmi', t, 'kappa')
+    k, nq = c['k'], nf.msc.NQ[t]
+    assert c['points'].sum() == 1 and c['points'][k] and c['elements'].sum() == 1 and c['elements'][k // nq]
+    assert np.array_equal(c['U_bad'], c['U']) and np.isnan(c['ep_bad'][3, k]) and np.isnan(c['ep_bad']).sum() == 1
+    assert np.array_equal(np.delete(c['ep_bad'], k, axis=1), np.delete(c['ep'], k, axis=1))
+    lo, hi = c['coord'].min(axis=1, keepdims=True), c['coord'].max(axis=1, keepdims=True)
+    xy = c['coord'][:, c['elem'][:, k // nq]]
+    assert ((xy > lo) & (xy < hi)).all()                                    # an interior element
+    ref = nf.elem_ref(c, t)
+    E, _ = ref.strain(c['U'])
+    assert nf.trial_strain_nan(E, c['ep_bad'], c['e0'], model='vmi').sum() == 1
+    good = nf.restate('vmi', E, c['ep'], c['mats'], c['e0'], curve=c['curve'])
+    for accept in (False, True):
+        r = nf.restate('vmi', E, c['ep_bad'], c['mats'], c['e0'], accept, curve=c['curve'])
+        _rule_1('vmi', r, c['points'], c['mats'])
+        assert np.array_equal(r['ind_p'][~c['points']], good['ind_p'][~c['points']])
+        assert np.isnan(r['s'][[0, 1, 3], k]).all() and np.array_equal(r['ep'][:, k], c['ep_bad'][:, k], equal_nan=True)
+        for key in ('s', 'ds'):
+            assert np.array_equal(r[key][:, ~c['points']], good[key][:, ~c['points']])
+    with np.errstate(invalid='ignore'):
+        K, _, F, _ = ref.assemble(r['ds'], r['s'])
+    assert np.array_equal(np.isnan(F), c['dofs']) and np.isfinite(K).all()
+    dirty = nf.dirty_entries(c, ref.pattern())
+    Kc, _, _, _ = ref.assemble(good['ds'], None)
+    assert np.array_equal(K[~dirty], Kc[~dirty])
+
+
+@pytest.mark.parametrize('model,t,kind', [c for c in nf.model_mesh_cases() if c[2] != 'kappa'])
 def test_mesh_cases_reach_what_they_exist_for(model, t, kind):
     c = nf.mesh_case(model, t, kind)
+    assert c['ep_bad'] is c['ep']
     elem, n_e = c['elem'], c['elem'].shape[1]
     assert n_e == 257 and (n_e * nf.msc.NQ[t]) % 256 == nf.msc.NQ[t]
     n_dirty = int(c['elements'].sum())
@@ -125,8 +177,8 @@ def test_mesh_cases_reach_what_they_exist_for(model, t, kind):
     assert np.array_equal(np.isnan(E), np.broadcast_to(c['points'], E.shape)) and np.isfinite(E[:, ~c['points']]).all()
     E_clean, _ = ref.strain(c['U'])
     assert np.array_equal(E[:, ~c['points']], E_clean[:, ~c['points']])
-    good = nf.restate(model, E_clean, c['ep'], c['mats'], c['e0'])
-    r = nf.restate(model, E, c['ep'], c['mats'], c['e0'])
+    good = nf.restate(model, E_clean, c['ep'], c['mats'], c['e0'], curve=c['curve'])
+    r = nf.restate(model, E, c['ep'], c['mats'], c['e0'], curve=c['curve'])
     _rule_1(model, r, c['points'], c['mats'])
     assert np.array_equal(r['ind_p'][~c['points']], good['ind_p'][~c['points']])
     assert np.isnan(r['s'][:, c['points']]).all()
