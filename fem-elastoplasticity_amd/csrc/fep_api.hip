@@ -15,6 +15,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace fep;
@@ -104,7 +105,8 @@ struct fep_ctx {
     Route route = Route::Coo;
     bool have_materials = false;
     int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
-    uint2* vm_blk = nullptr;                            // FEP_MODEL_VM / _MC: per-workgroup plastic counts of the point kernel
+    uint2* point_blk = nullptr;                         // step_model: per-workgroup branch counters of the point stage (every
+                                                        // model but Drucker-Prager, and Drucker-Prager with a field)
     Hard hard = flat_hard();                            // FEP_MODEL_VMI: fep_ctx_set_hardening (one segment of slope 0 until then)
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
@@ -230,6 +232,17 @@ template <class F> static int with_type(int elem_type, F&& f) {
         default: return FEP_EINVAL;
     }
 }
+// f(int_c<FEP_MODEL_*>) for the material model `model`; FEP_EINVAL for an id that is none (4 is unassigned)
+template <class F> static int with_model(int model, F&& f) {
+    switch (model) {
+        case FEP_MODEL_DP: return f(int_c<FEP_MODEL_DP>{});
+        case FEP_MODEL_VM: return f(int_c<FEP_MODEL_VM>{});
+        case FEP_MODEL_MC: return f(int_c<FEP_MODEL_MC>{});
+        case FEP_MODEL_VMPS: return f(int_c<FEP_MODEL_VMPS>{});
+        case FEP_MODEL_VMI: return f(int_c<FEP_MODEL_VMI>{});
+        default: return FEP_EINVAL;
+    }
+}
 template <class F> static int with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
 // A switch that only the ablation build varies: the product instantiates the value `Product` alone and refuses the other
 // one (FEP_ESTATE: a context the product never creates)
@@ -330,36 +343,80 @@ static E0 make_e0(const double* e0_h) {
     return z;
 }
 
-// The material models, one row each, indexed by FEP_MODEL_*: the tag a model puts into its kernels' names and its kernel of each
-// point-kernel family.  point_*_kernel<NP, NQ> has no Drucker-Prager row, that step being the fused element route: model - 1.
-constexpr int kModels = 4;
-static const char* const kModelTag[kModels] = {"", "vm_", "mc_", "vmps_"};
-static constexpr decltype(&return_map_kernel) kReturnMapKernel[kModels] = {return_map_kernel, return_map_vm_kernel, return_map_mc_kernel,
-                                                                                   return_map_vmps_kernel};
-static constexpr decltype(&p1_point_kernel) kP1PointKernel[kModels] = {p1_point_kernel, p1_point_vm_kernel, p1_point_mc_kernel,
-                                                                               p1_point_vmps_kernel};
-template <int NP, int NQ>
-static constexpr decltype(&point_vm_kernel<NP, NQ>) kPointKernel[kModels - 1] = {point_vm_kernel<NP, NQ>, point_mc_kernel<NP, NQ>,
-                                                                                    point_vmps_kernel<NP, NQ>};
-static_assert(FEP_MODEL_DP == 0 && FEP_MODEL_VM == 1 && FEP_MODEL_MC == 2 && FEP_MODEL_VMPS == kModels - 1, "table order");
-// The fifth model, FEP_MODEL_VMI, is in none of the tables: its kernels have a signature of their own (the hardening curve as
-// one more argument), so the launches below name them, and the tables stay dense with id 4 outside them, refused as before.
-static_assert(FEP_MODEL_VMI > kModels, "id 4 stays unassigned");
-static bool known_model(int model) { return (model >= 0 && model < kModels) || model == FEP_MODEL_VMI; }
-static const char* model_tag(int model) { return model == FEP_MODEL_VMI ? "vmi_" : kModelTag[model]; }
-// The same families with an initial-strain field (fep_*_field_*): every model has a row in each, Drucker-Prager too, so these
-// are indexed by the model itself.
-// (The mesh-free pair fep_return_map_field_* keeps its three models: FEP_MODEL_VMPS is refused there, include/fep.h.)
-constexpr int kFieldFreeModels = 3;
-static constexpr decltype(&return_map_field_kernel<FEP_MODEL_DP>) kReturnMapFieldKernel[kFieldFreeModels] = {
-    return_map_field_kernel<FEP_MODEL_DP>, return_map_field_kernel<FEP_MODEL_VM>, return_map_field_kernel<FEP_MODEL_MC>};
-static constexpr decltype(&p1_point_field_kernel<FEP_MODEL_DP>) kP1PointFieldKernel[kModels] = {
-    p1_point_field_kernel<FEP_MODEL_DP>, p1_point_field_kernel<FEP_MODEL_VM>, p1_point_field_kernel<FEP_MODEL_MC>,
-    p1_point_field_kernel<FEP_MODEL_VMPS>};
-template <int NP, int NQ>
-static constexpr decltype(&point_field_kernel<FEP_MODEL_DP, NP, NQ>) kPointFieldKernel[kModels] = {
-    point_field_kernel<FEP_MODEL_DP, NP, NQ>, point_field_kernel<FEP_MODEL_VM, NP, NQ>, point_field_kernel<FEP_MODEL_MC, NP, NQ>,
-    point_field_kernel<FEP_MODEL_VMPS, NP, NQ>};
+// The material models.  ModelKernels<FEP_MODEL_*> is the only place that names a model's kernels: the tag the model puts into
+// their names, whether they take its hardening curve (Hard, by value, as their last argument), and its kernel of each
+// point-kernel family -- mesh-free, P1, general <NP, NQ> -- plain (FIELD false) and with an initial-strain field (fep_*_field_*).
+// nullptr: the model has no such kernel and its launcher refuses the call.  Drucker-Prager's plain general step is the fused
+// element route, and the mesh-free field pair fep_return_map_field_* keeps its three models (include/fep.h).
+template <bool FIELD, class P, class F> static constexpr auto pick(P plain, F with_field) {
+    if constexpr (FIELD) return with_field; else return plain;
+}
+template <class K> constexpr bool no_kernel = std::is_null_pointer_v<K>;
+template <int MODEL> struct ModelKernels;
+template <> struct ModelKernels<FEP_MODEL_DP> {
+    static constexpr const char* tag = "";
+    static constexpr bool has_hard = false;
+    template <bool FIELD> static constexpr auto return_map = pick<FIELD>(return_map_kernel, return_map_field_kernel<FEP_MODEL_DP>);
+    template <bool FIELD> static constexpr auto p1_point = pick<FIELD>(p1_point_kernel, p1_point_field_kernel<FEP_MODEL_DP>);
+    template <bool FIELD, int NP, int NQ>
+    static constexpr auto point = pick<FIELD>(nullptr, point_field_kernel<FEP_MODEL_DP, NP, NQ>);
+};
+template <> struct ModelKernels<FEP_MODEL_VM> {
+    static constexpr const char* tag = "vm_";
+    static constexpr bool has_hard = false;
+    template <bool FIELD> static constexpr auto return_map = pick<FIELD>(return_map_vm_kernel, return_map_field_kernel<FEP_MODEL_VM>);
+    template <bool FIELD> static constexpr auto p1_point = pick<FIELD>(p1_point_vm_kernel, p1_point_field_kernel<FEP_MODEL_VM>);
+    template <bool FIELD, int NP, int NQ>
+    static constexpr auto point = pick<FIELD>(point_vm_kernel<NP, NQ>, point_field_kernel<FEP_MODEL_VM, NP, NQ>);
+};
+template <> struct ModelKernels<FEP_MODEL_MC> {
+    static constexpr const char* tag = "mc_";
+    static constexpr bool has_hard = false;
+    template <bool FIELD> static constexpr auto return_map = pick<FIELD>(return_map_mc_kernel, return_map_field_kernel<FEP_MODEL_MC>);
+    template <bool FIELD> static constexpr auto p1_point = pick<FIELD>(p1_point_mc_kernel, p1_point_field_kernel<FEP_MODEL_MC>);
+    template <bool FIELD, int NP, int NQ>
+    static constexpr auto point = pick<FIELD>(point_mc_kernel<NP, NQ>, point_field_kernel<FEP_MODEL_MC, NP, NQ>);
+};
+template <> struct ModelKernels<FEP_MODEL_VMPS> {
+    static constexpr const char* tag = "vmps_";
+    static constexpr bool has_hard = false;
+    template <bool FIELD> static constexpr auto return_map = pick<FIELD>(return_map_vmps_kernel, nullptr);
+    template <bool FIELD> static constexpr auto p1_point = pick<FIELD>(p1_point_vmps_kernel, p1_point_field_kernel<FEP_MODEL_VMPS>);
+    template <bool FIELD, int NP, int NQ>
+    static constexpr auto point = pick<FIELD>(point_vmps_kernel<NP, NQ>, point_field_kernel<FEP_MODEL_VMPS, NP, NQ>);
+};
+template <> struct ModelKernels<FEP_MODEL_VMI> {
+    static constexpr const char* tag = "vmi_";
+    static constexpr bool has_hard = true;
+    template <bool FIELD> static constexpr auto return_map = pick<FIELD>(return_map_vmi_kernel, nullptr);
+    template <bool FIELD> static constexpr auto p1_point = pick<FIELD>(p1_point_vmi_kernel, p1_point_vmi_field_kernel);
+    template <bool FIELD, int NP, int NQ>
+    static constexpr auto point = pick<FIELD>(point_vmi_kernel<NP, NQ>, point_vmi_field_kernel<NP, NQ>);
+};
+
+// What a point kernel takes behind blk_counts: the initial-strain field and its scale (a *_field_kernel), then the hardening
+// curve (a model with has_hard)
+struct PointExtras { const double* field; double scale; const Hard* hard; };
+// The one launch of the three families: `kernel` of ModelKernels MK on kBlock threads with `args` and what `x` adds for it.
+// FEP_EINVAL: the model has no such kernel, or takes a curve and none came
+template <class MK, bool FIELD, class K, class... A>
+static int launch_point_kernel(K kernel, unsigned grid, hipStream_t st, const PointExtras& x, A... args) {
+    if constexpr (no_kernel<K>) return FEP_EINVAL;
+    else {
+        if (MK::has_hard && !x.hard) return FEP_EINVAL;
+        auto launch = [&](auto... extra) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, args..., extra...); };
+        auto with_hard = [&](auto... extra) { if constexpr (MK::has_hard) launch(extra..., *x.hard); else launch(extra...); };
+        if constexpr (FIELD) with_hard(x.field, x.scale); else with_hard();
+        HIP_TRY(hipGetLastError());
+        return FEP_OK;
+    }
+}
+// whether the mesh-free field pair takes `model`
+static bool has_return_map_field(int model) {
+    return with_model(model, [](auto m) {
+        return no_kernel<decltype(ModelKernels<decltype(m)::value>::template return_map<true>)> ? FEP_EINVAL : FEP_OK;
+    }) == FEP_OK;
+}
 
 // (`model`: the third and fourth parameter arrays are eta, c of Drucker-Prager, a, Y of von Mises in plane strain or plane stress,
 // or sin_phi, c of Mohr-Coulomb)
@@ -367,11 +424,9 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
                                const double* e_d, int64_t e_pt_stride, int64_t e_comp_stride,
                                const double* e0_h, double* ep_prev_d,
                                const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
-                               int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d,
-                               const double* field_d = nullptr, double scale = 0.0, const Hard* hard = nullptr) {
+                               int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d, const PointExtras& x) {
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_d || !shear_d || !bulk_d || !eta_d || !c_d)) return FEP_EINVAL;
-    if (model == FEP_MODEL_VMI && (!hard || field_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(device_id));
     hipStream_t st = (hipStream_t)stream;
     if (n_int == 0) { if (counts_d) HIP_TRY(hipMemsetAsync(counts_d, 0, 2 * sizeof(int64_t), st)); return FEP_OK; }
@@ -383,19 +438,15 @@ static int return_map_dev_impl(int model, int device_id, void* stream, int64_t n
     if (counts_d)
         FEP_TRY(stream_scratch(kScratchRmCounts, device_id, st, n_blocks * sizeof(uint2),
                                ((size_t)n_blocks + n_blocks / 4 + 64) * sizeof(uint2), (void**)&blk));
-    if (model == FEP_MODEL_VMI)
-        hipLaunchKernelGGL(return_map_vmi_kernel, dim3(n_blocks), dim3(kBlock), 0, st,
-                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
-                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk, *hard);
-    else if (field_d)
-        hipLaunchKernelGGL(kReturnMapFieldKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
-                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
-                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk, field_d, scale);
-    else
-        hipLaunchKernelGGL(kReturnMapKernel[model], dim3(n_blocks), dim3(kBlock), 0, st,
-                           n_int, e_d, e_pt_stride, e_comp_stride, make_e0(e0_h), ep_prev_d,
-                           shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, blk);
-    HIP_TRY(hipGetLastError());
+    FEP_TRY(with_model(model, [&](auto m) {
+        using MK = ModelKernels<decltype(m)::value>;
+        return with_bool(x.field != nullptr, [&](auto fld) {
+            constexpr bool FIELD = decltype(fld)::value;
+            return launch_point_kernel<MK, FIELD>(MK::template return_map<FIELD>, n_blocks, st, x, n_int, e_d, e_pt_stride,
+                                                  e_comp_stride, make_e0(e0_h), ep_prev_d, shear_d, bulk_d, eta_d, c_d, accept, s_d,
+                                                  ds_d, ind_p_d, blk);
+        });
+    }));
     if (counts_d) {
         hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)n_blocks, blk, (unsigned long long*)counts_d);
         HIP_TRY(hipGetLastError());
@@ -409,7 +460,7 @@ extern "C" int fep_return_map_dev(int device_id, void* stream, int64_t n_int,
                                   const double* shear_d, const double* bulk_d, const double* eta_d, const double* c_d,
                                   int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     return return_map_dev_impl(FEP_MODEL_DP, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
+                               shear_d, bulk_d, eta_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d, PointExtras{});
 }
 
 extern "C" int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
@@ -418,7 +469,7 @@ extern "C" int fep_return_map_vm_dev(int device_id, void* stream, int64_t n_int,
                                      const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
                                      int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     return return_map_dev_impl(FEP_MODEL_VM, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d, PointExtras{});
 }
 
 extern "C" int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
@@ -427,7 +478,7 @@ extern "C" int fep_return_map_mc_dev(int device_id, void* stream, int64_t n_int,
                                      const double* shear_d, const double* bulk_d, const double* sin_phi_d, const double* c_d,
                                      int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     return return_map_dev_impl(FEP_MODEL_MC, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, sin_phi_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d);
+                               shear_d, bulk_d, sin_phi_d, c_d, accept, s_d, ds_d, ind_p_d, counts_d, PointExtras{});
 }
 
 extern "C" int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_int,
@@ -436,7 +487,7 @@ extern "C" int fep_return_map_vmps_dev(int device_id, void* stream, int64_t n_in
                                        const double* shear_d, const double* bulk_d, const double* a_d, const double* y_d,
                                        int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
     return return_map_dev_impl(FEP_MODEL_VMPS, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d);
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d, PointExtras{});
 }
 
 extern "C" int fep_return_map_vmi_dev(int device_id, void* stream, int64_t n_int,
@@ -448,7 +499,7 @@ extern "C" int fep_return_map_vmi_dev(int device_id, void* stream, int64_t n_int
     Hard hard;
     FEP_TRY(make_hard(n_seg, kappa_h, slope_h, &hard));
     return return_map_dev_impl(FEP_MODEL_VMI, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d, nullptr, 0.0, &hard);
+                               shear_d, bulk_d, a_d, y_d, accept, s_d, ds_d, ind_p_d, counts_d, PointExtras{nullptr, 0.0, &hard});
 }
 
 extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, int64_t n_int,
@@ -456,9 +507,10 @@ extern "C" int fep_return_map_field_dev(int model, int device_id, void* stream, 
                                         const double* e0_h, const double* e0_field_d, double e0_scale, double* ep_prev_d,
                                         const double* shear_d, const double* bulk_d, const double* m3_d, const double* m4_d,
                                         int accept, double* s_d, double* ds_d, uint8_t* ind_p_d, int64_t* counts_d) {
-    if (model < 0 || model >= kFieldFreeModels || !e0_field_d) return FEP_EINVAL;
+    if (!has_return_map_field(model) || !e0_field_d) return FEP_EINVAL;
     return return_map_dev_impl(model, device_id, stream, n_int, e_d, e_pt_stride, e_comp_stride, e0_h, ep_prev_d,
-                               shear_d, bulk_d, m3_d, m4_d, accept, s_d, ds_d, ind_p_d, counts_d, e0_field_d, e0_scale);
+                               shear_d, bulk_d, m3_d, m4_d, accept, s_d, ds_d, ind_p_d, counts_d,
+                               PointExtras{e0_field_d, e0_scale, nullptr});
 }
 
 extern "C" int fep_host_alloc(void** ptr_h, int64_t bytes) {
@@ -481,7 +533,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
                                 const double* e0_h, double* ep_prev_h,
                                 const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
                                 int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h,
-                                const double* field_h = nullptr, double scale = 0.0, const Hard* hard = nullptr) {
+                                const PointExtras& x) {            // (x.field: host memory, 4 n_int values)
     if (n_int < 0) return FEP_EINVAL;
     if (n_int > 0 && (!e_h || !shear_h || !bulk_h || !eta_h || !c_h)) return FEP_EINVAL;
     if (counts_h) { counts_h[0] = 0; counts_h[1] = 0; }
@@ -499,7 +551,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     const double* e = call.in(kRmE, e_h, (size_t)span);
     double* ep = call.inout(kRmEp, ep_prev_h, 4 * n, accept != 0);
     const double *sh = call.in(kRmShear, shear_h, n), *bu = call.in(kRmBulk, bulk_h, n);
-    const double *m3 = call.in(kRmM3, eta_h, n), *m4 = call.in(kRmM4, c_h, n), *fld = call.in(kRmField, field_h, 4 * n);
+    const double *m3 = call.in(kRmM3, eta_h, n), *m4 = call.in(kRmM4, c_h, n), *fld = call.in(kRmField, x.field, 4 * n);
     if (timing) {
         (void)hipStreamSynchronize(call.stream());
         std::fprintf(stderr, "[fep] return_map_host: inputs on the device after %.3f ms\n", ms());
@@ -510,7 +562,7 @@ static int return_map_host_impl(int model, int device_id, int64_t n_int,
     call.out(kRmCounts, counts_h, 2);
     const int rf = call.run([&] {
         return return_map_dev_impl(model, device_id, call.stream(), n_int, e, e_pt_stride, e_comp_stride, e0_h, ep, sh, bu, m3, m4,
-                                   accept, s, ds, ip, cnt, fld, scale, hard);
+                                   accept, s, ds, ip, cnt, PointExtras{fld, x.scale, x.hard});
     });
     if (timing) std::fprintf(stderr, "[fep] return_map_host: done after %.3f ms\n", ms());
     return rf;
@@ -522,7 +574,7 @@ extern "C" int fep_return_map_host(int device_id, int64_t n_int,
                                    const double* shear_h, const double* bulk_h, const double* eta_h, const double* c_h,
                                    int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_DP, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, eta_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
+                                   bulk_h, eta_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h, PointExtras{}))
 }
 
 extern "C" int fep_return_map_vm_host(int device_id, int64_t n_int,
@@ -531,7 +583,7 @@ extern "C" int fep_return_map_vm_host(int device_id, int64_t n_int,
                                       const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
                                       int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_VM, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h, PointExtras{}))
 }
 
 extern "C" int fep_return_map_mc_host(int device_id, int64_t n_int,
@@ -540,7 +592,7 @@ extern "C" int fep_return_map_mc_host(int device_id, int64_t n_int,
                                       const double* shear_h, const double* bulk_h, const double* sin_phi_h, const double* c_h,
                                       int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_MC, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, sin_phi_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h))
+                                   bulk_h, sin_phi_h, c_h, accept, s_h, ds_h, ind_p_h, counts_h, PointExtras{}))
 }
 
 extern "C" int fep_return_map_vmps_host(int device_id, int64_t n_int,
@@ -549,7 +601,7 @@ extern "C" int fep_return_map_vmps_host(int device_id, int64_t n_int,
                                         const double* shear_h, const double* bulk_h, const double* a_h, const double* y_h,
                                         int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
     FEP_GUARD(return_map_host_impl(FEP_MODEL_VMPS, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h))
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h, PointExtras{}))
 }
 
 extern "C" int fep_return_map_vmi_host(int device_id, int64_t n_int,
@@ -561,7 +613,7 @@ extern "C" int fep_return_map_vmi_host(int device_id, int64_t n_int,
     Hard hard;
     FEP_TRY(make_hard(n_seg, kappa_h, slope_h, &hard));
     FEP_GUARD(return_map_host_impl(FEP_MODEL_VMI, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h, nullptr, 0.0, &hard))
+                                   bulk_h, a_h, y_h, accept, s_h, ds_h, ind_p_h, counts_h, PointExtras{nullptr, 0.0, &hard}))
 }
 
 extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int,
@@ -569,9 +621,10 @@ extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int
                                          const double* e0_h, const double* e0_field_h, double e0_scale, double* ep_prev_h,
                                          const double* shear_h, const double* bulk_h, const double* m3_h, const double* m4_h,
                                          int accept, double* s_h, double* ds_h, uint8_t* ind_p_h, int64_t* counts_h) {
-    if (model < 0 || model >= kFieldFreeModels || !e0_field_h) return FEP_EINVAL;
+    if (!has_return_map_field(model) || !e0_field_h) return FEP_EINVAL;
     FEP_GUARD(return_map_host_impl(model, device_id, n_int, e_h, e_pt_stride, e_comp_stride, e0_h, ep_prev_h, shear_h,
-                                   bulk_h, m3_h, m4_h, accept, s_h, ds_h, ind_p_h, counts_h, e0_field_h, e0_scale))
+                                   bulk_h, m3_h, m4_h, accept, s_h, ds_h, ind_p_h, counts_h,
+                                   PointExtras{e0_field_h, e0_scale, nullptr}))
 }
 
 using fep_host::Symbolic;
@@ -1090,8 +1143,10 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     // `pt`: the model's point kernel; `el`: the element routes' kernel, for Drucker-Prager the whole step from U, for the other
     // models the assembly from ds / s behind their point kernel (step_model)
     char tmp[256], pt[64], el[192];
-    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", model_tag(c->model));
-    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", model_tag(c->model), c->n_p, c->n_q);
+    const char* tag = "";
+    FEP_TRY(with_model(c->model, [&](auto m) { tag = ModelKernels<decltype(m)::value>::tag; return FEP_OK; }));
+    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", tag);
+    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", tag, c->n_p, c->n_q);
     std::snprintf(el, sizeof el, "%s%selement_kernel<%d, %d, %s, %s, %s, %d, %d>", dp ? "" : pt, dp ? "" : " + ", c->n_p, c->n_q, b(dp),
                   b(c->elem_geo), b(patch), patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
     if (c->route == Route::P1Node && c->p1_lds && dp && which == 1 && c->p1_fused && c->fused_mode >= 1) {
@@ -1169,20 +1224,20 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
 // The models besides Drucker-Prager run as point kernel + the route's assembly: the ds / s scratch and the point kernel's
 // per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
 extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
-    if (!c || !known_model(model)) return FEP_EINVAL;
+    if (!c || with_model(model, [](auto) { return FEP_OK; }) != FEP_OK) return FEP_EINVAL;
     if (model != FEP_MODEL_DP) {
 #ifdef FEP_ABLATION
         if (c->route == Route::GenNode) return FEP_ESTATE;
 #endif
         FEP_TRY(fep_set_device(c->device));
-        if (!c->ds_int || !c->s_int || !c->vm_blk) {
+        if (!c->ds_int || !c->s_int || !c->point_blk) {
             // refused while a capture is in progress (the query on the default stream fails during a capture on another)
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(nullptr, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_ESTATE; }
             if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
         }
         FEP_TRY(point_scratch(c, nullptr, true, true));
-        if (!c->vm_blk) FEP_TRY(dmalloc(c, &c->vm_blk, (int64_t)grid_for(c->n_int, kBlock)));
+        if (!c->point_blk) FEP_TRY(dmalloc(c, &c->point_blk, (int64_t)grid_for(c->n_int, kBlock)));
     }
     c->model = model;
     return FEP_OK;
@@ -1487,79 +1542,66 @@ static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const d
     return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
 }
 
-// Von Mises (plane strain and plane stress) and Mohr-Coulomb contexts (FEP_MODEL_VM, _VMPS, _MC): stage A is the model's point kernel (geometry, strain, return map; s / ds to the
-// caller's arrays or the context's scratch), stage B exactly what fep_assemble_dev launches for the route (the element routes'
-// element_kernel in its assembly-only form, then the route's assembly kernel), stage C the COO form's force gather.
-// `field_d` (fep_step_field_*): the same three stages with the *_field_kernel of the context's model, Drucker-Prager included.
+// Stage A of a staged step, and of Drucker-Prager's two-kernel P1 step: the point kernel of the context's model (ModelKernels),
+// p1_point_* for the 3-node triangle and point_*<NP, NQ> for the other types, with `field` its *_field_kernel
+static int launch_point_stage(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept, double* eout,
+                              double* s, double* ds, uint8_t* indp, uint2* blk, const double* field, double scale) {
+    const unsigned n_blocks = grid_for(c->n_int, kBlock);
+    const PointExtras x{field, scale, &c->hard};
+    return with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        return with_model(c->model, [&](auto m) {
+            using MK = ModelKernels<decltype(m)::value>;
+            return with_bool(field != nullptr, [&](auto fld) {
+                constexpr bool FIELD = decltype(fld)::value;
+                if constexpr (ET::type == FEP_P1)
+                    return launch_point_kernel<MK, FIELD>(MK::template p1_point<FIELD>, n_blocks, st, x, c->n_e, c->elem, c->xy,
+                                                          c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
+                                                          eout, s, ds, indp, blk);
+                else    // (Drucker-Prager has none without a field: fep_step_dev takes the element route)
+                    return launch_point_kernel<MK, FIELD>(MK::template point<FIELD, ET::NP, ET::NQ>, n_blocks, st, x, c->n_e,
+                                                          c->elem, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear, c->bulk,
+                                                          c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk);
+            });
+        });
+    });
+}
+
+// The assembly from ds / s that fep_assemble_dev and a staged step share: the element routes' element_kernel in its assembly-only
+// form, the route's assembly kernel, mark 2, the COO form's force gather, mark 3.  `own_call` (fep_assemble_dev): the element
+// kernel is stage A, launched whatever is wanted, with mark 1 behind it; in a staged step both lie in front of this, behind stage A
+static int launch_assembly_stages(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
+                                  bool own_call) {
+    bool counted = false, f_due = false;
+    if (element_route(c) && (own_call || k_data || f_out))
+        FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s),
+                                      const_cast<double*>(ds), nullptr, nullptr, k_data, f_out));
+    if (own_call) FEP_TRY(prof_mark(c, st));
+    FEP_TRY(launch_assembly(c, st, ds, s, k_data, f_out, nullptr, &counted, &f_due));
+    FEP_TRY(prof_mark(c, st));
+    if (f_due) FEP_TRY(launch_force(c, st, f_out));
+    FEP_TRY(prof_mark(c, st));
+    return FEP_OK;
+}
+
+// A staged step: every model but Drucker-Prager, and (`field_d`, fep_step_field_*) every model with a field.  Stage A is the model's
+// point kernel (geometry, strain, return map; s / ds to the caller's arrays or the context's scratch), stages B and C exactly what
+// fep_assemble_dev launches for the route.
 static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
                    double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt,
                    const double* field_d = nullptr, double scale = 0.0) {
-    if (!c->ds_int || !c->s_int || !c->vm_blk) return FEP_ESTATE;
+    if (!c->ds_int || !c->s_int || !c->point_blk) return FEP_ESTATE;
     if (k_data_d && !ds_d) ds_d = c->ds_int;
     if (f_out_d && !s_d) s_d = c->s_int;
-    uint2* blk = cnt ? c->vm_blk : nullptr;
-    const unsigned n_blocks = grid_for(c->n_int, kBlock);
-    bool counted = false, f_due = false;
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
     FEP_TRY(prof_mark(c, st));
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
-    FEP_TRY(with_type(c->elem_type, [&](auto et) {
-        using ET = decltype(et);
-        if (c->model == FEP_MODEL_VMI) {                 // the kernels with the hardening curve (not in the tables)
-            if constexpr (ET::type == FEP_P1) {
-                if (field_d)
-                    hipLaunchKernelGGL(p1_point_vmi_field_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
-                                       c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept,
-                                       e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale, c->hard);
-                else
-                    hipLaunchKernelGGL(p1_point_vmi_kernel, dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
-                                       c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d,
-                                       s_d, ds_d, ind_p_d, blk, c->hard);
-            } else {
-                if (field_d)
-                    hipLaunchKernelGGL((point_vmi_field_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st,
-                                       c->n_e, c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk,
-                                       c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale, c->hard);
-                else
-                    hipLaunchKernelGGL((point_vmi_kernel<ET::NP, ET::NQ>), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem,
-                                       c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c,
-                                       c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, c->hard);
-            }
-            return FEP_OK;
-        }
-        if (field_d) {
-            if constexpr (ET::type == FEP_P1)
-                hipLaunchKernelGGL(kP1PointFieldKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy,
-                                   c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d,
-                                   ds_d, ind_p_d, blk, field_d, scale);
-            else
-                hipLaunchKernelGGL((kPointFieldKernel<ET::NP, ET::NQ>[c->model]), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e,
-                                   c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c,
-                                   c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk, field_d, scale);
-            return FEP_OK;
-        }
-        if constexpr (ET::type == FEP_P1)
-            hipLaunchKernelGGL(kP1PointKernel[c->model], dim3(n_blocks), dim3(kBlock), 0, st, c->n_e, c->elem, c->xy, c->p1tab,
-                               u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu, accept, e_out_d, s_d, ds_d, ind_p_d, blk);
-        else
-            hipLaunchKernelGGL((kPointKernel<ET::NP, ET::NQ>[c->model - FEP_MODEL_VM]), dim3(n_blocks), dim3(kBlock), 0, st, c->n_e,
-                               c->elem, c->xy, c->dh1, c->dh2, c->wf, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu,
-                               accept, e_out_d, s_d, ds_d, ind_p_d, blk);
-        return FEP_OK;
-    }));
-    HIP_TRY(hipGetLastError());
+    FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, cnt ? c->point_blk : nullptr,
+                               field_d, scale));
     FEP_TRY(prof_mark(c, st));
-    if (k_data_d || f_out_d) {
-        if (element_route(c))
-            FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, s_d, ds_d, nullptr, nullptr,
-                                          k_data_d, f_out_d));
-        FEP_TRY(launch_assembly(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, &counted, &f_due));
-    }
-    FEP_TRY(prof_mark(c, st));
-    if (f_due) FEP_TRY(launch_force(c, st, f_out_d));
-    FEP_TRY(prof_mark(c, st));
+    FEP_TRY(launch_assembly_stages(c, st, ds_d, s_d, k_data_d, f_out_d, false));
     if (cnt) {
-        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)n_blocks, c->vm_blk, cnt);
+        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)grid_for(c->n_int, kBlock), c->point_blk, cnt);
         HIP_TRY(hipGetLastError());
     }
     return FEP_OK;
@@ -1604,12 +1646,8 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     FEP_TRY(prof_mark(c, st));
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
     if (c->route == Route::P1Node) {
-        if (!fused) {                                   // (the one-kernel step is all stage B)
-            hipLaunchKernelGGL(p1_point_kernel, dim3(grid_for(c->n_e, kBlock)), dim3(kBlock), 0, st,
-                               c->n_e, c->elem, c->xy, c->p1tab, u_d, e0, ep_prev_d, c->shear, c->bulk, c->eta, c->c, c->matu,
-                               accept, e_out_d, s_d, ds_d, ind_p_d, blk);
-            HIP_TRY(hipGetLastError());
-        }
+        if (!fused)                                     // (the one-kernel step is all stage B)
+            FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, nullptr, 0.0));
 #ifdef FEP_ABLATION
     } else if (c->route == Route::GenNode) {
         FEP_TRY(launch_point(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk));
@@ -1659,9 +1697,9 @@ extern "C" int fep_step_field_dev(fep_ctx* c, void* stream, const double* u_d, c
     hipStream_t st = (hipStream_t)stream;
     // (a von Mises / Mohr-Coulomb context holds all three since fep_ctx_set_model; Drucker-Prager gets them here, once)
     FEP_TRY(point_scratch(c, st, true, true));
-    if (!c->vm_blk) {
+    if (!c->point_blk) {
         FEP_TRY(scratch_alloc_allowed(st));
-        FEP_TRY(dmalloc(c, &c->vm_blk, (int64_t)grid_for(c->n_int, kBlock)));
+        FEP_TRY(dmalloc(c, &c->point_blk, (int64_t)grid_for(c->n_int, kBlock)));
     }
     return step_model(c, st, u_d, make_e0(e0_h), ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d,
                       (unsigned long long*)counts_d, e0_field_d, e0_scale);
@@ -1674,19 +1712,10 @@ extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, co
     if (!fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
     hipStream_t st = (hipStream_t)stream;
-    bool counted = false, f_due = false;
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
     FEP_TRY(prof_mark(c, st));
     FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
-    if (element_route(c))
-        FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s_d),
-                                      const_cast<double*>(ds_d), nullptr, nullptr, k_data_d, f_out_d));
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(launch_assembly(c, st, ds_d, s_d, k_data_d, f_out_d, nullptr, &counted, &f_due));
-    FEP_TRY(prof_mark(c, st));
-    if (f_due) FEP_TRY(launch_force(c, st, f_out_d));
-    FEP_TRY(prof_mark(c, st));
-    return FEP_OK;
+    return launch_assembly_stages(c, st, ds_d, s_d, k_data_d, f_out_d, true);
 }
 
 static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const double* e0_h, double* ep_prev_h, int accept,

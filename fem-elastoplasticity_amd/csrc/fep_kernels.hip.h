@@ -472,7 +472,8 @@ __device__ __forceinline__ int mc_return_map(const double e[3], const double z[4
 
 // The return map of a material model, and the counter its branch goes to (count_branches: 1 -> counts[0], 2 -> counts[1]):
 // Drucker-Prager counts smooth and apex as they are, von Mises its plastic points, Mohr-Coulomb face and edges together and
-// the apex apart.  `m3` / `m4` = eta / c, a / Y or sin_phi / c.  A new model is a line in each of the two.
+// the apex apart.  `m3` / `m4` = eta / c, a / Y or sin_phi / c.  A new model is a line in each of the two, its __global__ wrappers
+// below, and its ModelKernels specialisation in fep_api.hip, where the host learns of them.
 template <int MODEL>
 __device__ __forceinline__ int model_return_map(const double e[3], const double z[4], double p[4],
                                                 double G, double K, double m3, double m4, bool accept,
@@ -1756,7 +1757,8 @@ p1_point_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, doubl
                                field, scale);
 }
 // The field wrapper of the model with a hardening curve (FEP_MODEL_VMI), the curve behind the field.  It has a name of its own:
-// an overload of the template above would make the address in the dispatch tables of the other models ambiguous
+// an overload of the template above would make p1_point_field_kernel<MODEL>, as the other models' ModelKernels (fep_api.hip)
+// name it, ambiguous
 __global__ void __launch_bounds__(kBlock)
 p1_point_vmi_field_kernel(FEP_P1_POINT_ARGS, const double* __restrict__ field, double scale, Hard hc) {
     p1_point_body<FEP_MODEL_VMI, true>(n_e, elem, xy, tab, U, e0, ep, shear, bulk, m3, m4, mu, accept, Eout, S, DS, indp, blk_counts,
