@@ -87,6 +87,9 @@ class _HostOps:
     def setup_amg(self, K, coordinates):
         pass
 
+    def cautious(self, on):
+        """The second attempt of a load step (_load_history_loop): nothing to change for the direct solve."""
+
     def solve(self, K, rhs, criterion=None):
         rhs = np.asarray(rhs).ravel()
         x = np.zeros(rhs.size)
@@ -154,6 +157,7 @@ class _DeviceOps:
         self.counts = torch.zeros(2, dtype=torch.int64, device=self.dev)
         self.tmp = torch.empty(ctx.n_dof, **f64)
         self.pcg_iters = []
+        self.precond = None                                    # the solver's choice: multigrid when a hierarchy is loaded
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.dev).cuda_stream
@@ -204,6 +208,13 @@ class _DeviceOps:
         if self.amg:
             self.solver.setup_amg(self.host(K), coordinates, k_dev=K)
 
+    def cautious(self, on):
+        """The second attempt of a load step (_load_history_loop): while `on`, the multigrid ops solve with the block-Jacobi
+        preconditioner.  The multigrid's Chebyshev smoother takes its interval from K_elast; on a soft plastic tangent the
+        spectrum of the block-scaled matrix can leave it, the V-cycle is then indefinite and the conjugate gradients break
+        down at once (state 2), on any iterate with that tangent.  The block inverses of a positive definite K are definite."""
+        self.precond = 'jacobi' if on and self.amg else None
+
     def solve(self, K, rhs, criterion=None):
         # inexact Newton: while the iterate is far from converged the correction need not be solved to 11 digits.
         # `criterion` is the stopping quantity of the previous Newton iterate (DP:1075); the linear residual is asked
@@ -213,7 +224,8 @@ class _DeviceOps:
             rtol = max(self.rtol, self.inexact_rtol)
         elif self.forcing and criterion is not None and np.isfinite(criterion):
             rtol = min(self.forcing_cap, max(self.rtol, self.forcing * criterion))
-        x = self.solver.pcg(K, rhs, rtol=rtol, max_iter=self.max_iter)
+        kw = {} if self.precond is None else {'precond': self.precond}
+        x = self.solver.pcg(K, rhs, rtol=rtol, max_iter=self.max_iter, **kw)
         self.pcg_iters.append(self.solver.last['iters'])
         if self.solver.last['state'] != 1:
             x.fill_(float('nan'))
@@ -355,8 +367,19 @@ def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted, U=None, Ep
     load through prescribed displacements or an initial stress): for every `zeta` of `zetas` _newton_iteration on the residual
     zeta * f_ext - F(U), started from the last accepted U, then the accepting call, which updates the plastic strain in
     place: the state a load cycle carries.  The stopping quantity is 0 when the correction is exactly 0 (an elastic cycle
-    returns to exactly U = 0 at zeta = 0, where the quotient is 0/0).  There is no sub-stepping: a step that does not
-    converge ends the history and its index goes to hist['failed_at'].  `accepted(r, zeta, U, its)` records a step from
+    returns to exactly U = 0 at zeta = 0, where the quotient is 0/0).  There is no sub-stepping.  A step that does not
+    converge (25 iterates without a small stopping quantity, or a NaN one: a linear solve that broke down) is retried ONCE
+    from the last accepted state, the first correction solved on K_elast instead of the tangent, then the iteration as
+    before, with the ops `cautious` (the multigrid ops then precondition with the block inverses, which no tangent makes
+    indefinite); its index goes to hist['retries'], and `accepted` is told the iterations of both attempts and the elastic
+    correction.  (After a plastic step every point sits on its yield surface to rounding, so rounding decides which points
+    the first tangent of the next step takes for plastic.  If most are and the load goes back, the soft tangent carries the
+    iterate through the whole elastic range into reverse yielding, where the tangent is soft again, and the iteration
+    alternates between the two for good; the elastic correction is the exact answer to an elastic step.  DESIGN.md
+    section 7.)  A step that does not converge then either ends the history and its index goes to hist['failed_at'].
+    The retry is reached only after a failure: a history that converged without it has the same iterates and calls as
+    before.
+    `accepted(r, zeta, U, its)` records a step from
     the accepting call's result.  `U`, `Ep`: the state the history goes on from (vectors of `ops`; `Ep` is updated in place),
     instead of zero: a history that was refined on the way (vonmises.solve_cutout_cyclic, adapt_at); `accept_want`: what the
     accepting calls return.  Returns the last accepted U and the plastic strain."""
@@ -364,10 +387,22 @@ def _load_history_loop(ops, K_elast, f_ext, zetas, hist, *, accepted, U=None, Ep
     Ep = ops.new_ep() if Ep is None else Ep
     criterion = None
     hist['failed_at'] = None
+    hist.setdefault('retries', [])
     for k, zeta in enumerate(zetas):
         zeta = float(zeta)
-        U_it, its, criterion = _newton_iteration(ops, K_elast, U, Ep, None, lambda F: zeta * f_ext - F, hist, criterion,
-                                                 zero_dU_converged=True)
+        rhs_of = lambda F: zeta * f_ext - F                                                # noqa: E731
+        U_it, its, criterion = _newton_iteration(ops, K_elast, U, Ep, None, rhs_of, hist, criterion, zero_dU_converged=True)
+        if not criterion < 1e-10:
+            hist['retries'].append(k)
+            r = ops.step(U, Ep, want=('K', 'F'))
+            hist['n_calls'] += 1
+            U_el = U + ops.solve(K_elast, rhs_of(r['F']))
+            ops.cautious(True)
+            try:
+                U_it, again, criterion = _newton_iteration(ops, K_elast, U_el, Ep, None, rhs_of, hist, None, zero_dU_converged=True)
+            finally:
+                ops.cautious(False)
+            its += 1 + again
         if not criterion < 1e-10:
             hist['failed_at'] = k
             break

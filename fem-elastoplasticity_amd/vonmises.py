@@ -42,7 +42,8 @@ def solve_cutout_cyclic(element_type='P1', level=1, peak_traction=(0, 200), step
     accumulated multiplier, returned as 'kappa' too, with 'eps_p_bar' = sqrt(2/3) kappa.
 
     Returns a dict: 'zeta' (the accepted factors), 'U' (list of (2, n_n)), 'n_plast', 'newton_its', 'pcg_iters', 'Ep',
-    'f_ext' (2, n_n), 'mesh', 'failed_at' (index of the step that did not converge, or None) and 'work' =
+    'f_ext' (2, n_n), 'mesh', 'failed_at' (index of the step that did not converge, or None), 'retries' (indices of the steps
+    that took the second attempt, the one that starts with an elastic correction) and 'work' =
     sum_k (zeta_k + zeta_{k-1})/2 * f_ext . (U_k - U_{k-1}), the work of the external load over the accepted steps.
     `context_factory(elements, coordinates, dhatp1, dhatp2, wf)` may supply another object with MeshContext's
     `set_model / set_materials / step / geometry / close` (the tests run the loop on their CPU restatement that way).
@@ -209,7 +210,7 @@ def _cutout_adaptive(mesh, zetas, adapt_at, mark, theta, peak_traction, model, l
             U0 = Ep0 = None
             if carried is not None:
                 U0, Ep0 = carried if on_device else (ops.vec(carried[0]), np.ascontiguousarray(carried[1], dtype=np.float64))
-            n_before = len(hist['zeta'])
+            n_before, n_retried = len(hist['zeta']), len(hist.get('retries', ()))
             # The transferred state is admissible but not in equilibrium against the new test functions.  A segment therefore
             # begins by repeating the factor it was refined at: an accepted step of its own, with the plastic flow the finer
             # mesh asks for at that load.  (Going straight on to a smaller factor leaves the Newton iteration to unload and
@@ -225,8 +226,10 @@ def _cutout_adaptive(mesh, zetas, adapt_at, mark, theta, peak_traction, model, l
             for z, Uk in zip(hist['zeta'][n_before:], hist['U'][n_before:]):
                 work += 0.5 * (z + z_old) * float(np.sum(f_ext * (Uk - U_old)))
                 z_old, U_old = z, Uk
-            if hist['failed_at'] is not None:                                             # an index into the load factors
-                hist['failed_at'] += start - (1 if seg > 0 else 0)
+            shift = start - (1 if seg > 0 else 0)                                         # to an index into the load factors
+            hist['retries'][n_retried:] = [k + shift for k in hist['retries'][n_retried:]]
+            if hist['failed_at'] is not None:
+                hist['failed_at'] += shift
             if hist['failed_at'] is not None or seg == len(stops) - 1:
                 hist['Ep'] = np.array(ops.host(Ep))
                 break
