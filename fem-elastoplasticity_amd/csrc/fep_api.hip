@@ -97,77 +97,122 @@ static Hard flat_hard() {
     return h;
 }
 
+// Compile-time flavour: a branch on it folds away, and in a template the product never instantiates what lies behind it
+#ifdef FEP_ABLATION
+static constexpr bool kAblationBuild = true;
+#else
+static constexpr bool kAblationBuild = false;
+#endif
+
+// The state of each route: its plan's sizes and flags, its device tables, its per-step scratch.  A context fills the one its
+// Route tag names (its setup_*), and only that route's launchers read it.  `Variant`: what only the measurement build's
+// switches ever set to anything but the default here (the product runs the defaults).
+
+// P1 node route (fep_host.h, P1Plan): node-centric gather assembly from 48-byte geometry records
+struct P1NodeRoute {
+    struct Variant {                                    // ablation switches: the product keeps these defaults
+        int tile = 256;                                 // FEP_P1_TILE: node-pair blocks per workgroup of the assembly kernel
+        bool lds = true, pk = true;                     // FEP_P1_PATH: LDS-staged form, packed descriptors (the product declines any other plan)
+        bool dma = false;                               // FEP_P1_DMA=1: node data and gather codes of the one-kernel step by LDS-DMA
+        bool asm_from_nodes = false;                    // FEP_P1_ASM=nodes: assembly kernel with geometry from LDS-staged nodes (measured slower)
+        int fused_mode = 1;                             // FEP_P1_FUSED=off|kf|all: 0 = never, 1 = only when no point output is wanted, 2 = always
+        unsigned long long* clk = nullptr;              // FEP_P1_CLK=1: 8 stamps per tile of the last p1_node_lds_kernel launch, then of the last p1_fused_kernel launch
+    } v;
+    int n_tiles = 0;                                    // workgroups of the tile kernels
+    bool rng = false;                                   // element lists as runs (in trec) instead of wg_elist
+    // one-kernel step (p1_fused_kernel): per-tile node lists / runs, per staged element its tile-local node indices + owner bit
+    bool fused = false, fused_rng = false;
+    int L = 0, C = 0, NL = 0;                           // staged elements / gather codes / nodes per tile (max)
+    // device, static
+    int32_t* trec = nullptr;                            // one record of kRecInts ints per tile (fep_host.h, P1Plan::rec)
+    int32_t* wg_elist = nullptr;                        // list form (rng false); the runs of the run form ride in trec
+    uint16_t* perm_l = nullptr;                         // 16-bit gather codes
+    uint2* pk = nullptr;                                // packed block descriptors, lanes sorted by segment length
+    int32_t* wg_nlist = nullptr;
+    uint32_t* el_nodes = nullptr;
+    // tables of the variants the product never runs (NULL there): the unpacked descriptors read segptr, meta and ncol, the direct
+    // kernel (p1_node_kernel) these and its gather list perm2
+    int32_t *segptr = nullptr, *ncol = nullptr, *perm2 = nullptr;
+    uint32_t* meta = nullptr;
+    // device, scratch
+    double* geo = nullptr;                              // 48-byte geometry record per element (geometry_kernel)
+    unsigned long long* slot_counts = nullptr;          // one-kernel step: 256 slots x 16 words, zero between steps
+};
+
+// What element_kernel takes in either form of the element route (elem_form)
+struct ElemForm {
+    bool geo = true;                                    // geometry from coordinates instead of the dphi arrays
+    int lds_pad = 0;                                    // ablation switch FEP_ELEM_LDS_PAD: extra LDS bytes per workgroup (occupancy experiments)
+};
+
+// Patch form of the element route (fep_host.h, PatchPlan)
+struct PatchRoute {
+    struct Variant {                                    // ablation switches: the product keeps this default
+        unsigned long long* phase_clk = nullptr;        // FEP_PHASE_CLK=1: phase stamps of the last element_kernel launch (reported at destroy)
+    } v;
+    int eb = 0, tpb = 256, js = 1;                      // workgroup shape (ElemCfg)
+    int64_t n_patch = 0, n_open = 0, n_fopen = 0;
+    // device, static
+    int32_t *desc = nullptr, *plist = nullptr, *pel = nullptr, *pnodes = nullptr;
+    uint2 *items = nullptr, *fitems = nullptr;
+    uint16_t *codes = nullptr, *fcodes = nullptr;
+    uint4 *fix = nullptr, *ffix = nullptr;
+    uint2* fixT = nullptr;
+    // device, scratch rewritten by every step
+    double *Pc = nullptr, *Pf = nullptr;                // partial blocks / forces of the open items
+};
+
+// COO form of the element route: every K_e block through HBM
+struct CooRoute {
+    struct Variant {                                    // ablation switches: the product keeps this default
+        int csr_gathers = 4;                            // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
+                                                        // measured P2 / Q2 / P4 reduce kernel: 2: 0.406 / 0.376 / 0.654 ms, 4: 0.392 / 0.347 / 0.651,
+                                                        // 6: 0.382 / 0.371 / 0.650, 8 (5 waves per SIMD): 0.432 / 0.425 / 0.733)
+    } v;
+    int n_tiles = 0;                                    // tiles of csr_reduce*_kernel
+    bool kc_aos = false;                                // K_e half-blocks: all blocks of an element adjacent (AoS) or block-major (SoA)
+    // device, static
+    int32_t* tstart = nullptr;                          // first block of every tile
+    int32_t* perm = nullptr;                            // address of every contribution in Kc
+    uint2* pkc = nullptr;                               // packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
+    int32_t* segptr = nullptr;                          // the unpacked descriptors of csr_reduce_kernel, uploaded only without pkc
+    uint32_t* meta = nullptr;
+    // device, scratch rewritten by every step
+    double *Kc = nullptr, *fe = nullptr;
+};
+
 struct fep_ctx {
     int device = 0;
     int elem_type = 0;
     int n_p = 0, n_q = 0;
     int64_t n_e = 0, n_n = 0, n_int = 0, n_dof = 0, nnz = 0, n_blk = 0;
-    Route route = Route::Coo;
+    Route route = Route::Coo;                           // which of the route structs below is filled
+    P1NodeRoute p1;
+    PatchRoute patch;
+    CooRoute coo;
+    ElemForm elem_form;                                 // Patch and Coo
+#ifdef FEP_ABLATION
+    struct GenNodeRoute* gen = nullptr;                 // (defined with its set-up and launchers)
+#endif
     bool have_materials = false;
     int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
     uint2* point_blk = nullptr;                         // step_model: per-workgroup branch counters of the point stage (every
                                                         // model but Drucker-Prager, and Drucker-Prager with a field)
     Hard hard = flat_hard();                            // FEP_MODEL_VMI: fep_ctx_set_hardening (one segment of slope 0 until then)
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
-    uint2* pkc = nullptr;                               // COO route: packed block descriptors of csr_reduce_pk_kernel (NULL: fields too wide)
-    int csr_gathers = 4;                                // gathers in flight per lane of csr_reduce_kernel (FEP_CSR_GATHERS=2|4|6|8;
-                                                        // measured P2 / Q2 / P4 reduce kernel: 2: 0.406 / 0.376 / 0.654 ms, 4: 0.392 / 0.347 / 0.651,
-                                                        // 6: 0.382 / 0.371 / 0.650, 8 (5 waves per SIMD): 0.432 / 0.425 / 0.733)
-    bool kc_aos = false;                                // K_e half-blocks: all blocks of an element adjacent (AoS) or block-major (SoA)
-    // patch route of the element kernel: fep_host.h, PatchPlan
-    int patch_eb = 0, patch_tpb = 256, patch_js = 1;    // workgroup shape of the patch form (ElemCfg)
-    int lds_pad = 0;                                    // FEP_ELEM_LDS_PAD: extra LDS bytes per workgroup of element_kernel (occupancy experiments)
-    int64_t n_open = 0, n_fopen = 0;
-    int32_t *pt_desc = nullptr, *pt_plist = nullptr, *pt_pel = nullptr, *pt_pnodes = nullptr;
-    uint2 *pt_items = nullptr, *pt_fitems = nullptr;
-    uint16_t *pt_codes = nullptr, *pt_fcodes = nullptr;
-    uint4 *pt_fix = nullptr, *pt_ffix = nullptr;
-    uint2* pt_fixT = nullptr;
-    int64_t n_patch = 0;
-#ifdef FEP_ABLATION
-    unsigned long long* phase_clk = nullptr;            // FEP_PHASE_CLK=1: phase stamps of the last element_kernel launch (reported at destroy)
-    unsigned long long* p1_clk = nullptr;               // FEP_P1_CLK=1: 8 stamps per tile of the last p1_node_lds_kernel launch, then of the last p1_fused_kernel launch
-#endif
-    double *Pc = nullptr, *Pf = nullptr;                // partial blocks / forces of the open items (scratch, rewritten by every step)
-    bool elem_geo = true;                               // element_kernel: geometry from coordinates instead of the dphi arrays
     MatU matu{};                                        // homogeneous-material fast path (arrays not read)
     // device, static
     int32_t* elem = nullptr;
     double *coords = nullptr, *dh1 = nullptr, *dh2 = nullptr, *wf = nullptr;
     double *dphi1 = nullptr, *dphi2 = nullptr, *weight = nullptr, *det = nullptr;
     double *shear = nullptr, *bulk = nullptr, *eta = nullptr, *c = nullptr;
-    int32_t *segptr = nullptr, *perm = nullptr, *iptr = nullptr, *ilist = nullptr;
-    uint32_t* meta = nullptr;
-    // P1 fast path (node-centric gather assembly): 64-byte geometry records, re-encoded gather list
-    bool p1_lds = false;
-    double *geo = nullptr, *xy = nullptr;               // xy: interleaved (x,y) per node
+    int32_t *iptr = nullptr, *ilist = nullptr;
+    double* xy = nullptr;                               // interleaved (x,y) per node
     P1Tab p1tab{};
-    int32_t *perm2 = nullptr, *ncol = nullptr;
-    int32_t* wg_elist = nullptr;                        // list form (p1_rng false); the runs of the run form ride in trec
-    bool p1_rng = false, p1_pk = false;
-    uint2* pk = nullptr;                                // packed block descriptors, lanes sorted by segment length
-    int32_t* trec = nullptr;                            // P1 tiles: one record of kRecInts ints per tile (fep_host.h, P1Plan::rec)
-    int32_t* tstart = nullptr;                          // COO route: first block of every tile of csr_reduce_kernel
-    int n_wg_p1 = 0;   // LDS-staged variant: per-workgroup element lists
-    // one-kernel step (p1_fused_kernel): per-tile node lists / runs, per staged element its tile-local node indices + owner bit
-    bool p1_fused = false, p1_fused_rng = false;
-    bool asm_from_nodes = false;                        // FEP_P1_ASM=nodes: assembly kernel with geometry from LDS-staged nodes (measured slower)
-    bool p1_dma = false;                                // FEP_P1_DMA=1: node data and gather codes of the one-kernel step by LDS-DMA
-    int fused_mode = 1;                                 // FEP_P1_FUSED=off|kf|all: 0 = never, 1 = only when no point output is wanted (default), 2 = always
-    int lds_NL = 0;                                     // staged nodes per tile (max)
-    int32_t* wg_nlist = nullptr;
-    uint32_t* el_nodes = nullptr;
-    unsigned long long* slot_counts = nullptr;          // 256 slots x 16 words, zero between steps
     bool has_orphans = false;                           // nodes that belong to no element (their F entries are zeroed per step)
-    uint16_t* perm_l = nullptr;
-    int tile = 256;                                     // node-pair blocks per workgroup of the assembly kernel
-    int gn_tile = 256;                                  // GenNode route
-    size_t gn_lds = 0;
-    int lds_L = 0, lds_C = 0;                           // staged elements / gather codes per workgroup (max)
     // device, scratch rewritten by every step
-    double *Kc = nullptr, *fe = nullptr;
     double *s_int = nullptr, *ds_int = nullptr;     // used when the caller does not ask for s / ds
-    uint2* blk_counts = nullptr;
+    uint2* blk_counts = nullptr;                        // stage A's per-workgroup branch counters on every route (n_count_blocks of them)
     int n_count_blocks = 0;
     fep_stage::DeviceStore hbuf{kCtxBufCount};          // persistent device buffers of the *_host entry points, by CtxBuf
     // host copies of the pattern
@@ -247,11 +292,8 @@ template <class F> static int with_bool(bool v, F&& f) { return v ? f(std::true_
 // A switch that only the ablation build varies: the product instantiates the value `Product` alone and refuses the other
 // one (FEP_ESTATE: a context the product never creates)
 template <bool Product, class F> static int with_ablation_bool(bool v, F&& f) {
-#ifdef FEP_ABLATION
-    return with_bool(v, f);
-#else
-    return v == Product ? f(std::bool_constant<Product>{}) : FEP_ESTATE;
-#endif
+    if constexpr (kAblationBuild) return with_bool(v, f);
+    else return v == Product ? f(std::bool_constant<Product>{}) : FEP_ESTATE;
 }
 
 // Launches `kernel` with `lds` bytes of dynamic LDS, raising its limit first when `lds` is above `limit`
@@ -265,13 +307,7 @@ static int launch_lds(void (*kernel)(P...), unsigned grid, unsigned tpb, size_t 
 
 // ---------------------------------------------------------------------------------------
 extern "C" int fep_version(void) { return 1; }
-extern "C" int fep_build_is_ablation(void) {
-#ifdef FEP_ABLATION
-    return 1;
-#else
-    return 0;
-#endif
-}
+extern "C" int fep_build_is_ablation(void) { return kAblationBuild ? 1 : 0; }
 
 extern "C" const char* fep_strerror(int code) {
     switch (code) {
@@ -632,12 +668,13 @@ using fep_host::build_symbolic;
 
 static_assert(fep_host::kSegMax == fep::kSegMax, "tile descriptor layout shared by host and kernels");
 
-static int launch_geometry(fep_ctx* c) {
+// `p1_geo`: the node route's record array when that is the route (NULL: no records are written)
+static int launch_geometry(fep_ctx* c, double* p1_geo) {
     return with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
         hipLaunchKernelGGL((geometry_kernel<ET::NP, ET::NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, nullptr,
                            c->n_e, c->n_n, c->elem, c->coords, c->dh1, c->dh2, c->wf, c->dphi1, c->dphi2, c->weight, c->det,
-                           c->geo);
+                           p1_geo);
         HIP_TRY(hipGetLastError());
         return FEP_OK;
     });
@@ -658,12 +695,9 @@ template <class F> static int elem_shape(int elem_type, bool patch_form, bool ge
         return with_bool(patch_form, [&](auto pf) {
             constexpr bool PATCH = decltype(pf)::value;
             auto shape = [&](auto tpb_c, auto js_c) {
-#ifdef FEP_ABLATION
-                return with_bool(geo, [&](auto g) { return f(et, pf, g, tpb_c, js_c); });
-#else
                 constexpr bool G = elem_geo_default(ET::type, PATCH);
-                return geo == G ? f(et, pf, std::bool_constant<G>{}, tpb_c, js_c) : FEP_ESTATE;
-#endif
+                if constexpr (kAblationBuild) return with_bool(geo, [&](auto g) { return f(et, pf, g, tpb_c, js_c); });
+                else return geo == G ? f(et, pf, std::bool_constant<G>{}, tpb_c, js_c) : FEP_ESTATE;
             };
             if (tpb == kBlock && js == 1) return shape(int_c<kBlock>{}, int_c<1>{});
             if constexpr (PATCH && ET::type == FEP_P2) { if (tpb == 512 && js == 1) return shape(int_c<512>{}, int_c<1>{}); }
@@ -680,24 +714,105 @@ template <class F> static int elem_shape(int elem_type, bool patch_form, bool ge
 }
 
 static int elements_per_workgroup(const fep_ctx* c, bool patch_form, int tpb, int js, int* eb) {
-    return elem_shape(c->elem_type, patch_form, c->elem_geo, tpb, js, [&](auto et, auto, auto geo, auto tpb_c, auto js_c) {
+    return elem_shape(c->elem_type, patch_form, c->elem_form.geo, tpb, js, [&](auto et, auto, auto geo, auto tpb_c, auto js_c) {
         using ET = decltype(et);
         *eb = ElemCfg<ET::NP, ET::NQ, decltype(geo)::value, decltype(tpb_c)::value, decltype(js_c)::value>::EB;
         return FEP_OK;
     });
 }
 
+// What the route set-ups read of fep_ctx_create's inputs
+struct MeshIn {
+    const Symbolic& S;
+    const int32_t* elem;
+    const double *coords, *dh1, *dh2, *wf;
+    bool validate;                                      // FEP_VALIDATE_PLAN: replay every plan against the symbolic phase
+};
+
+#ifdef FEP_ABLATION
+// The measurement build's general node route, whole: its state, its set-up, its two launchers.
+// FEP_GEN_PATH=node: node route for P2 / Q1 / Q2 (point_kernel + node_lds_kernel; measured on MI355X, 1 M elements:
+// Q1 0.276 vs 0.286 ms, P2 1.80 vs 1.30 ms, Q2 0.41 vs 0.34 ms per step — its LDS gather costs n_q times the P1 one).
+struct GenNodeRoute {
+    int tile = 256;                                     // node-pair blocks per workgroup of node_lds_kernel
+    size_t lds = 0;
+    int L = 0, C = 0;                                   // staged elements / gather codes per workgroup (max)
+    int32_t *segptr = nullptr, *ncol = nullptr, *wg_elist = nullptr;
+    uint32_t* meta = nullptr;
+    uint16_t* perm_l = nullptr;
+};
+static constexpr size_t kLdsNodeLds = 48 * 1024;        // (node_lds_kernel raises its dynamic LDS limit from 48 KiB on)
+
+// *taken = false: no plan fits, the element route.
+static int setup_gen_node(fep_ctx* c, const MeshIn& in, bool* taken) {
+    fep_host::GnPlan G;
+    fep_host::build_gn_plan(in.S, c->n_p, c->n_q, c->n_e, G);
+    *taken = G.ok;
+    if (!G.ok) return FEP_OK;
+    c->gen = new (std::nothrow) GenNodeRoute();         // (freed by fep_ctx_destroy)
+    if (!c->gen) return FEP_ENOMEM;
+    GenNodeRoute& r = *c->gen;
+    r.tile = G.tile; r.L = G.L; r.C = G.C; r.lds = G.lds;
+    FEP_TRY(upload(c, &r.wg_elist, G.elist_pad.data(), (int64_t)G.elist_pad.size()));
+    FEP_TRY(upload(c, &r.perm_l, G.codes_pad.data(), (int64_t)G.codes_pad.size()));
+    FEP_TRY(upload(c, &r.ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
+    FEP_TRY(upload(c, &r.segptr, in.S.segptr.data(), (int64_t)in.S.segptr.size()));
+    FEP_TRY(upload(c, &r.meta, in.S.meta.data(), (int64_t)in.S.meta.size()));
+    c->n_count_blocks = (int)grid_for(c->n_int, kBlock);
+    return FEP_OK;
+}
+
+// GenNode route, stage A: point_kernel
+static int launch_point(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept, double* eout,
+                        double* s, double* ds, uint8_t* indp, uint2* blk) {
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
+        else {
+            hipLaunchKernelGGL((point_kernel<ET::NP, ET::NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, st, c->n_e,
+                               c->elem, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
+                               accept, eout, s, ds, indp, blk);
+            return FEP_OK;
+        }
+    }));
+    HIP_TRY(hipGetLastError());
+    return FEP_OK;
+}
+
+// GenNode route, stage B: node_lds_kernel
+static int launch_gn_node(fep_ctx* c, const GenNodeRoute& r, hipStream_t st, const double* ds, const double* s, double* k_data,
+                          double* f_out, unsigned long long* counts_d, bool* counted) {
+    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
+    const int n_wg = (int)grid_for(c->n_blk, r.tile);
+    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    FEP_TRY(with_type(c->elem_type, [&](auto et) {
+        using ET = decltype(et);
+        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
+        else return with_bool(r.tile == 256, [&](auto t256) {
+            constexpr int TPB = decltype(t256)::value ? 256 : 128;
+            return launch_lds(node_lds_kernel<ET::NP, ET::NQ, TPB>, grid, TPB, r.lds, kLdsNodeLds, st, c->n_blk, c->n_e,
+                              r.L, r.C, r.segptr, r.perm_l, r.meta, r.ncol, r.wg_elist, c->elem, c->xy,
+                              c->dh1, c->dh2, c->wf, k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out, n_wg,
+                              c->n_count_blocks, c->blk_counts, counts_d);
+        });
+    }));
+    *counted = counts_d != nullptr;
+    return FEP_OK;
+}
+#endif  // FEP_ABLATION
+
 extern "C" int fep_ctx_destroy(fep_ctx* c) {
     if (!c) return FEP_OK;
     if (fep_set_device(c->device) == FEP_OK) {
 #ifdef FEP_ABLATION
-        if (c->phase_clk && c->n_patch > 0) {            // mean shader clocks per phase of the LAST element_kernel launch
-            std::vector<unsigned long long> h((size_t)(12 * c->n_patch));
+        const int64_t n_patch = c->patch.n_patch;
+        if (c->patch.v.phase_clk && n_patch > 0) {            // mean shader clocks per phase of the LAST element_kernel launch
+            std::vector<unsigned long long> h((size_t)(12 * n_patch));
             if (hipDeviceSynchronize() == hipSuccess &&
-                hipMemcpy(h.data(), c->phase_clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
+                hipMemcpy(h.data(), c->patch.v.phase_clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
                 double acc[6] = {0, 0, 0, 0, 0, 0}, cyc = 0.0, real = 0.0, st_ids = 0.0, st_data = 0.0, st_bar = 0.0;
                 unsigned long long lo = ~0ull, hi = 0;
-                for (int64_t p = 0; p < c->n_patch; ++p) {
+                for (int64_t p = 0; p < n_patch; ++p) {
                     const unsigned long long* s = h.data() + 12 * p;
                     for (int k = 0; k < 6; ++k) acc[k] += (double)(s[k + 1] - s[k]);
                     lo = std::min(lo, s[0]); hi = std::max(hi, s[6]);
@@ -705,19 +820,19 @@ extern "C" int fep_ctx_destroy(fep_ctx* c) {
                     st_ids += (double)(s[10] - s[0]); st_data += (double)(s[11] - s[10]); st_bar += (double)(s[1] - s[11]);
                 }
                 std::fprintf(stderr, "[fep] staging of thread 0's wave: ids %.0f, node data %.0f, LDS writes + barrier (the other waves) %.0f\n",
-                             st_ids / c->n_patch, st_data / c->n_patch, st_bar / c->n_patch);
+                             st_ids / n_patch, st_data / n_patch, st_bar / n_patch);
                 std::fprintf(stderr, "[fep] phase clocks, mean per workgroup of %lld (stage, phase1, phase2, wait, image, phase3): "
-                             "%.0f %.0f %.0f %.0f %.0f %.0f  sum %.0f; first start -> last end %llu; shader clock %.0f MHz (s_memtime / s_memrealtime x 100 MHz over the workgroups)\n", (long long)c->n_patch,
-                             acc[0] / c->n_patch, acc[1] / c->n_patch, acc[2] / c->n_patch, acc[3] / c->n_patch, acc[4] / c->n_patch,
-                             acc[5] / c->n_patch, (acc[0] + acc[1] + acc[2] + acc[3] + acc[4] + acc[5]) / c->n_patch, hi - lo,
+                             "%.0f %.0f %.0f %.0f %.0f %.0f  sum %.0f; first start -> last end %llu; shader clock %.0f MHz (s_memtime / s_memrealtime x 100 MHz over the workgroups)\n", (long long)n_patch,
+                             acc[0] / n_patch, acc[1] / n_patch, acc[2] / n_patch, acc[3] / n_patch, acc[4] / n_patch,
+                             acc[5] / n_patch, (acc[0] + acc[1] + acc[2] + acc[3] + acc[4] + acc[5]) / n_patch, hi - lo,
                              real > 0 ? cyc / real * 100.0 : 0.0);
             }
         }
-        if (c->p1_clk && c->n_wg_p1 > 0) {               // mean shader clocks per phase of the LAST launch of each P1 tile kernel
-            const int64_t n = c->n_wg_p1;
+        if (c->p1.v.clk && c->p1.n_tiles > 0) {               // mean shader clocks per phase of the LAST launch of each P1 tile kernel
+            const int64_t n = c->p1.n_tiles;
             std::vector<unsigned long long> h((size_t)(16 * n));
             if (hipDeviceSynchronize() == hipSuccess &&
-                hipMemcpy(h.data(), c->p1_clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
+                hipMemcpy(h.data(), c->p1.v.clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
                 for (int k = 0; k < 2; ++k) {
                     double acc[5] = {0, 0, 0, 0, 0}, cyc = 0.0, real = 0.0;
                     int64_t seen = 0;
@@ -736,6 +851,7 @@ extern "C" int fep_ctx_destroy(fep_ctx* c) {
                 }
             }
         }
+        delete c->gen;
 #endif
         for (void* p : c->owned) (void)hipFree(p);
         for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);
@@ -769,23 +885,15 @@ extern "C" int fep_ctx_create(fep_ctx** ctx_out, int device_id, int elem_type, i
     return r;
 }
 
-// What the route set-ups read of fep_ctx_create's inputs
-struct MeshIn {
-    const Symbolic& S;
-    const int32_t* elem;
-    const double *coords, *dh1, *dh2, *wf;
-    bool validate;                                      // FEP_VALIDATE_PLAN: replay every plan against the symbolic phase
-};
-
 // P1 node route: the gather plan (fep_host.h, P1Plan) and its tables.  *taken = false: the product takes the element
 // route instead.
 static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
     *taken = false;
+    P1NodeRoute& r = c->p1;
     fep_host::P1Options opt;
-#ifdef FEP_ABLATION
     // FEP_P1_TILE=128: tiles of 128 blocks on 128 threads (16 instead of 8 resident per CU; VERDICT r3 item 5's structural
     // attempt: the K,F-only step measured 0.0706-0.0715 against 0.0629-0.0631 ms, profiles/r04_ablation.md)
-    if (const char* tl = fep_tune("FEP_P1_TILE")) c->tile = std::atoi(tl) == 128 ? 128 : 256;
+    if (const char* tl = fep_tune("FEP_P1_TILE")) r.v.tile = std::atoi(tl) == 128 ? 128 : 256;
     {   // FEP_P1_PATH=node_direct | node_list | node_unpacked | node2k: plans without one of the default's ingredients
         const char* pth = fep_tune("FEP_P1_PATH");
         auto is = [&](const char* v) { return pth && std::strcmp(pth, v) == 0; };
@@ -795,79 +903,62 @@ static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
         opt.allow_fused = !is("node2k");
         if (const char* sg = fep_tune("FEP_P1_SEGS")) opt.max_segs = std::max(1, std::min(std::atoi(sg), fep_host::kSegMax));
     }
-#endif
-    opt.tile = c->tile;
+    opt.tile = r.v.tile;
     fep_host::P1Plan P;
     FEP_TRY(fep_host::build_p1_plan(in.S, c->n_e, c->n_n, in.elem, opt, P));
     if (in.validate) {
         const int bad = fep_host::validate_p1_plan(P, in.S, c->n_e, c->n_n, in.elem);
         if (bad) { std::fprintf(stderr, "[fep] P1 plan fails check %d\n", bad); return FEP_EINVAL; }
     }
-#ifndef FEP_ABLATION
     // A mesh whose tiles do not fit the LDS-staged form or whose descriptor fields do not pack (node degree >= 2^12, ...)
     // takes the element route like every other element type: the product keeps ONE node route.
-    if (!(P.lds && P.pk)) {
+    if (!kAblationBuild && !(P.lds && P.pk)) {
         if (c->verbose) std::fprintf(stderr, "[fep] P1 plan without the LDS-staged packed form (lds %d pk %d): element route\n", (int)P.lds, (int)P.pk);
         return FEP_OK;
     }
-#endif
     *taken = true;
-    c->n_wg_p1 = (int)P.n_wg;
-    c->p1_lds = P.lds; c->lds_L = P.L; c->lds_C = P.C; c->p1_rng = P.rng; c->p1_pk = P.pk;
-    c->p1_fused = P.fused; c->p1_fused_rng = P.fused_rng; c->lds_NL = P.NL;
-#ifdef FEP_ABLATION
-    if (const char* am = fep_tune("FEP_P1_ASM")) c->asm_from_nodes = std::strcmp(am, "nodes") == 0;
-    if (const char* dm = fep_tune("FEP_P1_DMA")) c->p1_dma = std::strcmp(dm, "0") != 0;
+    r.n_tiles = (int)P.n_wg;
+    r.v.lds = P.lds; r.v.pk = P.pk;                     // (the product's plan has both: above)
+    r.L = P.L; r.C = P.C; r.rng = P.rng;
+    r.fused = P.fused; r.fused_rng = P.fused_rng; r.NL = P.NL;
+    if (const char* am = fep_tune("FEP_P1_ASM")) r.v.asm_from_nodes = std::strcmp(am, "nodes") == 0;
+    if (const char* dm = fep_tune("FEP_P1_DMA")) r.v.dma = std::strcmp(dm, "0") != 0;
     if (const char* fm = fep_tune("FEP_P1_FUSED"))
-        c->fused_mode = std::strcmp(fm, "off") == 0 ? 0 : std::strcmp(fm, "kf") == 0 ? 1 : 2;
+        r.v.fused_mode = std::strcmp(fm, "off") == 0 ? 0 : std::strcmp(fm, "kf") == 0 ? 1 : 2;
     if (fep_tune("FEP_P1_CLK") && P.n_wg > 0) {
-        FEP_TRY(dmalloc(c, &c->p1_clk, 16 * P.n_wg));
-        (void)hipMemset(c->p1_clk, 0, (size_t)(16 * P.n_wg) * sizeof(unsigned long long));
+        FEP_TRY(dmalloc(c, &r.v.clk, 16 * P.n_wg));
+        (void)hipMemset(r.v.clk, 0, (size_t)(16 * P.n_wg) * sizeof(unsigned long long));
     }
-#endif
-    FEP_TRY(upload(c, &c->perm2, P.perm2.data(), (int64_t)P.perm2.size()));
-    FEP_TRY(upload(c, &c->ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
+    // only the variants that read them get the direct kernel's gather list and the unpacked descriptors (never the product's plan)
+    if (!P.lds) FEP_TRY(upload(c, &r.perm2, P.perm2.data(), (int64_t)P.perm2.size()));
+    if (!(P.lds && P.pk)) {
+        FEP_TRY(upload(c, &r.segptr, in.S.segptr.data(), (int64_t)in.S.segptr.size()));
+        FEP_TRY(upload(c, &r.meta, in.S.meta.data(), (int64_t)in.S.meta.size()));
+        FEP_TRY(upload(c, &r.ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
+    }
     static_assert(fep_host::kRecInts == kRecInts && fep_host::kRecRng == kRecRng && fep_host::kRecNrng == kRecNrng &&
                   fep_host::kDescInts == 4 * (1 + kSegMax), "host and kernels agree on the tile record");
-    FEP_TRY(upload(c, &c->trec, P.rec.data(), (int64_t)P.rec.size()));
+    FEP_TRY(upload(c, &r.trec, P.rec.data(), (int64_t)P.rec.size()));
     if (P.lds) {
-        FEP_TRY(upload(c, &c->wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
-        FEP_TRY(upload(c, &c->perm_l, P.codes_pad.data(), (int64_t)P.codes_pad.size()));
-        if (P.pk) FEP_TRY(upload(c, &c->pk, (const uint2*)P.pkv.data(), (int64_t)P.pkv.size()));
+        FEP_TRY(upload(c, &r.wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
+        FEP_TRY(upload(c, &r.perm_l, P.codes_pad.data(), (int64_t)P.codes_pad.size()));
+        if (P.pk) FEP_TRY(upload(c, &r.pk, (const uint2*)P.pkv.data(), (int64_t)P.pkv.size()));
     }
     if (P.fused) {
-        FEP_TRY(upload(c, &c->el_nodes, P.elnodes.data(), (int64_t)P.elnodes.size()));
-        if (!P.fused_rng) FEP_TRY(upload(c, &c->wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size()));
-        FEP_TRY(dmalloc(c, &c->slot_counts, 256 * 16));
-        HIP_TRY(hipMemset(c->slot_counts, 0, 256 * 16 * sizeof(unsigned long long)));
+        FEP_TRY(upload(c, &r.el_nodes, P.elnodes.data(), (int64_t)P.elnodes.size()));
+        if (!P.fused_rng) FEP_TRY(upload(c, &r.wg_nlist, P.nlist_pad.data(), (int64_t)P.nlist_pad.size()));
+        FEP_TRY(dmalloc(c, &r.slot_counts, 256 * 16));
+        HIP_TRY(hipMemset(r.slot_counts, 0, 256 * 16 * sizeof(unsigned long long)));
     }
     if (c->verbose)
         std::fprintf(stderr, "[fep] P1 plan: %lld tiles of <= %d blocks in <= %d segment(s), staged elements %lld "
                      "(%.2f per element, <= %d per tile), staged nodes <= %d, codes <= %d; lds %d rng %d pk %d fused %d/%d\n",
                      (long long)P.n_wg, P.tile, P.n_segs, (long long)P.staged_total, (double)P.staged_total / (double)c->n_e,
                      P.L, P.NL, P.C, (int)P.lds, (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
-    FEP_TRY(dmalloc(c, &c->geo, 6 * c->n_e));
+    FEP_TRY(dmalloc(c, &r.geo, 6 * c->n_e));
     c->n_count_blocks = (int)grid_for(c->n_e, kBlock);
     return FEP_OK;
 }
-
-#ifdef FEP_ABLATION
-// FEP_GEN_PATH=node: node route for P2 / Q1 / Q2 (point_kernel + node_lds_kernel; measured on MI355X, 1 M elements:
-// Q1 0.276 vs 0.286 ms, P2 1.80 vs 1.30 ms, Q2 0.41 vs 0.34 ms per step — its LDS gather costs n_q times the P1 one).
-// *taken = false: no plan fits, the element route.
-static int setup_gen_node(fep_ctx* c, const MeshIn& in, bool* taken) {
-    fep_host::GnPlan G;
-    fep_host::build_gn_plan(in.S, c->n_p, c->n_q, c->n_e, G);
-    *taken = G.ok;
-    if (!G.ok) return FEP_OK;
-    c->gn_tile = G.tile; c->lds_L = G.L; c->lds_C = G.C; c->gn_lds = G.lds;
-    FEP_TRY(upload(c, &c->wg_elist, G.elist_pad.data(), (int64_t)G.elist_pad.size()));
-    FEP_TRY(upload(c, &c->perm_l, G.codes_pad.data(), (int64_t)G.codes_pad.size()));
-    FEP_TRY(upload(c, &c->ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
-    c->n_count_blocks = (int)grid_for(c->n_int, kBlock);
-    return FEP_OK;
-}
-#endif
 
 // Geometry of the element kernel from the coordinates (GEO) or from the streamed dphi arrays, fixed per type and form
 // (elem_geo_default): measured on MI355X (1 M elements, element kernel alone): recomputed geometry wins for Q1 (0.204 vs
@@ -878,11 +969,9 @@ static int setup_gen_node(fep_ctx* c, const MeshIn& in, bool* taken) {
 // gradient loads per point were a third of its workgroup's life), Q2 0.604 / 0.709, P2 0.632-0.638 / 0.700-0.710, Q1
 // 0.163-0.164 / 0.167-0.174: recomputed for every type in the patch form
 static void elem_form(fep_ctx* c, bool patch_form) {
-    c->elem_geo = elem_geo_default(c->elem_type, patch_form);
-#ifdef FEP_ABLATION
-    if (const char* ge = fep_tune("FEP_ELEM_GEO")) c->elem_geo = std::strcmp(ge, "0") != 0;
-    if (const char* lp = fep_tune("FEP_ELEM_LDS_PAD")) c->lds_pad = std::max(0, std::atoi(lp));
-#endif
+    c->elem_form.geo = elem_geo_default(c->elem_type, patch_form);
+    if (const char* ge = fep_tune("FEP_ELEM_GEO")) c->elem_form.geo = std::strcmp(ge, "0") != 0;
+    if (const char* lp = fep_tune("FEP_ELEM_LDS_PAD")) c->elem_form.lds_pad = std::max(0, std::atoi(lp));
 }
 
 // Patch form of the element route (no K_e round trip through HBM; same session, 0.25-4 M elements, profiles/r03_ablation.md,
@@ -902,31 +991,25 @@ static int setup_patch(fep_ctx* c, const MeshIn& in, bool* taken) {
     int tpb = c->elem_type == FEP_P2 ? 512 : c->elem_type == FEP_P4 ? FEP_P4_TPB : 256;
     int js = c->elem_type == FEP_P4 ? FEP_P4_JS : 1;
     bool shape_forced = false;
-#ifdef FEP_ABLATION
     if (const char* tpb_env = fep_tune("FEP_PATCH_TPB")) {
         tpb = std::atoi(tpb_env);
         const char* js_env = fep_tune("FEP_PATCH_JS");
         js = js_env ? std::atoi(js_env) : 1;
         shape_forced = true;
     }
-#endif
     int eb = 0;
     if (elements_per_workgroup(c, true, tpb, js, &eb) != FEP_OK) return FEP_EINVAL;      // no such instantiation
     fep_host::PatchPlan P;
     fep_host::PatchOptions popt;
-#ifdef FEP_ABLATION
     if (const char* po = fep_tune("FEP_PATCH_ORDER"))
         popt.order = std::strcmp(po, "consecutive") == 0 ? 0 : std::strcmp(po, "hilbert") == 0 ? 1 : 2;
-#endif
     // Q1 (64 elements per patch): 4 runs of 16 measured 6 % faster than 2 of 32; P2 with 56 elements: 4 runs of 14
     // (1.96 partials per element) 1-3 % faster than 2 of 28 (2.86); with 28 elements 2 runs of 14 (4 of 7: +7 %)
     popt.runs = (c->elem_type == FEP_Q1 || tpb == 512) ? 4 : 2;
     // (runs starting on 128-byte boundaries of the point arrays — 16 / gcd(16, n_q) elements — measured no faster and
     // cost a third more partials: the aligned starts leave short leftovers)
-#ifdef FEP_ABLATION
     if (const char* pr = fep_tune("FEP_PATCH_RUNS")) popt.runs = std::max(1, std::atoi(pr));
     if (const char* pa = fep_tune("FEP_PATCH_ALIGN")) popt.align = std::max(1, std::atoi(pa));
-#endif
     FEP_TRY(fep_host::build_patch_plan(in.S, c->n_p, c->n_e, c->n_n, in.elem, in.coords, eb, popt, P));
     if (!P.ok && tpb == 512 && js == 1 && !shape_forced) {         // the big patches cannot be built: the small ones
         tpb = 256;                                                  // (a forced shape is never changed silently)
@@ -940,55 +1023,53 @@ static int setup_patch(fep_ctx* c, const MeshIn& in, bool* taken) {
         if (bad) { std::fprintf(stderr, "[fep] patch plan fails check %d\n", bad); return FEP_EINVAL; }
     }
     *taken = true;
-    c->patch_tpb = tpb; c->patch_js = js;
-    c->patch_eb = P.eb; c->n_open = P.n_open; c->n_fopen = P.n_fopen; c->n_patch = P.n_patch;
+    PatchRoute& r = c->patch;
+    r.tpb = tpb; r.js = js;
+    r.eb = P.eb; r.n_open = P.n_open; r.n_fopen = P.n_fopen; r.n_patch = P.n_patch;
     // one zero pad entry after each item / code table: element_kernel reads them at clamped indices, also for a patch
     // without items
     P.items.push_back(fep_host::U2{0u, 0u});
     P.fitems.push_back(fep_host::U2{0u, 0u});
     P.codes.insert(P.codes.end(), 2, 0);
     P.fcodes.insert(P.fcodes.end(), 2, 0);
-    FEP_TRY(upload(c, &c->pt_desc, P.pdesc.data(), (int64_t)P.pdesc.size()));
-    FEP_TRY(upload(c, &c->pt_pel, P.pel.data(), (int64_t)P.pel.size()));
-    FEP_TRY(upload(c, &c->pt_pnodes, P.pnodes.data(), (int64_t)P.pnodes.size()));
-    FEP_TRY(upload(c, &c->pt_items, (const uint2*)P.items.data(), (int64_t)P.items.size()));
-    FEP_TRY(upload(c, &c->pt_codes, P.codes.data(), (int64_t)P.codes.size()));
-    FEP_TRY(upload(c, &c->pt_fitems, (const uint2*)P.fitems.data(), (int64_t)P.fitems.size()));
-    FEP_TRY(upload(c, &c->pt_fcodes, P.fcodes.data(), (int64_t)P.fcodes.size()));
-    FEP_TRY(upload(c, &c->pt_fix, (const uint4*)P.fix.data(), (int64_t)P.fix.size()));
-    FEP_TRY(upload(c, &c->pt_fixT, (const uint2*)P.fixT.data(), (int64_t)P.fixT.size()));
-    FEP_TRY(upload(c, &c->pt_ffix, (const uint4*)P.ffix.data(), (int64_t)P.ffix.size()));
-    FEP_TRY(upload(c, &c->pt_plist, P.plist.data(), (int64_t)P.plist.size()));
-#ifdef FEP_ABLATION
+    FEP_TRY(upload(c, &r.desc, P.pdesc.data(), (int64_t)P.pdesc.size()));
+    FEP_TRY(upload(c, &r.pel, P.pel.data(), (int64_t)P.pel.size()));
+    FEP_TRY(upload(c, &r.pnodes, P.pnodes.data(), (int64_t)P.pnodes.size()));
+    FEP_TRY(upload(c, &r.items, (const uint2*)P.items.data(), (int64_t)P.items.size()));
+    FEP_TRY(upload(c, &r.codes, P.codes.data(), (int64_t)P.codes.size()));
+    FEP_TRY(upload(c, &r.fitems, (const uint2*)P.fitems.data(), (int64_t)P.fitems.size()));
+    FEP_TRY(upload(c, &r.fcodes, P.fcodes.data(), (int64_t)P.fcodes.size()));
+    FEP_TRY(upload(c, &r.fix, (const uint4*)P.fix.data(), (int64_t)P.fix.size()));
+    FEP_TRY(upload(c, &r.fixT, (const uint2*)P.fixT.data(), (int64_t)P.fixT.size()));
+    FEP_TRY(upload(c, &r.ffix, (const uint4*)P.ffix.data(), (int64_t)P.ffix.size()));
+    FEP_TRY(upload(c, &r.plist, P.plist.data(), (int64_t)P.plist.size()));
     if (fep_tune("FEP_PHASE_CLK")) {
-        FEP_TRY(dmalloc(c, &c->phase_clk, 12 * P.n_patch));
-        (void)hipMemset(c->phase_clk, 0, (size_t)(12 * P.n_patch) * sizeof(unsigned long long));
+        FEP_TRY(dmalloc(c, &r.v.phase_clk, 12 * P.n_patch));
+        (void)hipMemset(r.v.phase_clk, 0, (size_t)(12 * P.n_patch) * sizeof(unsigned long long));
     }
-#endif
-    FEP_TRY(dmalloc(c, &c->Pc, 4 * P.n_part));
-    FEP_TRY(dmalloc(c, &c->Pf, 2 * P.n_fpart));
+    FEP_TRY(dmalloc(c, &r.Pc, 4 * P.n_part));
+    FEP_TRY(dmalloc(c, &r.Pf, 2 * P.n_fpart));
     if (c->verbose)
         std::fprintf(stderr, "[fep] patch plan: %lld patches of <= %d elements, %zu items (<= %d per patch), %lld open blocks of %lld, "
                      "%lld partials (%.2f per element), %lld open nodes\n", (long long)P.n_patch, P.eb, P.items.size(), P.max_items,
                      (long long)P.n_open, (long long)c->n_blk, (long long)P.n_part, (double)P.n_part / (double)c->n_e,
                      (long long)P.n_fopen);
-    c->n_count_blocks = (int)c->n_patch;
+    c->n_count_blocks = (int)r.n_patch;
     return FEP_OK;
 }
 
 // COO form of the element route: K_e / f_e through HBM, csr_reduce* and the force gather sum them per block / node
 static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& tstart) {
     elem_form(c, false);
+    CooRoute& r = c->coo;
     int eb = 0;
     if (elements_per_workgroup(c, false, kBlock, 1, &eb) != FEP_OK) return FEP_EINVAL;
     c->n_count_blocks = (int)grid_for(c->n_e, eb);
     // measured at ~1 M points per type (tools/elem_bench.py): the element-major layout pays for the 15-node element only
     // (P4: step 1.47 -> 1.35 ms; P2 0.96 -> 1.06, Q2 0.82 -> 0.94, Q1 0.22 -> 0.26: their stores lose coalescing)
-    c->kc_aos = c->elem_type == FEP_P4;
-#ifdef FEP_ABLATION
-    if (const char* kl = fep_tune("FEP_KC_LAYOUT")) c->kc_aos = std::strcmp(kl, "aos") == 0;
-    if (const char* cg = fep_tune("FEP_CSR_GATHERS")) c->csr_gathers = std::atoi(cg);
-#endif
+    r.kc_aos = c->elem_type == FEP_P4;
+    if (const char* kl = fep_tune("FEP_KC_LAYOUT")) r.kc_aos = std::strcmp(kl, "aos") == 0;
+    if (const char* cg = fep_tune("FEP_CSR_GATHERS")) r.v.csr_gathers = std::atoi(cg);
     const int n_p = c->n_p;
     const int64_t n_e = c->n_e;
     if ((int64_t)sym_block_count(n_p) * n_e >= (int64_t)1 << 30) return FEP_ERANGE;     // 2 * position fits int32
@@ -1000,12 +1081,12 @@ static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& t
             const int ab = (int)(v / n_e);
             const int64_t e = v - (int64_t)ab * n_e;
             int idx; bool tr;
-            sym_block_index(n_p, ab / n_p, ab % n_p, idx, tr, c->kc_aos);
-            const int64_t pos = c->kc_aos ? e * sym_block_count(n_p) + idx : (int64_t)idx * n_e + e;
+            sym_block_index(n_p, ab / n_p, ab % n_p, idx, tr, r.kc_aos);
+            const int64_t pos = r.kc_aos ? e * sym_block_count(n_p) + idx : (int64_t)idx * n_e + e;
             perm_sym[i] = (int32_t)(2 * pos + (tr ? 1 : 0));
         }
         perm_sym.resize(perm_sym.size() + 4, 0);                    // csr_reduce_pk_kernel reads the addresses four at a time
-        FEP_TRY(upload(c, &c->perm, perm_sym.data(), (int64_t)perm_sym.size()));
+        FEP_TRY(upload(c, &r.perm, perm_sym.data(), (int64_t)perm_sym.size()));
     }
     // one 8-byte descriptor per block, if its fields fit (count < 256, degree and slot < 4096)
     std::vector<uint2> pkc((size_t)c->n_blk);
@@ -1015,11 +1096,16 @@ static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& t
         fits = len < 256 && deg < 4096 && slot < 4096;
         pkc[b] = make_uint2((uint32_t)S.segptr[b], len | (deg << 8) | (slot << 20));
     }
-    if (fits) FEP_TRY(upload(c, &c->pkc, pkc.data(), (int64_t)pkc.size()));
-    FEP_TRY(upload(c, &c->tstart, tstart.data(), (int64_t)tstart.size()));
-    c->n_wg_p1 = (int)tstart.size() - 1;
-    FEP_TRY(dmalloc(c, &c->Kc, 4 * (int64_t)sym_block_count(n_p) * n_e));
-    FEP_TRY(dmalloc(c, &c->fe, 2 * (int64_t)n_p * n_e));
+    if (fits) {
+        FEP_TRY(upload(c, &r.pkc, pkc.data(), (int64_t)pkc.size()));
+    } else {                                            // csr_reduce_kernel reads every block's contribution list unpacked
+        FEP_TRY(upload(c, &r.segptr, S.segptr.data(), (int64_t)S.segptr.size()));
+        FEP_TRY(upload(c, &r.meta, S.meta.data(), (int64_t)S.meta.size()));
+    }
+    FEP_TRY(upload(c, &r.tstart, tstart.data(), (int64_t)tstart.size()));
+    r.n_tiles = (int)tstart.size() - 1;
+    FEP_TRY(dmalloc(c, &r.Kc, 4 * (int64_t)sym_block_count(n_p) * n_e));
+    FEP_TRY(dmalloc(c, &r.fe, 2 * (int64_t)n_p * n_e));
     return FEP_OK;
 }
 
@@ -1054,10 +1140,6 @@ static int choose_route(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>
     if (!taken) {
         c->route = Route::Coo;
         FEP_TRY(setup_coo(c, in, tstart));
-    }
-    if (c->route != Route::Patch) {                     // every block's contribution list (the node routes and the COO form)
-        FEP_TRY(upload(c, &c->segptr, in.S.segptr.data(), (int64_t)in.S.segptr.size()));
-        FEP_TRY(upload(c, &c->meta, in.S.meta.data(), (int64_t)in.S.meta.size()));
     }
     return FEP_OK;
 }
@@ -1121,7 +1203,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     FEP_TRY(choose_route(c, MeshIn{S, elements_h, coords_h, dhatp1_h, dhatp2_h, wf_h, env_now("FEP_VALIDATE_PLAN") != nullptr},
                          tstart));
     FEP_TRY(dmalloc(c, &c->blk_counts, c->n_count_blocks));
-    FEP_TRY(launch_geometry(c));
+    FEP_TRY(launch_geometry(c, c->route == Route::P1Node ? c->p1.geo : nullptr));
     if (hipDeviceSynchronize() != hipSuccess) { g_last_hip = (int)hipGetLastError(); return FEP_EHIP; }
     *ctx_out = c;
     return FEP_OK;
@@ -1148,22 +1230,23 @@ extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int6
     if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", tag);
     else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", tag, c->n_p, c->n_q);
     std::snprintf(el, sizeof el, "%s%selement_kernel<%d, %d, %s, %s, %s, %d, %d>", dp ? "" : pt, dp ? "" : " + ", c->n_p, c->n_q, b(dp),
-                  b(c->elem_geo), b(patch), patch ? c->patch_tpb : 256, patch ? c->patch_js : 1);
-    if (c->route == Route::P1Node && c->p1_lds && dp && which == 1 && c->p1_fused && c->fused_mode >= 1) {
-        std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", c->tile, b(c->p1_fused_rng), b(c->p1_dma));
-    } else if (c->route == Route::P1Node && c->p1_lds) {
-        std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, c->tile, b(c->p1_rng), b(c->p1_pk));
+                  b(c->elem_form.geo), b(patch), patch ? c->patch.tpb : 256, patch ? c->patch.js : 1);
+    const P1NodeRoute& p1 = c->p1;
+    if (c->route == Route::P1Node && p1.v.lds && dp && which == 1 && p1.fused && p1.v.fused_mode >= 1) {
+        std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", p1.v.tile, b(p1.fused_rng), b(p1.v.dma));
+    } else if (c->route == Route::P1Node && p1.v.lds) {
+        std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, p1.v.tile, b(p1.rng), b(p1.v.pk));
     } else if (c->route == Route::P1Node) {
         std::snprintf(tmp, sizeof tmp, "%s + p1_node_kernel", pt);
 #ifdef FEP_ABLATION
     } else if (c->route == Route::GenNode) {            // (Drucker-Prager only: fep_ctx_set_model)
         if (!dp) return FEP_ESTATE;
-        std::snprintf(tmp, sizeof tmp, "point_kernel<%d, %d> + node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, c->n_p, c->n_q, c->gn_tile);
+        std::snprintf(tmp, sizeof tmp, "point_kernel<%d, %d> + node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, c->n_p, c->n_q, c->gen->tile);
 #endif
     } else if (patch) {
         std::snprintf(tmp, sizeof tmp, "%s + fixup_kernel", el);
     } else {
-        std::snprintf(tmp, sizeof tmp, "%s + %s", el, c->pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
+        std::snprintf(tmp, sizeof tmp, "%s + %s", el, c->coo.pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
     }
     std::snprintf(buf, (size_t)cap, "%s", tmp);
     return FEP_OK;
@@ -1212,7 +1295,7 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     // the ds / s scratch of the two-kernel node routes must exist before the first fep_step_dev (which may run inside a
     // stream capture).  P1 contexts with the one-kernel step only need it for accepting calls that also ask for K / F
     // without ds / s (allocated on first use, outside any capture, by those rare callers).
-    if (!element_route(c) && !(c->route == Route::P1Node && c->p1_fused)) FEP_TRY(point_scratch(c, nullptr, true, true));
+    if (!element_route(c) && !(c->route == Route::P1Node && c->p1.fused)) FEP_TRY(point_scratch(c, nullptr, true, true));
     // every parameter constant over the mesh (the reference's demos): the kernels skip the four arrays
     bool uni = fep_tune("FEP_NO_UNIFORM") == nullptr;
     for (int64_t k = 1; uni && k < c->n_int; ++k)
@@ -1287,7 +1370,6 @@ static int prof_mark(fep_ctx* c, hipStream_t st) {
 }
 
 static constexpr size_t kLdsDefault = 64 * 1024;        // dynamic LDS a launch gets without raising the kernel's limit
-static constexpr size_t kLdsNodeLds = 48 * 1024;        // (node_lds_kernel raises it from 48 KiB on)
 
 // Nodes of no element get no block: no kernel writes their force except the COO form's force gather.  Their F is zeroed
 // per call, before mark 0 on the node routes, inside stage A on the patch route (in_stage_a).
@@ -1297,30 +1379,40 @@ static int zero_orphan_forces(fep_ctx* c, hipStream_t st, double* f_out, bool in
     return FEP_OK;
 }
 
+// What fep_step_dev, a staged step and fep_assemble_dev open with: the orphans' forces on the node routes, mark 0, the
+// orphans' forces on the patch route
+static int begin_call(fep_ctx* c, hipStream_t st, double* f_out) {
+    FEP_TRY(zero_orphan_forces(c, st, f_out, false));
+    FEP_TRY(prof_mark(c, st));
+    return zero_orphan_forces(c, st, f_out, true);
+}
+
 // element routes, stage A: element_kernel.  Patch form: phase 3 writes the caller's CSR values / force, fixup_kernel the
-// open rest; COO form: K_e / f_e to HBM (c->Kc, c->fe) when K / F are wanted
+// open rest; COO form: K_e / f_e to HBM (coo.Kc, coo.fe) when K / F are wanted.  The one launcher the two forms share: it
+// reads `ef` and, by the route, the patch form's tables or the COO form's scratch
 template <bool FROM_U>
-static int launch_element(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept,
+static int launch_element(fep_ctx* c, const ElemForm& ef, hipStream_t st, const double* u, E0 e0, double* ep, int accept,
                           double* eout, double* s, double* ds, uint8_t* indp, uint2* blk_counts, double* k_data, double* f_out) {
     const bool patch = c->route == Route::Patch;
-    double* Kc = !patch && k_data ? c->Kc : nullptr;
-    double* fe = !patch && f_out ? c->fe : nullptr;
-    const PatchArgs pa{c->pt_desc, c->pt_pel, c->pt_pnodes, c->pt_items, c->pt_codes, c->pt_fitems, c->pt_fcodes, c->Pc, c->Pf,
+    const PatchRoute& pr = c->patch;                    // (all defaults on the COO form: no tables, 256 threads)
+    double* Kc = !patch && k_data ? c->coo.Kc : nullptr;
+    double* fe = !patch && f_out ? c->coo.fe : nullptr;
+    const PatchArgs pa{pr.desc, pr.pel, pr.pnodes, pr.items, pr.codes, pr.fitems, pr.fcodes, pr.Pc, pr.Pf,
                        patch ? k_data : nullptr, patch ? f_out : nullptr
 #ifdef FEP_ABLATION
-                       , c->phase_clk
+                       , pr.v.phase_clk
 #endif
     };
-    FEP_TRY(elem_shape(c->elem_type, patch, c->elem_geo, c->patch_tpb, c->patch_js, [&](auto et, auto pf, auto geo, auto tpb_c, auto js_c) {
+    FEP_TRY(elem_shape(c->elem_type, patch, ef.geo, pr.tpb, pr.js, [&](auto et, auto pf, auto geo, auto tpb_c, auto js_c) {
         using ET = decltype(et);
         constexpr bool PATCH = decltype(pf)::value, GEO = decltype(geo)::value;
         constexpr int TPB = decltype(tpb_c)::value, JS = decltype(js_c)::value;
         using Cfg = ElemCfg<ET::NP, ET::NQ, GEO, TPB, JS>;
-        if (c->patch_eb != 0 && c->patch_eb != Cfg::EB) return FEP_ESTATE;
+        if (pr.eb != 0 && pr.eb != Cfg::EB) return FEP_ESTATE;
         hipLaunchKernelGGL((element_kernel<ET::NP, ET::NQ, FROM_U, GEO, PATCH, TPB, JS>),
-                           dim3(PATCH ? (unsigned)c->n_patch : grid_for(c->n_e, Cfg::EB)), dim3(TPB), (size_t)c->lds_pad, st, c->n_e,
+                           dim3(PATCH ? (unsigned)pr.n_patch : grid_for(c->n_e, Cfg::EB)), dim3(TPB), (size_t)ef.lds_pad, st, c->n_e,
                            c->elem, c->dphi1, c->dphi2, c->weight, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear,
-                           c->bulk, c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk_counts, Kc, fe, c->kc_aos ? 1 : 0, pa);
+                           c->bulk, c->eta, c->c, c->matu, accept, eout, s, ds, indp, blk_counts, Kc, fe, c->coo.kc_aos ? 1 : 0, pa);
         return FEP_OK;
     }));
     HIP_TRY(hipGetLastError());
@@ -1329,24 +1421,24 @@ static int launch_element(fep_ctx* c, hipStream_t st, const double* u, E0 e0, do
 
 // COO form, stage B: K_e blocks -> CSR values (the force gather rides in the reduce kernel's launch: the workgroups past
 // the last tile take 256 nodes each; so does the counter sum).  *f_due: F is still to be gathered (stage C)
-static int launch_reduce(fep_ctx* c, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d,
+static int launch_reduce(fep_ctx* c, const CooRoute& r, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d,
                          bool* counted, bool* f_due) {
     *f_due = f_out && !k_data;
     if (!k_data) return FEP_OK;
-    ForceArgs fa{c->n_n, c->iptr, c->ilist, c->fe, f_out};
-    const unsigned grid = (unsigned)c->n_wg_p1 + (counts_d ? 1u : 0u) + (f_out ? grid_for(c->n_n, kBlock) : 0u);
+    ForceArgs fa{c->n_n, c->iptr, c->ilist, r.fe, f_out};
+    const unsigned grid = (unsigned)r.n_tiles + (counts_d ? 1u : 0u) + (f_out ? grid_for(c->n_n, kBlock) : 0u);
     auto reduce = [&](auto gathers) {
         hipLaunchKernelGGL(csr_reduce_kernel<decltype(gathers)::value>, dim3(grid), dim3(kBlock), 0, st,
-                           c->n_wg_p1, c->tstart, c->segptr, c->perm, c->meta, c->Kc, k_data, c->n_count_blocks,
+                           r.n_tiles, r.tstart, r.segptr, r.perm, r.meta, r.Kc, k_data, c->n_count_blocks,
                            c->blk_counts, counts_d, fa);
     };
-    if (c->pkc)
-        hipLaunchKernelGGL(csr_reduce_pk_kernel, dim3(grid), dim3(kBlock), 0, st, c->n_wg_p1,
-                           c->tstart, c->pkc, c->perm, c->Kc, k_data, c->n_count_blocks, c->blk_counts, counts_d, fa);
+    if (r.pkc)
+        hipLaunchKernelGGL(csr_reduce_pk_kernel, dim3(grid), dim3(kBlock), 0, st, r.n_tiles,
+                           r.tstart, r.pkc, r.perm, r.Kc, k_data, c->n_count_blocks, c->blk_counts, counts_d, fa);
 #ifdef FEP_ABLATION
-    else if (c->csr_gathers == 2) reduce(int_c<2>{});
-    else if (c->csr_gathers == 6) reduce(int_c<6>{});
-    else if (c->csr_gathers == 8) reduce(int_c<8>{});
+    else if (r.v.csr_gathers == 2) reduce(int_c<2>{});
+    else if (r.v.csr_gathers == 6) reduce(int_c<6>{});
+    else if (r.v.csr_gathers == 8) reduce(int_c<8>{});
 #endif
     else reduce(int_c<4>{});                             // (descriptor fields too wide for the packed form: four gathers in flight)
     HIP_TRY(hipGetLastError());
@@ -1355,21 +1447,21 @@ static int launch_reduce(fep_ctx* c, hipStream_t st, double* k_data, double* f_o
 }
 
 // COO form, stage C: the force gather when the reduce kernel did not take it
-static int launch_force(fep_ctx* c, hipStream_t st, double* f_out) {
+static int launch_force(fep_ctx* c, const CooRoute& r, hipStream_t st, double* f_out) {
     hipLaunchKernelGGL(force_reduce_kernel, dim3(grid_for(c->n_n, kBlock)), dim3(kBlock), 0, st,
-                       c->n_n, c->iptr, c->ilist, c->fe, f_out);
+                       c->n_n, c->iptr, c->ilist, r.fe, f_out);
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
 
 // patch form, stage B: open blocks / open nodes from the patches' partials (+ the branch counters on the side)
-static int launch_fixup(fep_ctx* c, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d, bool* counted) {
-    const unsigned nb_k = k_data ? grid_for(c->n_open, kBlock) : 0u;
-    const unsigned nb_f = f_out ? grid_for(c->n_fopen, kBlock) : 0u;
+static int launch_fixup(fep_ctx* c, const PatchRoute& r, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d, bool* counted) {
+    const unsigned nb_k = k_data ? grid_for(r.n_open, kBlock) : 0u;
+    const unsigned nb_f = f_out ? grid_for(r.n_fopen, kBlock) : 0u;
     const unsigned grid = nb_k + nb_f + (counts_d ? 1u : 0u);
     if (grid == 0) return FEP_OK;
-    hipLaunchKernelGGL(fixup_kernel, dim3(grid), dim3(kBlock), 0, st, (int)nb_k, c->n_open, c->pt_fix, c->pt_fixT, c->n_fopen, c->pt_ffix,
-                       c->pt_plist, c->Pc, c->Pf, k_data, f_out, c->n_count_blocks, c->blk_counts, counts_d);
+    hipLaunchKernelGGL(fixup_kernel, dim3(grid), dim3(kBlock), 0, st, (int)nb_k, r.n_open, r.fix, r.fixT, r.n_fopen, r.ffix,
+                       r.plist, r.Pc, r.Pf, k_data, f_out, c->n_count_blocks, c->blk_counts, counts_d);
     HIP_TRY(hipGetLastError());
     *counted = counts_d != nullptr;
     return FEP_OK;
@@ -1377,67 +1469,68 @@ static int launch_fixup(fep_ctx* c, hipStream_t st, double* k_data, double* f_ou
 
 // P1 node route, stage B: the assembly kernel (reads ds / s, writes CSR values and nodal force; with `counts_d` it also
 // sums the point kernel's per-workgroup branch counters: *counted)
-static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                          unsigned long long* counts_d, bool* counted) {
+static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, const double* ds, const double* s, double* k_data,
+                          double* f_out, unsigned long long* counts_d, bool* counted) {
     if (!((k_data && ds) || (f_out && s))) return FEP_OK;
     if (!k_data) ds = nullptr;
     if (!f_out) s = nullptr;
-    const int n_wg = c->n_wg_p1;
+    const int n_wg = r.n_tiles;
     const unsigned grid = 8 * ((n_wg + 7) / 8);
 #ifdef FEP_ABLATION
-    if (c->p1_fused && c->asm_from_nodes) {
+    if (r.fused && r.v.asm_from_nodes) {
         // opt-in (FEP_P1_ASM=nodes): assembly-only form of the one-kernel step, geometry from the tile's LDS-staged nodes
         // instead of the 48-byte record per staged element (same values bit for bit; 25 % fewer bytes but one barrier
         // and the geometry arithmetic more: 72.0 against 66.4 us at 1 M elements, profiles/r02_ablation.md)
-        const size_t lds_stage = (((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * 2 + 15) & ~(size_t)15) +
-                                 (size_t)c->lds_NL * 2 * sizeof(double2);
-        const size_t lds = std::max(lds_stage, (size_t)c->tile * 3 * sizeof(double2));
-        if (c->lds_L > 256 || c->lds_NL > 256) return FEP_ESTATE;
-        FEP_TRY(with_bool(c->p1_fused_rng, [&](auto rng) {
+        const size_t lds_stage = (((size_t)r.L * 15 * sizeof(double) + (size_t)r.C * 2 + 15) & ~(size_t)15) +
+                                 (size_t)r.NL * 2 * sizeof(double2);
+        const size_t lds = std::max(lds_stage, (size_t)r.v.tile * 3 * sizeof(double2));
+        if (r.L > 256 || r.NL > 256) return FEP_ESTATE;
+        FEP_TRY(with_bool(r.fused_rng, [&](auto rng) {
             return launch_lds(p1_fused_kernel<false, 256, decltype(rng)::value, 1, 1, true>, grid, 256, lds, kLdsDefault, st,
-                              c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l, c->wg_elist,
-                              c->wg_nlist, c->el_nodes, c->pk, c->trec, c->xy, c->p1tab,
+                              c->n_e, r.L, r.C, r.NL, r.perm_l, r.wg_elist,
+                              r.wg_nlist, r.el_nodes, r.pk, r.trec, c->xy, c->p1tab,
                               (const double*)nullptr, make_e0(nullptr), (const double*)nullptr, c->shear, c->bulk, c->eta,
                               c->c, c->matu, (double*)nullptr, (double*)nullptr, (double*)nullptr, (uint8_t*)nullptr,
                               k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, c->n_count_blocks, c->blk_counts, counts_d,
-                              c->p1_clk ? c->p1_clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr);
+                              r.v.clk ? r.v.clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr);
         }));
         *counted = counts_d != nullptr;
         return FEP_OK;
     }
-    if (!c->p1_lds) {
+    if (!r.v.lds) {
         hipLaunchKernelGGL(p1_node_kernel, dim3(grid_for(c->n_blk, kBlock)), dim3(kBlock), 0, st,
-                           c->n_blk, c->n_e, c->segptr, c->perm2, c->meta, c->ncol, c->geo, ds, s, k_data, f_out);
+                           c->n_blk, c->n_e, r.segptr, r.perm2, r.meta, r.ncol, r.geo, ds, s, k_data, f_out);
         HIP_TRY(hipGetLastError());
         return FEP_OK;
     }
 #else
-    if (!c->p1_lds) return FEP_ESTATE;
+    if (!r.v.lds) return FEP_ESTATE;
 #endif
     // operands + codes while gathering, then the same LDS holds the tile's output (4*TPB values + forces)
-    const size_t lds = std::max((size_t)c->lds_L * 15 * sizeof(double) + (size_t)c->lds_C * sizeof(uint16_t),
-                                (size_t)c->tile * 3 * sizeof(double2));
+    const size_t lds = std::max((size_t)r.L * 15 * sizeof(double) + (size_t)r.C * sizeof(uint16_t),
+                                (size_t)r.v.tile * 3 * sizeof(double2));
     if (c->verbose) {
         static bool once = false;
         if (!once) {
             once = true;
             std::fprintf(stderr, "[fep] p1 assembly kernel: %d tiles of <= %d blocks, staged elements <= %d, codes <= %d, "
-                         "LDS %zu bytes per workgroup\n", n_wg, c->tile, c->lds_L, c->lds_C, lds);
+                         "LDS %zu bytes per workgroup\n", n_wg, r.v.tile, r.L, r.C, lds);
         }
     }
     // tiles of 128 blocks (ablation build, FEP_P1_TILE) or 256 (128 / 512 were measured slower, profiles/r01_ablation.md)
-    FEP_TRY(with_ablation_bool<false>(c->tile == 128, [&](auto t128) {
+    FEP_TRY(with_ablation_bool<false>(r.v.tile == 128, [&](auto t128) {
         constexpr int TPB = decltype(t128)::value ? 128 : 256;
-        if (c->lds_L > TPB) return FEP_ESTATE;          // one staged element per lane (fep_host.h)
-        return with_bool(c->p1_rng, [&](auto rng) {
-            // (the product's node route always has packed descriptors: setup_p1_node)
-            return with_ablation_bool<true>(c->p1_pk, [&](auto pk) {
+        if (r.L > TPB) return FEP_ESTATE;          // one staged element per lane (fep_host.h)
+        return with_bool(r.rng, [&](auto rng) {
+            // (the product's node route always has packed descriptors: setup_p1_node.  That instantiation never reads
+            // segptr, meta and ncol -- every use lies behind the compile-time PK -- and gets them as NULL)
+            return with_ablation_bool<true>(r.v.pk, [&](auto pk) {
                 return launch_lds(p1_node_lds_kernel<TPB, decltype(rng)::value, 1, decltype(pk)::value>, grid, TPB, lds,
-                                  kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol,
-                                  c->wg_elist, c->pk, c->trec, c->geo, ds, s, k_data, f_out, n_wg,
+                                  kLdsDefault, st, c->n_e, r.L, r.C, r.segptr, r.perm_l, r.meta, r.ncol,
+                                  r.wg_elist, r.pk, r.trec, r.geo, ds, s, k_data, f_out, n_wg,
                                   c->n_count_blocks, c->blk_counts, counts_d
 #ifdef FEP_ABLATION
-                                  , c->p1_clk
+                                  , r.v.clk
 #endif
                                   );
             });
@@ -1447,74 +1540,34 @@ static int launch_p1_node(fep_ctx* c, hipStream_t st, const double* ds, const do
     return FEP_OK;
 }
 
-#ifdef FEP_ABLATION
-// GenNode route, stage A: point_kernel
-static int launch_point(fep_ctx* c, hipStream_t st, const double* u, E0 e0, double* ep, int accept, double* eout,
-                        double* s, double* ds, uint8_t* indp, uint2* blk) {
-    FEP_TRY(with_type(c->elem_type, [&](auto et) {
-        using ET = decltype(et);
-        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
-        else {
-            hipLaunchKernelGGL((point_kernel<ET::NP, ET::NQ>), dim3(grid_for(c->n_int, kBlock)), dim3(kBlock), 0, st, c->n_e,
-                               c->elem, c->xy, c->dh1, c->dh2, c->wf, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
-                               accept, eout, s, ds, indp, blk);
-            return FEP_OK;
-        }
-    }));
-    HIP_TRY(hipGetLastError());
-    return FEP_OK;
-}
-
-// GenNode route, stage B: node_lds_kernel
-static int launch_gn_node(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                          unsigned long long* counts_d, bool* counted) {
-    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
-    const int n_wg = (int)grid_for(c->n_blk, c->gn_tile);
-    const unsigned grid = 8 * ((n_wg + 7) / 8);
-    FEP_TRY(with_type(c->elem_type, [&](auto et) {
-        using ET = decltype(et);
-        if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
-        else return with_bool(c->gn_tile == 256, [&](auto t256) {
-            constexpr int TPB = decltype(t256)::value ? 256 : 128;
-            return launch_lds(node_lds_kernel<ET::NP, ET::NQ, TPB>, grid, TPB, c->gn_lds, kLdsNodeLds, st, c->n_blk, c->n_e,
-                              c->lds_L, c->lds_C, c->segptr, c->perm_l, c->meta, c->ncol, c->wg_elist, c->elem, c->xy,
-                              c->dh1, c->dh2, c->wf, k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out, n_wg,
-                              c->n_count_blocks, c->blk_counts, counts_d);
-        });
-    }));
-    *counted = counts_d != nullptr;
-    return FEP_OK;
-}
-#endif  // FEP_ABLATION
-
 // P1, one kernel per step (non-accepting calls with K and/or F wanted): p1_fused_kernel, then the counter sum
-static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, const double* ep, double* eout, double* s,
-                           double* ds, uint8_t* indp, double* k_data, double* f_out, unsigned long long* counts_d) {
-    const bool dma = c->p1_dma;
-    const size_t Cp = dma ? ((size_t)c->lds_C + 127) & ~(size_t)127 : (size_t)c->lds_C;
-    const size_t NLp = dma ? ((size_t)c->lds_NL + 63) & ~(size_t)63 : (size_t)c->lds_NL;
-    const size_t lds_stage = (((size_t)c->lds_L * 15 * sizeof(double) + Cp * 2 + 15) & ~(size_t)15) + NLp * 2 * sizeof(double2);
-    const size_t lds = std::max(lds_stage, (size_t)c->tile * 3 * sizeof(double2));
-    const int n_wg = c->n_wg_p1;
+static int launch_p1_fused(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, const double* u, E0 e0, const double* ep, double* eout,
+                           double* s, double* ds, uint8_t* indp, double* k_data, double* f_out, unsigned long long* counts_d) {
+    const bool dma = r.v.dma;
+    const size_t Cp = dma ? ((size_t)r.C + 127) & ~(size_t)127 : (size_t)r.C;
+    const size_t NLp = dma ? ((size_t)r.NL + 63) & ~(size_t)63 : (size_t)r.NL;
+    const size_t lds_stage = (((size_t)r.L * 15 * sizeof(double) + Cp * 2 + 15) & ~(size_t)15) + NLp * 2 * sizeof(double2);
+    const size_t lds = std::max(lds_stage, (size_t)r.v.tile * 3 * sizeof(double2));
+    const int n_wg = r.n_tiles;
     const unsigned grid = 8 * ((n_wg + 7) / 8);
     // L, NL <= threads: one staged element / node per lane (fep_host.h)
-    if (c->lds_L > c->tile || c->lds_NL > c->tile) return FEP_ESTATE;
+    if (r.L > r.v.tile || r.NL > r.v.tile) return FEP_ESTATE;
     // (the product runs the one-kernel step for K,F-only calls: fused_mode 1)
     const bool full = eout || s || ds || indp;
     FEP_TRY(with_ablation_bool<false>(full, [&](auto full_c) {
-        return with_bool(c->p1_fused_rng, [&](auto rng) {
+        return with_bool(r.fused_rng, [&](auto rng) {
             return with_ablation_bool<false>(dma, [&](auto dma_c) {
-                return with_ablation_bool<false>(c->tile == 128, [&](auto t128) {
+                return with_ablation_bool<false>(r.v.tile == 128, [&](auto t128) {
                     constexpr int TPB = decltype(t128)::value ? 128 : 256;
                     return launch_lds(p1_fused_kernel<decltype(full_c)::value, TPB, decltype(rng)::value, 1, 1, false, decltype(dma_c)::value>,
-                                      grid, TPB, lds, kLdsDefault, st, c->n_e, c->lds_L, c->lds_C, c->lds_NL, c->perm_l,
-                                      c->wg_elist, c->wg_nlist, c->el_nodes,
-                                      c->pk, c->trec, c->xy, c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
+                                      grid, TPB, lds, kLdsDefault, st, c->n_e, r.L, r.C, r.NL, r.perm_l,
+                                      r.wg_elist, r.wg_nlist, r.el_nodes,
+                                      r.pk, r.trec, c->xy, c->p1tab, u, e0, ep, c->shear, c->bulk, c->eta, c->c, c->matu,
                                       eout, s, ds, indp, k_data, f_out, n_wg,
-                                      counts_d ? c->slot_counts : (unsigned long long*)nullptr, (const double*)nullptr,
+                                      counts_d ? r.slot_counts : (unsigned long long*)nullptr, (const double*)nullptr,
                                       (const double*)nullptr, 0, (const uint2*)nullptr, (unsigned long long*)nullptr
 #ifdef FEP_ABLATION
-                                      , c->p1_clk ? c->p1_clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr
+                                      , r.v.clk ? r.v.clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr
 #endif
                                       );
                 });
@@ -1522,7 +1575,7 @@ static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, c
         });
     }));
     if (counts_d) {
-        hipLaunchKernelGGL(counts_finalize_kernel, dim3(1), dim3(256), 0, st, c->slot_counts, counts_d);
+        hipLaunchKernelGGL(counts_finalize_kernel, dim3(1), dim3(256), 0, st, r.slot_counts, counts_d);
         HIP_TRY(hipGetLastError());
     }
     return FEP_OK;
@@ -1534,12 +1587,12 @@ static int launch_p1_fused(fep_ctx* c, hipStream_t st, const double* u, E0 e0, c
 static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
                            unsigned long long* counts_d, bool* counted, bool* f_due) {
     *counted = *f_due = false;
-    if (c->route == Route::P1Node) return launch_p1_node(c, st, ds, s, k_data, f_out, counts_d, counted);
+    if (c->route == Route::P1Node) return launch_p1_node(c, c->p1, st, ds, s, k_data, f_out, counts_d, counted);
 #ifdef FEP_ABLATION
-    if (c->route == Route::GenNode) return launch_gn_node(c, st, ds, s, k_data, f_out, counts_d, counted);
+    if (c->route == Route::GenNode) return launch_gn_node(c, *c->gen, st, ds, s, k_data, f_out, counts_d, counted);
 #endif
-    if (c->route == Route::Patch) return launch_fixup(c, st, k_data, f_out, counts_d, counted);
-    return launch_reduce(c, st, k_data, f_out, counts_d, counted, f_due);
+    if (c->route == Route::Patch) return launch_fixup(c, c->patch, st, k_data, f_out, counts_d, counted);
+    return launch_reduce(c, c->coo, st, k_data, f_out, counts_d, counted, f_due);
 }
 
 // Stage A of a staged step, and of Drucker-Prager's two-kernel P1 step: the point kernel of the context's model (ModelKernels),
@@ -1574,12 +1627,12 @@ static int launch_assembly_stages(fep_ctx* c, hipStream_t st, const double* ds, 
                                   bool own_call) {
     bool counted = false, f_due = false;
     if (element_route(c) && (own_call || k_data || f_out))
-        FEP_TRY(launch_element<false>(c, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s),
+        FEP_TRY(launch_element<false>(c, c->elem_form, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s),
                                       const_cast<double*>(ds), nullptr, nullptr, k_data, f_out));
     if (own_call) FEP_TRY(prof_mark(c, st));
     FEP_TRY(launch_assembly(c, st, ds, s, k_data, f_out, nullptr, &counted, &f_due));
     FEP_TRY(prof_mark(c, st));
-    if (f_due) FEP_TRY(launch_force(c, st, f_out));
+    if (f_due) FEP_TRY(launch_force(c, c->coo, st, f_out));
     FEP_TRY(prof_mark(c, st));
     return FEP_OK;
 }
@@ -1593,9 +1646,7 @@ static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, doub
     if (!c->ds_int || !c->s_int || !c->point_blk) return FEP_ESTATE;
     if (k_data_d && !ds_d) ds_d = c->ds_int;
     if (f_out_d && !s_d) s_d = c->s_int;
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    FEP_TRY(begin_call(c, st, f_out_d));
     FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, cnt ? c->point_blk : nullptr,
                                field_d, scale));
     FEP_TRY(prof_mark(c, st));
@@ -1624,8 +1675,8 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     if (c->model != FEP_MODEL_DP)
         return step_model(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt);
     const bool point_outputs = e_out_d || s_d || ds_d || ind_p_d;
-    const bool fused = c->route == Route::P1Node && c->p1_fused && !accept && (k_data_d || f_out_d) &&
-                       c->fused_mode > (point_outputs ? 1 : 0);
+    const bool fused = c->route == Route::P1Node && c->p1.fused && !accept && (k_data_d || f_out_d) &&
+                       c->p1.v.fused_mode > (point_outputs ? 1 : 0);
     if (!element_route(c) && !fused) {                  // the assembly kernel reads ds / s from HBM
         FEP_TRY(point_scratch(c, st, k_data_d && !ds_d, f_out_d && !s_d));
         if (k_data_d && !ds_d) ds_d = c->ds_int;
@@ -1642,9 +1693,7 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
     if (fix_side && !side) { HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming)); }
 #endif
     bool counted = false, f_due = false;
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    FEP_TRY(begin_call(c, st, f_out_d));
     if (c->route == Route::P1Node) {
         if (!fused)                                     // (the one-kernel step is all stage B)
             FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, nullptr, 0.0));
@@ -1657,22 +1706,22 @@ extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const d
         ms = side;
 #endif
     } else {
-        FEP_TRY(launch_element<true>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
+        FEP_TRY(launch_element<true>(c, c->elem_form, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
     }
     FEP_TRY(prof_mark(c, ms));
     if (fused) {
-        FEP_TRY(launch_p1_fused(c, st, u_d, e0, ep_prev_d, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt));
+        FEP_TRY(launch_p1_fused(c, c->p1, st, u_d, e0, ep_prev_d, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt));
         counted = true;
     } else {
         FEP_TRY(launch_assembly(c, ms, ds_d, s_d, k_data_d, f_out_d, cnt, &counted, &f_due));
     }
     FEP_TRY(prof_mark(c, ms));
-    if (f_due) FEP_TRY(launch_force(c, ms, f_out_d));
+    if (f_due) FEP_TRY(launch_force(c, c->coo, ms, f_out_d));
     FEP_TRY(prof_mark(c, ms));
 #ifdef FEP_ABLATION
     if (fix_side) {
         HIP_TRY(hipEventRecord(ev_b, side));
-        FEP_TRY(launch_element<true>(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
+        FEP_TRY(launch_element<true>(c, c->elem_form, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
         HIP_TRY(hipStreamWaitEvent(st, ev_b, 0));
     }
 #endif
@@ -1712,9 +1761,7 @@ extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, co
     if (!fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
     hipStream_t st = (hipStream_t)stream;
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, false));
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(zero_orphan_forces(c, st, f_out_d, true));
+    FEP_TRY(begin_call(c, st, f_out_d));
     return launch_assembly_stages(c, st, ds_d, s_d, k_data_d, f_out_d, true);
 }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / LDS / occupancy table of every kernel of libfep_hip.so as hipcc reports it
-(-Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).  `python tools/kernel_resources.py [filter]`."""
+(-Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).  `python tools/kernel_resources.py [--ablation] [filter]`;
+--ablation compiles the measurement build (-DFEP_ABLATION)."""
 import os
 import re
 import subprocess
@@ -10,11 +11,13 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def main():
-    flt = sys.argv[1] if len(sys.argv) > 1 else ''
+    args = [a for a in sys.argv[1:] if a != '--ablation']
+    defs = ['-DFEP_ABLATION'] if '--ablation' in sys.argv[1:] else []
+    flt = args[0] if args else ''
     rows = []
     for src in ('fep_api.hip', 'fep_solver.hip'):
-        out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
-                              '-Rpass-analysis=kernel-resource-usage', '-o', '/dev/null', src], cwd=CSRC,
+        out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared'] + defs +
+                             ['-Rpass-analysis=kernel-resource-usage', '-o', '/dev/null', src], cwd=CSRC,
                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
         cur = None
         for line in out.splitlines():
