@@ -666,8 +666,6 @@ extern "C" int fep_return_map_field_host(int model, int device_id, int64_t n_int
 using fep_host::Symbolic;
 using fep_host::build_symbolic;
 
-static_assert(fep_host::kSegMax == fep::kSegMax, "tile descriptor layout shared by host and kernels");
-
 // `p1_geo`: the node route's record array when that is the route (NULL: no records are written)
 static int launch_geometry(fep_ctx* c, double* p1_geo) {
     return with_type(c->elem_type, [&](auto et) {
@@ -784,7 +782,7 @@ static int launch_gn_node(fep_ctx* c, const GenNodeRoute& r, hipStream_t st, con
                           double* f_out, unsigned long long* counts_d, bool* counted) {
     if (!((k_data && ds) || (f_out && s))) return FEP_OK;
     const int n_wg = (int)grid_for(c->n_blk, r.tile);
-    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    const unsigned grid = xcd_grid(n_wg);
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
         using ET = decltype(et);
         if constexpr (ET::type == FEP_P1 || ET::type == FEP_P4) return FEP_EINVAL;
@@ -936,8 +934,6 @@ static int setup_p1_node(fep_ctx* c, const MeshIn& in, bool* taken) {
         FEP_TRY(upload(c, &r.meta, in.S.meta.data(), (int64_t)in.S.meta.size()));
         FEP_TRY(upload(c, &r.ncol, in.S.ncol.data(), (int64_t)in.S.ncol.size()));
     }
-    static_assert(fep_host::kRecInts == kRecInts && fep_host::kRecRng == kRecRng && fep_host::kRecNrng == kRecNrng &&
-                  fep_host::kDescInts == 4 * (1 + kSegMax), "host and kernels agree on the tile record");
     FEP_TRY(upload(c, &r.trec, P.rec.data(), (int64_t)P.rec.size()));
     if (P.lds) {
         FEP_TRY(upload(c, &r.wg_elist, P.elist_pad.data(), (int64_t)P.elist_pad.size()));
@@ -1088,13 +1084,14 @@ static int setup_coo(fep_ctx* c, const MeshIn& in, const std::vector<int32_t>& t
         perm_sym.resize(perm_sym.size() + 4, 0);                    // csr_reduce_pk_kernel reads the addresses four at a time
         FEP_TRY(upload(c, &r.perm, perm_sym.data(), (int64_t)perm_sym.size()));
     }
-    // one 8-byte descriptor per block, if its fields fit (count < 256, degree and slot < 4096)
+    // one 8-byte descriptor per block, if its fields fit (fep_layout.h: pkc)
     std::vector<uint2> pkc((size_t)c->n_blk);
     bool fits = fep_tune("FEP_CSR_UNPACKED") == nullptr;
     for (int64_t b = 0; b < c->n_blk && fits; ++b) {
-        const uint32_t len = (uint32_t)(S.segptr[b + 1] - S.segptr[b]), deg = S.meta[b] >> 16, slot = S.meta[b] & 0x7fffu;
-        fits = len < 256 && deg < 4096 && slot < 4096;
-        pkc[b] = make_uint2((uint32_t)S.segptr[b], len | (deg << 8) | (slot << 20));
+        const Meta mt = unpack_meta(S.meta[b]);
+        const Pkc f{S.segptr[b + 1] - S.segptr[b], mt.deg, mt.slot};
+        fits = pkc_fits(f);
+        pkc[b] = make_uint2((uint32_t)S.segptr[b], pack_pkc(f.len, f.deg, f.slot));
     }
     if (fits) {
         FEP_TRY(upload(c, &r.pkc, pkc.data(), (int64_t)pkc.size()));
@@ -1475,15 +1472,13 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
     if (!k_data) ds = nullptr;
     if (!f_out) s = nullptr;
     const int n_wg = r.n_tiles;
-    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    const unsigned grid = xcd_grid(n_wg);
 #ifdef FEP_ABLATION
     if (r.fused && r.v.asm_from_nodes) {
         // opt-in (FEP_P1_ASM=nodes): assembly-only form of the one-kernel step, geometry from the tile's LDS-staged nodes
         // instead of the 48-byte record per staged element (same values bit for bit; 25 % fewer bytes but one barrier
         // and the geometry arithmetic more: 72.0 against 66.4 us at 1 M elements, profiles/r02_ablation.md)
-        const size_t lds_stage = (((size_t)r.L * 15 * sizeof(double) + (size_t)r.C * 2 + 15) & ~(size_t)15) +
-                                 (size_t)r.NL * 2 * sizeof(double2);
-        const size_t lds = std::max(lds_stage, (size_t)r.v.tile * 3 * sizeof(double2));
+        const size_t lds = (size_t)p1_tile_lds(r.L, r.C, r.NL, r.v.tile, false, true).total;
         if (r.L > 256 || r.NL > 256) return FEP_ESTATE;
         FEP_TRY(with_bool(r.fused_rng, [&](auto rng) {
             return launch_lds(p1_fused_kernel<false, 256, decltype(rng)::value, 1, 1, true>, grid, 256, lds, kLdsDefault, st,
@@ -1507,8 +1502,7 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
     if (!r.v.lds) return FEP_ESTATE;
 #endif
     // operands + codes while gathering, then the same LDS holds the tile's output (4*TPB values + forces)
-    const size_t lds = std::max((size_t)r.L * 15 * sizeof(double) + (size_t)r.C * sizeof(uint16_t),
-                                (size_t)r.v.tile * 3 * sizeof(double2));
+    const size_t lds = (size_t)p1_tile_lds(r.L, r.C, 0, r.v.tile, false, false).total;
     if (c->verbose) {
         static bool once = false;
         if (!once) {
@@ -1544,12 +1538,9 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
 static int launch_p1_fused(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, const double* u, E0 e0, const double* ep, double* eout,
                            double* s, double* ds, uint8_t* indp, double* k_data, double* f_out, unsigned long long* counts_d) {
     const bool dma = r.v.dma;
-    const size_t Cp = dma ? ((size_t)r.C + 127) & ~(size_t)127 : (size_t)r.C;
-    const size_t NLp = dma ? ((size_t)r.NL + 63) & ~(size_t)63 : (size_t)r.NL;
-    const size_t lds_stage = (((size_t)r.L * 15 * sizeof(double) + Cp * 2 + 15) & ~(size_t)15) + NLp * 2 * sizeof(double2);
-    const size_t lds = std::max(lds_stage, (size_t)r.v.tile * 3 * sizeof(double2));
+    const size_t lds = (size_t)p1_tile_lds(r.L, r.C, r.NL, r.v.tile, dma, true).total;
     const int n_wg = r.n_tiles;
-    const unsigned grid = 8 * ((n_wg + 7) / 8);
+    const unsigned grid = xcd_grid(n_wg);
     // L, NL <= threads: one staged element / node per lane (fep_host.h)
     if (r.L > r.v.tile || r.NL > r.v.tile) return FEP_ESTATE;
     // (the product runs the one-kernel step for K,F-only calls: fused_mode 1)

@@ -23,8 +23,10 @@
 #include <vector>
 
 #include "../../include/fep.h"
+#include "fep_layout.h"
 
 namespace fep_host {
+using namespace fep_layout;                             // every packed word of the plans: pack_* / unpack_* / *_fits
 
 struct U2 { uint32_t x, y; };
 
@@ -68,7 +70,7 @@ struct Symbolic {
     std::vector<int32_t> iptr, ilist;        // node -> incident (a*n_e + e), ordered by (e, a)
     std::vector<int32_t> nptr, ncol;         // node CSR (sorted neighbour nodes); block id = position in ncol
     std::vector<int32_t> segptr, perm;       // block -> contributions (a*NP+b)*n_e + e
-    std::vector<uint32_t> meta;              // block -> (deg << 16) | (diag << 15) | slot
+    std::vector<uint32_t> meta;              // block -> pack_meta(deg, diag, slot)
 };
 
 inline int build_symbolic(int n_p, int64_t n_e, int64_t n_n, const int32_t* elem, Symbolic& S) {
@@ -111,7 +113,7 @@ inline int build_symbolic(int n_p, int64_t n_e, int64_t n_n, const int32_t* elem
     S.nptr.assign(n_n + 1, 0);
     int64_t tot = 0;
     for (int64_t n = 0; n < n_n; ++n) {
-        if (deg[n] > 0x7fff) return FEP_ERANGE;
+        if (!meta_fits(deg[n], 0, deg[n])) return FEP_ERANGE;              // (a slot field that holds the degree holds every slot)
         tot += deg[n];
         if (tot >= INT32_MAX / 4) return FEP_ERANGE;
         S.nptr[n + 1] = (int32_t)tot;
@@ -134,7 +136,7 @@ inline int build_symbolic(int n_p, int64_t n_e, int64_t n_n, const int32_t* elem
                     ++slot;
                     const int64_t blk = S.nptr[n] + slot;
                     S.ncol[blk] = buf[i].first;
-                    S.meta[blk] = ((uint32_t)deg[n] << 16) | (buf[i].first == (int32_t)n ? 0x8000u : 0u) | (uint32_t)slot;
+                    S.meta[blk] = pack_meta((uint32_t)deg[n], buf[i].first == (int32_t)n ? 1u : 0u, (uint32_t)slot);
                     S.segptr[blk] = (int32_t)pos;
                 }
                 S.perm[pos++] = buf[i].second;
@@ -163,31 +165,23 @@ inline int row_tiles(const Symbolic& S, int64_t n_n, int tile, std::vector<int32
 // P1 fast path: gather plan of p1_node_lds_kernel / p1_fused_kernel.
 //
 // A tile = up to kSegMax SEGMENTS, each a run of consecutive nodes (with all their blocks), at most `tile` blocks and
-// 255 nodes in total.  One segment per tile gives the row strips of round 1 (36 consecutive nodes: ~150 staged elements
+// kTileNodesMax nodes in total.  One segment per tile gives the row strips of round 1 (36 consecutive nodes: ~150 staged elements
 // for 72 owned ones on a row-numbered structured mesh).  With two segments the second one is the longest run of
 // consecutive, still unassigned neighbour ids of the first (on a row-numbered mesh: the row above), which makes the
 // tile two rows high: ~114 staged elements and ~80 instead of ~114 staged nodes for the same 256 blocks.  Every tile
 // still writes its CSR values / forces as one contiguous range PER SEGMENT.  Which tiling is used is decided by
 // counting: the multi-segment one must stage at least 5 % fewer elements over the whole mesh.
 //
-//   tdesc  kDescInts int32 per tile: [pk_base, n_blocks, n_nodes, n_segments | staged elements << 4 | staged nodes << 16]
-//          then kSegMax x [first_block, n_blocks, first_node, n_nodes]  (scalar loads in the kernels)
-//   rec    what the kernels read of the three per-tile tables: ONE record of kRecInts int32 (256 bytes, so 64-byte aligned
-//          in an allocation that is) per tile, fetched in one scalar round trip at kernel entry:
-//          [0, kDescInts) the tile's tdesc, [kRecRng, +16) its element runs (rng_tab), [kRecNrng, +16) its node runs
-//          (nrng_tab); everything else zero.  A plan in list form (rng / fused_rng false) leaves the run part zero:
-//          eight runs of cumulative count 0, none of them live.
+// The tables and the format of every word in them: fep_layout.h (tile record, pk, gather code, el_nodes).
+//   tdesc / rec           per tile its descriptor / the record the kernels fetch (descriptor + run tables)
 //   elist_pad / rng_tab   sorted unique elements of the tile, padded to L with its first element / as <= 8 runs
-//   codes_pad             gather codes (local element << 4 | a << 2 | b) in tile block order, padded to C
+//   codes_pad             gather codes in tile block order, padded to C
 //   pkv                   per lane of the tile (lanes sorted by descending segment length) the packed descriptor
-//                         x: code offset:11 | len:4 | deg:8 | slot:8 | diag:1,  y: block index in tile | node index << 8
 //   fused step:  nlist_pad / nrng_tab  the nodes the staged elements touch;  elnodes  per staged element its three
-//                tile-local node indices (10 bits each) | owner bit 30 (first tile in order that stages the element)
+//                tile-local node indices | owner bit (first tile in order that stages the element)
 // ---------------------------------------------------------------------------------------
-constexpr int kSegMax = 4;
-constexpr int kDescInts = 4 * (1 + kSegMax);
-constexpr int kRecInts = 64, kRecRng = 32, kRecNrng = 48;
-static_assert(kDescInts <= kRecRng && kRecRng + 16 <= kRecNrng && kRecNrng + 16 <= kRecInts, "the tile record's parts do not overlap");
+
+constexpr int kTileNodesMax = (int)field_max(kHeadNnBits < kPkNodeBits ? kHeadNnBits : kPkNodeBits);   // the node count / index fields
 
 struct P1Options {
     int tile = 256;
@@ -201,7 +195,7 @@ struct P1Plan {
     int64_t n_wg = 0, staged_total = 0, staged_nodes_total = 0;
     std::vector<int32_t> tdesc;
     std::vector<int32_t> rec;                // tile records (see above): the device copy of tdesc, rng_tab and nrng_tab
-    std::vector<int32_t> perm2;              // global gather list (e << 4 | a << 2 | b), block order: direct kernel
+    std::vector<int32_t> perm2;              // global gather list (pack_gather(e, a, b)), block order: direct kernel
     bool lds = false, rng = false, pk = false, fused = false, fused_rng = false;
     int L = 0, C = 0, NL = 0;
     std::vector<int32_t> elist_pad, rng_tab, nlist_pad, nrng_tab;
@@ -233,7 +227,7 @@ inline int make_tiles(const Symbolic& S, int64_t n_n, int tile, int max_segs, st
                                             max_segs > 1 ? tile / max_segs + 8 : tile);
             int64_t n = start;
             int blocks = 0;
-            while (n < n_n && !assigned[n] && blocks + (S.nptr[n + 1] - S.nptr[n]) <= seg_budget && total_nodes + (int)(n - start) < 255) {
+            while (n < n_n && !assigned[n] && blocks + (S.nptr[n + 1] - S.nptr[n]) <= seg_budget && total_nodes + (int)(n - start) < kTileNodesMax) {
                 blocks += S.nptr[n + 1] - S.nptr[n];
                 ++n;
             }
@@ -308,13 +302,13 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
     P = P1Plan();
     P.tile = opt.tile;
     const int TILE = opt.tile;
-    if (n_e >= (int64_t)1 << 27) return FEP_ERANGE;
+    if (!gather_fits(n_e, 0, 0, kGatherElemBits)) return FEP_ERANGE;                // (the element field holds n_e itself)
     const int64_t n_blk = (int64_t)S.ncol.size();
     P.perm2.resize(S.perm.size());
     for (size_t i = 0; i < S.perm.size(); ++i) {
         const int64_t code = S.perm[i];
         const int64_t ab = code / n_e, e = code - ab * n_e;
-        P.perm2[i] = (int32_t)((e << 4) | ((ab / 3) << 2) | (ab % 3));
+        P.perm2[i] = (int32_t)pack_gather((uint32_t)e, (uint32_t)(ab / 3), (uint32_t)(ab % 3));
     }
     std::vector<Tile> tiles;
     const int r = make_tiles(S, n_n, TILE, max_segs, tiles);
@@ -330,7 +324,7 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
                 if (t.nseg < 2) continue;
                 l.clear();
                 for (int s = 0; s < t.nseg; ++s)
-                    for (int32_t c = S.segptr[t.fb[s]]; c < S.segptr[t.fb[s] + t.nb[s]]; ++c) l.push_back(P.perm2[c] >> 4);
+                    for (int32_t c = S.segptr[t.fb[s]]; c < S.segptr[t.fb[s] + t.nb[s]]; ++c) l.push_back(unpack_gather((uint32_t)P.perm2[c]).i);
                 std::sort(l.begin(), l.end());
                 count[g] = (int32_t)(std::unique(l.begin(), l.end()) - l.begin());
             }
@@ -360,7 +354,8 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
             d[4 + 4 * s] = t.fb[s]; d[5 + 4 * s] = t.nb[s]; d[6 + 4 * s] = t.fn[s]; d[7 + 4 * s] = t.nn[s];
             nb += t.nb[s]; nn += t.nn[s];
         }
-        d[0] = (int32_t)pk_base; d[1] = nb; d[2] = nn; d[3] = t.nseg;
+        d[0] = (int32_t)pk_base; d[1] = nb;
+        set_tile_head(d, TileHead{nn, 0, t.nseg, 0, 0});                             // (the staged counts join it below)
         pk_base += nb;
         P.n_segs = std::max(P.n_segs, t.nseg);
     }
@@ -379,10 +374,10 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
             const Tile& t = tiles[g];
             std::vector<int32_t>& l = lists[g];
             for (int s = 0; s < t.nseg; ++s)
-                for (int32_t c = S.segptr[t.fb[s]]; c < S.segptr[t.fb[s] + t.nb[s]]; ++c) l.push_back(P.perm2[c] >> 4);
+                for (int32_t c = S.segptr[t.fb[s]]; c < S.segptr[t.fb[s] + t.nb[s]]; ++c) l.push_back(unpack_gather((uint32_t)P.perm2[c]).i);
             std::sort(l.begin(), l.end());
             l.erase(std::unique(l.begin(), l.end()), l.end());
-            if (l.size() > 4095) too_big[g] = 1;
+            if (!in_field((int64_t)l.size(), kHeadElBits)) too_big[g] = 1;            // (its count: the head; its slots: the gather code)
         }
     });
     for (int64_t g = 0; g < n_wg; ++g)
@@ -413,9 +408,9 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
             std::vector<uint16_t>& cd = codes[g];
             for (int s = 0; s < t.nseg; ++s)
                 for (int32_t c = S.segptr[t.fb[s]]; c < S.segptr[t.fb[s] + t.nb[s]]; ++c) {
-                    const int32_t e = P.perm2[c] >> 4;
-                    const int32_t loc = std::lower_bound(where.begin(), where.end(), std::make_pair(e, (int32_t)0))->second;
-                    cd.push_back((uint16_t)((loc << 4) | (P.perm2[c] & 15)));
+                    const Gather gc = unpack_gather((uint32_t)P.perm2[c]);
+                    const int32_t loc = std::lower_bound(where.begin(), where.end(), std::make_pair((int32_t)gc.i, (int32_t)0))->second;
+                    cd.push_back((uint16_t)pack_gather((uint32_t)loc, (uint32_t)gc.a, (uint32_t)gc.b));
                 }
         }
     });
@@ -425,14 +420,18 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
         cmax = std::max(cmax, codes[g].size());
         P.staged_total += (int64_t)lists[g].size();
     }
-    for (int64_t g = 0; g < n_wg; ++g) P.tdesc[(size_t)g * kDescInts + 3] |= (int32_t)(lists[g].size() << 4);   // staged elements of the tile
+    for (int64_t g = 0; g < n_wg; ++g) {                                             // staged elements of the tile
+        int32_t* d = P.tdesc.data() + g * kDescInts;
+        TileHead h = tile_head(d);
+        h.n_el = (int)lists[g].size();
+        set_tile_head(d, h);
+    }
     P.C = (int)((cmax + 7) & ~(size_t)7);
     P.L = (int)((lmax + 1) & ~(size_t)1);
     // 15 doubles per staged element; the staged kernels hold ONE element and <= 4 gather codes per lane in registers.
     // (A tile of B blocks over N nodes stages at most B - N elements — every staged element is a distinct neighbour
     // relation of one of its nodes — and touches at most B nodes, so with B <= tile = threads both always fit.)
-    P.lds = lmax <= (size_t)TILE && cmax <= 4 * (size_t)TILE &&
-            (size_t)P.L * 15 * sizeof(double) + (size_t)P.C * 2 <= 96 * 1024;
+    P.lds = lmax <= (size_t)TILE && cmax <= 4 * (size_t)TILE && p1_tile_lds(P.L, P.C, 0, TILE, false, false).total <= kP1LdsLimit;
     if (!P.lds) return FEP_OK;
     const int64_t LP = P.L, CP = P.C;
     P.elist_pad.assign((size_t)(n_wg * LP), 0);
@@ -448,7 +447,7 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
     }
     P.rng = fits;
     // packed block descriptors, if every field fits its bit width; lanes sorted by descending segment length
-    bool pk_ok = opt.allow_pk && CP <= 2047 && TILE <= 256;
+    bool pk_ok = opt.allow_pk && in_field(CP, kPkOffBits) && in_field(TILE - 1, kPkBlkBits);
     P.pkv.assign((size_t)n_blk, U2{0u, 0u});
     std::vector<uint8_t> pk_bad((size_t)n_wg, 0);
     if (pk_ok)
@@ -458,7 +457,7 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
                 const Tile& t = tiles[g];
                 const int32_t* d = P.tdesc.data() + g * kDescInts;
                 const int nb = d[1];
-                if (d[2] > 255) { pk_bad[g] = 1; continue; }
+                if (tile_head(d).nn > kTileNodesMax) { pk_bad[g] = 1; continue; }
                 order.resize(nb); blk.resize(nb); node_of.resize(nb); off.resize(nb);
                 int k = 0, node_base = 0, o = 0;
                 for (int s = 0; s < t.nseg; ++s) {
@@ -478,12 +477,10 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
                 for (int lane = 0; lane < nb; ++lane) {
                     const int kk = order[lane];
                     const int32_t b = blk[kk];
-                    const uint32_t mt = S.meta[b];
-                    const uint32_t len = (uint32_t)(S.segptr[b + 1] - S.segptr[b]), deg = mt >> 16, slot = mt & 0x7fffu;
-                    const uint32_t diag = (mt >> 15) & 1u;
-                    if (len > 15 || deg > 255 || slot > 255 || off[kk] > 2047) { pk_bad[g] = 1; break; }
-                    P.pkv[(size_t)d[0] + lane] = U2{(uint32_t)off[kk] | (len << 11) | (deg << 15) | (slot << 23) | (diag << 31),
-                                                    (uint32_t)kk | ((uint32_t)node_of[kk] << 8)};
+                    const Meta mt = unpack_meta(S.meta[b]);
+                    const Pk f{off[kk], S.segptr[b + 1] - S.segptr[b], mt.deg, mt.slot, mt.diag, kk, node_of[kk]};
+                    if (!pk_fits(f)) { pk_bad[g] = 1; break; }
+                    P.pkv[(size_t)d[0] + lane] = U2{pack_pk_x(f.off, f.len, f.deg, f.slot, f.diag), pack_pk_y(f.blk, f.node)};
                 }
             }
         });
@@ -504,14 +501,12 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
                 for (int a = 0; a < 3; ++a) nl.push_back(elem[(int64_t)a * n_e + e]);
             std::sort(nl.begin(), nl.end());
             nl.erase(std::unique(nl.begin(), nl.end()), nl.end());
-            if (nl.size() > 1023) { nbad[g] = 1; continue; }
+            if (!in_field((int64_t)nl.size(), kElNodeBits)) { nbad[g] = 1; continue; }    // (a field that holds the count holds every index)
             for (size_t i = 0; i < l.size(); ++i) {
-                uint32_t word = 0u;
-                for (int a = 0; a < 3; ++a) {
-                    const int32_t nd = elem[(int64_t)a * n_e + l[i]];
-                    word |= (uint32_t)(std::lower_bound(nl.begin(), nl.end(), nd) - nl.begin()) << (10 * a);
-                }
-                P.elnodes[(size_t)(g * LP) + i] = word;
+                uint32_t loc[3];
+                for (int a = 0; a < 3; ++a)
+                    loc[a] = (uint32_t)(std::lower_bound(nl.begin(), nl.end(), elem[(int64_t)a * n_e + l[i]]) - nl.begin());
+                P.elnodes[(size_t)(g * LP) + i] = pack_el_nodes(loc[0], loc[1], loc[2], 0u);
             }
             for (size_t i = l.size(); i < (size_t)LP; ++i) P.elnodes[(size_t)(g * LP) + i] = P.elnodes[(size_t)(g * LP)];
         }
@@ -524,8 +519,12 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
     }
     if (nlmax == 0 || nlmax > (size_t)TILE) { P.elnodes.clear(); return FEP_OK; }
     for (int64_t g = 0; g < n_wg; ++g) {                                             // owner bit = slot < n_own; the count rides in the descriptor
-        for (int32_t i = 0; i < n_own[g]; ++i) P.elnodes[(size_t)(g * LP) + i] |= 1u << 30;
-        P.tdesc[(size_t)g * kDescInts + 2] |= n_own[g] << 8;
+        for (int32_t i = 0; i < n_own[g]; ++i) P.elnodes[(size_t)(g * LP) + i] |= pack_el_nodes(0u, 0u, 0u, 1u);
+        int32_t* d = P.tdesc.data() + g * kDescInts;
+        TileHead h = tile_head(d);
+        h.n_own = n_own[g];
+        h.n_nd = (int)nlists[g].size();                                              // staged nodes of the tile
+        set_tile_head(d, h);
     }
     const int64_t NLP = (int64_t)((nlmax + 1) & ~(size_t)1);
     P.NL = (int)NLP;
@@ -538,10 +537,8 @@ inline int build_p1_tables_segs(const Symbolic& S, int64_t n_e, int64_t n_n, con
         std::copy(nl.begin(), nl.end(), P.nlist_pad.begin() + g * NLP);
         if (nfits) runs_of(nl, P.nrng_tab.data() + g * 16, nfits);
     }
-    for (int64_t g = 0; g < n_wg; ++g) P.tdesc[(size_t)g * kDescInts + 3] |= (int32_t)(nlists[g].size() << 16);  // staged nodes of the tile
     P.fused_rng = nfits;
-    const size_t lds_f = (((size_t)P.L * 15 * sizeof(double) + (size_t)P.C * 2 + 15) & ~(size_t)15) + (size_t)NLP * 32;
-    P.fused = lds_f <= 96 * 1024;
+    P.fused = p1_tile_lds(P.L, P.C, P.NL, TILE, false, true).total <= kP1LdsLimit;
     if (!P.fused) P.elnodes.clear();
     return FEP_OK;
 }
@@ -588,8 +585,9 @@ inline int validate_p1_plan(const P1Plan& P, const Symbolic& S, int64_t n_e, int
     int64_t pk_base = 0;
     for (int64_t g = 0; g < P.n_wg; ++g) {
         const int32_t* d = P.tdesc.data() + g * kDescInts;
-        const int nseg = d[3] & 15, n_staged = (d[3] >> 4) & 4095, n_staged_nodes = (d[3] >> 16) & 4095;
-        const int nn_desc = d[2] & 255, n_own = d[2] >> 8;                           // (n_own is packed in only by the one-kernel plan)
+        const TileHead h = tile_head(d);
+        const int nseg = h.nseg, n_staged = h.n_el, n_staged_nodes = h.n_nd;
+        const int nn_desc = h.nn, n_own = h.n_own;                                   // (n_own is packed in only by the one-kernel plan)
         if (d[0] != pk_base || nseg < 1 || nseg > kSegMax || d[1] > P.tile || d[1] < 1 || n_own > n_staged) return 2;
         int nb = 0, nn = 0;
         for (int s = 0; s < nseg; ++s) {
@@ -618,26 +616,22 @@ inline int validate_p1_plan(const P1Plan& P, const Symbolic& S, int64_t n_e, int
         }
         if (P.rng) {
             const int32_t* r = P.rng_tab.data() + g * 16;
-            for (int i = 0; i < P.L; ++i) {
-                int e = r[0] + i;
-                for (int k = 1; k < 8; ++k) e = i >= r[2 * k - 1] ? r[2 * k] + (i - r[2 * k - 1]) : e;
-                e = i < r[15] ? e : r[0];
-                if (e != el[i]) return 7;
-            }
+            for (int i = 0; i < P.L; ++i)
+                if (run_entry(r, i) != el[i]) return 7;
         }
         if (P.pk) {
             std::vector<uint8_t> lane_blk((size_t)nb, 0);
             for (int lane = 0; lane < nb; ++lane) {
                 const U2 w = P.pkv[(size_t)d[0] + lane];
-                const int beg = (int)(w.x & 2047u), len = (int)((w.x >> 11) & 15u), deg = (int)((w.x >> 15) & 255u);
-                const int slot = (int)((w.x >> 23) & 255u), blk = (int)(w.y & 255u), nod = (int)((w.y >> 8) & 255u);
+                const Pk f = unpack_pk(w.x, w.y);
+                const int beg = f.off, len = f.len, deg = f.deg, slot = f.slot, blk = f.blk, nod = f.node;
                 if (beg + len > P.C || blk >= nb || nod >= nn || lane_blk[blk]) return 8;
                 lane_blk[blk] = 1;
                 const int rel = 4 * blk - 2 * slot;
                 if (rel < 0 || (rel >> 1) + deg + 1 > 2 * nb || slot >= deg) return 9;
                 for (int c = beg; c < beg + len; ++c) {
-                    const unsigned code = P.codes_pad[(size_t)g * P.C + c];
-                    if ((int)(code >> 4) >= n_list || ((code >> 2) & 3) > 2 || (code & 3) > 2) return 10;
+                    const Gather gc = unpack_gather(P.codes_pad[(size_t)g * P.C + c]);
+                    if (gc.i >= n_list || gc.a > 2 || gc.b > 2) return 10;
                 }
             }
         }
@@ -651,20 +645,16 @@ inline int validate_p1_plan(const P1Plan& P, const Symbolic& S, int64_t n_e, int
             if (n_nl != n_staged_nodes) return 19;
             if (P.fused_rng) {
                 const int32_t* r = P.nrng_tab.data() + g * 16;
-                for (int i = 0; i < P.NL; ++i) {
-                    int n = r[0] + i;
-                    for (int k = 1; k < 8; ++k) n = i >= r[2 * k - 1] ? r[2 * k] + (i - r[2 * k - 1]) : n;
-                    n = i < r[15] ? n : r[0];
-                    if (n != nl[i]) return 12;
-                }
+                for (int i = 0; i < P.NL; ++i)
+                    if (run_entry(r, i) != nl[i]) return 12;
             }
             for (int i = 0; i < P.L; ++i) {
                 const uint32_t w = P.elnodes[(size_t)g * P.L + i];
                 for (int a = 0; a < 3; ++a) {
-                    const int loc = (int)((w >> (10 * a)) & 1023u);
+                    const int loc = el_node(w, a);
                     if (loc >= P.NL || nl[loc] != elem[(int64_t)a * n_e + el[i]]) return 13;
                 }
-                if (((w >> 30) & 1u) != (i < n_own ? 1u : 0u)) return 14;                  // owner bit <=> slot < n_own
+                if (unpack_el_nodes(w).own != (i < n_own ? 1 : 0)) return 14;              // owner bit <=> slot < n_own
                 if (i < n_own) owners[el[i]]++;
             }
         }
@@ -677,7 +667,7 @@ inline int validate_p1_plan(const P1Plan& P, const Symbolic& S, int64_t n_e, int
 
 // ---------------------------------------------------------------------------------------
 // Node route of P2 / Q1 / Q2 (ablation build only, FEP_GEN_PATH=node): per tile of `tile` consecutive blocks the sorted unique
-// element list and 16-bit gather codes (local element << 8 | a << 4 | b).
+// element list and 16-bit gather codes (fep_layout.h: pack_gn_code).
 // ---------------------------------------------------------------------------------------
 struct GnPlan {
     bool ok = false;
@@ -703,11 +693,11 @@ inline void build_gn_plan(const Symbolic& S, int n_p, int n_q, int64_t n_e, GnPl
                 for (int32_t t = t0; t < t1; ++t) l.push_back((int32_t)(S.perm[t] % n_e));
                 std::sort(l.begin(), l.end());
                 l.erase(std::unique(l.begin(), l.end()), l.end());
-                if (l.size() > 256) { bad[g] = 1; continue; }
+                if (!l.empty() && !gn_code_fits((int64_t)l.size() - 1, n_p - 1, n_p - 1)) { bad[g] = 1; continue; }
                 for (int32_t t = t0; t < t1; ++t) {
                     const int64_t ab = S.perm[t] / n_e, e = S.perm[t] % n_e;
                     const int32_t loc = (int32_t)(std::lower_bound(l.begin(), l.end(), (int32_t)e) - l.begin());
-                    perm_l[t] = (uint16_t)((loc << 8) | ((int)(ab / n_p) << 4) | (int)(ab % n_p));
+                    perm_l[t] = (uint16_t)pack_gn_code((uint32_t)loc, (uint32_t)(ab / n_p), (uint32_t)(ab % n_p));
                 }
             }
         });
@@ -720,9 +710,9 @@ inline void build_gn_plan(const Symbolic& S, int n_p, int n_q, int64_t n_e, GnPl
             cmax = std::max(cmax, (size_t)(S.segptr[b1] - S.segptr[b0]));
         }
         const int L = (int)lmax, C = (int)((cmax + 7) & ~(size_t)7);
-        const size_t lds = ((size_t)(9 + 2 * n_p) * L * n_q + 2 * (size_t)n_p * n_q + n_q + (n_q & 1)) * sizeof(double) +
-                           (size_t)C * sizeof(uint16_t);
-        if (!ok || lmax > 256 || lds > 64 * 1024) continue;
+        if (!ok) continue;
+        const size_t lds = gn_lds_bytes(n_p, n_q, L, C);
+        if (lds > 64 * 1024) continue;
         G.ok = true; G.tile = TILE; G.L = L; G.C = C; G.lds = lds;
         G.elist_pad.assign((size_t)(n_wg * L), 0);
         G.codes_pad.assign((size_t)(n_wg * C), 0);
@@ -759,19 +749,10 @@ inline void build_gn_plan(const Symbolic& S, int n_p, int n_q, int64_t n_e, GnPl
 // Deterministic (fixed order, no atomics); the association differs from the flat element order of the COO route
 // ((a+b+c) + (d+e+f) instead of a+b+c+d+e+f for a vertex on a patch boundary), so the two routes agree to rounding only.
 //
-//   pdesc   kPatchDescInts int32 per patch: item_off, n_items, code_off, n_codes, fitem_off, n_fitems, fcode_off, n_fcodes
 //   pel     eb int32 per patch: its elements, ascending, padded with -1;   pnodes  [patch][a][local element] node ids (0 padded)
-//   items   x: code offset in the patch:13 | (count-1):6 | degree of the row node:12 | open:1
-//           y: closed: position of the block's first row in double2 units (2*nptr[n] + slot); open: partial slot
-//   codes   uint16 (position of the stored block in the LDS image: patch_image_pos) << 1 | transposed
-//   fitems  x: code offset:13 | (count-1):6 | open << 31;  y: node | force partial slot;   fcodes  patch_force_pos
-//   fix     per upper open block: x = position (as items.y), y = degree | count << 16, z = first partial slot,
-//           w = second partial slot (count <= 2) or offset into plist (count > 2: `count` slots, ascending patch)
-//   fixT    its mirror: x = position of the transposed block (0xffffffff: diagonal block, no mirror), y = degree of ITS row node
-//   ffix    per open node:  x = node, y = count, z / w as above
+//   pdesc, items, codes, fitems, fcodes, fix, fixT, ffix and the LDS image they address: fep_layout.h (patch route)
 // ---------------------------------------------------------------------------------------
 struct U4 { uint32_t x, y, z, w; };
-constexpr int kPatchDescInts = 8;
 
 struct PatchOptions {
     int order = 2;                                      // 0: consecutive elements, 1: Hilbert curve through the centroids,
@@ -791,26 +772,6 @@ struct PatchPlan {
     std::vector<U4> fix, ffix;
     std::vector<U2> fixT;
 };
-
-// Where the phase-3 LDS image keeps the stored block (j, a) of local element el, in 16-byte slots of a plane (fep_kernels.hip.h,
-// ElemCfg, uses the same formulas).  SKEWED: with the plain (j*n_p + a)*eb + el a step in a is eb slots and a step in j
-// n_p*eb slots — both multiples of 16 slots = the 256-byte bank row for every element type (eb is a multiple of 8, n_p*eb of
-// 16), so the gather of a CSR row's blocks, which walks j and a at fixed el, put all 16 lanes of a `ds_read_b128` group on ONE
-// slot (P4: 49 % of the LDS cycles were conflict cycles).  Odd element stride ebp = eb | 1, and one more slot per j when n_p
-// is even, make both steps odd.
-inline int patch_ebp(int eb) { return eb | 1; }
-inline int patch_image_period(int n_p, int eb) { return n_p * patch_ebp(eb) + ((n_p & 1) ? 0 : 1); }      // slots per j
-inline int patch_image_pos(int n_p, int eb, int j, int a, int el) { return j * patch_image_period(n_p, eb) + a * patch_ebp(eb) + el; }
-inline int patch_image_slots(int n_p, int eb) { return (n_p / 2 + 1) * patch_image_period(n_p, eb); }
-inline int patch_force_pos(int eb, int a, int el) { return a * patch_ebp(eb) + el; }
-
-// where element_kernel keeps the block (a, b) of K_e (same function as fep::sym_block_index, block-major numbering)
-inline void patch_block_index(int n_p, int a, int b, int& idx, bool& transposed) {
-    const int j = b >= a ? b - a : b - a + n_p;
-    const bool direct = 2 * j < n_p || (2 * j == n_p && a < n_p / 2);
-    if (direct) { idx = j * n_p + a; transposed = false; }
-    else { idx = (n_p - j) * n_p + b; transposed = true; }
-}
 
 // position of (x, y), 16 bits each, along the Hilbert curve of order 16
 inline uint32_t hilbert_d(uint32_t x, uint32_t y) {
@@ -950,7 +911,8 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
     P = PatchPlan();
     P.eb = eb;
     const int nj = n_p / 2 + 1;
-    if (eb < 1 || (int64_t)n_p * n_p * eb > 8192 || patch_image_slots(n_p, eb) >= 32768) return FEP_OK;       // field widths: plan not usable
+    // field widths (the last code offset of a full patch, the last slot of the image): plan not usable
+    if (eb < 1 || !in_field((int64_t)n_p * n_p * eb - 1, kItemOffBits) || !patch_code_fits(patch_image_slots(n_p, eb) - 1, 0)) return FEP_OK;
     const int64_t n_blk = (int64_t)S.ncol.size();
     std::vector<int32_t> patch_of;
     patch_grouping(S, n_p, n_e, n_n, elem, coords, eb, opt, P.pel, patch_of);
@@ -994,16 +956,16 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
     int64_t n_plist = 0;
     for (int64_t n = 0; n < n_n; ++n) {
         const uint32_t deg = (uint32_t)(S.nptr[n + 1] - S.nptr[n]);
-        if (deg > 4095) return FEP_OK;
+        if (!in_field(deg, kItemDegBits)) return FEP_OK;
         for (int32_t b = S.nptr[n]; b < S.nptr[n + 1]; ++b) {
             if (npb[b] < 2) continue;
             const int64_t m = S.ncol[b];
             if (m < n) { open_idx[b] = -2; continue; }
             open_idx[b] = (int32_t)P.fix.size();
-            U4 f{(uint32_t)(2 * (int64_t)S.nptr[n] + (b - S.nptr[n])), deg | ((uint32_t)npb[b] << 16), 0u, 0u};
+            U4 f{(uint32_t)(2 * (int64_t)S.nptr[n] + (b - S.nptr[n])), pack_fix(deg, npb[b]), 0u, 0u};
             if (npb[b] > 2) { f.w = (uint32_t)n_plist; n_plist += npb[b]; }
             P.fix.push_back(f);
-            U2 ft{0xffffffffu, 0u};
+            U2 ft{kNoMirror, 0u};
             if (m != n) {                                                    // the mirror block (m, n)
                 const int32_t* row = S.ncol.data() + S.nptr[m];
                 const int64_t slot = std::lower_bound(row, S.ncol.data() + S.nptr[m + 1], (int32_t)n) - row;
@@ -1054,8 +1016,8 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
                         const int32_t nb = elem[(int64_t)b * n_e + pe[el]];
                         const int32_t blk = (int32_t)(S.nptr[na] + (std::lower_bound(row, row_end, nb) - row));
                         int idx; bool tr;
-                        patch_block_index(n_p, a, b, idx, tr);
-                        tup.push_back(Tup{blk, (uint16_t)((patch_image_pos(n_p, eb, idx / n_p, idx % n_p, el) << 1) | (tr ? 1 : 0))});
+                        sym_block_index(n_p, a, b, idx, tr);
+                        tup.push_back(Tup{blk, (uint16_t)pack_patch_code((uint32_t)patch_image_pos(n_p, eb, idx / n_p, idx % n_p, el), tr ? 1u : 0u)});
                     }
                 }
             // (el, a, b) generation order = ascending element id: the stable sorts keep it inside every block / node
@@ -1069,17 +1031,17 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
                 while (j < tup.size() && tup[j].key == tup[i].key) ++j;
                 const int32_t b = tup[i].key;
                 const uint32_t cnt = (uint32_t)(j - i);
-                if (cnt > 64) { O.fail = 1; break; }
+                if (!in_field((int64_t)cnt - 1, kItemCntBits)) { O.fail = 1; break; }
                 const bool all_here = (int32_t)cnt == S.segptr[b + 1] - S.segptr[b];
                 if ((npb[b] < 2) != all_here) { O.fail = 2; break; }
                 if (open_idx[b] == -2) { i = j; continue; }                 // lower open block: its mirror carries the partial
                 if (open_idx[b] == -1) {
-                    const uint32_t deg = S.meta[b] >> 16, slot = S.meta[b] & 0x7fffu;
-                    O.items.push_back(U2{(uint32_t)(O.codes.size() - code0) | ((cnt - 1) << 13) | (deg << 19),
+                    const uint32_t deg = (uint32_t)unpack_meta(S.meta[b]).deg, slot = (uint32_t)unpack_meta(S.meta[b]).slot;
+                    O.items.push_back(U2{pack_patch_item((uint32_t)(O.codes.size() - code0), cnt, deg, 0u),
                                          (uint32_t)(2 * (int64_t)(b - (int32_t)slot) + slot)});
                     for (size_t k = i; k < j; ++k) O.codes.push_back(tup[k].code);
                 } else {
-                    open_items.push_back(U2{(uint32_t)open_codes.size() | ((cnt - 1) << 13) | (1u << 31), 0u});
+                    open_items.push_back(U2{pack_patch_item((uint32_t)open_codes.size(), cnt, 0u, 1u), 0u});
                     for (size_t k = i; k < j; ++k) open_codes.push_back(tup[k].code);
                     open_keys.push_back(b);
                 }
@@ -1088,10 +1050,9 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
             if (O.fail) break;
             const uint32_t shift = (uint32_t)(O.codes.size() - code0);
             for (size_t i = 0; i < open_items.size(); ++i) {
-                U2 it = open_items[i];
-                it.x += shift;                                               // code offset: behind the closed items' codes
-                it.y = (uint32_t)O.open_b.size();                            // worker-local slot, rebased after the join
-                O.items.push_back(it);
+                const PatchItem f = unpack_patch_item(open_items[i].x);
+                // code offset: behind the closed items' codes;  y: worker-local slot, rebased after the join
+                O.items.push_back(U2{pack_patch_item((uint32_t)f.off + shift, (uint32_t)f.cnt, 0u, 1u), (uint32_t)O.open_b.size()});
                 O.open_b.push_back(open_keys[i]);
                 O.open_p.push_back((int32_t)p);
             }
@@ -1103,12 +1064,12 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
                 while (j < ftup.size() && ftup[j].key == ftup[i].key) ++j;
                 const int32_t n = ftup[i].key;
                 const uint32_t cnt = (uint32_t)(j - i);
-                if (cnt > 64) { O.fail = 1; break; }
+                if (!in_field((int64_t)cnt - 1, kItemCntBits)) { O.fail = 1; break; }
                 const bool closed = (int32_t)cnt == S.iptr[n + 1] - S.iptr[n];
                 if ((npn[n] < 2) != closed) { O.fail = 2; break; }
                 uint32_t y = (uint32_t)n;
                 if (!closed) { y = (uint32_t)O.fopen_n.size(); O.fopen_n.push_back(n); O.fopen_p.push_back((int32_t)p); }
-                O.fitems.push_back(U2{(uint32_t)(O.fcodes.size() - fcode0) | ((cnt - 1) << 13) | (closed ? 0u : 1u << 31), y});
+                O.fitems.push_back(U2{pack_patch_item((uint32_t)(O.fcodes.size() - fcode0), cnt, 0u, closed ? 0u : 1u), y});
                 for (size_t k = i; k < j; ++k) O.fcodes.push_back(ftup[k].code);
                 i = j;
             }
@@ -1144,8 +1105,8 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
     std::vector<std::thread> th;
     auto finish = [&](int w) {
         Out& O = outs[(size_t)w];
-        for (U2& it : O.items) if (it.x >> 31) it.y += (uint32_t)bs[w];
-        for (U2& it : O.fitems) if (it.x >> 31) it.y += (uint32_t)bfs[w];
+        for (U2& it : O.items) if (unpack_patch_item(it.x).open) it.y += (uint32_t)bs[w];
+        for (U2& it : O.fitems) if (unpack_patch_item(it.x).open) it.y += (uint32_t)bfs[w];
         std::copy(O.items.begin(), O.items.end(), P.items.begin() + bi[w]);
         std::copy(O.codes.begin(), O.codes.end(), P.codes.begin() + bc[w]);
         std::copy(O.fitems.begin(), O.fitems.end(), P.fitems.begin() + bfi[w]);
@@ -1164,7 +1125,7 @@ inline int build_patch_plan(const Symbolic& S, int n_p, int64_t n_e, int64_t n_n
             const int rank = (int)(std::lower_bound(buf.begin(), buf.end(), p) - buf.begin());
             U4& f = P.fix[(size_t)open_idx[b]];
             const uint32_t slot = (uint32_t)(bs[w] + (int64_t)s);
-            if ((f.y >> 16) > 2) { P.plist[(size_t)f.w + rank] = (int32_t)slot; if (rank == 0) f.z = slot; }
+            if (unpack_fix(f.y).cnt > 2) { P.plist[(size_t)f.w + rank] = (int32_t)slot; if (rank == 0) f.z = slot; }
             else if (rank == 0) f.z = slot; else f.w = slot;
         }
         for (size_t s = 0; s < O.fopen_n.size(); ++s) {
@@ -1221,7 +1182,7 @@ inline int validate_patch_plan(const PatchPlan& P, const Symbolic& S, int n_p, i
     for (int a = 0; a < n_p; ++a)
         for (int b = 0; b < n_p; ++b) {
             int idx; bool tr;
-            patch_block_index(n_p, a, b, idx, tr);
+            sym_block_index(n_p, a, b, idx, tr);
             if (idx < 0 || idx >= nj * n_p) return 2;
             if (a != b || !tr) ab_of[(size_t)2 * idx + (tr ? 1 : 0)] = a * n_p + b;
         }
@@ -1253,16 +1214,17 @@ inline int validate_patch_plan(const PatchPlan& P, const Symbolic& S, int n_p, i
         std::vector<int32_t> seq;
         for (int32_t i = 0; i < d[1]; ++i) {
             const U2 it = P.items[(size_t)d[0] + i];
-            const int off = (int)(it.x & 8191u), cnt = (int)((it.x >> 13) & 63u) + 1, deg = (int)((it.x >> 19) & 4095u);
-            const bool open = it.x >> 31;
+            const PatchItem f = unpack_patch_item(it.x);
+            const int off = f.off, cnt = f.cnt, deg = f.deg;
+            const bool open = f.open;
             if (off + cnt > d[3]) return 5;
             seq.clear();
             for (int k = 0; k < cnt; ++k) {
-                const unsigned code = P.codes[(size_t)d[2] + off + k];
-                const int pos = (int)(code >> 1), per = patch_image_period(n_p, eb), ebp = patch_ebp(eb);
+                const PatchCode code = unpack_patch_code(P.codes[(size_t)d[2] + off + k]);
+                const int pos = code.pos, per = patch_image_period(n_p, eb), ebp = patch_ebp(eb);
                 const int jj = pos / per, rem = pos % per, aa = rem / ebp, el = rem % ebp, idx = jj * n_p + aa;
                 if (jj >= nj || aa >= n_p || el >= nel || patch_image_pos(n_p, eb, jj, aa, el) != pos) return 6;
-                const int ab = ab_of[(size_t)2 * idx + (code & 1u)];
+                const int ab = ab_of[(size_t)2 * idx + code.transposed];
                 if (ab < 0) return 7;
                 seq.push_back((int32_t)((int64_t)ab * n_e + pe[el]));
             }
@@ -1287,8 +1249,9 @@ inline int validate_patch_plan(const PatchPlan& P, const Symbolic& S, int n_p, i
         }
         for (int32_t i = 0; i < d[5]; ++i) {
             const U2 it = P.fitems[(size_t)d[4] + i];
-            const int off = (int)(it.x & 8191u), cnt = (int)((it.x >> 13) & 63u) + 1;
-            const bool open = it.x >> 31;
+            const PatchItem f = unpack_patch_item(it.x);
+            const int off = f.off, cnt = f.cnt;
+            const bool open = f.open;
             if (off + cnt > d[7]) return 13;
             seq.clear();
             for (int k = 0; k < cnt; ++k) {
@@ -1325,7 +1288,7 @@ inline int validate_patch_plan(const PatchPlan& P, const Symbolic& S, int n_p, i
     std::vector<int64_t> sl;
     std::vector<int32_t> all;
     for (const U4& f : P.fix) {
-        const int cnt = (int)(f.y >> 16), deg = (int)(f.y & 0xffffu);
+        const int cnt = unpack_fix(f.y).cnt, deg = unpack_fix(f.y).deg;
         if (cnt < 1 || !slots_of(f, cnt, sl)) return 21;
         const int64_t n = std::upper_bound(S.nptr.begin(), S.nptr.end(), (int32_t)(f.x / 2)) - S.nptr.begin() - 1;
         if (n < 0 || n >= n_n || deg != S.nptr[n + 1] - S.nptr[n]) return 22;
@@ -1344,7 +1307,7 @@ inline int validate_patch_plan(const PatchPlan& P, const Symbolic& S, int n_p, i
         // the mirror block: same elements, (a, b) swapped
         const U2 ft = P.fixT[(size_t)(&f - P.fix.data())];
         const int64_t m = S.ncol[b];
-        if (m == n) { if (ft.x != 0xffffffffu) return 39; continue; }
+        if (m == n) { if (ft.x != kNoMirror) return 39; continue; }
         if (m < n) return 39;                                                // only upper blocks have entries
         const int64_t slot_t = (int64_t)ft.x - 2 * (int64_t)S.nptr[m];
         if (slot_t < 0 || slot_t >= S.nptr[m + 1] - S.nptr[m] || (int64_t)ft.y != S.nptr[m + 1] - S.nptr[m]) return 40;

@@ -12,7 +12,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fep_layout.h"
+
 namespace fep {
+using namespace fep_layout;                             // the table formats the kernels read (one definition, shared with the planner)
 
 constexpr int kBlock = 256;
 
@@ -763,18 +766,6 @@ __device__ __forceinline__ void geometry_at_q(const double* __restrict__ t1, con
 // arrays are not read at all.  `on` is set by fep_ctx_set_materials_host when every array is constant.
 struct MatU { double shear, bulk, eta, c; int on; };
 
-// Where element_kernel keeps the block (a, b) of K_e: index of the stored block and whether it is the transpose.
-// `row_major`: the stored blocks of an element are numbered a*(n_p/2+1) + j (a lane's blocks adjacent: the AoS layout,
-// Kc[(e*NB + idx)*4]) instead of j*n_p + a (the SoA layout, Kc[(idx*n_e + e)*4]).
-inline __host__ __device__ void sym_block_index(int n_p, int a, int b, int& idx, bool& transposed, bool row_major = false) {
-    const int j = b >= a ? b - a : b - a + n_p;
-    const bool direct = 2 * j < n_p || (2 * j == n_p && a < n_p / 2);
-    const int nj = n_p / 2 + 1;
-    if (direct) { idx = row_major ? a * nj + j : j * n_p + a; transposed = false; }
-    else { idx = row_major ? b * nj + (n_p - j) : (n_p - j) * n_p + b; transposed = true; }
-}
-inline __host__ __device__ int sym_block_count(int n_p) { return (n_p / 2 + 1) * n_p; }   // upper bound on idx + 1
-
 // JS > 1 (patch form): phase 2 runs on JS lanes per (element, local node), each with 1/JS of the node's NJ stored blocks —
 // the 15-node element at JS = 2 on 512 threads keeps its 16-element patches (same LDS, same plan) at twice the waves per
 // CU and half the accumulators per lane.
@@ -802,11 +793,10 @@ template <int NP, int NQ, bool GEO = false, int TPB = kBlock, int JS = 1> struct
     static constexpr int kPts = (2 * NP + 9) * NPTS;
     static constexpr int kXY = 2 * NP * EB;             // one double2 per (local node, element)
     static constexpr int kTab = 2 * NP * NQ + NQ + (NQ & 1);
-    // skewed image (fep_host.h: patch_image_pos): odd element stride, one more slot per j for even NP
-    static constexpr int EBP = EB | 1;
-    static constexpr int PER = NP * EBP + ((NP & 1) ? 0 : 1);      // slots per j
-    static constexpr int SLOTS = NJ * PER;                          // double2 per plane
-    static constexpr int kKl = 4 * SLOTS, kFl = 2 * NP * EBP;
+    // skewed image (fep_layout.h: patch_image_pos)
+    static constexpr int EBP = patch_ebp(EB), PER = patch_image_period(NP, EB);
+    static constexpr int SLOTS = patch_image_slots(NP, EB);         // double2 per plane
+    static constexpr int kKl = 4 * SLOTS, kFl = 2 * patch_force_slots(NP, EB);
     static constexpr int kCodes = (NP * NP * EB + 3) / 4 + 1, kFcodes = (NP * EB + 3) / 4 + 1;    // doubles holding the uint16 codes
     static constexpr int kPhase3 = kKl + kFl + kCodes + kFcodes;
 };
@@ -816,7 +806,7 @@ template <int NP, int NQ, bool GEO = false, int TPB = kBlock, int JS = 1> struct
 // node-pair block (force: one node) in the fixed (e, a, b) order and writes either the finished CSR block / nodal force
 // (every contribution inside the patch) or a partial for fixup_kernel.  No K_e round trip through HBM.
 struct PatchArgs {
-    const int32_t* pdesc;                               // 8 ints per patch (scalar loads)
+    const int32_t* pdesc;                               // kPatchDescInts ints per patch (scalar loads)
     const int32_t* pel; const int32_t* pnodes;          // the patch's elements (ascending, -1 padded) and their nodes [a][local element]
     const uint2* items; const uint16_t* codes;
     const uint2* fitems; const uint16_t* fcodes;
@@ -877,8 +867,8 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
     const int t = threadIdx.x;
     const int64_t e0blk = (int64_t)blockIdx.x * EB;     // COO form: the workgroup's elements are e0blk .. e0blk + nel - 1
     const int64_t n_int = n_e * NQ;
-    // patch form: the elements are listed in pel (any ids, ascending); pdesc: 8 ints per patch (uniform address: scalar loads)
-    const int32_t* pd = PATCH ? pa.pdesc + (int64_t)blockIdx.x * 8 : nullptr;
+    // patch form: the elements are listed in pel (any ids, ascending); pdesc: kPatchDescInts ints per patch (uniform address: scalar loads)
+    const int32_t* pd = PATCH ? pa.pdesc + (int64_t)blockIdx.x * kPatchDescInts : nullptr;
     const int item_off = PATCH ? pd[0] : 0, n_items = PATCH ? pd[1] : 0, code_off = PATCH ? pd[2] : 0, n_codes = PATCH ? pd[3] : 0;
     const int fitem_off = PATCH ? pd[4] : 0, n_fitems = PATCH ? pd[5] : 0, fcode_off = PATCH ? pd[6] : 0, n_fcodes = PATCH ? pd[7] : 0;
     const int nel = PATCH ? n_fcodes / NP : (int)((n_e - e0blk) < EB ? (n_e - e0blk) : EB);
@@ -1090,10 +1080,10 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
     }
 
     // ---- phase 3 (patch route) --------------------------------------------------------
-    // stored block (j, a, el): first row at Kr0[pos], second row at Kr1[pos], pos = j*PER + a*EBP + el (two planes, skewed: ElemCfg)
+    // stored block (j, a, el): first row at Kr0[pos], second row at Kr1[pos], pos = patch_image_pos(j, a, el) (two planes, skewed)
     double2* Kr0 = reinterpret_cast<double2*>(lds);
     double2* Kr1 = Kr0 + C::SLOTS;
-    double2* fl2 = reinterpret_cast<double2*>(lds + C::kKl);           // force pair (a, el) at [a * EBP + el]
+    double2* fl2 = reinterpret_cast<double2*>(lds + C::kKl);           // force pair (a, el) at [patch_force_pos]
     const uint16_t* codes_l = reinterpret_cast<const uint16_t*>(codes32);
     const uint16_t* fcodes_l = reinterpret_cast<const uint16_t*>(fcodes32);
     // Phase 3's tables, fetched behind phase 2 — EVERY item descriptor of the patch (at most NP*NP*EB of them), so that phase 3
@@ -1146,11 +1136,11 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
             const int jj = j0 + j;
             if (JS > 1 && jj >= NJ) continue;
             if (NP % 2 == 0 && jj == NP / 2 && a >= NP / 2) continue;
-            const int pos = jj * C::PER + a * C::EBP + el;
+            const int pos = patch_image_pos(NP, C::EB, jj, a, el);
             Kr0[pos] = make_double2(kk[j][0], kk[j][1]);
             Kr1[pos] = make_double2(kk[j][2], kk[j][3]);
         }
-        if (JS == 1 || h == 0) fl2[a * C::EBP + el] = make_double2(f0, f1);
+        if (JS == 1 || h == 0) fl2[patch_force_pos(C::EB, a, el)] = make_double2(f0, f1);
     }
 #pragma unroll
     for (int r = 0; r < CWPT; ++r) { const int i = r * TPB + t; if (i < (n_codes + 1) / 2) codes32[i] = cpre[r]; }
@@ -1173,8 +1163,9 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
 #pragma unroll
             for (int u = 0; u < IT; ++u) {
                 const bool on = (g * IT + u) * TPB + t < n_items;
-                off[u] = (int)(dsc[g * IT + u].x & 8191u);
-                cnt[u] = on ? (int)((dsc[g * IT + u].x >> 13) & 63u) + 1 : 0;
+                const PatchItem it = unpack_patch_item(dsc[g * IT + u].x);
+                off[u] = it.off;
+                cnt[u] = on ? it.cnt : 0;
                 kmax = cnt[u] > kmax ? cnt[u] : kmax;
                 a00[u] = 0.0; a01[u] = 0.0; a10[u] = 0.0; a11[u] = 0.0;
             }
@@ -1184,11 +1175,11 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
 #pragma unroll
                 for (int u = 0; u < IT; ++u) { const int kc = k < cnt[u] ? k : (cnt[u] > 0 ? cnt[u] - 1 : 0); code[u] = codes_l[off[u] + kc]; }
 #pragma unroll
-                for (int u = 0; u < IT; ++u) { r0[u] = Kr0[code[u] >> 1]; r1[u] = Kr1[code[u] >> 1]; }
+                for (int u = 0; u < IT; ++u) { r0[u] = Kr0[patch_code_pos(code[u])]; r1[u] = Kr1[patch_code_pos(code[u])]; }
 #pragma unroll
                 for (int u = 0; u < IT; ++u) {
                     if (k < cnt[u]) {
-                        const bool tr = code[u] & 1u;
+                        const bool tr = patch_code_transposed(code[u]);
                         a00[u] += r0[u].x; a01[u] += tr ? r1[u].x : r0[u].y; a10[u] += tr ? r0[u].y : r1[u].x; a11[u] += r1[u].y;
                     }
                 }
@@ -1197,11 +1188,12 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
             for (int u = 0; u < IT; ++u) {
                 if (cnt[u] == 0) continue;
                 const uint32_t x = dsc[g * IT + u].x, y = dsc[g * IT + u].y;
-                if (x >> 31) {                                         // partial: slot y of the side buffer
+                const PatchItem it = unpack_patch_item(x);
+                if (it.open) {                                        // partial: slot y of the side buffer
                     Pc2[2 * (int64_t)y] = make_double2(a00[u], a01[u]);
                     Pc2[2 * (int64_t)y + 1] = make_double2(a10[u], a11[u]);
                 } else {                                               // finished CSR block: its two rows
-                    const int deg = (int)((x >> 19) & 4095u);
+                    const int deg = it.deg;
                     data2[y] = make_double2(a00[u], a01[u]);
                     data2[(int64_t)y + deg] = make_double2(a10[u], a11[u]);
                 }
@@ -1215,10 +1207,11 @@ element_kernel(int64_t n_e, const int32_t* __restrict__ elem,
         for (int u = 0; u < FIT; ++u) {
             if (u * TPB + t >= n_fitems) continue;
             const uint2 d = fdsc[u];
-            const int off = (int)(d.x & 8191u), cnt = (int)((d.x >> 13) & 63u) + 1;
+            const PatchItem it = unpack_patch_item(d.x);
+            const int off = it.off, cnt = it.cnt;
             double g0 = 0.0, g1 = 0.0;
             for (int k = 0; k < cnt; ++k) { const double2 v = fl2[fcodes_l[off + k]]; g0 += v.x; g1 += v.y; }
-            if (d.x >> 31) Pf2[d.y] = make_double2(g0, g1); else F2[d.y] = make_double2(g0, g1);
+            if (it.open) Pf2[d.y] = make_double2(g0, g1); else F2[d.y] = make_double2(g0, g1);
         }
     }
     FEP_STAMP_P(pa, blockIdx.x, 6);                                                  // thread 0's wave has issued its last store
@@ -1240,7 +1233,7 @@ fixup_kernel(int nb_k, int64_t n_open, const uint4* __restrict__ fix, const uint
         const int64_t i = (int64_t)g * kBlock + threadIdx.x;
         if (i >= n_open) return;
         const uint4 f = fix[i];
-        const int cnt = (int)(f.y >> 16), deg = (int)(f.y & 0xffffu);
+        const int cnt = unpack_fix(f.y).cnt, deg = unpack_fix(f.y).deg;
         const double2* P2 = reinterpret_cast<const double2*>(Pc);
         double a00, a01, a10, a11;
         const uint2 ft = fixT[i];                                      // (issued with the partials, not behind them)
@@ -1264,7 +1257,7 @@ fixup_kernel(int nb_k, int64_t n_open, const uint4* __restrict__ fix, const uint
         double2* data2 = reinterpret_cast<double2*>(data);
         data2[f.x] = make_double2(a00, a01);
         data2[(int64_t)f.x + deg] = make_double2(a10, a11);
-        if (ft.x != 0xffffffffu) {                      // the mirror block (column node, row node): the transpose
+        if (ft.x != kNoMirror) {                     // the mirror block (column node, row node): the transpose
             data2[ft.x] = make_double2(a00, a10);
             data2[(int64_t)ft.x + ft.y] = make_double2(a01, a11);
         }
@@ -1362,7 +1355,7 @@ csr_reduce_kernel(int n_tiles, const int32_t* __restrict__ tstart, const int32_t
                 }
             }
         }
-        const int sl = (int)(m & 0x7fffu), deg = (int)(m >> 16);
+        const int sl = unpack_meta(m).slot, deg = unpack_meta(m).deg;
         const int rel = 2 * (int)threadIdx.x - sl;          // (CSR position - 4*sb0) / 2
         out2[rel] = make_double2(a00, a01);
         out2[rel + deg] = make_double2(a10, a11);
@@ -1373,7 +1366,7 @@ csr_reduce_kernel(int n_tiles, const int32_t* __restrict__ tstart, const int32_t
 }
 
 // The same reduce with fewer vector-memory instructions per lane (its time follows their count): ONE 8-byte descriptor
-// per block (x: first contribution, y: count:8 | degree:12 | slot:12) instead of segptr x2 + meta, and the lane's
+// per block (fep_layout.h: pkc) instead of segptr x2 + meta, and the lane's
 // contribution addresses four at a time with one 16-byte load (`perm` is padded by 4 entries; the load needs 4-byte
 // alignment only).  Same adds in the same order.
 struct __attribute__((packed, aligned(4))) PermQuad { int32_t v[4]; };
@@ -1392,7 +1385,7 @@ csr_reduce_pk_kernel(int n_tiles, const int32_t* __restrict__ tstart, const uint
     if ((int)threadIdx.x < nb) {
         const uint2 d = pkc[sb0 + threadIdx.x];
         const int32_t* pl = perm + d.x;
-        const int len = (int)(d.y & 255u), deg = (int)((d.y >> 8) & 4095u), sl = (int)(d.y >> 20);
+        const int len = unpack_pkc(d.y).len, deg = unpack_pkc(d.y).deg, sl = unpack_pkc(d.y).slot;
         double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
         for (int t = 0; t < len; t += 4) {
             const PermQuad q = *reinterpret_cast<const PermQuad*>(pl + t);
@@ -1775,13 +1768,14 @@ p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, c
     if (sb >= n_blk) return;
     const int32_t beg = segptr[sb], end = segptr[sb + 1];
     const uint32_t m = meta[sb];
-    const bool diag = (m >> 15) & 1u;
+    const bool diag = unpack_meta(m).diag;
     const bool want_f = diag && F != nullptr && S != nullptr;
     double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0, f0 = 0.0, f1 = 0.0;
     for (int32_t t = beg; t < end; ++t) {
         const uint32_t code = (uint32_t)perm2[t];
-        const int64_t e = code >> 4;
-        const int a = (code >> 2) & 3, b = code & 3;
+        const Gather gc = unpack_gather(code);
+        const int64_t e = gc.i;
+        const int a = gc.a, b = gc.b;
         const double* g = geo + e * 6;
         const double d1[3] = {g[0], g[1], -(g[0] + g[1])}, d2[3] = {g[2], g[3], -(g[2] + g[3])};
         const double a1 = d1[a], a2 = d2[a], b1 = d1[b], b2 = d2[b], w = g[4];
@@ -1803,7 +1797,7 @@ p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, c
         }
     }
     if (data) {
-        const int64_t s = m & 0x7fffu, deg = m >> 16;
+        const int64_t s = unpack_meta(m).slot, deg = unpack_meta(m).deg;
         const int64_t pos0 = 4 * sb - 2 * s;
         *reinterpret_cast<double2*>(data + pos0) = make_double2(k00, k01);
         *reinterpret_cast<double2*>(data + pos0 + 2 * deg) = make_double2(k10, k11);
@@ -1819,25 +1813,20 @@ p1_node_kernel(int64_t n_blk, int64_t n_e, const int32_t* __restrict__ segptr, c
 // into LDS with coalesced loads over its precomputed, sorted element list, then every lane
 // gathers from LDS only.
 //   wg_elist[wg*L + i]   sorted unique elements of the workgroup, padded to L with its first element
-//   perm_l[wg*C + k]     gather codes (local element index << 4) | a << 2 | b   (uint16), padded to C
+//   perm_l[wg*C + k]     gather codes (fep_layout.h: pack_gather; uint16), padded to C
 //   LDS: rec[15][L] doubles, L = max list length, then the workgroup's gather codes (uint16)
 // ---------------------------------------------------------------------------------------
 // RNG = true: the tile's sorted element list is given as <= 8 runs of consecutive ids, 16 ints per tile
 // (start_r, cumulative count_r), fetched with scalar loads; the operand loads then depend on no vector
 // load at all, which takes one memory round trip out of every workgroup's critical path.  Chosen by the
 // host whenever every tile's list compresses into 8 runs (any mesh numbered with locality).
-// PK = true: the lane's block descriptor is ONE 8-byte load (pk.x: beg_local:11 | len:4 | deg:8 | slot:8 | diag:1,
-// pk.y: block index in the tile | node index in the tile << 8) instead of segptr x2 + meta + ncol, and the lanes of
-// a tile are SORTED by descending segment length: the diagonal blocks (one contribution per incident element, 6 on
-// a regular mesh, against 2 for an edge block) fill the first wave instead of setting the trip count of all four.
+// PK = true: the lane's block descriptor is ONE 8-byte load (fep_layout.h: pk) instead of segptr x2 + meta + ncol, and
+// the lanes of a tile are SORTED by descending segment length: the diagonal blocks (one contribution per incident element,
+// 6 on a regular mesh, against 2 for an edge block) fill the first wave instead of setting the trip count of all four.
 //
-// Tiles (fep_host.h, P1Plan): up to kSegMax segments of consecutive nodes; the tile's record `trec` (kRecInts ints, 256
-// bytes) holds 1 + kSegMax int4: (pk_base, n_blocks, n_nodes, n_segments) and per segment (first_block, n_blocks,
-// first_node, n_nodes), then at kRecRng the element runs and at kRecNrng the node runs of RNG plans, all read with scalar
-// loads in ONE round trip at kernel entry (load_tile_rec).  The tile's CSR values and forces leave as one contiguous range
-// per segment.  Without PK every tile has exactly one segment (its blocks are first_block + lane).
-constexpr int kSegMax = 4;
-constexpr int kRecInts = 64, kRecRng = 32, kRecNrng = 48;
+// Tiles (fep_host.h, P1Plan): up to kSegMax segments of consecutive nodes; the tile's record `trec` (fep_layout.h) is read
+// with scalar loads in ONE round trip at kernel entry (load_tile_rec).  The tile's CSR values and forces leave as one
+// contiguous range per segment.  Without PK every tile has exactly one segment (its blocks are first_block + lane).
 
 // LDS-DMA (global_load_lds): the lane's 16 / 4 bytes at `g` go straight to LDS at wave_base + lane * size — no VGPR, no
 // ds_write.  `wave_base` must be wave-uniform; the data is visible to ds_read after s_waitcnt vmcnt + a barrier
@@ -1883,7 +1872,8 @@ __device__ __forceinline__ TileDesc load_tile_rec(const int32_t* __restrict__ tr
     else if (ER) asm volatile("" : FEP_PIN16(a), FEP_PIN4(b, 0), FEP_PIN16(er));
     else asm volatile("" : FEP_PIN16(a), FEP_PIN4(b, 0));
     TileDesc t;
-    t.pk_base = a[0]; t.nb = a[1]; t.nn = a[2] & 255; t.n_own = a[2] >> 8; t.nseg = a[3] & 15; t.n_el = (a[3] >> 4) & 4095; t.n_nd = (a[3] >> 16) & 4095;
+    const TileHead h = unpack_tile_head(a[2], a[3]);
+    t.pk_base = a[0]; t.nb = a[1]; t.nn = h.nn; t.n_own = h.n_own; t.nseg = h.nseg; t.n_el = h.n_el; t.n_nd = h.n_nd;
     t.fb0 = a[4]; t.fn0 = a[6]; t.fb1 = a[8]; t.fn1 = a[10]; t.fb2 = a[12]; t.fn2 = a[14]; t.fb3 = b[0]; t.fn3 = b[2];
     const int be0 = 2 * a[5], be1 = be0 + 2 * a[9], be2 = be1 + 2 * a[13];
     const int ne0 = a[7], ne1 = ne0 + a[11], ne2 = ne1 + a[15];
@@ -1891,14 +1881,6 @@ __device__ __forceinline__ TileDesc load_tile_rec(const int32_t* __restrict__ tr
     t.nends = ne0 | (ne1 << 8) | (ne2 << 16);
     asm volatile("" : "+s"(t.bends), "+s"(t.nends));   // (opaque: unpacking must not lead back to the eight sizes)
     return t;
-}
-
-// Slot i of a list given as <= 8 runs (start_r, cumulative count_r); slots past the list repeat its first entry.
-__device__ __forceinline__ int run_entry(const int (&r)[16], int i) {
-    int e = r[0] + i;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) e = i >= r[2 * k - 1] ? r[2 * k] + (i - r[2 * k - 1]) : e;
-    return i < r[15] ? e : r[0];
 }
 
 // The tile's LDS output image -> HBM: CSR values (2*nb double2 in tile block order) and forces (nn double2 in tile
@@ -1958,14 +1940,10 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
                    unsigned long long* __restrict__ counts_out FEP_P1_CLK_PARAM) {
     extern __shared__ __attribute__((aligned(16))) double rec[];      // [15][L]
     FEP_P1_STAMP_ENTRY();
-    // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with a
-    // private L2.  Give every XCD one contiguous eighth of the tiles, so that the element rows
-    // re-staged by the workgroups of the next node row hit in the SAME L2 instead of the fabric.
     // the arguments the head needs, fetched as one batch (one wait for them, one for the tile's record below)
     if (RNG) asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)geo), "s"((uint64_t)DS), "s"((uint64_t)S), "s"(n_e));
     else asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)wg_elist), "s"(L));
-    const int chunk = (n_wg + 7) >> 3;
-    const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+    const int wg = xcd_tile_of_block(blockIdx.x, n_wg);               // XCD-aware tile order (fep_layout.h)
     if (wg >= n_wg) return;
     // Two dependent memory levels only: every table is padded to a fixed per-tile stride (element list:
     // L entries, gather codes: C entries, unused slots repeat a valid entry), so all first-level
@@ -2015,14 +1993,13 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     uint32_t m;
     uint32_t pk_y = 0;
     if (PK) {
-        // lanes of a tile are sorted by descending segment length (host): pk.y = block index inside the tile |
-        // index of the lane's node inside the tile << 8
+        // lanes of a tile are sorted by descending segment length (host)
         const uint2 w2 = live ? pk[sb] : make_uint2(0u, 0u);
-        const uint32_t w = w2.x;
+        const Pk d = unpack_pk(w2.x, w2.y);
         pk_y = w2.y;
-        beg = (int32_t)(w & 2047u);
-        end = beg + (int32_t)((w >> 11) & 15u);
-        m = (((w >> 15) & 255u) << 16) | ((w >> 31) << 15) | ((w >> 23) & 255u);     // deg | diag | slot
+        beg = d.off;
+        end = beg + d.len;
+        m = pack_meta(d.deg, d.diag, d.slot);
     } else {
         beg = live ? segptr[sb] : 0;
         end = live ? segptr[sb + 1] : 0;
@@ -2039,7 +2016,8 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
         if (r * TPB + (int)(threadIdx.x & ~63u) < CW) cd[r] = codes_w[i < CW ? i : 0];   // wave-uniform: idle waves issue nothing
     }
     // (4) operands -> LDS
-    uint16_t* codes = reinterpret_cast<uint16_t*>(rec + 15 * L);
+    const P1Lds lds = p1_tile_lds(L, C, 0, TPB, false, false);
+    uint16_t* codes = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + lds.codes);
     FEP_P1_STAMP_AFTER(wg, 2, g0[0].x);
 #pragma unroll
     for (int r = 0; r < EPT; ++r) {
@@ -2056,21 +2034,21 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
         }
     }
     // (5) codes -> LDS, first code of the tile
-    uint32_t* codes32 = reinterpret_cast<uint32_t*>(rec + 15 * L);
+    uint32_t* codes32 = reinterpret_cast<uint32_t*>(codes);
 #pragma unroll
     for (int q = 0; q < CWPT; ++q) {
         const int ci = q * TPB + (int)threadIdx.x;
         if (ci < CW) codes32[ci] = cd[q];
     }
     __shared__ int32_t t0_sh;
-    const bool is_diag = (m >> 15) & 1u;
+    const bool is_diag = unpack_meta(m).diag;
     if (!PK && threadIdx.x == 0) t0_sh = beg;
     __syncthreads();
     FEP_P1_STAMP(wg, 3);
     int32_t t0, fnode_k = -1;
     if (PK) {
         t0 = 0;                                        // pk holds tile-local code offsets
-        fnode_k = is_diag ? (int)((pk_y >> 8) & 255u) : -1;       // k-th node of the tile
+        fnode_k = is_diag ? unpack_pk(0u, pk_y).node : -1;        // k-th node of the tile
     } else {
         t0 = t0_sh;
     }
@@ -2078,8 +2056,8 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0, f0 = 0.0, f1 = 0.0;
     if (live) {
         for (int32_t t = beg; t < end; ++t) {
-            const unsigned code = codes[t - t0];
-            const int i = code >> 4, a = (code >> 2) & 3, b = code & 3;
+            const Gather gc = unpack_gather(codes[t - t0]);
+            const int i = gc.i, a = gc.a, b = gc.b;
             const double a1 = rec[(9 + a) * L + i], a2 = rec[(12 + a) * L + i];
             const double b1 = rec[(9 + b) * L + i], b2 = rec[(12 + b) * L + i];
             if (DS) {
@@ -2105,13 +2083,13 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
     __syncthreads();                                   // every lane is done reading the staged operands
     double2* out2 = reinterpret_cast<double2*>(rec);
     if (live && data) {
-        const int64_t sl = m & 0x7fffu, deg = m >> 16;
-        const int blk = PK ? (int)(pk_y & 255u) : (int)threadIdx.x;   // block index inside the tile
+        const int64_t sl = unpack_meta(m).slot, deg = unpack_meta(m).deg;
+        const int blk = PK ? unpack_pk(0u, pk_y).blk : (int)threadIdx.x;   // block index inside the tile
         const int rel = 4 * blk - 2 * (int)sl;                   // = CSR position - 4*(first block), always even
         out2[rel >> 1] = make_double2(k00, k01);
         out2[(rel >> 1) + (int)deg] = make_double2(k10, k11);
     }
-    double2* fo2 = out2 + 2 * TPB;
+    double2* fo2 = reinterpret_cast<double2*>(reinterpret_cast<char*>(rec) + lds.out_forces);
     if (PK) { if (want_f) fo2[fnode_k] = make_double2(f0, f1); }
     __syncthreads();
     store_tile_outputs<TPB>(td, out2, fo2, data, (PK && S != nullptr) ? F : nullptr);
@@ -2131,7 +2109,7 @@ p1_node_lds_kernel(int64_t n_e, int L, int C, const int32_t* __restrict__ segptr
 //   * the NODES its ~150 staged elements touch (~110) are staged once per tile: coordinates and displacements go to
 //     LDS with one 16-byte load each per node (`nrng`: <= 8 runs of consecutive node ids, scalar loads; or the
 //     list `wg_nlist`), instead of 6 dependent 16-byte gathers per staged element;
-//   * per staged element one 4-byte word `el_nodes` = its three tile-local node indices (10 bits each) and the
+//   * per staged element one 4-byte word `el_nodes` = its three tile-local node indices (fep_layout.h: el_nodes) and the
 //     OWNER bit: every element is staged by ~2 tiles, exactly one of them (the first in tile order) writes the
 //     element's s / ds / ind_p / strain and counts its branch;
 //   * the lane of a staged element reads its nodes from LDS, forms the P1 geometry (p1_geometry: bit-identical to
@@ -2170,8 +2148,7 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
     // the arguments the head needs, fetched as one batch (one wait for them, one for the tile's record below)
     if (RNG) asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)xy), "s"((uint64_t)U));
     else asm volatile("" :: "s"(n_wg), "s"((uint64_t)trec), "s"((uint64_t)wg_elist), "s"((uint64_t)wg_nlist), "s"(L), "s"(NL));
-    const int chunk = (n_wg + 7) >> 3;                                // XCD-aware tile order (see p1_node_lds_kernel)
-    const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+    const int wg = xcd_tile_of_block(blockIdx.x, n_wg);               // XCD-aware tile order (fep_layout.h)
     if (wg >= n_wg) return;
     int er[16], nr[16];
     const TileDesc td = load_tile_rec<RNG, RNG>(trec, wg, er, nr);
@@ -2204,11 +2181,11 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
     FEP_P1_STAMP_AFTER(wg, 1, el[0] + nd[0]);
     // (2) loads, all issued before the first use: node data, the slots' node words / plastic strain / materials
     const int n_el = td.n_el, n_nd = td.n_nd;           // this tile's staged elements / nodes (<= L / NL)
-    const int Cp = DMA ? (C + 127) & ~127 : C, NLp = DMA ? (NL + 63) & ~63 : NL;      // padded code / node regions (see above)
-    uint16_t* codes = reinterpret_cast<uint16_t*>(rec + 15 * L);
-    uint32_t* codes32 = reinterpret_cast<uint32_t*>(rec + 15 * L);
-    double2* lxy = reinterpret_cast<double2*>(reinterpret_cast<char*>(rec) + (((size_t)15 * L * 8 + (size_t)Cp * 2 + 15) & ~(size_t)15));
-    double2* lu = lxy + NLp;
+    const P1Lds lds = p1_tile_lds(L, C, NL, TPB, DMA, true);          // the regions of the LDS image (fep_layout.h)
+    uint16_t* codes = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + lds.codes);
+    uint32_t* codes32 = reinterpret_cast<uint32_t*>(codes);
+    double2* lxy = reinterpret_cast<double2*>(reinterpret_cast<char*>(rec) + lds.nodes_xy);
+    double2* lu = lxy + lds.NLp;                                       // = rec + lds.nodes_u
     double2 nxy[NPT], nu[NPT];
 #pragma unroll
     for (int r = 0; r < NPT; ++r) {
@@ -2283,7 +2260,8 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
             const uint32_t wv = enw[r];
             const int64_t e = el[r];
             own = i < td.n_own;                          // the tile's own elements come first in its staged list
-            const int i0 = (int)(wv & 1023u), i1 = (int)((wv >> 10) & 1023u), i2 = (int)((wv >> 20) & 1023u);
+            const ElNodes en = unpack_el_nodes(wv);
+            const int i0 = en.n0, i1 = en.n1, i2 = en.n2;
             const double2 c0 = lxy[i0], c1 = lxy[i1], c2 = lxy[i2];
             double d1[3], d2[3], w;
             p1_geometry(tab, c0, c1, c2, d1, d2, w);
@@ -2330,19 +2308,18 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
         if (sc[1]) atomicAdd(&slot[1], (unsigned long long)sc[1]);
     }
     // (6) gather: p1_node_lds_kernel's, packed descriptors
-    const uint32_t wd = w2.x;
-    const uint32_t pk_y = w2.y;
-    const int32_t beg = (int32_t)(wd & 2047u);
-    const int32_t end = beg + (int32_t)((wd >> 11) & 15u);
-    const uint32_t deg = (wd >> 15) & 255u, slot_s = (wd >> 23) & 255u;
-    const bool is_diag = (wd >> 31) != 0u;
-    const int fnode_k = is_diag ? (int)((pk_y >> 8) & 255u) : -1;
+    const Pk pd = unpack_pk(w2.x, w2.y);
+    const int32_t beg = pd.off;
+    const int32_t end = beg + pd.len;
+    const uint32_t deg = pd.deg, slot_s = pd.slot;
+    const bool is_diag = pd.diag != 0;
+    const int fnode_k = is_diag ? pd.node : -1;
     const bool want_f = live && is_diag && F != nullptr;
     double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0, f0 = 0.0, f1 = 0.0;
     if (live) {
         for (int32_t t = beg; t < end; ++t) {
-            const unsigned code = codes[t];
-            const int i = code >> 4, a = (code >> 2) & 3, b = code & 3;
+            const Gather gc = unpack_gather(codes[t]);
+            const int i = gc.i, a = gc.a, b = gc.b;
             const double a1 = rec[(9 + a) * L + i], a2 = rec[(12 + a) * L + i];
             const double b1 = rec[(9 + b) * L + i], b2 = rec[(12 + b) * L + i];
             if (data) {
@@ -2365,12 +2342,12 @@ p1_fused_kernel(int64_t n_e, int L, int C, int NL,
     __syncthreads();                                   // every lane is done reading the staged operands
     double2* out2 = reinterpret_cast<double2*>(rec);
     if (live && data) {
-        const int blk = (int)(pk_y & 255u);
+        const int blk = pd.blk;
         const int rel = 4 * blk - 2 * (int)slot_s;
         out2[rel >> 1] = make_double2(k00, k01);
         out2[(rel >> 1) + (int)deg] = make_double2(k10, k11);
     }
-    double2* fo2 = out2 + 2 * TPB;
+    double2* fo2 = reinterpret_cast<double2*>(reinterpret_cast<char*>(rec) + lds.out_forces);
     if (want_f) fo2[fnode_k] = make_double2(f0, f1);
     __syncthreads();
     store_tile_outputs<TPB>(td, out2, fo2, data, F);
@@ -2600,10 +2577,9 @@ node_lds_kernel(int64_t n_blk, int64_t n_e, int L, int C, const int32_t* __restr
     double* t1 = rec + (int64_t)NF * SL;
     double* t2 = t1 + NP * NQ;
     double* tw = t2 + NP * NQ;
-    uint16_t* codes = reinterpret_cast<uint16_t*>(tw + NQ + (NQ & 1));
+    uint16_t* codes = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + gn_lds_codes(NP, NQ, L));
     __shared__ int32_t t0_sh;
-    const int chunk = (n_wg + 7) >> 3;                                // XCD-aware tile order (see p1_node_lds_kernel)
-    const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+    const int wg = xcd_tile_of_block(blockIdx.x, n_wg);               // XCD-aware tile order (fep_layout.h)
     if (counts_out != nullptr && blockIdx.x == 0) sum_block_counts(n_count_blocks, blk_counts, counts_out);
     if (wg >= n_wg) return;
     const int64_t n_int = n_e * NQ;
@@ -2614,7 +2590,7 @@ node_lds_kernel(int64_t n_blk, int64_t n_e, int L, int C, const int32_t* __restr
     for (int i = threadIdx.x; i < NQ; i += TPB) tw[i] = wf[i];
     const int32_t beg = live ? segptr[sb] : 0, end = live ? segptr[sb + 1] : 0;
     const uint32_t m = live ? meta[sb] : 0u;
-    const int32_t fnode = (live && ((m >> 15) & 1u)) ? ncol[sb] : -1;
+    const int32_t fnode = (live && unpack_meta(m).diag) ? ncol[sb] : -1;
     for (int i = threadIdx.x; i < C; i += TPB) codes[i] = perm_l[(int64_t)wg * C + i];
     if (threadIdx.x == 0) t0_sh = beg;
     __syncthreads();                                                  // tables ready
@@ -2651,8 +2627,9 @@ node_lds_kernel(int64_t n_blk, int64_t n_e, int L, int C, const int32_t* __restr
     double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0, f0 = 0.0, f1 = 0.0;
     for (int32_t t = beg; t < end; ++t) {
         const unsigned code = codes[t - t0];
-        const int a = (code >> 4) & 15, b = code & 15;
-        const int s0 = (int)(code >> 8) * NQ;
+        const Gather gc = unpack_gn_code(code);
+        const int a = gc.a, b = gc.b;
+        const int s0 = gc.i * NQ;
         for (int q = 0; q < NQ; ++q) {
             const int sl = s0 + q;
             const double a1 = rec[(9 + a) * SL + sl], a2 = rec[(9 + NP + a) * SL + sl];
@@ -2674,7 +2651,7 @@ node_lds_kernel(int64_t n_blk, int64_t n_e, int L, int C, const int32_t* __restr
         }
     }
     if (data) {
-        const int64_t s = m & 0x7fffu, deg = m >> 16;
+        const int64_t s = unpack_meta(m).slot, deg = unpack_meta(m).deg;
         const int64_t pos0 = 4 * sb - 2 * s;
         *reinterpret_cast<double2*>(data + pos0) = make_double2(k00, k01);
         *reinterpret_cast<double2*>(data + pos0 + 2 * deg) = make_double2(k10, k11);

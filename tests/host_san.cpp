@@ -42,8 +42,9 @@ int main(int argc, char** argv) {
         int diag = 0;
         for (int32_t b = S.nptr[n]; b < S.nptr[n + 1]; ++b) {
             if (b > S.nptr[n] && S.ncol[b] <= S.ncol[b - 1]) return 1;
-            if ((S.meta[b] >> 15) & 1u) { ++diag; if (S.ncol[b] != n) return 1; }
-            if ((int)(S.meta[b] & 0x7fffu) != b - S.nptr[n] || (int)(S.meta[b] >> 16) != S.nptr[n + 1] - S.nptr[n]) return 1;
+            const Meta m = unpack_meta(S.meta[b]);
+            if (m.diag) { ++diag; if (S.ncol[b] != n) return 1; }
+            if (m.slot != b - S.nptr[n] || m.deg != S.nptr[n + 1] - S.nptr[n]) return 1;
         }
         if (diag != (S.nptr[n + 1] > S.nptr[n] ? 1 : 0)) return 1;
     }
@@ -66,7 +67,8 @@ int main(int argc, char** argv) {
                     (int)P.rng, (int)P.pk, (int)P.fused, (int)P.fused_rng);
         if (r == FEP_OK && P.n_wg > 0) {
             const int32_t* d = P.tdesc.data() + (size_t)(P.n_wg - 1) * kDescInts;
-            std::printf("last tile: blocks %d nodes %d own %d staged %d\n", d[1], d[2] & 255, d[2] >> 8, (d[3] >> 4) & 4095);
+            const TileHead h = tile_head(d);
+            std::printf("last tile: blocks %d nodes %d own %d staged %d\n", d[1], h.nn, h.n_own, h.n_el);
         }
         rc = (r != FEP_OK || bad) ? 1 : 0;
         std::printf("result %s\n", rc ? "FAILED" : "ok");
@@ -112,10 +114,9 @@ int main(int argc, char** argv) {
             for (int64_t g = 0; g < n_wg && !rc; ++g) {
                 const int64_t b0 = g * G.tile, b1 = std::min<int64_t>(n_blk, b0 + G.tile);
                 for (int32_t t = S.segptr[b0]; t < S.segptr[b1]; ++t) {
-                    const unsigned code = G.codes_pad[(size_t)(g * G.C + (t - S.segptr[b0]))];
+                    const Gather code = unpack_gn_code(G.codes_pad[(size_t)(g * G.C + (t - S.segptr[b0]))]);
                     const int64_t ab = S.perm[t] / n_e, e = S.perm[t] % n_e;
-                    if ((int)(code >> 8) >= G.L || G.elist_pad[(size_t)(g * G.L + (code >> 8))] != e ||
-                        (int)((code >> 4) & 15) != ab / n_p || (int)(code & 15) != ab % n_p) rc = 1;
+                    if (code.i >= G.L || G.elist_pad[(size_t)(g * G.L + code.i)] != e || code.a != ab / n_p || code.b != ab % n_p) rc = 1;
                 }
             }
         }

@@ -3,7 +3,7 @@
 //   tile_record_host MESHFILE
 // MESHFILE as for host_san.cpp: int32 n_p (= 3), n_e, n_n, then the elements (3 x n_e, C order).  Builds the default plan
 // and the variants that change what a record holds (one / four segments, list form, two-kernel plan), decodes every
-// record the way the kernels do (fep_kernels.hip.h: load_tile_rec, run_entry) and compares with the plan's own tables.
+// record with the kernels' own decoder (fep_layout.h: unpack_tile_head, run_entry) and compares with the plan's own tables.
 // Prints one line per plan; exit code 0 = all records decode, 1 = a mismatch, 2 = unreadable mesh file.
 #include <cstdint>
 #include <cstdio>
@@ -13,13 +13,6 @@
 #include "../fem-elastoplasticity_amd/csrc/fep_host.h"
 
 using namespace fep_host;
-
-// slot i of a list given as <= 8 runs: the kernels' run_entry
-static int run_entry(const int32_t* r, int i) {
-    int e = r[0] + i;
-    for (int k = 1; k < 8; ++k) e = i >= r[2 * k - 1] ? r[2 * k] + (i - r[2 * k - 1]) : e;
-    return i < r[15] ? e : r[0];
-}
 
 // 0, or the number of the first failed check
 static int check_records(const P1Plan& P) {
@@ -34,7 +27,8 @@ static int check_records(const P1Plan& P) {
         for (int i = kDescInts; i < kRecRng; ++i)
             if (r[i] != 0) return 4;                                                                     // padding
         // the descriptor's fields as the kernels unpack them
-        const int nseg = r[3] & 15, n_el = (r[3] >> 4) & 4095, n_nd = (r[3] >> 16) & 4095, nn = r[2] & 255, n_own = r[2] >> 8;
+        const TileHead h = tile_head(r);
+        const int nseg = h.nseg, n_el = h.n_el, n_nd = h.n_nd, nn = h.nn, n_own = h.n_own;
         int nb = 0, nnodes = 0;
         for (int s = 0; s < kSegMax; ++s) {
             if (s >= nseg && (r[4 + 4 * s] | r[5 + 4 * s] | r[6 + 4 * s] | r[7 + 4 * s]) != 0) return 5;  // unused segments are empty
