@@ -4,6 +4,7 @@
 #include "fep_host.h"
 #include "fep_kernels.hip.h"
 #include "fep_staging.h"
+#include "fep_step_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -42,17 +43,11 @@ thread_local int fep_g_last_hip = 0;
 static const char* env_now(const char* name) { const char* v = std::getenv(name); return (v && *v) ? v : nullptr; }
 static bool env_is(const char* name, const char* v) { const char* r = env_now(name); return r && std::strcmp(r, v) == 0; }
 
-// What a context runs, chosen once at creation (choose_route):
-//   P1Node   P1's node route: p1_point_kernel + p1_node_lds_kernel, or p1_fused_kernel alone (K,F-only steps)
-//   Patch    element_kernel in its patch form (K_e summed in LDS) + fixup_kernel: every other type, P1 with FEP_ROUTE=patch
-//   Coo      element_kernel with every K_e block through HBM + csr_reduce*: FEP_ROUTE=coo, or a mesh without a patch plan
-//   GenNode  (-DFEP_ABLATION, FEP_GEN_PATH=node) P2 / Q1 / Q2: point_kernel + node_lds_kernel
-enum class Route {
-    P1Node, Patch, Coo,
-#ifdef FEP_ABLATION
-    GenNode,
-#endif
-};
+// What a context runs, chosen once at creation (choose_route), and what each of its calls launches (fep_step_plan.h)
+using fep_plan::Route;
+using fep_plan::StageA;
+using fep_plan::StageB;
+using fep_plan::StepPlan;
 
 // Persistent device buffers of a context's *_host entry points (fep_ctx::hbuf; their sizes: size_host_buffers).  One block
 // per enumerator before kCtxBufCount; the names after it share the block of a call that never runs at the same time (the
@@ -196,8 +191,6 @@ struct fep_ctx {
 #endif
     bool have_materials = false;
     int model = FEP_MODEL_DP;                           // fep_ctx_set_model: which return map the steps run
-    uint2* point_blk = nullptr;                         // step_model: per-workgroup branch counters of the point stage (every
-                                                        // model but Drucker-Prager, and Drucker-Prager with a field)
     Hard hard = flat_hard();                            // FEP_MODEL_VMI: fep_ctx_set_hardening (one segment of slope 0 until then)
     std::vector<void*> owned;                           // every device allocation of dmalloc / upload (freed by fep_ctx_destroy)
     MatU matu{};                                        // homogeneous-material fast path (arrays not read)
@@ -212,8 +205,8 @@ struct fep_ctx {
     bool has_orphans = false;                           // nodes that belong to no element (their F entries are zeroed per step)
     // device, scratch rewritten by every step
     double *s_int = nullptr, *ds_int = nullptr;     // used when the caller does not ask for s / ds
-    uint2* blk_counts = nullptr;                        // stage A's per-workgroup branch counters on every route (n_count_blocks of them)
-    int n_count_blocks = 0;
+    uint2* blk_counts = nullptr;                        // per-workgroup branch counters of the stage that counts: room for the route's
+    int n_count_blocks = 0;                             // stage-A grid (n_count_blocks) and for the point kernel's
     fep_stage::DeviceStore hbuf{kCtxBufCount};          // persistent device buffers of the *_host entry points, by CtxBuf
     // host copies of the pattern
     std::vector<int32_t> indptr, indices;
@@ -779,8 +772,7 @@ static int launch_point(fep_ctx* c, hipStream_t st, const double* u, E0 e0, doub
 
 // GenNode route, stage B: node_lds_kernel
 static int launch_gn_node(fep_ctx* c, const GenNodeRoute& r, hipStream_t st, const double* ds, const double* s, double* k_data,
-                          double* f_out, unsigned long long* counts_d, bool* counted) {
-    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
+                          double* f_out, int n_counts, unsigned long long* counts_d) {
     const int n_wg = (int)grid_for(c->n_blk, r.tile);
     const unsigned grid = xcd_grid(n_wg);
     FEP_TRY(with_type(c->elem_type, [&](auto et) {
@@ -791,11 +783,14 @@ static int launch_gn_node(fep_ctx* c, const GenNodeRoute& r, hipStream_t st, con
             return launch_lds(node_lds_kernel<ET::NP, ET::NQ, TPB>, grid, TPB, r.lds, kLdsNodeLds, st, c->n_blk, c->n_e,
                               r.L, r.C, r.segptr, r.perm_l, r.meta, r.ncol, r.wg_elist, c->elem, c->xy,
                               c->dh1, c->dh2, c->wf, k_data ? ds : nullptr, f_out ? s : nullptr, k_data, f_out, n_wg,
-                              c->n_count_blocks, c->blk_counts, counts_d);
+                              n_counts, c->blk_counts, counts_d);
         });
     }));
-    *counted = counts_d != nullptr;
     return FEP_OK;
+}
+template <class N> static void name_point(const fep_ctx* c, N& o) { o.add("point_kernel<%d, %d>", c->n_p, c->n_q); }
+template <class N> static void name_gn_node(const fep_ctx* c, const GenNodeRoute& r, N& o) {
+    o.add("node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, r.tile == 256 ? 256 : 128);
 }
 #endif  // FEP_ABLATION
 
@@ -1199,7 +1194,7 @@ static int ctx_create_impl(fep_ctx*& c, fep_ctx** ctx_out, int device_id, int el
     FEP_TRY(fep_host::row_tiles(S, n_n, kBlock, tstart));
     FEP_TRY(choose_route(c, MeshIn{S, elements_h, coords_h, dhatp1_h, dhatp2_h, wf_h, env_now("FEP_VALIDATE_PLAN") != nullptr},
                          tstart));
-    FEP_TRY(dmalloc(c, &c->blk_counts, c->n_count_blocks));
+    FEP_TRY(dmalloc(c, &c->blk_counts, std::max<int64_t>(c->n_count_blocks, grid_for(c->n_int, kBlock))));
     FEP_TRY(launch_geometry(c, c->route == Route::P1Node ? c->p1.geo : nullptr));
     if (hipDeviceSynchronize() != hipSuccess) { g_last_hip = (int)hipGetLastError(); return FEP_EHIP; }
     *ctx_out = c;
@@ -1213,54 +1208,26 @@ extern "C" int fep_ctx_sizes(const fep_ctx* c, int64_t sizes[8]) {
     return FEP_OK;
 }
 
-// The kernels of a step, named as rocprofv3 prints them (bench.py labels its roofline with these and checks them against the
-// kernel names of the recorded counter passes)
-extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int64_t cap) {
-    if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
-    auto b = [](bool v) { return v ? "true" : "false"; };
-    const bool dp = c->model == FEP_MODEL_DP, patch = c->route == Route::Patch;
-    // `pt`: the model's point kernel; `el`: the element routes' kernel, for Drucker-Prager the whole step from U, for the other
-    // models the assembly from ds / s behind their point kernel (step_model)
-    char tmp[256], pt[64], el[192];
-    const char* tag = "";
-    FEP_TRY(with_model(c->model, [&](auto m) { tag = ModelKernels<decltype(m)::value>::tag; return FEP_OK; }));
-    if (c->elem_type == FEP_P1) std::snprintf(pt, sizeof pt, "p1_point_%skernel", tag);
-    else std::snprintf(pt, sizeof pt, "point_%skernel<%d, %d>", tag, c->n_p, c->n_q);
-    std::snprintf(el, sizeof el, "%s%selement_kernel<%d, %d, %s, %s, %s, %d, %d>", dp ? "" : pt, dp ? "" : " + ", c->n_p, c->n_q, b(dp),
-                  b(c->elem_form.geo), b(patch), patch ? c->patch.tpb : 256, patch ? c->patch.js : 1);
-    const P1NodeRoute& p1 = c->p1;
-    if (c->route == Route::P1Node && p1.v.lds && dp && which == 1 && p1.fused && p1.v.fused_mode >= 1) {
-        std::snprintf(tmp, sizeof tmp, "p1_fused_kernel<false, %d, %s, 1, 1, false, %s>", p1.v.tile, b(p1.fused_rng), b(p1.v.dma));
-    } else if (c->route == Route::P1Node && p1.v.lds) {
-        std::snprintf(tmp, sizeof tmp, "%s + p1_node_lds_kernel<%d, %s, 1, %s>", pt, p1.v.tile, b(p1.rng), b(p1.v.pk));
-    } else if (c->route == Route::P1Node) {
-        std::snprintf(tmp, sizeof tmp, "%s + p1_node_kernel", pt);
-#ifdef FEP_ABLATION
-    } else if (c->route == Route::GenNode) {            // (Drucker-Prager only: fep_ctx_set_model)
-        if (!dp) return FEP_ESTATE;
-        std::snprintf(tmp, sizeof tmp, "point_kernel<%d, %d> + node_lds_kernel<%d, %d, %d>", c->n_p, c->n_q, c->n_p, c->n_q, c->gen->tile);
-#endif
-    } else if (patch) {
-        std::snprintf(tmp, sizeof tmp, "%s + fixup_kernel", el);
-    } else {
-        std::snprintf(tmp, sizeof tmp, "%s + %s", el, c->coo.pkc ? "csr_reduce_pk_kernel" : "csr_reduce_kernel<4>");
-    }
-    std::snprintf(buf, (size_t)cap, "%s", tmp);
-    return FEP_OK;
+// What plan_step reads of a context
+static fep_plan::StepFacts facts_of(const fep_ctx* c) {
+    fep_plan::StepFacts f;
+    f.route = c->route;
+    f.dp = c->model == FEP_MODEL_DP;
+    f.lds = c->p1.v.lds; f.fused = c->p1.fused; f.fused_mode = c->p1.v.fused_mode; f.asm_from_nodes = c->p1.v.asm_from_nodes;
+    f.pkc = c->coo.pkc != nullptr;
+    return f;
 }
 
-// The two-kernel node routes pass ds / s from the point kernel to the assembly kernel through HBM: the internal ds (want_ds)
-// / s (want_s) scratch for callers that want K / F without them, allocated once (refused while `st` is being captured)
-static int point_scratch(fep_ctx* c, hipStream_t st, bool want_ds, bool want_s) {
-    want_ds = want_ds && !c->ds_int;
-    want_s = want_s && !c->s_int;
+// The only place that allocates the internal ds / s arrays (fep_plan::Scratch: a plan's `need`, or prealloc_scratch of the
+// context's facts), each once; refused while `st` is being captured
+static int ensure_scratch(fep_ctx* c, hipStream_t st, fep_plan::Scratch need) {
+    const bool want_ds = need.ds && !c->ds_int, want_s = need.s && !c->s_int;
     if (want_ds || want_s) FEP_TRY(scratch_alloc_allowed(st));
     if (want_ds) FEP_TRY(dmalloc(c, &c->ds_int, 9 * c->n_int));
     if (want_s) FEP_TRY(dmalloc(c, &c->s_int, 4 * c->n_int));
     return FEP_OK;
 }
 
-static bool element_route(const fep_ctx* c) { return c->route == Route::Patch || c->route == Route::Coo; }
 extern "C" int fep_ctx_geometry_host(fep_ctx* c, double* dphi1_h, double* dphi2_h, double* weight_h, double* det_h) {
     if (!c) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
@@ -1289,10 +1256,9 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     HIP_TRY(hipMemcpy(c->eta, eta_h, nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->c, c_h, nb, hipMemcpyHostToDevice));
     c->have_materials = true;
-    // the ds / s scratch of the two-kernel node routes must exist before the first fep_step_dev (which may run inside a
-    // stream capture).  P1 contexts with the one-kernel step only need it for accepting calls that also ask for K / F
-    // without ds / s (allocated on first use, outside any capture, by those rare callers).
-    if (!element_route(c) && !(c->route == Route::P1Node && c->p1.fused)) FEP_TRY(point_scratch(c, nullptr, true, true));
+    // the ds / s scratch of every step that does not allocate on first use must exist before the first fep_step_dev (which
+    // may run inside a stream capture)
+    FEP_TRY(ensure_scratch(c, nullptr, fep_plan::prealloc_scratch(facts_of(c))));
     // every parameter constant over the mesh (the reference's demos): the kernels skip the four arrays
     bool uni = fep_tune("FEP_NO_UNIFORM") == nullptr;
     for (int64_t k = 1; uni && k < c->n_int; ++k)
@@ -1301,23 +1267,23 @@ extern "C" int fep_ctx_set_materials_host(fep_ctx* c, const double* shear_h, con
     return FEP_OK;
 }
 
-// The models besides Drucker-Prager run as point kernel + the route's assembly: the ds / s scratch and the point kernel's
-// per-workgroup counters are allocated here, so that fep_step_dev never allocates on such a context.
+// The models besides Drucker-Prager run as point kernel + the route's assembly: their ds / s scratch is allocated here, so
+// that fep_step_dev never allocates on such a context.
 extern "C" int fep_ctx_set_model(fep_ctx* c, int model) {
     if (!c || with_model(model, [](auto) { return FEP_OK; }) != FEP_OK) return FEP_EINVAL;
     if (model != FEP_MODEL_DP) {
-#ifdef FEP_ABLATION
         if (c->route == Route::GenNode) return FEP_ESTATE;
-#endif
         FEP_TRY(fep_set_device(c->device));
-        if (!c->ds_int || !c->s_int || !c->point_blk) {
+        fep_plan::StepFacts facts = facts_of(c);
+        facts.dp = false;
+        const fep_plan::Scratch need = fep_plan::prealloc_scratch(facts);
+        if (!fep_plan::covers(fep_plan::Scratch{c->ds_int != nullptr, c->s_int != nullptr}, need)) {
             // refused while a capture is in progress (the query on the default stream fails during a capture on another)
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(nullptr, &cs) != hipSuccess) { (void)hipGetLastError(); return FEP_ESTATE; }
             if (cs != hipStreamCaptureStatusNone) return FEP_ESTATE;
         }
-        FEP_TRY(point_scratch(c, nullptr, true, true));
-        if (!c->point_blk) FEP_TRY(dmalloc(c, &c->point_blk, (int64_t)grid_for(c->n_int, kBlock)));
+        FEP_TRY(ensure_scratch(c, nullptr, need));
     }
     c->model = model;
     return FEP_OK;
@@ -1353,6 +1319,20 @@ extern "C" int fep_ctx_device_ptr(const fep_ctx* c, int which, void** ptr_d) {
     }
     return FEP_OK;
 }
+
+// The kernels of a plan as rocprofv3 prints them, joined by " + " (fep_ctx_kernel_names).  Each name_* function stands next
+// to the launcher that picks the kernel's template arguments and reads the same fields
+struct Names {
+    char s[512] = "";
+    size_t n = 0;
+    template <class... A> void add(const char* fmt, A... a) {
+        if (n) n += (size_t)std::snprintf(s + n, sizeof s - n, " + ");
+        n = std::min(n, sizeof s - 1);
+        n += (size_t)std::snprintf(s + n, sizeof s - n, fmt, a...);
+        n = std::min(n, sizeof s - 1);
+    }
+};
+static const char* tf(bool v) { return v ? "true" : "false"; }
 
 // ---------------------------------------------------------------------------------------
 // hot path
@@ -1415,32 +1395,40 @@ static int launch_element(fep_ctx* c, const ElemForm& ef, hipStream_t st, const 
     HIP_TRY(hipGetLastError());
     return FEP_OK;
 }
+static void name_element(const fep_ctx* c, const ElemForm& ef, bool from_u, Names& o) {
+    const bool patch = c->route == Route::Patch;
+    o.add("element_kernel<%d, %d, %s, %s, %s, %d, %d>", c->n_p, c->n_q, tf(from_u), tf(ef.geo), tf(patch), c->patch.tpb, c->patch.js);
+}
 
-// COO form, stage B: K_e blocks -> CSR values (the force gather rides in the reduce kernel's launch: the workgroups past
-// the last tile take 256 nodes each; so does the counter sum).  *f_due: F is still to be gathered (stage C)
-static int launch_reduce(fep_ctx* c, const CooRoute& r, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d,
-                         bool* counted, bool* f_due) {
-    *f_due = f_out && !k_data;
-    if (!k_data) return FEP_OK;
+// COO form, stage B (K wanted): K_e blocks -> CSR values (the force gather rides in the reduce kernel's launch: the workgroups
+// past the last tile take 256 nodes each; so does the sum of `n_counts` branch counters).  `form`: StageB::ReducePk or Reduce
+static int reduce_gathers(const CooRoute& r) {          // gathers in flight of the unpacked form: four, but for the ablation switch
+    const int g = r.v.csr_gathers;
+    return kAblationBuild && (g == 2 || g == 6 || g == 8) ? g : 4;
+}
+static int launch_reduce(fep_ctx* c, const CooRoute& r, hipStream_t st, StageB form, double* k_data, double* f_out, int n_counts,
+                         unsigned long long* counts_d) {
     ForceArgs fa{c->n_n, c->iptr, c->ilist, r.fe, f_out};
     const unsigned grid = (unsigned)r.n_tiles + (counts_d ? 1u : 0u) + (f_out ? grid_for(c->n_n, kBlock) : 0u);
     auto reduce = [&](auto gathers) {
         hipLaunchKernelGGL(csr_reduce_kernel<decltype(gathers)::value>, dim3(grid), dim3(kBlock), 0, st,
-                           r.n_tiles, r.tstart, r.segptr, r.perm, r.meta, r.Kc, k_data, c->n_count_blocks,
-                           c->blk_counts, counts_d, fa);
+                           r.n_tiles, r.tstart, r.segptr, r.perm, r.meta, r.Kc, k_data, n_counts, c->blk_counts, counts_d, fa);
     };
-    if (r.pkc)
+    if (form == StageB::ReducePk)
         hipLaunchKernelGGL(csr_reduce_pk_kernel, dim3(grid), dim3(kBlock), 0, st, r.n_tiles,
-                           r.tstart, r.pkc, r.perm, r.Kc, k_data, c->n_count_blocks, c->blk_counts, counts_d, fa);
+                           r.tstart, r.pkc, r.perm, r.Kc, k_data, n_counts, c->blk_counts, counts_d, fa);
 #ifdef FEP_ABLATION
-    else if (r.v.csr_gathers == 2) reduce(int_c<2>{});
-    else if (r.v.csr_gathers == 6) reduce(int_c<6>{});
-    else if (r.v.csr_gathers == 8) reduce(int_c<8>{});
+    else if (reduce_gathers(r) == 2) reduce(int_c<2>{});
+    else if (reduce_gathers(r) == 6) reduce(int_c<6>{});
+    else if (reduce_gathers(r) == 8) reduce(int_c<8>{});
 #endif
     else reduce(int_c<4>{});                             // (descriptor fields too wide for the packed form: four gathers in flight)
     HIP_TRY(hipGetLastError());
-    *counted = counts_d != nullptr;
     return FEP_OK;
+}
+static void name_reduce(const CooRoute& r, StageB form, Names& o) {
+    if (form == StageB::ReducePk) o.add("%s", "csr_reduce_pk_kernel");
+    else o.add("csr_reduce_kernel<%d>", reduce_gathers(r));
 }
 
 // COO form, stage C: the force gather when the reduce kernel did not take it
@@ -1451,30 +1439,30 @@ static int launch_force(fep_ctx* c, const CooRoute& r, hipStream_t st, double* f
     return FEP_OK;
 }
 
-// patch form, stage B: open blocks / open nodes from the patches' partials (+ the branch counters on the side)
-static int launch_fixup(fep_ctx* c, const PatchRoute& r, hipStream_t st, double* k_data, double* f_out, unsigned long long* counts_d, bool* counted) {
+// patch form, stage B: open blocks / open nodes from the patches' partials (+ the sum of `n_counts` branch counters on the
+// side).  A mesh whose patches leave nothing open gives an empty grid when no counters are summed: nothing is launched
+static int launch_fixup(fep_ctx* c, const PatchRoute& r, hipStream_t st, double* k_data, double* f_out, int n_counts,
+                        unsigned long long* counts_d) {
     const unsigned nb_k = k_data ? grid_for(r.n_open, kBlock) : 0u;
     const unsigned nb_f = f_out ? grid_for(r.n_fopen, kBlock) : 0u;
     const unsigned grid = nb_k + nb_f + (counts_d ? 1u : 0u);
     if (grid == 0) return FEP_OK;
     hipLaunchKernelGGL(fixup_kernel, dim3(grid), dim3(kBlock), 0, st, (int)nb_k, r.n_open, r.fix, r.fixT, r.n_fopen, r.ffix,
-                       r.plist, r.Pc, r.Pf, k_data, f_out, c->n_count_blocks, c->blk_counts, counts_d);
+                       r.plist, r.Pc, r.Pf, k_data, f_out, n_counts, c->blk_counts, counts_d);
     HIP_TRY(hipGetLastError());
-    *counted = counts_d != nullptr;
     return FEP_OK;
 }
 
-// P1 node route, stage B: the assembly kernel (reads ds / s, writes CSR values and nodal force; with `counts_d` it also
-// sums the point kernel's per-workgroup branch counters: *counted)
-static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, const double* ds, const double* s, double* k_data,
-                          double* f_out, unsigned long long* counts_d, bool* counted) {
-    if (!((k_data && ds) || (f_out && s))) return FEP_OK;
+// P1 node route, stage B (K or F wanted): the assembly kernel `form` names -- StageB::Tile, Direct or FromNodes -- reads ds / s,
+// writes CSR values and nodal force; with `counts_d` it also sums `n_counts` per-workgroup branch counters (not the direct kernel)
+static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, StageB form, const double* ds, const double* s,
+                          double* k_data, double* f_out, int n_counts, unsigned long long* counts_d) {
     if (!k_data) ds = nullptr;
     if (!f_out) s = nullptr;
     const int n_wg = r.n_tiles;
     const unsigned grid = xcd_grid(n_wg);
 #ifdef FEP_ABLATION
-    if (r.fused && r.v.asm_from_nodes) {
+    if (form == StageB::FromNodes) {
         // opt-in (FEP_P1_ASM=nodes): assembly-only form of the one-kernel step, geometry from the tile's LDS-staged nodes
         // instead of the 48-byte record per staged element (same values bit for bit; 25 % fewer bytes but one barrier
         // and the geometry arithmetic more: 72.0 against 66.4 us at 1 M elements, profiles/r02_ablation.md)
@@ -1486,21 +1474,19 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
                               r.wg_nlist, r.el_nodes, r.pk, r.trec, c->xy, c->p1tab,
                               (const double*)nullptr, make_e0(nullptr), (const double*)nullptr, c->shear, c->bulk, c->eta,
                               c->c, c->matu, (double*)nullptr, (double*)nullptr, (double*)nullptr, (uint8_t*)nullptr,
-                              k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, c->n_count_blocks, c->blk_counts, counts_d,
+                              k_data, f_out, n_wg, (unsigned long long*)nullptr, ds, s, n_counts, c->blk_counts, counts_d,
                               r.v.clk ? r.v.clk + 8 * (size_t)n_wg : (unsigned long long*)nullptr);
         }));
-        *counted = counts_d != nullptr;
         return FEP_OK;
     }
-    if (!r.v.lds) {
+    if (form == StageB::Direct) {
         hipLaunchKernelGGL(p1_node_kernel, dim3(grid_for(c->n_blk, kBlock)), dim3(kBlock), 0, st,
                            c->n_blk, c->n_e, r.segptr, r.perm2, r.meta, r.ncol, r.geo, ds, s, k_data, f_out);
         HIP_TRY(hipGetLastError());
         return FEP_OK;
     }
-#else
-    if (!r.v.lds) return FEP_ESTATE;
 #endif
+    if (form != StageB::Tile) return FEP_ESTATE;        // (the product runs the tile kernel alone)
     // operands + codes while gathering, then the same LDS holds the tile's output (4*TPB values + forces)
     const size_t lds = (size_t)p1_tile_lds(r.L, r.C, 0, r.v.tile, false, false).total;
     if (c->verbose) {
@@ -1522,7 +1508,7 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
                 return launch_lds(p1_node_lds_kernel<TPB, decltype(rng)::value, 1, decltype(pk)::value>, grid, TPB, lds,
                                   kLdsDefault, st, c->n_e, r.L, r.C, r.segptr, r.perm_l, r.meta, r.ncol,
                                   r.wg_elist, r.pk, r.trec, r.geo, ds, s, k_data, f_out, n_wg,
-                                  c->n_count_blocks, c->blk_counts, counts_d
+                                  n_counts, c->blk_counts, counts_d
 #ifdef FEP_ABLATION
                                   , r.v.clk
 #endif
@@ -1530,8 +1516,12 @@ static int launch_p1_node(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, cons
             });
         });
     }));
-    *counted = counts_d != nullptr;
     return FEP_OK;
+}
+static void name_p1_node(const P1NodeRoute& r, StageB form, Names& o) {
+    if (form == StageB::FromNodes) o.add("p1_fused_kernel<false, 256, %s, 1, 1, true, false>", tf(r.fused_rng));
+    else if (form == StageB::Direct) o.add("%s", "p1_node_kernel");
+    else o.add("p1_node_lds_kernel<%d, %s, 1, %s>", r.v.tile, tf(r.rng), tf(r.v.pk));
 }
 
 // P1, one kernel per step (non-accepting calls with K and/or F wanted): p1_fused_kernel, then the counter sum
@@ -1571,19 +1561,8 @@ static int launch_p1_fused(fep_ctx* c, const P1NodeRoute& r, hipStream_t st, con
     }
     return FEP_OK;
 }
-
-// Stage B of every route but the one-kernel step: the route's assembly kernel (the node routes read ds / s, the element
-// routes stage A's partials / K_e blocks).  *counted: it also summed the branch counters; *f_due: F is still to be
-// gathered (stage C, COO form only)
-static int launch_assembly(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                           unsigned long long* counts_d, bool* counted, bool* f_due) {
-    *counted = *f_due = false;
-    if (c->route == Route::P1Node) return launch_p1_node(c, c->p1, st, ds, s, k_data, f_out, counts_d, counted);
-#ifdef FEP_ABLATION
-    if (c->route == Route::GenNode) return launch_gn_node(c, *c->gen, st, ds, s, k_data, f_out, counts_d, counted);
-#endif
-    if (c->route == Route::Patch) return launch_fixup(c, c->patch, st, k_data, f_out, counts_d, counted);
-    return launch_reduce(c, c->coo, st, k_data, f_out, counts_d, counted, f_due);
+static void name_p1_fused(const P1NodeRoute& r, bool full, Names& o) {
+    o.add("p1_fused_kernel<%s, %d, %s, 1, 1, false, %s>", tf(full), r.v.tile, tf(r.fused_rng), tf(r.v.dma));
 }
 
 // Stage A of a staged step, and of Drucker-Prager's two-kernel P1 step: the point kernel of the context's model (ModelKernels),
@@ -1611,116 +1590,121 @@ static int launch_point_stage(fep_ctx* c, hipStream_t st, const double* u, E0 e0
     });
 }
 
-// The assembly from ds / s that fep_assemble_dev and a staged step share: the element routes' element_kernel in its assembly-only
-// form, the route's assembly kernel, mark 2, the COO form's force gather, mark 3.  `own_call` (fep_assemble_dev): the element
-// kernel is stage A, launched whatever is wanted, with mark 1 behind it; in a staged step both lie in front of this, behind stage A
-static int launch_assembly_stages(fep_ctx* c, hipStream_t st, const double* ds, const double* s, double* k_data, double* f_out,
-                                  bool own_call) {
-    bool counted = false, f_due = false;
-    if (element_route(c) && (own_call || k_data || f_out))
-        FEP_TRY(launch_element<false>(c, c->elem_form, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s),
-                                      const_cast<double*>(ds), nullptr, nullptr, k_data, f_out));
-    if (own_call) FEP_TRY(prof_mark(c, st));
-    FEP_TRY(launch_assembly(c, st, ds, s, k_data, f_out, nullptr, &counted, &f_due));
-    FEP_TRY(prof_mark(c, st));
-    if (f_due) FEP_TRY(launch_force(c, c->coo, st, f_out));
-    FEP_TRY(prof_mark(c, st));
-    return FEP_OK;
+static int name_point_stage(const fep_ctx* c, Names& o) {       // (without a field: the steps fep_ctx_kernel_names describes)
+    return with_model(c->model, [&](auto m) {
+        const char* tag = ModelKernels<decltype(m)::value>::tag;
+        if (c->elem_type == FEP_P1) o.add("p1_point_%skernel", tag);
+        else o.add("point_%skernel<%d, %d>", tag, c->n_p, c->n_q);
+        return FEP_OK;
+    });
 }
 
-// A staged step: every model but Drucker-Prager, and (`field_d`, fep_step_field_*) every model with a field.  Stage A is the model's
-// point kernel (geometry, strain, return map; s / ds to the caller's arrays or the context's scratch), stages B and C exactly what
-// fep_assemble_dev launches for the route.
-static int step_model(fep_ctx* c, hipStream_t st, const double* u_d, E0 e0, double* ep_prev_d, int accept, double* e_out_d,
-                   double* s_d, double* ds_d, uint8_t* ind_p_d, double* k_data_d, double* f_out_d, unsigned long long* cnt,
-                   const double* field_d = nullptr, double scale = 0.0) {
-    if (!c->ds_int || !c->s_int || !c->point_blk) return FEP_ESTATE;
-    if (k_data_d && !ds_d) ds_d = c->ds_int;
-    if (f_out_d && !s_d) s_d = c->s_int;
-    FEP_TRY(begin_call(c, st, f_out_d));
-    FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, cnt ? c->point_blk : nullptr,
-                               field_d, scale));
-    FEP_TRY(prof_mark(c, st));
-    FEP_TRY(launch_assembly_stages(c, st, ds_d, s_d, k_data_d, f_out_d, false));
-    if (cnt) {
-        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, (int)grid_for(c->n_int, kBlock), c->point_blk, cnt);
-        HIP_TRY(hipGetLastError());
-    }
-    return FEP_OK;
-}
+// What a call hands to run_step.  s / ds: the caller's arrays (fep_assemble_dev: its inputs), NULL where it has none
+struct StepArgs {
+    const double* u; E0 e0; double* ep; int accept;
+    double *e, *s, *ds; uint8_t* indp;
+    double *K, *F; unsigned long long* cnt;
+    const double* field; double scale;
+};
 
-// fep_step_dev and fep_assemble_dev record four events per call (fep_ctx_profile_end: three intervals):
-//   mark 0, stage A (point / element kernel), mark 1, stage B (assembly), mark 2, stage C (COO: force gather), mark 3
-// then the branch-counter sum if no kernel took it.
-extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const double* e0_h,
-                            double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d,
-                            uint8_t* ind_p_d, double* k_data_d, double* f_out_d, int64_t* counts_d) {
-    if (!c || !u_d) return FEP_EINVAL;
-    if (!fep_aligned16(u_d) || !fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
-    if (!c->have_materials) return FEP_ESTATE;
-    FEP_TRY(fep_set_device(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* cnt = (unsigned long long*)counts_d;
-    uint2* blk = cnt ? c->blk_counts : nullptr;
-    const E0 e0 = make_e0(e0_h);
-    if (c->model != FEP_MODEL_DP)
-        return step_model(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt);
-    const bool point_outputs = e_out_d || s_d || ds_d || ind_p_d;
-    const bool fused = c->route == Route::P1Node && c->p1.fused && !accept && (k_data_d || f_out_d) &&
-                       c->p1.v.fused_mode > (point_outputs ? 1 : 0);
-    if (!element_route(c) && !fused) {                  // the assembly kernel reads ds / s from HBM
-        FEP_TRY(point_scratch(c, st, k_data_d && !ds_d, f_out_d && !s_d));
-        if (k_data_d && !ds_d) ds_d = c->ds_int;
-        if (f_out_d && !s_d) s_d = c->s_int;
-    }
+// The one launch sequence of fep_step_dev, fep_step_field_dev and fep_assemble_dev, which record four events per call
+// (fep_ctx_profile_end: three intervals):
+//   begin_call (mark 0), stage A, mark 1, the assembly-only element kernel of a staged step, stage B (with counts_finalize_kernel
+//   behind the one-kernel step), mark 2, stage C (COO form: the force gather), mark 3, counts_reduce_kernel if no kernel took the sum
+static int run_step(fep_ctx* c, hipStream_t st, const StepPlan& p, const StepArgs& a) {
+    using fep_plan::CountGrid;
+    using fep_plan::CountSum;
+    double* ds = a.ds ? a.ds : p.use.ds ? c->ds_int : nullptr;
+    double* s = a.s ? a.s : p.use.s ? c->s_int : nullptr;
+    // the per-workgroup counters the summing launch reads: those of the stage that counted (the one-kernel step counts in its slots)
+    const int n_counts = p.grid == CountGrid::RouteStageA ? c->n_count_blocks : p.grid == CountGrid::PointKernel ? (int)grid_for(c->n_int, kBlock) : 0;
+    uint2* blk = n_counts ? c->blk_counts : nullptr;
+    unsigned long long* cnt_b = p.sum == CountSum::StageB || p.sum == CountSum::Finalize ? a.cnt : nullptr;
+    auto element_from_u = [&] { return launch_element<true>(c, c->elem_form, st, a.u, a.e0, a.ep, a.accept, a.e, s, ds, a.indp, blk, a.K, a.F); };
+    auto element_from_ds = [&] { return launch_element<false>(c, c->elem_form, st, nullptr, make_e0(nullptr), nullptr, 0, nullptr, s, ds, nullptr, nullptr, a.K, a.F); };
     hipStream_t ms = st;                                // stream of marks 1-3 and of stages B and C
 #ifdef FEP_ABLATION
     // FEP_FIX_SIDE=1 — an UPPER BOUND, not a route: fixup_kernel on a side stream, NOT ordered behind this call's element kernel (it
     // adds whatever partials the call before left; K's open blocks are stale), joined at the end: what a perfectly overlapped
     // fix-up could save
-    const bool fix_side = c->route == Route::Patch && fep_tune("FEP_FIX_SIDE");
+    const bool fix_side = p.a == StageA::ElementFromU && c->route == Route::Patch && fep_tune("FEP_FIX_SIDE");
     static hipStream_t side = nullptr;
     static hipEvent_t ev_a = nullptr, ev_b = nullptr;
     if (fix_side && !side) { HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming)); }
+#else
+    constexpr bool fix_side = false;
 #endif
-    bool counted = false, f_due = false;
-    FEP_TRY(begin_call(c, st, f_out_d));
-    if (c->route == Route::P1Node) {
-        if (!fused)                                     // (the one-kernel step is all stage B)
-            FEP_TRY(launch_point_stage(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, nullptr, 0.0));
+    FEP_TRY(begin_call(c, st, a.F));
+    switch (p.a) {
+        case StageA::None: break;
+        case StageA::Point: FEP_TRY(launch_point_stage(c, st, a.u, a.e0, a.ep, a.accept, a.e, s, ds, a.indp, blk, a.field, a.scale)); break;
+        case StageA::ElementFromU: if (!fix_side) FEP_TRY(element_from_u()); break;
+        case StageA::ElementFromDs: FEP_TRY(element_from_ds()); break;
 #ifdef FEP_ABLATION
-    } else if (c->route == Route::GenNode) {
-        FEP_TRY(launch_point(c, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk));
-    } else if (fix_side) {
+        case StageA::GenPoint: FEP_TRY(launch_point(c, st, a.u, a.e0, a.ep, a.accept, a.e, s, ds, a.indp, blk)); break;
+#endif
+        default: return FEP_ESTATE;
+    }
+#ifdef FEP_ABLATION
+    if (fix_side) {
         HIP_TRY(hipEventRecord(ev_a, st));
         HIP_TRY(hipStreamWaitEvent(side, ev_a, 0));
         ms = side;
+    }
 #endif
-    } else {
-        FEP_TRY(launch_element<true>(c, c->elem_form, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
+    FEP_TRY(prof_mark(c, ms));
+    if (p.elem_assembly) FEP_TRY(element_from_ds());
+    switch (p.b) {
+        case StageB::None: break;
+        case StageB::OneKernel: FEP_TRY(launch_p1_fused(c, c->p1, st, a.u, a.e0, a.ep, a.e, a.s, a.ds, a.indp, a.K, a.F, cnt_b)); break;
+        case StageB::Tile: case StageB::Direct: case StageB::FromNodes:
+            FEP_TRY(launch_p1_node(c, c->p1, ms, p.b, ds, s, a.K, a.F, n_counts, cnt_b)); break;
+        case StageB::Fixup: FEP_TRY(launch_fixup(c, c->patch, ms, a.K, a.F, n_counts, cnt_b)); break;
+        case StageB::ReducePk: case StageB::Reduce: FEP_TRY(launch_reduce(c, c->coo, ms, p.b, a.K, a.F, n_counts, cnt_b)); break;
+#ifdef FEP_ABLATION
+        case StageB::GenNode: FEP_TRY(launch_gn_node(c, *c->gen, ms, ds, s, a.K, a.F, n_counts, cnt_b)); break;
+#endif
+        default: return FEP_ESTATE;
     }
     FEP_TRY(prof_mark(c, ms));
-    if (fused) {
-        FEP_TRY(launch_p1_fused(c, c->p1, st, u_d, e0, ep_prev_d, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, cnt));
-        counted = true;
-    } else {
-        FEP_TRY(launch_assembly(c, ms, ds_d, s_d, k_data_d, f_out_d, cnt, &counted, &f_due));
-    }
-    FEP_TRY(prof_mark(c, ms));
-    if (f_due) FEP_TRY(launch_force(c, c->coo, ms, f_out_d));
+    if (p.force_gather) FEP_TRY(launch_force(c, c->coo, ms, a.F));
     FEP_TRY(prof_mark(c, ms));
 #ifdef FEP_ABLATION
     if (fix_side) {
         HIP_TRY(hipEventRecord(ev_b, side));
-        FEP_TRY(launch_element<true>(c, c->elem_form, st, u_d, e0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, blk, k_data_d, f_out_d));
+        FEP_TRY(element_from_u());
         HIP_TRY(hipStreamWaitEvent(st, ev_b, 0));
     }
 #endif
-    if (cnt && !counted) {
-        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, c->n_count_blocks, c->blk_counts, cnt);
+    if (p.sum == CountSum::Reduce) {
+        hipLaunchKernelGGL(counts_reduce_kernel, dim3(1), dim3(1024), 0, st, n_counts, c->blk_counts, a.cnt);
         HIP_TRY(hipGetLastError());
     }
     return FEP_OK;
+}
+
+// One step: validate, plan, ensure the plan's scratch, run.  `field_d`: fep_step_field_dev
+static int step_dev_impl(fep_ctx* c, void* stream, const double* u_d, const double* e0_h, const double* field_d, double scale,
+                         double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d, uint8_t* ind_p_d,
+                         double* k_data_d, double* f_out_d, int64_t* counts_d) {
+    if (!fep_aligned16(u_d) || !fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
+    if (!c->have_materials) return FEP_ESTATE;
+    if (field_d && c->route == Route::GenNode) return FEP_ESTATE;
+    FEP_TRY(fep_set_device(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const fep_plan::StepWants w{accept != 0, e_out_d != nullptr, s_d != nullptr, ds_d != nullptr, ind_p_d != nullptr,
+                                k_data_d != nullptr, f_out_d != nullptr, counts_d != nullptr, field_d != nullptr, false};
+    const StepPlan plan = fep_plan::plan_step(facts_of(c), w);
+    FEP_TRY(ensure_scratch(c, st, plan.need));
+    return run_step(c, st, plan, StepArgs{u_d, make_e0(e0_h), ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d,
+                                          (unsigned long long*)counts_d, field_d, scale});
+}
+
+extern "C" int fep_step_dev(fep_ctx* c, void* stream, const double* u_d, const double* e0_h,
+                            double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d,
+                            uint8_t* ind_p_d, double* k_data_d, double* f_out_d, int64_t* counts_d) {
+    if (!c || !u_d) return FEP_EINVAL;
+    return step_dev_impl(c, stream, u_d, e0_h, nullptr, 0.0, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d, counts_d);
 }
 
 extern "C" int fep_step_field_dev(fep_ctx* c, void* stream, const double* u_d, const double* e0_h,
@@ -1728,21 +1712,8 @@ extern "C" int fep_step_field_dev(fep_ctx* c, void* stream, const double* u_d, c
                                   double* ep_prev_d, int accept, double* e_out_d, double* s_d, double* ds_d,
                                   uint8_t* ind_p_d, double* k_data_d, double* f_out_d, int64_t* counts_d) {
     if (!c || !u_d || !e0_field_d) return FEP_EINVAL;
-    if (!fep_aligned16(u_d) || !fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
-    if (!c->have_materials) return FEP_ESTATE;
-#ifdef FEP_ABLATION
-    if (c->route == Route::GenNode) return FEP_ESTATE;
-#endif
-    FEP_TRY(fep_set_device(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    // (a von Mises / Mohr-Coulomb context holds all three since fep_ctx_set_model; Drucker-Prager gets them here, once)
-    FEP_TRY(point_scratch(c, st, true, true));
-    if (!c->point_blk) {
-        FEP_TRY(scratch_alloc_allowed(st));
-        FEP_TRY(dmalloc(c, &c->point_blk, (int64_t)grid_for(c->n_int, kBlock)));
-    }
-    return step_model(c, st, u_d, make_e0(e0_h), ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d, f_out_d,
-                      (unsigned long long*)counts_d, e0_field_d, e0_scale);
+    return step_dev_impl(c, stream, u_d, e0_h, e0_field_d, e0_scale, ep_prev_d, accept, e_out_d, s_d, ds_d, ind_p_d, k_data_d,
+                         f_out_d, counts_d);
 }
 
 extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, const double* s_d,
@@ -1752,8 +1723,12 @@ extern "C" int fep_assemble_dev(fep_ctx* c, void* stream, const double* ds_d, co
     if (!fep_aligned16(f_out_d) || !fep_aligned16(k_data_d)) return FEP_EINVAL;
     FEP_TRY(fep_set_device(c->device));
     hipStream_t st = (hipStream_t)stream;
-    FEP_TRY(begin_call(c, st, f_out_d));
-    return launch_assembly_stages(c, st, ds_d, s_d, k_data_d, f_out_d, true);
+    fep_plan::StepWants w;
+    w.K = k_data_d != nullptr; w.F = f_out_d != nullptr; w.assemble = true;
+    const StepPlan plan = fep_plan::plan_step(facts_of(c), w);
+    FEP_TRY(ensure_scratch(c, st, plan.need));
+    return run_step(c, st, plan, StepArgs{nullptr, make_e0(nullptr), nullptr, 0, nullptr, const_cast<double*>(s_d),
+                                          const_cast<double*>(ds_d), nullptr, k_data_d, f_out_d, nullptr, nullptr, 0.0});
 }
 
 static int step_host_impl(fep_ctx* c, bool u_planar, const double* u_h, const double* e0_h, double* ep_prev_h, int accept,
@@ -2086,6 +2061,43 @@ extern "C" int fep_load_traction_host(int device_id, int64_t n_n, int64_t n_e_s,
                                       const double* dhatp1_s_h, const double* wf_s_h, const double* t_int_h, double* f_out_h) {
     FEP_GUARD(load_traction_impl(device_id, nullptr, n_n, n_e_s, n_p_s, n_q_s, edges_h, xy_h, true, hatp_s_h, dhatp1_s_h, wf_s_h,
                                  t_int_h, true, f_out_h, true))
+}
+
+// The kernels of a step, named as rocprofv3 prints them (bench.py labels its roofline with these and checks them against the
+// kernel names of the recorded counter passes): the stages of the plan of a non-accepting step that wants every output
+// (which = 0) or K and F alone (1), without the counter sum
+extern "C" int fep_ctx_kernel_names(const fep_ctx* c, int which, char* buf, int64_t cap) {
+    if (!c || !buf || cap <= 0 || (which != 0 && which != 1)) return FEP_EINVAL;
+    fep_plan::StepWants w;
+    w.K = w.F = true;
+    w.e = w.s = w.ds = w.ind_p = which == 0;
+    const StepPlan p = fep_plan::plan_step(facts_of(c), w);
+    Names o;
+    switch (p.a) {
+        case StageA::None: break;
+        case StageA::Point: FEP_TRY(name_point_stage(c, o)); break;
+        case StageA::ElementFromU: name_element(c, c->elem_form, true, o); break;
+        case StageA::ElementFromDs: name_element(c, c->elem_form, false, o); break;
+#ifdef FEP_ABLATION
+        case StageA::GenPoint: name_point(c, o); break;
+#endif
+        default: return FEP_ESTATE;
+    }
+    if (p.elem_assembly) name_element(c, c->elem_form, false, o);
+    switch (p.b) {
+        case StageB::None: break;
+        case StageB::OneKernel: name_p1_fused(c->p1, which == 0, o); break;
+        case StageB::Tile: case StageB::Direct: case StageB::FromNodes: name_p1_node(c->p1, p.b, o); break;
+        case StageB::Fixup: o.add("%s", "fixup_kernel"); break;
+        case StageB::ReducePk: case StageB::Reduce: name_reduce(c->coo, p.b, o); break;
+#ifdef FEP_ABLATION
+        case StageB::GenNode: name_gn_node(c, *c->gen, o); break;
+#endif
+        default: return FEP_ESTATE;
+    }
+    if (p.force_gather) o.add("%s", "force_reduce_kernel");
+    std::snprintf(buf, (size_t)cap, "%s", o.s);
+    return FEP_OK;
 }
 
 extern "C" int fep_ctx_profile_begin(fep_ctx* c) {

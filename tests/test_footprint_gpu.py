@@ -3,7 +3,7 @@ What every launch form WRITES: all of its outputs, nothing else, and the same bi
 
 The per-entry tests compare the full-output step with float64 references; every other form (the K,F-only step, on P1
 p1_fused_kernel, the kernel a Newton iterate runs; the K-only and F-only steps; the accepting step; assemble(ds, s); the same
-forms of step_model and of the field step) is pinned to that step bitwise.  This module runs the forms through step_dev /
+forms of the staged steps of the other models and of the field step) is pinned to that step bitwise.  This module runs the forms through step_dev /
 assemble_dev on caller memory with known contents (tests/footprint.py): a fresh arena of poison per call, inputs copied in,
 the call on torch's current stream, a synchronise, then
   1. every guard band (64 KiB before and after every array) is intact;

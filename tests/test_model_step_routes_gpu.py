@@ -1,6 +1,6 @@
 """
 The step of a von Mises, of a Mohr-Coulomb and of a 'vmi' context (von Mises with isotropic hardening on a piecewise-linear
-curve; fep_api.hip: step_model, whose one launcher appends the curve where the model's ModelKernels says it has one) on every
+curve; fep_api.hip: the staged plan of run_step, whose one point-stage launcher appends the curve where the model's ModelKernels says it has one) on every
 route, against the element-by-element float64 reference (tests/elem_ref.py) and the models' restatements (tests/vm_ref.py,
 tests/mc_ref.py, tests/vmi_ref.py), entry by entry.
 

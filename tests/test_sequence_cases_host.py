@@ -194,7 +194,7 @@ class StaleUniformFlag(SwitchContext):
 
 
 class CountersNotReset(SwitchContext):
-    """b. blk_counts / point_blk / slot_counts: the branch counters are not zeroed between steps, n_smooth accumulates."""
+    """b. blk_counts / slot_counts: the branch counters are not zeroed between steps, n_smooth accumulates."""
     def _after_step(self, r, want):
         self._acc = getattr(self, '_acc', 0) + int(r['n_smooth'])
         r['n_smooth'] = self._acc

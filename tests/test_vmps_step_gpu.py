@@ -1,4 +1,4 @@
-"""The step of a plane-stress von Mises context (fep_api.hip: step_model with p1_point_vmps_kernel / point_vmps_kernel<NP, NQ>
+"""The step of a plane-stress von Mises context (fep_api.hip: the staged plan of run_step with p1_point_vmps_kernel / point_vmps_kernel<NP, NQ>
 and the context's own assembly) on every element type and route, the closed forms through the whole stack, and the cyclic
 driver with `plane_stress=True`.
 

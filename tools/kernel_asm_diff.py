@@ -47,6 +47,8 @@ def kernels(asm):
             cur = None
             continue
         s = re.sub(r'\s*;.*$', '', s)                   # comments (they carry source positions and symbol offsets)
+        s = re.sub(r'\.L([A-Za-z]+)\d+_(\d+)', r'.L\1_\2', s)     # local labels carry the function's number in its unit (.LBB78_2):
+                                                        # the order in which the host code instantiates the kernels, not code
         if s:
             out[cur].append(s)
     return {k: '\n'.join(v) for k, v in out.items()}
